@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """RWR seeds/s + achieved HBM GB/s on the synthetic bipartite like-graphs of BASELINE.md.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS
 a rank; typed as plain `python bench.py --gpus N` it starts the N ranks itself (child processes through
@@ -18,11 +18,16 @@ The line also carries
   roofline      -- dominant kernel (the batched SpMM), DENSE launches only (every row walked, every entry's source row
                    gathered; the first iterations of a run skip the rows that are still exactly zero and are NOT credited
                    with the full byte count): ALGORITHMIC bytes (SURVEY.md 8d formula) / their durations measured with HIP
-                   events on the library's own stream inside the timed region; roofline.k1_spmv is the same for the
-                   single-seed SpMV (the kernel BASELINE.json's 70 % target names), measured after the timed region;
+                   events on the library's own stream inside the timed region.
+With --full (rank 0 at N = 1) it also measures, after the timed region,
+  single_seed_call, roofline.k1_spmv -- the single-seed call and its SpMV (the kernel BASELINE.json's 70 % target names);
   cpu_baseline  -- the oracle's C restatement ("port": the reference is C# and cannot be
                    built here) timed on this host's cores on a bounded seed sample, plus a
-                   bitwise comparison of that sample with the GPU result.
+                   bitwise comparison of that sample with the GPU result (--no-cpu-baseline leaves it out).
+--config C1 is a workload of its own (see bench_c1) and always runs its side passes.
+
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float64; see dump_outputs), so that two
+builds can be compared output for output: with the same arguments the inputs are the same in every run.
 """
 from __future__ import annotations
 
@@ -95,6 +100,11 @@ def main():
     ap.add_argument("--mode", default="exact", choices=["exact"])
     ap.add_argument("--tile-seeds", type=int, default=0)
     ap.add_argument("--tile-group", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the single-seed call (roofline.k1_spmv) and "
+                         "the CPU baseline, after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seeds", type=int, default=0, help="seeds in the CPU sample (0 = one per thread)")
     ap.add_argument("--cpu-threads", type=int, default=16, help="host threads of the CPU baseline")
@@ -105,6 +115,8 @@ def main():
                     help="seeds: graph replicated, seeds sharded, no collective (config 4, the default);  rows: transition "
                          "matrix partitioned by source rows, all-reduce of the rank matrix per iteration (config 5)")
     args = ap.parse_args()
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dump-outputs: a dry run computes nothing")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args.gpus))
@@ -172,6 +184,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     st = G.stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, ids=ids, scores=sc, counts=cnt)
 
     if rank == 0:
         seeds_total = K * world * args.steps
@@ -238,7 +252,7 @@ def main():
                                          "note": "traffic = PMC bytes per dense launch from the committed profile (fingerprint-guarded), "
                                                  "not measured in this run; duration = this run's HIP events"}
         single = None
-        if world == 1:
+        if world == 1 and args.full:
             # the unmodified harness's call shape (Experiment.cs:109): ONE seed per call.  Outside the timed region;
             # reported beside the batch figure because it is what a drop-in user of the C# host sees per call -- and its
             # SpMV is the kernel BASELINE.json's 70 % target names (roofline.k1_spmv).
@@ -259,7 +273,7 @@ def main():
                 "kernel": "k_spmv (single seed, dense steps)", "bound": "hbm", "achieved": k1_ach, "peak": HBM_PEAK_GBPS,
                 "unit": "GB/s", "frac": k1_ach / HBM_PEAK_GBPS, "launches": k1_launches,
                 "avg_launch_ms": k1_ms / max(k1_launches, 1), "algorithmic_bytes_per_launch": k1_bytes}
-        if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(flat, seeds, ids, sc, cnt, args, single_seed=(s0, single))
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -369,6 +383,9 @@ def bench_c1(args):
     res = [None] * len(graphs)
     elapsed = timed(gpu_pass_batched, res)
     value = len(graphs) * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, 0, 1, hits=[r[0] for r in res], precision_sums=[r[1] for r in res],
+                     list_lengths=[r[2] for r in res])
     out = {"metric": "ego-network evaluations/s (Graph.buildGraph + Recommendation(0, 0.15f, T) + Hits/AP per graph)", "value": value,
            "unit": "graphs/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -437,6 +454,28 @@ def bench_c1(args):
                                "hits_and_precision_sums_bitwise_equal": bool(same),
                                "result_dat_lines_identical": lines(res) == lines(cres), "result_dat_lines": len(lines(res))}
     print(json.dumps(out), flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d: str, rank: int, world: int, **arrays) -> None:
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (node ids and counts are exact in it), with a .rank<r>
+    suffix when N > 1 (each rank has its own shard of the seeds).  The arrays share their first axis (one row per seed
+    or graph); beyond DUMP_MAX_BYTES in all, a fixed seeded sample of rows is written instead, its row numbers as
+    DIR/sample_rows.npy."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    rows = len(next(iter(arrays.values())))
+    total = sum(a.nbytes for a in arrays.values())
+    sfx = f".rank{rank}" if world > 1 else ""
+    os.makedirs(d, exist_ok=True)
+    if total > DUMP_MAX_BYTES:
+        keep = max(1, DUMP_MAX_BYTES * rows // (total + 8 * rows))
+        pick = np.sort(np.random.default_rng(20261015).choice(rows, size=keep, replace=False))
+        arrays = {k: a[pick] for k, a in arrays.items()}
+        arrays["sample_rows"] = pick.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, f"{k}{sfx}.npy"), a)
 
 
 def matrix_bytes(n: int, nnz: int, uniform_path: bool) -> int:
@@ -509,6 +548,8 @@ def bench_row_partitioned(args, rank, local_rank, world, flat, U, I, g, n, nnz):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:             # every rank returns the whole batch
+        dump_outputs(args.dump_outputs, 0, 1, ids=ids, scores=sc, counts=cnt)
     if rank == 0:
         G = 1
         while G < K:

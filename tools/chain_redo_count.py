@@ -1,7 +1,7 @@
 """Blocks the seed-row carry redoes per single-seed call (stats.chain_redo_blocks); with the experiments build and
 RWR_X_CARRY_DBG=1 the carry kernel prints where its time goes."""
 import sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import recommendersystems_amd._lib as _lib
 if os.environ.get("RWR_TOOLS_EXP_LIB"):

@@ -19,12 +19,12 @@ done
 cd $root
 out=$root/gpurun_out/r03_lines
 mkdir -p $out
-python3 bench.py > $out/C4.json 2> $out/C4.log || echo "C4 line failed"
+python3 bench.py --full > $out/C4.json 2> $out/C4.log || echo "C4 line failed"
 echo "done C4 line"
-for cfg in C2 C3; do python3 bench.py --config $cfg --steps 3 --warmup 1 > $out/$cfg.json 2> $out/$cfg.log || echo "$cfg failed"; echo "done $cfg line"; done
+for cfg in C2 C3; do python3 bench.py --config $cfg --steps 3 --warmup 1 --full > $out/$cfg.json 2> $out/$cfg.log || echo "$cfg failed"; echo "done $cfg line"; done
 python3 bench.py --config C1 --steps 3 --warmup 1 > $out/C1.json 2> $out/C1.log || echo "C1 failed"
 echo "done C1 line"
-python3 bench.py --config C5 --steps 2 --warmup 1 --cpu-threads 4 --cpu-seeds 2 > $out/C5.json 2> $out/C5.log || echo "C5 failed"
+python3 bench.py --config C5 --steps 2 --warmup 1 --full --cpu-threads 4 --cpu-seeds 2 > $out/C5.json 2> $out/C5.log || echo "C5 failed"
 echo "done C5 line"
 python3 bench.py --config C5 --partition rows --steps 3 --warmup 1 --no-cpu-baseline > $out/C5_rows.json 2> $out/C5_rows.log || echo "C5 rows failed"
 echo "done C5 rows line"

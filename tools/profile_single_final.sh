@@ -14,5 +14,6 @@ for cfg in C3 C2; do
   echo "done single $cfg"
 done
 cd $root
-mkdir -p gpurun_out/final3
-for cfg in C2 C3; do python3 bench.py --config $cfg --steps 3 --warmup 1 > gpurun_out/final3/$cfg.json 2> gpurun_out/final3/$cfg.log || echo "$cfg failed"; echo "done $cfg line"; done
+lines=$(dirname "$out")/final3             # beside the profile directories above
+mkdir -p $lines
+for cfg in C2 C3; do python3 bench.py --config $cfg --steps 3 --warmup 1 --full > $lines/$cfg.json 2> $lines/$cfg.log || echo "$cfg failed"; echo "done $cfg line"; done
