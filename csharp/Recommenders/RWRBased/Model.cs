@@ -1,6 +1,8 @@
 // Drop-in replacement of Recommenders/RWRBased/Model.cs: same public fields and methods; run*() execute on
 // the GPU through rwr_model_run and leave the result in `rank` exactly as the reference does; deliverRanks() is one
 // propagation on the GPU (rwr_model_deliver), updateRanks()/checkConvergence() are the reference's array loops.
+// A host-edited `restart` (a public field of the reference, Model.cs:12) takes rwr_model_run_restart /
+// rwr_model_deliver_restart instead.
 namespace Recommenders.RWRBased {
     public class Model {
         public Graph graph;
@@ -34,7 +36,15 @@ namespace Recommenders.RWRBased {
         }
 
         void Run(int mode, double value) {
-            CheckRestart();
+            if (CustomRestart()) {
+                // the whole loop on the device from the current rank, with the edited restart vector
+                for (int i = 0; i < nNodes; i++)
+                    if (nextRank[i] != 0)
+                        throw new System.InvalidOperationException("run() on a non-zero nextRank: call updateRanks() first");
+                long it;
+                Native.Check(Native.rwr_model_run_restart(graph.handle, restart, rank, dampingFactor, mode, value, rank, out it));
+                return;
+            }
             if (CtorState()) {
                 long iters;
                 Native.Check(Native.rwr_model_run(graph.handle, seed, dampingFactor, mode, value, rank, out iters));
@@ -57,23 +67,28 @@ namespace Recommenders.RWRBased {
         public void run(double threshold) { Run(1, threshold); }
         public void run(int nIterations) { Run(0, nIterations); }
 
-        // `restart` is a public field of the reference, but only the constructors' restart vectors have a device kernel
-        // (one-hot at the seed / uniform 1/n): a host-edited vector is refused, as the Python mirror does
-        void CheckRestart() {
+        // `restart` is a public field of the reference: true when the host has edited it (then the *_restart entry points
+        // run; the constructors' one-hot / uniform vectors keep the seed / global paths), as the Python mirror decides
+        bool CustomRestart() {
+            if (restart == null || restart.Length != nNodes)
+                throw new System.ArgumentException("Model.restart must hold nNodes values");
             for (int i = 0; i < nNodes; i++) {
                 double expect = seed < 0 ? 1d / nNodes : (i == seed ? 1d : 0d);
-                if (restart[i] != expect)
-                    throw new System.NotSupportedException("Model.restart was modified: only the constructors' restart vectors are supported");
+                if (restart[i] != expect) return true;
             }
+            return false;
         }
 
         // the reference's public single steps (Model.cs:76,103,110)
         public void deliverRanks() {
-            CheckRestart();
+            bool custom = CustomRestart();
             for (int i = 0; i < nNodes; i++)
                 if (nextRank[i] != 0)
                     throw new System.InvalidOperationException("deliverRanks() on a non-zero nextRank: call updateRanks() first");
-            Native.Check(Native.rwr_model_deliver(graph.handle, seed, dampingFactor, rank, nextRank));
+            if (custom)
+                Native.Check(Native.rwr_model_deliver_restart(graph.handle, restart, dampingFactor, rank, nextRank));
+            else
+                Native.Check(Native.rwr_model_deliver(graph.handle, seed, dampingFactor, rank, nextRank));
         }
         public void updateRanks() {
             for (int i = 0; i < nNodes; i++) { rank[i] = nextRank[i]; nextRank[i] = 0; }

@@ -164,11 +164,13 @@ public:
     int64_t iterations = 0;
 
     // the reference's public single steps
-    void deliverRanks()                                        // :76-100 -> rwr_model_deliver
+    void deliverRanks()                                        // :76-100 -> rwr_model_deliver(_restart)
     {
+        const bool custom = custom_restart_();
         for (double v : nextRank)
             if (v != 0.0) throw std::logic_error("deliverRanks() on a non-zero nextRank: call updateRanks() first");
-        check(rwr_model_deliver(graph.handle(), seed_, dampingFactor, rank.data(), nextRank.data()));
+        if (custom) check(rwr_model_deliver_restart(graph.handle(), restart.data(), dampingFactor, rank.data(), nextRank.data()));
+        else check(rwr_model_deliver(graph.handle(), seed_, dampingFactor, rank.data(), nextRank.data()));
     }
     void updateRanks()                                         // :103-108
     {
@@ -192,8 +194,25 @@ private:
         }
         return true;
     }
+    // the public field restart (Model.cs:12) edited by the host: the *_restart entry points serve it
+    bool custom_restart_() const
+    {
+        if ((int)restart.size() != nNodes) throw std::invalid_argument("Model.restart must hold nNodes values");
+        for (int i = 0; i < nNodes; ++i) {
+            const double expect = seed_ < 0 ? 1.0 / nNodes : (i == seed_ ? 1.0 : 0.0);
+            if (restart[i] != expect) return true;
+        }
+        return false;
+    }
     void run_(int mode, double value)
     {
+        if (custom_restart_()) {                               // the whole loop on the device, from the current rank
+            for (double v : nextRank)
+                if (v != 0.0) throw std::logic_error("run() on a non-zero nextRank: call updateRanks() first");
+            check(rwr_model_run_restart(graph.handle(), restart.data(), rank.data(), dampingFactor, mode, value, rank.data(),
+                                        &iterations));
+            return;
+        }
         if (ctor_state_()) {                                   // the whole loop stays on the device
             check(rwr_model_run(graph.handle(), seed_, dampingFactor, mode, value, rank.data(), &iterations));
             nextRank.assign(nNodes, 0.0);

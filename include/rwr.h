@@ -253,6 +253,20 @@ int32_t rwr_model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, do
  * uniform restart (tolerance parity, as rwr_model_run).  rank and next_rank hold n doubles and may not alias. */
 int32_t rwr_model_deliver(rwr_graph *g, int32_t seed, double d, const double *rank, double *next_rank);
 
+/* Model with a caller-set restart vector: the public field Model.restart (Model.cs:12), which deliverRanks reads on every
+ * step (Model.cs:92-93 for rows with links, :96-97 for dangling rows) -- how a user of the reference runs multi-seed or
+ * topic-weighted walks.  restart: n doubles, any finite values; rank_in: the starting rank (n doubles; may alias rank_out).
+ * run_mode / value / rank_out / iters_out as rwr_model_run.  Bitwise in EXACT mode when at most RWR_RESTART_EXACT_MAX
+ * entries of restart are non-zero (-0.0 counts as zero), tolerance parity otherwise (as the global model).  A NULL graph,
+ * restart or rank pointer fails with RWR_E_INVALID; a non-finite entry of restart or of the rank with RWR_E_UNSUPPORTED
+ * (inf * 0 would turn every row into NaN in the reference). */
+#define RWR_RESTART_EXACT_MAX 256
+int32_t rwr_model_run_restart(rwr_graph *g, const double *restart, const double *rank_in, double d,
+                              int32_t run_mode, double value, double *rank_out, int64_t *iters_out);
+/* ONE deliverRanks() with a caller-set restart vector (as rwr_model_deliver; rank and next_rank may alias) */
+int32_t rwr_model_deliver_restart(rwr_graph *g, const double *restart, double d,
+                                  const double *rank, double *next_rank);
+
 /* ---- row-partitioned mode (graphs beyond one GPU; BASELINE.json config 5) ------------
  * An ADDITION: the reference has no distributed mode.  The transition matrix is partitioned by SOURCE rows
  * (the reference's native layout: graph[i] = out-links of i, Graph.cs:43): rank r owns the contiguous node slab

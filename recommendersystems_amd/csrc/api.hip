@@ -825,6 +825,27 @@ int32_t rwr_model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, do
     return RWR_OK;
 }
 
+int32_t rwr_model_run_restart(rwr_graph *g, const double *restart, const double *rank_in, double d, int32_t run_mode,
+                              double value, double *rank_out, int64_t *iters_out)
+{
+    g_err[0] = 0;
+    if (!g || !restart || !rank_in || !rank_out) { set_error("rwr_model_run_restart: NULL argument"); return RWR_E_INVALID; }
+    if (run_mode != RWR_RUN_ITERATIONS && run_mode != RWR_RUN_THRESHOLD && run_mode != RWR_RUN_DEFAULT_THRESHOLD) {
+        set_error("rwr_model_run_restart: unknown run_mode %d", run_mode);
+        return RWR_E_INVALID;
+    }
+    RWR_BIND(g);
+    return model_run_restart(g, restart, rank_in, d, run_mode, value, rank_out, iters_out);
+}
+
+int32_t rwr_model_deliver_restart(rwr_graph *g, const double *restart, double d, const double *rank, double *next_rank)
+{
+    g_err[0] = 0;
+    if (!g || !restart || !rank || !next_rank) { set_error("rwr_model_deliver_restart: NULL argument"); return RWR_E_INVALID; }
+    RWR_BIND(g);
+    return model_deliver_restart(g, restart, d, rank, next_rank);
+}
+
 int32_t rwr_part_begin(rwr_graph *g, int32_t slab_lo, int32_t slab_hi, const int32_t *seeds, int32_t K, double d,
                        void *dev_x, int32_t *tile_seeds_out)
 {

@@ -175,6 +175,18 @@ int32_t part_rank(rwr_graph *g, double *x, int32_t top_n, int64_t *ids, double *
 int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double value, double *rank_out,
                   int64_t *iters_out);
 int32_t model_deliver(rwr_graph *g, int32_t seed, double d, const double *rank_in, double *next_out);
+// restart.hip: Model with a caller-set restart vector (rwr_model_run_restart / rwr_model_deliver_restart)
+int32_t model_run_restart(rwr_graph *g, const double *v, const double *rank_in, double d, int32_t run_mode, double value,
+                          double *rank_out, int64_t *iters_out);
+int32_t model_deliver_restart(rwr_graph *g, const double *v, double d, const double *rank_in, double *next_out);
+// iterate.hip pieces it shares with the global model: the link-only single-row SpMV (no_seed: a device int32 holding -1),
+// the tree-summed restart mass and |a - b| sums into *total (partials in g->d_part[0, MODEL_RED_PARTS)), |a - b| per node
+constexpr int MODEL_RED_PARTS = 256;
+void launch_linkonly_spmv(rwr_graph *g, const double *X, double *Y, const int32_t *no_seed, double c1, bool hub_scan,
+                          hipStream_t s);
+void launch_restart_mass(rwr_graph *g, const double *X, double c1, double *total, hipStream_t s);
+void launch_l1(rwr_graph *g, const double *a, const double *b, int32_t n, double *total, hipStream_t s);
+void launch_absdiff(const double *a, const double *b, int32_t n, double *out, hipStream_t s);
 // spmv.hip: single-seed SpMV (list-order sums, rows binned by in-degree)
 // (zin != nullptr: value-free form -- gathers zin, reads no per-entry value; zout (may be nullptr) receives the next z)
 // (hub_scan: every addend is known to be >= 0 and finite -- weights, ranks and 1-d -- so that rows of >= 2048 in-links may

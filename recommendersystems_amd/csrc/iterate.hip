@@ -1280,6 +1280,28 @@ __global__ void k_add_restart_share(double *__restrict__ y, int32_t n, const dou
     if (i < n) y[i] += *total * inv_n;
 }
 
+// pieces of the global model and of checkConvergence that restart.hip (custom restart vectors) runs as well
+static_assert(MODEL_RED_PARTS == RED_GRID, "engine.h: MODEL_RED_PARTS");
+void launch_linkonly_spmv(rwr_graph *g, const double *X, double *Y, const int32_t *no_seed, double c1, bool hub_scan,
+                          hipStream_t s)
+{
+    launch_spmm<1>(g, 1, X, Y, no_seed, c1, 0, nullptr, nullptr, s, nullptr, nullptr, nullptr, hub_scan);
+}
+void launch_restart_mass(rwr_graph *g, const double *X, double c1, double *total, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_rr_partial, dim3(RED_GRID), dim3(256), 0, s, X, g->dangling.p, g->n, c1, g->d_part.p);
+    hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(1), 0, s, g->d_part.p, RED_GRID, total);
+}
+void launch_l1(rwr_graph *g, const double *a, const double *b, int32_t n, double *total, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_l1_partial, dim3(RED_GRID), dim3(256), 0, s, a, b, n, g->d_part.p);
+    hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(1), 0, s, g->d_part.p, RED_GRID, total);
+}
+void launch_absdiff(const double *a, const double *b, int32_t n, double *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_absdiff, dim3(cdiv((size_t)n, 256)), dim3(256), 0, s, a, b, n, out);
+}
+
 int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double value, double *rank_out,
                   int64_t *iters_out)
 {

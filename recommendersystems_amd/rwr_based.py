@@ -282,7 +282,7 @@ def EvaluateGraphs(graphs, seeds, dampingFactor: float, nIteration: int, testSet
 
 
 class Model:
-    """class Model (Model.cs:5-116) backed by rwr_model_run."""
+    """class Model (Model.cs:5-116) backed by rwr_model_run (rwr_model_run_restart once the host has edited restart)."""
 
     def __init__(self, graph: Graph, dampingFactor: float, targetNode: Optional[int] = None):
         self.graph = graph
@@ -314,6 +314,18 @@ class Model:
         r = self.rank
         return bool(r[self._seed] == float(n) and np.count_nonzero(r) == (1 if n else 0))
 
+    def _custom_restart(self) -> Optional[np.ndarray]:
+        """The public field restart (Model.cs:12) as a contiguous float64 array when the host has edited it, else None
+        (the constructor's one-hot / uniform vector, which the seed / global paths serve)."""
+        n = self.nNodes
+        v = np.ascontiguousarray(self.restart, dtype=np.float64)
+        if v.shape != (n,):
+            raise ValueError(f"Model.restart must hold {n} values")
+        expect = np.full(n, 1.0 / n) if self._seed < 0 else np.zeros(n)
+        if 0 <= self._seed < n:
+            expect[self._seed] = 1.0
+        return None if np.array_equal(v, expect) else v
+
     def run(self, arg=None) -> None:
         """run(int) / run(double) / run()  (Model.cs:68-73, 57-66, 52-55).  From the constructor's state the whole loop
         runs on the device (rwr_model_run); on a model that has already been advanced -- the reference's run() continues
@@ -325,6 +337,20 @@ class Model:
             mode, value = _lib.RWR_RUN_DEFAULT_THRESHOLD, 0.0
         else:
             mode, value = _lib.RWR_RUN_THRESHOLD, float(arg)
+        v = self._custom_restart()
+        if v is not None:
+            # an edited restart vector: the whole loop on the device from the current rank (rwr_model_run_restart)
+            if np.any(self.nextRank != 0):
+                raise RuntimeError("run() on a non-zero nextRank (the reference would add on top of it): call updateRanks() first")
+            rank = np.ascontiguousarray(self.rank, dtype=np.float64)
+            out = np.empty(self.nNodes, dtype=np.float64)
+            it = C.c_int64(0)
+            _lib.check(lib.rwr_model_run_restart(self.graph._handle(), _p(v, C.c_double), _p(rank, C.c_double),
+                                                 self.dampingFactor, mode, value, _p(out, C.c_double), C.byref(it)))
+            self.rank = out
+            self.nextRank = np.zeros(self.nNodes)
+            self.iterations = int(it.value)
+            return
         if not self._ctor_state():
             if mode == _lib.RWR_RUN_ITERATIONS:                  # Model.cs:68-73
                 for _ in range(int(value)):
@@ -356,15 +382,15 @@ class Model:
         n = self.nNodes
         if np.any(self.nextRank != 0):
             raise RuntimeError("deliverRanks() on a non-zero nextRank (the reference would add on top of it): call updateRanks() first")
-        expect = np.full(n, 1.0 / n) if self._seed < 0 else np.zeros(n)
-        if 0 <= self._seed < n:
-            expect[self._seed] = 1.0
-        if not np.array_equal(np.asarray(self.restart, dtype=np.float64), expect):
-            raise RuntimeError("Model.restart was modified: only the constructors' restart vectors are supported")
+        v = self._custom_restart()
         rank = np.ascontiguousarray(self.rank, dtype=np.float64)
         out = np.empty(n, dtype=np.float64)
-        _lib.check(_lib.load().rwr_model_deliver(self.graph._handle(), self._seed, self.dampingFactor,
-                                                 _p(rank, C.c_double), _p(out, C.c_double)))
+        if v is not None:
+            _lib.check(_lib.load().rwr_model_deliver_restart(self.graph._handle(), _p(v, C.c_double), self.dampingFactor,
+                                                             _p(rank, C.c_double), _p(out, C.c_double)))
+        else:
+            _lib.check(_lib.load().rwr_model_deliver(self.graph._handle(), self._seed, self.dampingFactor,
+                                                     _p(rank, C.c_double), _p(out, C.c_double)))
         self.nextRank = out
 
     def updateRanks(self) -> None:
