@@ -316,6 +316,36 @@ __global__ void k_u32_to_i32(const uint32_t *__restrict__ a, int32_t *__restrict
     if (p < m) b[p] = (int32_t)a[p];
 }
 
+// rows of the batch's last two steps (tail_rows_prepare): flag every source of an explicit link into an ITEM row,
+// one wave per ITEM row walking its transposed in-list -- the entries the SpMM gathers for that row
+__global__ __launch_bounds__(256) void k_tail_flag(int32_t n_items, const int32_t *__restrict__ item_rows,
+                                                   const int64_t *__restrict__ in_ptr, const int32_t *__restrict__ in_src,
+                                                   uint8_t *__restrict__ flag)
+{
+    const int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+    if (q >= n_items) return;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int32_t j = item_rows[q];
+    const int64_t p1 = in_ptr[j + 1];
+    for (int64_t p = in_ptr[j] + lane; p < p1; p += WAVE) flag[in_src[p]] = 1;
+}
+// ... and the keys of a stable one-bit partition of row_order: rows whose flag equals `match` first; *count = how many
+__global__ __launch_bounds__(256) void k_tail_keys(int32_t n, const int32_t *__restrict__ row_order,
+                                                   const uint8_t *__restrict__ flag, uint8_t match,
+                                                   uint32_t *__restrict__ key, uint32_t *__restrict__ val, int *__restrict__ count)
+{
+    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    bool in = false;
+    if (r < n) {
+        const int32_t i = row_order[r];
+        in = flag[i] == match;
+        key[r] = in ? 0u : 1u;
+        val[r] = (uint32_t)i;
+    }
+    const unsigned long long b = __ballot(in);
+    if ((threadIdx.x & (WAVE - 1)) == 0 && b) atomicAdd(count, (int)__popcll(b));
+}
+
 // incremental rebuild: overwrite type and/or weight of the listed raw links
 __global__ __launch_bounds__(256) void k_patch_links(int64_t count, const int64_t *__restrict__ idx,
                                                      const uint8_t *__restrict__ new_type, const double *__restrict__ new_w,
@@ -805,6 +835,7 @@ static int32_t graph_derive(rwr_graph *g, bool first)
     g->sw_ent.release();
     g->sw_wgblk.release();
     g->sw_partial = 0;
+    g->tail_state = 0;   // a link's type or weight may have changed which rows link into ITEM rows
     g->part_G = 0;   // a row-partitioned run sized for the previous matrix is over: rwr_part_step asks for a new rwr_part_begin
 
     const int32_t n = g->n;
@@ -1018,6 +1049,51 @@ int32_t ensure_in_w(rwr_graph *g)
                            g->w_src.p, g->in_w.p);
         RWR_HIP(hipGetLastError());
     }
+    return RWR_OK;
+}
+
+// The two row lists of a batch's last steps, derived from the built matrix: a stable one-bit partition of
+// row_order each, so that both keep its in-degree-descending load balance.
+int32_t tail_rows_prepare(rwr_graph *g)
+{
+    if (g->tail_state == 1) return RWR_OK;
+    const int32_t n = g->n;
+    hipStream_t s = g->stream;
+    DevBuf<uint8_t> flag, temp;
+    DevBuf<uint32_t> key, key2, val, val2;
+    DevBuf<int> cnt;
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    RWR_TRY(flag.alloc(nn));
+    RWR_TRY(key.alloc(nn));
+    RWR_TRY(key2.alloc(nn));
+    RWR_TRY(val.alloc(nn));
+    RWR_TRY(val2.alloc(nn));
+    RWR_TRY(cnt.alloc(2));
+    RWR_TRY(temp.alloc(radix_sort_temp_bytes(nn, 1)));
+    RWR_HIP(hipMemsetAsync(flag.p, 0, nn, s));
+    RWR_HIP(hipMemsetAsync(cnt.p, 0, 2 * sizeof(int), s));
+    if (g->n_items > 0)
+        hipLaunchKernelGGL(k_tail_flag, dim3(cdiv((size_t)g->n_items, 256 / WAVE)), dim3(256), 0, s, g->n_items,
+                           g->item_rows.p, g->in_ptr.p, g->in_src.p, flag.p);
+    for (int l = 0; l < 2; ++l) {
+        int h_cnt = 0;
+        if (n > 0) {
+            hipLaunchKernelGGL(k_tail_keys, dim3(cdiv((size_t)n, 256)), dim3(256), 0, s, n, g->row_order.p,
+                               l == 0 ? g->node_type.p : flag.p, (uint8_t)(l == 0 ? RWR_NODE_ITEM : 1), key.p, val.p, cnt.p + l);
+            bool alt = false;
+            RWR_TRY(radix_sort_pairs<uint32_t>(key.p, key2.p, val.p, val2.p, (size_t)n, 1, 1, temp.p, s, &alt));
+            RWR_HIP(hipMemcpyAsync(&h_cnt, cnt.p + l, sizeof(int), hipMemcpyDeviceToHost, s));
+            RWR_HIP(hipStreamSynchronize(s));
+            RWR_TRY(g->tail_rows[l].alloc((size_t)(h_cnt > 0 ? h_cnt : 1)));
+            if (h_cnt > 0)
+                hipLaunchKernelGGL(k_u32_to_i32, dim3(cdiv((size_t)h_cnt, 256)), dim3(256), 0, s, alt ? val2.p : val.p,
+                                   g->tail_rows[l].p, (int64_t)h_cnt);
+        }
+        g->tail_n[l] = h_cnt;
+    }
+    RWR_HIP(hipGetLastError());
+    RWR_HIP(hipStreamSynchronize(s));   // the scratch buffers are released on return
+    g->tail_state = 1;
     return RWR_OK;
 }
 

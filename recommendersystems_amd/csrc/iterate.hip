@@ -35,7 +35,7 @@ template <int G, bool VF>
 __global__ __launch_bounds__(256) void k_spmm(int32_t n, const int64_t *__restrict__ in_ptr,
                                               const int32_t *__restrict__ in_src,
                                               const double *__restrict__ in_w,
-                                              const int32_t *__restrict__ row_order,
+                                              const int32_t *__restrict__ row_order, int32_t nrows,
                                               const double *__restrict__ X, double *__restrict__ Y,
                                               const int32_t *__restrict__ seeds, double c1, int skip_seed_row,
                                               const double *__restrict__ w_src, double *__restrict__ Zout)
@@ -52,11 +52,11 @@ __global__ __launch_bounds__(256) void k_spmm(int32_t n, const int64_t *__restri
     const int32_t my_seed = skip_seed_row ? seeds[tile * G + k] : -1;
     const int wpb = blockDim.x / WAVE;
     const int64_t nwaves = (int64_t)gridDim.x * wpb;
-    for (int64_t rb = ((int64_t)blockIdx.x * wpb + threadIdx.x / WAVE) * RPW; rb < n; rb += nwaves * RPW) {
+    for (int64_t rb = ((int64_t)blockIdx.x * wpb + threadIdx.x / WAVE) * RPW; rb < nrows; rb += nwaves * RPW) {
         const int64_t r = rb + sub;
         int32_t j = -1;
         int64_t p = 0, e = 0;
-        if (r < n) {
+        if (r < nrows) {
             j = row_order[r];
             p = in_ptr[j];
             e = in_ptr[j + 1];
@@ -108,11 +108,13 @@ __global__ __launch_bounds__(256) void k_spmm(int32_t n, const int64_t *__restri
 // the non-negative accumulator bitwise unchanged.  WRITE records the non-zero rows of Y for the next step.
 // VF: the value-free form (see k_spmm): X is the z matrix, one index load + one bpermute + one gather + ONE add per
 // entry, no weight stream, no multiplies; the epilogue writes the row's next z.
-template <int G, int CH, bool CHECK, bool WRITE, bool VF>
+// LIST: the launch walks a row list rather than every row -- the same code; a separate instantiation only so
+// that kernel traces and counter passes tell these launches from the dense ones
+template <int G, int CH, bool CHECK, bool WRITE, bool VF, bool LIST>
 __global__ __launch_bounds__(256) void k_spmm_chunked(int32_t n, const int64_t *__restrict__ in_ptr,
                                                       const int32_t *__restrict__ in_src,
                                                       const double *__restrict__ in_w,
-                                                      const int32_t *__restrict__ row_order,
+                                                      const int32_t *__restrict__ row_order, int32_t nrows,
                                                       const double *__restrict__ X, double *__restrict__ Y,
                                                       const int32_t *__restrict__ seeds, double c1,
                                                       int skip_seed_row, const uint32_t *__restrict__ nz_in,
@@ -137,11 +139,11 @@ __global__ __launch_bounds__(256) void k_spmm_chunked(int32_t n, const int64_t *
     const int32_t my_seed = skip_seed_row ? seeds[tile * G + k] : -1;
     const int wpb = blockDim.x / WAVE;
     const int64_t nwaves = (int64_t)gridDim.x * wpb;
-    for (int64_t rb = ((int64_t)blockIdx.x * wpb + threadIdx.x / WAVE) * RPW; rb < n; rb += nwaves * RPW) {
+    for (int64_t rb = ((int64_t)blockIdx.x * wpb + threadIdx.x / WAVE) * RPW; rb < nrows; rb += nwaves * RPW) {
         const int64_t r = rb + sub;
         int32_t j = -1;
         int64_t p = 0, e = 0;
-        if (r < n) {
+        if (r < nrows) {
             j = row_order[r];
             p = in_ptr[j];
             e = in_ptr[j + 1];
@@ -654,31 +656,39 @@ template <int G>
 static void launch_spmm(rwr_graph *g, int tg, const double *X, double *Y, const int32_t *seeds, double c1,
                         int skip, const uint32_t *nz_in, uint32_t *nz_out, hipStream_t s,
                         const uint32_t *act = nullptr, const double *Zin = nullptr, double *Zout = nullptr,
-                        bool hub_scan = false)
+                        bool hub_scan = false, const int32_t *rows = nullptr, int32_t nrows = 0)
 {
     // Zin != nullptr: value-free form -- the kernels gather Zin (z of the current ranks) instead of X and read no weights
     const bool vf = Zin != nullptr;
     const double *GS = vf ? Zin : X;   // gather source
+    // rows != nullptr: only the nrows rows of that list (a batch's last steps); X / Y / Z keep their n rows
+    const bool listed = rows != nullptr;
+    if (!listed) { rows = g->row_order.p; nrows = g->n; }
     constexpr int RPW = WAVE / G;
-    unsigned want = cdiv((size_t)g->n, (size_t)RPW * 4);
-    unsigned gx = want < 8192u ? want : 8192u;
+    unsigned want = cdiv((size_t)nrows, (size_t)RPW * 4);
+    unsigned gx = want < 1u ? 1u : want < 8192u ? want : 8192u;
     static const int variant = [] { const char *e = getenv("RWR_SPMM"); return e ? atoi(e) : 1; }();
     if constexpr (G == 1) {
-        if (tg == 1 && variant != 0) {
+        if (tg == 1 && variant != 0) {   // (every row: the callers pass no row list to this path)
             launch_spmv_exact(g, X, Y, seeds, c1, skip, act, nz_out, s, Zin, Zout, hub_scan);
             return;
         }
     }
     if constexpr (G >= 8) {
         if (variant != 0) {
-#define RWR_SPMM_LAUNCH3(CH, CHK, WR, VFF)                                                                         \
-    hipLaunchKernelGGL((k_spmm_chunked<G, CH, CHK, WR, VFF>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p,    \
-                       g->in_src.p, g->in_w.p, g->row_order.p, GS, Y, seeds, c1, skip, nz_in, nz_out, act,         \
+#define RWR_SPMM_LAUNCH4(CH, CHK, WR, VFF, LST)                                                                        \
+    hipLaunchKernelGGL((k_spmm_chunked<G, CH, CHK, WR, VFF, LST>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p,    \
+                       g->in_src.p, g->in_w.p, rows, nrows, GS, Y, seeds, c1, skip, nz_in, nz_out, act,                  \
                        g->w_src.p, Zout)
+#define RWR_SPMM_LAUNCH3(CH, CHK, WR, VFF)                       \
+    {                                                            \
+        if (listed) RWR_SPMM_LAUNCH4(CH, CHK, WR, VFF, true);    \
+        else RWR_SPMM_LAUNCH4(CH, CHK, WR, VFF, false);          \
+    }
 #define RWR_SPMM_LAUNCH2(CH, CHK, WR)                    \
     {                                                    \
-        if (vf) RWR_SPMM_LAUNCH3(CH, CHK, WR, true);     \
-        else RWR_SPMM_LAUNCH3(CH, CHK, WR, false);       \
+        if (vf) RWR_SPMM_LAUNCH3(CH, CHK, WR, true)      \
+        else RWR_SPMM_LAUNCH3(CH, CHK, WR, false)        \
     }
 #define RWR_SPMM_LAUNCH(CH)                                  \
     {                                                        \
@@ -690,6 +700,7 @@ static void launch_spmm(rwr_graph *g, int tg, const double *X, double *Y, const 
             if (variant == 2) RWR_SPMM_LAUNCH(8)
             else if (variant == 3) RWR_SPMM_LAUNCH(4)
             else RWR_SPMM_LAUNCH((G > 16 ? 16 : G))
+#undef RWR_SPMM_LAUNCH4
 #undef RWR_SPMM_LAUNCH3
 #undef RWR_SPMM_LAUNCH2
 #undef RWR_SPMM_LAUNCH
@@ -698,10 +709,10 @@ static void launch_spmm(rwr_graph *g, int tg, const double *X, double *Y, const 
     }
     if (vf)
         hipLaunchKernelGGL((k_spmm<G, true>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p, g->in_w.p,
-                           g->row_order.p, GS, Y, seeds, c1, skip, g->w_src.p, Zout);
+                           rows, nrows, GS, Y, seeds, c1, skip, g->w_src.p, Zout);
     else
         hipLaunchKernelGGL((k_spmm<G, false>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p, g->in_w.p,
-                           g->row_order.p, GS, Y, seeds, c1, skip, g->w_src.p, Zout);
+                           rows, nrows, GS, Y, seeds, c1, skip, g->w_src.p, Zout);
 }
 template <int G>
 // the addends of the links into the seeds; tiny, runs on the MAIN stream ahead of the fork so that the chain kernel is
@@ -879,7 +890,10 @@ struct GroupIter {
     }
 
     // last = no further step follows: the value-free path need not form the next z
-    int32_t step(EvPool &pool, std::vector<hipEvent_t> &spmm_ev, std::vector<hipEvent_t> &chain_ev, bool last = false)
+    // rows != nullptr: the SpMM produces only the nrows rows of that list (a batch's last two steps);
+    // chain = false: no seed row of this step is read afterwards, its chain is not run
+    int32_t step(EvPool &pool, std::vector<hipEvent_t> &spmm_ev, std::vector<hipEvent_t> &chain_ev, bool last = false,
+                 const int32_t *rows = nullptr, int32_t nrows = 0, bool chain = true)
     {
         const int32_t n = g->n;
         hipStream_t s = g->stream, s2 = g->stream2;
@@ -900,7 +914,7 @@ struct GroupIter {
         }
         if (serial) s2 = s;
         // (while X is sparse the bitmap-walking chain serves a whole tile at once; for a single seed the scan is cheaper)
-        const bool scan_now = scan && (!act || G == 1);
+        const bool scan_now = chain && scan && (!act || G == 1);
         bool scan_side = false;
         bool seed_z_done = false;
         if (scan_now) {
@@ -928,7 +942,7 @@ struct GroupIter {
             if (prof) { RWR_HIP(hipEventRecord(c1e, sc)); chain_ev.push_back(c0); chain_ev.push_back(c1e); }
             if (scan_side) RWR_HIP(hipEventRecord(g->ev_join, s2));
             s2 = s;
-        } else {
+        } else if (chain) {
             // fork: the seed-row chain runs beside the SpMM on the second stream
             RWR_DISPATCH_G(G, launch_seed_terms<GG>(g, tg, X, d_seeds, c1, d_evoff, s, Zc));
             gate_it = (use_gate && s2 != s) ? g->d_gate.p + (it % GATE_SLOTS) : nullptr;
@@ -948,30 +962,52 @@ struct GroupIter {
         hipEvent_t a = nullptr, b = nullptr;
         if (prof) { a = pool.get(); b = pool.get(); RWR_HIP(hipEventRecord(a, s)); }
         double *zout = (Zc && !last) ? Zn : nullptr;
-        RWR_DISPATCH_G(G, launch_spmm<GG>(g, tg, X, Y, d_seeds, c1, 1, nz_in, nz_out, s, act, Zc, zout, addends_nonneg));
-        if (prof) { RWR_HIP(hipEventRecord(b, s)); spmm_ev.push_back(a); spmm_ev.push_back(b); g->spmm_ev_dense.push_back(nz_in ? 0 : 1); }
-        if (!nz_in) { g->stats.spmm_dense_launches += 1; ++dense_steps; }
-        if ((s2 != s && !scan_now) || scan_side) RWR_HIP(hipStreamWaitEvent(s, g->ev_join, 0));
+        RWR_DISPATCH_G(G, launch_spmm<GG>(g, tg, X, Y, d_seeds, c1, 1, nz_in, nz_out, s, act, Zc, zout, addends_nonneg, rows, nrows));
+        // (a launch over a row list is no dense launch either: it walks only part of the matrix)
+        const bool dense = !nz_in && !rows;
+        if (prof) { RWR_HIP(hipEventRecord(b, s)); spmm_ev.push_back(a); spmm_ev.push_back(b); g->spmm_ev_dense.push_back(dense ? 1 : 0); }
+        if (dense) { g->stats.spmm_dense_launches += 1; ++dense_steps; }
+        if ((s2 != s && !scan_now && chain) || scan_side) RWR_HIP(hipStreamWaitEvent(s, g->ev_join, 0));
         // value-free path: the seed rows' own z, now that the seed-row kernel has left their rank in Y
-        if (zout && !seed_z_done) hipLaunchKernelGGL(k_seed_z, dim3(cdiv((size_t)tg * G, 64)), dim3(64), 0, s, n, tg, G, Y, zout, d_seeds, g->w_src.p, c1);
+        if (zout && !seed_z_done && chain) hipLaunchKernelGGL(k_seed_z, dim3(cdiv((size_t)tg * G, 64)), dim3(64), 0, s, n, tg, G, Y, zout, d_seeds, g->w_src.p, c1);
         RWR_HIP(hipGetLastError());
         { double *t = X; X = Y; Y = t; }   // Model.updateRanks (Model.cs:103-108)
         { double *t = Zc; Zc = Zn; Zn = t; }
         { uint32_t *tz = nz_cur; nz_cur = nz_oth; nz_oth = tz; }
         g->stats.spmm_launches += 1;
-        g->stats.chain_launches += 1;
+        g->stats.chain_launches += chain ? 1 : 0;
         ++it;
         return RWR_OK;
     }
 };
 
+// rank_only: the caller reads nothing of the final ranks but their ITEM rows (Recommender.cs:29-31), so the last two steps
+// produce only the rows that reach them; item_seed: a seed of the group is itself an ITEM row
 int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const int64_t *d_evoff, double d,
                       int64_t n_iter, double **final_X, EvPool &pool, std::vector<hipEvent_t> &spmm_ev,
-                      std::vector<hipEvent_t> &chain_ev, int64_t *dense_steps)
+                      std::vector<hipEvent_t> &chain_ev, int64_t *dense_steps, bool rank_only = false, bool item_seed = true)
 {
     GroupIter gi(g, G, tg, d_seeds, d_evoff, d);
     RWR_TRY(gi.init());
-    for (int64_t it = 0; it < n_iter; ++it) RWR_TRY(gi.step(pool, spmm_ev, chain_ev, it + 1 == n_iter));
+    static const int tail_env = [] { const char *e = getenv("RWR_TAIL_ROWS"); return e ? atoi(e) : 1; }();
+    // (one seed on its own takes the single-seed SpMV, whose rows stay all rows)
+    const bool tails = rank_only && tail_env != 0 && !(G == 1 && tg == 1);
+    if (tails) RWR_TRY(tail_rows_prepare(g));
+    for (int64_t it = 0; it < n_iter; ++it) {
+        const int64_t left = n_iter - it;   // this step and those after it
+        const int32_t *rows = nullptr;
+        int32_t nrows = 0;
+        bool chain = true;
+        if (tails && left == 1) {
+            // the last step: the ITEM rows; the seed rows only where the seed is an ITEM
+            rows = g->tail_rows[0].p; nrows = g->tail_n[0]; chain = item_seed;
+        } else if (tails && left == 2 && !item_seed) {
+            // the step before: the sources of the ITEM rows' in-links, plus the seed rows (chain).  A last-step chain
+            // would fold the restart addend of EVERY row of this step's ranks, so with an ITEM seed this step stays whole
+            rows = g->tail_rows[1].p; nrows = g->tail_n[1];
+        }
+        RWR_TRY(gi.step(pool, spmm_ev, chain_ev, left == 1, rows, nrows, chain));
+    }
     *final_X = gi.X;
     *dense_steps = gi.dense_steps;
     return RWR_OK;
@@ -1026,7 +1062,8 @@ static int32_t ensure_workspace(rwr_graph *g, int G, int32_t K, int *TG_out)
 // seeds (the only non-streaming work of the exact seed-row kernel) spread evenly over the tiles instead of
 // piling up in the tile that would hold the batch's hottest seeds.  slot_k maps a slot back to the
 // caller's batch position; padding slots hold seed -1.  Also: offsets of every slot's in-link term list.
-static int32_t upload_seed_slots(rwr_graph *g, const int32_t *seeds, int32_t K, int G, std::vector<int32_t> *slot_k_out)
+static int32_t upload_seed_slots(rwr_graph *g, const int32_t *seeds, int32_t K, int G, std::vector<int32_t> *slot_k_out,
+                                 std::vector<int32_t> *slot_seed_out = nullptr)
 {
     const int ntiles = (int)cdiv((size_t)K, (size_t)G);
     const size_t slots = (size_t)ntiles * G;
@@ -1053,6 +1090,7 @@ static int32_t upload_seed_slots(rwr_graph *g, const int32_t *seeds, int32_t K, 
     RWR_HIP(hipMemcpy(g->d_slot_k.p, sk.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice));
     RWR_HIP(hipMemcpy(g->d_evoff.p, off.data(), (slots + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     if (slot_k_out) *slot_k_out = sk;
+    if (slot_seed_out) *slot_seed_out = hs;
     return RWR_OK;
 }
 
@@ -1143,8 +1181,8 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
     int TG = 1;
     RWR_TRY(ensure_workspace(g, G, K, &TG));
     const int ntiles = (int)cdiv((size_t)K, (size_t)G);
-    std::vector<int32_t> slot_k;
-    RWR_TRY(upload_seed_slots(g, seeds, K, G, &slot_k));
+    std::vector<int32_t> slot_k, slot_seed;
+    RWR_TRY(upload_seed_slots(g, seeds, K, G, &slot_k, &slot_seed));
     if (any_dangling) {   // slots map to positions in the live list: translate to the caller's batch positions
         for (auto &v : slot_k) if (v >= 0) v = live_rows[v];
         RWR_HIP(hipMemcpy(g->d_slot_k.p, slot_k.data(), slot_k.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1161,7 +1199,11 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
         hipEvent_t i0 = nullptr, i1 = nullptr;
         if (prof) { i0 = pool.get(); i1 = pool.get(); RWR_HIP(hipEventRecord(i0, s)); }
         int64_t dense_steps = 0;
-        RWR_TRY(iterate_group(g, G, tg, dseeds, g->d_evoff.p + (size_t)t0 * G, d, n_iter, &Xf, pool, spmm_ev, chain_ev, &dense_steps));
+        bool item_seed = false;
+        for (size_t q = (size_t)t0 * G; q < (size_t)(t0 + tg) * G; ++q)
+            item_seed = item_seed || (slot_seed[q] >= 0 && g->h_is_item[slot_seed[q]]);
+        RWR_TRY(iterate_group(g, G, tg, dseeds, g->d_evoff.p + (size_t)t0 * G, d, n_iter, &Xf, pool, spmm_ev, chain_ev,
+                              &dense_steps, true, item_seed));
         if (prof) { RWR_HIP(hipEventRecord(i1, s)); iter_ev.push_back(i0); iter_ev.push_back(i1); }
         int32_t real = 0;
         for (size_t q = (size_t)t0 * G; q < (size_t)(t0 + tg) * G; ++q) real += slot_k[q] >= 0;

@@ -48,8 +48,11 @@ def main():
                              "Infinity-Cache hits are included in FETCH_SIZE",
                "kernels": kernels}
     json.dump(summary, open(out_summary, "w"), indent=1)
-    # the DENSE variant only (template arguments CHECK = false, WRITE = false): the launches bench.py prices
-    spmm = {k: v for k, v in kernels.items() if k.startswith("rwr::k_spmm_chunked") and ", false, false," in k
+    # the DENSE variant only (template arguments CHECK = false, WRITE = false, LIST = false): the launches bench.py prices
+    def dense(k):
+        a = [t.strip() for t in k.split("<", 1)[1].rstrip(">").split(",")] if "<" in k else []
+        return len(a) >= 5 and a[2] == "false" and a[3] == "false" and (len(a) < 6 or a[5] == "false")
+    spmm = {k: v for k, v in kernels.items() if k.startswith("rwr::k_spmm_chunked") and dense(k)
             and "hbm_side_bytes_per_launch_corrected" in v}
     launches = sum(v["launches_in_pass_FETCH_SIZE"] for v in spmm.values())
     if launches:
