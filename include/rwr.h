@@ -119,6 +119,8 @@ typedef struct rwr_stats {
                                 (Model.cs:84,87) is ONE double per source node and step; the kernels gather it and
                                 read no per-entry value (4 instead of 12 matrix bytes per entry) -- bitwise equal */
     int32_t reserved1;
+    int64_t frontier_list_launches; /* SpMM launches of a batch's first steps that walked only each tile's
+                                       frontier row list (the rows an out-link of a non-zero row reaches) */
 } rwr_stats;
 
 /* ---- library ------------------------------------------------------------------------- */

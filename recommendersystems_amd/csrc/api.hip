@@ -906,6 +906,7 @@ int32_t rwr_reset_stats(rwr_graph *g)
     s.spmm_launches = s.spmm_seed_steps = s.chain_launches = s.seeds_done = s.chain_redo_blocks = 0;
     s.spmm_dense_ms = 0;
     s.spmm_dense_launches = s.spmm_dense_seed_steps = 0;
+    s.frontier_list_launches = 0;
     return RWR_OK;
 }
 

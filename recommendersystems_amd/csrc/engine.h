@@ -100,6 +100,7 @@ struct rwr_graph {
     rwr::DevBuf<double> d_part;       // partial sums of the deterministic tree reductions (global model, row-partitioned restart mass)
     rwr::DevBuf<unsigned int> d_gate;   // exact mode: check-in counter of the resident chain workgroups
     rwr::DevBuf<uint32_t> d_nz;       // [2][tile][ceil(n/32)] bitmaps: row of X / Y has a non-zero (first iterations)
+    rwr::DevBuf<int32_t> fl_rows;     // [tile][n] frontier row lists of a batch's first steps, then [tile] their lengths
     rwr::DevBuf<int64_t> d_evoff;     // exact mode: per seed slot, offset of its in-link terms in d_evterm
     rwr::DevBuf<double> d_evterm;     // exact mode: ((1-d) x_src) * w of every link INTO a seed, list order
     // exact mode, parallel seed-row chain (chain_scan.hip): per (tile, block, seed) approximate block sum,

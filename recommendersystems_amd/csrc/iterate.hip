@@ -110,17 +110,17 @@ __global__ __launch_bounds__(256) void k_spmm(int32_t n, const int64_t *__restri
 // entry, no weight stream, no multiplies; the epilogue writes the row's next z.
 // LIST: the launch walks a row list rather than every row -- the same code; a separate instantiation only so
 // that kernel traces and counter passes tell these launches from the dense ones
-template <int G, int CH, bool CHECK, bool WRITE, bool VF, bool LIST>
-__global__ __launch_bounds__(256) void k_spmm_chunked(int32_t n, const int64_t *__restrict__ in_ptr,
-                                                      const int32_t *__restrict__ in_src,
-                                                      const double *__restrict__ in_w,
-                                                      const int32_t *__restrict__ row_order, int32_t nrows,
-                                                      const double *__restrict__ X, double *__restrict__ Y,
-                                                      const int32_t *__restrict__ seeds, double c1,
-                                                      int skip_seed_row, const uint32_t *__restrict__ nz_in,
-                                                      uint32_t *__restrict__ nz_out,
-                                                      const uint32_t *__restrict__ act,
-                                                      const double *__restrict__ w_src, double *__restrict__ Zout)
+template <int G, int CH, bool CHECK, bool WRITE, bool VF>
+__device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__restrict__ in_ptr,
+                                                  const int32_t *__restrict__ in_src,
+                                                  const double *__restrict__ in_w,
+                                                  const int32_t *__restrict__ row_order, int32_t nrows,
+                                                  const double *__restrict__ X, double *__restrict__ Y,
+                                                  const int32_t *__restrict__ seeds, double c1,
+                                                  int skip_seed_row, const uint32_t *__restrict__ nz_in,
+                                                  uint32_t *__restrict__ nz_out,
+                                                  const uint32_t *__restrict__ act,
+                                                  const double *__restrict__ w_src, double *__restrict__ Zout)
 {
     static_assert(G >= 8 && G <= 64, "chunked SpMM needs 8 <= G <= 64");
     constexpr int RPW = WAVE / G;
@@ -232,30 +232,99 @@ __global__ __launch_bounds__(256) void k_spmm_chunked(int32_t n, const int64_t *
     }
 }
 
+template <int G, int CH, bool CHECK, bool WRITE, bool VF, bool LIST>
+__global__ __launch_bounds__(256) void k_spmm_chunked(int32_t n, const int64_t *__restrict__ in_ptr,
+                                                      const int32_t *__restrict__ in_src,
+                                                      const double *__restrict__ in_w,
+                                                      const int32_t *__restrict__ row_order, int32_t nrows,
+                                                      const double *__restrict__ X, double *__restrict__ Y,
+                                                      const int32_t *__restrict__ seeds, double c1,
+                                                      int skip_seed_row, const uint32_t *__restrict__ nz_in,
+                                                      uint32_t *__restrict__ nz_out,
+                                                      const uint32_t *__restrict__ act,
+                                                      const double *__restrict__ w_src, double *__restrict__ Zout)
+{
+    spmm_chunked_body<G, CH, CHECK, WRITE, VF>(n, in_ptr, in_src, in_w, row_order, nrows, X, Y, seeds, c1, skip_seed_row,
+                                               nz_in, nz_out, act, w_src, Zout);
+}
+
+// Frontier-list steps: the same body over a per-tile row list built by k_mark_active -- tile t walks the
+// fl_cnt[t] rows of fl_rows[t * n ...], and no other row of Y / Zout is written.  Every listed row is written whole (all G
+// lanes but the seed's own, which the seed-row chain writes).  The count lives on the device: the host never waits for it.
+template <int G, int CH, bool VF>
+__global__ __launch_bounds__(256) void k_spmm_frontier(int32_t n, const int64_t *__restrict__ in_ptr,
+                                                       const int32_t *__restrict__ in_src,
+                                                       const double *__restrict__ in_w,
+                                                       const int32_t *__restrict__ fl_rows,
+                                                       const int32_t *__restrict__ fl_cnt,
+                                                       const double *__restrict__ X, double *__restrict__ Y,
+                                                       const int32_t *__restrict__ seeds, double c1,
+                                                       int skip_seed_row, const uint32_t *__restrict__ nz_in,
+                                                       uint32_t *__restrict__ nz_out,
+                                                       const double *__restrict__ w_src, double *__restrict__ Zout)
+{
+    const int tile = blockIdx.y;
+    spmm_chunked_body<G, CH, true, true, VF>(n, in_ptr, in_src, in_w, fl_rows + (size_t)tile * (size_t)n, fl_cnt[tile], X, Y,
+                                             seeds, c1, skip_seed_row, nz_in, nz_out, nullptr, w_src, Zout);
+}
+
 // First iterations: destination rows that can become non-zero = out-neighbours (explicit links) of the rows of X
 // that hold a non-zero.  One thread per bitmap word of the tile; pushes over the RAW out-links.
+// fl_rows != nullptr (frontier-list step): also the tile's row list -- the lane whose atomicOr sets a new
+// bit appends the row (one atomicAdd per wave), and the tile's seed rows are marked and listed too, so that every row the
+// step writes is written whole.  Each row enters a tile's list once.
 __global__ __launch_bounds__(256) void k_mark_active(int32_t n, const uint32_t *__restrict__ nz, uint32_t *__restrict__ act,
                                                      const int64_t *__restrict__ rowptr, const int32_t *__restrict__ dst,
-                                                     const uint8_t *__restrict__ etype)
+                                                     const uint8_t *__restrict__ etype, int G, const int32_t *__restrict__ seeds,
+                                                     int32_t *__restrict__ fl_rows, int32_t *__restrict__ fl_cnt)
 {
     // one WAVE per bitmap word; the lanes stride over the out-links of each non-zero row of that word
     const size_t nzw = ((size_t)n + 31) / 32;
     const int tile = blockIdx.y;
     const int lane = threadIdx.x & (WAVE - 1);
     const size_t wi = (size_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+    uint32_t *a = act + (size_t)tile * nzw;
+    int32_t *list = fl_rows ? fl_rows + (size_t)tile * (size_t)n : nullptr;
+    if (list && blockIdx.x == 0 && threadIdx.x < (unsigned)G) {
+        const int32_t sr = seeds[tile * G + threadIdx.x];
+        if (sr >= 0) {
+            const uint32_t bit = 1u << (sr & 31);
+            if (!(atomicOr(&a[(uint32_t)sr >> 5], bit) & bit)) list[atomicAdd(&fl_cnt[tile], 1)] = sr;
+        }
+    }
     if (wi >= nzw) return;
     uint32_t w = nz[(size_t)tile * nzw + wi];
-    uint32_t *a = act + (size_t)tile * nzw;
     while (w) {
         const int b = __builtin_ctz(w);
         w &= w - 1;
         const int64_t i = (int64_t)wi * 32 + b;
         const int64_t p1 = rowptr[i + 1];
-        for (int64_t p = rowptr[i] + lane; p < p1; p += WAVE)
-            if (etype[p] != RWR_EDGE_UNDEFINED) {
-                const int32_t t = dst[p];
-                atomicOr(&a[(uint32_t)t >> 5], 1u << (t & 31));
+        if (!list) {
+            for (int64_t p = rowptr[i] + lane; p < p1; p += WAVE)
+                if (etype[p] != RWR_EDGE_UNDEFINED) {
+                    const int32_t t = dst[p];
+                    atomicOr(&a[(uint32_t)t >> 5], 1u << (t & 31));
+                }
+            continue;
+        }
+        for (int64_t p0 = rowptr[i]; p0 < p1; p0 += WAVE) {   // (i is wave-uniform: every lane takes the same trips)
+            const int64_t p = p0 + lane;
+            bool add = false;
+            int32_t t = 0;
+            if (p < p1 && etype[p] != RWR_EDGE_UNDEFINED) {
+                t = dst[p];
+                const uint32_t bit = 1u << (t & 31);
+                add = !(atomicOr(&a[(uint32_t)t >> 5], bit) & bit);
             }
+            const unsigned long long m = __ballot(add);
+            if (!m) continue;
+            const int leader = __builtin_ctzll(m);
+            int base = 0;
+            if (lane == leader) base = atomicAdd(&fl_cnt[tile], (int)__popcll(m));
+            base = __shfl(base, leader);
+            const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            if (add) list[base + below] = t;
+        }
     }
 }
 
@@ -337,7 +406,8 @@ __global__ __launch_bounds__(256) void k_seed_terms(int32_t n, const int64_t *__
                                                     const int32_t *__restrict__ in_src,
                                                     const double *__restrict__ in_w, const double *__restrict__ X,
                                                     const int32_t *__restrict__ seeds, double c1,
-                                                    const int64_t *__restrict__ evoff, double *__restrict__ evterm)
+                                                    const int64_t *__restrict__ evoff, double *__restrict__ evterm,
+                                                    const uint32_t *__restrict__ nz)
 {
     const int slot = blockIdx.y;                 // tile * G + k
     const int32_t s = seeds[slot];
@@ -346,11 +416,17 @@ __global__ __launch_bounds__(256) void k_seed_terms(int32_t n, const int64_t *__
     const double *x = X + (size_t)tile * (size_t)n * G + k;
     const int64_t p0 = in_ptr[s], deg = in_ptr[s + 1] - p0;
     double *out = evterm + evoff[slot];
+    // nz (frontier steps): the tile's bitmap of the rows of X that hold a non-zero.  A row whose bit is clear is zero or
+    // stale and is never read: its addend is +0.0, what (1-d)*0*w gives with non-negative weights
+    if (nz) nz += (size_t)tile * (((size_t)n + 31) / 32);
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < deg; q += (int64_t)gridDim.x * blockDim.x) {
-        if (VF) {
-            out[q] = x[(size_t)in_src[p0 + q] * G];
+        const int32_t i = in_src[p0 + q];
+        if (nz && !((nz[(uint32_t)i >> 5] >> (i & 31)) & 1u)) {
+            out[q] = 0.0;
+        } else if (VF) {
+            out[q] = x[(size_t)i * G];
         } else {
-            const double rw = c1 * x[(size_t)in_src[p0 + q] * G];
+            const double rw = c1 * x[(size_t)i * G];
             out[q] = rw * in_w[p0 + q];
         }
     }
@@ -573,6 +649,8 @@ __global__ __launch_bounds__(WAVE + CH3_NST) void k_seed_chain_roles(
 
 // Model ctor, Model.cs:42-49: rank[seed] = nNodes, everything else 0
 // (value-free path: Z receives the seed's z, ((1-d) n) * w_src[seed])
+// Each seed row is written whole -- n in the lanes whose seed it is, 0 in the others -- so that it is valid even where the
+// matrix was not cleared (Z on the frontier-list path).  Slots that share a seed row write the same values.
 __global__ void k_init_seeds(int32_t n, int ntiles, int G, double *__restrict__ X,
                              const int32_t *__restrict__ seeds, uint32_t *__restrict__ nz,
                              double *__restrict__ Z = nullptr, const double *__restrict__ w_src = nullptr, double c1 = 0.0)
@@ -581,9 +659,16 @@ __global__ void k_init_seeds(int32_t n, int ntiles, int G, double *__restrict__ 
     if (q >= ntiles * G) return;
     const int32_t s = seeds[q];
     if (s < 0) return;
-    X[(size_t)(q / G) * (size_t)n * G + (size_t)s * G + (q % G)] = (double)n;
-    if (Z) { const double rw = c1 * (double)n; Z[(size_t)(q / G) * (size_t)n * G + (size_t)s * G + (q % G)] = rw * w_src[s]; }
-    if (nz) atomicOr(&nz[(size_t)(q / G) * (((size_t)n + 31) / 32) + ((uint32_t)s >> 5)], 1u << (s & 31));
+    const int tile = q / G;
+    const size_t row = (size_t)tile * (size_t)n * G + (size_t)s * G;
+    const double rw = c1 * (double)n;
+    const double zs = Z ? rw * w_src[s] : 0.0;
+    for (int kk = 0; kk < G; ++kk) {
+        const bool mine = seeds[tile * G + kk] == s;
+        X[row + kk] = mine ? (double)n : 0.0;
+        if (Z) Z[row + kk] = mine ? zs : 0.0;
+    }
+    if (nz) atomicOr(&nz[(size_t)tile * (((size_t)n + 31) / 32) + ((uint32_t)s >> 5)], 1u << (s & 31));
 }
 
 // Recommender.cs:20-24,29: the seed's RAW out-links of type LIKE are not candidates.
@@ -714,20 +799,42 @@ static void launch_spmm(rwr_graph *g, int tg, const double *X, double *Y, const 
         hipLaunchKernelGGL((k_spmm<G, false>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p, g->in_w.p,
                            rows, nrows, GS, Y, seeds, c1, skip, g->w_src.p, Zout);
 }
+// Frontier-list step: the SpMM over each tile's own row list, whose length only the device knows.  The
+// grid is sized for a list of a tenth of the rows (the lists of C4's frontier steps hold 0.05 % and 4 %); the launch
+// strides over longer ones.
+template <int G>
+static void launch_spmm_frontier(rwr_graph *g, int tg, const double *X, double *Y, const int32_t *seeds, double c1,
+                                 const uint32_t *nz_in, uint32_t *nz_out, hipStream_t s, const int32_t *fl_rows,
+                                 const int32_t *fl_cnt, const double *Zin, double *Zout)
+{
+    if constexpr (G >= 8) {
+        constexpr int RPW = WAVE / G;
+        constexpr int CH = G > 16 ? 16 : G;
+        const unsigned want = cdiv((size_t)g->n / 10 + 1, (size_t)RPW * 4);
+        const unsigned gx = want < 1u ? 1u : want < 2048u ? want : 2048u;
+        if (Zin)
+            hipLaunchKernelGGL((k_spmm_frontier<G, CH, true>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p,
+                               g->in_w.p, fl_rows, fl_cnt, Zin, Y, seeds, c1, 1, nz_in, nz_out, g->w_src.p, Zout);
+        else
+            hipLaunchKernelGGL((k_spmm_frontier<G, CH, false>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p,
+                               g->in_w.p, fl_rows, fl_cnt, X, Y, seeds, c1, 1, nz_in, nz_out, g->w_src.p, Zout);
+    }
+}
 template <int G>
 // the addends of the links into the seeds; tiny, runs on the MAIN stream ahead of the fork so that the chain kernel is
 // the first thing its stream has to dispatch once the fork event fires (it must get its CUs before the SpMM's
 // half-million workgroups flood the dispatcher, or it only starts when the SpMM drains)
+// (nz: the frontier bitmap of X, when X may hold stale rows -- DESIGN §3.3.2)
 static void launch_seed_terms(rwr_graph *g, int tg, const double *X, const int32_t *seeds, double c1,
-                              const int64_t *evoff, hipStream_t s, const double *Zin)
+                              const int64_t *evoff, hipStream_t s, const double *Zin, const uint32_t *nz = nullptr)
 {
     const unsigned term_blocks = g->max_in_deg > 256 * 8 ? 8u : cdiv((size_t)(g->max_in_deg > 0 ? g->max_in_deg : 1), 256);
     if (Zin)
         hipLaunchKernelGGL((k_seed_terms<G, true>), dim3(term_blocks, tg * G), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p,
-                           g->in_w.p, Zin, seeds, c1, evoff, g->d_evterm.p);
+                           g->in_w.p, Zin, seeds, c1, evoff, g->d_evterm.p, nz);
     else
         hipLaunchKernelGGL((k_seed_terms<G, false>), dim3(term_blocks, tg * G), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p,
-                           g->in_w.p, X, seeds, c1, evoff, g->d_evterm.p);
+                           g->in_w.p, X, seeds, c1, evoff, g->d_evterm.p, nz);
 }
 template <int G>
 static void launch_chain(rwr_graph *g, int tg, const double *X, double *Y, const int32_t *seeds, double c1,
@@ -824,6 +931,7 @@ struct GroupIter {
     int act_iters = 0;   // iterations whose SpMM only visits the out-neighbours of non-zero rows
     int64_t dense_steps = 0;   // steps whose SpMM walked every row (no frontier bitmap)
     bool addends_nonneg = false;   // weights, ranks and 1-d all >= 0 and finite: exact parallel reductions are allowed
+    bool flist = false;  // frontier-list steps allowed: Z is not cleared, rows outside the bitmaps may be stale
 
     GroupIter(rwr_graph *g_, int G_, int tg_, const int32_t *seeds, const int64_t *evoff, double d)
         : g(g_), G(G_), tg(tg_), d_seeds(seeds), d_evoff(evoff), c1(1 - d) /* Model.cs:84: (1 - dampingFactor) */,
@@ -831,13 +939,13 @@ struct GroupIter {
 
     // fresh = Model ctor (rank = n at the seed, 0 elsewhere);  !fresh = X already holds a caller-supplied rank vector
     // (Model.deliverRanks called on its own): no frontier knowledge, and the binade scan only if those ranks are >= 0
-    int32_t init(bool fresh = true, bool ranks_nonneg = true)
+    // allow_flist: the caller (iterate_group) may run frontier-list steps, see step()
+    int32_t init(bool fresh = true, bool ranks_nonneg = true, bool allow_flist = false)
     {
         const int32_t n = g->n;
         hipStream_t s = g->stream;
         const size_t elems = (size_t)tg * (size_t)n * G;
         if (fresh) RWR_HIP(hipMemsetAsync(X, 0, elems * sizeof(double), s));
-        if (fresh && Zc) RWR_HIP(hipMemsetAsync(Zc, 0, elems * sizeof(double), s));
         if (!fresh && Zc) hipLaunchKernelGGL(k_make_z, dim3(cdiv(elems, 256)), dim3(256), 0, s, (int64_t)elems, G, X, Zc, g->w_src.p, c1);
         // frontier bitmaps for the first iterations (chunked SpMM only)
         static const int nz_iters_env = [] { const char *e = RWR_TUNE_ENV("RWR_NZ_ITERS"); return e ? atoi(e) : 4; }();
@@ -860,6 +968,16 @@ struct GroupIter {
         if (G == 1 && tg == 1 && act_env < 0 && n < act_min_n) nz_iters = act_iters = 0;
         if (!fresh) nz_iters = act_iters = 0;
         const size_t nzw = ((size_t)n + 31) / 32;
+        // frontier-list steps need a bitmap-checking step after each of them (nz_iters >= 2) and a per-tile row list
+        static const int flist_env = [] { const char *e = getenv("RWR_FRONTIER_LIST"); return e ? atoi(e) : 1; }();
+        flist = allow_flist && fresh && flist_env != 0 && G >= 8 && nz_iters >= 2 && act_iters >= 1;
+        if (flist && g->fl_rows.ensure((size_t)tg * (size_t)n + (size_t)tg) != RWR_OK) {
+            (void)hipGetLastError();   // (no room for the lists: the bitmap-probing steps of before, which need none)
+            flist = false;
+        }
+        // Z is read only through the frontier bitmaps until a step has written it whole: on the frontier-list path the
+        // seed rows (k_init_seeds) are all of it that must be valid
+        if (fresh && Zc && !flist) RWR_HIP(hipMemsetAsync(Zc, 0, elems * sizeof(double), s));
         nz_cur = nz_iters > 0 ? g->d_nz.p : nullptr;
         nz_oth = nz_iters > 0 ? g->d_nz.p + (size_t)tg * nzw : nullptr;
         if (nz_cur) RWR_HIP(hipMemsetAsync(nz_cur, 0, (size_t)tg * nzw * sizeof(uint32_t), s));
@@ -892,8 +1010,9 @@ struct GroupIter {
     // last = no further step follows: the value-free path need not form the next z
     // rows != nullptr: the SpMM produces only the nrows rows of that list (a batch's last two steps);
     // chain = false: no seed row of this step is read afterwards, its chain is not run
+    // may_list: the caller allows this step to write only its frontier's rows (it is neither a tail-list step nor the last)
     int32_t step(EvPool &pool, std::vector<hipEvent_t> &spmm_ev, std::vector<hipEvent_t> &chain_ev, bool last = false,
-                 const int32_t *rows = nullptr, int32_t nrows = 0, bool chain = true)
+                 const int32_t *rows = nullptr, int32_t nrows = 0, bool chain = true, bool may_list = false)
     {
         const int32_t n = g->n;
         hipStream_t s = g->stream, s2 = g->stream2;
@@ -907,11 +1026,23 @@ struct GroupIter {
         uint32_t *nz_out = (it + 1 < nz_iters) ? nz_oth : nullptr;
         if (nz_out) RWR_HIP(hipMemsetAsync(nz_out, 0, (size_t)tg * nzw * sizeof(uint32_t), s));
         uint32_t *act = (nz_in && it < act_iters) ? g->d_nz.p + 2 * (size_t)tg * nzw : nullptr;
+        // Frontier-list step: the SpMM writes only the rows of its frontier, and every other row of Y / Zn
+        // keeps whatever it held.  Allowed where the next step reads the output only through the bitmap this step writes:
+        // that step probes it (it + 1 < nz_iters) and either is itself an act step (bitmap-walking seed-row chain) or, at
+        // it = 1, writes over the cleared X_0, whose only non-zero rows -- the seed rows -- are in the list, so that its
+        // output is a whole vector for the chains that read every row.
+        const bool list_now = flist && act && may_list && !rows && !last && it + 1 < nz_iters &&
+                              (it + 1 < act_iters || it == 1);
+        int32_t *fl_rows = list_now ? g->fl_rows.p : nullptr;
+        int32_t *fl_cnt = list_now ? g->fl_rows.p + (size_t)tg * (size_t)n : nullptr;
         if (act) {
             RWR_HIP(hipMemsetAsync(act, 0, (size_t)tg * nzw * sizeof(uint32_t), s));
+            if (fl_cnt) RWR_HIP(hipMemsetAsync(fl_cnt, 0, (size_t)tg * sizeof(int32_t), s));
             hipLaunchKernelGGL(k_mark_active, dim3(cdiv(nzw, 4), tg), dim3(256), 0, s, n, nz_in, act, g->rowptr.p,
-                               g->dst.p, g->etype.p);
+                               g->dst.p, g->etype.p, G, d_seeds, fl_rows, fl_cnt);
         }
+        // rows of X / Zc outside the bitmap may be stale: the seed-row terms read through it (exact for zero rows as well)
+        const uint32_t *nz_terms = flist ? nz_in : nullptr;
         if (serial) s2 = s;
         // (while X is sparse the bitmap-walking chain serves a whole tile at once; for a single seed the scan is cheaper)
         const bool scan_now = chain && scan && (!act || G == 1);
@@ -934,7 +1065,7 @@ struct GroupIter {
             // (a single seed per tile: the chain kernels gather the link terms from z themselves and leave the seed row's next z)
             const bool self = chain_scan_self_contained(G);
             seed_z_done = self;
-            if (!(self && Zc)) RWR_DISPATCH_G(G, launch_seed_terms<GG>(g, tg, X, d_seeds, c1, d_evoff, sc, Zc));
+            if (!(self && Zc)) RWR_DISPATCH_G(G, launch_seed_terms<GG>(g, tg, X, d_seeds, c1, d_evoff, sc, Zc, nz_terms));
             hipEvent_t c0 = nullptr, c1e = nullptr;
             if (prof) { c0 = pool.get(); c1e = pool.get(); RWR_HIP(hipEventRecord(c0, sc)); }
             RWR_TRY(chain_scan_step(g, G, tg, X, Y, d_seeds, d_evoff, c1, nz_out, sc, self ? Zc : nullptr,
@@ -944,7 +1075,7 @@ struct GroupIter {
             s2 = s;
         } else if (chain) {
             // fork: the seed-row chain runs beside the SpMM on the second stream
-            RWR_DISPATCH_G(G, launch_seed_terms<GG>(g, tg, X, d_seeds, c1, d_evoff, s, Zc));
+            RWR_DISPATCH_G(G, launch_seed_terms<GG>(g, tg, X, d_seeds, c1, d_evoff, s, Zc, nz_terms));
             gate_it = (use_gate && s2 != s) ? g->d_gate.p + (it % GATE_SLOTS) : nullptr;
             if (gate_it) RWR_HIP(hipMemsetAsync(gate_it, 0, sizeof(unsigned int), s));
             RWR_HIP(hipEventRecord(g->ev_fork, s));
@@ -962,7 +1093,11 @@ struct GroupIter {
         hipEvent_t a = nullptr, b = nullptr;
         if (prof) { a = pool.get(); b = pool.get(); RWR_HIP(hipEventRecord(a, s)); }
         double *zout = (Zc && !last) ? Zn : nullptr;
-        RWR_DISPATCH_G(G, launch_spmm<GG>(g, tg, X, Y, d_seeds, c1, 1, nz_in, nz_out, s, act, Zc, zout, addends_nonneg, rows, nrows));
+        if (list_now) {
+            RWR_DISPATCH_G(G, launch_spmm_frontier<GG>(g, tg, X, Y, d_seeds, c1, nz_in, nz_out, s, fl_rows, fl_cnt, Zc, zout));
+        } else {
+            RWR_DISPATCH_G(G, launch_spmm<GG>(g, tg, X, Y, d_seeds, c1, 1, nz_in, nz_out, s, act, Zc, zout, addends_nonneg, rows, nrows));
+        }
         // (a launch over a row list is no dense launch either: it walks only part of the matrix)
         const bool dense = !nz_in && !rows;
         if (prof) { RWR_HIP(hipEventRecord(b, s)); spmm_ev.push_back(a); spmm_ev.push_back(b); g->spmm_ev_dense.push_back(dense ? 1 : 0); }
@@ -976,6 +1111,7 @@ struct GroupIter {
         { uint32_t *tz = nz_cur; nz_cur = nz_oth; nz_oth = tz; }
         g->stats.spmm_launches += 1;
         g->stats.chain_launches += chain ? 1 : 0;
+        g->stats.frontier_list_launches += list_now ? 1 : 0;
         ++it;
         return RWR_OK;
     }
@@ -988,7 +1124,7 @@ int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const
                       std::vector<hipEvent_t> &chain_ev, int64_t *dense_steps, bool rank_only = false, bool item_seed = true)
 {
     GroupIter gi(g, G, tg, d_seeds, d_evoff, d);
-    RWR_TRY(gi.init());
+    RWR_TRY(gi.init(true, true, true));
     static const int tail_env = [] { const char *e = getenv("RWR_TAIL_ROWS"); return e ? atoi(e) : 1; }();
     // (one seed on its own takes the single-seed SpMV, whose rows stay all rows)
     const bool tails = rank_only && tail_env != 0 && !(G == 1 && tg == 1);
@@ -1006,7 +1142,7 @@ int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const
             // would fold the restart addend of EVERY row of this step's ranks, so with an ITEM seed this step stays whole
             rows = g->tail_rows[1].p; nrows = g->tail_n[1];
         }
-        RWR_TRY(gi.step(pool, spmm_ev, chain_ev, left == 1, rows, nrows, chain));
+        RWR_TRY(gi.step(pool, spmm_ev, chain_ev, left == 1, rows, nrows, chain, !rows && left >= 2));
     }
     *final_X = gi.X;
     *dense_steps = gi.dense_steps;
@@ -1583,7 +1719,8 @@ static int32_t part_spmm(rwr_graph *g, const double *x, double *y, hipStream_t s
             const int64_t first = (int64_t)g->part_lo & ~(int64_t)63;
             hipLaunchKernelGGL(k_make_z_nz, dim3(cdiv((size_t)((int64_t)g->part_hi - first), 256)), dim3(256), 0, s, g->part_lo, g->part_hi, G, x,
                                g->Z0.p, g->w_src.p, c1, nz);
-            if (mark) hipLaunchKernelGGL(k_mark_active, dim3(cdiv(nzw, 4), 1), dim3(256), 0, s, g->n, nz, act, g->rowptr.p, g->dst.p, g->etype.p);
+            if (mark) hipLaunchKernelGGL(k_mark_active, dim3(cdiv(nzw, 4), 1), dim3(256), 0, s, g->n, nz, act, g->rowptr.p, g->dst.p, g->etype.p,
+                                         0, nullptr, nullptr, nullptr);
             RWR_DISPATCH_G(G, launch_spmm<GG>(g, 1, x, y, g->d_seeds.p, c1, 0, nz, nullptr, s, mark ? act : nullptr, zin, nullptr, false));
             return RWR_OK;
         }
