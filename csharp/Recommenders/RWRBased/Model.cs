@@ -2,7 +2,7 @@
 // the GPU through rwr_model_run and leave the result in `rank` exactly as the reference does; deliverRanks() is one
 // propagation on the GPU (rwr_model_deliver), updateRanks()/checkConvergence() are the reference's array loops.
 // A host-edited `restart` (a public field of the reference, Model.cs:12) takes rwr_model_run_restart /
-// rwr_model_deliver_restart instead.
+// rwr_model_deliver_restart instead.  The static RunBatch (an addition) runs many seeds' models in one rwr_model_run_batch call.
 namespace Recommenders.RWRBased {
     public class Model {
         public Graph graph;
@@ -66,6 +66,30 @@ namespace Recommenders.RWRBased {
         public void run() { Run(2, 0); }
         public void run(double threshold) { Run(1, threshold); }
         public void run(int nIterations) { Run(0, nIterations); }
+
+        // K personalised models in one call (rwr_model_run_batch), an addition beside the reference surface: ranks[k] and
+        // iterations[k] are what new Model(graph, dampingFactor, seeds[k]).run(...) leaves in rank / its step count
+        public static double[][] RunBatch(Graph graph, double dampingFactor, int[] seeds, int nIterations, out long[] iterations) {
+            return RunBatch(graph, dampingFactor, seeds, 0, nIterations, out iterations);
+        }
+        public static double[][] RunBatch(Graph graph, double dampingFactor, int[] seeds, double threshold, out long[] iterations) {
+            return RunBatch(graph, dampingFactor, seeds, 1, threshold, out iterations);
+        }
+        public static double[][] RunBatch(Graph graph, double dampingFactor, int[] seeds, out long[] iterations) {
+            return RunBatch(graph, dampingFactor, seeds, 2, 0, out iterations);
+        }
+        static double[][] RunBatch(Graph graph, double dampingFactor, int[] seeds, int mode, double value, out long[] iterations) {
+            int K = seeds.Length, n = graph.size();
+            var flat = new double[(long)K * n];
+            iterations = new long[K];
+            Native.Check(Native.rwr_model_run_batch(graph.handle, seeds, K, dampingFactor, mode, value, flat, iterations));
+            var ranks = new double[K][];
+            for (int k = 0; k < K; k++) {
+                ranks[k] = new double[n];
+                System.Array.Copy(flat, (long)k * n, ranks[k], 0, n);
+            }
+            return ranks;
+        }
 
         // `restart` is a public field of the reference: true when the host has edited it (then the *_restart entry points
         // run; the constructors' one-hot / uniform vectors keep the seed / global paths), as the Python mirror decides

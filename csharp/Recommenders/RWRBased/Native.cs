@@ -55,6 +55,10 @@ namespace Recommenders.RWRBased {
 
         [DllImport(Lib)] public static extern int rwr_model_deliver(GraphHandle g, int seed, double d, double[] rank, double[] next_rank);
 
+        // K personalised Models in one call: rank_out is K x n row-major, iters_out K counts (Model.RunBatch)
+        [DllImport(Lib)] public static extern int rwr_model_run_batch(GraphHandle g, int[] seeds, int K, double d, int run_mode,
+            double value, double[] rank_out, long[] iters_out);
+
         [DllImport(Lib)] public static extern int rwr_model_run_restart(GraphHandle g, double[] restart, double[] rank_in, double d,
             int run_mode, double value, double[] rank_out, out long iters_out);
 

@@ -158,6 +158,18 @@ public:
         restart.assign(nNodes, 0.0);
         if (targetNode >= 0 && targetNode < nNodes) { rank[targetNode] = nNodes; restart[targetNode] = 1.0; }
     }
+    // K personalised models in one call (rwr_model_run_batch), an addition beside the reference surface: ranks[k] /
+    // iterations[k] are what Model(g, d, seeds[k]).run(...) leaves in rank / iterations; run(int) / run(double) / run() arguments
+    static std::vector<std::vector<double>> runBatch(Graph &g, double d, const std::vector<int> &seeds, int nIterations,
+                                                     std::vector<int64_t> *iterations = nullptr)
+    { return runBatch_(g, d, seeds, RWR_RUN_ITERATIONS, nIterations, iterations); }
+    static std::vector<std::vector<double>> runBatch(Graph &g, double d, const std::vector<int> &seeds, double threshold,
+                                                     std::vector<int64_t> *iterations = nullptr)
+    { return runBatch_(g, d, seeds, RWR_RUN_THRESHOLD, threshold, iterations); }
+    static std::vector<std::vector<double>> runBatch(Graph &g, double d, const std::vector<int> &seeds,
+                                                     std::vector<int64_t> *iterations = nullptr)
+    { return runBatch_(g, d, seeds, RWR_RUN_DEFAULT_THRESHOLD, 0, iterations); }
+
     void run() { run_(RWR_RUN_DEFAULT_THRESHOLD, 0); }         // :52-55
     void run(double threshold) { run_(RWR_RUN_THRESHOLD, threshold); }   // :57-66
     void run(int nIterations) { run_(RWR_RUN_ITERATIONS, nIterations); } // :68-73
@@ -185,6 +197,19 @@ public:
 
 private:
     int seed_;
+    static std::vector<std::vector<double>> runBatch_(Graph &g, double d, const std::vector<int> &seeds, int run_mode,
+                                                      double value, std::vector<int64_t> *iterations)
+    {
+        const int32_t K = (int32_t)seeds.size();
+        const size_t n = (size_t)g.size();
+        std::vector<double> flat((size_t)K * n);
+        std::vector<int64_t> it((size_t)K);
+        check(rwr_model_run_batch(g.handle(), seeds.data(), K, d, run_mode, value, flat.data(), it.data()));
+        std::vector<std::vector<double>> ranks((size_t)K);
+        for (int32_t k = 0; k < K; ++k) ranks[k].assign(flat.begin() + (ptrdiff_t)(k * n), flat.begin() + (ptrdiff_t)((k + 1) * n));
+        if (iterations) *iterations = it;
+        return ranks;
+    }
     bool ctor_state_() const
     {
         for (int i = 0; i < nNodes; ++i) {

@@ -100,7 +100,8 @@ typedef struct rwr_stats {
                                 power-iteration step of one seed                                */
     double  chain_ms;        /* seed-row kernels (sequential fold or binade scan)                */
     int64_t chain_launches;
-    double  rank_ms;         /* exclusion mask + top-k / sort + gather                          */
+    double  rank_ms;         /* exclusion mask + top-k / sort + gather (rwr_model_run_batch: the
+                                extraction of finished columns into row-major staging)          */
     double  iterate_wall_ms; /* device time from the first to the last event of the iterate
                                 phase (SpMM and seed-row kernels overlapped)                    */
     double  total_wall_ms;   /* host wall time inside rwr_recommend* calls                      */
@@ -247,6 +248,20 @@ int32_t rwr_recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float
  * iters_out (optional) the number of deliverRanks() calls made. */
 int32_t rwr_model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double value,
                       double *rank_out, int64_t *iters_out);
+/* K personalised Models (Model.cs:33-50) run in one call -- an addition beside the reference surface (every Model is
+ * independent, Recommender.cs:16): row k of rank_out (K x n, row-major) and iters_out[k] are bitwise what
+ * rwr_model_run(g, seeds[k], d, run_mode, value, ...) returns, for every run_mode, graph and damping factor that
+ * rwr_model_run accepts (negative weights and d outside [0, 1] included: those run seed by seed).
+ *   - Threshold modes: each seed stops at its own convergence step (the same diff < threshold test, Model.cs:58-65) and
+ *     its row is the rank after that step.  A seed that does not converge within RWR_MAX_ITERS fails the whole call with
+ *     RWR_E_UNSUPPORTED, as rwr_model_run does.
+ *   - Argument errors, before any device work: K == 0 is a no-op (RWR_OK); K < 0, a NULL g, NULL seeds or NULL rank_out
+ *     (K > 0) or an unknown run_mode give RWR_E_INVALID; a seed outside [0, n) -- -1 included: the global model stays on
+ *     rwr_model_run -- gives RWR_E_RANGE with its batch position in the message.
+ *   - Duplicate and dangling seeds are allowed.  iters_out may be NULL.
+ *   - opts.tile_seeds, tile_group and workspace_bytes keep their meaning (the seeds run as tiles of the batched SpMM). */
+int32_t rwr_model_run_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t run_mode,
+                            double value, double *rank_out, int64_t *iters_out);
 /* ONE Model.deliverRanks() (Model.cs:76-100) on a rank vector held by the caller: next_rank = what the reference would
  * leave in nextRank (which updateRanks() has zeroed before, Model.cs:103-108) for the given rank.  Backs the public
  * step-by-step API -- deliverRanks / updateRanks / checkConvergence (Model.cs:76,103,110) -- for a host that drives the

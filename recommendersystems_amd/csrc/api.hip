@@ -825,6 +825,28 @@ int32_t rwr_model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, do
     return RWR_OK;
 }
 
+int32_t rwr_model_run_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t run_mode, double value,
+                            double *rank_out, int64_t *iters_out)
+{
+    g_err[0] = 0;
+    if (!g || K < 0 || (K > 0 && (!seeds || !rank_out))) {
+        set_error("rwr_model_run_batch: NULL argument or negative K");
+        return RWR_E_INVALID;
+    }
+    if (run_mode != RWR_RUN_ITERATIONS && run_mode != RWR_RUN_THRESHOLD && run_mode != RWR_RUN_DEFAULT_THRESHOLD) {
+        set_error("rwr_model_run_batch: unknown run_mode %d", run_mode);
+        return RWR_E_INVALID;
+    }
+    for (int32_t k = 0; k < K; ++k)
+        if (seeds[k] < 0 || seeds[k] >= g->n) {   // (-1, the global model, stays on rwr_model_run)
+            set_error("rwr_model_run_batch: seed %d (batch position %d) is outside [0, %d)", seeds[k], k, g->n);
+            return RWR_E_RANGE;
+        }
+    if (K == 0) return RWR_OK;
+    RWR_BIND(g);
+    return model_run_batch(g, seeds, K, d, run_mode, value, rank_out, iters_out);
+}
+
 int32_t rwr_model_run_restart(rwr_graph *g, const double *restart, const double *rank_in, double d, int32_t run_mode,
                               double value, double *rank_out, int64_t *iters_out)
 {

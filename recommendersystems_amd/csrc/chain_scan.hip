@@ -367,8 +367,10 @@ __global__ __launch_bounds__(64) void k_cs_carry(int32_t n, int nchunks, const u
                                                  const int32_t *__restrict__ e_pred, const long long *__restrict__ d0,
                                                  const long long *__restrict__ d1, uint32_t *__restrict__ nz_out,
                                                  unsigned long long *__restrict__ redo_count, int direct,
-                                                 double *__restrict__ zout = nullptr, const double *__restrict__ w_src = nullptr)
+                                                 double *__restrict__ zout = nullptr, const double *__restrict__ w_src = nullptr,
+                                                 double *__restrict__ sums = nullptr)
 {
+    // sums != nullptr: the sum goes to sums[slot] instead of Y (the G-wide checkConvergence, chain_scan_sum_cols)
     const int slot = blockIdx.x, lane = threadIdx.x;
     const int tile = slot / G, k = slot % G;
     const int32_t sd = seeds[slot];
@@ -382,7 +384,8 @@ __global__ __launch_bounds__(64) void k_cs_carry(int32_t n, int nchunks, const u
         for (int c = 0; c < nchunks; ++c)
             s = cs_redo_block<G>(s, n, nchunks, c, tile, k, dangling, X, seeds, c1, in_ptr, in_src, evoff, evterm, lnk);
         if (lane == 0) {
-            Y[(size_t)tile * (size_t)n * G + (size_t)sd * G + k] = s;
+            if (sums) sums[slot] = s;
+            else Y[(size_t)tile * (size_t)n * G + (size_t)sd * G + k] = s;
             if (zout) { const double rw = c1 * s; zout[(size_t)tile * (size_t)n * G + (size_t)sd * G + k] = rw * w_src[sd]; }   // Model.cs:84,87
             if (nz_out && s != 0.0)
                 atomicOr(&nz_out[(size_t)tile * (((size_t)n + 31) / 32) + ((uint32_t)sd >> 5)], 1u << (sd & 31));
@@ -446,7 +449,8 @@ __global__ __launch_bounds__(64) void k_cs_carry(int32_t n, int nchunks, const u
     }
 #undef CS_LOAD
     if (lane == 0) {
-        Y[(size_t)tile * (size_t)n * G + (size_t)sd * G + k] = s;
+        if (sums) sums[slot] = s;
+        else Y[(size_t)tile * (size_t)n * G + (size_t)sd * G + k] = s;
         if (nz_out && s != 0.0)
             atomicOr(&nz_out[(size_t)tile * (((size_t)n + 31) / 32) + ((uint32_t)sd >> 5)], 1u << (sd & 31));
         if (redo_count && redo) atomicAdd(redo_count, (unsigned long long)redo);
@@ -931,7 +935,8 @@ __global__ __launch_bounds__(64) void k_cs_carry1(int32_t n, int nchunks, const 
                                                   const int32_t *__restrict__ ek, const long long *__restrict__ d0,
                                                   const long long *__restrict__ d1, const double *__restrict__ side,
                                                   uint32_t *__restrict__ nz_out, unsigned long long *__restrict__ redo_count,
-                                                  double *__restrict__ zout, const double *__restrict__ w_src)
+                                                  double *__restrict__ zout, const double *__restrict__ w_src,
+                                                  double *__restrict__ sums = nullptr)
 {
     const int slot = blockIdx.x, lane = threadIdx.x;
     const int32_t sd = seeds[slot];
@@ -1075,7 +1080,8 @@ __global__ __launch_bounds__(64) void k_cs_carry1(int32_t n, int nchunks, const 
                (double)(__builtin_amdgcn_s_memrealtime() - t_begin) * 0.01, (double)t_redo * 0.01);
 #endif
     if (lane == 0) {
-        Y[(size_t)slot * (size_t)n + (size_t)sd] = s;
+        if (sums) sums[slot] = s;
+        else Y[(size_t)slot * (size_t)n + (size_t)sd] = s;
         // value-free path: the seed row's own z for the next step (the SpMV leaves the seed's row alone)
         if (zout) { const double rw = c1 * s; zout[(size_t)slot * (size_t)n + (size_t)sd] = rw * w_src[sd]; }   // Model.cs:84,87
         if (nz_out && s != 0.0) atomicOr(&nz_out[(size_t)slot * (((size_t)n + 31) / 32) + ((uint32_t)sd >> 5)], 1u << (sd & 31));
@@ -1124,7 +1130,7 @@ int32_t chain_scan_prepare(rwr_graph *g, int G, int tg, const int32_t *d_seeds, 
 // one step's seed-row chain for a tile group (the link terms d_evterm must already be on the stream)
 static int32_t chain_scan_launch(rwr_graph *g, int G, int tg, const double *X, double *Y, const int32_t *d_seeds,
                                  const int64_t *d_evoff, double c1, uint32_t *nz_out, const int32_t *lnk, hipStream_t s,
-                                 const double *zterms = nullptr, double *zout = nullptr);
+                                 const double *zterms = nullptr, double *zout = nullptr, double *sums = nullptr);
 
 static bool cs_split_enabled()
 {
@@ -1166,9 +1172,39 @@ int32_t chain_scan_sum(rwr_graph *g, const double *D, double *out, hipStream_t s
     return chain_scan_launch(g, 1, 1, D, out, g->cs_lnk0.p + nchunks + 1, g->d_evoff.p, 0.0, nullptr, g->cs_lnk0.p, s);
 }
 
+// The same, G columns per tile and tg tiles at once (K Models in one call, rwr_model_run_batch): D is a tile group's
+// [tile][n][G] matrix of |rank - nextRank|, every slot's "seed" is node 0 and its link table is all zero, so that column k
+// of tile t is summed in row order by slot t * G + k; the carry writes the sum to sums[t * G + k] instead of a row of Y.
+// cs_lnk0 = [tg * G][nchunks + 1] zero link counts, then tg * G zero seeds.
+int32_t chain_scan_sum_cols_prepare(rwr_graph *g, int G, int tg, hipStream_t s)
+{
+    const int nchunks = cs_nchunks(g->n, G);
+    const size_t slots = (size_t)tg * G, cells = slots * nchunks;
+    RWR_TRY(g->cs_approx.ensure(cells));
+    RWR_TRY(g->cs_e.ensure(cells));
+    RWR_TRY(g->cs_d0.ensure(cells));
+    RWR_TRY(g->cs_d1.ensure(cells));
+    if (G == 1) RWR_TRY(g->cs_side.ensure(cells * CS_SIDE_WORDS));
+    if (G == 1) RWR_TRY(g->cs_mx.ensure((size_t)tg * (size_t)(CsGeom<1>::CH + CS_MX_LINKS)));
+    const size_t words = slots * ((size_t)nchunks + 1) + slots;
+    RWR_TRY(g->cs_lnk0.ensure(words));
+    if (!g->cs_redo.p) {
+        RWR_TRY(g->cs_redo.alloc(1));
+        RWR_HIP(hipMemsetAsync(g->cs_redo.p, 0, sizeof(unsigned long long), s));
+    }
+    RWR_HIP(hipMemsetAsync(g->cs_lnk0.p, 0, words * sizeof(int32_t), s));
+    return RWR_OK;
+}
+int32_t chain_scan_sum_cols(rwr_graph *g, int G, int tg, const double *D, const int64_t *evoff, double *sums, hipStream_t s)
+{
+    const size_t slots = (size_t)tg * G;
+    const int32_t *zero_seeds = g->cs_lnk0.p + slots * ((size_t)cs_nchunks(g->n, G) + 1);
+    return chain_scan_launch(g, G, tg, D, nullptr, zero_seeds, evoff, 0.0, nullptr, g->cs_lnk0.p, s, nullptr, nullptr, sums);
+}
+
 static int32_t chain_scan_launch(rwr_graph *g, int G, int tg, const double *X, double *Y, const int32_t *d_seeds,
                                  const int64_t *d_evoff, double c1, uint32_t *nz_out, const int32_t *lnk, hipStream_t s,
-                                 const double *zterms, double *zout)
+                                 const double *zterms, double *zout, double *sums)
 {
     const int nchunks = cs_nchunks(g->n, G);
     const dim3 grid((unsigned)nchunks, (unsigned)tg);
@@ -1193,7 +1229,7 @@ static int32_t chain_scan_launch(rwr_graph *g, int G, int tg, const double *X, d
         CS_DISPATCH_G(G, hipLaunchKernelGGL(k_cs_carry<GG>, dim3((unsigned)(tg * G)), dim3(64), 0, s, g->n, nchunks, g->dangling.p, X, Y,
                                             d_seeds, c1, g->in_ptr.p, g->in_src.p, evo, evt, lnk,
                                             g->cs_approx.p, g->cs_e.p, g->cs_d0.p, g->cs_d1.p, nz_out, g->cs_redo.p, 1,
-                                            self ? zout : (double *)nullptr, g->w_src.p));
+                                            self ? zout : (double *)nullptr, g->w_src.p, sums));
         RWR_HIP(hipGetLastError());
         return RWR_OK;
     }
@@ -1209,7 +1245,7 @@ static int32_t chain_scan_launch(rwr_graph *g, int G, int tg, const double *X, d
                            evo, evt, lnk, g->cs_approx.p, g->cs_e.p, g->cs_d0.p, g->cs_d1.p, g->cs_side.p, own_sums, g->cs_mx.p);
         hipLaunchKernelGGL(k_cs_carry1, dim3((unsigned)tg), dim3(64), 0, s, g->n, nchunks, g->dangling.p, X, Y, d_seeds, c1, g->in_ptr.p,
                            g->in_src.p, evo, evt, lnk, g->cs_approx.p, g->cs_e.p, g->cs_d0.p, g->cs_d1.p, g->cs_side.p, nz_out,
-                           g->cs_redo.p, zout, g->w_src.p);
+                           g->cs_redo.p, zout, g->w_src.p, sums);
         RWR_HIP(hipGetLastError());
         return RWR_OK;
     }
@@ -1222,7 +1258,8 @@ static int32_t chain_scan_launch(rwr_graph *g, int G, int tg, const double *X, d
                                         g->cs_e.p, (double *)nullptr, g->cs_d0.p, g->cs_d1.p));
     CS_DISPATCH_G(G, hipLaunchKernelGGL(k_cs_carry<GG>, dim3((unsigned)(tg * G)), dim3(64), 0, s, g->n, nchunks, g->dangling.p, X, Y,
                                         d_seeds, c1, g->in_ptr.p, g->in_src.p, d_evoff, g->d_evterm.p, lnk,
-                                        g->cs_approx.p, g->cs_e.p, g->cs_d0.p, g->cs_d1.p, nz_out, g->cs_redo.p, 0));
+                                        g->cs_approx.p, g->cs_e.p, g->cs_d0.p, g->cs_d1.p, nz_out, g->cs_redo.p, 0,
+                                        (double *)nullptr, (const double *)nullptr, sums));
     RWR_HIP(hipGetLastError());
     return RWR_OK;
 }

@@ -112,7 +112,10 @@ struct rwr_graph {
     rwr::DevBuf<double> cs_mx;        // single seed: scratch row of the exact-start block's addend sequence
     rwr::DevBuf<int32_t> cs_lnk;
     rwr::DevBuf<int32_t> cs_lnk0;     // all-zero link table + slot for chain_scan_sum (checkConvergence)
-    rwr::DevBuf<double> cs_diff;      // |rank - nextRank| per node (checkConvergence)
+    rwr::DevBuf<double> cs_diff;      // |rank - nextRank| per node (checkConvergence); rwr_model_run_batch: [tile][n][G], the
+                                      // tile group's differences and, between steps, the row-major staging of extracted columns
+    rwr::DevBuf<double> cs_sums;      // rwr_model_run_batch: per (tile, slot) sum of the differences, the G-wide checkConvergence
+    rwr::DevBuf<int32_t> mb_row;      // rwr_model_run_batch: per (tile, slot) staging row of a column extracted now, -1 = none
     rwr::DevBuf<unsigned long long> cs_redo;   // blocks redone by the carry kernel (binade crossings + mispredictions)
     rwr::DevBuf<uint64_t> keys, keys_alt;
     rwr::DevBuf<uint32_t> vals, vals_alt;
@@ -184,6 +187,9 @@ int32_t part_rank(rwr_graph *g, double *x, int32_t top_n, int64_t *ids, double *
 int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double value, double *rank_out,
                   int64_t *iters_out);
 int32_t model_deliver(rwr_graph *g, int32_t seed, double d, const double *rank_in, double *next_out);
+// K personalised Models in one call (rwr_model_run_batch): row k of rank_out / iters_out[k] as model_run for seeds[k]
+int32_t model_run_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t run_mode, double value,
+                        double *rank_out, int64_t *iters_out);
 // restart.hip: Model with a caller-set restart vector (rwr_model_run_restart / rwr_model_deliver_restart)
 int32_t model_run_restart(rwr_graph *g, const double *v, const double *rank_in, double d, int32_t run_mode, double value,
                           double *rank_out, int64_t *iters_out);
@@ -226,6 +232,10 @@ int32_t chain_scan_step(rwr_graph *g, int G, int tg, const double *X, double *Y,
 bool chain_scan_self_contained(int G);   // G == 1: no k_seed_terms / k_seed_z launches around the step
 int32_t chain_scan_collect(rwr_graph *g, hipStream_t s);
 int32_t chain_scan_sum(rwr_graph *g, const double *D, double *out, hipStream_t s);   // exact sequential sum of n addends >= 0
+// ... of every column of a tile group's [tile][n][G] matrix of addends >= 0: sums[tile * G + k].  _prepare once per tile group
+// (scratch cells and the all-zero link table; evoff: the group's d_evoff slots, never dereferenced past their pointer)
+int32_t chain_scan_sum_cols_prepare(rwr_graph *g, int G, int tg, hipStream_t s);
+int32_t chain_scan_sum_cols(rwr_graph *g, int G, int tg, const double *D, const int64_t *evoff, double *sums, hipStream_t s);
 
 
 }  // namespace rwr

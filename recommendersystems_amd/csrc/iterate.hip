@@ -25,6 +25,7 @@
 #include <chrono>
 #include <climits>
 #include <cstdlib>
+#include <new>
 
 namespace rwr {
 
@@ -1149,21 +1150,28 @@ int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const
     return RWR_OK;
 }
 
-static int32_t ensure_workspace(rwr_graph *g, int G, int32_t K, int *TG_out)
+// extra_mats: further [tile][n][G] matrices the caller needs per tile (rwr_model_run_batch: the difference / staging matrix
+// in g->cs_diff), counted in the sizing so that a large graph shrinks the tile group instead of failing
+static int32_t ensure_workspace(rwr_graph *g, int G, int32_t K, int *TG_out, int extra_mats = 0)
 {
     const size_t n = (size_t)g->n;
     const int ntiles = (int)cdiv((size_t)K, (size_t)G);
+    // a model batch's difference / staging matrix (TG * n * G doubles) is given back before a call that needs none sizes its
+    // tile group, instead of holding memory that call would count as taken (model_run needs at most n of it, and re-takes them)
+    // (the stream is idle: every entry point synchronises before it returns)
+    if (!extra_mats && g->cs_diff.count > n) g->cs_diff.release();
     size_t cap = (size_t)g->opts.workspace_bytes;
     if (cap == 0) {
         size_t fr = 0, tot = 0;
         RWR_HIP(hipMemGetInfo(&fr, &tot));
         // what is already held by the rank matrices counts as available
         fr += (g->X.count + g->Y.count + g->Z0.count + g->Z1.count) * sizeof(double);
+        if (extra_mats) fr += g->cs_diff.count * sizeof(double);
         // three quarters of what is free go to the rank matrices; the rest stays for the buffers sized after them (frontier
         // bitmaps and seed slots below -- inside the retry loop --, chain-scan cells, ranking keys) and for other handles
         cap = fr / 2 + fr / 4;
     }
-    const size_t mats = g->vf ? 4 : 2;   // X, Y (+ the value-free path's z of the current and of the next ranks)
+    const size_t mats = (g->vf ? 4 : 2) + (size_t)extra_mats;   // X, Y (+ the value-free path's z of the current and of the next ranks)
     const size_t per_tile = mats * n * (size_t)G * sizeof(double);
     int TG = g->opts.tile_group > 0 ? g->opts.tile_group : (int)(cap / (per_tile ? per_tile : 1));
     if (TG < 1) TG = 1;
@@ -1181,6 +1189,7 @@ static int32_t ensure_workspace(rwr_graph *g, int G, int32_t K, int *TG_out)
             rc = g->Z0.ensure((size_t)TG * n * G);
             if (rc == RWR_OK) rc = g->Z1.ensure((size_t)TG * n * G);
         }
+        if (rc == RWR_OK && extra_mats) rc = g->cs_diff.ensure((size_t)TG * n * G);
         if (rc == RWR_OK) rc = g->d_seeds.ensure((size_t)ntiles * G);
         if (rc == RWR_OK) rc = g->d_nz.ensure(3 * (size_t)TG * ((n + 31) / 32));   // X, Y non-zero rows + active destination rows
         if (rc == RWR_OK) rc = g->d_gate.ensure(64);
@@ -1188,6 +1197,7 @@ static int32_t ensure_workspace(rwr_graph *g, int G, int32_t K, int *TG_out)
         if (rc != RWR_E_NOMEM || TG <= 1 || g->opts.tile_group > 0) return rc;
         (void)hipGetLastError();
         g->X.release(); g->Y.release(); g->Z0.release(); g->Z1.release(); g->d_nz.release();
+        if (extra_mats) g->cs_diff.release();
         TG = (TG + 1) / 2;
     }
     *TG_out = TG;
@@ -1480,6 +1490,13 @@ void launch_absdiff(const double *a, const double *b, int32_t n, double *out, hi
     hipLaunchKernelGGL(k_absdiff, dim3(cdiv((size_t)n, 256)), dim3(256), 0, s, a, b, n, out);
 }
 
+// threshold runs that have not converged after this many steps fail (RWR_MAX_ITERS, read once per process)
+static int64_t model_max_iters()
+{
+    static const int64_t v = [] { const char *e = getenv("RWR_MAX_ITERS"); return e ? atoll(e) : (int64_t)1000000; }();
+    return v;
+}
+
 int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double value, double *rank_out,
                   int64_t *iters_out)
 {
@@ -1495,7 +1512,7 @@ int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double
     hipStream_t s = g->stream;
     EvPool pool;
     std::vector<hipEvent_t> a, b;
-    static const int64_t max_iters = [] { const char *e = getenv("RWR_MAX_ITERS"); return e ? atoll(e) : (int64_t)1000000; }();
+    const int64_t max_iters = model_max_iters();
     const bool by_count = run_mode == RWR_RUN_ITERATIONS;
     // Model.cs:53: threshold = (1 / double.MaxValue) * n   (a subnormal-scale number: "until nothing changes")
     const double threshold = run_mode == RWR_RUN_DEFAULT_THRESHOLD ? (1 / 1.7976931348623157e308) * n : value;
@@ -1614,6 +1631,194 @@ int32_t model_deliver(rwr_graph *g, int32_t seed, double d, const double *rank_i
     RWR_HIP(hipMemcpyAsync(next_out, out, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     RWR_HIP(hipStreamSynchronize(s));
     return RWR_OK;
+}
+
+// ---- K personalised Models in one call (rwr_model_run_batch) -------------------------------------------
+
+// |rank - nextRank| of every element of a tile group's [tile][n][G] matrices (Model.cs:113): the addends of the G-wide
+// checkConvergence scan
+__global__ __launch_bounds__(256) void k_absdiff_mat(const double *__restrict__ a, const double *__restrict__ b, int64_t elems,
+                                                     double *__restrict__ d)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += (int64_t)gridDim.x * blockDim.x) {
+        const double x = a[i], y = b[i];
+        d[i] = (x > y) ? (x - y) : (y - x);
+    }
+}
+
+// Columns of a tile group's rank matrix X[tile][n][G] into row-major staging rows: slot (tile, k) with row_of[tile * G + k] =
+// j >= 0 goes to out[j * n ...].  A workgroup takes EX_ELEMS consecutive elements of one tile (EX_ELEMS / G whole rows),
+// reads them coalesced into LDS (row stride G + 1: a column walk hits distinct banks) and writes each selected column's
+// piece as one contiguous run.
+constexpr int EX_ELEMS = 2048;
+template <int G>
+__global__ __launch_bounds__(256) void k_extract_cols(int32_t n, const double *__restrict__ X, const int32_t *__restrict__ row_of,
+                                                      double *__restrict__ out)
+{
+    constexpr int ROWS = EX_ELEMS / G;
+    __shared__ double t[ROWS * (G + 1)];
+    const int tile = blockIdx.y;
+    const int32_t *sel = row_of + (size_t)tile * G;
+    bool any = false;
+    for (int k = 0; k < G; ++k) any = any || sel[k] >= 0;
+    if (!any) return;                                        // no column of this tile is wanted now (uniform per workgroup)
+    const int64_t r0 = (int64_t)blockIdx.x * ROWS;
+    const int nr = (int)((int64_t)n - r0 < ROWS ? (int64_t)n - r0 : ROWS);
+    const double *x = X + (size_t)tile * (size_t)n * G + (size_t)r0 * G;
+    for (int q = threadIdx.x; q < nr * G; q += 256) t[(q / G) * (G + 1) + (q % G)] = x[q];
+    __syncthreads();
+    for (int q = threadIdx.x; q < G * ROWS; q += 256) {
+        const int k = q / ROWS, r = q % ROWS;
+        const int32_t j = sel[k];
+        if (j >= 0 && r < nr) out[(size_t)j * (size_t)n + (size_t)(r0 + r)] = t[r * (G + 1) + k];
+    }
+}
+
+// Tile group by tile group: GroupIter (no frontier-list steps, no row lists: every step writes every row of X), then each
+// real slot's column goes to its caller row -- after step T (iteration mode) or after the step at which its own
+// checkConvergence holds (threshold modes; the sums of all G * tg columns come back with one synchronisation per step).
+static int32_t model_run_batch_body(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t run_mode, double value,
+                                    double *rank_out, int64_t *iters_out)
+{
+    const double t_begin = now_ms();
+    const int32_t n = g->n;
+    // one Model, or a graph / damping factor outside the domain of the batched kernels (negative ranks: the frontier
+    // kernels and the binade scan step aside, and the G > 1 step was never checked there): rwr_model_run per seed.
+    // Its statistics are those of K rwr_model_run calls (tile_seeds / tile_group untouched) plus this call's wall time.
+    if (K == 1 || !g->nonneg || !(d >= 0.0 && d <= 1.0)) {
+        for (int32_t k = 0; k < K; ++k)
+            RWR_TRY(model_run(g, seeds[k], d, run_mode, value, rank_out + (size_t)k * n, iters_out ? iters_out + k : nullptr));
+        g->stats.total_wall_ms += now_ms() - t_begin;
+        return RWR_OK;
+    }
+    const bool by_count = run_mode == RWR_RUN_ITERATIONS;
+    const double threshold = run_mode == RWR_RUN_DEFAULT_THRESHOLD ? (1 / 1.7976931348623157e308) * n : value;   // Model.cs:53
+    const int64_t max_iters = model_max_iters();
+    int64_t T = by_count ? (int64_t)value : max_iters;
+    if (T < 0) T = 0;
+    const int G = resolve_G(g, K);
+    int TG = 1;
+    RWR_TRY(ensure_workspace(g, G, K, &TG, 1));             // + cs_diff: differences, then staging of the extracted columns
+    const int ntiles = (int)cdiv((size_t)K, (size_t)G);
+    std::vector<int32_t> slot_k;
+    RWR_TRY(upload_seed_slots(g, seeds, K, G, &slot_k));
+    RWR_TRY(g->cs_sums.ensure((size_t)TG * G));
+    RWR_TRY(g->mb_row.ensure((size_t)TG * G));
+    hipStream_t s = g->stream;
+    const bool prof = g->opts.profile != 0;
+    EvPool pool;
+    std::vector<hipEvent_t> spmm_ev, chain_ev, iter_ev, ext_ev;
+    g->spmm_ev_dense.clear();
+    auto drain = [&]() -> int32_t {                          // (after a synchronisation: fold the profile events, recycle them)
+        if (prof) {
+            for (size_t i = 0; i + 1 < spmm_ev.size(); i += 2)
+                if (i / 2 < g->spmm_ev_dense.size() && g->spmm_ev_dense[i / 2]) {
+                    float ms = 0.f;
+                    RWR_HIP(hipEventElapsedTime(&ms, spmm_ev[i], spmm_ev[i + 1]));
+                    g->stats.spmm_dense_ms += ms;
+                }
+            RWR_TRY(drain_events(spmm_ev, &g->stats.spmm_ms));
+            RWR_TRY(drain_events(chain_ev, &g->stats.chain_ms));
+            RWR_TRY(drain_events(iter_ev, &g->stats.iterate_wall_ms));
+            RWR_TRY(drain_events(ext_ev, &g->stats.rank_ms));
+        }
+        spmm_ev.clear(); chain_ev.clear(); g->spmm_ev_dense.clear();
+        pool.used = 0;
+        return RWR_OK;
+    };
+    std::vector<int32_t> row_of;
+    std::vector<double> dist;
+    for (int t0 = 0; t0 < ntiles; t0 += TG) {
+        const int tg = (ntiles - t0 < TG) ? (ntiles - t0) : TG;
+        const size_t q0 = (size_t)t0 * G, nslots = (size_t)tg * G;
+        const int64_t *evoff = g->d_evoff.p + q0;
+        const size_t elems = nslots * (size_t)n;
+        int32_t live = 0;                                    // real slots whose column is not out yet
+        for (size_t q = 0; q < nslots; ++q) live += slot_k[q0 + q] >= 0;
+        const int32_t real = live;
+        std::vector<uint8_t> out_done(nslots, 0);
+        GroupIter gi(g, G, tg, g->d_seeds.p + q0, evoff, d);
+        RWR_TRY(gi.init(true, true, /*allow_flist=*/false));
+        if (!by_count) RWR_TRY(chain_scan_sum_cols_prepare(g, G, tg, s));
+        int64_t steps = 0;
+        for (;;) {
+            if (by_count ? steps == T : steps > 0) {
+                // the columns whose run ends here: every one after step T, the converged ones in threshold mode
+                row_of.assign(nslots, -1);
+                int32_t m = 0;
+                for (size_t q = 0; q < nslots; ++q) {
+                    const int32_t k = slot_k[q0 + q];
+                    if (k < 0 || out_done[q] || !(by_count || dist[q] < threshold)) continue;   // Model.cs:64
+                    row_of[q] = m++;
+                    out_done[q] = 1;
+                    if (iters_out) iters_out[k] = steps;
+                }
+                if (m > 0) {
+                    RWR_HIP(hipMemcpyAsync(g->mb_row.p, row_of.data(), nslots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+                    hipEvent_t a = nullptr, b = nullptr;
+                    if (prof) { a = pool.get(); b = pool.get(); RWR_HIP(hipEventRecord(a, s)); }
+                    RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_extract_cols<GG>, dim3(cdiv((size_t)n, EX_ELEMS / GG), (unsigned)tg),
+                                                         dim3(256), 0, s, n, gi.X, g->mb_row.p, g->cs_diff.p));
+                    RWR_HIP(hipGetLastError());
+                    if (prof) { RWR_HIP(hipEventRecord(b, s)); ext_ev.push_back(a); ext_ev.push_back(b); }
+                    for (size_t q = 0; q < nslots; ++q)
+                        if (row_of[q] >= 0)
+                            RWR_HIP(hipMemcpyAsync(rank_out + (size_t)slot_k[q0 + q] * n, g->cs_diff.p + (size_t)row_of[q] * n,
+                                                   sizeof(double) * n, hipMemcpyDeviceToHost, s));
+                    RWR_HIP(hipStreamSynchronize(s));
+                    RWR_TRY(drain());
+                    live -= m;
+                }
+                if (live == 0) break;
+            }
+            if (steps == T) {
+                set_error("rwr_model_run_batch: no convergence within %lld iterations (RWR_MAX_ITERS)", (long long)max_iters);
+                RWR_HIP(hipStreamSynchronize(g->stream2));
+                return RWR_E_UNSUPPORTED;
+            }
+            hipEvent_t i0 = nullptr, i1 = nullptr;
+            if (prof) { i0 = pool.get(); i1 = pool.get(); RWR_HIP(hipEventRecord(i0, s)); }
+            RWR_TRY(gi.step(pool, spmm_ev, chain_ev, by_count && steps + 1 == T));   // deliverRanks + updateRanks
+            ++steps;
+            if (!by_count) {                                 // checkConvergence of every column (Model.cs:58-65, 110-115)
+                hipLaunchKernelGGL(k_absdiff_mat, dim3(std::min<size_t>(cdiv(elems, 256), 16384)), dim3(256), 0, s, gi.Y, gi.X,
+                                   (int64_t)elems, g->cs_diff.p);
+                RWR_TRY(chain_scan_sum_cols(g, G, tg, g->cs_diff.p, evoff, g->cs_sums.p, s));
+            }
+            if (prof) { RWR_HIP(hipEventRecord(i1, s)); iter_ev.push_back(i0); iter_ev.push_back(i1); }
+            if (!by_count) {
+                dist.resize(nslots);
+                RWR_HIP(hipMemcpyAsync(dist.data(), g->cs_sums.p, nslots * sizeof(double), hipMemcpyDeviceToHost, s));
+                RWR_HIP(hipStreamSynchronize(s));
+                RWR_TRY(drain());
+            }
+        }
+        g->stats.spmm_seed_steps += (int64_t)real * steps;
+        g->stats.spmm_dense_seed_steps += (int64_t)real * gi.dense_steps;
+    }
+    RWR_HIP(hipStreamSynchronize(s));
+    RWR_HIP(hipStreamSynchronize(g->stream2));
+    RWR_TRY(drain());
+    if (prof) RWR_TRY(chain_scan_collect(g, s));
+    g->stats.tile_seeds = G;
+    g->stats.tile_group = TG;
+    g->stats.total_wall_ms += now_ms() - t_begin;
+    return RWR_OK;
+}
+
+// no C++ exception crosses the C boundary
+int32_t model_run_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t run_mode, double value,
+                        double *rank_out, int64_t *iters_out)
+{
+    try {
+        return model_run_batch_body(g, seeds, K, d, run_mode, value, rank_out, iters_out);
+    } catch (const std::bad_alloc &) {
+        set_error("rwr_model_run_batch: host allocation failed");
+        return RWR_E_NOMEM;
+    } catch (...) {
+        set_error("rwr_model_run_batch: unexpected host exception");
+        return RWR_E_HIP;
+    }
 }
 
 // ---- row-partitioned mode (include/rwr.h: rwr_part_*) -----------------------------------------------------------

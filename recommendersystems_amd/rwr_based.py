@@ -377,6 +377,27 @@ class Model:
         self.nextRank = np.zeros(self.nNodes)
         self.iterations = int(it.value)
 
+    @staticmethod
+    def RunBatch(graph: Graph, dampingFactor: float, seeds, arg=None) -> Tuple[np.ndarray, np.ndarray]:
+        """K personalised models in one call (rwr_model_run_batch), an addition beside the reference surface:
+        returns (ranks, iterations), ranks[k] / iterations[k] being what Model(graph, dampingFactor, seeds[k]).run(arg)
+        leaves in rank / iterations.  arg as in run(): an int gives iterations, a float a threshold, None the default
+        threshold (each seed then stops at its own convergence step)."""
+        lib = _lib.load()
+        if isinstance(arg, (int, np.integer)) and not isinstance(arg, bool):
+            mode, value = _lib.RWR_RUN_ITERATIONS, float(arg)
+        elif arg is None:
+            mode, value = _lib.RWR_RUN_DEFAULT_THRESHOLD, 0.0
+        else:
+            mode, value = _lib.RWR_RUN_THRESHOLD, float(arg)
+        s = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        K, n = int(s.shape[0]), graph.size()
+        ranks = np.zeros((K, n), dtype=np.float64)
+        iters = np.zeros(K, dtype=np.int64)
+        _lib.check(lib.rwr_model_run_batch(graph._handle(), _p(s, C.c_int32), K, float(dampingFactor), mode, value,
+                                           _p(ranks, C.c_double), _p(iters, C.c_int64)))
+        return ranks, iters
+
     def deliverRanks(self) -> None:
         """Model.deliverRanks (Model.cs:76-100): nextRank <- one propagation of the current rank (rwr_model_deliver)."""
         n = self.nNodes
