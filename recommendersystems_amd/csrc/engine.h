@@ -64,11 +64,16 @@ struct rwr_graph {
     std::vector<uint8_t> h_is_item;
     rwr::DevBuf<int32_t> item_order;  // ITEM rows by id descending
     rwr::DevBuf<int32_t> item_rows;   // ITEM rows by row index ascending
-    // rows the ranking depends on in a batch's last two steps, both in row_order's order: tail_rows[0] = the
-    // ITEM rows, tail_rows[1] = every row with an explicit link into an ITEM row.  Built on first use (tail_rows_prepare),
-    // dropped by every (re)build: tail_state 0 = not built, 1 = built
-    rwr::DevBuf<int32_t> tail_rows[2];
-    int32_t tail_n[2] = {0, 0};
+    // rows the ranking depends on in a batch's last steps, each in row_order's order: tail_rows[0] = the ITEM
+    // rows, tail_rows[k] = every row with an explicit link into a row of tail_rows[k - 1], for k < tail_depth <= TAIL_MAX
+    // (at most n x 4 B per level).  h_tail_flag[i] bit k: a seed at row i needs its seed-row chain at step T - k (bit 0: i is
+    // an ITEM row; bit 1: i has an explicit raw link into an ITEM row it does not LIKE; bit k >= 2: i is in tail_rows[k]).
+    // Built on first use (tail_rows_prepare), dropped by every (re)build: tail_state 0 = not built, 1 = built
+    static constexpr int TAIL_MAX = 4;
+    rwr::DevBuf<int32_t> tail_rows[TAIL_MAX];
+    int32_t tail_n[TAIL_MAX] = {0, 0, 0, 0};
+    int32_t tail_depth = 0;
+    std::vector<uint8_t> h_tail_flag;
     int32_t tail_state = 0;
 
     // single-seed SpMV of value-free graphs as a source-block sweep with z staged through LDS (sweep.hip): 0 = not decided
@@ -157,7 +162,7 @@ int32_t graph_build(rwr_graph *g, const int64_t *node_id, const uint8_t *node_ty
 int32_t graph_update_links(rwr_graph *g, int64_t count, const int64_t *idx, const uint8_t *etype, const double *w);
 // value-free graphs: materialise in_w (= w_src[in_src]) for an entry point that runs the weighted kernels
 int32_t ensure_in_w(rwr_graph *g);
-// g->tail_rows / tail_n of the current matrix (built once per (re)build)
+// g->tail_rows / tail_n / tail_depth / h_tail_flag of the current matrix (built once per (re)build)
 int32_t tail_rows_prepare(rwr_graph *g);
 // many ego-network-sized graphs at once (rwr_eval_graphs): one build launch, one call launch, one evaluation launch
 bool graph_fits_small_build(int32_t n, int64_t m);

@@ -1009,8 +1009,8 @@ struct GroupIter {
     }
 
     // last = no further step follows: the value-free path need not form the next z
-    // rows != nullptr: the SpMM produces only the nrows rows of that list (a batch's last two steps);
-    // chain = false: no seed row of this step is read afterwards, its chain is not run
+    // rows != nullptr: the SpMM produces only the nrows rows of that list (a batch's last steps);
+    // chain = false: no seed row of this step reaches a row the ranking reads, its chain is not run
     // may_list: the caller allows this step to write only its frontier's rows (it is neither a tail-list step nor the last)
     int32_t step(EvPool &pool, std::vector<hipEvent_t> &spmm_ev, std::vector<hipEvent_t> &chain_ev, bool last = false,
                  const int32_t *rows = nullptr, int32_t nrows = 0, bool chain = true, bool may_list = false)
@@ -1118,32 +1118,46 @@ struct GroupIter {
     }
 };
 
-// rank_only: the caller reads nothing of the final ranks but their ITEM rows (Recommender.cs:29-31), so the last two steps
-// produce only the rows that reach them; item_seed: a seed of the group is itself an ITEM row
+// rank_only: the caller reads nothing of the final ranks but their ITEM rows outside each seed's LIKE targets
+// (Recommender.cs:20-31), so the last steps produce only the rows that reach them; h_seeds: the group's
+// tg * G seed slots on the host (-1 = padding), whose tail flags decide which of those steps run their seed-row chain.
+//
+// The invariant of the tail plan: every row that a later step's SpMM or chain reads is written by the step before it, and a
+// stale (seed row, seed column) pair reaches only rows excluded for that seed.  Step T - k (k < tail_depth) walks tail_rows[k],
+// which holds every source of the rows step T - k + 1 walks; its chain runs only if a seed of the group has flag bit k (its
+// seed row may reach a row the ranking reads), and then, since that chain reads every row of the step before, step T - k is
+// the last restricted one.  Without any flag bit below tail_depth, steps T .. T - tail_depth + 1 are restricted and chainless,
+// and step T - tail_depth is whole.  A restricted step never writes a frontier row list, and where it also probes the frontier
+// bitmaps it reads and writes them as any other step does (it writes the bits of the rows it walks).
 int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const int64_t *d_evoff, double d,
                       int64_t n_iter, double **final_X, EvPool &pool, std::vector<hipEvent_t> &spmm_ev,
-                      std::vector<hipEvent_t> &chain_ev, int64_t *dense_steps, bool rank_only = false, bool item_seed = true)
+                      std::vector<hipEvent_t> &chain_ev, int64_t *dense_steps, bool rank_only = false,
+                      const int32_t *h_seeds = nullptr)
 {
     GroupIter gi(g, G, tg, d_seeds, d_evoff, d);
     RWR_TRY(gi.init(true, true, true));
     static const int tail_env = [] { const char *e = getenv("RWR_TAIL_ROWS"); return e ? atoi(e) : 1; }();
     // (one seed on its own takes the single-seed SpMV, whose rows stay all rows)
-    const bool tails = rank_only && tail_env != 0 && !(G == 1 && tg == 1);
-    if (tails) RWR_TRY(tail_rows_prepare(g));
+    const bool tails = rank_only && h_seeds && tail_env != 0 && !(G == 1 && tg == 1);
+    unsigned need = 0;   // bit k: some seed of the group needs its chain at step T - k
+    int last_tail = -1;  // steps T - last_tail .. T walk row lists
+    if (tails) {
+        RWR_TRY(tail_rows_prepare(g));
+        for (size_t q = 0; q < (size_t)tg * G; ++q)
+            if (h_seeds[q] >= 0) need |= g->h_tail_flag[h_seeds[q]];
+        last_tail = g->tail_depth - 1;
+        for (int k = 0; k < g->tail_depth; ++k)
+            if ((need >> k) & 1u) { last_tail = k; break; }
+    }
     for (int64_t it = 0; it < n_iter; ++it) {
-        const int64_t left = n_iter - it;   // this step and those after it
+        const int64_t k = n_iter - 1 - it;   // this is step T - k
         const int32_t *rows = nullptr;
         int32_t nrows = 0;
         bool chain = true;
-        if (tails && left == 1) {
-            // the last step: the ITEM rows; the seed rows only where the seed is an ITEM
-            rows = g->tail_rows[0].p; nrows = g->tail_n[0]; chain = item_seed;
-        } else if (tails && left == 2 && !item_seed) {
-            // the step before: the sources of the ITEM rows' in-links, plus the seed rows (chain).  A last-step chain
-            // would fold the restart addend of EVERY row of this step's ranks, so with an ITEM seed this step stays whole
-            rows = g->tail_rows[1].p; nrows = g->tail_n[1];
+        if (k <= last_tail) {
+            rows = g->tail_rows[k].p; nrows = g->tail_n[k]; chain = ((need >> k) & 1u) != 0;
         }
-        RWR_TRY(gi.step(pool, spmm_ev, chain_ev, left == 1, rows, nrows, chain, !rows && left >= 2));
+        RWR_TRY(gi.step(pool, spmm_ev, chain_ev, k == 0, rows, nrows, chain, !rows && k >= 1));
     }
     *final_X = gi.X;
     *dense_steps = gi.dense_steps;
@@ -1345,11 +1359,8 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
         hipEvent_t i0 = nullptr, i1 = nullptr;
         if (prof) { i0 = pool.get(); i1 = pool.get(); RWR_HIP(hipEventRecord(i0, s)); }
         int64_t dense_steps = 0;
-        bool item_seed = false;
-        for (size_t q = (size_t)t0 * G; q < (size_t)(t0 + tg) * G; ++q)
-            item_seed = item_seed || (slot_seed[q] >= 0 && g->h_is_item[slot_seed[q]]);
         RWR_TRY(iterate_group(g, G, tg, dseeds, g->d_evoff.p + (size_t)t0 * G, d, n_iter, &Xf, pool, spmm_ev, chain_ev,
-                              &dense_steps, true, item_seed));
+                              &dense_steps, true, slot_seed.data() + (size_t)t0 * G));
         if (prof) { RWR_HIP(hipEventRecord(i1, s)); iter_ev.push_back(i0); iter_ev.push_back(i1); }
         int32_t real = 0;
         for (size_t q = (size_t)t0 * G; q < (size_t)(t0 + tg) * G; ++q) real += slot_k[q] >= 0;
