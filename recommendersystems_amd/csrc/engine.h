@@ -142,7 +142,6 @@ struct rwr_graph {
     hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_d = nullptr;   // profiling pairs
 
     rwr_stats stats{};
-    std::vector<uint8_t> spmm_ev_dense;   // per profiled SpMM launch: 1 = dense (no frontier skipping)
 };
 
 namespace rwr {

@@ -20,12 +20,14 @@
 // nextRank += rw * weight (Model.cs:87) -- two roundings, never an FMA (the file is built
 // with -ffp-contract=off).
 #include "engine.h"
+#include "step_plan.h"
 
 #include <algorithm>
 #include <chrono>
 #include <climits>
 #include <cstdlib>
 #include <new>
+#include <type_traits>
 
 namespace rwr {
 
@@ -738,88 +740,86 @@ __global__ __launch_bounds__(256) void k_make_z_nz(int32_t lo, int32_t hi, int G
 
 // ------------------------------------------------------------------------------ host side
 
+// The plan's environment values, read once per process (the RWR_TUNE_ENV ones only by the experiments build)
+static PlanInput read_plan_knobs()
+{
+    PlanInput v;
+    const char *e;
+    if ((e = getenv("RWR_SPMM"))) v.spmm = atoi(e);
+    if ((e = RWR_TUNE_ENV("RWR_NZ_ITERS"))) v.nz_iters = atoi(e);
+    if ((e = getenv("RWR_ACT_ITERS"))) v.act_iters = atoi(e);
+    if ((e = RWR_TUNE_ENV("RWR_ACT_MIN_N"))) v.act_min_n = atol(e);
+    if ((e = getenv("RWR_FRONTIER_LIST"))) v.frontier_list = atoi(e);
+    if ((e = getenv("RWR_CHAIN"))) v.chain = atoi(e);
+    if ((e = RWR_TUNE_ENV("RWR_SCAN_WORK"))) v.scan_work = atof(e);
+    if ((e = RWR_TUNE_ENV("RWR_SCAN_SIDE"))) v.scan_side = atoi(e);
+    if ((e = RWR_TUNE_ENV("RWR_GATE"))) v.gate = atoi(e);
+    if ((e = getenv("RWR_TAIL_ROWS"))) v.tail_rows = atoi(e);
+    if ((e = RWR_TUNE_ENV("RWR_CHAIN_SERIAL"))) v.two_streams = atoi(e) == 0;
+    return v;
+}
+static const PlanInput &plan_knobs() { static const PlanInput k = read_plan_knobs(); return k; }
+
+// f(std::true_type or std::false_type, ...) for runtime bools: one instantiation of f per combination
+template <class F> static void bool_dispatch(F &&f) { f(); }
+template <class F, class... B> static void bool_dispatch(F &&f, bool b, B... bs)
+{
+    bool_dispatch([&](auto... c) { if (b) f(std::true_type{}, c...); else f(std::false_type{}, c...); }, bs...);
+}
+
+// rows: every row, a tail level (a batch's last steps; X / Y / Z keep their n rows) or the tiles' frontier
+// lists (their lengths only the device knows; the grid is sized for a list of a tenth of the rows -- the lists
+// of C4's frontier steps hold 0.05 % and 4 % -- and the launch strides over longer ones)
 template <int G>
 static void launch_spmm(rwr_graph *g, int tg, const double *X, double *Y, const int32_t *seeds, double c1,
                         int skip, const uint32_t *nz_in, uint32_t *nz_out, hipStream_t s,
                         const uint32_t *act = nullptr, const double *Zin = nullptr, double *Zout = nullptr,
-                        bool hub_scan = false, const int32_t *rows = nullptr, int32_t nrows = 0)
+                        bool hub_scan = false, RowSource rows = {})
 {
     // Zin != nullptr: value-free form -- the kernels gather Zin (z of the current ranks) instead of X and read no weights
     const bool vf = Zin != nullptr;
     const double *GS = vf ? Zin : X;   // gather source
-    // rows != nullptr: only the nrows rows of that list (a batch's last steps); X / Y / Z keep their n rows
-    const bool listed = rows != nullptr;
-    if (!listed) { rows = g->row_order.p; nrows = g->n; }
     constexpr int RPW = WAVE / G;
+    constexpr int CH = G > 16 ? 16 : G;   // entries per chunk = row gathers in flight per lane
+    if constexpr (G >= 8) {
+        if (rows.kind == Rows::Frontier) {
+            const int32_t *fl_rows = g->fl_rows.p, *fl_cnt = g->fl_rows.p + (size_t)tg * (size_t)g->n;
+            const unsigned want = cdiv((size_t)g->n / 10 + 1, (size_t)RPW * 4);
+            const unsigned gx = want < 1u ? 1u : want < 2048u ? want : 2048u;
+            bool_dispatch([&](auto v) {
+                hipLaunchKernelGGL((k_spmm_frontier<G, CH, decltype(v)::value>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p,
+                                   g->in_src.p, g->in_w.p, fl_rows, fl_cnt, GS, Y, seeds, c1, skip, nz_in, nz_out, g->w_src.p, Zout);
+            }, vf);
+            return;
+        }
+    }
+    const bool listed = rows.kind == Rows::Tail;
+    const int32_t *order = listed ? g->tail_rows[rows.level].p : g->row_order.p;
+    const int32_t nrows = listed ? g->tail_n[rows.level] : g->n;
     unsigned want = cdiv((size_t)nrows, (size_t)RPW * 4);
     unsigned gx = want < 1u ? 1u : want < 8192u ? want : 8192u;
-    static const int variant = [] { const char *e = getenv("RWR_SPMM"); return e ? atoi(e) : 1; }();
     if constexpr (G == 1) {
-        if (tg == 1 && variant != 0) {   // (every row: the callers pass no row list to this path)
+        if (tg == 1 && plan_knobs().spmm != 0) {   // (every row: the callers pass no row list to this path)
             launch_spmv_exact(g, X, Y, seeds, c1, skip, act, nz_out, s, Zin, Zout, hub_scan);
             return;
         }
     }
     if constexpr (G >= 8) {
-        if (variant != 0) {
-#define RWR_SPMM_LAUNCH4(CH, CHK, WR, VFF, LST)                                                                        \
-    hipLaunchKernelGGL((k_spmm_chunked<G, CH, CHK, WR, VFF, LST>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p,    \
-                       g->in_src.p, g->in_w.p, rows, nrows, GS, Y, seeds, c1, skip, nz_in, nz_out, act,                  \
-                       g->w_src.p, Zout)
-#define RWR_SPMM_LAUNCH3(CH, CHK, WR, VFF)                       \
-    {                                                            \
-        if (listed) RWR_SPMM_LAUNCH4(CH, CHK, WR, VFF, true);    \
-        else RWR_SPMM_LAUNCH4(CH, CHK, WR, VFF, false);          \
-    }
-#define RWR_SPMM_LAUNCH2(CH, CHK, WR)                    \
-    {                                                    \
-        if (vf) RWR_SPMM_LAUNCH3(CH, CHK, WR, true)      \
-        else RWR_SPMM_LAUNCH3(CH, CHK, WR, false)        \
-    }
-#define RWR_SPMM_LAUNCH(CH)                                  \
-    {                                                        \
-        if (nz_in && nz_out) RWR_SPMM_LAUNCH2(CH, true, true)    \
-        else if (nz_in) RWR_SPMM_LAUNCH2(CH, true, false)        \
-        else RWR_SPMM_LAUNCH2(CH, false, false)                  \
-    }
-            // entries per chunk = row gathers in flight per lane (variant 2: 8, variant 3: 4)
-            if (variant == 2) RWR_SPMM_LAUNCH(8)
-            else if (variant == 3) RWR_SPMM_LAUNCH(4)
-            else RWR_SPMM_LAUNCH((G > 16 ? 16 : G))
-#undef RWR_SPMM_LAUNCH4
-#undef RWR_SPMM_LAUNCH3
-#undef RWR_SPMM_LAUNCH2
-#undef RWR_SPMM_LAUNCH
+        if (plan_knobs().spmm != 0) {
+            bool_dispatch([&](auto chk, auto wr, auto v, auto lst) {
+                if constexpr (decltype(chk)::value || !decltype(wr)::value)
+                    hipLaunchKernelGGL((k_spmm_chunked<G, CH, decltype(chk)::value, decltype(wr)::value, decltype(v)::value,
+                                                       decltype(lst)::value>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p,
+                                       g->in_src.p, g->in_w.p, order, nrows, GS, Y, seeds, c1, skip, nz_in, nz_out, act,
+                                       g->w_src.p, Zout);
+            }, nz_in != nullptr, nz_in && nz_out, vf, listed);
             return;
         }
     }
-    if (vf)
-        hipLaunchKernelGGL((k_spmm<G, true>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p, g->in_w.p,
-                           rows, nrows, GS, Y, seeds, c1, skip, g->w_src.p, Zout);
-    else
-        hipLaunchKernelGGL((k_spmm<G, false>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p, g->in_w.p,
-                           rows, nrows, GS, Y, seeds, c1, skip, g->w_src.p, Zout);
-}
-// Frontier-list step: the SpMM over each tile's own row list, whose length only the device knows.  The
-// grid is sized for a list of a tenth of the rows (the lists of C4's frontier steps hold 0.05 % and 4 %); the launch
-// strides over longer ones.
-template <int G>
-static void launch_spmm_frontier(rwr_graph *g, int tg, const double *X, double *Y, const int32_t *seeds, double c1,
-                                 const uint32_t *nz_in, uint32_t *nz_out, hipStream_t s, const int32_t *fl_rows,
-                                 const int32_t *fl_cnt, const double *Zin, double *Zout)
-{
-    if constexpr (G >= 8) {
-        constexpr int RPW = WAVE / G;
-        constexpr int CH = G > 16 ? 16 : G;
-        const unsigned want = cdiv((size_t)g->n / 10 + 1, (size_t)RPW * 4);
-        const unsigned gx = want < 1u ? 1u : want < 2048u ? want : 2048u;
-        if (Zin)
-            hipLaunchKernelGGL((k_spmm_frontier<G, CH, true>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p,
-                               g->in_w.p, fl_rows, fl_cnt, Zin, Y, seeds, c1, 1, nz_in, nz_out, g->w_src.p, Zout);
-        else
-            hipLaunchKernelGGL((k_spmm_frontier<G, CH, false>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p,
-                               g->in_w.p, fl_rows, fl_cnt, X, Y, seeds, c1, 1, nz_in, nz_out, g->w_src.p, Zout);
-    }
+    bool_dispatch([&](auto v) {
+        hipLaunchKernelGGL((k_spmm<G, decltype(v)::value>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p,
+                           g->in_w.p, order, nrows, GS, Y, seeds, c1, skip, g->w_src.p, Zout);
+    }, vf);
 }
 template <int G>
 // the addends of the links into the seeds; tiny, runs on the MAIN stream ahead of the fork so that the chain kernel is
@@ -830,24 +830,22 @@ static void launch_seed_terms(rwr_graph *g, int tg, const double *X, const int32
                               const int64_t *evoff, hipStream_t s, const double *Zin, const uint32_t *nz = nullptr)
 {
     const unsigned term_blocks = g->max_in_deg > 256 * 8 ? 8u : cdiv((size_t)(g->max_in_deg > 0 ? g->max_in_deg : 1), 256);
-    if (Zin)
-        hipLaunchKernelGGL((k_seed_terms<G, true>), dim3(term_blocks, tg * G), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p,
-                           g->in_w.p, Zin, seeds, c1, evoff, g->d_evterm.p, nz);
-    else
-        hipLaunchKernelGGL((k_seed_terms<G, false>), dim3(term_blocks, tg * G), dim3(256), 0, s, g->n, g->in_ptr.p, g->in_src.p,
-                           g->in_w.p, X, seeds, c1, evoff, g->d_evterm.p, nz);
+    bool_dispatch([&](auto v) {
+        hipLaunchKernelGGL((k_seed_terms<G, decltype(v)::value>), dim3(term_blocks, tg * G), dim3(256), 0, s, g->n, g->in_ptr.p,
+                           g->in_src.p, g->in_w.p, Zin ? Zin : X, seeds, c1, evoff, g->d_evterm.p, nz);
+    }, Zin != nullptr);
 }
 template <int G>
 static void launch_chain(rwr_graph *g, int tg, const double *X, double *Y, const int32_t *seeds, double c1,
                          const int64_t *evoff, uint32_t *nz_out, unsigned int *gate, hipStream_t s,
-                         const uint32_t *nz_sparse, int variant)
+                         Chain kind, const uint32_t *nz_x)
 {
-    if (nz_sparse) {   // X still sparse: visit only its non-zero rows
+    if (kind == Chain::Sparse) {   // X still sparse: visit only the non-zero rows of its bitmap nz_x
         hipLaunchKernelGGL(k_seed_chain_sparse<G>, dim3(tg), dim3(64), 0, s, g->n, g->in_ptr.p, g->in_src.p,
-                           g->dangling.p, X, Y, seeds, c1, evoff, g->d_evterm.p, nz_sparse, nz_out, gate);
+                           g->dangling.p, X, Y, seeds, c1, evoff, g->d_evterm.p, nz_x, nz_out, gate);
         return;
     }
-    if (variant != 0) {   // 0 = simple reference kernel
+    if (kind == Chain::Roles) {
         constexpr size_t smem = 2 * CH3_CE * sizeof(double);
         // (per launch, not once per process: the attribute belongs to the current device, and one process may hold
         //  graphs on several devices)
@@ -873,21 +871,53 @@ constexpr int RP_BLOCK = 256;
         default: { constexpr int GG = 64; CALL; } break; \
     }
 
-struct EvPool {
-    std::vector<hipEvent_t> ev;
-    size_t used = 0;
-    hipEvent_t get()
+// Profile events of a call (opts.profile): begin / end pairs of the profiled stages, from a pool of events that fold()
+// folds into rwr_stats and recycles after a synchronisation.  With profiling off every method does nothing.
+struct Profile {
+    const bool on;
+    std::vector<hipEvent_t> pool, spmm, chain, rank, iter;   // the pool; pairs of the SpMM, chain, ranking, iteration stages
+    size_t used = 0;                                          // (pool[0 .. used) are in flight)
+    std::vector<uint8_t> dense;                               // per SpMM pair: 1 = a dense launch
+    explicit Profile(const rwr_graph *g) : on(g->opts.profile != 0) {}
+    ~Profile() { for (auto e : pool) (void)hipEventDestroy(e); }
+    // an event of the pool recorded on s: the begin of a pair
+    int32_t record(hipEvent_t &e, hipStream_t s)
     {
-        if (used == ev.size()) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return nullptr;
-            ev.push_back(e);
-        }
-        return ev[used++];
+        e = nullptr;
+        if (!on) return RWR_OK;
+        if (used == pool.size()) { RWR_HIP(hipEventCreate(&e)); pool.push_back(e); }
+        e = pool[used++];
+        RWR_HIP(hipEventRecord(e, s));
+        return RWR_OK;
     }
-    ~EvPool()
+    // the end of the pair that `a` began, recorded on s
+    int32_t end(std::vector<hipEvent_t> &stage, hipEvent_t a, hipStream_t s)
     {
-        for (auto e : ev) (void)hipEventDestroy(e);
+        hipEvent_t b; RWR_TRY(record(b, s));
+        if (on) stage.insert(stage.end(), {a, b});
+        return RWR_OK;
+    }
+    void reset() { spmm.clear(); chain.clear(); rank.clear(); iter.clear(); dense.clear(); used = 0; }
+    int32_t fold(rwr_graph *g)
+    {
+        auto drain = [&](const std::vector<hipEvent_t> &v, double *acc, bool dense_only) -> int32_t {
+            for (size_t i = 0; i + 1 < v.size(); i += 2) {
+                float ms = 0.f;
+                if (dense_only && !dense[i / 2]) continue;
+                RWR_HIP(hipEventElapsedTime(&ms, v[i], v[i + 1]));
+                *acc += ms;
+            }
+            return RWR_OK;
+        };
+        if (on) {
+            RWR_TRY(drain(spmm, &g->stats.spmm_dense_ms, true));
+            RWR_TRY(drain(spmm, &g->stats.spmm_ms, false));
+            RWR_TRY(drain(chain, &g->stats.chain_ms, false));
+            RWR_TRY(drain(rank, &g->stats.rank_ms, false));
+            RWR_TRY(drain(iter, &g->stats.iterate_wall_ms, false));
+        }
+        reset();
+        return RWR_OK;
     }
 };
 
@@ -915,7 +945,8 @@ static int resolve_G(const rwr_graph *g, int32_t K)
 }
 
 // One tile group's power iteration: init() = Model ctor (Model.cs:33-50), step() = deliverRanks + updateRanks
-// (Model.cs:76-108).  After step() `X` holds the new ranks and `Y` still holds the previous ones.
+// (Model.cs:76-108) as plan_step() (step_plan.h) decided it.  After step() `X` holds the new ranks and `Y` still holds the
+// previous ones.
 struct GroupIter {
     rwr_graph *g;
     int G, tg;
@@ -925,240 +956,121 @@ struct GroupIter {
     double *X, *Y;
     double *Zc = nullptr, *Zn = nullptr;   // value-free path: z of the current ranks / of the ranks being produced
     uint32_t *nz_cur = nullptr, *nz_oth = nullptr;
-    int nz_iters = 0;
+    PlanConfig cfg;
     int64_t it = 0;
-    bool scan = false;   // exact mode: seed-row chain by the parallel binade scan (chain_scan.hip)
-    int chain_kind = 1;  // 0 simple one-lane loop, 1 auto, 2 scan, 3 role-specialised fold
-    int act_iters = 0;   // iterations whose SpMM only visits the out-neighbours of non-zero rows
     int64_t dense_steps = 0;   // steps whose SpMM walked every row (no frontier bitmap)
-    bool addends_nonneg = false;   // weights, ranks and 1-d all >= 0 and finite: exact parallel reductions are allowed
-    bool flist = false;  // frontier-list steps allowed: Z is not cleared, rows outside the bitmaps may be stale
 
     GroupIter(rwr_graph *g_, int G_, int tg_, const int32_t *seeds, const int64_t *evoff, double d)
         : g(g_), G(G_), tg(tg_), d_seeds(seeds), d_evoff(evoff), c1(1 - d) /* Model.cs:84: (1 - dampingFactor) */,
           X(g_->X.p), Y(g_->Y.p), Zc(g_->vf ? g_->Z0.p : nullptr), Zn(g_->vf ? g_->Z1.p : nullptr) {}
 
     // fresh = Model ctor (rank = n at the seed, 0 elsewhere);  !fresh = X already holds a caller-supplied rank vector
-    // (Model.deliverRanks called on its own): no frontier knowledge, and the binade scan only if those ranks are >= 0
-    // allow_flist: the caller (iterate_group) may run frontier-list steps, see step()
-    int32_t init(bool fresh = true, bool ranks_nonneg = true, bool allow_flist = false)
+    // (Model.deliverRanks called on its own);  ranking_only: the caller (iterate_group) reads only the ranking
+    int32_t init(bool fresh = true, bool ranks_nonneg = true, bool ranking_only = false)
     {
         const int32_t n = g->n;
         hipStream_t s = g->stream;
         const size_t elems = (size_t)tg * (size_t)n * G;
+        PlanInput in = plan_knobs();
+        in.n = n; in.nnz = g->nnz; in.nonneg = g->nonneg; in.big_n = spmv_big_n(); in.seed_row_kernel = g->opts.seed_row_kernel;
+        in.scan_self = chain_scan_self_contained(G); in.G = G; in.tg = tg; in.c1 = c1;
+        in.fresh = fresh; in.ranks_nonneg = ranks_nonneg; in.ranking_only = ranking_only;
+        cfg = plan_config(in);
         if (fresh) RWR_HIP(hipMemsetAsync(X, 0, elems * sizeof(double), s));
         if (!fresh && Zc) hipLaunchKernelGGL(k_make_z, dim3(cdiv(elems, 256)), dim3(256), 0, s, (int64_t)elems, G, X, Zc, g->w_src.p, c1);
-        // frontier bitmaps for the first iterations (chunked SpMM only)
-        static const int nz_iters_env = [] { const char *e = RWR_TUNE_ENV("RWR_NZ_ITERS"); return e ? atoi(e) : 4; }();
-        static const int spmm_variant = [] { const char *e = getenv("RWR_SPMM"); return e ? atoi(e) : 1; }();
-        // (skipping +0.0 addends is only a bitwise no-op while every accumulator is >= +0.0: weights must be >= 0)
-        nz_iters = (G >= 8 && spmm_variant != 0 && g->nonneg) ? nz_iters_env : 0;
-        // iterations 0 and 1: the non-zero rows are few enough to mark their out-neighbours; every other row is 0
-        // (iteration 1 only on sparse graphs: on dense ones -- hundreds of links per node -- marking the 2-hop
-        //  neighbourhood costs more atomics than the skipped rows save)
-        static const int act_env = [] { const char *e = getenv("RWR_ACT_ITERS"); return e ? atoi(e) : -1; }();
-        act_iters = act_env >= 0 ? act_env : ((g->nnz / (g->n > 0 ? g->n : 1)) <= 64 ? 2 : 1);
-        // single exact seed (lane-per-row SpMV): row-level skipping only, for exactly those iterations
-        // (on multi-million-node sparse graphs a single seed's 3-hop frontier is still worth marking: measured -7 % per call
-        //  on the 6 M-node graph, +10 % on the 0.6 M-node one)
-        if (G == 1 && tg == 1 && act_env < 0 && act_iters == 2 && g->n >= spmv_big_n()) act_iters = 3;
-        if (G == 1 && tg == 1 && spmm_variant != 0 && g->nonneg) nz_iters = act_iters;
-        // (a single seed on a graph of ego-network size: marking the frontier takes longer than the dense step it replaces --
-        //  measured 38 us against 8 at 12 K nodes, 25 against 28 at 120 K)
-        static const int64_t act_min_n = [] { const char *e = RWR_TUNE_ENV("RWR_ACT_MIN_N"); return e ? atol(e) : 200000l; }();
-        if (G == 1 && tg == 1 && act_env < 0 && n < act_min_n) nz_iters = act_iters = 0;
-        if (!fresh) nz_iters = act_iters = 0;
         const size_t nzw = ((size_t)n + 31) / 32;
-        // frontier-list steps need a bitmap-checking step after each of them (nz_iters >= 2) and a per-tile row list
-        static const int flist_env = [] { const char *e = getenv("RWR_FRONTIER_LIST"); return e ? atoi(e) : 1; }();
-        flist = allow_flist && fresh && flist_env != 0 && G >= 8 && nz_iters >= 2 && act_iters >= 1;
-        if (flist && g->fl_rows.ensure((size_t)tg * (size_t)n + (size_t)tg) != RWR_OK) {
+        if (cfg.flist && g->fl_rows.ensure((size_t)tg * (size_t)n + (size_t)tg) != RWR_OK) {
             (void)hipGetLastError();   // (no room for the lists: the bitmap-probing steps of before, which need none)
-            flist = false;
+            cfg.flist = false;
         }
         // Z is read only through the frontier bitmaps until a step has written it whole: on the frontier-list path the
         // seed rows (k_init_seeds) are all of it that must be valid
-        if (fresh && Zc && !flist) RWR_HIP(hipMemsetAsync(Zc, 0, elems * sizeof(double), s));
-        nz_cur = nz_iters > 0 ? g->d_nz.p : nullptr;
-        nz_oth = nz_iters > 0 ? g->d_nz.p + (size_t)tg * nzw : nullptr;
+        if (fresh && Zc && !cfg.flist) RWR_HIP(hipMemsetAsync(Zc, 0, elems * sizeof(double), s));
+        nz_cur = cfg.nz_iters > 0 ? g->d_nz.p : nullptr;
+        nz_oth = cfg.nz_iters > 0 ? g->d_nz.p + (size_t)tg * nzw : nullptr;
         if (nz_cur) RWR_HIP(hipMemsetAsync(nz_cur, 0, (size_t)tg * nzw * sizeof(uint32_t), s));
         if (fresh) hipLaunchKernelGGL(k_init_seeds, dim3(cdiv((size_t)tg * G, 64)), dim3(64), 0, s, n, tg, G, X, d_seeds, nz_cur, Zc, g->w_src.p, c1);
         RWR_HIP(hipGetLastError());
-        it = 0;
-        // Seed-row chain of the dense iterations.  The role-specialised fold (k_seed_chain_roles) takes ~20 cycles per
-        // row whatever the batch, which a large batch hides behind its SpMM; the binade scan reads X twice but is
-        // parallel, so it wins whenever the SpMM of the group is shorter than the fold: small tile groups, and above
-        // all the single-seed call of the unmodified harness.  RWR_CHAIN: 0 simple kernel, 1 auto, 2 scan, 3 roles.
-        //            opts.seed_row_kernel (1 fold, 2 scan, 3 simple) takes precedence over the environment.
-        static const int chain_env = [] { const char *e = getenv("RWR_CHAIN"); return e ? atoi(e) : 1; }();
-        // auto: per step the fold costs ~10 ns per node whatever the batch (hidden if the SpMM is longer); the scan
-        // costs ~6.7 ps per (node, seed) on top of an SpMM of ~0.89 ps per (link, seed)  (measured, MI355X, 20 M- and
-        // 200 M-link graphs) => scan while  seeds * (0.89 * links/node + 6.7) < 10000  (about 280 seeds there)
-        static const double scan_work = [] { const char *e = RWR_TUNE_ENV("RWR_SCAN_WORK"); return e ? atof(e) : 10000.0; }();
-        const int sel = g->opts.seed_row_kernel;
-        chain_kind = sel == 1 ? 3 : sel == 2 ? 2 : sel == 3 ? 0 : chain_env;
-        const double per_seed = 0.89 * (double)g->nnz / (double)(g->n > 0 ? g->n : 1) + 6.7;
-        addends_nonneg = c1 >= 0.0 && c1 <= 1.0 && g->nonneg && ranks_nonneg;
-        scan = c1 >= 0.0 && c1 <= 1.0 && g->nonneg && ranks_nonneg &&
-               (chain_kind == 2 || (chain_kind == 1 && (double)tg * G * per_seed < scan_work));
-        if (scan) RWR_TRY(chain_scan_prepare(g, G, tg, d_seeds, s));
-        if (Zc && G == 1 && tg == 1 && addends_nonneg) RWR_TRY(sweep_prepare(g));   // single seed: the source-block sweep (sweep.hip)
+        if (cfg.scan) RWR_TRY(chain_scan_prepare(g, G, tg, d_seeds, s));
+        if (Zc && G == 1 && tg == 1 && cfg.addends_nonneg) RWR_TRY(sweep_prepare(g));   // single seed: the source-block sweep (sweep.hip)
         // (the simple one-lane reference kernel of the seed row walks the weighted in-lists itself)
-        if (Zc && chain_kind == 0 && !scan) RWR_TRY(ensure_in_w(g));
+        if (Zc && cfg.chain_kind == 0 && !cfg.scan) RWR_TRY(ensure_in_w(g));
         return RWR_OK;
     }
 
-    // last = no further step follows: the value-free path need not form the next z
-    // rows != nullptr: the SpMM produces only the nrows rows of that list (a batch's last steps);
-    // chain = false: no seed row of this step reaches a row the ranking reads, its chain is not run
-    // may_list: the caller allows this step to write only its frontier's rows (it is neither a tail-list step nor the last)
-    int32_t step(EvPool &pool, std::vector<hipEvent_t> &spmm_ev, std::vector<hipEvent_t> &chain_ev, bool last = false,
-                 const int32_t *rows = nullptr, int32_t nrows = 0, bool chain = true, bool may_list = false)
+    int32_t step(const StepPlan &p, Profile &prof)
     {
         const int32_t n = g->n;
-        hipStream_t s = g->stream, s2 = g->stream2;
-        const bool prof = g->opts.profile != 0;
+        hipStream_t s = g->stream;
         const size_t nzw = ((size_t)n + 31) / 32;
         constexpr int GATE_SLOTS = 64;
-        static const int use_gate = [] { const char *e = RWR_TUNE_ENV("RWR_GATE"); return e ? atoi(e) : 1; }();
-        static const int serial = [] { const char *e = RWR_TUNE_ENV("RWR_CHAIN_SERIAL"); return e ? atoi(e) : 0; }();
-        unsigned int *gate_it = nullptr;
-        const uint32_t *nz_in = (it < nz_iters) ? nz_cur : nullptr;
-        uint32_t *nz_out = (it + 1 < nz_iters) ? nz_oth : nullptr;
+        const uint32_t *nz_in = p.probe ? nz_cur : nullptr;
+        uint32_t *nz_out = p.write_bits ? nz_oth : nullptr;
         if (nz_out) RWR_HIP(hipMemsetAsync(nz_out, 0, (size_t)tg * nzw * sizeof(uint32_t), s));
-        uint32_t *act = (nz_in && it < act_iters) ? g->d_nz.p + 2 * (size_t)tg * nzw : nullptr;
-        // Frontier-list step: the SpMM writes only the rows of its frontier, and every other row of Y / Zn
-        // keeps whatever it held.  Allowed where the next step reads the output only through the bitmap this step writes:
-        // that step probes it (it + 1 < nz_iters) and either is itself an act step (bitmap-walking seed-row chain) or, at
-        // it = 1, writes over the cleared X_0, whose only non-zero rows -- the seed rows -- are in the list, so that its
-        // output is a whole vector for the chains that read every row.
-        const bool list_now = flist && act && may_list && !rows && !last && it + 1 < nz_iters &&
-                              (it + 1 < act_iters || it == 1);
-        int32_t *fl_rows = list_now ? g->fl_rows.p : nullptr;
-        int32_t *fl_cnt = list_now ? g->fl_rows.p + (size_t)tg * (size_t)n : nullptr;
+        uint32_t *act = p.mark ? g->d_nz.p + 2 * (size_t)tg * nzw : nullptr;
+        const bool listed = p.rows.kind == Rows::Frontier;
         if (act) {
+            int32_t *fl_rows = listed ? g->fl_rows.p : nullptr, *fl_cnt = listed ? fl_rows + (size_t)tg * (size_t)n : nullptr;
             RWR_HIP(hipMemsetAsync(act, 0, (size_t)tg * nzw * sizeof(uint32_t), s));
             if (fl_cnt) RWR_HIP(hipMemsetAsync(fl_cnt, 0, (size_t)tg * sizeof(int32_t), s));
             hipLaunchKernelGGL(k_mark_active, dim3(cdiv(nzw, 4), tg), dim3(256), 0, s, n, nz_in, act, g->rowptr.p,
                                g->dst.p, g->etype.p, G, d_seeds, fl_rows, fl_cnt);
         }
-        // rows of X / Zc outside the bitmap may be stale: the seed-row terms read through it (exact for zero rows as well)
-        const uint32_t *nz_terms = flist ? nz_in : nullptr;
-        if (serial) s2 = s;
-        // (while X is sparse the bitmap-walking chain serves a whole tile at once; for a single seed the scan is cheaper)
-        const bool scan_now = chain && scan && (!act || G == 1);
-        bool scan_side = false;
-        bool seed_z_done = false;
-        if (scan_now) {
-            // the parallel chain.  Batches: on the main stream, ahead of the SpMM (which skips the seed rows).  A single seed:
-            // on the second stream BESIDE the SpMV -- the two read the same vectors and write disjoint rows, and for one seed
-            // the chain's five small kernels take as long as the SpMV itself (C2: ~100 us each), so the step costs their
-            // maximum instead of their sum.
-            static const int side_env = [] { const char *e = RWR_TUNE_ENV("RWR_SCAN_SIDE"); return e ? atoi(e) : 1; }();
-            // (only on graphs large enough for the kernels to outlast the fork / join: measured -29 % per call at 224 K nodes,
-            //  neutral at 120 K, +19 % at 12 K)
-            scan_side = side_env && G == 1 && tg == 1 && s2 != s && g->n >= 100000;
-            hipStream_t sc = scan_side ? s2 : s;
-            if (scan_side) {
-                RWR_HIP(hipEventRecord(g->ev_fork, s));
-                RWR_HIP(hipStreamWaitEvent(s2, g->ev_fork, 0));
-            }
-            // (a single seed per tile: the chain kernels gather the link terms from z themselves and leave the seed row's next z)
-            const bool self = chain_scan_self_contained(G);
-            seed_z_done = self;
-            if (!(self && Zc)) RWR_DISPATCH_G(G, launch_seed_terms<GG>(g, tg, X, d_seeds, c1, d_evoff, sc, Zc, nz_terms));
-            hipEvent_t c0 = nullptr, c1e = nullptr;
-            if (prof) { c0 = pool.get(); c1e = pool.get(); RWR_HIP(hipEventRecord(c0, sc)); }
-            RWR_TRY(chain_scan_step(g, G, tg, X, Y, d_seeds, d_evoff, c1, nz_out, sc, self ? Zc : nullptr,
-                                    (self && Zc && !last) ? Zn : nullptr));
-            if (prof) { RWR_HIP(hipEventRecord(c1e, sc)); chain_ev.push_back(c0); chain_ev.push_back(c1e); }
-            if (scan_side) RWR_HIP(hipEventRecord(g->ev_join, s2));
-            s2 = s;
-        } else if (chain) {
-            // fork: the seed-row chain runs beside the SpMM on the second stream
-            RWR_DISPATCH_G(G, launch_seed_terms<GG>(g, tg, X, d_seeds, c1, d_evoff, s, Zc, nz_terms));
-            gate_it = (use_gate && s2 != s) ? g->d_gate.p + (it % GATE_SLOTS) : nullptr;
+        const uint32_t *nz_terms = p.terms_nz ? nz_in : nullptr;
+        double *zout = (Zc && p.form_z) ? Zn : nullptr;
+        hipStream_t sc = p.chain_side ? g->stream2 : s;   // the chain's stream
+        unsigned int *gate_it = p.gate ? g->d_gate.p + (it % GATE_SLOTS) : nullptr;
+        if (p.chain != Chain::None) {
+            // A fold: its link terms on the main stream ahead of the fork (launch_seed_terms), then the fold beside the SpMM.
+            // The binade scan: on the main stream ahead of the SpMM (which skips the seed rows), or for a single seed on the
+            // second stream beside the SpMV -- the two read the same vectors and write disjoint rows.
+            if (!p.scan()) RWR_DISPATCH_G(G, launch_seed_terms<GG>(g, tg, X, d_seeds, c1, d_evoff, s, Zc, nz_terms));
             if (gate_it) RWR_HIP(hipMemsetAsync(gate_it, 0, sizeof(unsigned int), s));
-            RWR_HIP(hipEventRecord(g->ev_fork, s));
-            if (s2 != s) RWR_HIP(hipStreamWaitEvent(s2, g->ev_fork, 0));
-            hipEvent_t c0 = nullptr, c1e = nullptr;
-            if (prof) { c0 = pool.get(); c1e = pool.get(); RWR_HIP(hipEventRecord(c0, s2)); }
-            RWR_DISPATCH_G(G, launch_chain<GG>(g, tg, X, Y, d_seeds, c1, d_evoff, nz_out, gate_it, s2, act ? nz_in : nullptr, chain_kind));
-            if (prof) { RWR_HIP(hipEventRecord(c1e, s2)); chain_ev.push_back(c0); chain_ev.push_back(c1e); }
-            RWR_HIP(hipEventRecord(g->ev_join, s2));
+            if (p.chain_side) { RWR_HIP(hipEventRecord(g->ev_fork, s)); RWR_HIP(hipStreamWaitEvent(sc, g->ev_fork, 0)); }
+            if (p.scan() && !(p.chain_self && Zc)) RWR_DISPATCH_G(G, launch_seed_terms<GG>(g, tg, X, d_seeds, c1, d_evoff, sc, Zc, nz_terms));
+            hipEvent_t c0; RWR_TRY(prof.record(c0, sc));
+            if (p.scan())
+                RWR_TRY(chain_scan_step(g, G, tg, X, Y, d_seeds, d_evoff, c1, nz_out, sc, p.chain_self ? Zc : nullptr,
+                                        p.chain_self ? zout : nullptr));
+            else
+                RWR_DISPATCH_G(G, launch_chain<GG>(g, tg, X, Y, d_seeds, c1, d_evoff, nz_out, gate_it, sc, p.chain, nz_in));
+            RWR_TRY(prof.end(prof.chain, c0, sc));
+            if (p.chain_side) RWR_HIP(hipEventRecord(g->ev_join, sc));
         }
-        if (gate_it && !scan_now) {
-            const unsigned expected = (unsigned)(tg < 192 ? tg : 192);
-            hipLaunchKernelGGL(k_gate, dim3(1), dim3(1), 0, s, gate_it, expected);
-        }
-        hipEvent_t a = nullptr, b = nullptr;
-        if (prof) { a = pool.get(); b = pool.get(); RWR_HIP(hipEventRecord(a, s)); }
-        double *zout = (Zc && !last) ? Zn : nullptr;
-        if (list_now) {
-            RWR_DISPATCH_G(G, launch_spmm_frontier<GG>(g, tg, X, Y, d_seeds, c1, nz_in, nz_out, s, fl_rows, fl_cnt, Zc, zout));
-        } else {
-            RWR_DISPATCH_G(G, launch_spmm<GG>(g, tg, X, Y, d_seeds, c1, 1, nz_in, nz_out, s, act, Zc, zout, addends_nonneg, rows, nrows));
-        }
-        // (a launch over a row list is no dense launch either: it walks only part of the matrix)
-        const bool dense = !nz_in && !rows;
-        if (prof) { RWR_HIP(hipEventRecord(b, s)); spmm_ev.push_back(a); spmm_ev.push_back(b); g->spmm_ev_dense.push_back(dense ? 1 : 0); }
-        if (dense) { g->stats.spmm_dense_launches += 1; ++dense_steps; }
-        if ((s2 != s && !scan_now && chain) || scan_side) RWR_HIP(hipStreamWaitEvent(s, g->ev_join, 0));
+        if (gate_it) hipLaunchKernelGGL(k_gate, dim3(1), dim3(1), 0, s, gate_it, (unsigned)(tg < 192 ? tg : 192));
+        hipEvent_t a; RWR_TRY(prof.record(a, s));
+        RWR_DISPATCH_G(G, launch_spmm<GG>(g, tg, X, Y, d_seeds, c1, 1, nz_in, nz_out, s, act, Zc, zout, cfg.addends_nonneg, p.rows));
+        RWR_TRY(prof.end(prof.spmm, a, s));
+        if (prof.on) prof.dense.push_back(p.dense());
+        if (p.dense()) { g->stats.spmm_dense_launches += 1; ++dense_steps; }
+        if (p.chain_side) RWR_HIP(hipStreamWaitEvent(s, g->ev_join, 0));
         // value-free path: the seed rows' own z, now that the seed-row kernel has left their rank in Y
-        if (zout && !seed_z_done && chain) hipLaunchKernelGGL(k_seed_z, dim3(cdiv((size_t)tg * G, 64)), dim3(64), 0, s, n, tg, G, Y, zout, d_seeds, g->w_src.p, c1);
+        if (zout && p.seed_z) hipLaunchKernelGGL(k_seed_z, dim3(cdiv((size_t)tg * G, 64)), dim3(64), 0, s, n, tg, G, Y, zout, d_seeds, g->w_src.p, c1);
         RWR_HIP(hipGetLastError());
         { double *t = X; X = Y; Y = t; }   // Model.updateRanks (Model.cs:103-108)
         { double *t = Zc; Zc = Zn; Zn = t; }
         { uint32_t *tz = nz_cur; nz_cur = nz_oth; nz_oth = tz; }
         g->stats.spmm_launches += 1;
-        g->stats.chain_launches += chain ? 1 : 0;
-        g->stats.frontier_list_launches += list_now ? 1 : 0;
+        g->stats.chain_launches += p.chain != Chain::None; g->stats.frontier_list_launches += listed;
         ++it;
         return RWR_OK;
     }
 };
 
-// rank_only: the caller reads nothing of the final ranks but their ITEM rows outside each seed's LIKE targets
-// (Recommender.cs:20-31), so the last steps produce only the rows that reach them; h_seeds: the group's
-// tg * G seed slots on the host (-1 = padding), whose tail flags decide which of those steps run their seed-row chain.
-//
-// The invariant of the tail plan: every row that a later step's SpMM or chain reads is written by the step before it, and a
-// stale (seed row, seed column) pair reaches only rows excluded for that seed.  Step T - k (k < tail_depth) walks tail_rows[k],
-// which holds every source of the rows step T - k + 1 walks; its chain runs only if a seed of the group has flag bit k (its
-// seed row may reach a row the ranking reads), and then, since that chain reads every row of the step before, step T - k is
-// the last restricted one.  Without any flag bit below tail_depth, steps T .. T - tail_depth + 1 are restricted and chainless,
-// and step T - tail_depth is whole.  A restricted step never writes a frontier row list, and where it also probes the frontier
-// bitmaps it reads and writes them as any other step does (it writes the bits of the rows it walks).
-int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const int64_t *d_evoff, double d,
-                      int64_t n_iter, double **final_X, EvPool &pool, std::vector<hipEvent_t> &spmm_ev,
-                      std::vector<hipEvent_t> &chain_ev, int64_t *dense_steps, bool rank_only = false,
-                      const int32_t *h_seeds = nullptr)
+// A tile group of recommend_batch: T steps of the plan.  h_seeds: the group's tg * G seed slots on the host (-1 = padding),
+// whose tail flags decide which of the last steps run their seed-row chain.
+int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const int64_t *d_evoff, const int32_t *h_seeds,
+                      double d, int64_t T, Profile &prof, double **final_X, int64_t *dense_steps)
 {
     GroupIter gi(g, G, tg, d_seeds, d_evoff, d);
     RWR_TRY(gi.init(true, true, true));
-    static const int tail_env = [] { const char *e = getenv("RWR_TAIL_ROWS"); return e ? atoi(e) : 1; }();
-    // (one seed on its own takes the single-seed SpMV, whose rows stay all rows)
-    const bool tails = rank_only && h_seeds && tail_env != 0 && !(G == 1 && tg == 1);
-    unsigned need = 0;   // bit k: some seed of the group needs its chain at step T - k
-    int last_tail = -1;  // steps T - last_tail .. T walk row lists
-    if (tails) {
+    if (gi.cfg.tails) {
         RWR_TRY(tail_rows_prepare(g));
+        gi.cfg.tail_depth = g->tail_depth;
         for (size_t q = 0; q < (size_t)tg * G; ++q)
-            if (h_seeds[q] >= 0) need |= g->h_tail_flag[h_seeds[q]];
-        last_tail = g->tail_depth - 1;
-        for (int k = 0; k < g->tail_depth; ++k)
-            if ((need >> k) & 1u) { last_tail = k; break; }
+            if (h_seeds[q] >= 0) gi.cfg.need |= g->h_tail_flag[h_seeds[q]];
     }
-    for (int64_t it = 0; it < n_iter; ++it) {
-        const int64_t k = n_iter - 1 - it;   // this is step T - k
-        const int32_t *rows = nullptr;
-        int32_t nrows = 0;
-        bool chain = true;
-        if (k <= last_tail) {
-            rows = g->tail_rows[k].p; nrows = g->tail_n[k]; chain = ((need >> k) & 1u) != 0;
-        }
-        RWR_TRY(gi.step(pool, spmm_ev, chain_ev, k == 0, rows, nrows, chain, !rows && k >= 1));
-    }
+    while (gi.it < T) RWR_TRY(gi.step(plan_step(gi.cfg, gi.it, T), prof));
     *final_X = gi.X;
     *dense_steps = gi.dense_steps;
     return RWR_OK;
@@ -1260,17 +1172,6 @@ static double now_ms()
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
-static int32_t drain_events(std::vector<hipEvent_t> &v, double *acc)
-{
-    for (size_t i = 0; i + 1 < v.size(); i += 2) {
-        float ms = 0.f;
-        RWR_HIP(hipEventElapsedTime(&ms, v[i], v[i + 1]));
-        *acc += ms;
-    }
-    v.clear();
-    return RWR_OK;
-}
-
 int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
                         int64_t *ids, double *scores, int32_t *counts, int64_t row_stride)
 {
@@ -1348,26 +1249,21 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
         RWR_HIP(hipMemcpy(g->d_slot_k.p, slot_k.data(), slot_k.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
 
-    EvPool pool;
-    std::vector<hipEvent_t> spmm_ev, chain_ev, rank_ev, iter_ev;
-    const bool prof = g->opts.profile != 0;
-    g->spmm_ev_dense.clear();
+    Profile prof(g);
     for (int t0 = 0; t0 < ntiles; t0 += TG) {
         const int tg = (ntiles - t0 < TG) ? (ntiles - t0) : TG;
         const int32_t *dseeds = g->d_seeds.p + (size_t)t0 * G;
         double *Xf = nullptr;
-        hipEvent_t i0 = nullptr, i1 = nullptr;
-        if (prof) { i0 = pool.get(); i1 = pool.get(); RWR_HIP(hipEventRecord(i0, s)); }
+        hipEvent_t i0; RWR_TRY(prof.record(i0, s));
         int64_t dense_steps = 0;
-        RWR_TRY(iterate_group(g, G, tg, dseeds, g->d_evoff.p + (size_t)t0 * G, d, n_iter, &Xf, pool, spmm_ev, chain_ev,
-                              &dense_steps, true, slot_seed.data() + (size_t)t0 * G));
-        if (prof) { RWR_HIP(hipEventRecord(i1, s)); iter_ev.push_back(i0); iter_ev.push_back(i1); }
+        RWR_TRY(iterate_group(g, G, tg, dseeds, g->d_evoff.p + (size_t)t0 * G, slot_seed.data() + (size_t)t0 * G, d, n_iter,
+                              prof, &Xf, &dense_steps));
+        RWR_TRY(prof.end(prof.iter, i0, s));
         int32_t real = 0;
         for (size_t q = (size_t)t0 * G; q < (size_t)(t0 + tg) * G; ++q) real += slot_k[q] >= 0;
         g->stats.spmm_seed_steps += (int64_t)real * n_iter;
         g->stats.spmm_dense_seed_steps += (int64_t)real * dense_steps;
-        hipEvent_t a = nullptr, b = nullptr;
-        if (prof) { a = pool.get(); b = pool.get(); RWR_HIP(hipEventRecord(a, s)); }
+        hipEvent_t a; RWR_TRY(prof.record(a, s));
         hipLaunchKernelGGL(k_exclude, dim3((unsigned)(tg * G)), dim3(64), 0, s, n, tg, G, g->rowptr.p,
                            g->dst.p, g->etype.p, Xf, dseeds);
         RWR_HIP(hipGetLastError());
@@ -1380,7 +1276,7 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
                                   dseeds + (size_t)t * G, s));
             }
         }
-        if (prof) { RWR_HIP(hipEventRecord(b, s)); rank_ev.push_back(a); rank_ev.push_back(b); }
+        RWR_TRY(prof.end(prof.rank, a, s));
     }
     if (any_dangling) RWR_TRY(emit_dangling(g, dang_rows, dang_seeds, top_n, s));
     // results: K_all x top_n (device rows are top_n wide; host rows are row_stride wide)
@@ -1396,19 +1292,8 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
     RWR_HIP(hipStreamSynchronize(s));
     RWR_HIP(hipStreamSynchronize(g->stream2));
     for (int32_t k = 0; k < K_all; ++k) counts[k] = hc[k];
-    if (prof) RWR_TRY(chain_scan_collect(g, s));
-    if (prof) {
-        for (size_t i = 0; i + 1 < spmm_ev.size(); i += 2)
-            if (i / 2 < g->spmm_ev_dense.size() && g->spmm_ev_dense[i / 2]) {
-                float ms = 0.f;
-                RWR_HIP(hipEventElapsedTime(&ms, spmm_ev[i], spmm_ev[i + 1]));
-                g->stats.spmm_dense_ms += ms;
-            }
-        RWR_TRY(drain_events(spmm_ev, &g->stats.spmm_ms));
-        RWR_TRY(drain_events(chain_ev, &g->stats.chain_ms));
-        RWR_TRY(drain_events(rank_ev, &g->stats.rank_ms));
-        RWR_TRY(drain_events(iter_ev, &g->stats.iterate_wall_ms));
-    }
+    if (prof.on) RWR_TRY(chain_scan_collect(g, s));
+    RWR_TRY(prof.fold(g));
     g->stats.tile_seeds = G;
     g->stats.tile_group = TG;
     g->stats.seeds_done += K_all;
@@ -1521,8 +1406,7 @@ int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double
     int TG = 1;
     RWR_TRY(ensure_workspace(g, G, 1, &TG));
     hipStream_t s = g->stream;
-    EvPool pool;
-    std::vector<hipEvent_t> a, b;
+    Profile prof(g);
     const int64_t max_iters = model_max_iters();
     const bool by_count = run_mode == RWR_RUN_ITERATIONS;
     // Model.cs:53: threshold = (1 / double.MaxValue) * n   (a subnormal-scale number: "until nothing changes")
@@ -1540,7 +1424,7 @@ int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double
         GroupIter gi(g, G, 1, g->d_seeds.p, g->d_evoff.p, d);
         RWR_TRY(gi.init());
         while (done < T) {
-            RWR_TRY(gi.step(pool, a, b));                                   // deliverRanks + updateRanks
+            RWR_TRY(gi.step(plan_step(gi.cfg, gi.it, -1), prof));           // deliverRanks + updateRanks
             ++done;
             if (!by_count) {                                                // checkConvergence (Model.cs:58-65)
                 // the reference's sequential sum of |rank[i] - nextRank[i]|, reproduced bit for bit by the binade scan
@@ -1553,7 +1437,7 @@ int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double
                 RWR_HIP(hipMemcpyAsync(&diff, scalar, sizeof(double), hipMemcpyDeviceToHost, s));
                 RWR_HIP(hipStreamSynchronize(s));
                 if (diff < threshold) { converged = true; break; }
-                a.clear(); b.clear(); pool.used = 0;                        // (synchronised above: safe to recycle)
+                prof.reset();                                               // (synchronised above: safe to recycle)
             }
         }
         Xf = gi.X;
@@ -1616,11 +1500,10 @@ int32_t model_deliver(rwr_graph *g, int32_t seed, double d, const double *rank_i
     double *out = nullptr;
     if (seed >= 0) {
         RWR_TRY(upload_seed_slots(g, &seed, 1, 1, nullptr));
-        EvPool pool;
-        std::vector<hipEvent_t> a, b;
+        Profile prof(g);
         GroupIter gi(g, 1, 1, g->d_seeds.p, g->d_evoff.p, d);
         RWR_TRY(gi.init(false, nonneg));
-        RWR_TRY(gi.step(pool, a, b));
+        RWR_TRY(gi.step(plan_step(gi.cfg, 0, -1), prof));
         RWR_HIP(hipStreamSynchronize(s));
         RWR_HIP(hipStreamSynchronize(g->stream2));
         out = gi.X;                                   // (step() swapped: X holds nextRank)
@@ -1716,27 +1599,7 @@ static int32_t model_run_batch_body(rwr_graph *g, const int32_t *seeds, int32_t 
     RWR_TRY(g->cs_sums.ensure((size_t)TG * G));
     RWR_TRY(g->mb_row.ensure((size_t)TG * G));
     hipStream_t s = g->stream;
-    const bool prof = g->opts.profile != 0;
-    EvPool pool;
-    std::vector<hipEvent_t> spmm_ev, chain_ev, iter_ev, ext_ev;
-    g->spmm_ev_dense.clear();
-    auto drain = [&]() -> int32_t {                          // (after a synchronisation: fold the profile events, recycle them)
-        if (prof) {
-            for (size_t i = 0; i + 1 < spmm_ev.size(); i += 2)
-                if (i / 2 < g->spmm_ev_dense.size() && g->spmm_ev_dense[i / 2]) {
-                    float ms = 0.f;
-                    RWR_HIP(hipEventElapsedTime(&ms, spmm_ev[i], spmm_ev[i + 1]));
-                    g->stats.spmm_dense_ms += ms;
-                }
-            RWR_TRY(drain_events(spmm_ev, &g->stats.spmm_ms));
-            RWR_TRY(drain_events(chain_ev, &g->stats.chain_ms));
-            RWR_TRY(drain_events(iter_ev, &g->stats.iterate_wall_ms));
-            RWR_TRY(drain_events(ext_ev, &g->stats.rank_ms));
-        }
-        spmm_ev.clear(); chain_ev.clear(); g->spmm_ev_dense.clear();
-        pool.used = 0;
-        return RWR_OK;
-    };
+    Profile prof(g);                                         // (column extraction counts as ranking time)
     std::vector<int32_t> row_of;
     std::vector<double> dist;
     for (int t0 = 0; t0 < ntiles; t0 += TG) {
@@ -1766,18 +1629,17 @@ static int32_t model_run_batch_body(rwr_graph *g, const int32_t *seeds, int32_t 
                 }
                 if (m > 0) {
                     RWR_HIP(hipMemcpyAsync(g->mb_row.p, row_of.data(), nslots * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                    hipEvent_t a = nullptr, b = nullptr;
-                    if (prof) { a = pool.get(); b = pool.get(); RWR_HIP(hipEventRecord(a, s)); }
+                    hipEvent_t a; RWR_TRY(prof.record(a, s));
                     RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_extract_cols<GG>, dim3(cdiv((size_t)n, EX_ELEMS / GG), (unsigned)tg),
                                                          dim3(256), 0, s, n, gi.X, g->mb_row.p, g->cs_diff.p));
                     RWR_HIP(hipGetLastError());
-                    if (prof) { RWR_HIP(hipEventRecord(b, s)); ext_ev.push_back(a); ext_ev.push_back(b); }
+                    RWR_TRY(prof.end(prof.rank, a, s));
                     for (size_t q = 0; q < nslots; ++q)
                         if (row_of[q] >= 0)
                             RWR_HIP(hipMemcpyAsync(rank_out + (size_t)slot_k[q0 + q] * n, g->cs_diff.p + (size_t)row_of[q] * n,
                                                    sizeof(double) * n, hipMemcpyDeviceToHost, s));
                     RWR_HIP(hipStreamSynchronize(s));
-                    RWR_TRY(drain());
+                    RWR_TRY(prof.fold(g));
                     live -= m;
                 }
                 if (live == 0) break;
@@ -1787,21 +1649,20 @@ static int32_t model_run_batch_body(rwr_graph *g, const int32_t *seeds, int32_t 
                 RWR_HIP(hipStreamSynchronize(g->stream2));
                 return RWR_E_UNSUPPORTED;
             }
-            hipEvent_t i0 = nullptr, i1 = nullptr;
-            if (prof) { i0 = pool.get(); i1 = pool.get(); RWR_HIP(hipEventRecord(i0, s)); }
-            RWR_TRY(gi.step(pool, spmm_ev, chain_ev, by_count && steps + 1 == T));   // deliverRanks + updateRanks
+            hipEvent_t i0; RWR_TRY(prof.record(i0, s));
+            RWR_TRY(gi.step(plan_step(gi.cfg, steps, by_count ? T : -1), prof));   // deliverRanks + updateRanks
             ++steps;
             if (!by_count) {                                 // checkConvergence of every column (Model.cs:58-65, 110-115)
                 hipLaunchKernelGGL(k_absdiff_mat, dim3(std::min<size_t>(cdiv(elems, 256), 16384)), dim3(256), 0, s, gi.Y, gi.X,
                                    (int64_t)elems, g->cs_diff.p);
                 RWR_TRY(chain_scan_sum_cols(g, G, tg, g->cs_diff.p, evoff, g->cs_sums.p, s));
             }
-            if (prof) { RWR_HIP(hipEventRecord(i1, s)); iter_ev.push_back(i0); iter_ev.push_back(i1); }
+            RWR_TRY(prof.end(prof.iter, i0, s));
             if (!by_count) {
                 dist.resize(nslots);
                 RWR_HIP(hipMemcpyAsync(dist.data(), g->cs_sums.p, nslots * sizeof(double), hipMemcpyDeviceToHost, s));
                 RWR_HIP(hipStreamSynchronize(s));
-                RWR_TRY(drain());
+                RWR_TRY(prof.fold(g));
             }
         }
         g->stats.spmm_seed_steps += (int64_t)real * steps;
@@ -1809,8 +1670,8 @@ static int32_t model_run_batch_body(rwr_graph *g, const int32_t *seeds, int32_t 
     }
     RWR_HIP(hipStreamSynchronize(s));
     RWR_HIP(hipStreamSynchronize(g->stream2));
-    RWR_TRY(drain());
-    if (prof) RWR_TRY(chain_scan_collect(g, s));
+    RWR_TRY(prof.fold(g));
+    if (prof.on) RWR_TRY(chain_scan_collect(g, s));
     g->stats.tile_seeds = G;
     g->stats.tile_group = TG;
     g->stats.total_wall_ms += now_ms() - t_begin;
