@@ -2,7 +2,6 @@
 // usable gfx950 device every compute entry fails with RWR_E_NO_DEVICE.
 #include <stdarg.h>
 #include <algorithm>
-#include <chrono>
 #include <mutex>
 #include <vector>
 #include <stdlib.h>
@@ -34,13 +33,6 @@ static int usable_devices()
 
 // "is device d a gfx950" -- asked once per device and process: hipGetDeviceProperties goes to the driver under a runtime-wide
 // lock, and the reference's harness creates a graph per fold and methodology from ten threads (Program.cs:11)
-#ifdef RWR_EXPERIMENTS
-static double now_ms()
-{
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-#endif
 static int32_t check_gfx950(int device)
 {
     static std::mutex mu;
@@ -577,7 +569,6 @@ int32_t rwr_eval_graphs(int32_t count, const rwr_graph_desc *graphs, const int32
                 g->n = graphs[i].n_nodes;
                 g->nnz_raw = graphs[i].rowptr[graphs[i].n_nodes];
                 g->stream = kit.stream;
-                g->borrowed = 1;
                 g->stats.struct_size = sizeof(rwr_stats);
                 gs.push_back(g);
             }

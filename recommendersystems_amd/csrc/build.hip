@@ -1167,7 +1167,8 @@ int32_t tail_rows_prepare(rwr_graph *g)
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// A batch of ego-network-sized graphs built with ONE launch (rwr_eval_graphs, multi.hip).  The reference builds one such
+// A batch of ego-network-sized graphs built with ONE launch (rwr_eval_graphs in api.hip: graphs_build_multi here, then
+// recommend_small_multi in small.hip and eval_ranked_multi in rank.hip).  The reference builds one such
 // graph per fold and methodology (Experiment.cs:69-105) and ten of its threads do so at once (Program.cs:11); handled one
 // graph per call that is two synchronisations and a dozen runtime calls per graph, and the threads queue up behind the
 // runtime rather than the GPU.  Here every graph of the batch gets a workgroup of k_build_small_multi: one H2D copy of all

@@ -92,11 +92,11 @@ struct rwr_graph {
     rwr::DevBuf<int32_t> sm_tab;      // small.hip: places of the seed row's addends (per call)
     void *sm_pin = nullptr;           // small.hip: pinned host buffer the one-launch kernel writes the ranked list into
     void *sm_stage = nullptr;         // build.hip: pinned staging buffer of an ego-network-sized graph's upload / read-back
-    // a handle built as part of a batch (multi.hip): its staging slot and read-back area lie in the batch's pinned arena, the
-    // device-side landing area in the batch's one buffer (one H2D copy for all graphs); none of them is owned by the handle
+    // a handle built as part of a batch (rwr_eval_graphs in api.hip; graphs_build_multi in build.hip, recommend_small_multi in
+    // small.hip): its staging slot and read-back area lie in the batch's pinned arena, the device-side landing area in the
+    // batch's one buffer (one H2D copy for all graphs); none of them is owned by the handle
     uint8_t *sm_out = nullptr;
     const uint8_t *stage_dev_ext = nullptr;
-    int32_t borrowed = 0;             // streams / events / pinned buffers belong to the batch context, not to this handle
     rwr::DevBuf<uint8_t> d_stage;     // ... and its device-side landing area
     int32_t sm_pin_count = -1;        // >= 0: the last single-seed call left its list (that many entries) in sm_pin
     rwr::DevBuf<double> Z0, Z1;       // value-free path: z = ((1-d) x) * w_src of the current / next ranks, same layout
@@ -146,6 +146,20 @@ struct rwr_graph {
 
 namespace rwr {
 
+// CALL with GG = the tile width G as a constant expression (a power of two <= 64)
+#define RWR_DISPATCH_G(G, CALL)                          \
+    switch (G) {                                         \
+        case 1: { constexpr int GG = 1; CALL; } break;   \
+        case 2: { constexpr int GG = 2; CALL; } break;   \
+        case 4: { constexpr int GG = 4; CALL; } break;   \
+        case 8: { constexpr int GG = 8; CALL; } break;   \
+        case 16: { constexpr int GG = 16; CALL; } break; \
+        case 32: { constexpr int GG = 32; CALL; } break; \
+        default: { constexpr int GG = 64; CALL; } break; \
+    }
+
+double now_ms();   // recommend.hip: a steady clock, for the wall times of rwr_stats
+
 // Node count from which a graph counts as "beyond the L2s" (its rank vector no longer fits them): two-phase row order of
 // the single-seed SpMV, one more frontier iteration, 32-seed tiles.
 // RWR_BIG_N overrides the default of 2 M so that small test graphs can reach the same code paths.
@@ -174,7 +188,7 @@ int32_t recommend_small_multi(rwr_graph **gs, const int32_t *seeds, int32_t coun
 int32_t eval_ranked_multi(rwr_graph **gs, int32_t count, const int64_t *test_ptr_host, const int64_t *test_sorted_host,
                           int64_t *n_hits, double *sum_precision, int64_t *list_len, hipStream_t s);
 
-// runs the power iteration for K seeds and leaves, per seed, the ranked list
+// recommend.hip: runs the power iteration for K seeds and leaves, per seed, the ranked list
 // (mode 0: top-k into host arrays; mode 1: full rank vector of one seed)
 int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
                         int64_t *ids, double *scores, int32_t *counts, int64_t row_stride);
@@ -182,12 +196,23 @@ int32_t eval_ranked(rwr_graph *g, int32_t cnt, const int64_t *test_sorted_host, 
                     double *sum_precision);
 int32_t eval_ranked_batch(rwr_graph *g, int32_t K, int64_t row_stride, const int64_t *test_ptr_host,
                           const int64_t *test_sorted_host, int64_t *n_hits, double *sum_precision);
+// rank.hip: the exclusion (k_exclude: X[tile][n][G], one seed per slot, -1 = none) and the ranking of a tile group / one tile
+void launch_exclude(rwr_graph *g, int G, int tg, double *X, const int32_t *d_seeds, hipStream_t s);
+int32_t rank_group_select(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, const double *X,
+                          const int32_t *d_seeds, hipStream_t s);
+int rank_select_max_k();
+int32_t emit_dangling(rwr_graph *g, const std::vector<int32_t> &rows, const std::vector<int32_t> &seeds, int32_t top_n,
+                      hipStream_t s);
+int32_t rank_tile(rwr_graph *g, int G, const int32_t *d_slot_k_tile, int32_t top_n, const double *X,
+                  const int32_t *d_seeds_tile, hipStream_t s);
+// partition.hip: the row-partitioned mode (rwr_part_*)
 int32_t part_begin(rwr_graph *g, int32_t lo, int32_t hi, const int32_t *seeds, int32_t K, double d, double *x,
                    int32_t *G_out);
 int32_t part_local_step(rwr_graph *g, const double *x, double *y, double *r);
 int32_t part_step(rwr_graph *g, const double *x, double *y, hipStream_t stream);
 int32_t part_finish_step(rwr_graph *g, double *y, const double *r);
 int32_t part_rank(rwr_graph *g, double *x, int32_t top_n, int64_t *ids, double *scores, int32_t *counts);
+// model.hip: Model.run / deliverRanks (seed -1: the global model)
 int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double value, double *rank_out,
                   int64_t *iters_out);
 int32_t model_deliver(rwr_graph *g, int32_t seed, double d, const double *rank_in, double *next_out);
@@ -198,14 +223,26 @@ int32_t model_run_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
 int32_t model_run_restart(rwr_graph *g, const double *v, const double *rank_in, double d, int32_t run_mode, double value,
                           double *rank_out, int64_t *iters_out);
 int32_t model_deliver_restart(rwr_graph *g, const double *v, double d, const double *rank_in, double *next_out);
-// iterate.hip pieces it shares with the global model: the link-only single-row SpMV (no_seed: a device int32 holding -1),
-// the tree-summed restart mass and |a - b| sums into *total (partials in g->d_part[0, MODEL_RED_PARTS)), |a - b| per node
+// model.hip pieces restart.hip runs as well.  A run's end condition (Model.run(int) / run(double) / run(), Model.cs:52-66):
+// T steps at most; !by_count: until checkConvergence's distance is < threshold, a failure after max_iters = RWR_MAX_ITERS steps
+struct RunEnd {
+    bool by_count;
+    double threshold;
+    int64_t T, max_iters;
+    RunEnd(int32_t run_mode, double value, int32_t n);
+};
+int64_t model_max_iters();
+// the tree-summed restart mass and |a - b| sums into *total (partials in g->d_part[0, MODEL_RED_PARTS), which the caller
+// sizes to MODEL_RED_PARTS + 8: model_scalar() is the cell behind the partials), |a - b| per node
 constexpr int MODEL_RED_PARTS = 256;
-void launch_linkonly_spmv(rwr_graph *g, const double *X, double *Y, const int32_t *no_seed, double c1, bool hub_scan,
-                          hipStream_t s);
+inline double *model_scalar(rwr_graph *g) { return g->d_part.p + MODEL_RED_PARTS; }
 void launch_restart_mass(rwr_graph *g, const double *X, double c1, double *total, hipStream_t s);
 void launch_l1(rwr_graph *g, const double *a, const double *b, int32_t n, double *total, hipStream_t s);
 void launch_absdiff(const double *a, const double *b, int32_t n, double *out, hipStream_t s);
+// checkConvergence (Model.cs:110-115) of two rank vectors on g->stream, read back (one synchronisation): the reference's
+// sequential sum bit for bit (binade scan), or the tree sum (tolerance parity: global model, wide restart vectors)
+int32_t converge_exact(rwr_graph *g, const double *a, const double *b, double *dist);
+int32_t converge_tree(rwr_graph *g, const double *a, const double *b, double *dist);
 // spmv.hip: single-seed SpMV (list-order sums, rows binned by in-degree)
 // (zin != nullptr: value-free form -- gathers zin, reads no per-entry value; zout (may be nullptr) receives the next z)
 // (hub_scan: every addend is known to be >= 0 and finite -- weights, ranks and 1-d -- so that rows of >= 2048 in-links may

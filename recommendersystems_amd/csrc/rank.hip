@@ -450,16 +450,27 @@ __global__ __launch_bounds__(256) void k_rank_small(int32_t n_items, const int32
     }
 }
 
-#define RWR_DISPATCH_G(G, CALL)                          \
-    switch (G) {                                         \
-        case 1: { constexpr int GG = 1; CALL; } break;   \
-        case 2: { constexpr int GG = 2; CALL; } break;   \
-        case 4: { constexpr int GG = 4; CALL; } break;   \
-        case 8: { constexpr int GG = 8; CALL; } break;   \
-        case 16: { constexpr int GG = 16; CALL; } break; \
-        case 32: { constexpr int GG = 32; CALL; } break; \
-        default: { constexpr int GG = 64; CALL; } break; \
-    }
+// Recommender.cs:20-24,29: the seed's RAW out-links of type LIKE are not candidates.
+// Marked by overwriting their (final) score with -1 -- valid scores are >= 0.
+__global__ __launch_bounds__(64) void k_exclude(int32_t n, int ntiles, int G, const int64_t *__restrict__ rowptr,
+                                                const int32_t *__restrict__ dst, const uint8_t *__restrict__ etype,
+                                                double *__restrict__ X, const int32_t *__restrict__ seeds)
+{
+    // one wave per seed slot, the lanes stride over the seed's raw out-links
+    const int q = blockIdx.x;
+    if (q >= ntiles * G) return;
+    const int32_t s = seeds[q];
+    if (s < 0) return;
+    double *x = X + (size_t)(q / G) * (size_t)n * G + (q % G);
+    const int64_t p1 = rowptr[s + 1];
+    for (int64_t p = rowptr[s] + threadIdx.x; p < p1; p += WAVE)
+        if (etype[p] == RWR_EDGE_LIKE) x[(size_t)dst[p] * G] = -1.0;
+}
+void launch_exclude(rwr_graph *g, int G, int tg, double *X, const int32_t *d_seeds, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_exclude, dim3((unsigned)(tg * G)), dim3(64), 0, s, g->n, tg, G, g->rowptr.p, g->dst.p, g->etype.p, X,
+                       d_seeds);
+}
 
 int32_t rank_tile(rwr_graph *g, int G, const int32_t *d_slot_k_tile, int32_t top_n, const double *X,
                   const int32_t *d_seeds_tile, hipStream_t s)

@@ -12,7 +12,7 @@
 #include <cmath>
 #include <new>
 
-#include "engine.h"
+#include "iterate.h"
 
 namespace rwr {
 
@@ -189,11 +189,7 @@ static int32_t model_restart_body(rwr_graph *g, const double *v, const double *r
         if (v[i] != 0.0) { sup.push_back(i); vs.push_back(v[i]); }
     const int32_t nsup = (int32_t)sup.size();
     const bool exact = nsup <= RWR_RESTART_EXACT_MAX;
-    const bool by_count = run_mode == RWR_RUN_ITERATIONS;
-    const double threshold = run_mode == RWR_RUN_DEFAULT_THRESHOLD ? (1 / 1.7976931348623157e308) * n : value;   // Model.cs:53
-    static const int64_t max_iters = [] { const char *e = getenv("RWR_MAX_ITERS"); return e ? atoll(e) : (int64_t)1000000; }();
-    int64_t T = by_count ? (int64_t)value : max_iters;
-    if (T < 0) T = 0;
+    const RunEnd end(run_mode, value, n);
     const double c1 = 1 - d;
     // every link addend >= 0 and finite (over a run the ranks stay >= 0 only when v >= 0 too): the SpMV may then sum hub rows
     // by the exact parallel reduction; otherwise its general kernels run (as rwr_model_deliver does for negative ranks)
@@ -208,7 +204,6 @@ static int32_t model_restart_body(rwr_graph *g, const double *v, const double *r
     RWR_TRY(g->Y.ensure((size_t)n));
     RWR_TRY(g->d_seeds.ensure(1));
     RWR_TRY(g->d_part.ensure(MODEL_RED_PARTS + 8));
-    double *scalar = g->d_part.p + MODEL_RED_PARTS;
     const int32_t no_seed = -1;
     RWR_HIP(hipMemcpyAsync(g->d_seeds.p, &no_seed, sizeof(int32_t), hipMemcpyHostToDevice, s));
     if (exact && nsup > 0) {
@@ -222,15 +217,13 @@ static int32_t model_restart_body(rwr_graph *g, const double *v, const double *r
         RWR_TRY(d_v.alloc((size_t)n));
         RWR_HIP(hipMemcpyAsync(d_v.p, v, sizeof(double) * n, hipMemcpyHostToDevice, s));
     }
-    if (exact && !by_count) {
-        RWR_TRY(g->cs_diff.ensure((size_t)n));
-        RWR_TRY(g->d_evterm.ensure(1));
-    }
     double *X = g->X.p, *Y = g->Y.p;
+    SpmmArgs sp;                                                     // the link-only SpMV: no seed row, every row's links
+    sp.seeds = g->d_seeds.p, sp.c1 = c1, sp.hub_scan = hub_scan;
     RWR_HIP(hipMemcpyAsync(X, rank_in, sizeof(double) * n, hipMemcpyHostToDevice, s));
     int64_t done = 0;
     bool converged = false;
-    while (done < T) {
+    while (done < end.T) {
         if (exact) {
             if (nsup > 0) {                                          // the support rows' chains beside the SpMV
                 RWR_HIP(hipEventRecord(g->ev_fork, s));
@@ -240,35 +233,30 @@ static int32_t model_restart_body(rwr_graph *g, const double *v, const double *r
                 RWR_HIP(hipGetLastError());
                 RWR_HIP(hipEventRecord(g->ev_join, s2));
             }
-            launch_linkonly_spmv(g, X, Y, g->d_seeds.p, c1, hub_scan, s);
+            sp.X = X, sp.Y = Y;
+            launch_spmm(g, 1, 1, sp, s);
             if (nsup > 0) {
                 RWR_HIP(hipStreamWaitEvent(s, g->ev_join, 0));
                 hipLaunchKernelGGL(k_restart_scatter, dim3(cdiv((size_t)nsup, 256)), dim3(256), 0, s, nsup, d_sup.p, d_fold.p, Y);
             }
         } else {
-            launch_restart_mass(g, X, c1, scalar, s);
-            launch_linkonly_spmv(g, X, Y, g->d_seeds.p, c1, hub_scan, s);
-            hipLaunchKernelGGL(k_add_restart_vec, dim3(cdiv((size_t)n, 256)), dim3(256), 0, s, Y, n, scalar, d_v.p);
+            launch_restart_mass(g, X, c1, model_scalar(g), s);
+            sp.X = X, sp.Y = Y;
+            launch_spmm(g, 1, 1, sp, s);
+            hipLaunchKernelGGL(k_add_restart_vec, dim3(cdiv((size_t)n, 256)), dim3(256), 0, s, Y, n, model_scalar(g), d_v.p);
         }
         RWR_HIP(hipGetLastError());
         { double *t = X; X = Y; Y = t; }
         ++done;
-        if (!by_count) {                                             // checkConvergence (Model.cs:58-65, 110-115)
-            if (exact) {
-                // the reference's sequential sum of |rank - nextRank|, bit for bit (same iteration count)
-                launch_absdiff(X, Y, n, g->cs_diff.p, s);
-                RWR_TRY(chain_scan_sum(g, g->cs_diff.p, scalar, s));
-            } else {
-                launch_l1(g, X, Y, n, scalar, s);
-            }
+        if (!end.by_count) {                                         // checkConvergence (Model.cs:58-65, 110-115)
+            // exact: the reference's sequential sum of |rank - nextRank|, bit for bit (same iteration count)
             double diff = 0;
-            RWR_HIP(hipMemcpyAsync(&diff, scalar, sizeof(double), hipMemcpyDeviceToHost, s));
-            RWR_HIP(hipStreamSynchronize(s));
-            if (diff < threshold) { converged = true; break; }
+            RWR_TRY(exact ? converge_exact(g, X, Y, &diff) : converge_tree(g, X, Y, &diff));
+            if (diff < end.threshold) { converged = true; break; }
         }
     }
-    if (!by_count && !converged) {
-        set_error("%s: no convergence within %lld iterations (RWR_MAX_ITERS)", who, (long long)max_iters);
+    if (!end.by_count && !converged) {
+        set_error("%s: no convergence within %lld iterations (RWR_MAX_ITERS)", who, (long long)end.max_iters);
         return RWR_E_UNSUPPORTED;
     }
     RWR_HIP(hipMemcpyAsync(rank_out, X, sizeof(double) * n, hipMemcpyDeviceToHost, s));

@@ -256,7 +256,7 @@ __device__ __forceinline__ void small_rwr_body(
         __builtin_memcpy(&sv, &u, 8);
         out_id[i] = id;
         out_score[i] = sv;
-        if (pin_id) {                                  // (a batch of graphs keeps its lists on the device: multi.hip)
+        if (pin_id) {                                  // (a batch of graphs keeps its lists on the device: recommend_small_multi)
             pin_id[i] = id;
             pin_score[i] = sv;
         }

@@ -7,7 +7,8 @@ set -e
 root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/build/asan
 mkdir -p $out
-for f in api build iterate spmv sweep small chain_scan rank sort; do
+for f in $(make -s -C $root/recommendersystems_amd/csrc print-srcs); do
+  f=${f%.hip}
   /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fno-gpu-flush-denormals-to-zero \
       -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer \
       -c $root/recommendersystems_amd/csrc/$f.hip -o $out/$f.o &
