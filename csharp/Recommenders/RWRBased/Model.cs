@@ -2,7 +2,8 @@
 // the GPU through rwr_model_run and leave the result in `rank` exactly as the reference does; deliverRanks() is one
 // propagation on the GPU (rwr_model_deliver), updateRanks()/checkConvergence() are the reference's array loops.
 // A host-edited `restart` (a public field of the reference, Model.cs:12) takes rwr_model_run_restart /
-// rwr_model_deliver_restart instead.  The static RunBatch (an addition) runs many seeds' models in one rwr_model_run_batch call.
+// rwr_model_deliver_restart instead.  The static RunBatch (an addition) runs many seeds' models in one rwr_model_run_batch call,
+// RunRestartBatch many restart vectors' models in one rwr_model_run_restart_batch call.
 namespace Recommenders.RWRBased {
     public class Model {
         public Graph graph;
@@ -83,6 +84,51 @@ namespace Recommenders.RWRBased {
             var flat = new double[(long)K * n];
             iterations = new long[K];
             Native.Check(Native.rwr_model_run_batch(graph.handle, seeds, K, dampingFactor, mode, value, flat, iterations));
+            var ranks = new double[K][];
+            for (int k = 0; k < K; k++) {
+                ranks[k] = new double[n];
+                System.Array.Copy(flat, (long)k * n, ranks[k], 0, n);
+            }
+            return ranks;
+        }
+
+        // K models with caller-set restart vectors in one call (rwr_model_run_restart_batch), an addition beside the reference
+        // surface: vector k has restart[nodes[k][j]] = weights[k][j] and zero elsewhere; start[k] >= 0 is the state of
+        // new Model(graph, dampingFactor, start[k]), -1 (or start == null) that of new Model(graph, dampingFactor).
+        // ranks[k] and iterations[k] are what that Model leaves after its restart field was set and run(...) called
+        public static double[][] RunRestartBatch(Graph graph, double dampingFactor, int[][] nodes, double[][] weights,
+                                                 int[] start, int nIterations, out long[] iterations) {
+            return RunRestartBatch(graph, dampingFactor, nodes, weights, start, 0, nIterations, out iterations);
+        }
+        public static double[][] RunRestartBatch(Graph graph, double dampingFactor, int[][] nodes, double[][] weights,
+                                                 int[] start, double threshold, out long[] iterations) {
+            return RunRestartBatch(graph, dampingFactor, nodes, weights, start, 1, threshold, out iterations);
+        }
+        public static double[][] RunRestartBatch(Graph graph, double dampingFactor, int[][] nodes, double[][] weights,
+                                                 int[] start, out long[] iterations) {
+            return RunRestartBatch(graph, dampingFactor, nodes, weights, start, 2, 0, out iterations);
+        }
+        static double[][] RunRestartBatch(Graph graph, double dampingFactor, int[][] nodes, double[][] weights, int[] start,
+                                          int mode, double value, out long[] iterations) {
+            int K = nodes.Length, n = graph.size();
+            if (weights.Length != K || (start != null && start.Length != K))
+                throw new System.ArgumentException("nodes, weights and start must hold one entry per vector");
+            var ptr = new long[K + 1];
+            for (int k = 0; k < K; k++) {
+                if (nodes[k].Length != weights[k].Length)
+                    throw new System.ArgumentException("a restart vector's nodes and weights differ in length");
+                ptr[k + 1] = ptr[k] + nodes[k].Length;
+            }
+            var idx = new int[ptr[K]];
+            var val = new double[ptr[K]];
+            for (int k = 0; k < K; k++) {
+                System.Array.Copy(nodes[k], 0, idx, ptr[k], nodes[k].Length);
+                System.Array.Copy(weights[k], 0, val, ptr[k], weights[k].Length);
+            }
+            var flat = new double[(long)K * n];
+            iterations = new long[K];
+            Native.Check(Native.rwr_model_run_restart_batch(graph.handle, K, ptr, idx, val, start, dampingFactor, mode, value, flat,
+                                                            iterations));
             var ranks = new double[K][];
             for (int k = 0; k < K; k++) {
                 ranks[k] = new double[n];

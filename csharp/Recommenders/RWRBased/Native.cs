@@ -59,6 +59,9 @@ namespace Recommenders.RWRBased {
         [DllImport(Lib)] public static extern int rwr_model_run_batch(GraphHandle g, int[] seeds, int K, double d, int run_mode,
             double value, double[] rank_out, long[] iters_out);
 
+        [DllImport(Lib)] public static extern int rwr_model_run_restart_batch(GraphHandle g, int K, long[] sup_ptr, int[] sup_idx,
+            double[] sup_val, int[] start, double d, int run_mode, double value, double[] rank_out, long[] iters_out);
+
         [DllImport(Lib)] public static extern int rwr_model_run_restart(GraphHandle g, double[] restart, double[] rank_in, double d,
             int run_mode, double value, double[] rank_out, out long iters_out);
 

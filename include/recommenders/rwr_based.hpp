@@ -170,6 +170,26 @@ public:
                                                      std::vector<int64_t> *iterations = nullptr)
     { return runBatch_(g, d, seeds, RWR_RUN_DEFAULT_THRESHOLD, 0, iterations); }
 
+    // K models with caller-set restart vectors in one call (rwr_model_run_restart_batch), an addition beside the reference
+    // surface: vector k has restart[nodes[k][j]] = weights[k][j] and zero elsewhere; start[k] >= 0 is the state of
+    // Model(g, d, start[k]), -1 (or an empty start) that of Model(g, d).  ranks[k] / iterations[k] are what that Model leaves
+    // after its restart field was set and run(...) called
+    static std::vector<std::vector<double>> runRestartBatch(Graph &g, double d, const std::vector<std::vector<int>> &nodes,
+                                                            const std::vector<std::vector<double>> &weights,
+                                                            const std::vector<int> &start, int nIterations,
+                                                            std::vector<int64_t> *iterations = nullptr)
+    { return runRestartBatch_(g, d, nodes, weights, start, RWR_RUN_ITERATIONS, nIterations, iterations); }
+    static std::vector<std::vector<double>> runRestartBatch(Graph &g, double d, const std::vector<std::vector<int>> &nodes,
+                                                            const std::vector<std::vector<double>> &weights,
+                                                            const std::vector<int> &start, double threshold,
+                                                            std::vector<int64_t> *iterations = nullptr)
+    { return runRestartBatch_(g, d, nodes, weights, start, RWR_RUN_THRESHOLD, threshold, iterations); }
+    static std::vector<std::vector<double>> runRestartBatch(Graph &g, double d, const std::vector<std::vector<int>> &nodes,
+                                                            const std::vector<std::vector<double>> &weights,
+                                                            const std::vector<int> &start,
+                                                            std::vector<int64_t> *iterations = nullptr)
+    { return runRestartBatch_(g, d, nodes, weights, start, RWR_RUN_DEFAULT_THRESHOLD, 0, iterations); }
+
     void run() { run_(RWR_RUN_DEFAULT_THRESHOLD, 0); }         // :52-55
     void run(double threshold) { run_(RWR_RUN_THRESHOLD, threshold); }   // :57-66
     void run(int nIterations) { run_(RWR_RUN_ITERATIONS, nIterations); } // :68-73
@@ -205,6 +225,35 @@ private:
         std::vector<double> flat((size_t)K * n);
         std::vector<int64_t> it((size_t)K);
         check(rwr_model_run_batch(g.handle(), seeds.data(), K, d, run_mode, value, flat.data(), it.data()));
+        std::vector<std::vector<double>> ranks((size_t)K);
+        for (int32_t k = 0; k < K; ++k) ranks[k].assign(flat.begin() + (ptrdiff_t)(k * n), flat.begin() + (ptrdiff_t)((k + 1) * n));
+        if (iterations) *iterations = it;
+        return ranks;
+    }
+    static std::vector<std::vector<double>> runRestartBatch_(Graph &g, double d, const std::vector<std::vector<int>> &nodes,
+                                                             const std::vector<std::vector<double>> &weights,
+                                                             const std::vector<int> &start, int run_mode, double value,
+                                                             std::vector<int64_t> *iterations)
+    {
+        const int32_t K = (int32_t)nodes.size();
+        const size_t n = (size_t)g.size();
+        if (weights.size() != nodes.size() || (!start.empty() && start.size() != nodes.size()))
+            throw std::invalid_argument("runRestartBatch: nodes, weights and start must hold one entry per vector");
+        std::vector<int64_t> ptr((size_t)K + 1, 0);
+        std::vector<int32_t> idx;
+        std::vector<double> val;
+        for (int32_t k = 0; k < K; ++k) {
+            if (nodes[k].size() != weights[k].size())
+                throw std::invalid_argument("runRestartBatch: a restart vector's nodes and weights differ in length");
+            idx.insert(idx.end(), nodes[k].begin(), nodes[k].end());
+            val.insert(val.end(), weights[k].begin(), weights[k].end());
+            ptr[(size_t)k + 1] = (int64_t)idx.size();
+        }
+        std::vector<int32_t> st(start.begin(), start.end());
+        std::vector<double> flat((size_t)K * n);
+        std::vector<int64_t> it((size_t)K);
+        check(rwr_model_run_restart_batch(g.handle(), K, ptr.data(), idx.data(), val.data(), st.empty() ? nullptr : st.data(), d,
+                                          run_mode, value, flat.data(), it.data()));
         std::vector<std::vector<double>> ranks((size_t)K);
         for (int32_t k = 0; k < K; ++k) ranks[k].assign(flat.begin() + (ptrdiff_t)(k * n), flat.begin() + (ptrdiff_t)((k + 1) * n));
         if (iterations) *iterations = it;

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RWR_VERSION_STRING "0.3.0"
+#define RWR_VERSION_STRING "0.4.0"
 
 /* status codes */
 enum {
@@ -283,6 +283,29 @@ int32_t rwr_model_run_restart(rwr_graph *g, const double *restart, const double 
 /* ONE deliverRanks() with a caller-set restart vector (as rwr_model_deliver; rank and next_rank may alias) */
 int32_t rwr_model_deliver_restart(rwr_graph *g, const double *restart, double d,
                                   const double *rank, double *next_rank);
+/* K Models with caller-set restart vectors (Model.restart, Model.cs:12) run in one call -- an addition beside the reference
+ * surface.  Vector k has the non-zero entries restart[sup_idx[q]] = sup_val[q], q in [sup_ptr[k], sup_ptr[k+1]), zero elsewhere.
+ * start[k] >= 0: the personalised constructor's rank (Model.cs:44: n at start[k], 0 elsewhere); start[k] == -1: the global
+ * constructor's (Model.cs:25: every rank 1).  start == NULL: all -1.
+ * Row k of rank_out (K x n, row-major) and iters_out[k] are what
+ *     rwr_model_run_restart(g, dense(v_k), rank0_k, d, run_mode, value, ...)
+ * returns: bitwise whenever that call is bitwise (at most RWR_RESTART_EXACT_MAX non-zero entries), for every run_mode.
+ *   - Argument errors, all found before any device work: a NULL g, K < 0, a NULL sup_ptr or rank_out, NULL sup_idx or
+ *     sup_val while sup_ptr[K] > 0, a sup_ptr that does not start at 0 or that decreases, an unknown run_mode, or the same
+ *     index twice within one vector (which a dense vector cannot express; the message carries k and the index) give
+ *     RWR_E_INVALID; an index outside [0, n) or a start[k] outside [-1, n) gives RWR_E_RANGE with the batch position in the
+ *     message; a non-finite sup_val gives RWR_E_UNSUPPORTED, as rwr_model_run_restart does.  K == 0 is a no-op (RWR_OK).
+ *   - An entry whose value is +-0.0 is dropped (-0.0 counts as zero); an empty support is legal (a link-only walk).
+ *   - Threshold modes: each vector stops at its own step (the reference's sequential |diff| sum, Model.cs:58-65, 110-115).
+ *     A vector that does not converge within RWR_MAX_ITERS fails the whole call with RWR_E_UNSUPPORTED; the message names
+ *     the smallest such k.  iters_out may be NULL.
+ *   - A vector with more than RWR_RESTART_EXACT_MAX non-zero entries (the tolerance class), a graph with a negative
+ *     weight, d outside [0, 1] or K == 1: the call runs vector by vector through rwr_model_run_restart, whose results it
+ *     then returns.
+ *   - opts.tile_seeds, tile_group and workspace_bytes keep their meaning (the vectors run as tiles of the batched SpMM). */
+int32_t rwr_model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                    const double *sup_val, const int32_t *start, double d,
+                                    int32_t run_mode, double value, double *rank_out, int64_t *iters_out);
 
 /* ---- row-partitioned mode (graphs beyond one GPU; BASELINE.json config 5) ------------
  * An ADDITION: the reference has no distributed mode.  The transition matrix is partitioned by SOURCE rows

@@ -2,6 +2,7 @@
 // usable gfx950 device every compute entry fails with RWR_E_NO_DEVICE.
 #include <stdarg.h>
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <vector>
 #include <stdlib.h>
@@ -849,6 +850,62 @@ int32_t rwr_model_run_restart(rwr_graph *g, const double *restart, const double 
     }
     RWR_BIND(g);
     return model_run_restart(g, restart, rank_in, d, run_mode, value, rank_out, iters_out);
+}
+
+int32_t rwr_model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                    const double *sup_val, const int32_t *start, double d, int32_t run_mode, double value,
+                                    double *rank_out, int64_t *iters_out)
+{
+    static const char *const who = "rwr_model_run_restart_batch";
+    g_err[0] = 0;
+    if (!g) { set_error("%s: NULL graph", who); return RWR_E_INVALID; }
+    if (K < 0) { set_error("%s: negative K", who); return RWR_E_INVALID; }
+    if (K == 0) return RWR_OK;
+    if (!sup_ptr || !rank_out) { set_error("%s: NULL sup_ptr or rank_out", who); return RWR_E_INVALID; }
+    if (run_mode != RWR_RUN_ITERATIONS && run_mode != RWR_RUN_THRESHOLD && run_mode != RWR_RUN_DEFAULT_THRESHOLD) {
+        set_error("%s: unknown run_mode %d", who, run_mode);
+        return RWR_E_INVALID;
+    }
+    if (sup_ptr[0] != 0) { set_error("%s: sup_ptr[0] = %lld, not 0", who, (long long)sup_ptr[0]); return RWR_E_INVALID; }
+    for (int32_t k = 0; k < K; ++k)
+        if (sup_ptr[k + 1] < sup_ptr[k]) {
+            set_error("%s: sup_ptr decreases at batch position %d", who, k);
+            return RWR_E_INVALID;
+        }
+    if (sup_ptr[K] > 0 && (!sup_idx || !sup_val)) { set_error("%s: NULL sup_idx or sup_val", who); return RWR_E_INVALID; }
+    const int32_t n = g->n;
+    try {
+        std::vector<int32_t> sorted;
+        for (int32_t k = 0; k < K; ++k) {
+            if (start && (start[k] < -1 || start[k] >= n)) {
+                set_error("%s: start %d (batch position %d) is outside [-1, %d)", who, start[k], k, n);
+                return RWR_E_RANGE;
+            }
+            for (int64_t q = sup_ptr[k]; q < sup_ptr[k + 1]; ++q) {
+                if (sup_idx[q] < 0 || sup_idx[q] >= n) {
+                    set_error("%s: index %d (batch position %d) is outside [0, %d)", who, sup_idx[q], k, n);
+                    return RWR_E_RANGE;
+                }
+                if (!std::isfinite(sup_val[q])) {
+                    set_error("%s: restart[%d] = %g (batch position %d) is not finite (rr * 0 would be NaN in every row)", who,
+                              sup_idx[q], sup_val[q], k);
+                    return RWR_E_UNSUPPORTED;
+                }
+            }
+            sorted.assign(sup_idx + sup_ptr[k], sup_idx + sup_ptr[k + 1]);
+            std::sort(sorted.begin(), sorted.end());
+            const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+            if (dup != sorted.end()) {
+                set_error("%s: index %d appears twice in vector %d", who, *dup, k);
+                return RWR_E_INVALID;
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        set_error("%s: host allocation failed", who);
+        return RWR_E_NOMEM;
+    }
+    RWR_BIND(g);
+    return model_run_restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out);
 }
 
 int32_t rwr_model_deliver_restart(rwr_graph *g, const double *restart, double d, const double *rank, double *next_rank)

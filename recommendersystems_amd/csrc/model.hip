@@ -287,6 +287,16 @@ __global__ __launch_bounds__(256) void k_extract_cols(int32_t n, const double *_
     }
 }
 
+void launch_absdiff_mat(const double *a, const double *b, size_t elems, double *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_absdiff_mat, dim3(std::min<size_t>(cdiv(elems, 256), 16384)), dim3(256), 0, s, a, b, (int64_t)elems, out);
+}
+void launch_extract_cols(rwr_graph *g, int G, int tg, const double *X, const int32_t *row_of, double *out, hipStream_t s)
+{
+    RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_extract_cols<GG>, dim3(cdiv((size_t)g->n, EX_ELEMS / GG), (unsigned)tg), dim3(256), 0, s,
+                                         g->n, X, row_of, out));
+}
+
 // Tile group by tile group: GroupIter (no frontier-list steps, no row lists: every step writes every row of X), then each
 // real slot's column goes to its caller row -- after step T (iteration mode) or after the step at which its own
 // checkConvergence holds (threshold modes; the sums of all G * tg columns come back with one synchronisation per step).
@@ -347,8 +357,7 @@ static int32_t model_run_batch_body(rwr_graph *g, const int32_t *seeds, int32_t 
                 if (m > 0) {
                     RWR_HIP(hipMemcpyAsync(g->mb_row.p, row_of.data(), nslots * sizeof(int32_t), hipMemcpyHostToDevice, s));
                     hipEvent_t a; RWR_TRY(prof.record(a, s));
-                    RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_extract_cols<GG>, dim3(cdiv((size_t)n, EX_ELEMS / GG), (unsigned)tg),
-                                                         dim3(256), 0, s, n, gi.X, g->mb_row.p, g->cs_diff.p));
+                    launch_extract_cols(g, G, tg, gi.X, g->mb_row.p, g->cs_diff.p, s);
                     RWR_HIP(hipGetLastError());
                     RWR_TRY(prof.end(prof.rank, a, s));
                     for (size_t q = 0; q < nslots; ++q)
@@ -370,8 +379,7 @@ static int32_t model_run_batch_body(rwr_graph *g, const int32_t *seeds, int32_t 
             RWR_TRY(gi.step(plan_step(gi.cfg, steps, by_count ? T : -1), prof));   // deliverRanks + updateRanks
             ++steps;
             if (!by_count) {                                 // checkConvergence of every column (Model.cs:58-65, 110-115)
-                hipLaunchKernelGGL(k_absdiff_mat, dim3(std::min<size_t>(cdiv(elems, 256), 16384)), dim3(256), 0, s, gi.Y, gi.X,
-                                   (int64_t)elems, g->cs_diff.p);
+                launch_absdiff_mat(gi.Y, gi.X, elems, g->cs_diff.p, s);
                 RWR_TRY(chain_scan_sum_cols(g, G, tg, g->cs_diff.p, evoff, g->cs_sums.p, s));
             }
             RWR_TRY(prof.end(prof.iter, i0, s));

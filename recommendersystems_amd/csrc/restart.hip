@@ -9,6 +9,7 @@
 // n-term chain of its own:
 //   |S| <= RWR_RESTART_EXACT_MAX   k_restart_fold, one wave per support row beside the link-only SpMV, bitwise;
 //   |S| >  RWR_RESTART_EXACT_MAX   link-only SpMV + (tree-summed restart mass) * v[r], tolerance parity like the global model.
+#include <algorithm>
 #include <cmath>
 #include <new>
 
@@ -30,15 +31,16 @@ struct FoldWindow {
 
 // (indices clamped instead of branches: the loads issue back to back and are waited for only where they are used; a
 // position past the end reads element 0 -- every buffer holds at least one -- and is masked)
+// (xs: distance between consecutive rows of X in doubles -- 1 for a rank vector, G for a column of a tile)
 __device__ __forceinline__ void fold_load(FoldWindow &f, int64_t i, int64_t p, int32_t n, int64_t pe, int lane,
-                                          const double *__restrict__ X, const uint8_t *__restrict__ dangling,
+                                          const double *__restrict__ X, size_t xs, const uint8_t *__restrict__ dangling,
                                           const int32_t *__restrict__ in_src, const double *__restrict__ in_w)
 {
 #pragma unroll
     for (int e = 0; e < RS_E; ++e) {
         const int64_t q = i + lane * RS_E + e;
         const int64_t qc = q < n ? q : 0;
-        f.xr[e] = X[qc];
+        f.xr[e] = X[(size_t)qc * xs];
         f.dg[e] = dangling[qc];
         const int64_t l = p + lane * RS_E + e;
         const int64_t lc = l < pe ? l : 0;
@@ -55,27 +57,24 @@ __device__ __forceinline__ int wave_sum(int v)
     return v;
 }
 
-// grid = |S| one-wave workgroups; out[k] = next[sup[k]] (bitwise the reference's fold).  Every addend is formed in parallel
-// (64 lanes x RS_E rows, the same for links), placed at its position in the merged sequence through LDS, and lane 0 adds
-// the round's RS_W addends strictly in order.  The next round's rows and links are loaded before that serial fold, so their
-// latency hides behind it.  Merge-path: the first RS_W addends of the merged remainder lie inside the two RS_W-wide
-// windows, and their window-local positions are their true positions.
-__global__ __launch_bounds__(WAVE) void k_restart_fold(int32_t n, const int32_t *__restrict__ sup, const double *__restrict__ vs,
-                                                      const int64_t *__restrict__ in_ptr, const int32_t *__restrict__ in_src,
-                                                      const double *__restrict__ in_w, const double *__restrict__ X,
-                                                      const uint8_t *__restrict__ dangling, double c1, double *__restrict__ out)
+// next[r] of one support row r with restart value v, by one wave (bitwise the reference's fold).  Every addend is formed in
+// parallel (64 lanes x RS_E rows, the same for links), placed at its position in the merged sequence through LDS, and lane
+// 0 adds the round's RS_W addends strictly in order.  The next round's rows and links are loaded before that serial fold,
+// so their latency hides behind it.  Merge-path: the first RS_W addends of the merged remainder lie inside the two
+// RS_W-wide windows, and their window-local positions are their true positions.  X: rank of row q at X[q * xs].
+// The result is valid in lane 0.
+__device__ __forceinline__ double restart_fold_row(int32_t n, int32_t r, double v, const int64_t *__restrict__ in_ptr,
+                                                   const int32_t *__restrict__ in_src, const double *__restrict__ in_w,
+                                                   const double *__restrict__ X, size_t xs,
+                                                   const uint8_t *__restrict__ dangling, double c1, double *seq, int32_t *cnt)
 {
-    __shared__ double seq[RS_W];
-    __shared__ int32_t cnt[RS_W];
     const int lane = threadIdx.x;
-    const int32_t r = sup[blockIdx.x];
-    const double v = vs[blockIdx.x];
     int64_t p = in_ptr[r];
     const int64_t pe = in_ptr[r + 1];
     int64_t i = 0;
     double acc = 0.0;
     FoldWindow f;
-    fold_load(f, i, p, n, pe, lane, X, dangling, in_src, in_w);
+    fold_load(f, i, p, n, pe, lane, X, xs, dangling, in_src, in_w);
     while (i < n || p < pe) {
         const int64_t left = (pe - p) + ((int64_t)n - i);
         const int m = left < RS_W ? (int)left : RS_W;
@@ -89,7 +88,7 @@ __global__ __launch_bounds__(WAVE) void k_restart_fold(int32_t n, const int32_t 
         for (int e = 0; e < RS_E; ++e) {
             const int64_t rel = (int64_t)f.src[e] - i;              // >= 0: links of rows before i are folded already
             const bool in = rel >= 0 && rel < RS_W;
-            const double rw = c1 * X[in ? f.src[e] : r];            // Model.cs:84
+            const double rw = c1 * X[(size_t)(in ? f.src[e] : r) * xs];   // Model.cs:84
             lt[e] = rw * f.w[e];                                    // Model.cs:87
             lpos[e] = in ? lane * RS_E + e + (int)rel : RS_W;
             if (in) atomicAdd(&cnt[rel], 1);
@@ -127,14 +126,87 @@ __global__ __launch_bounds__(WAVE) void k_restart_fold(int32_t n, const int32_t 
         if (a + b != m) break;                                      // (cannot happen: the merge always advances)
         i += b;
         p += a;
-        if (i < n || p < pe) fold_load(f, i, p, n, pe, lane, X, dangling, in_src, in_w);
+        if (i < n || p < pe) fold_load(f, i, p, n, pe, lane, X, xs, dangling, in_src, in_w);
         if (lane == 0) {
 #pragma unroll 8
             for (int t = 0; t < m; ++t) acc += seq[t];              // Model.cs:87 / :93 / :97, in order
         }
         __syncthreads();
     }
-    if (lane == 0) out[blockIdx.x] = (i < n || p < pe) ? __builtin_nan("") : acc;
+    return (i < n || p < pe) ? __builtin_nan("") : acc;
+}
+
+// grid = |S| one-wave workgroups; out[k] = next[sup[k]]
+__global__ __launch_bounds__(WAVE) void k_restart_fold(int32_t n, const int32_t *__restrict__ sup, const double *__restrict__ vs,
+                                                      const int64_t *__restrict__ in_ptr, const int32_t *__restrict__ in_src,
+                                                      const double *__restrict__ in_w, const double *__restrict__ X,
+                                                      const uint8_t *__restrict__ dangling, double c1, double *__restrict__ out)
+{
+    __shared__ double seq[RS_W];
+    __shared__ int32_t cnt[RS_W];
+    const double acc = restart_fold_row(n, sup[blockIdx.x], vs[blockIdx.x], in_ptr, in_src, in_w, X, 1, dangling, c1, seq, cnt);
+    if (threadIdx.x == 0) out[blockIdx.x] = acc;
+}
+
+// The chains of a tile group of rwr_model_run_restart_batch (restart_batch.hip): one one-wave workgroup per
+// (vector, support row) pair, every pair of the group in one launch.  Pair j: support row pr[j] with restart value pv[j] of
+// the vector in slot pq[j] = tile * G + lane of the group's rank matrix X[tile][n][G] -- the same fold as k_restart_fold over
+// column pq[j] of the interleaved tile (row q of the column at distance q * G).  The pairs are ordered by slot, so the
+// chains that are resident together walk the same tile and share its 128-byte lines in the L2s.  6 KB of LDS, 116 VGPRs and
+// one wave per workgroup: 16 chains are resident per CU.
+__global__ __launch_bounds__(WAVE) void k_restart_fold_cols(int32_t n, int G, const int32_t *__restrict__ pq,
+                                                           const int32_t *__restrict__ pr, const double *__restrict__ pv,
+                                                           const int64_t *__restrict__ in_ptr, const int32_t *__restrict__ in_src,
+                                                           const double *__restrict__ in_w, const double *__restrict__ X,
+                                                           const uint8_t *__restrict__ dangling, double c1, double *__restrict__ out)
+{
+    __shared__ double seq[RS_W];
+    __shared__ int32_t cnt[RS_W];
+    const int32_t q = pq[blockIdx.x];
+    const double *col = X + (size_t)(q / G) * (size_t)n * (size_t)G + (size_t)(q % G);
+    const double acc = restart_fold_row(n, pr[blockIdx.x], pv[blockIdx.x], in_ptr, in_src, in_w, col, (size_t)G, dangling, c1, seq, cnt);
+    if (threadIdx.x == 0) out[blockIdx.x] = acc;
+}
+
+// ... and replace the link-only values the SpMM wrote for them in Y[tile][n][G]
+__global__ void k_restart_scatter_cols(int32_t npairs, int32_t n, int G, const int32_t *__restrict__ pq,
+                                       const int32_t *__restrict__ pr, const double *__restrict__ fold, double *__restrict__ Y)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= npairs) return;
+    const int32_t q = pq[j];
+    Y[(size_t)(q / G) * (size_t)n * (size_t)G + (size_t)pr[j] * (size_t)G + (size_t)(q % G)] = fold[j];
+}
+
+// rank of a tile group's slots as the constructors leave it: st[slot] >= 0 personalised (Model.cs:44: n at the node, 0
+// elsewhere), -1 global (Model.cs:25: every rank 1), -2 a padding slot (a zero column)
+__global__ __launch_bounds__(256) void k_restart_init_cols(int32_t n, int G, int64_t elems, const int32_t *__restrict__ st,
+                                                           double *__restrict__ X)
+{
+    const int64_t per_tile = (int64_t)n * G;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t tile = i / per_tile, in_tile = i - tile * per_tile;
+        const int32_t row = (int32_t)(in_tile / G), s = st[tile * G + in_tile % G];
+        X[i] = s == -1 ? 1.0 : (s == row ? (double)n : 0.0);
+    }
+}
+
+void launch_restart_fold_cols(rwr_graph *g, int G, int32_t npairs, const int32_t *pq, const int32_t *pr, const double *pv,
+                              const double *X, double c1, double *fold, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_restart_fold_cols, dim3((unsigned)npairs), dim3(WAVE), 0, s, g->n, G, pq, pr, pv, g->in_ptr.p, g->in_src.p,
+                       g->in_w.p, X, g->dangling.p, c1, fold);
+}
+void launch_restart_scatter_cols(rwr_graph *g, int G, int32_t npairs, const int32_t *pq, const int32_t *pr, const double *fold,
+                                 double *Y, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_restart_scatter_cols, dim3(cdiv((size_t)npairs, 256)), dim3(256), 0, s, npairs, g->n, G, pq, pr, fold, Y);
+}
+void launch_restart_init_cols(rwr_graph *g, int G, int tg, const int32_t *st, double *X, hipStream_t s)
+{
+    const size_t elems = (size_t)tg * (size_t)g->n * (size_t)G;
+    hipLaunchKernelGGL(k_restart_init_cols, dim3(std::min<size_t>(cdiv(elems, 256), 16384)), dim3(256), 0, s, g->n, G,
+                       (int64_t)elems, st, X);
 }
 
 // the folded support rows replace the link-only values the SpMV wrote for them

@@ -1,0 +1,280 @@
+// K Models with caller-set restart vectors in one call (rwr_model_run_restart_batch): the cross product of
+// restart.hip (one vector per call) and model.hip's batch of personalised Models (K seeds per call).
+//
+// Vector k sits in one slot (tile, lane) of the rank matrices X[tile][n][G].  One step of a tile group is
+//   main stream    the link-only SpMM at G lanes: every row of every column receives its in-links in list order -- all a row
+//                  outside the column's support receives (restart.hip: its restart addends are rr * 0);
+//   second stream  k_restart_fold_cols: one in-order chain per (vector, support row) pair of the group, all in one launch,
+//                  into a side buffer;
+//   main stream    after the join, k_restart_scatter_cols puts the folded rows over the link-only values.
+// Threshold modes sum |rank - nextRank| per column with the exact G-wide scan and stop each vector at its own step, as
+// model_run_batch does for seeds; the finished columns leave through k_extract_cols and one D2H per row.
+//
+// The SpMM runs the weighted kernels (ensure_in_w, as restart.hip): the step lasts as long as its chains, which the SpMM
+// runs beside, so the value-free form's smaller matrix stream would shorten nothing (measured).
+#include <algorithm>
+#include <cstring>
+#include <new>
+
+#include "iterate.h"
+
+namespace rwr {
+
+namespace {
+// scratch buffers of one call are released only after both streams are idle (also on error paths): declared after them
+struct StreamsIdle {
+    rwr_graph *g;
+    ~StreamsIdle()
+    {
+        (void)hipStreamSynchronize(g->stream);
+        (void)hipStreamSynchronize(g->stream2);
+    }
+};
+}  // namespace
+
+// Outside the batched domain: rwr_model_run_restart per vector, on the dense vector and the constructor's rank
+static int32_t run_vector_by_vector(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
+                                    const int32_t *start, double d, int32_t run_mode, double value, double *rank_out,
+                                    int64_t *iters_out)
+{
+    const int32_t n = g->n;
+    std::vector<double> v((size_t)n), x((size_t)n);
+    for (int32_t k = 0; k < K; ++k) {
+        std::fill(v.begin(), v.end(), 0.0);
+        for (int64_t q = sup_ptr[k]; q < sup_ptr[k + 1]; ++q) v[sup_idx[q]] = sup_val[q];
+        const int32_t st = start ? start[k] : -1;
+        std::fill(x.begin(), x.end(), st < 0 ? 1.0 : 0.0);         // Model.cs:25 / :44
+        if (st >= 0) x[st] = (double)n;
+        const int32_t rc = model_run_restart(g, v.data(), x.data(), d, run_mode, value, rank_out + (size_t)k * n,
+                                             iters_out ? iters_out + k : nullptr);
+        if (rc != RWR_OK) {
+            char msg[400];
+            snprintf(msg, sizeof(msg), "%s", rwr_last_error());
+            set_error("rwr_model_run_restart_batch: vector %d: %s", k, msg);
+            return rc;
+        }
+    }
+    return RWR_OK;
+}
+
+static int32_t model_run_restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                            const double *sup_val, const int32_t *start, double d, int32_t run_mode,
+                                            double value, double *rank_out, int64_t *iters_out)
+{
+    const double t_begin = now_ms();
+    const int32_t n = g->n;
+    // the non-zero entries of every vector (-0.0 counts as zero), and the batch-wide sign of the values
+    std::vector<int64_t> nzp((size_t)K + 1, 0);
+    bool v_nonneg = true, wide = false;
+    for (int32_t k = 0; k < K; ++k) {
+        int64_t c = 0;
+        for (int64_t q = sup_ptr[k]; q < sup_ptr[k + 1]; ++q) {
+            c += sup_val[q] != 0.0;
+            v_nonneg = v_nonneg && sup_val[q] >= 0.0;
+        }
+        nzp[(size_t)k + 1] = nzp[k] + c;
+        wide = wide || c > RWR_RESTART_EXACT_MAX;
+    }
+    // one vector, a vector of the tolerance class, or a graph / damping factor outside the domain of the batched kernels
+    // (model_run_batch's policy): rwr_model_run_restart per vector, which the contract is equality with
+    if (K == 1 || wide || !g->nonneg || !(d >= 0.0 && d <= 1.0)) {
+        RWR_TRY(run_vector_by_vector(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out));
+        g->stats.total_wall_ms += now_ms() - t_begin;
+        return RWR_OK;
+    }
+    const RunEnd end(run_mode, value, n);
+    const bool by_count = end.by_count;
+    const int64_t T = end.T;
+    const double c1 = 1 - d;                                   // Model.cs:84
+    const int G = resolve_G(g, K);
+    int TG = 1;
+    RWR_TRY(ensure_workspace(g, G, K, &TG, 1));               // + cs_diff: differences, then staging of the extracted columns
+    const int ntiles = (int)cdiv((size_t)K, (size_t)G);
+    const size_t slots = (size_t)ntiles * G;
+    // vectors dealt to tile slots round-robin over the tiles (as upload_seed_slots deals seeds): slot_k = batch position, -1 =
+    // padding; st = the slot's start node (-2 = padding: a zero column without support)
+    std::vector<int32_t> slot_k(slots, -1), st(slots, -2), no_seed(slots, -1);
+    for (int32_t k = 0; k < K; ++k) {
+        const size_t slot = (size_t)(k % ntiles) * G + (size_t)(k / ntiles);
+        slot_k[slot] = k;
+        st[slot] = start ? start[k] : -1;
+    }
+    // the (vector, support row) pairs in slot order, pq relative to the slot's tile group; group gi's pairs are [gp[gi], gp[gi + 1])
+    const int ngroups = (int)cdiv((size_t)ntiles, (size_t)TG);
+    std::vector<int64_t> gp((size_t)ngroups + 1, 0);
+    std::vector<int32_t> pq, pr;
+    std::vector<double> pv;
+    pq.reserve((size_t)nzp[K]); pr.reserve((size_t)nzp[K]); pv.reserve((size_t)nzp[K]);
+    for (size_t slot = 0; slot < slots; ++slot) {
+        const int grp = (int)(slot / G) / TG;
+        const int32_t k = slot_k[slot];
+        if (k >= 0)
+            for (int64_t q = sup_ptr[k]; q < sup_ptr[k + 1]; ++q)
+                if (sup_val[q] != 0.0) {
+                    pq.push_back((int32_t)(slot - (size_t)grp * TG * G));
+                    pr.push_back(sup_idx[q]);
+                    pv.push_back(sup_val[q]);
+                }
+        gp[(size_t)grp + 1] = (int64_t)pq.size();
+    }
+    for (int gi = 1; gi <= ngroups; ++gi) gp[gi] = std::max(gp[gi], gp[gi - 1]);
+    const size_t npairs_all = pq.size();
+
+    hipStream_t s = g->stream, s2 = g->stream2;
+    DevBuf<int32_t> d_pq, d_pr, d_st;
+    DevBuf<double> d_pv, d_fold;
+    StreamsIdle idle{g};
+    RWR_TRY(ensure_in_w(g));                                    // the link-only SpMM runs the weighted kernels
+    RWR_TRY(g->d_seeds.ensure(slots));
+    RWR_TRY(g->d_evoff.ensure(slots + 1));
+    RWR_TRY(g->d_evterm.ensure(1));
+    RWR_TRY(g->d_part.ensure(MODEL_RED_PARTS + 8));
+    RWR_TRY(g->cs_sums.ensure((size_t)TG * G));
+    RWR_TRY(g->mb_row.ensure((size_t)TG * G));
+    RWR_TRY(d_st.alloc(slots));
+    RWR_HIP(hipMemcpyAsync(g->d_seeds.p, no_seed.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    RWR_HIP(hipMemsetAsync(g->d_evoff.p, 0, (slots + 1) * sizeof(int64_t), s));
+    RWR_HIP(hipMemcpyAsync(d_st.p, st.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (npairs_all > 0) {
+        RWR_TRY(d_pq.alloc(npairs_all));
+        RWR_TRY(d_pr.alloc(npairs_all));
+        RWR_TRY(d_pv.alloc(npairs_all));
+        RWR_TRY(d_fold.alloc(npairs_all));
+        RWR_HIP(hipMemcpyAsync(d_pq.p, pq.data(), npairs_all * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_pr.p, pr.data(), npairs_all * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_pv.p, pv.data(), npairs_all * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    RWR_HIP(hipStreamSynchronize(s));                           // (the host vectors above are pageable)
+
+    Profile prof(g);                                            // (column extraction counts as ranking time)
+    std::vector<int32_t> row_of;
+    std::vector<double> dist;
+    int32_t stuck = -1;                                         // threshold modes: smallest k that did not converge
+    for (int t0 = 0, grp = 0; t0 < ntiles; t0 += TG, ++grp) {
+        const int tg = (ntiles - t0 < TG) ? (ntiles - t0) : TG;
+        const size_t q0 = (size_t)t0 * G, nslots = (size_t)tg * G;
+        const size_t elems = nslots * (size_t)n;
+        const int32_t npairs = (int32_t)(gp[(size_t)grp + 1] - gp[grp]);
+        const int32_t *gq = d_pq.p + gp[grp], *gr = d_pr.p + gp[grp];
+        const double *gv = d_pv.p + gp[grp];
+        double *gf = d_fold.p + gp[grp];
+        int32_t live = 0;                                       // real slots whose column is not out yet
+        for (size_t q = 0; q < nslots; ++q) live += slot_k[q0 + q] >= 0;
+        const int32_t real = live;
+        std::vector<uint8_t> out_done(nslots, 0);
+        double *X = g->X.p, *Y = g->Y.p;
+        launch_restart_init_cols(g, G, tg, d_st.p + q0, X, s);  // Model ctor (Model.cs:25 / :44)
+        RWR_HIP(hipGetLastError());
+        if (!by_count) RWR_TRY(chain_scan_sum_cols_prepare(g, G, tg, s));
+        SpmmArgs sp;                                            // link-only: no seed row, every row, no bitmaps, no row lists
+        sp.seeds = g->d_seeds.p + q0, sp.c1 = c1;
+        // restart.hip's rule, batch-wide: the constructors' ranks are >= 0 and stay so while every restart value is
+        sp.hub_scan = v_nonneg;
+        int64_t steps = 0;
+        for (;;) {
+            if (by_count ? steps == T : steps > 0) {
+                // the columns whose run ends here: every one after step T, the converged ones in threshold mode
+                row_of.assign(nslots, -1);
+                int32_t m = 0;
+                for (size_t q = 0; q < nslots; ++q) {
+                    const int32_t k = slot_k[q0 + q];
+                    if (k < 0 || out_done[q] || !(by_count || dist[q] < end.threshold)) continue;   // Model.cs:64
+                    row_of[q] = m++;
+                    out_done[q] = 1;
+                    if (iters_out) iters_out[k] = steps;
+                }
+                if (m > 0) {
+                    RWR_HIP(hipMemcpyAsync(g->mb_row.p, row_of.data(), nslots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+                    hipEvent_t a; RWR_TRY(prof.record(a, s));
+                    launch_extract_cols(g, G, tg, X, g->mb_row.p, g->cs_diff.p, s);
+                    RWR_HIP(hipGetLastError());
+                    RWR_TRY(prof.end(prof.rank, a, s));
+                    for (size_t q = 0; q < nslots; ++q)
+                        if (row_of[q] >= 0)
+                            RWR_HIP(hipMemcpyAsync(rank_out + (size_t)slot_k[q0 + q] * n, g->cs_diff.p + (size_t)row_of[q] * n,
+                                                   sizeof(double) * n, hipMemcpyDeviceToHost, s));
+                    RWR_HIP(hipStreamSynchronize(s));
+                    RWR_TRY(prof.fold(g));
+                    live -= m;
+                }
+                if (live == 0) break;
+            }
+            if (steps == T) {                                   // RWR_MAX_ITERS steps made: the later groups still decide the smallest k
+                for (size_t q = 0; q < nslots; ++q) {
+                    const int32_t k = slot_k[q0 + q];
+                    if (k >= 0 && !out_done[q] && (stuck < 0 || k < stuck)) stuck = k;
+                }
+                break;
+            }
+            hipEvent_t i0; RWR_TRY(prof.record(i0, s));
+            if (npairs > 0) {                                   // the support rows' chains beside the SpMM
+                RWR_HIP(hipEventRecord(g->ev_fork, s));
+                RWR_HIP(hipStreamWaitEvent(s2, g->ev_fork, 0));
+                hipEvent_t c0; RWR_TRY(prof.record(c0, s2));
+                launch_restart_fold_cols(g, G, npairs, gq, gr, gv, X, c1, gf, s2);
+                RWR_HIP(hipGetLastError());
+                RWR_TRY(prof.end(prof.chain, c0, s2));
+                RWR_HIP(hipEventRecord(g->ev_join, s2));
+            }
+            hipEvent_t a; RWR_TRY(prof.record(a, s));
+            sp.X = X, sp.Y = Y;
+            launch_spmm(g, G, tg, sp, s);
+            RWR_TRY(prof.end(prof.spmm, a, s));
+            if (prof.on) prof.dense.push_back(1);
+            if (npairs > 0) {
+                RWR_HIP(hipStreamWaitEvent(s, g->ev_join, 0));
+                launch_restart_scatter_cols(g, G, npairs, gq, gr, gf, Y, s);
+            }
+            RWR_HIP(hipGetLastError());
+            { double *t = X; X = Y; Y = t; }                    // Model.updateRanks (Model.cs:103-108)
+            ++steps;
+            g->stats.spmm_launches += 1;
+            g->stats.spmm_dense_launches += 1;
+            g->stats.chain_launches += npairs > 0;
+            if (!by_count) {                                    // checkConvergence of every column (Model.cs:58-65, 110-115)
+                launch_absdiff_mat(Y, X, elems, g->cs_diff.p, s);
+                RWR_TRY(chain_scan_sum_cols(g, G, tg, g->cs_diff.p, g->d_evoff.p + q0, g->cs_sums.p, s));
+            }
+            RWR_TRY(prof.end(prof.iter, i0, s));
+            if (!by_count) {
+                dist.resize(nslots);
+                RWR_HIP(hipMemcpyAsync(dist.data(), g->cs_sums.p, nslots * sizeof(double), hipMemcpyDeviceToHost, s));
+                RWR_HIP(hipStreamSynchronize(s));
+                RWR_TRY(prof.fold(g));
+            }
+        }
+        g->stats.spmm_seed_steps += (int64_t)real * steps;
+        g->stats.spmm_dense_seed_steps += (int64_t)real * steps;
+    }
+    RWR_HIP(hipStreamSynchronize(s));
+    RWR_HIP(hipStreamSynchronize(s2));
+    RWR_TRY(prof.fold(g));
+    if (prof.on) RWR_TRY(chain_scan_collect(g, s));
+    g->stats.tile_seeds = G;
+    g->stats.tile_group = TG;
+    g->stats.total_wall_ms += now_ms() - t_begin;
+    if (stuck >= 0) {
+        set_error("rwr_model_run_restart_batch: vector %d: no convergence within %lld iterations (RWR_MAX_ITERS)", stuck,
+                  (long long)end.max_iters);
+        return RWR_E_UNSUPPORTED;
+    }
+    return RWR_OK;
+}
+
+// no C++ exception crosses the C boundary
+int32_t model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
+                                const int32_t *start, double d, int32_t run_mode, double value, double *rank_out,
+                                int64_t *iters_out)
+{
+    try {
+        return model_run_restart_batch_body(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out);
+    } catch (const std::bad_alloc &) {
+        set_error("rwr_model_run_restart_batch: host allocation failed");
+        return RWR_E_NOMEM;
+    } catch (...) {
+        set_error("rwr_model_run_restart_batch: unexpected host exception");
+        return RWR_E_HIP;
+    }
+}
+
+}  // namespace rwr

@@ -398,6 +398,56 @@ class Model:
                                            _p(ranks, C.c_double), _p(iters, C.c_int64)))
         return ranks, iters
 
+    @staticmethod
+    def RunRestartBatch(graph: Graph, dampingFactor: float, restarts, starts=None, arg=None,
+                        out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """K models with caller-set restart vectors in one call (rwr_model_run_restart_batch), an addition beside the
+        reference surface: returns (ranks, iterations), ranks[k] / iterations[k] being what a Model whose restart field
+        holds vector k leaves after run(arg).  restarts: a sequence of {node: weight} dicts or (indices, values) pairs;
+        starts[k] >= 0: Model(graph, dampingFactor, starts[k]), -1 (or starts=None): Model(graph, dampingFactor).  arg as
+        in RunBatch.  out: an optional (K, n) float64 array to receive the ranks."""
+        lib = _lib.load()
+        if isinstance(arg, (int, np.integer)) and not isinstance(arg, bool):
+            mode, value = _lib.RWR_RUN_ITERATIONS, float(arg)
+        elif arg is None:
+            mode, value = _lib.RWR_RUN_DEFAULT_THRESHOLD, 0.0
+        else:
+            mode, value = _lib.RWR_RUN_THRESHOLD, float(arg)
+        idx, val, ptr = [], [], [0]
+        for r in restarts:
+            if isinstance(r, dict):
+                i, v = list(r.keys()), list(r.values())
+            else:
+                i, v = r
+            i = np.asarray(i, dtype=np.int32).reshape(-1)
+            v = np.asarray(v, dtype=np.float64).reshape(-1)
+            if i.shape != v.shape:
+                raise ValueError("a restart vector's indices and values differ in length")
+            idx.append(i)
+            val.append(v)
+            ptr.append(ptr[-1] + int(i.shape[0]))
+        K, n = len(idx), graph.size()
+        sup_ptr = np.asarray(ptr, dtype=np.int64)
+        sup_idx = np.ascontiguousarray(np.concatenate(idx) if K else np.zeros(0, dtype=np.int32), dtype=np.int32)
+        sup_val = np.ascontiguousarray(np.concatenate(val) if K else np.zeros(0), dtype=np.float64)
+        st = None
+        if starts is not None:
+            st = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1)
+            if st.shape[0] != K:
+                raise ValueError(f"starts must hold {K} values")
+        if out is None:
+            ranks = np.zeros((K, n), dtype=np.float64)
+        else:
+            ranks = out
+            if ranks.shape != (K, n) or ranks.dtype != np.float64 or not ranks.flags.c_contiguous:
+                raise ValueError(f"out must be a C-contiguous float64 array of shape ({K}, {n})")
+        iters = np.zeros(K, dtype=np.int64)
+        _lib.check(lib.rwr_model_run_restart_batch(graph._handle(), K, _p(sup_ptr, C.c_int64), _p(sup_idx, C.c_int32),
+                                                   _p(sup_val, C.c_double), None if st is None else _p(st, C.c_int32),
+                                                   float(dampingFactor), mode, value, _p(ranks, C.c_double),
+                                                   _p(iters, C.c_int64)))
+        return ranks, iters
+
     def deliverRanks(self) -> None:
         """Model.deliverRanks (Model.cs:76-100): nextRank <- one propagation of the current rank (rwr_model_deliver)."""
         n = self.nNodes
