@@ -51,12 +51,45 @@ namespace Recommenders.RWRBased {
                         idx.Add(p); nt.Add(etype[p]); nw.Add(w[p]);
                     }
                 Native.Check(Native.rwr_graph_update_links(handle, idx.Count, idx.ToArray(), nt.ToArray(), nw.ToArray()));
+            } else if (handle != null && !handle.IsInvalid && sentW != null && GrownLists(id, type, prevRowptr, prevDst, prevEtype, w)) {
+                // same nodes, every old list a bitwise prefix of the new one => send only the new links (rwr_graph_append_links)
+                var asrc = new List<int>(); var adst = new List<int>(); var at = new List<byte>(); var aw = new List<double>();
+                for (int i = 0; i < n; i++)
+                    for (long p = rowptr[i] + (prevRowptr[i + 1] - prevRowptr[i]); p < rowptr[i + 1]; p++) {
+                        asrc.Add(i); adst.Add(dst[p]); at.Add(etype[p]); aw.Add(w[p]);
+                    }
+                Native.Check(Native.rwr_graph_append_links(handle, asrc.Count, asrc.ToArray(), adst.ToArray(), at.ToArray(), aw.ToArray(), null));
             } else {
                 var opts = new RwrOpts { struct_size = 40, device = -1, mode = -1 };
                 Native.Check(Native.rwr_graph_create(n, id, type, rowptr, dst, etype, w, ref opts, out handle));
             }
             sentId = id; sentType = type; sentW = w;
             if (GraphFieldLimit > 0 && m <= GraphFieldLimit) LoadNormalizedGraph();
+        }
+
+        // rwr_graph_append_links on a built graph: link q goes to the end of edges[src[q]] ON THE DEVICE (what
+        // edges[src].Add(new ForwardLink(...)) does to the list, Graph.cs:40); returns the positions of the new links in the new
+        // flattened raw list (for rwr_graph_update_links).  The dictionaries are not touched: add the same links to `edges`, and
+        // the next buildGraph() finds nothing more to send.
+        public long[] AppendLinks(int[] src, ForwardLink[] links) {
+            if (src.Length != links.Length) throw new System.ArgumentException("one source per link");
+            int n = nodes.Count, count = src.Length;
+            var ad = new int[count]; var at = new byte[count]; var aw = new double[count]; var pos = new long[count];
+            for (int q = 0; q < count; q++) { ad[q] = links[q].targetNode; at[q] = (byte)links[q].type; aw[q] = links[q].weight; }
+            Native.Check(Native.rwr_graph_append_links(handle, count, src, ad, at, aw, pos));
+            // the flat copies behind LoadNormalizedGraph() and the next buildGraph()'s diff follow
+            var add = new long[n + 1];
+            foreach (int s in src) add[s + 1]++;
+            for (int i = 0; i < n; i++) add[i + 1] += add[i];
+            var rp = new long[n + 1];
+            for (int i = 0; i <= n; i++) rp[i] = rowptr[i] + add[i];
+            var nd = new int[rp[n]]; var nt = new byte[rp[n]]; var nw = new double[rp[n]];
+            for (int i = 0; i < n; i++)
+                for (long p = rowptr[i]; p < rowptr[i + 1]; p++) { nd[p + add[i]] = dst[p]; nt[p + add[i]] = etype[p]; nw[p + add[i]] = sentW[p]; }
+            for (int q = 0; q < count; q++) { nd[pos[q]] = ad[q]; nt[pos[q]] = at[q]; nw[pos[q]] = aw[q]; }
+            rowptr = rp; dst = nd; etype = nt; sentW = nw;
+            graph = null;
+            return pos;
         }
 
         // the flat arrays buildGraph() hands to librwr, without building: Recommender.EvaluateGraphs sends many graphs at once
@@ -81,6 +114,21 @@ namespace Recommenders.RWRBased {
             for (int i = 0; i < rowptr.Length; i++) if (oldRowptr[i] != rowptr[i]) return false;
             for (long p = 0; p < dst.LongLength; p++) if (oldDst[p] != dst[p]) return false;
             for (int i = 0; i < id.Length; i++) if (sentId[i] != id[i] || sentType[i] != type[i]) return false;
+            return true;
+        }
+
+        bool GrownLists(long[] id, byte[] type, long[] oldRowptr, int[] oldDst, byte[] oldEtype, double[] w) {
+            if (oldRowptr == null || oldRowptr.Length != rowptr.Length || sentId.Length != id.Length) return false;
+            for (int i = 0; i < id.Length; i++) if (sentId[i] != id[i] || sentType[i] != type[i]) return false;
+            for (int i = 0; i + 1 < rowptr.Length; i++) {
+                long len = oldRowptr[i + 1] - oldRowptr[i];
+                if (rowptr[i + 1] - rowptr[i] < len) return false;
+                for (long k = 0; k < len; k++) {
+                    long o = oldRowptr[i] + k, f = rowptr[i] + k;
+                    if (dst[f] != oldDst[o] || etype[f] != oldEtype[o] ||
+                        System.BitConverter.DoubleToInt64Bits(w[f]) != System.BitConverter.DoubleToInt64Bits(sentW[o])) return false;
+                }
+            }
             return true;
         }
 

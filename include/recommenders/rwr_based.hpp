@@ -92,6 +92,16 @@ public:
                     idx.push_back((int64_t)p); nt.push_back(etype_[p]); nw.push_back(w[p]);
                 }
             check(rwr_graph_update_links(h_, (int64_t)idx.size(), idx.data(), nt.data(), nw.data()));
+        } else if (h_ && id == sent_id_ && type == sent_type_ && grownLists(rowptr, w)) {
+            // same nodes, every old list a bitwise prefix of the new one => only the new links cross (rwr_graph_append_links)
+            std::vector<int32_t> as, ad;
+            std::vector<uint8_t> at;
+            std::vector<double> aw;
+            for (int i = 0; i < n; ++i)
+                for (int64_t p = rowptr[i] + (rowptr_[i + 1] - rowptr_[i]); p < rowptr[i + 1]; ++p) {
+                    as.push_back(i); ad.push_back(dst_[p]); at.push_back(etype_[p]); aw.push_back(w[p]);
+                }
+            check(rwr_graph_append_links(h_, (int64_t)as.size(), as.data(), ad.data(), at.data(), aw.data(), nullptr));
         } else {
             rwr_graph_destroy(h_);
             h_ = nullptr;
@@ -99,6 +109,39 @@ public:
         }
         rowptr_ = rowptr;
         sent_id_ = id; sent_type_ = type; sent_dst_ = dst_; sent_etype_ = etype_; sent_w_ = w;
+    }
+
+    // rwr_graph_append_links on a built graph: link q goes to the end of edges[src[q]] on the device (edges[src].Add(...),
+    // Graph.cs:40); returns the positions of the new links in the new flattened raw list.  The caller's `edges` are not
+    // touched: add the same links there before the next buildGraph(), which then finds nothing more to send.
+    std::vector<int64_t> appendLinks(const std::vector<int32_t> &src, const std::vector<ForwardLink> &links)
+    {
+        if (src.size() != links.size()) throw std::invalid_argument("one source per link");
+        std::vector<int32_t> d(links.size());
+        std::vector<uint8_t> t(links.size());
+        std::vector<double> w(links.size());
+        for (size_t q = 0; q < links.size(); ++q) { d[q] = links[q].targetNode; t[q] = (uint8_t)links[q].type; w[q] = links[q].weight; }
+        std::vector<int64_t> pos(links.size());
+        check(rwr_graph_append_links(handle(), (int64_t)src.size(), src.data(), d.data(), t.data(), w.data(), pos.data()));
+        // the flat copies behind graph() and the next buildGraph()'s diff follow
+        const int n = (int)nodes.size();
+        std::vector<int64_t> rp(rowptr_);
+        std::vector<int64_t> add((size_t)n + 1, 0);
+        for (int32_t s : src) ++add[(size_t)s + 1];
+        for (int i = 0; i < n; ++i) add[(size_t)i + 1] += add[i];
+        for (int i = 0; i <= n; ++i) rp[i] += add[i];
+        std::vector<int32_t> nd((size_t)rp[n]);
+        std::vector<uint8_t> nt((size_t)rp[n]);
+        std::vector<double> nw((size_t)rp[n]);
+        for (int i = 0; i < n; ++i)
+            for (int64_t p = rowptr_[i]; p < rowptr_[i + 1]; ++p) {
+                const size_t f = (size_t)(p + add[i]);
+                nd[f] = sent_dst_[p]; nt[f] = sent_etype_[p]; nw[f] = sent_w_[p];
+            }
+        for (size_t q = 0; q < links.size(); ++q) { nd[(size_t)pos[q]] = d[q]; nt[(size_t)pos[q]] = t[q]; nw[(size_t)pos[q]] = w[q]; }
+        rowptr_ = rp; dst_ = nd; etype_ = nt;
+        sent_dst_ = nd; sent_etype_ = nt; sent_w_ = nw;
+        return pos;
     }
 
     // the public field Graph.graph (Graph.cs:43): normalised explicit links per node; empty optional == null
@@ -127,6 +170,23 @@ public:
     }
 
 private:
+    // every list as long as before or longer, and its old part bit for bit what the device holds (dst_ / etype_: the new lists)
+    bool grownLists(const std::vector<int64_t> &rowptr, const std::vector<double> &w) const
+    {
+        if (rowptr.size() != rowptr_.size()) return false;
+        const size_t n = rowptr.size() - 1;
+        for (size_t i = 0; i < n; ++i) {
+            const int64_t len = rowptr_[i + 1] - rowptr_[i];
+            if (rowptr[i + 1] - rowptr[i] < len) return false;
+            for (int64_t k = 0; k < len; ++k) {
+                const size_t o = (size_t)(rowptr_[i] + k), f = (size_t)(rowptr[i] + k);
+                if (dst_[f] != sent_dst_[o] || etype_[f] != sent_etype_[o] || std::memcmp(&w[f], &sent_w_[o], sizeof(double)) != 0)
+                    return false;
+            }
+        }
+        return true;
+    }
+
     rwr_graph *h_ = nullptr;
     std::vector<int64_t> rowptr_;
     std::vector<int32_t> dst_;

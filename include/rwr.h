@@ -168,6 +168,37 @@ int32_t rwr_graph_destroy(rwr_graph *g);
  * fails with RWR_E_INVALID until it is destroyed. */
 int32_t rwr_graph_update_links(rwr_graph *g, int64_t count, const int64_t *link_index,
                                const uint8_t *etype /* may be NULL */, const double *w /* may be NULL */);
+/* Appends links to the resident graph: link q = (dst[q], etype[q], w[q]) goes to the END of node
+ * src[q]'s list, which is what edges[src].Add(new ForwardLink(dst, etype, w)) does to the
+ * reference's List<ForwardLink> (Graph.cs:40).  Links with the same src keep the order of q; src
+ * need not be sorted.  The library merges them into its resident raw lists on the device (only
+ * the new links cross the boundary) and re-runs Graph.buildGraph and the transpose there: the
+ * resulting state -- normalised weights, dangling flags, in-neighbour lists, processing orders,
+ * rwr_graph_size, the nnz_raw / nnz / uniform / uniform_path statistics -- is bit for bit what
+ * rwr_graph_create would build from the patched lists, and every later call behaves accordingly
+ * (a new LIKE link of a seed is excluded from its Recommendation, Recommender.cs:20-24).
+ * etype values and weights are taken as rwr_graph_create takes them; a negative or NaN weight is
+ * legal and moves the graph out of the Recommendation entries' domain (see rwr_recommend).
+ * Positions: new_index_out[q] (may be NULL) is the position of link q in the NEW flattened raw
+ * list, for a later rwr_graph_update_links.  Positions handed out earlier move: the link at old
+ * position e of row i is now at e + (number of appended links with src < i).
+ * count == 0 just rebuilds, as rwr_graph_update_links does.
+ * Not in scope: appending NODES (n and every n-sized array stay as they are: create a new graph)
+ * and REMOVING links (relabel them to UNDEFINED through rwr_graph_update_links, which leaves the
+ * walk bit for bit as if they were gone).
+ * Errors, all found on the host before any device work; they leave the graph exactly as it was:
+ * RWR_E_INVALID (g NULL, count < 0, a NULL src/dst/etype/w with count > 0, a handle invalidated
+ * earlier), RWR_E_RANGE (a src[q] or dst[q] outside [0, n); the message names q),
+ * RWR_E_UNSUPPORTED (nnz_raw + count beyond this build's limit of 2^32-2 links).
+ * Failures come in two phases.  BEFORE THE SWAP: the merged lists are written into new buffers,
+ * which the handle takes only when all of them exist; running out of device memory up to there
+ * returns RWR_E_NOMEM and leaves the graph untouched and usable.  AFTER THE SWAP: a failure inside
+ * the rebuild (out of device memory, a HIP error) invalidates the handle exactly as a failed
+ * rwr_graph_update_links does: every later call on it fails with RWR_E_INVALID until it is
+ * destroyed.  Not to be called concurrently with other calls on the same handle. */
+int32_t rwr_graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, const int32_t *dst,
+                               const uint8_t *etype, const double *w,
+                               int64_t *new_index_out /* count, may be NULL */);
 /* Graph.size() (Graph.cs:91-93) plus link counts; any out pointer may be NULL */
 int32_t rwr_graph_size(const rwr_graph *g, int32_t *n, int64_t *nnz_raw, int64_t *nnz_explicit);
 /* Backs the public field Graph.graph (Graph.cs:43): w_out[e] = normalised weight of raw

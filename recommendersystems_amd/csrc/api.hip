@@ -82,7 +82,7 @@ struct DeviceGuard {
 };
 #define RWR_BIND(g)                                                                                              \
     if ((g)->poisoned) {                                                                                         \
-        rwr::set_error("this graph handle was invalidated by a failed rwr_graph_update_links; destroy it");       \
+        rwr::set_error("this graph handle was invalidated by a failed rebuild (rwr_graph_update_links / rwr_graph_append_links); destroy it"); \
         return RWR_E_INVALID;                                                                                    \
     }                                                                                                            \
     rwr::DeviceGuard dev_guard__((g)->device);                                                                   \
@@ -388,6 +388,24 @@ int32_t rwr_graph_update_links(rwr_graph *g, int64_t count, const int64_t *link_
     const int32_t rc = graph_update_links(g, count, link_index, etype, w);
     // a failure after the raw lists were patched leaves derived arrays that no longer match them
     if (rc != RWR_OK && rc != RWR_E_RANGE && rc != RWR_E_INVALID) g->poisoned = 1;
+    return rc;
+}
+
+int32_t rwr_graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, const int32_t *dst, const uint8_t *etype,
+                               const double *w, int64_t *new_index_out)
+{
+    g_err[0] = 0;
+    if (!g) { set_error("rwr_graph_append_links: graph is NULL"); return RWR_E_INVALID; }
+    if (count < 0 || (count > 0 && (!src || !dst || !etype || !w))) {
+        set_error("rwr_graph_append_links: count must be >= 0 and src/dst/etype/w non-NULL when count > 0");
+        return RWR_E_INVALID;
+    }
+    RWR_BIND(g);
+    bool swapped = false;
+    const int32_t rc = graph_append_links(g, count, src, dst, etype, w, new_index_out, &swapped);
+    // before the swap the handle still holds the old lists and everything derived from them; a failure after it leaves derived
+    // arrays that no longer match the merged lists
+    if (rc != RWR_OK && swapped) g->poisoned = 1;
     return rc;
 }
 

@@ -1,0 +1,283 @@
+// rwr_graph_append_links: links appended to the lists of a resident graph.  The host plan (append_plan.h) says
+// where everything goes; the kernels here merge the resident raw lists with the new links into NEW buffers, the handle takes
+// them, and build.hip's re-derive (the incremental rebuild with nothing to patch) rebuilds the walk's data from them -- the same
+// kernels in the same order as rwr_graph_create, hence the same bits.
+#include "engine.h"
+#include "append_plan.h"
+
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+namespace rwr {
+
+template <typename T>
+static void swap_blocks(DevBuf<T> &a, DevBuf<T> &b)
+{
+    T *tp = a.p; a.p = b.p; b.p = tp;
+    size_t tc = a.count; a.count = b.count; b.count = tc;
+    size_t tr = a.reserved; a.reserved = b.reserved; b.reserved = tr;
+}
+
+// ---- rwr_graph_append_links: the resident raw lists merged with a few new links, on the device.
+// The host plan (append_plan.h) leaves one table entry per DISTINCT appended source s_j: brk[j] = rowptr_old[s_j + 1] and
+// cum[j] = links appended to s_0 .. s_j.  The old flat position e moves to e + cum[upper_bound(brk, e) - 1]: between two
+// breakpoints the move is constant, so the copy is a sequence of plain shifted block copies.
+constexpr int AP_THREADS = 256;
+constexpr int AP_CHUNK = 8192;     // old positions per workgroup
+// More breakpoints than this in a chunk: the dense path of k_append_merge (per-element shifts).  The value is reasoned, not
+// tuned: a segment is walked by all 256 lanes, so segments under 256 elements leave lanes idle in every one of the three block
+// copies, and 8 192 / 32 = 256 is the average segment length at which that starts.  A bisection over at most 8 192 breakpoints
+// of the chunk costs each element up to 13 uniform-ish loads from a table the whole workgroup keeps in cache.
+constexpr int AP_DENSE_BREAKS = 32;
+
+// the experiments build's wall-clock stamps (RWR_APPEND_TIMING=1), as RWR_BUILD_TIMING in build.hip: tools/append_latency.py
+static double at_now()
+{
+    using namespace std::chrono;
+    return duration<double, std::micro>(steady_clock::now().time_since_epoch()).count();
+}
+static const bool at_on = [] { const char *e = RWR_TUNE_ENV("RWR_APPEND_TIMING"); return e && atoi(e) != 0; }();
+#define AT(label) do { if (at_on) { const double t__ = at_now(); fprintf(stderr, "[append] %-28s %8.1f us\n", label, t__ - at_t); at_t = t__; } } while (0)
+
+// rowptr_new[i] = rowptr_old[i] + (appended links with src < i), i in [0, n]
+__global__ __launch_bounds__(256) void k_append_rowptr(int32_t n, int32_t nb, const int32_t *__restrict__ srcs,
+                                                       const int64_t *__restrict__ cum, const int64_t *__restrict__ rp_old,
+                                                       int64_t *__restrict__ rp_new)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    int lo = 0, hi = nb;               // lower_bound(srcs, i)
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)srcs[mid] < i) lo = mid + 1;
+        else hi = mid;
+    }
+    rp_new[i] = rp_old[i] + (lo > 0 ? cum[lo - 1] : 0);
+}
+
+// one segment [a, b) of old positions, all moving by sh: three coalesced block copies by the whole workgroup
+template <typename T>
+__device__ __forceinline__ void append_copy_seg(const T *__restrict__ src, T *__restrict__ out, int64_t a, int64_t b, int64_t sh,
+                                                int tid)
+{
+    int64_t e = a + tid;
+    for (; e + 3 * AP_THREADS < b; e += 4 * AP_THREADS) {      // four loads in flight per lane
+        const T v0 = src[e], v1 = src[e + AP_THREADS], v2 = src[e + 2 * AP_THREADS], v3 = src[e + 3 * AP_THREADS];
+        out[e + sh] = v0;
+        out[e + sh + AP_THREADS] = v1;
+        out[e + sh + 2 * AP_THREADS] = v2;
+        out[e + sh + 3 * AP_THREADS] = v3;
+    }
+    for (; e < b; e += AP_THREADS) out[e + sh] = src[e];
+}
+// ... of the byte array: four elements per lane, stored as one aligned dword (the source is as aligned as the shift leaves it:
+// it is read byte by byte, from lines the neighbouring lanes read as well)
+__device__ __forceinline__ void append_copy_seg_bytes(const uint8_t *__restrict__ src, uint8_t *__restrict__ out, int64_t a,
+                                                      int64_t b, int64_t sh, int tid)
+{
+    const int64_t len = b - a;
+    int64_t head = (int64_t)((4 - (reinterpret_cast<uintptr_t>(out + a + sh) & 3)) & 3);
+    if (head > len) head = len;
+    if (tid < head) out[a + sh + tid] = src[a + tid];
+    const int64_t nd = (len - head) >> 2;                      // whole dwords
+    const uint8_t *s4 = src + a + head;
+    uint32_t *o4 = reinterpret_cast<uint32_t *>(out + a + sh + head);
+    for (int64_t d = tid; d < nd; d += AP_THREADS) {
+        const uint8_t *q = s4 + 4 * d;
+        o4[d] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+    }
+    const int64_t t0 = head + 4 * nd;                          // up to three bytes left
+    if (tid < len - t0) out[a + sh + t0 + tid] = src[a + t0 + tid];
+}
+
+// A workgroup takes AP_CHUNK consecutive old positions and finds the breakpoints inside its chunk ONCE, brk[j .. jend) (every
+// lane runs the same two bisections: uniform loads).  Then one of two paths, chosen per chunk:
+// * sparse, at most AP_DENSE_BREAKS breakpoints in the chunk: it walks them, and each segment in between is three shifted
+//   block copies without any search per element;
+// * dense, more than that: every lane takes elements in lane order and finds each one's shift by bisecting brk[j .. jend).
+// Both write every old position of the chunk exactly once, at e + shift(e): the choice changes the speed, never the result.
+__global__ __launch_bounds__(AP_THREADS) void k_append_merge(int64_t m_old, int32_t nb, const int64_t *__restrict__ brk,
+                                                             const int64_t *__restrict__ cum, const int32_t *__restrict__ dst_o,
+                                                             const uint8_t *__restrict__ et_o, const double *__restrict__ w_o,
+                                                             int32_t *__restrict__ dst_n, uint8_t *__restrict__ et_n,
+                                                             double *__restrict__ w_n)
+{
+    const int tid = threadIdx.x;
+    const int64_t c0 = (int64_t)blockIdx.x * AP_CHUNK;
+    const int64_t c1 = c0 + AP_CHUNK < m_old ? c0 + AP_CHUNK : m_old;
+    int lo = 0, hi = nb;               // upper_bound(brk, c0)
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (brk[mid] <= c0) lo = mid + 1;
+        else hi = mid;
+    }
+    int j = lo;
+    // Many breakpoints inside the chunk (a bulk append that touches most rows: segments of a few dozen elements, which would
+    // leave most lanes idle in the block copies below): every lane takes elements of the chunk in lane order and finds each
+    // one's shift by bisecting the chunk's OWN breakpoints, brk[j .. jend) -- at most 13 steps over entries the whole workgroup
+    // reads.  brk[0 .. j) <= c0 <= e, so the bisection of [j, jend) is the global upper_bound(brk, e).  Loads stay
+    // lane-consecutive; the stores of a wave fall into a few pieces of consecutive addresses.
+    int jend = j;
+    {
+        int h2 = nb;                   // upper_bound(brk, c1 - 1) within [j, nb)
+        while (jend < h2) {
+            const int mid = (jend + h2) >> 1;
+            if (brk[mid] <= c1 - 1) jend = mid + 1;
+            else h2 = mid;
+        }
+    }
+    if (jend - j > AP_DENSE_BREAKS) {
+        for (int64_t e = c0 + tid; e < c1; e += AP_THREADS) {
+            int l2 = j, h2 = jend;     // upper_bound(brk, e) within [j, jend)
+            while (l2 < h2) {
+                const int mid = (l2 + h2) >> 1;
+                if (brk[mid] <= e) l2 = mid + 1;
+                else h2 = mid;
+            }
+            const int64_t sh = l2 > 0 ? cum[l2 - 1] : 0;
+            w_n[e + sh] = w_o[e];
+            dst_n[e + sh] = dst_o[e];
+            et_n[e + sh] = et_o[e];
+        }
+        return;
+    }
+    int64_t a = c0;
+    while (a < c1) {
+        const int64_t sh = j > 0 ? cum[j - 1] : 0;             // (brk[j] > a here)
+        const int64_t b = (j < nb && brk[j] < c1) ? brk[j] : c1;
+        append_copy_seg<double>(w_o, w_n, a, b, sh, tid);
+        append_copy_seg<int32_t>(dst_o, dst_n, a, b, sh, tid);
+        append_copy_seg_bytes(et_o, et_n, a, b, sh, tid);
+        a = b;
+        while (j < nb && brk[j] <= a) ++j;                      // (coinciding breakpoints: rows without links in between)
+    }
+}
+
+// the new links into the gaps the merge left: pos[k] ascending (the links are in list order)
+__global__ __launch_bounds__(256) void k_append_scatter(int64_t count, const int64_t *__restrict__ pos, const int32_t *__restrict__ dst_a,
+                                                        const uint8_t *__restrict__ et_a, const double *__restrict__ w_a,
+                                                        int32_t *__restrict__ dst_n, uint8_t *__restrict__ et_n,
+                                                        double *__restrict__ w_n)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const int64_t p = pos[k];
+    dst_n[p] = dst_a[k];
+    et_n[p] = et_a[k];
+    w_n[p] = w_a[k];
+}
+
+// Appends links to the resident raw lists and re-derives (rwr_graph_append_links).  Two phases: everything up to
+// the swap works on NEW buffers -- an argument error or a failed allocation leaves the graph as it was -- and from the swap on
+// (*swapped) a failure leaves raw and derived arrays out of step, as in graph_update_links.
+int32_t graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, const int32_t *dst, const uint8_t *etype,
+                           const double *w, int64_t *new_index_out, bool *swapped)
+{
+    const int32_t n = g->n;
+    hipStream_t s = g->stream;
+    *swapped = false;
+    double at_t = at_on ? at_now() : 0.0;
+    const AppendPlan plan = append_plan(n, g->h_rowptr.data(), count, src, dst);
+    if (plan.verdict == APPEND_BAD_SRC) {
+        set_error("rwr_graph_append_links: src[%lld] = %d is outside [0, %d)", (long long)plan.bad_q, src[plan.bad_q], n);
+        return RWR_E_RANGE;
+    }
+    if (plan.verdict == APPEND_BAD_DST) {
+        set_error("rwr_graph_append_links: dst[%lld] = %d is outside [0, %d)", (long long)plan.bad_q, dst[plan.bad_q], n);
+        return RWR_E_RANGE;
+    }
+    if (plan.verdict == APPEND_TOO_MANY) {
+        set_error("rwr_graph_append_links: %lld + %lld links exceed this build's per-device limit of 2^32-2", (long long)plan.m_old,
+                  (long long)count);
+        return RWR_E_UNSUPPORTED;
+    }
+    if (count <= 0) {
+        *swapped = true;               // (nothing to merge: a plain rebuild, with rwr_graph_update_links' failure rule)
+        return graph_update_links(g, 0, nullptr, nullptr, nullptr);
+    }
+    const int64_t m_old = plan.m_old, m_new = plan.m_new;
+    const size_t nb = plan.srcs.size();
+    AT("plan (host)");
+    // the new links in list order
+    std::vector<int32_t> h_dst((size_t)count);
+    std::vector<uint8_t> h_et((size_t)count);
+    std::vector<double> h_w((size_t)count);
+    for (int64_t k = 0; k < count; ++k) {
+        const int64_t q = plan.order[(size_t)k];
+        h_dst[(size_t)k] = dst[q];
+        h_et[(size_t)k] = etype[q];
+        h_w[(size_t)k] = w[q];
+    }
+    AT("new links in order (host)");
+    // ---- phase 1: every buffer exists before anything is launched
+    DevBuf<int64_t> rp_n, d_brk, d_cum, d_pos;
+    DevBuf<int32_t> dst_n, d_srcs, d_dst;
+    DevBuf<uint8_t> et_n, d_et;
+    DevBuf<double> w_n, wn_n, d_w;
+    RWR_TRY(rp_n.alloc((size_t)n + 1));
+    RWR_TRY(dst_n.alloc((size_t)m_new));
+    RWR_TRY(et_n.alloc((size_t)m_new));
+    RWR_TRY(w_n.alloc((size_t)m_new));
+    RWR_TRY(wn_n.alloc((size_t)m_new));
+    RWR_TRY(d_srcs.alloc(nb));
+    RWR_TRY(d_brk.alloc(nb));
+    RWR_TRY(d_cum.alloc(nb));
+    RWR_TRY(d_pos.alloc((size_t)count));
+    RWR_TRY(d_dst.alloc((size_t)count));
+    RWR_TRY(d_et.alloc((size_t)count));
+    RWR_TRY(d_w.alloc((size_t)count));
+    AT("allocate new buffers");
+    // (a failure from here to the swap waits for the stream before it returns: the copies read this function's vectors and the
+    //  kernels write its buffers, all of which go away on return -- and the handle, untouched, stays usable)
+    auto merge = [&]() -> int32_t {
+        RWR_HIP(hipMemcpyAsync(d_srcs.p, plan.srcs.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_brk.p, plan.brk.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_cum.p, plan.cum.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_pos.p, plan.pos.data(), sizeof(int64_t) * (size_t)count, hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_dst.p, h_dst.data(), sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_et.p, h_et.data(), (size_t)count, hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_w.p, h_w.data(), sizeof(double) * (size_t)count, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_append_rowptr, dim3(cdiv((size_t)n + 1, 256)), dim3(256), 0, s, n, (int32_t)nb, d_srcs.p, d_cum.p,
+                           g->rowptr.p, rp_n.p);
+        if (m_old > 0)
+            hipLaunchKernelGGL(k_append_merge, dim3(cdiv((size_t)m_old, (size_t)AP_CHUNK)), dim3(AP_THREADS), 0, s, m_old,
+                               (int32_t)nb, d_brk.p, d_cum.p, g->dst.p, g->etype.p, g->w_raw.p, dst_n.p, et_n.p, w_n.p);
+        hipLaunchKernelGGL(k_append_scatter, dim3(cdiv((size_t)count, 256)), dim3(256), 0, s, count, d_pos.p, d_dst.p, d_et.p,
+                           d_w.p, dst_n.p, et_n.p, w_n.p);
+        RWR_HIP(hipGetLastError());
+        RWR_HIP(hipStreamSynchronize(s));
+        return RWR_OK;
+    };
+    const int32_t merge_rc = merge();
+    if (merge_rc != RWR_OK) {
+        (void)hipStreamSynchronize(s);
+        return merge_rc;
+    }
+    AT("upload + merge kernels");
+    // ---- phase 2: the handle takes the merged lists
+    *swapped = true;
+    swap_blocks(g->rowptr, rp_n);
+    swap_blocks(g->dst, dst_n);
+    swap_blocks(g->etype, et_n);
+    swap_blocks(g->w_raw, w_n);
+    swap_blocks(g->w_norm_raw, wn_n);
+    {
+        size_t j = 0;
+        for (int32_t i = 0; i <= n; ++i) {                      // h_rowptr[i] += appended links with src < i
+            while (j < nb && plan.srcs[j] < i) ++j;
+            g->h_rowptr[(size_t)i] += j > 0 ? plan.cum[j - 1] : 0;
+        }
+    }
+    g->nnz_raw = m_new;
+    g->stats.nnz_raw = m_new;
+    if (m_new > ONE_LAUNCH_MAX_M) g->staged = 0;                // past the one-launch build: the general derive from now on
+    if (new_index_out) memcpy(new_index_out, plan.new_index.data(), sizeof(int64_t) * (size_t)count);
+    AT("swap + host row pointers");
+    const int32_t rc = graph_update_links(g, 0, nullptr, nullptr, nullptr);   // (count 0: the re-derive alone, build.hip)
+    AT("re-derive");
+    return rc;
+}
+
+}  // namespace rwr

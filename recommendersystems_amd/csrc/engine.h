@@ -173,6 +173,14 @@ int32_t graph_build(rwr_graph *g, const int64_t *node_id, const uint8_t *node_ty
                     const int32_t *dst, const uint8_t *etype, const double *w);
 
 int32_t graph_update_links(rwr_graph *g, int64_t count, const int64_t *idx, const uint8_t *etype, const double *w);
+// The largest link count the one-launch paths of an ego-network-sized graph take: small.hip's one-launch Recommendation and the
+// one-launch build (build.hip keeps its own STAGE_MAX_M of the same value: that file is part of the benchmark's traffic
+// fingerprint and is not edited for a constant; small_build_ok re-checks nnz_raw against it on every build)
+constexpr int64_t ONE_LAUNCH_MAX_M = 65536;
+// rwr_graph_append_links: merges the links into the resident raw lists (new buffers, swapped in when all of them exist:
+// *swapped) and re-derives; the plan of the merge is append_plan.h's
+int32_t graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, const int32_t *dst, const uint8_t *etype,
+                           const double *w, int64_t *new_index_out, bool *swapped);
 // value-free graphs: materialise in_w (= w_src[in_src]) for an entry point that runs the weighted kernels
 int32_t ensure_in_w(rwr_graph *g);
 // g->tail_rows / tail_n / tail_depth / h_tail_flag of the current matrix (built once per (re)build)

@@ -68,12 +68,56 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def _grown_lists(old_flat, new_flat):
+    """The links by which the lists of ``new_flat`` exceed those of ``old_flat`` (both as ``Graph._flatten`` returns them):
+    ``(src, dst, etype, w)`` of the appended links, row by row in list order, when the node arrays are equal and every old
+    list is a bitwise prefix of the new one (weights compared as uint64); ``None`` otherwise.  No change gives empty arrays."""
+    o_id, o_type, o_rp, o_dst, o_et, o_w = old_flat
+    n_id, n_type, n_rp, n_dst, n_et, n_w = new_flat
+    if o_id.shape != n_id.shape or not ((o_id == n_id).all() and (o_type == n_type).all()):
+        return None
+    o_len, n_len = np.diff(o_rp), np.diff(n_rp)
+    if (n_len < o_len).any():
+        return None
+    n = int(o_id.shape[0])
+    rows = np.arange(n, dtype=np.int64)
+    # where the old link at flat position e sits in the new lists: same row, same place in the row
+    kept = np.arange(int(o_rp[n]), dtype=np.int64) + np.repeat(n_rp[:-1] - o_rp[:-1], o_len)
+    if not ((n_dst[kept] == o_dst).all() and (n_et[kept] == o_et).all()
+            and (n_w[kept].view(np.uint64) == o_w.view(np.uint64)).all()):
+        return None
+    added = np.ones(int(n_rp[n]), dtype=bool)
+    added[kept] = False
+    src = np.repeat(rows, n_len - o_len).astype(np.int32)
+    return src, n_dst[added], n_et[added], n_w[added]
+
+
+def _merged_flat(flat, src, dst, etype, w, pos):
+    """``flat`` (as ``Graph._flatten`` returns it) with the links (src, dst, etype, w) at the positions ``pos`` that
+    rwr_graph_append_links gave them: new arrays, the old links in their order in the places in between."""
+    node_id, node_type, rowptr, o_dst, o_et, o_w = flat
+    n = int(node_id.shape[0])
+    m_new = int(rowptr[n]) + int(pos.shape[0])
+    old = np.ones(m_new, dtype=bool)
+    old[pos] = False
+    out = []
+    for o, a in ((o_dst, dst), (o_et, etype), (o_w, w)):
+        x = np.empty(m_new, dtype=o.dtype)
+        x[old] = o
+        x[pos] = a
+        out.append(x)
+    new_rowptr = rowptr.copy()
+    new_rowptr[1:] += np.cumsum(np.bincount(src, minlength=n).astype(np.int64))
+    return (node_id, node_type, new_rowptr, out[0], out[1], out[2])
+
+
 class Graph:
     """class Graph (Graph.cs:37-94).  ``nodes``/``edges`` are the caller's dictionaries
     (kept by reference, Graph.cs:46-47); ``buildGraph()`` hands the RAW links to
     rwr_graph_create, which filters/normalises/transposes on the device."""
 
     incremental_rebuilds = 0     # buildGraph() calls (all instances) that went through rwr_graph_update_links
+    append_rebuilds = 0          # ... and those that went through rwr_graph_append_links (lists that only grew)
 
     def __init__(self, nodes: Dict[int, Node], edges: Dict[int, List[ForwardLink]], *, mode: Optional[str] = None,
                  device: int = -1, tile_seeds: int = 0, tile_group: int = 0, profile: bool = False,
@@ -129,7 +173,9 @@ class Graph:
 
         Called again on the same object after the caller mutated its dictionaries (the harness relabels link types
         between runs, Experiment.cs:84-101): when nodes, list lengths and targets are unchanged, only the links whose
-        type or weight differ are sent (rwr_graph_update_links); the device state is the same either way."""
+        type or weight differ are sent (rwr_graph_update_links); when the lists only grew at their ends, only the new links
+        (rwr_graph_append_links); lists that grew AND whose old links changed are sent whole.  The device state is the same
+        either way."""
         lib = _lib.load()
         flat = self._flat if self._flat is not None else self._flatten()
         node_id, node_type, rowptr, dst, etype, w = flat
@@ -141,6 +187,17 @@ class Graph:
                 self.updateLinks(changed, etype[changed], w[changed])
                 self._sent = flat
                 Graph.incremental_rebuilds += 1
+                return
+            grown = _grown_lists(self._sent, flat)
+            if grown is not None:
+                # (the library directly: appendLinks would merge the links into a copy of _sent, and flat IS that merge)
+                s, t, et, ww = (np.ascontiguousarray(a) for a in grown)
+                _lib.check(lib.rwr_graph_append_links(self._handle(), int(s.shape[0]), _p(s, C.c_int32), _p(t, C.c_int32),
+                                                      _p(et, C.c_uint8), _p(ww, C.c_double), None))
+                self._rowptr = rowptr
+                self._sent = flat
+                self._graph_cache = None
+                Graph.append_rebuilds += 1
                 return
         if self._h:
             lib.rwr_graph_destroy(self._h)
@@ -165,6 +222,37 @@ class Graph:
             self._handle(), int(idx.shape[0]), _p(idx, C.c_int64),
             None if et is None else _p(et, C.c_uint8), None if ww is None else _p(ww, C.c_double)))
         self._graph_cache = None
+
+    def appendLinks(self, src, dst, etype, w) -> np.ndarray:
+        """rwr_graph_append_links: link q goes to the end of node src[q]'s list (edges[src].Add(...), Graph.cs:40), then the
+        device-side rebuild.  Returns the positions of the new links in the new flattened raw list (for updateLinks); the
+        link at old position e of row i is now at e + (appended links with src < i).
+
+        The object's record of what the device holds follows.  A dictionary graph: the caller adds the same links to
+        ``edges`` (this call does not touch the dictionaries) and the next buildGraph() finds nothing more to send.  A flat
+        graph: the object continues with merged COPIES of the arrays; the caller's arrays are not touched."""
+        s = np.ascontiguousarray(src, dtype=np.int32)
+        t = np.ascontiguousarray(dst, dtype=np.int32)
+        et = np.ascontiguousarray(etype, dtype=np.uint8)
+        ww = np.ascontiguousarray(w, dtype=np.float64)
+        if s.ndim != 1 or t.shape != s.shape or et.shape != s.shape or ww.shape != s.shape:
+            raise ValueError("src / dst / etype / w must be one-dimensional and of one length")
+        pos = np.zeros(s.shape[0], dtype=np.int64)
+        _lib.check(_lib.load().rwr_graph_append_links(
+            self._handle(), int(s.shape[0]), _p(s, C.c_int32), _p(t, C.c_int32), _p(et, C.c_uint8), _p(ww, C.c_double),
+            _p(pos, C.c_int64)))
+        if self._flat is not None:
+            self._flat = _merged_flat(self._flat, s, t, et, ww, pos)
+            self._desc = None
+            self._rowptr = self._flat[2]
+        else:
+            if self._sent is not None:
+                self._sent = _merged_flat(self._sent, s, t, et, ww, pos)
+            rowptr = self._rowptr.copy()
+            rowptr[1:] += np.cumsum(np.bincount(s, minlength=self._n).astype(np.int64))
+            self._rowptr = rowptr
+        self._graph_cache = None
+        return pos
 
     def size(self) -> int:
         """Graph.size() (Graph.cs:91-93)."""

@@ -1,0 +1,458 @@
+"""rwr_graph_append_links on the GPU: after the call the handle must be bit for bit what rwr_graph_create builds
+from the patched lists.  The yardstick of every case is therefore a FRESH handle created from the lists a brute-force
+host-side append produces (stable sort of old + new links by source: edges[src].Add(...), Graph.cs:40); on the smallest case
+the C oracle is asked as well.  "Equal" = the bits of rwr_graph_get_normalized, rwr_graph_size, the uniform / uniform_path
+flags, rwr_model_run for three seeds and the global model, the full rwr_recommend lists of those seeds and a
+rwr_recommend_batch of 40 seeds at top-10."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import graphgen as gg
+
+pytestmark = pytest.mark.gpu
+
+D = 0.15
+T = 6
+
+
+def _api():
+    from recommendersystems_amd import _lib
+    from recommendersystems_amd.rwr_based import Graph, Model, Recommender, _p
+    return _lib, Graph, Model, Recommender, _p
+
+
+def bipartite(seed, n_users, n_items, n_likes, *, unit=True, p_undefined=0.03):
+    """A LIKE graph in both directions with shuffled lists, built without Python loops (graphgen.random_graph walks its
+    lists per link).  unit=False mixes in other weights, so that the weighted kernels run instead of the value-free ones."""
+    rng = np.random.default_rng(seed)
+    u = (rng.random(n_likes) * rng.random(n_likes) * n_users).astype(np.int64)
+    v = (rng.random(n_likes) * rng.random(n_likes) * n_items).astype(np.int64)
+    key = np.unique(u * n_items + v)
+    u, v = key // n_items, key % n_items + n_users
+    src = np.concatenate([u, v])
+    dst = np.concatenate([v, u]).astype(np.int32)
+    order = np.lexsort((rng.random(src.shape[0]), src))
+    src, dst = src[order], dst[order]
+    n = n_users + n_items
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(src, minlength=n), out=rowptr[1:])
+    m = dst.shape[0]
+    etype = np.where(rng.random(m) < p_undefined, gg.EDGE_UNDEFINED, gg.EDGE_LIKE).astype(np.uint8)
+    w = np.ones(m) if unit else rng.choice(np.array([1.0, 1.0, 0.5, 2.25, 3.0]), m)
+    node_type = np.array([gg.NODE_USER] * n_users + [gg.NODE_ITEM] * n_items, dtype=np.uint8)
+    node_id = rng.permutation(np.arange(500, 500 + 3 * n, 3, dtype=np.int64))
+    return dict(node_id=node_id, node_type=node_type, rowptr=rowptr, dst=dst, etype=etype, w=w)
+
+
+def patched(g, src, dst, etype, w):
+    """(the lists of g with link q appended to list src[q], positions of the new links): the brute force."""
+    n = g["node_id"].shape[0]
+    m = int(g["rowptr"][n])
+    src = np.asarray(src, dtype=np.int64)
+    all_src = np.concatenate([np.repeat(np.arange(n, dtype=np.int64), np.diff(g["rowptr"])), src])
+    order = np.argsort(all_src, kind="stable")
+    where = np.empty(order.shape[0], dtype=np.int64)
+    where[order] = np.arange(order.shape[0])
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(all_src, minlength=n), out=rowptr[1:])
+    out = dict(node_id=g["node_id"], node_type=g["node_type"], rowptr=rowptr,
+               dst=np.concatenate([g["dst"], np.asarray(dst, dtype=np.int32)])[order],
+               etype=np.concatenate([g["etype"], np.asarray(etype, dtype=np.uint8)])[order],
+               w=np.concatenate([g["w"], np.asarray(w, dtype=np.float64)])[order])
+    return out, where[m:]
+
+
+def random_links(seed, g, n_users, count, *, weights=(1.0,)):
+    rng = np.random.default_rng(seed)
+    n = g["node_id"].shape[0]
+    back = rng.random(count) < 0.2                       # a fifth of them item -> user
+    users = rng.integers(0, n_users, count)
+    items = rng.integers(n_users, n, count)
+    src = np.where(back, items, users).astype(np.int32)
+    dst = np.where(back, users, items).astype(np.int32)
+    return src, dst, np.full(count, gg.EDGE_LIKE, dtype=np.uint8), rng.choice(np.array(weights), count)
+
+
+def build(g):
+    _, Graph, _, _, _ = _api()
+    G = Graph.from_flat(**g)
+    G.buildGraph()
+    return G
+
+
+def sizes(G):
+    _lib, _, _, _, _ = _api()
+    n, raw, ex = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.load().rwr_graph_size(G._handle(), C.byref(n), C.byref(raw), C.byref(ex)))
+    return n.value, raw.value, ex.value
+
+
+def snapshot(G, seeds, batch_seeds, *, recommend=True):
+    _, _, Model, Recommender, _ = _api()
+    snap = {}
+    wn, dg = G.normalized()
+    snap["w_norm"], snap["dangling"] = wn.view(np.uint64).copy(), dg.copy()
+    snap["size"] = sizes(G)
+    st = G.stats()
+    snap["flags"] = (st["uniform"], st["uniform_path"], st["nnz_raw"], st["nnz"])
+    for s in list(seeds) + [None]:
+        mdl = Model(G, float(np.float32(D)), s)
+        mdl.run(T)
+        snap["model", s] = mdl.rank.view(np.uint64).copy()
+    if recommend:
+        rec = Recommender(G)
+        for s in seeds:
+            ids, sc = rec.RecommendationArrays(s, D, T)
+            snap["rec_ids", s], snap["rec_sc", s] = ids.copy(), sc.view(np.uint64).copy()
+        bi, bs, bc = rec.RecommendationBatch(np.asarray(batch_seeds, dtype=np.int32), D, T, 10)
+        snap["batch"] = (bi, bs.view(np.uint64), bc)
+    return snap
+
+
+def assert_same(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        x, y = a[k], b[k]
+        if isinstance(x, tuple):
+            assert len(x) == len(y) and all(np.array_equal(p, q) for p, q in zip(x, y)), k
+        else:
+            assert np.array_equal(x, y), k
+
+
+def check_against_fresh(G, lists, seeds, batch_seeds, **kw):
+    F = build(lists)
+    try:
+        assert_same(snapshot(G, seeds, batch_seeds, **kw), snapshot(F, seeds, batch_seeds, **kw))
+    finally:
+        F.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------ cases
+
+def test_one_launch_path():
+    """40 users x 60 items, 300 likes (the one-launch build), plus 25 links in shuffled source order, three for one source."""
+    from oracle.c_oracle import FlatGraph
+    _, _, _, Recommender, _ = _api()
+    g = gg.random_graph(3, n_users=40, n_items=60, n_likes=300, n_friend=20, n_mention=15)
+    src, dst, et, w = random_links(11, g, 40, 25, weights=(1.0, 0.75))
+    src[[2, 9, 20]] = 7
+    dst[[2, 9, 20]] = [41, 77, 58]
+    G = build(g)
+    pos = G.appendLinks(src, dst, et, w)
+    want, want_pos = patched(g, src, dst, et, w)
+    assert np.array_equal(pos, want_pos)
+    seeds, batch = (0, 7, 33), np.arange(40)
+    check_against_fresh(G, want, seeds, batch)
+    ids, sc = Recommender(G).RecommendationArrays(7, D, T)
+    oi, osc = FlatGraph(**want).recommend(7, D, T)
+    assert np.array_equal(ids, oi) and np.array_equal(sc.view(np.uint64), osc.view(np.uint64))
+    G.close()
+
+
+def test_crossing_the_one_launch_limit():
+    """~65 000 links plus 1 000: the link count passes 65 536 and the handle leaves the one-launch build; then a second append
+    on the same handle, now on the general path."""
+    n_users = 3000
+    g = bipartite(5, n_users, 5000, 36000)
+    m = int(g["rowptr"][-1])
+    keep = 64800                                       # trim to just under the limit, whatever the generator's duplicates left
+    assert m > keep
+    cut = np.minimum(g["rowptr"], keep)
+    g = dict(g, rowptr=cut, dst=g["dst"][:keep], etype=g["etype"][:keep], w=g["w"][:keep])
+    assert g["node_id"].shape[0] <= 8192 and keep <= 65536
+    G = build(g)
+    a = random_links(21, g, n_users, 1000)
+    pos = G.appendLinks(*a)
+    want, want_pos = patched(g, *a)
+    assert np.array_equal(pos, want_pos) and int(want["rowptr"][-1]) > 65536
+    seeds, batch = (0, 17, int(a[0][0]) if a[0][0] < n_users else 5), np.arange(0, 400, 10)
+    check_against_fresh(G, want, seeds, batch)
+    b = random_links(22, g, n_users, 700)
+    pos2 = G.appendLinks(*b)
+    want2, want_pos2 = patched(want, *b)
+    assert np.array_equal(pos2, want_pos2)
+    check_against_fresh(G, want2, seeds, batch)
+    G.close()
+
+
+def test_general_path_two_calls():
+    """n above 8 192 (the general build from the start), weighted kernels; 5 000 links in two calls.  The positions the first
+    call returned move by the second call's shifts: updating the links there must hit the same links as on the host."""
+    n_users = 4000
+    g = bipartite(9, n_users, 9000, 70000, unit=False)
+    G = build(g)
+    a = random_links(31, g, n_users, 3000, weights=(1.0, 0.5))
+    b = random_links(32, g, n_users, 2000, weights=(1.0, 3.0))
+    pos_a = G.appendLinks(*a)
+    want_a, want_pos_a = patched(g, *a)
+    assert np.array_equal(pos_a, want_pos_a)
+    pos_b = G.appendLinks(*b)
+    want_b, want_pos_b = patched(want_a, *b)
+    assert np.array_equal(pos_b, want_pos_b)
+    seeds, batch = (1, 250, 3999), np.arange(0, 4000, 100)
+    check_against_fresh(G, want_b, seeds, batch)
+    # header rule: the link at old position e of row i moves to e + (appended links with src < i)
+    moved = pos_a + np.searchsorted(np.sort(b[0]), a[0], side="left")
+    assert np.array_equal(want_b["dst"][moved], a[1]) and np.array_equal(want_b["w"][moved], a[3])
+    pick = moved[:60]
+    G.updateLinks(pick, None, np.full(pick.shape[0], 4.5))
+    want_c = dict(want_b, w=want_b["w"].copy())
+    want_c["w"][pick] = 4.5
+    check_against_fresh(G, want_c, seeds, batch)
+    G.close()
+
+
+def _small(uniform=False):
+    return gg.random_graph(13, n_users=50, n_items=70, n_likes=260, uniform=uniform, p_undefined=0.0 if uniform else 0.05)
+
+
+def test_edge_dangling_node_gets_a_link():
+    g = _small()
+    deg = np.diff(g["rowptr"])
+    node = int(np.flatnonzero(deg == 0)[0])              # an item nobody liked: no out-link at all
+    G = build(g)
+    assert G.normalized()[1][node] == 1
+    a = ([node], [3], [gg.EDGE_LIKE], [1.0])
+    G.appendLinks(*a)
+    assert G.normalized()[1][node] == 0
+    check_against_fresh(G, patched(g, *a)[0], (0, 3, 20), np.arange(40))
+    G.close()
+
+
+def test_edge_undefined_link():
+    g = _small()
+    G = build(g)
+    _, raw0, nnz0 = sizes(G)
+    a = ([4], [60], [gg.EDGE_UNDEFINED], [1.0])
+    G.appendLinks(*a)
+    assert sizes(G)[1:] == (raw0 + 1, nnz0)
+    st = G.stats()
+    assert (st["nnz_raw"], st["nnz"]) == (raw0 + 1, nnz0)
+    check_against_fresh(G, patched(g, *a)[0], (0, 4, 20), np.arange(40))
+    G.close()
+
+
+def test_edge_new_like_is_excluded():
+    _, _, _, Recommender, _ = _api()
+    g = _small()
+    seed = 2
+    G = build(g)
+    before, _ = Recommender(G).RecommendationArrays(seed, D, T)
+    row = slice(int(g["rowptr"][seed]), int(g["rowptr"][seed + 1]))
+    liked = set(g["dst"][row][g["etype"][row] == gg.EDGE_LIKE].tolist())
+    item = next(i for i in range(50, 120) if i not in liked and int(g["node_id"][i]) in set(before.tolist()))
+    a = ([seed], [item], [gg.EDGE_LIKE], [1.0])
+    G.appendLinks(*a)
+    after, _ = Recommender(G).RecommendationArrays(seed, D, T)
+    assert int(g["node_id"][item]) not in set(after.tolist()) and after.shape[0] == before.shape[0] - 1
+    check_against_fresh(G, patched(g, *a)[0], (0, seed, 20), np.arange(40))
+    G.close()
+
+
+def test_edge_weight_breaks_uniformity():
+    g = _small(uniform=True)
+    G = build(g)
+    assert G.stats()["uniform_path"] == 1
+    src = int(np.flatnonzero(np.diff(g["rowptr"])[:50] > 0)[0])
+    a = ([src], [55], [gg.EDGE_LIKE], [2.0])
+    G.appendLinks(*a)
+    st = G.stats()
+    assert st["uniform"] == 0 and st["uniform_path"] == 0
+    check_against_fresh(G, patched(g, *a)[0], (0, src, 20), np.arange(40))
+    G.close()
+
+
+def test_edge_negative_weight():
+    _lib, _, _, Recommender, _ = _api()
+    g = _small()
+    G = build(g)
+    a = ([6], [61], [gg.EDGE_LIKE], [-0.5])
+    G.appendLinks(*a)
+    with pytest.raises(_lib.RwrError) as e:
+        Recommender(G).RecommendationArrays(6, D, T)
+    assert e.value.status == _lib.RWR_E_UNSUPPORTED
+    check_against_fresh(G, patched(g, *a)[0], (0, 6, 20), np.arange(40), recommend=False)
+    G.close()
+
+
+def test_warm_handle():
+    """Every lazily built structure of the previous matrix exists (tail rows, frontier lists, batch workspaces, the sweep
+    tables of a single-seed call, the model batch's matrices) when the links arrive."""
+    _, _, Model, Recommender, _ = _api()
+    n_users = 4000
+    g = bipartite(17, n_users, 9000, 60000)
+    G = build(g)
+    rec = Recommender(G)
+    batch = np.arange(0, 4000, 100)
+    rec.RecommendationBatch(batch.astype(np.int32), D, T, 10)
+    rec.RecommendationArrays(5, D, T)
+    Model.RunBatch(G, float(np.float32(D)), batch[:16], T)
+    a = random_links(41, g, n_users, 2500)
+    G.appendLinks(*a)
+    want, _ = patched(g, *a)
+    F = build(want)
+    seeds = (5, 250, 3999)
+    assert_same(snapshot(G, seeds, batch), snapshot(F, seeds, batch))
+    ra, ia = Model.RunBatch(G, float(np.float32(D)), batch[:16], T)
+    rf, if_ = Model.RunBatch(F, float(np.float32(D)), batch[:16], T)
+    assert np.array_equal(ra.view(np.uint64), rf.view(np.uint64)) and np.array_equal(ia, if_)
+    F.close()
+    G.close()
+
+
+def test_interplay_update_links_and_count_zero():
+    g = _small()
+    G = build(g)
+    a = random_links(51, g, 50, 12, weights=(1.0, 0.25))
+    pos = G.appendLinks(*a)
+    want, _ = patched(g, *a)
+    new_t = np.where(np.arange(12) % 3 == 0, gg.EDGE_UNDEFINED, gg.EDGE_FOLLOW).astype(np.uint8)
+    new_w = np.linspace(0.5, 3.0, 12)
+    G.updateLinks(pos, new_t, new_w)
+    want2 = dict(want, etype=want["etype"].copy(), w=want["w"].copy())
+    want2["etype"][pos], want2["w"][pos] = new_t, new_w
+    seeds, batch = (0, int(a[0][0]) if a[0][0] < 50 else 1, 20), np.arange(40)
+    check_against_fresh(G, want2, seeds, batch)
+    empty = G.appendLinks(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros(0))
+    assert empty.shape == (0,)
+    check_against_fresh(G, want2, seeds, batch)
+    G.close()
+
+
+def test_errors_leave_a_live_graph_alone():
+    _lib, _, _, _, _p = _api()
+    lib = _lib.load()
+    g = _small()
+    n = g["node_id"].shape[0]
+    G = build(g)
+    seeds, batch = (0, 9, 20), np.arange(40)
+    before = snapshot(G, seeds, batch)
+    src = np.array([1, 2, 3, 4], dtype=np.int32)
+    dst = np.array([60, 61, 62, 63], dtype=np.int32)
+    et = np.full(4, gg.EDGE_LIKE, dtype=np.uint8)
+    w = np.ones(4)
+    out = np.full(4, -7, dtype=np.int64)
+    h = G._handle()
+
+    def call(count, s, d, t, ww):
+        ptr = lambda a, ty: None if a is None else _p(a, ty)
+        return lib.rwr_graph_append_links(h, count, ptr(s, C.c_int32), ptr(d, C.c_int32), ptr(t, C.c_uint8), ptr(ww, C.c_double),
+                                          _p(out, C.c_int64))
+
+    def message():
+        return lib.rwr_last_error().decode()
+
+    for bad, q in ((n, 2), (-1, 0), (2 ** 31 - 1, 3)):
+        s = src.copy()
+        s[q] = bad
+        assert call(4, s, dst, et, w) == _lib.RWR_E_RANGE
+        assert "src[%d]" % q in message(), message()
+        d = dst.copy()
+        d[q] = bad
+        assert call(4, src, d, et, w) == _lib.RWR_E_RANGE
+        assert "dst[%d]" % q in message(), message()
+    assert call(-1, src, dst, et, w) == _lib.RWR_E_INVALID
+    for k in range(4):
+        args = [src, dst, et, w]
+        args[k] = None
+        assert call(4, *args) == _lib.RWR_E_INVALID
+    assert (out == -7).all()
+    assert_same(snapshot(G, seeds, batch), before)       # same bits, not poisoned
+    assert call(4, src, dst, et, w) == _lib.RWR_OK        # ... and the same arguments, valid, go through
+    G._rowptr = patched(g, src, dst, et, w)[0]["rowptr"]
+    assert np.array_equal(out, patched(g, src, dst, et, w)[1])
+    check_against_fresh(G, patched(g, src, dst, et, w)[0], seeds, batch)
+    G.close()
+
+
+def test_mirror_dictionary_graph():
+    """A dictionary Graph whose lists only grew rebuilds through rwr_graph_append_links; one whose old link changed as well
+    is sent whole."""
+    _, Graph, _, _, _ = _api()
+    from recommendersystems_amd.rwr_based import EdgeType, ForwardLink, Node, NodeType
+    g = _small()
+    n = g["node_id"].shape[0]
+    nodes = {i: Node(int(g["node_id"][i]), NodeType(int(g["node_type"][i]))) for i in range(n)}
+    edges = {i: [ForwardLink(int(g["dst"][e]), EdgeType(int(g["etype"][e])), float(g["w"][e]))
+                 for e in range(int(g["rowptr"][i]), int(g["rowptr"][i + 1]))] for i in range(n)}
+    G = Graph(nodes, edges)
+    G.buildGraph()
+    seeds, batch = (0, 8, 20), np.arange(40)
+
+    def fresh_equal():
+        F = Graph(nodes, edges)
+        F.buildGraph()
+        try:
+            assert_same(snapshot(G, seeds, batch), snapshot(F, seeds, batch))
+        finally:
+            F.close()
+
+    for s, t in ((8, 66), (3, 70), (8, 51), (119, 2)):
+        edges[s].append(ForwardLink(t, EdgeType.LIKE, 1.0))
+    a0, i0 = Graph.append_rebuilds, Graph.incremental_rebuilds
+    G.buildGraph()
+    assert (Graph.append_rebuilds, Graph.incremental_rebuilds) == (a0 + 1, i0)
+    fresh_equal()
+    edges[5].append(ForwardLink(67, EdgeType.LIKE, 1.0))
+    edges[8][0].weight = 2.5                             # grew AND an old link changed: destroy + create
+    G.buildGraph()
+    assert (Graph.append_rebuilds, Graph.incremental_rebuilds) == (a0 + 1, i0)
+    fresh_equal()
+    G.close()
+
+
+def test_mirror_append_links_then_build_graph():
+    """Graph.appendLinks directly, the same links added to the dictionaries, buildGraph() again: the links must not be sent
+    a second time (the object's record of what the device holds follows the append)."""
+    _, Graph, _, _, _ = _api()
+    from recommendersystems_amd.rwr_based import EdgeType, ForwardLink, Node, NodeType
+    g = _small()
+    n = g["node_id"].shape[0]
+    nodes = {i: Node(int(g["node_id"][i]), NodeType(int(g["node_type"][i]))) for i in range(n)}
+    edges = {i: [ForwardLink(int(g["dst"][e]), EdgeType(int(g["etype"][e])), float(g["w"][e]))
+                 for e in range(int(g["rowptr"][i]), int(g["rowptr"][i + 1]))] for i in range(n)}
+    G = Graph(nodes, edges)
+    G.buildGraph()
+    new = [(8, 66, 1.0), (3, 70, 0.5), (8, 51, 1.0), (119, 2, 1.0)]
+    pos = G.appendLinks([s for s, _, _ in new], [t for _, t, _ in new], [int(EdgeType.LIKE)] * 4, [w for _, _, w in new])
+    for s, t, w in new:
+        edges[s].append(ForwardLink(t, EdgeType.LIKE, w))
+    flat = G._flatten()
+    assert np.array_equal(flat[3][pos], [t for _, t, _ in new])
+    raw_after_append = sizes(G)[1]
+    a0, i0 = Graph.append_rebuilds, Graph.incremental_rebuilds
+    G.buildGraph()
+    assert sizes(G)[1] == raw_after_append == int(g["rowptr"][-1]) + 4
+    assert (Graph.append_rebuilds, Graph.incremental_rebuilds) == (a0, i0 + 1)      # nothing grew: an update of no links
+    F = Graph(nodes, edges)
+    F.buildGraph()
+    seeds, batch = (0, 8, 20), np.arange(40)
+    assert_same(snapshot(G, seeds, batch), snapshot(F, seeds, batch))
+    # the public field pairs the new lists with the new weights
+    assert {i: None if L is None else [(l.targetNode, int(l.type), l.weight) for l in L] for i, L in G.graph.items()} == \
+           {i: None if L is None else [(l.targetNode, int(l.type), l.weight) for l in L] for i, L in F.graph.items()}
+    F.close()
+    G.close()
+
+
+def test_mirror_flat_graph_follows_the_append():
+    """A flat Graph continues with merged copies of its arrays: the public field, normalized() and a later buildGraph() see
+    the appended links; the caller's arrays are untouched."""
+    g = _small()
+    keep = {k: v.copy() for k, v in g.items()}
+    G = build(g)
+    a = random_links(61, g, 50, 9, weights=(1.0, 0.25))
+    G.appendLinks(*a)
+    want, _ = patched(g, *a)
+    assert all(np.array_equal(g[k], keep[k]) for k in g)
+    F = build(want)
+    fields = lambda X: {i: None if L is None else [(l.targetNode, int(l.type), l.weight) for l in L] for i, L in X.graph.items()}
+    assert fields(G) == fields(F)
+    G.buildGraph()                                        # destroy + create from the merged copies
+    seeds, batch = (0, 9, 20), np.arange(40)
+    assert sizes(G) == sizes(F)
+    assert_same(snapshot(G, seeds, batch), snapshot(F, seeds, batch))
+    F.close()
+    G.close()
