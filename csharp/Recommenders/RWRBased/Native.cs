@@ -64,6 +64,12 @@ namespace Recommenders.RWRBased {
         [DllImport(Lib)] public static extern int rwr_model_run_restart_batch(GraphHandle g, int K, long[] sup_ptr, int[] sup_idx,
             double[] sup_val, int[] start, double d, int run_mode, double value, double[] rank_out, long[] iters_out);
 
+        // the same K walks ranked on the device: top_n (id, score) entries per vector, the LIKEd items of the members of
+        // exclusion set k (excl_ptr / excl_idx in CSR form; excl_ptr null: the nodes of vector k's support) left out
+        [DllImport(Lib)] public static extern int rwr_recommend_restart_batch(GraphHandle g, int K, long[] sup_ptr, int[] sup_idx,
+            double[] sup_val, int[] start, long[] excl_ptr, int[] excl_idx, double d, int n_iter, int top_n, long[] ids,
+            double[] scores, int[] counts);
+
         [DllImport(Lib)] public static extern int rwr_model_run_restart(GraphHandle g, double[] restart, double[] rank_in, double d,
             int run_mode, double value, double[] rank_out, out long iters_out);
 

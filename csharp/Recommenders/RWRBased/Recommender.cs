@@ -71,5 +71,48 @@ namespace Recommenders.RWRBased {
             }
             return all;
         }
+
+        // addition: the top-N lists of K walks with caller-set restart vectors (Model.restart), ranked on the device
+        // (rwr_recommend_restart_batch).  Vector k has restart[nodes[k][j]] = weights[k][j] >= 0 and zero elsewhere; start as in
+        // Model.RunRestartBatch.  exclude[k]: the nodes whose LIKEd items are not candidates of vector k (Recommender.cs:20-24
+        // for each of them); exclude == null: the nodes of vector k's own support.  List k is what ranking the rank of that
+        // Model after run(nIteration) gives
+        public List<KeyValuePair<long, double>>[] RecommendationRestartBatch(int[][] nodes, double[][] weights, int[] start,
+                                                                             double dampingFactor, int nIteration, int topN,
+                                                                             int[][] exclude = null) {
+            if (topN < 1) throw new System.ArgumentOutOfRangeException("topN", "RecommendationRestartBatch needs topN >= 1");
+            int K = nodes.Length;
+            if (weights.Length != K || (start != null && start.Length != K) || (exclude != null && exclude.Length != K))
+                throw new System.ArgumentException("nodes, weights, start and exclude must hold one entry per vector");
+            var ptr = new long[K + 1];
+            for (int k = 0; k < K; k++) {
+                if (nodes[k].Length != weights[k].Length)
+                    throw new System.ArgumentException("a restart vector's nodes and weights differ in length");
+                ptr[k + 1] = ptr[k] + nodes[k].Length;
+            }
+            var idx = new int[ptr[K]];
+            var val = new double[ptr[K]];
+            for (int k = 0; k < K; k++) {
+                System.Array.Copy(nodes[k], 0, idx, ptr[k], nodes[k].Length);
+                System.Array.Copy(weights[k], 0, val, ptr[k], weights[k].Length);
+            }
+            long[] exclPtr = null;
+            int[] exclIdx = null;
+            if (exclude != null) {
+                exclPtr = new long[K + 1];
+                for (int k = 0; k < K; k++) exclPtr[k + 1] = exclPtr[k] + exclude[k].Length;
+                exclIdx = new int[exclPtr[K]];
+                for (int k = 0; k < K; k++) System.Array.Copy(exclude[k], 0, exclIdx, exclPtr[k], exclude[k].Length);
+            }
+            var ids = new long[(long)K * topN]; var scores = new double[(long)K * topN]; var counts = new int[K];
+            Native.Check(Native.rwr_recommend_restart_batch(graph.handle, K, ptr, idx, val, start, exclPtr, exclIdx, dampingFactor,
+                                                            nIteration, topN, ids, scores, counts));
+            var all = new List<KeyValuePair<long, double>>[K];
+            for (int k = 0; k < K; k++) {
+                all[k] = new List<KeyValuePair<long, double>>(counts[k]);
+                for (int q = 0; q < counts[k]; q++) all[k].Add(new KeyValuePair<long, double>(ids[(long)k * topN + q], scores[(long)k * topN + q]));
+            }
+            return all;
+        }
     }
 }

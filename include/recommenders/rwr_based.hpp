@@ -387,6 +387,44 @@ public:
         return out;
     }
 
+    // addition: the top-N lists of K walks with caller-set restart vectors, ranked on the device (rwr_recommend_restart_batch).
+    // nodes / weights (>= 0) / start as in Model::runRestartBatch.  exclude[k]: the nodes whose LIKEd items are not candidates
+    // of vector k (Recommender.cs:20-24 for each of them); exclude == nullptr: the nodes of vector k's own support
+    std::vector<std::vector<std::pair<int64_t, double>>> recommendRestartBatch(
+        const std::vector<std::vector<int>> &nodes, const std::vector<std::vector<double>> &weights, const std::vector<int> &start,
+        double dampingFactor, int nIteration, int topN, const std::vector<std::vector<int>> *exclude = nullptr)
+    {
+        const int32_t K = (int32_t)nodes.size();
+        if (topN < 1) throw std::invalid_argument("recommendRestartBatch: topN must be >= 1");
+        if (weights.size() != nodes.size() || (!start.empty() && start.size() != nodes.size()) ||
+            (exclude && exclude->size() != nodes.size()))
+            throw std::invalid_argument("recommendRestartBatch: nodes, weights, start and exclude must hold one entry per vector");
+        std::vector<int64_t> ptr((size_t)K + 1, 0), eptr((size_t)K + 1, 0);
+        std::vector<int32_t> idx, eidx;
+        std::vector<double> val;
+        for (int32_t k = 0; k < K; ++k) {
+            if (nodes[k].size() != weights[k].size())
+                throw std::invalid_argument("recommendRestartBatch: a restart vector's nodes and weights differ in length");
+            idx.insert(idx.end(), nodes[k].begin(), nodes[k].end());
+            val.insert(val.end(), weights[k].begin(), weights[k].end());
+            ptr[(size_t)k + 1] = (int64_t)idx.size();
+            if (exclude) eidx.insert(eidx.end(), (*exclude)[k].begin(), (*exclude)[k].end());
+            eptr[(size_t)k + 1] = (int64_t)eidx.size();
+        }
+        std::vector<int32_t> st(start.begin(), start.end());
+        std::vector<int64_t> ids((size_t)K * (size_t)topN);
+        std::vector<double> scores((size_t)K * (size_t)topN);
+        std::vector<int32_t> counts((size_t)K);
+        check(rwr_recommend_restart_batch(graph_.handle(), K, ptr.data(), idx.data(), val.data(), st.empty() ? nullptr : st.data(),
+                                          exclude ? eptr.data() : nullptr, eidx.data(), dampingFactor, nIteration, topN,
+                                          ids.data(), scores.data(), counts.data()));
+        std::vector<std::vector<std::pair<int64_t, double>>> out((size_t)K);
+        for (int32_t k = 0; k < K; ++k)
+            for (int32_t q = 0; q < counts[k]; ++q)
+                out[k].emplace_back(ids[(size_t)k * (size_t)topN + q], scores[(size_t)k * (size_t)topN + q]);
+        return out;
+    }
+
 private:
     Graph &graph_;
 };

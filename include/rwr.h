@@ -337,6 +337,31 @@ int32_t rwr_model_deliver_restart(rwr_graph *g, const double *restart, double d,
 int32_t rwr_model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
                                     const double *sup_val, const int32_t *start, double d,
                                     int32_t run_mode, double value, double *rank_out, int64_t *iters_out);
+/* The same K walks ranked on the device: the top_n candidates of every vector instead of its rank row -- the list a group
+ * of users or a topic is recommended.  Vectors and starts exactly as in rwr_model_run_restart_batch; n_iter as Model.run(int)
+ * (a negative count runs no step; there is no threshold mode: Recommendation takes an iteration count, Recommender.cs:14-18).
+ * Exclusion set k is the node list excl_idx[excl_ptr[k] .. excl_ptr[k+1]): the RAW out-links of type LIKE of every node in it
+ * are not candidates (Recommender.cs:20-24 applied to each member).  excl_ptr == NULL: set k is the indices listed in vector
+ * k's support, whatever their values -- a group is not recommended what its members already like.  A node may appear twice
+ * in a set; an empty set is legal; the support and start nodes themselves are NOT excluded (the reference does not exclude
+ * the seed node either).
+ * Result k: the rank row that rwr_model_run_restart(g, dense(v_k), rank0_k, d, RWR_RUN_ITERATIONS, n_iter, ...) returns; of
+ * it the ITEM nodes that no member of set k LIKEs, by score descending, then id descending (Recommender.cs:35-38); the first
+ * top_n of them in row k of ids / scores (K x top_n, row-major), counts[k] = entries written, the rest of the row id 0 /
+ * score 0.  Ids are identical to that composition and scores bitwise equal to it, for every vector (K == 1 and a vector
+ * with more than RWR_RESTART_EXACT_MAX non-zero entries run vector by vector through that very call).
+ *   - The domain is that of the Recommendation entries: a graph with a negative weight, d outside [0, 1], a non-finite or a
+ *     negative sup_val give RWR_E_UNSUPPORTED (the ranking marks exclusions with -1 and relies on scores >= 0;
+ *     rwr_model_run_restart_batch remains the way to run signed vectors).
+ *   - Argument errors, all found before any device work: everything rwr_model_run_restart_batch reports for the vectors,
+ *     with the same status; NULL ids / scores / counts (K > 0), top_n < 1, an excl_ptr that does not start at 0 or that
+ *     decreases, a NULL excl_idx while excl_ptr[K] > 0 give RWR_E_INVALID; an exclusion index outside [0, n) gives
+ *     RWR_E_RANGE with the batch position in the message.  A NULL g is refused first; K == 0 is a no-op (RWR_OK).
+ *     A refused call writes nothing. */
+int32_t rwr_recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                    const double *sup_val, const int32_t *start, const int64_t *excl_ptr,
+                                    const int32_t *excl_idx, double d, int32_t n_iter, int32_t top_n,
+                                    int64_t *ids, double *scores, int32_t *counts);
 
 /* ---- row-partitioned mode (graphs beyond one GPU; BASELINE.json config 5) ------------
  * An ADDITION: the reference has no distributed mode.  The transition matrix is partitioned by SOURCE rows

@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "engine.h"
+#include "exclude_plan.h"
 
 namespace rwr {
 
@@ -870,20 +871,11 @@ int32_t rwr_model_run_restart(rwr_graph *g, const double *restart, const double 
     return model_run_restart(g, restart, rank_in, d, run_mode, value, rank_out, iters_out);
 }
 
-int32_t rwr_model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
-                                    const double *sup_val, const int32_t *start, double d, int32_t run_mode, double value,
-                                    double *rank_out, int64_t *iters_out)
+// The K restart vectors of a batch (CSR) and their start nodes, as both batched restart entries take them: the pointer array,
+// then per vector its start, its indices and values, and that no index appears twice.  `who` names the entry in the message.
+static int32_t check_restart_vectors(const char *who, int32_t n, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                     const double *sup_val, const int32_t *start)
 {
-    static const char *const who = "rwr_model_run_restart_batch";
-    g_err[0] = 0;
-    if (!g) { set_error("%s: NULL graph", who); return RWR_E_INVALID; }
-    if (K < 0) { set_error("%s: negative K", who); return RWR_E_INVALID; }
-    if (K == 0) return RWR_OK;
-    if (!sup_ptr || !rank_out) { set_error("%s: NULL sup_ptr or rank_out", who); return RWR_E_INVALID; }
-    if (run_mode != RWR_RUN_ITERATIONS && run_mode != RWR_RUN_THRESHOLD && run_mode != RWR_RUN_DEFAULT_THRESHOLD) {
-        set_error("%s: unknown run_mode %d", who, run_mode);
-        return RWR_E_INVALID;
-    }
     if (sup_ptr[0] != 0) { set_error("%s: sup_ptr[0] = %lld, not 0", who, (long long)sup_ptr[0]); return RWR_E_INVALID; }
     for (int32_t k = 0; k < K; ++k)
         if (sup_ptr[k + 1] < sup_ptr[k]) {
@@ -891,7 +883,6 @@ int32_t rwr_model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_
             return RWR_E_INVALID;
         }
     if (sup_ptr[K] > 0 && (!sup_idx || !sup_val)) { set_error("%s: NULL sup_idx or sup_val", who); return RWR_E_INVALID; }
-    const int32_t n = g->n;
     try {
         std::vector<int32_t> sorted;
         for (int32_t k = 0; k < K; ++k) {
@@ -922,8 +913,81 @@ int32_t rwr_model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_
         set_error("%s: host allocation failed", who);
         return RWR_E_NOMEM;
     }
+    return RWR_OK;
+}
+
+int32_t rwr_model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                    const double *sup_val, const int32_t *start, double d, int32_t run_mode, double value,
+                                    double *rank_out, int64_t *iters_out)
+{
+    static const char *const who = "rwr_model_run_restart_batch";
+    g_err[0] = 0;
+    if (!g) { set_error("%s: NULL graph", who); return RWR_E_INVALID; }
+    if (K < 0) { set_error("%s: negative K", who); return RWR_E_INVALID; }
+    if (K == 0) return RWR_OK;
+    if (!sup_ptr || !rank_out) { set_error("%s: NULL sup_ptr or rank_out", who); return RWR_E_INVALID; }
+    if (run_mode != RWR_RUN_ITERATIONS && run_mode != RWR_RUN_THRESHOLD && run_mode != RWR_RUN_DEFAULT_THRESHOLD) {
+        set_error("%s: unknown run_mode %d", who, run_mode);
+        return RWR_E_INVALID;
+    }
+    RWR_TRY(check_restart_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start));
     RWR_BIND(g);
     return model_run_restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out);
+}
+
+int32_t rwr_recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                    const double *sup_val, const int32_t *start, const int64_t *excl_ptr,
+                                    const int32_t *excl_idx, double d, int32_t n_iter, int32_t top_n, int64_t *ids,
+                                    double *scores, int32_t *counts)
+{
+    static const char *const who = "rwr_recommend_restart_batch";
+    g_err[0] = 0;
+    if (!g) { set_error("%s: NULL graph", who); return RWR_E_INVALID; }
+    if (K < 0) { set_error("%s: negative K", who); return RWR_E_INVALID; }
+    if (K == 0) return RWR_OK;
+    if (!sup_ptr || !ids || !scores || !counts) { set_error("%s: NULL sup_ptr, ids, scores or counts", who); return RWR_E_INVALID; }
+    if (top_n < 1) { set_error("%s: top_n must be >= 1", who); return RWR_E_INVALID; }
+    RWR_TRY(check_restart_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start));
+    // the domain of the Recommendation entries: the exclusion marker (-1) and the ranking keys assume scores >= 0
+    for (int32_t k = 0; k < K; ++k)
+        for (int64_t q = sup_ptr[k]; q < sup_ptr[k + 1]; ++q)
+            if (sup_val[q] < 0.0) {
+                set_error("%s: restart[%d] = %g (batch position %d) is negative: ranks could go negative; "
+                          "rwr_model_run_restart_batch runs signed vectors", who, sup_idx[q], sup_val[q], k);
+                return RWR_E_UNSUPPORTED;
+            }
+    if (excl_ptr) {
+        const rwr::ExcludeCheck c = rwr::exclude_check(g->n, K, excl_ptr, excl_idx);
+        switch (c.verdict) {
+            case rwr::EXCLUDE_OK: break;
+            case rwr::EXCLUDE_BAD_PTR0:
+                set_error("%s: excl_ptr[0] = %lld, not 0", who, (long long)excl_ptr[0]);
+                return RWR_E_INVALID;
+            case rwr::EXCLUDE_PTR_DECREASES:
+                set_error("%s: excl_ptr decreases at batch position %d", who, c.bad_k);
+                return RWR_E_INVALID;
+            case rwr::EXCLUDE_NULL_IDX:
+                set_error("%s: NULL excl_idx", who);
+                return RWR_E_INVALID;
+            case rwr::EXCLUDE_BAD_INDEX:
+                set_error("%s: exclusion index %d (batch position %d) is outside [0, %d)", who, c.bad_index, c.bad_k, g->n);
+                return RWR_E_RANGE;
+        }
+    }
+    if (!g->nonneg) {
+        set_error("%s: Recommendation needs non-negative finite link weights and positive row sums; "
+                  "rwr_model_run_restart_batch accepts such graphs", who);
+        return RWR_E_UNSUPPORTED;
+    }
+    if (!(d >= 0.0 && d <= 1.0)) {
+        set_error("%s: Recommendation needs a damping factor in [0, 1] (got %g); rwr_model_run_restart_batch accepts any value", who, d);
+        return RWR_E_UNSUPPORTED;
+    }
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    RWR_BIND(g);
+    // excl_ptr == NULL: set k is the indices of vector k's support, whatever their values
+    return recommend_restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, excl_ptr ? excl_ptr : sup_ptr,
+                                   excl_ptr ? excl_idx : sup_idx, d, n_iter, top_n, ids, scores, counts);
 }
 
 int32_t rwr_model_deliver_restart(rwr_graph *g, const double *restart, double d, const double *rank, double *next_rank)

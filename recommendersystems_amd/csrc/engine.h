@@ -200,12 +200,18 @@ int32_t eval_ranked_multi(rwr_graph **gs, int32_t count, const int64_t *test_ptr
 // (mode 0: top-k into host arrays; mode 1: full rank vector of one seed)
 int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
                         int64_t *ids, double *scores, int32_t *counts, int64_t row_stride);
+// ... the K_all x top_n lists of g->d_out_id / d_out_score / d_counts into the caller's arrays (host rows row_stride wide)
+int32_t copy_lists_back(rwr_graph *g, int32_t K_all, int32_t top_n, int64_t *ids, double *scores, int32_t *counts,
+                        int64_t row_stride);
 int32_t eval_ranked(rwr_graph *g, int32_t cnt, const int64_t *test_sorted_host, int64_t n_test, int64_t *n_hits,
                     double *sum_precision);
 int32_t eval_ranked_batch(rwr_graph *g, int32_t K, int64_t row_stride, const int64_t *test_ptr_host,
                           const int64_t *test_sorted_host, int64_t *n_hits, double *sum_precision);
 // rank.hip: the exclusion (k_exclude: X[tile][n][G], one seed per slot, -1 = none) and the ranking of a tile group / one tile
 void launch_exclude(rwr_graph *g, int G, int tg, double *X, const int32_t *d_seeds, hipStream_t s);
+// ... of a set of nodes per slot (k_exclude_segments): the segments exclude_plan.h cut the members' raw lists into
+void launch_exclude_segments(rwr_graph *g, int G, int32_t nseg, const int32_t *seg_slot, const int64_t *seg_p0,
+                             const int64_t *seg_p1, double *X, hipStream_t s);
 int32_t rank_group_select(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, const double *X,
                           const int32_t *d_seeds, hipStream_t s);
 int rank_select_max_k();
@@ -236,6 +242,11 @@ int32_t model_deliver_restart(rwr_graph *g, const double *v, double d, const dou
 int32_t model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
                                 const int32_t *start, double d, int32_t run_mode, double value, double *rank_out,
                                 int64_t *iters_out);
+// ... and the same walks ranked on the device (rwr_recommend_restart_batch): the top_n candidates of every vector,
+// the raw LIKE links of the members of set k (set_ptr / set_idx, validated by exclude_check) excluded; T steps, values >= 0
+int32_t recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
+                                const int32_t *start, const int64_t *set_ptr, const int32_t *set_idx, double d, int32_t n_iter,
+                                int32_t top_n, int64_t *ids, double *scores, int32_t *counts);
 // ... and its kernels (restart.hip, beside the fold they share with the single call).  Pair j = support row pr[j] with
 // restart value pv[j] of the vector in slot pq[j] = tile * G + lane of the group's X[tile][n][G]; fold[j] receives the
 // row's next rank; st[slot]: the constructor's start node, -1 = every rank 1, -2 = padding slot

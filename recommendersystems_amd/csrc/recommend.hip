@@ -120,8 +120,8 @@ double now_ms()
 
 // The results of a call, K_all x top_n (device rows are top_n wide; host rows are row_stride wide), once the main stream
 // has finished.  ids / scores NULL: the caller consumes the lists on the device (e.g. rwr_recommend_eval).
-static int32_t copy_lists_back(rwr_graph *g, int32_t K_all, int32_t top_n, int64_t *ids, double *scores, int32_t *counts,
-                               int64_t row_stride)
+int32_t copy_lists_back(rwr_graph *g, int32_t K_all, int32_t top_n, int64_t *ids, double *scores, int32_t *counts,
+                        int64_t row_stride)
 {
     hipStream_t s = g->stream;
     std::vector<int32_t> hc((size_t)K_all);

@@ -12,10 +12,16 @@
 //
 // The SpMM runs the weighted kernels (ensure_in_w, as restart.hip): the step lasts as long as its chains, which the SpMM
 // runs beside, so the value-free form's smaller matrix stream would shorten nothing (measured).
+//
+// rwr_recommend_restart_batch is the same driver -- slot dealing, pair upload, step loop, statistics -- with
+// another end of a tile group: after step T the raw LIKE links of every vector's exclusion set are marked in X
+// (k_exclude_segments over exclude_plan.h's segments) and the group is ranked where it lies (rank.hip), so K x top_n entries
+// leave the device in place of K x n.  `Ranked` carries what that end needs; a call without one is the full-vector entry.
 #include <algorithm>
 #include <cstring>
 #include <new>
 
+#include "exclude_plan.h"
 #include "iterate.h"
 
 namespace rwr {
@@ -30,36 +36,123 @@ struct StreamsIdle {
         (void)hipStreamSynchronize(g->stream2);
     }
 };
+
+// The ranked end of a call: the exclusion sets (CSR over batch positions), the lists' width and destination, and the device
+// copy of the exclusion plan.  Declared by the entry point before its StreamsIdle, so the buffers outlive the kernels.
+struct Ranked {
+    const int64_t *set_ptr;
+    const int32_t *set_idx;
+    int32_t top_n;
+    int64_t *ids;
+    double *scores;
+    int32_t *counts;
+    ExcludePlan plan;
+    DevBuf<int32_t> d_seg_slot;
+    DevBuf<int64_t> d_seg_p0, d_seg_p1;
+};
 }  // namespace
 
-// Outside the batched domain: rwr_model_run_restart per vector, on the dense vector and the constructor's rank
+// The zeroed output tables of the call (indexed by batch position), the slots' batch positions in g->d_slot_k -- the ranking's
+// output-row table and, read through its `seeds` parameter, its liveness array -- and the exclusion plan of that slot
+// assignment (slots_per_group slots form a tile group).  The host vectors are pageable: the caller synchronises s.
+static int32_t ranked_prepare(rwr_graph *g, Ranked &rk, int32_t K, const std::vector<int32_t> &slot_k, size_t slots_per_group,
+                              hipStream_t s)
+{
+    const size_t out_all = (size_t)K * (size_t)rk.top_n, slots = slot_k.size();
+    RWR_TRY(g->d_out_id.ensure(out_all + 64));
+    RWR_TRY(g->d_out_score.ensure(out_all + 64));
+    RWR_TRY(g->d_counts.ensure((size_t)K + 64));
+    RWR_HIP(hipMemsetAsync(g->d_out_id.p, 0, out_all * sizeof(int64_t), s));
+    RWR_HIP(hipMemsetAsync(g->d_out_score.p, 0, out_all * sizeof(double), s));
+    RWR_HIP(hipMemsetAsync(g->d_counts.p, 0, (size_t)K * sizeof(int32_t), s));
+    RWR_TRY(g->d_slot_k.ensure(slots));
+    RWR_HIP(hipMemcpyAsync(g->d_slot_k.p, slot_k.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    rk.plan = exclude_plan(g->n, g->h_rowptr.data(), slots, slot_k.data(), slots_per_group, K, rk.set_ptr, rk.set_idx);
+    if (rk.plan.check.verdict != EXCLUDE_OK) {                  // (api.hip refuses such sets before the call gets here)
+        set_error("rwr_recommend_restart_batch: exclusion sets failed their check (verdict %d)", (int)rk.plan.check.verdict);
+        return RWR_E_INVALID;
+    }
+    const size_t nseg = rk.plan.seg_slot.size();
+    if (nseg > 0x7FFFFFFFull) { set_error("rwr_recommend_restart_batch: too many exclusion segments"); return RWR_E_UNSUPPORTED; }
+    if (nseg > 0) {
+        RWR_TRY(rk.d_seg_slot.alloc(nseg));
+        RWR_TRY(rk.d_seg_p0.alloc(nseg));
+        RWR_TRY(rk.d_seg_p1.alloc(nseg));
+        RWR_HIP(hipMemcpyAsync(rk.d_seg_slot.p, rk.plan.seg_slot.data(), nseg * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(rk.d_seg_p0.p, rk.plan.seg_p0.data(), nseg * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(rk.d_seg_p1.p, rk.plan.seg_p1.data(), nseg * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    }
+    return RWR_OK;
+}
+
+// Tile group grp (tg tiles of G slots from slot q0 on) holds its final ranks in X: the exclusion, then the ranking as
+// recommend_batch runs it, the slots' batch positions standing in for the seeds (>= 0: a live slot)
+static int32_t ranked_finish_group(rwr_graph *g, const Ranked &rk, int G, int tg, int grp, size_t q0, double *X, Profile &prof,
+                                   hipStream_t s)
+{
+    const int64_t j0 = rk.plan.group_off[(size_t)grp], nseg = rk.plan.group_off[(size_t)grp + 1] - j0;
+    const int32_t *slot_k = g->d_slot_k.p + q0;
+    hipEvent_t a; RWR_TRY(prof.record(a, s));
+    launch_exclude_segments(g, G, (int32_t)nseg, rk.d_seg_slot.p + j0, rk.d_seg_p0.p + j0, rk.d_seg_p1.p + j0, X, s);
+    RWR_HIP(hipGetLastError());
+    if (rk.top_n <= rank_select_max_k()) {
+        RWR_TRY(rank_group_select(g, G, tg, slot_k, rk.top_n, X, slot_k, s));
+    } else {
+        for (int t = 0; t < tg; ++t)
+            RWR_TRY(rank_tile(g, G, slot_k + (size_t)t * G, rk.top_n, X + (size_t)t * (size_t)g->n * G, slot_k + (size_t)t * G, s));
+    }
+    RWR_TRY(prof.end(prof.rank, a, s));
+    return RWR_OK;
+}
+
+// Outside the batched domain: rwr_model_run_restart per vector, on the dense vector and the constructor's rank.  rk: each
+// row goes back to the device as a tile of one lane -- vector k its own tile group of one slot -- for the same exclusion and
+// ranking as a batched group's
 static int32_t run_vector_by_vector(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
                                     const int32_t *start, double d, int32_t run_mode, double value, double *rank_out,
-                                    int64_t *iters_out)
+                                    int64_t *iters_out, Ranked *rk, const char *who)
 {
     const int32_t n = g->n;
-    std::vector<double> v((size_t)n), x((size_t)n);
+    hipStream_t s = g->stream;
+    std::vector<double> v((size_t)n), x((size_t)n), row(rk ? (size_t)n : 0);
+    Profile prof(g);
+    if (rk) {
+        std::vector<int32_t> slot_k((size_t)K);
+        for (int32_t k = 0; k < K; ++k) slot_k[(size_t)k] = k;
+        RWR_TRY(ranked_prepare(g, *rk, K, slot_k, 1, s));
+        RWR_HIP(hipStreamSynchronize(s));
+    }
     for (int32_t k = 0; k < K; ++k) {
         std::fill(v.begin(), v.end(), 0.0);
         for (int64_t q = sup_ptr[k]; q < sup_ptr[k + 1]; ++q) v[sup_idx[q]] = sup_val[q];
         const int32_t st = start ? start[k] : -1;
         std::fill(x.begin(), x.end(), st < 0 ? 1.0 : 0.0);         // Model.cs:25 / :44
         if (st >= 0) x[st] = (double)n;
-        const int32_t rc = model_run_restart(g, v.data(), x.data(), d, run_mode, value, rank_out + (size_t)k * n,
+        const int32_t rc = model_run_restart(g, v.data(), x.data(), d, run_mode, value, rk ? row.data() : rank_out + (size_t)k * n,
                                              iters_out ? iters_out + k : nullptr);
         if (rc != RWR_OK) {
             char msg[400];
             snprintf(msg, sizeof(msg), "%s", rwr_last_error());
-            set_error("rwr_model_run_restart_batch: vector %d: %s", k, msg);
+            set_error("%s: vector %d: %s", who, k, msg);
             return rc;
+        }
+        if (rk) {
+            RWR_TRY(g->X.ensure((size_t)n));
+            RWR_HIP(hipMemcpyAsync(g->X.p, row.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+            RWR_TRY(ranked_finish_group(g, *rk, 1, 1, k, (size_t)k, g->X.p, prof, s));
+            RWR_HIP(hipStreamSynchronize(s));                   // (the next vector's run reuses row and X)
+            RWR_TRY(prof.fold(g));
         }
     }
     return RWR_OK;
 }
 
-static int32_t model_run_restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
-                                            const double *sup_val, const int32_t *start, double d, int32_t run_mode,
-                                            double value, double *rank_out, int64_t *iters_out)
+// rk == nullptr: rwr_model_run_restart_batch, the finished columns leave as rows of rank_out.  Otherwise
+// rwr_recommend_restart_batch (run_mode = RWR_RUN_ITERATIONS; a nonneg graph, d in [0, 1] and values >= 0 are api.hip's check):
+// the finished groups are ranked on the device and the lists copied back once, after the last group
+static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                  const double *sup_val, const int32_t *start, double d, int32_t run_mode,
+                                  double value, double *rank_out, int64_t *iters_out, Ranked *rk, const char *who)
 {
     const double t_begin = now_ms();
     const int32_t n = g->n;
@@ -78,7 +171,11 @@ static int32_t model_run_restart_batch_body(rwr_graph *g, int32_t K, const int64
     // one vector, a vector of the tolerance class, or a graph / damping factor outside the domain of the batched kernels
     // (model_run_batch's policy): rwr_model_run_restart per vector, which the contract is equality with
     if (K == 1 || wide || !g->nonneg || !(d >= 0.0 && d <= 1.0)) {
-        RWR_TRY(run_vector_by_vector(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out));
+        RWR_TRY(run_vector_by_vector(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out, rk, who));
+        if (rk) {
+            RWR_TRY(copy_lists_back(g, K, rk->top_n, rk->ids, rk->scores, rk->counts, rk->top_n));
+            g->stats.seeds_done += K;
+        }
         g->stats.total_wall_ms += now_ms() - t_begin;
         return RWR_OK;
     }
@@ -88,7 +185,8 @@ static int32_t model_run_restart_batch_body(rwr_graph *g, int32_t K, const int64
     const double c1 = 1 - d;                                   // Model.cs:84
     const int G = resolve_G(g, K);
     int TG = 1;
-    RWR_TRY(ensure_workspace(g, G, K, &TG, 1));               // + cs_diff: differences, then staging of the extracted columns
+    // + cs_diff: differences, then staging of the extracted columns (the ranked end needs neither)
+    RWR_TRY(ensure_workspace(g, G, K, &TG, rk ? 0 : 1));
     const int ntiles = (int)cdiv((size_t)K, (size_t)G);
     const size_t slots = (size_t)ntiles * G;
     // vectors dealt to tile slots round-robin over the tiles (as upload_seed_slots deals seeds): slot_k = batch position, -1 =
@@ -144,6 +242,7 @@ static int32_t model_run_restart_batch_body(rwr_graph *g, int32_t K, const int64
         RWR_HIP(hipMemcpyAsync(d_pr.p, pr.data(), npairs_all * sizeof(int32_t), hipMemcpyHostToDevice, s));
         RWR_HIP(hipMemcpyAsync(d_pv.p, pv.data(), npairs_all * sizeof(double), hipMemcpyHostToDevice, s));
     }
+    if (rk) RWR_TRY(ranked_prepare(g, *rk, K, slot_k, (size_t)TG * G, s));
     RWR_HIP(hipStreamSynchronize(s));                           // (the host vectors above are pageable)
 
     Profile prof(g);                                            // (column extraction counts as ranking time)
@@ -172,6 +271,10 @@ static int32_t model_run_restart_batch_body(rwr_graph *g, int32_t K, const int64
         sp.hub_scan = v_nonneg;
         int64_t steps = 0;
         for (;;) {
+            if (rk && steps == T) {                             // every column ends here and stays on the device
+                RWR_TRY(ranked_finish_group(g, *rk, G, tg, grp, q0, X, prof, s));
+                break;
+            }
             if (by_count ? steps == T : steps > 0) {
                 // the columns whose run ends here: every one after step T, the converged ones in threshold mode
                 row_of.assign(nslots, -1);
@@ -246,6 +349,10 @@ static int32_t model_run_restart_batch_body(rwr_graph *g, int32_t K, const int64
         g->stats.spmm_seed_steps += (int64_t)real * steps;
         g->stats.spmm_dense_seed_steps += (int64_t)real * steps;
     }
+    if (rk) {                                                   // one copy-back of K x top_n entries, as recommend_batch's
+        RWR_TRY(copy_lists_back(g, K, rk->top_n, rk->ids, rk->scores, rk->counts, rk->top_n));
+        g->stats.seeds_done += K;
+    }
     RWR_HIP(hipStreamSynchronize(s));
     RWR_HIP(hipStreamSynchronize(s2));
     RWR_TRY(prof.fold(g));
@@ -254,7 +361,7 @@ static int32_t model_run_restart_batch_body(rwr_graph *g, int32_t K, const int64
     g->stats.tile_group = TG;
     g->stats.total_wall_ms += now_ms() - t_begin;
     if (stuck >= 0) {
-        set_error("rwr_model_run_restart_batch: vector %d: no convergence within %lld iterations (RWR_MAX_ITERS)", stuck,
+        set_error("%s: vector %d: no convergence within %lld iterations (RWR_MAX_ITERS)", who, stuck,
                   (long long)end.max_iters);
         return RWR_E_UNSUPPORTED;
     }
@@ -262,19 +369,37 @@ static int32_t model_run_restart_batch_body(rwr_graph *g, int32_t K, const int64
 }
 
 // no C++ exception crosses the C boundary
+static int32_t restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
+                             const int32_t *start, double d, int32_t run_mode, double value, double *rank_out, int64_t *iters_out,
+                             Ranked *rk, const char *who)
+{
+    try {
+        return restart_batch_body(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out, rk, who);
+    } catch (const std::bad_alloc &) {
+        set_error("%s: host allocation failed", who);
+        return RWR_E_NOMEM;
+    } catch (...) {
+        set_error("%s: unexpected host exception", who);
+        return RWR_E_HIP;
+    }
+}
+
 int32_t model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
                                 const int32_t *start, double d, int32_t run_mode, double value, double *rank_out,
                                 int64_t *iters_out)
 {
-    try {
-        return model_run_restart_batch_body(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out);
-    } catch (const std::bad_alloc &) {
-        set_error("rwr_model_run_restart_batch: host allocation failed");
-        return RWR_E_NOMEM;
-    } catch (...) {
-        set_error("rwr_model_run_restart_batch: unexpected host exception");
-        return RWR_E_HIP;
-    }
+    return restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out, nullptr,
+                         "rwr_model_run_restart_batch");
+}
+
+int32_t recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
+                                const int32_t *start, const int64_t *set_ptr, const int32_t *set_idx, double d, int32_t n_iter,
+                                int32_t top_n, int64_t *ids, double *scores, int32_t *counts)
+{
+    Ranked rk{set_ptr, set_idx, top_n, ids, scores, counts, {}, {}, {}, {}};
+    StreamsIdle idle{g};                                        // (the plan's device copy outlives the kernels that read it)
+    return restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, d, RWR_RUN_ITERATIONS, (double)n_iter, nullptr, nullptr, &rk,
+                         "rwr_recommend_restart_batch");
 }
 
 }  // namespace rwr

@@ -501,28 +501,8 @@ class Model:
             mode, value = _lib.RWR_RUN_DEFAULT_THRESHOLD, 0.0
         else:
             mode, value = _lib.RWR_RUN_THRESHOLD, float(arg)
-        idx, val, ptr = [], [], [0]
-        for r in restarts:
-            if isinstance(r, dict):
-                i, v = list(r.keys()), list(r.values())
-            else:
-                i, v = r
-            i = np.asarray(i, dtype=np.int32).reshape(-1)
-            v = np.asarray(v, dtype=np.float64).reshape(-1)
-            if i.shape != v.shape:
-                raise ValueError("a restart vector's indices and values differ in length")
-            idx.append(i)
-            val.append(v)
-            ptr.append(ptr[-1] + int(i.shape[0]))
-        K, n = len(idx), graph.size()
-        sup_ptr = np.asarray(ptr, dtype=np.int64)
-        sup_idx = np.ascontiguousarray(np.concatenate(idx) if K else np.zeros(0, dtype=np.int32), dtype=np.int32)
-        sup_val = np.ascontiguousarray(np.concatenate(val) if K else np.zeros(0), dtype=np.float64)
-        st = None
-        if starts is not None:
-            st = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1)
-            if st.shape[0] != K:
-                raise ValueError(f"starts must hold {K} values")
+        K, sup_ptr, sup_idx, sup_val, st = _pack_restarts(restarts, starts)
+        n = graph.size()
         if out is None:
             ranks = np.zeros((K, n), dtype=np.float64)
         else:
@@ -563,6 +543,34 @@ class Model:
             return 0.0 < threshold
         diff = np.cumsum(np.abs(np.asarray(self.rank, dtype=np.float64) - self.nextRank))   # cumsum adds left to right
         return bool(diff[-1] < threshold)
+
+
+def _pack_restarts(restarts, starts):
+    """K restart vectors -- {node: weight} dicts or (indices, values) pairs -- as the CSR arrays of the batched restart
+    entries, and the start nodes as int32 (None stays None): (K, sup_ptr, sup_idx, sup_val, starts)."""
+    idx, val, ptr = [], [], [0]
+    for r in restarts:
+        if isinstance(r, dict):
+            i, v = list(r.keys()), list(r.values())
+        else:
+            i, v = r
+        i = np.asarray(i, dtype=np.int32).reshape(-1)
+        v = np.asarray(v, dtype=np.float64).reshape(-1)
+        if i.shape != v.shape:
+            raise ValueError("a restart vector's indices and values differ in length")
+        idx.append(i)
+        val.append(v)
+        ptr.append(ptr[-1] + int(i.shape[0]))
+    K = len(idx)
+    sup_ptr = np.asarray(ptr, dtype=np.int64)
+    sup_idx = np.ascontiguousarray(np.concatenate(idx) if K else np.zeros(0, dtype=np.int32), dtype=np.int32)
+    sup_val = np.ascontiguousarray(np.concatenate(val) if K else np.zeros(0), dtype=np.float64)
+    st = None
+    if starts is not None:
+        st = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1)
+        if st.shape[0] != K:
+            raise ValueError(f"starts must hold {K} values")
+    return K, sup_ptr, sup_idx, sup_val, st
 
 
 class Recommender:
@@ -649,4 +657,31 @@ class Recommender:
         _lib.check(lib.rwr_recommend_batch(self.graph._handle(), _p(seeds, C.c_int32), K, C.c_float(dampingFactor),
                                            int(nIteration), int(topN), _p(ids, C.c_int64), _p(sc, C.c_double),
                                            _p(counts, C.c_int32)))
+        return ids, sc, counts
+
+    def RecommendationRestartBatch(self, restarts, starts, dampingFactor: float, nIteration: int, topN: int, exclude=None):
+        """Top-N lists of K walks with caller-set restart vectors, ranked on the device (rwr_recommend_restart_batch, an
+        addition, see include/rwr.h): (ids[K,topN], scores[K,topN], counts[K]).  restarts and starts as in
+        Model.RunRestartBatch (non-negative weights).  exclude: a sequence of K node lists -- the items their members LIKE
+        are not candidates of vector k; None: the nodes of vector k's own support."""
+        lib = _lib.load()
+        K, sup_ptr, sup_idx, sup_val, st = _pack_restarts(restarts, starts)
+        ep = ei = None
+        if exclude is not None:
+            sets = [np.asarray(e, dtype=np.int32).reshape(-1) for e in exclude]
+            if len(sets) != K:
+                raise ValueError(f"exclude must hold {K} node lists")
+            ep = np.zeros(K + 1, dtype=np.int64)
+            ep[1:] = np.cumsum([len(e) for e in sets])
+            ei = np.ascontiguousarray(np.concatenate(sets) if K else np.zeros(0, dtype=np.int32), dtype=np.int32)
+        topN = int(topN)
+        ids = np.zeros((K, max(topN, 0)), dtype=np.int64)
+        sc = np.zeros((K, max(topN, 0)), dtype=np.float64)
+        counts = np.zeros(K, dtype=np.int32)
+        _lib.check(lib.rwr_recommend_restart_batch(self.graph._handle(), K, _p(sup_ptr, C.c_int64), _p(sup_idx, C.c_int32),
+                                                   _p(sup_val, C.c_double), None if st is None else _p(st, C.c_int32),
+                                                   None if ep is None else _p(ep, C.c_int64),
+                                                   None if ei is None else _p(ei, C.c_int32), float(dampingFactor),
+                                                   int(nIteration), topN, _p(ids, C.c_int64), _p(sc, C.c_double),
+                                                   _p(counts, C.c_int32)))
         return ids, sc, counts
