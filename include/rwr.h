@@ -122,6 +122,10 @@ typedef struct rwr_stats {
     int32_t reserved1;
     int64_t frontier_list_launches; /* SpMM launches of a batch's first steps that walked only each tile's
                                        frontier row list (the rows an out-link of a non-zero row reaches) */
+    int64_t rank_fused_groups;      /* tile groups of rwr_recommend_batch whose ranking ran inside the last step: the
+                                       step's second part kept only the rows that reach the seeds' thresholds */
+    int64_t rank_fused_fallbacks;   /* ... groups that tried and ran the step whole after all: a seed's candidates
+                                       did not fit its buffer */
 } rwr_stats;
 
 /* ---- library ------------------------------------------------------------------------- */

@@ -125,6 +125,7 @@ struct rwr_graph {
     rwr::DevBuf<uint64_t> keys, keys_alt;
     rwr::DevBuf<uint32_t> vals, vals_alt;
     rwr::DevBuf<uint8_t> sort_temp;
+    rwr::DevBuf<uint8_t> fused_ws;    // ranking inside the last step: per slot tau, append cursor, candidates
     rwr::DevBuf<int64_t> d_out_id;
     rwr::DevBuf<double> d_out_score;
     rwr::DevBuf<int32_t> d_counts;
@@ -213,7 +214,7 @@ void launch_exclude(rwr_graph *g, int G, int tg, double *X, const int32_t *d_see
 void launch_exclude_segments(rwr_graph *g, int G, int32_t nseg, const int32_t *seg_slot, const int64_t *seg_p0,
                              const int64_t *seg_p1, double *X, hipStream_t s);
 int32_t rank_group_select(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, const double *X,
-                          const int32_t *d_seeds, hipStream_t s);
+                          const int32_t *d_seeds, hipStream_t s, const int32_t *rows = nullptr, int32_t nrows = 0);
 int rank_select_max_k();
 int32_t emit_dangling(rwr_graph *g, const std::vector<int32_t> &rows, const std::vector<int32_t> &seeds, int32_t top_n,
                       hipStream_t s);

@@ -4,6 +4,8 @@
 #include "engine.h"
 #include "step_plan.h"
 
+#include <optional>
+
 namespace rwr {
 
 // One SpMM  Y = (1-d) P^T X  over tg tiles of G seeds.  Zin != nullptr: value-free form -- the kernels gather Zin (z of the
@@ -11,6 +13,21 @@ namespace rwr {
 // bitmaps of X / Y (first iterations), act: the rows the step can reach (k_mark_active).  hub_scan: see launch_spmv_exact.
 // rows: every row, a tail level (a batch's last steps; X / Y / Z keep their n rows) or the tiles' frontier
 // lists.  G = 1, skip_seed_row = false, seeds -> a device int32 holding -1: the link-only single-row SpMV.
+// A row of a tile's candidate buffer and what the selecting launch appends to: slot = tile * G + lane; a lane whose
+// row sum is >= tau[slot] takes position atomicAdd(cursor[slot], 1) of its slot's `stride` entries and stores (row, score)
+// there while the position is below cap, else sets *overflow.  Integer atomics only.
+struct RowScore {
+    int32_t row, pad;
+    double score;
+};
+struct SelSink {
+    const double *tau = nullptr;
+    int32_t *cursor = nullptr;
+    RowScore *cand = nullptr;
+    int32_t cap = 0, stride = 0;
+    int32_t *overflow = nullptr;
+};
+
 struct SpmmArgs {
     const double *X = nullptr;
     double *Y = nullptr;
@@ -24,6 +41,8 @@ struct SpmmArgs {
     double *Zout = nullptr;
     bool hub_scan = false;
     RowSource rows{};
+    int32_t row_first = 0, row_count = -1;   // a tail level's rows [row_first, row_first + row_count) only (-1: to the end)
+    const SelSink *sel = nullptr;            // the launch writes no Y: it appends the rows that reach tau (k_spmm_select)
 };
 void launch_spmm(rwr_graph *g, int G, int tg, const SpmmArgs &a, hipStream_t s);
 // k_init_seeds (Model ctor), k_make_z (z of `elems` elements of X, w_src[0] belonging to X's first row), k_make_z_nz (z and
@@ -74,13 +93,34 @@ struct GroupIter {
     // fresh = Model ctor (rank = n at the seed, 0 elsewhere);  !fresh = X already holds a caller-supplied rank vector
     // (Model.deliverRanks called on its own);  ranking_only: the caller (iterate_group) reads only the ranking
     int32_t init(bool fresh = true, bool ranks_nonneg = true, bool ranking_only = false);
-    int32_t step(const StepPlan &p, Profile &prof);
+    // row_first / row_count: a tail step over that part of its row list only
+    int32_t step(const StepPlan &p, Profile &prof, int32_t row_first = 0, int32_t row_count = -1);
+    // The step that has just run (a chainless tail step that forms no z), again over rows [row_first, row_first + row_count)
+    // of its list: its inputs are the other ping-pong buffers, still intact.  sel: select instead of writing (SelSink)
+    int32_t redo_rows(const StepPlan &p, Profile &prof, int32_t row_first, int32_t row_count, const SelSink *sel);
 };
 
 // A tile group of recommend_batch: T steps of the plan.  h_seeds: the group's tg * G seed slots on the host (-1 = padding),
 // whose tail flags decide which of the last steps run their seed-row chain.
+// split: head > 0 asks for the last step over the first `head` rows of tail_rows[0] only.  Granted (taken)
+// when that step is a chainless, probe-free walk of tail level 0 by the chunked kernels; gi / last then let the caller run
+// the rest of the step (GroupIter::redo_rows).
+struct SplitLast {
+    int32_t head = 0;
+    bool taken = false;
+    StepPlan last;
+    std::optional<GroupIter> gi;   // out: the group's iterator after the head part
+};
 int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const int64_t *d_evoff, const int32_t *h_seeds,
-                      double d, int64_t T, Profile &prof, double **final_X, int64_t *dense_steps);
+                      double d, int64_t T, Profile &prof, double **final_X, int64_t *dense_steps, SplitLast *split = nullptr);
+
+// rank.hip, the ranking inside the last step: the candidate capacity per slot (SEL_SLOTS - top_n, or less:
+// RWR_RANK_FUSED_CAP); after the head's select, the group's thresholds and cleared cursors (fills *sink); after the
+// selecting launch, the merge of the head's lists with the candidates
+int rank_fused_capacity(int32_t top_n);
+int32_t rank_fused_prepare(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, SelSink *sink, hipStream_t s);
+int32_t rank_fused_merge(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, const int32_t *d_seeds, int32_t top_n,
+                         const SelSink &sink, hipStream_t s);
 
 // recommend.hip: seeds per tile, the batch workspace (extra_mats: further [tile][n][G] matrices the caller needs per tile),
 // the seeds dealt to tile slots (d_seeds, d_slot_k, d_evoff)

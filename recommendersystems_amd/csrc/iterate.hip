@@ -115,7 +115,9 @@ __global__ __launch_bounds__(256) void k_spmm(int32_t n, const int64_t *__restri
 // entry, no weight stream, no multiplies; the epilogue writes the row's next z.
 // LIST: the launch walks a row list rather than every row -- the same code; a separate instantiation only so
 // that kernel traces and counter passes tell these launches from the dense ones
-template <int G, int CH, bool CHECK, bool WRITE, bool VF>
+// SEL: the selecting form of a ranking-only batch's last step (k_spmm_select): no Y, no z -- a lane of a real
+// slot whose sum reaches the slot's threshold appends (row, sum) to the slot's candidate buffer (one integer atomicAdd)
+template <int G, int CH, bool CHECK, bool WRITE, bool VF, bool SEL = false>
 __device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__restrict__ in_ptr,
                                                   const int32_t *__restrict__ in_src,
                                                   const double *__restrict__ in_w,
@@ -125,14 +127,16 @@ __device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__re
                                                   int skip_seed_row, const uint32_t *__restrict__ nz_in,
                                                   uint32_t *__restrict__ nz_out,
                                                   const uint32_t *__restrict__ act,
-                                                  const double *__restrict__ w_src, double *__restrict__ Zout)
+                                                  const double *__restrict__ w_src, double *__restrict__ Zout,
+                                                  const SelSink sink = SelSink{})
 {
     static_assert(G >= 8 && G <= 64, "chunked SpMM needs 8 <= G <= 64");
+    static_assert(!SEL || (!CHECK && !WRITE), "the selecting form probes and writes no bitmap");
     constexpr int RPW = WAVE / G;
     const int tile = blockIdx.y;
     const size_t toff = (size_t)tile * (size_t)n * G;
     X += toff;
-    Y += toff;
+    if (!SEL) Y += toff;
     if (VF && Zout) Zout += toff;
     const size_t nzw = ((size_t)n + 31) / 32;
     if (CHECK) nz_in += (size_t)tile * nzw;
@@ -142,6 +146,12 @@ __device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__re
     const int sub = lane / G, k = lane % G;
     const int gbase = (lane - k) << 2;      // byte address of the group's lane 0 for ds_bpermute
     const int32_t my_seed = skip_seed_row ? seeds[tile * G + k] : -1;
+    bool sel_real = false;
+    double sel_tau = 0.0;
+    if (SEL) {
+        sel_real = seeds[tile * G + k] >= 0;
+        sel_tau = sink.tau[tile * G + k];
+    }
     const int wpb = blockDim.x / WAVE;
     const int64_t nwaves = (int64_t)gridDim.x * wpb;
     for (int64_t rb = ((int64_t)blockIdx.x * wpb + threadIdx.x / WAVE) * RPW; rb < nrows; rb += nwaves * RPW) {
@@ -225,7 +235,14 @@ __device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__re
             }
             p += cnt;
         }
-        if (j >= 0 && j != my_seed) {
+        if constexpr (SEL) {
+            if (j >= 0 && j != my_seed && sel_real && acc >= sel_tau) {   // (ties at tau are kept)
+                const int slot = tile * G + k;
+                const int32_t at = atomicAdd(&sink.cursor[slot], 1);
+                if (at < sink.cap) sink.cand[(size_t)slot * (size_t)sink.stride + (size_t)at] = RowScore{j, 0, acc};
+                else *sink.overflow = 1;
+            }
+        } else if (j >= 0 && j != my_seed) {
             Y[(size_t)j * G + k] = acc;
             if (VF && Zout) { const double rw = c1 * acc; Zout[(size_t)j * G + k] = rw * w_src[j]; }
         }
@@ -251,6 +268,20 @@ __global__ __launch_bounds__(256) void k_spmm_chunked(int32_t n, const int64_t *
 {
     spmm_chunked_body<G, CH, CHECK, WRITE, VF>(n, in_ptr, in_src, in_w, row_order, nrows, X, Y, seeds, c1, skip_seed_row,
                                                nz_in, nz_out, act, w_src, Zout);
+}
+
+// The selecting part of a ranking-only batch's last step: the same body over the rest of tail_rows[0], which
+// writes no rank: the rows whose sum reaches the slot's threshold tau go to the slot's candidate buffer (SelSink)
+template <int G, int CH, bool VF>
+__global__ __launch_bounds__(256) void k_spmm_select(int32_t n, const int64_t *__restrict__ in_ptr,
+                                                     const int32_t *__restrict__ in_src,
+                                                     const double *__restrict__ in_w,
+                                                     const int32_t *__restrict__ rows, int32_t nrows,
+                                                     const double *__restrict__ X, const int32_t *__restrict__ seeds,
+                                                     double c1, const SelSink sink)
+{
+    spmm_chunked_body<G, CH, false, false, VF, true>(n, in_ptr, in_src, in_w, rows, nrows, X, nullptr, seeds, c1, 1, nullptr,
+                                                     nullptr, nullptr, nullptr, nullptr, sink);
 }
 
 // Frontier-list steps: the same body over a per-tile row list built by k_mark_active -- tile t walks the
@@ -777,12 +808,28 @@ static void launch_spmm_g(rwr_graph *g, int tg, const SpmmArgs &a, hipStream_t s
     }
     const bool listed = a.rows.kind == Rows::Tail;
     const int32_t *order = listed ? g->tail_rows[a.rows.level].p : g->row_order.p;
-    const int32_t nrows = listed ? g->tail_n[a.rows.level] : g->n;
+    int32_t nrows = listed ? g->tail_n[a.rows.level] : g->n;
+    if (listed) {   // a part of the level's list
+        const int32_t first = a.row_first < nrows ? a.row_first : nrows;
+        order += first;
+        nrows = (a.row_count >= 0 && a.row_count < nrows - first) ? a.row_count : nrows - first;
+    }
+    if (nrows <= 0 && (a.sel || a.row_count >= 0)) return;   // an empty part
     unsigned want = cdiv((size_t)nrows, (size_t)RPW * 4);
     unsigned gx = want < 1u ? 1u : want < 8192u ? want : 8192u;
     if constexpr (G == 1) {
         if (tg == 1 && plan_knobs().spmm != 0) {   // (every row: the callers pass no row list to this path)
             launch_spmv_exact(g, a.X, a.Y, a.seeds, a.c1, skip, a.act, a.nz_out, s, a.Zin, a.Zout, a.hub_scan);
+            return;
+        }
+    }
+    if constexpr (G >= 8) {
+        if (a.sel) {   // (split_last_ok: only with the chunked kernels)
+            const SelSink sink = *a.sel;
+            bool_dispatch([&](auto v) {
+                hipLaunchKernelGGL((k_spmm_select<G, CH, decltype(v)::value>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p,
+                                   g->in_src.p, g->in_w.p, order, nrows, GS, a.seeds, a.c1, sink);
+            }, vf);
             return;
         }
     }
@@ -936,7 +983,7 @@ int32_t GroupIter::init(bool fresh, bool ranks_nonneg, bool ranking_only)
     return RWR_OK;
 }
 
-int32_t GroupIter::step(const StepPlan &p, Profile &prof)
+int32_t GroupIter::step(const StepPlan &p, Profile &prof, int32_t row_first, int32_t row_count)
 {
     const int32_t n = g->n;
     hipStream_t s = g->stream;
@@ -980,6 +1027,7 @@ int32_t GroupIter::step(const StepPlan &p, Profile &prof)
     sp.X = X, sp.Y = Y, sp.seeds = d_seeds, sp.c1 = c1, sp.skip_seed_row = true;
     sp.nz_in = nz_in, sp.nz_out = nz_out, sp.act = act, sp.Zin = Zc, sp.Zout = zout;
     sp.hub_scan = cfg.addends_nonneg, sp.rows = p.rows;
+    sp.row_first = row_first, sp.row_count = row_count;
     launch_spmm(g, G, tg, sp, s);
     RWR_TRY(prof.end(prof.spmm, a, s));
     if (prof.on) prof.dense.push_back(p.dense());
@@ -997,9 +1045,26 @@ int32_t GroupIter::step(const StepPlan &p, Profile &prof)
     return RWR_OK;
 }
 
+int32_t GroupIter::redo_rows(const StepPlan &p, Profile &prof, int32_t row_first, int32_t row_count, const SelSink *sel)
+{
+    // step() has swapped the buffers: Y holds the ranks the step read and Zn their z; X is what it wrote
+    hipStream_t s = g->stream;
+    hipEvent_t a; RWR_TRY(prof.record(a, s));
+    SpmmArgs sp;
+    sp.X = Y, sp.Y = X, sp.seeds = d_seeds, sp.c1 = c1, sp.skip_seed_row = true;
+    sp.Zin = Zn, sp.Zout = nullptr;
+    sp.hub_scan = cfg.addends_nonneg, sp.rows = p.rows;
+    sp.row_first = row_first, sp.row_count = row_count, sp.sel = sel;
+    launch_spmm(g, G, tg, sp, s);
+    RWR_TRY(prof.end(prof.spmm, a, s));
+    if (prof.on) prof.dense.push_back(0);
+    RWR_HIP(hipGetLastError());
+    return RWR_OK;
+}
+
 // A tile group of the batched Recommendation: T steps of the plan (iterate.h)
 int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const int64_t *d_evoff, const int32_t *h_seeds,
-                      double d, int64_t T, Profile &prof, double **final_X, int64_t *dense_steps)
+                      double d, int64_t T, Profile &prof, double **final_X, int64_t *dense_steps, SplitLast *split)
 {
     GroupIter gi(g, G, tg, d_seeds, d_evoff, d);
     RWR_TRY(gi.init(true, true, true));
@@ -1009,7 +1074,20 @@ int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const
         for (size_t q = 0; q < (size_t)tg * G; ++q)
             if (h_seeds[q] >= 0) gi.cfg.need |= g->h_tail_flag[h_seeds[q]];
     }
-    while (gi.it < T) RWR_TRY(gi.step(plan_step(gi.cfg, gi.it, T), prof));
+    // the last step in two parts: a chainless, probe-free walk of tail level 0 by the chunked kernels only
+    bool split_ok = false;
+    if (split && split->head > 0 && T >= 1 && G >= 8 && plan_knobs().spmm != 0) {
+        const StepPlan last = plan_step(gi.cfg, T - 1, T);
+        split_ok = last.rows.kind == Rows::Tail && last.rows.level == 0 && !last.probe && !last.write_bits && !last.form_z &&
+                   last.chain == Chain::None;
+        split->last = last;
+    }
+    while (gi.it < T) {
+        const StepPlan p = plan_step(gi.cfg, gi.it, T);
+        if (split_ok && gi.it == T - 1) RWR_TRY(gi.step(p, prof, 0, split->head));
+        else RWR_TRY(gi.step(p, prof));
+    }
+    if (split_ok) { split->taken = true; split->gi.emplace(gi); }
     *final_X = gi.X;
     *dense_steps = gi.dense_steps;
     return RWR_OK;

@@ -6,7 +6,7 @@
 // DataLoader.cs:51-58, so List.Sort's instability cannot show).  Scores are mapped to
 // order-preserving 64-bit keys; non-candidates (excluded by k_exclude: score -1, or a
 // padding lane) get the largest key and sort to the end.
-#include "engine.h"
+#include "iterate.h"
 
 #include <cstring>
 
@@ -345,23 +345,12 @@ __global__ __launch_bounds__(256) void k_sel_collect(int32_t n, int32_t n_items,
     }
 }
 
-// one block per segment: bitonic sort (descending) of the collected candidates, emit the first top_n
-__global__ __launch_bounds__(256) void k_sel_sort_emit(const int32_t *__restrict__ slot_k, int32_t top_n,
-                                                       const SelState *__restrict__ st,
-                                                       const SelCand *__restrict__ cand, int64_t *__restrict__ out_id,
-                                                       double *__restrict__ out_score, int32_t *__restrict__ out_counts)
+// the workgroup's N2 (a power of two) entries of sc sorted descending by (hi, lo) (bitonic); the first min(cnt, top_n) go out
+// as row orow of the result tables.  Entries {0, 0} lie below every real key.  The caller has synchronised after filling sc
+__device__ __forceinline__ void sel_sort_emit(SelCand *sc, int N2, int cnt, int32_t orow, int32_t top_n,
+                                              int64_t *__restrict__ out_id, double *__restrict__ out_score,
+                                              int32_t *__restrict__ out_counts)
 {
-    extern __shared__ SelCand sc[];
-    const int seg = blockIdx.x;
-    const int32_t orow = slot_k[seg];            // batch position of this slot's seed
-    if (orow < 0) return;
-    int cnt = st[seg].cand_cnt;
-    if (cnt > SEL_SLOTS) cnt = SEL_SLOTS;
-    int N2 = 1;
-    while (N2 < cnt) N2 <<= 1;
-    const SelCand *c = cand + (size_t)seg * SEL_SLOTS;
-    for (int i = threadIdx.x; i < N2; i += blockDim.x) sc[i] = (i < cnt) ? c[i] : SelCand{0ull, 0ull};
-    __syncthreads();
     for (int size = 2; size <= N2; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
             for (int t = threadIdx.x; t < N2 / 2; t += blockDim.x) {
@@ -388,6 +377,112 @@ __global__ __launch_bounds__(256) void k_sel_sort_emit(const int32_t *__restrict
         __builtin_memcpy(&s, &u, 8);
         out_score[(size_t)orow * top_n + i] = s;
     }
+}
+
+// one block per segment: bitonic sort (descending) of the collected candidates, emit the first top_n
+__global__ __launch_bounds__(256) void k_sel_sort_emit(const int32_t *__restrict__ slot_k, int32_t top_n,
+                                                       const SelState *__restrict__ st,
+                                                       const SelCand *__restrict__ cand, int64_t *__restrict__ out_id,
+                                                       double *__restrict__ out_score, int32_t *__restrict__ out_counts)
+{
+    extern __shared__ SelCand sc[];
+    const int seg = blockIdx.x;
+    const int32_t orow = slot_k[seg];            // batch position of this slot's seed
+    if (orow < 0) return;
+    int cnt = st[seg].cand_cnt;
+    if (cnt > SEL_SLOTS) cnt = SEL_SLOTS;
+    int N2 = 1;
+    while (N2 < cnt) N2 <<= 1;
+    const SelCand *c = cand + (size_t)seg * SEL_SLOTS;
+    for (int i = threadIdx.x; i < N2; i += blockDim.x) sc[i] = (i < cnt) ? c[i] : SelCand{0ull, 0ull};
+    __syncthreads();
+    sel_sort_emit(sc, N2, cnt, orow, top_n, out_id, out_score, out_counts);
+}
+
+// ---------------------------------------------------------------------------------------
+// Ranking inside the last step.  The select above has ranked the head -- the first H rows of tail_rows[0] --
+// exactly: row orow of the result tables holds each seed's top_n of the head and its count.
+// k_sel_tau: the threshold the rest of the step selects by -- the score of the head's top_n-th entry, a lower bound of the
+// final top_n-th score, or 0 (every score qualifies) when the head gave fewer than top_n; and the cleared append cursor.
+// ---------------------------------------------------------------------------------------
+__global__ void k_sel_tau(int nseg, int32_t top_n, const int32_t *__restrict__ slot_k, const int32_t *__restrict__ out_counts,
+                          const double *__restrict__ out_score, double *__restrict__ tau, int32_t *__restrict__ cursor)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nseg) return;
+    const int32_t orow = slot_k[q];
+    double t = 0.0;
+    if (orow >= 0 && out_counts[orow] >= top_n) t = out_score[(size_t)orow * top_n + (top_n - 1)];
+    tau[q] = t;
+    cursor[q] = 0;
+}
+
+// k_sel_merge, one block per slot: the head's entries and the rows k_spmm_select appended -- less the seed's raw LIKE links,
+// read exactly as k_exclude reads them, in whatever order the list holds them -- sorted by (score desc, id desc); the first
+// top_n and the count go out.  The append order differs from run to run; the keys are unique, so the result does not.
+constexpr int MERGE_LIKES = 256;
+__global__ __launch_bounds__(256) void k_sel_merge(const int32_t *__restrict__ slot_k, const int32_t *__restrict__ seeds,
+                                                   int32_t top_n, const int32_t *__restrict__ cursor,
+                                                   const RowScore *__restrict__ body, int32_t cap, int32_t stride,
+                                                   const int64_t *__restrict__ rowptr, const int32_t *__restrict__ dst,
+                                                   const uint8_t *__restrict__ etype, const int64_t *__restrict__ node_id,
+                                                   int64_t *__restrict__ out_id, double *__restrict__ out_score,
+                                                   int32_t *__restrict__ out_counts)
+{
+    extern __shared__ SelCand sc[];
+    __shared__ int32_t likes[MERGE_LIKES];
+    __shared__ int n_excl;
+    const int seg = blockIdx.x, tid = threadIdx.x;
+    const int32_t orow = slot_k[seg];
+    const int32_t seed = seeds[seg];
+    if (orow < 0 || seed < 0) return;
+    int hc = out_counts[orow];
+    if (hc > top_n) hc = top_n;
+    int bc = cursor[seg];
+    if (bc > cap) bc = cap;
+    if (bc == 0) return;                         // nothing beyond the head: its list stands
+    const int total = hc + bc;                   // <= top_n + cap <= SEL_SLOTS
+    int N2 = 1;
+    while (N2 < total) N2 <<= 1;
+    if (tid == 0) n_excl = 0;
+    const RowScore *b = body + (size_t)seg * (size_t)stride;
+    for (int i = tid; i < N2; i += blockDim.x) {
+        SelCand c{0ull, 0ull};
+        if (i < hc) {
+            c.hi = f64_orderable(out_score[(size_t)orow * top_n + i]);
+            c.lo = i64_orderable(out_id[(size_t)orow * top_n + i]);
+        } else if (i < total) {
+            const RowScore r = b[i - hc];
+            c.hi = f64_orderable(r.score);       // (>= 2^63: scores are >= +0.0)
+            c.lo = (uint64_t)(uint32_t)r.row;    // the row, until the exclusion is through
+        }
+        sc[i] = c;
+    }
+    __syncthreads();
+    // Recommender.cs:20-24,29: the seed's raw LIKE links are no candidates
+    const int64_t p0 = rowptr[seed], p1 = rowptr[seed + 1];
+    for (int64_t pb = p0; pb < p1; pb += MERGE_LIKES) {
+        const int64_t p = pb + tid;
+        if (tid < MERGE_LIKES) likes[tid] = (p < p1 && etype[p] == RWR_EDGE_LIKE) ? dst[p] : -1;
+        __syncthreads();
+        const int nl = (p1 - pb < MERGE_LIKES) ? (int)(p1 - pb) : MERGE_LIKES;
+        for (int i = hc + tid; i < total; i += blockDim.x) {
+            const SelCand c = sc[i];
+            if (c.hi == 0ull) continue;          // excluded already (a link listed twice)
+            const int32_t row = (int32_t)c.lo;
+            bool hit = false;
+            for (int l = 0; l < nl; ++l) hit = hit || likes[l] == row;
+            if (hit) {
+                sc[i] = SelCand{0ull, 0ull};
+                atomicAdd(&n_excl, 1);
+            }
+        }
+        __syncthreads();
+    }
+    for (int i = hc + tid; i < total; i += blockDim.x)
+        if (sc[i].hi != 0ull) sc[i].lo = i64_orderable(node_id[(int32_t)sc[i].lo]);
+    __syncthreads();
+    sel_sort_emit(sc, N2, total - n_excl, orow, top_n, out_id, out_score, out_counts);
 }
 
 // Few items (an ego network: n_items <= SEL_SLOTS): the whole ranked list of a seed is one workgroup's bitonic sort in
@@ -538,10 +633,12 @@ int32_t rank_tile(rwr_graph *g, int G, const int32_t *d_slot_k_tile, int32_t top
 }
 
 // top-k for a whole tile group in one go (select path; top_n <= SEL_MAX_K)
+// rows / nrows: the rows to rank, in any order (nullptr: the ITEM rows, g->item_rows)
 int32_t rank_group_select(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, const double *X,
-                          const int32_t *d_seeds, hipStream_t s)
+                          const int32_t *d_seeds, hipStream_t s, const int32_t *rows, int32_t nrows)
 {
-    const int32_t m = g->n_items;
+    const int32_t m = rows ? nrows : g->n_items;
+    if (!rows) rows = g->item_rows.p;
     if (m == 0) return RWR_OK;
     const int nseg = tg * G;
     const size_t st_bytes = (size_t)nseg * sizeof(SelState);
@@ -565,22 +662,59 @@ int32_t rank_group_select(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, 
     constexpr int SEL_FUSED_LEVELS = 3;
     if (fused_env && nseg <= 64) {
         for (int level = 0; level < SEL_FUSED_LEVELS; ++level)
-            RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_sel_hist<GG>, dim3(nblk, tg), dim3(256), 0, s, g->n, m, g->item_rows.p,
+            RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_sel_hist<GG>, dim3(nblk, tg), dim3(256), 0, s, g->n, m, rows,
                                                  g->node_id.p, X, st, ghist, level, ticket));
-        RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_sel_tail<GG>, dim3(tg), dim3(256), 0, s, g->n, m, g->item_rows.p, g->node_id.p, X, st,
+        RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_sel_tail<GG>, dim3(tg), dim3(256), 0, s, g->n, m, rows, g->node_id.p, X, st,
                                              SEL_FUSED_LEVELS));
     } else {
         for (int level = 0; level < SEL_LEVELS; ++level) {
-            RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_sel_hist<GG>, dim3(nblk, tg), dim3(256), 0, s, g->n, m, g->item_rows.p,
+            RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_sel_hist<GG>, dim3(nblk, tg), dim3(256), 0, s, g->n, m, rows,
                                                  g->node_id.p, X, st, ghist, level, (unsigned int *)nullptr));
             hipLaunchKernelGGL(k_sel_decide, dim3(cdiv((size_t)nseg, 64)), dim3(64), 0, s, nseg, st, ghist, level);
         }
     }
-    RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_sel_collect<GG>, dim3(nblk, tg), dim3(256), 0, s, g->n, m, g->item_rows.p,
+    RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_sel_collect<GG>, dim3(nblk, tg), dim3(256), 0, s, g->n, m, rows,
                                          g->node_id.p, X, st, d_seeds, cand));
     (void)hipFuncSetAttribute((const void *)k_sel_sort_emit, hipFuncAttributeMaxDynamicSharedMemorySize,
                               SEL_SLOTS * (int)sizeof(SelCand));   // per launch: the attribute is per device
     hipLaunchKernelGGL(k_sel_sort_emit, dim3(nseg), dim3(256), SEL_SLOTS * sizeof(SelCand), s, d_slot_k, top_n, st, cand,
+                       g->d_out_id.p, g->d_out_score.p, g->d_counts.p);
+    RWR_HIP(hipGetLastError());
+    return RWR_OK;
+}
+
+// The second half of the ranking inside the last step; the workspace of a group's tau, cursors, overflow flag
+// and candidate buffers, the threshold after the head's select, the merge after the selecting launch
+int rank_fused_capacity(int32_t top_n)
+{
+    static const int env_cap = [] { const char *e = getenv("RWR_RANK_FUSED_CAP"); return e ? atoi(e) : 0; }();
+    const int cap = SEL_SLOTS - top_n;
+    return (env_cap > 0 && env_cap < cap) ? env_cap : cap;
+}
+int32_t rank_fused_prepare(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, SelSink *sink, hipStream_t s)
+{
+    const size_t nseg = (size_t)tg * G;
+    const int cap = rank_fused_capacity(top_n);
+    const size_t tau_bytes = nseg * sizeof(double), cur_bytes = ((nseg + 2) * sizeof(int32_t) + 15) & ~(size_t)15;
+    RWR_TRY(g->fused_ws.ensure(tau_bytes + cur_bytes + nseg * (size_t)cap * sizeof(RowScore) + 64));
+    sink->tau = (const double *)g->fused_ws.p;
+    sink->cursor = (int32_t *)(g->fused_ws.p + tau_bytes);
+    sink->overflow = sink->cursor + nseg;
+    sink->cand = (RowScore *)(g->fused_ws.p + tau_bytes + cur_bytes);
+    sink->cap = cap, sink->stride = cap;
+    RWR_HIP(hipMemsetAsync(sink->overflow, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_sel_tau, dim3(cdiv(nseg, 64)), dim3(64), 0, s, (int)nseg, top_n, d_slot_k, g->d_counts.p, g->d_out_score.p,
+                       (double *)g->fused_ws.p, sink->cursor);
+    RWR_HIP(hipGetLastError());
+    return RWR_OK;
+}
+int32_t rank_fused_merge(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, const int32_t *d_seeds, int32_t top_n,
+                         const SelSink &sink, hipStream_t s)
+{
+    (void)hipFuncSetAttribute((const void *)k_sel_merge, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              SEL_SLOTS * (int)sizeof(SelCand));
+    hipLaunchKernelGGL(k_sel_merge, dim3((unsigned)(tg * G)), dim3(256), SEL_SLOTS * sizeof(SelCand), s, d_slot_k, d_seeds, top_n,
+                       sink.cursor, sink.cand, sink.cap, sink.stride, g->rowptr.p, g->dst.p, g->etype.p, g->node_id.p,
                        g->d_out_id.p, g->d_out_score.p, g->d_counts.p);
     RWR_HIP(hipGetLastError());
     return RWR_OK;

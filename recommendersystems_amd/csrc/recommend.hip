@@ -205,6 +205,24 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
         RWR_HIP(hipMemcpy(g->d_slot_k.p, slot_k.data(), slot_k.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
 
+    // Ranking inside the last step: the step runs over the first H rows of tail_rows[0], the select ranks those,
+    // and the rest of the step keeps only the rows that reach each seed's threshold.  By default from RANK_FUSED_MIN_ITEMS ITEM
+    // rows on: below, the select's passes over the item block are cheaper than the second sort per seed and the
+    // synchronising copy per group that the split adds (C3, 62 K items: -0.4 %).  RWR_RANK_FUSED=0: off, =2: whatever the size;
+    // RWR_RANK_FUSED_HEAD: H (default: the power of two at or above a sixteenth of the ITEM rows)
+    constexpr int32_t RANK_FUSED_MIN_ITEMS = 1 << 18;
+    static const int force_sort = [] { const char *e = RWR_TUNE_ENV("RWR_RANK_SORT"); return e ? atoi(e) : 0; }();
+    static const int fused_env = [] { const char *e = getenv("RWR_RANK_FUSED"); return e ? atoi(e) : 1; }();
+    static const long head_env = [] { const char *e = getenv("RWR_RANK_FUSED_HEAD"); return e ? atol(e) : 0L; }();
+    const bool select_path = top_n <= rank_select_max_k() && !force_sort;
+    int32_t head_rows = 0;
+    if (fused_env && select_path && top_n >= 1 && g->n_items > 0 && (fused_env == 2 || g->n_items >= RANK_FUSED_MIN_ITEMS)) {
+        int64_t h = 1;
+        while (h * 16 < (int64_t)g->n_items) h <<= 1;
+        if (head_env > 0) h = head_env;
+        head_rows = (int32_t)(h < (int64_t)g->n_items ? h : (int64_t)g->n_items);
+    }
+
     Profile prof(g);
     for (int t0 = 0; t0 < ntiles; t0 += TG) {
         const int tg = (ntiles - t0 < TG) ? (ntiles - t0) : TG;
@@ -212,8 +230,10 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
         double *Xf = nullptr;
         hipEvent_t i0; RWR_TRY(prof.record(i0, s));
         int64_t dense_steps = 0;
+        SplitLast split;
+        split.head = head_rows;
         RWR_TRY(iterate_group(g, G, tg, dseeds, g->d_evoff.p + (size_t)t0 * G, slot_seed.data() + (size_t)t0 * G, d, n_iter,
-                              prof, &Xf, &dense_steps));
+                              prof, &Xf, &dense_steps, &split));
         RWR_TRY(prof.end(prof.iter, i0, s));
         int32_t real = 0;
         for (size_t q = (size_t)t0 * G; q < (size_t)(t0 + tg) * G; ++q) real += slot_k[q] >= 0;
@@ -222,9 +242,37 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
         hipEvent_t a; RWR_TRY(prof.record(a, s));
         launch_exclude(g, G, tg, Xf, dseeds, s);
         RWR_HIP(hipGetLastError());
-        static const int force_sort = [] { const char *e = RWR_TUNE_ENV("RWR_RANK_SORT"); return e ? atoi(e) : 0; }();
-        if (top_n <= rank_select_max_k() && !force_sort) {
-            RWR_TRY(rank_group_select(g, G, tg, g->d_slot_k.p + (size_t)t0 * G, top_n, Xf, dseeds, s));
+        const int32_t *slot_k_g = g->d_slot_k.p + (size_t)t0 * G;
+        bool ranked = false;
+        if (split.taken) {
+            // the head (in-degree-descending: tail_rows[0] is a stable partition of row_order) is ranked exactly; its top_n-th
+            // score bounds the final one from below, and the rest of the step selects by it while it computes
+            const int32_t n_tail = g->tail_n[0];
+            const int32_t H = head_rows < n_tail ? head_rows : n_tail;
+            RWR_TRY(rank_group_select(g, G, tg, slot_k_g, top_n, Xf, dseeds, s, g->tail_rows[0].p, H));
+            ranked = true;
+            if (H < n_tail) {
+                SelSink sink;
+                RWR_TRY(rank_fused_prepare(g, G, tg, slot_k_g, top_n, &sink, s));
+                RWR_TRY(split.gi->redo_rows(split.last, prof, H, n_tail - H, &sink));
+                RWR_TRY(rank_fused_merge(g, G, tg, slot_k_g, dseeds, top_n, sink, s));
+                int32_t overflow = 0;   // (one small synchronising copy per group)
+                RWR_HIP(hipMemcpyAsync(&overflow, sink.overflow, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                RWR_HIP(hipStreamSynchronize(s));
+                if (overflow) {
+                    // some seed's candidates did not fit: the step again, whole (its inputs are intact), ranked as without the split
+                    RWR_TRY(split.gi->redo_rows(split.last, prof, 0, -1, nullptr));
+                    launch_exclude(g, G, tg, Xf, dseeds, s);
+                    RWR_HIP(hipGetLastError());
+                    g->stats.rank_fused_fallbacks += 1;
+                    ranked = false;
+                }
+            }
+            g->stats.rank_fused_groups += ranked;
+        }
+        if (ranked) {
+        } else if (select_path) {
+            RWR_TRY(rank_group_select(g, G, tg, slot_k_g, top_n, Xf, dseeds, s));
         } else {
             for (int t = 0; t < tg; ++t) {
                 RWR_TRY(rank_tile(g, G, g->d_slot_k.p + (size_t)(t0 + t) * G, top_n, Xf + (size_t)t * (size_t)n * G,
