@@ -126,6 +126,10 @@ typedef struct rwr_stats {
                                        step's second part kept only the rows that reach the seeds' thresholds */
     int64_t rank_fused_fallbacks;   /* ... groups that tried and ran the step whole after all: a seed's candidates
                                        did not fit its buffer */
+    int64_t rank_pruned_rows;       /* ... (row, tile) pairs the second part skipped without gathering a rank row: the sum of
+                                       a float bound over the row's in-list showed that no seed of the tile reaches its
+                                       threshold there (groups that fell back count nothing); RWR_RANK_PRUNE=0: none */
+    double  rank_bound_ms;          /* time of the bound tables and the rows' keep bits (part of rank_ms; profile only) */
 } rwr_stats;
 
 /* ---- library ------------------------------------------------------------------------- */

@@ -1060,6 +1060,8 @@ int32_t rwr_reset_stats(rwr_graph *g)
     s.spmm_dense_launches = s.spmm_dense_seed_steps = 0;
     s.frontier_list_launches = 0;
     s.rank_fused_groups = s.rank_fused_fallbacks = 0;
+    s.rank_pruned_rows = 0;
+    s.rank_bound_ms = 0;
     return RWR_OK;
 }
 

@@ -1092,6 +1092,7 @@ int32_t ensure_in_w(rwr_graph *g)
 int32_t tail_rows_prepare(rwr_graph *g)
 {
     if (g->tail_state == 1) return RWR_OK;
+    g->bound_first = -1;
     static const int depth_env = [] {
         const char *e = getenv("RWR_TAIL_DEPTH");
         const int v = e ? atoi(e) : rwr_graph::TAIL_MAX;

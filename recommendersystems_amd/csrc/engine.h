@@ -126,6 +126,9 @@ struct rwr_graph {
     rwr::DevBuf<uint32_t> vals, vals_alt;
     rwr::DevBuf<uint8_t> sort_temp;
     rwr::DevBuf<uint8_t> fused_ws;    // ranking inside the last step: per slot tau, append cursor, candidates
+    rwr::DevBuf<uint8_t> bound_ws;    // ... pruning its body: the tiles' bound tables, the rows' keep bits, flags and counters
+    int32_t bound_first = -1, bound_lo = 0, bound_hi = 0;   // source rows [lo, hi) of the in-links of tail_rows[0] from bound_first
+                                                            // on (-1: not known; reset whenever the tail rows are rebuilt)
     rwr::DevBuf<int64_t> d_out_id;
     rwr::DevBuf<double> d_out_score;
     rwr::DevBuf<int32_t> d_counts;

@@ -26,6 +26,9 @@ struct SelSink {
     RowScore *cand = nullptr;
     int32_t cap = 0, stride = 0;
     int32_t *overflow = nullptr;
+    // pruned body (rank_bound_prepare): tile t walks the list_cnt[t] rows at list + t * list_stride instead of the launch's rows
+    const int32_t *list = nullptr, *list_cnt = nullptr;
+    int64_t list_stride = 0;
 };
 
 struct SpmmArgs {
@@ -59,14 +62,14 @@ void launch_mark_active(rwr_graph *g, int G, int tg, const uint32_t *nz, uint32_
 // folds into rwr_stats and recycles after a synchronisation.  With profiling off every method does nothing.
 struct Profile {
     const bool on;
-    std::vector<hipEvent_t> pool, spmm, chain, rank, iter;   // the pool; pairs of the SpMM, chain, ranking, iteration stages
+    std::vector<hipEvent_t> pool, spmm, chain, rank, iter, bound;   // the pool; pairs of the SpMM, chain, ranking, iteration, body-bound stages
     size_t used = 0;                                          // (pool[0 .. used) are in flight)
     std::vector<uint8_t> dense;                               // per SpMM pair: 1 = a dense launch
     explicit Profile(const rwr_graph *g) : on(g->opts.profile != 0) {}
     ~Profile() { for (auto e : pool) (void)hipEventDestroy(e); }
     int32_t record(hipEvent_t &e, hipStream_t s);             // an event of the pool recorded on s: the begin of a pair
     int32_t end(std::vector<hipEvent_t> &stage, hipEvent_t a, hipStream_t s);   // the end of the pair that `a` began
-    void reset() { spmm.clear(); chain.clear(); rank.clear(); iter.clear(); dense.clear(); used = 0; }
+    void reset() { spmm.clear(); chain.clear(); rank.clear(); iter.clear(); bound.clear(); dense.clear(); used = 0; }
     int32_t fold(rwr_graph *g);
 };
 
@@ -121,6 +124,12 @@ int rank_fused_capacity(int32_t top_n);
 int32_t rank_fused_prepare(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, SelSink *sink, hipStream_t s);
 int32_t rank_fused_merge(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, const int32_t *d_seeds, int32_t top_n,
                          const SelSink &sink, hipStream_t s);
+// Pruning the body (rank_bound.h), after rank_fused_prepare and before the selecting launch over the `count` rows
+// of tail_rows[0] from `first` on: per tile the bound table of the source rows (Z: the z matrix the step gathers) and each
+// rows' keep bits, compacted into the tiles' row lists (sink->list); *pruned (device) receives the (row, tile) pairs the launch
+// will skip.  Leaves sink->list null when pruning is off (RWR_RANK_PRUNE=0) or its workspace cannot be had.
+int32_t rank_bound_prepare(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const double *Z, int32_t first, int32_t count,
+                           SelSink *sink, unsigned long long **pruned, hipStream_t s);
 
 // recommend.hip: seeds per tile, the batch workspace (extra_mats: further [tile][n][G] matrices the caller needs per tile),
 // the seeds dealt to tile slots (d_seeds, d_slot_k, d_evoff)

@@ -280,6 +280,11 @@ __global__ __launch_bounds__(256) void k_spmm_select(int32_t n, const int64_t *_
                                                      const double *__restrict__ X, const int32_t *__restrict__ seeds,
                                                      double c1, const SelSink sink)
 {
+    // pruned body (rank_bound_prepare): the tile walks its own list of the rows it may still need; its length lives on the device
+    if (sink.list) {
+        rows = sink.list + (size_t)blockIdx.y * (size_t)sink.list_stride;
+        nrows = sink.list_cnt[blockIdx.y];
+    }
     spmm_chunked_body<G, CH, false, false, VF, true>(n, in_ptr, in_src, in_w, rows, nrows, X, nullptr, seeds, c1, 1, nullptr,
                                                      nullptr, nullptr, nullptr, nullptr, sink);
 }
@@ -946,6 +951,7 @@ int32_t Profile::fold(rwr_graph *g)
         RWR_TRY(drain(chain, &g->stats.chain_ms, false));
         RWR_TRY(drain(rank, &g->stats.rank_ms, false));
         RWR_TRY(drain(iter, &g->stats.iterate_wall_ms, false));
+        RWR_TRY(drain(bound, &g->stats.rank_bound_ms, false));
     }
     reset();
     return RWR_OK;

@@ -254,11 +254,19 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
             if (H < n_tail) {
                 SelSink sink;
                 RWR_TRY(rank_fused_prepare(g, G, tg, slot_k_g, top_n, &sink, s));
+                // value-free path: the thresholds bound every body row's scores from one float per in-link, and the
+                // selecting launch walks only the rows some seed of the tile may still need (rank_bound.h)
+                unsigned long long *d_pruned = nullptr, pruned = 0;
+                hipEvent_t b0; RWR_TRY(prof.record(b0, s));
+                RWR_TRY(rank_bound_prepare(g, G, tg, dseeds, split.gi->Zn, H, n_tail - H, &sink, &d_pruned, s));
+                RWR_TRY(prof.end(prof.bound, b0, s));
                 RWR_TRY(split.gi->redo_rows(split.last, prof, H, n_tail - H, &sink));
                 RWR_TRY(rank_fused_merge(g, G, tg, slot_k_g, dseeds, top_n, sink, s));
                 int32_t overflow = 0;   // (one small synchronising copy per group)
                 RWR_HIP(hipMemcpyAsync(&overflow, sink.overflow, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                if (d_pruned) RWR_HIP(hipMemcpyAsync(&pruned, d_pruned, sizeof pruned, hipMemcpyDeviceToHost, s));
                 RWR_HIP(hipStreamSynchronize(s));
+                if (!overflow) g->stats.rank_pruned_rows += (int64_t)pruned;
                 if (overflow) {
                     // some seed's candidates did not fit: the step again, whole (its inputs are intact), ranked as without the split
                     RWR_TRY(split.gi->redo_rows(split.last, prof, 0, -1, nullptr));
