@@ -822,16 +822,21 @@ int32_t rwr_model_deliver(rwr_graph *g, int32_t seed, double d, const double *ra
     return model_deliver(g, seed, d, rank, next_rank);
 }
 
+// the run modes of Model.run (rwr.h); `who` names the entry in the message
+static int32_t check_run_mode(const char *who, int32_t run_mode)
+{
+    if (run_mode == RWR_RUN_ITERATIONS || run_mode == RWR_RUN_THRESHOLD || run_mode == RWR_RUN_DEFAULT_THRESHOLD) return RWR_OK;
+    set_error("%s: unknown run_mode %d", who, run_mode);
+    return RWR_E_INVALID;
+}
+
 int32_t rwr_model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double value, double *rank_out,
                       int64_t *iters_out)
 {
     g_err[0] = 0;
     if (!g || !rank_out) { set_error("rwr_model_run: NULL argument"); return RWR_E_INVALID; }
     RWR_BIND(g);
-    if (run_mode != RWR_RUN_ITERATIONS && run_mode != RWR_RUN_THRESHOLD && run_mode != RWR_RUN_DEFAULT_THRESHOLD) {
-        set_error("rwr_model_run: unknown run_mode %d", run_mode);
-        return RWR_E_INVALID;
-    }
+    RWR_TRY(check_run_mode("rwr_model_run", run_mode));
     RWR_TRY(model_run(g, seed, d, run_mode, value, rank_out, iters_out));
     return RWR_OK;
 }
@@ -844,10 +849,7 @@ int32_t rwr_model_run_batch(rwr_graph *g, const int32_t *seeds, int32_t K, doubl
         set_error("rwr_model_run_batch: NULL argument or negative K");
         return RWR_E_INVALID;
     }
-    if (run_mode != RWR_RUN_ITERATIONS && run_mode != RWR_RUN_THRESHOLD && run_mode != RWR_RUN_DEFAULT_THRESHOLD) {
-        set_error("rwr_model_run_batch: unknown run_mode %d", run_mode);
-        return RWR_E_INVALID;
-    }
+    RWR_TRY(check_run_mode("rwr_model_run_batch", run_mode));
     for (int32_t k = 0; k < K; ++k)
         if (seeds[k] < 0 || seeds[k] >= g->n) {   // (-1, the global model, stays on rwr_model_run)
             set_error("rwr_model_run_batch: seed %d (batch position %d) is outside [0, %d)", seeds[k], k, g->n);
@@ -863,10 +865,7 @@ int32_t rwr_model_run_restart(rwr_graph *g, const double *restart, const double 
 {
     g_err[0] = 0;
     if (!g || !restart || !rank_in || !rank_out) { set_error("rwr_model_run_restart: NULL argument"); return RWR_E_INVALID; }
-    if (run_mode != RWR_RUN_ITERATIONS && run_mode != RWR_RUN_THRESHOLD && run_mode != RWR_RUN_DEFAULT_THRESHOLD) {
-        set_error("rwr_model_run_restart: unknown run_mode %d", run_mode);
-        return RWR_E_INVALID;
-    }
+    RWR_TRY(check_run_mode("rwr_model_run_restart", run_mode));
     RWR_BIND(g);
     return model_run_restart(g, restart, rank_in, d, run_mode, value, rank_out, iters_out);
 }
@@ -926,10 +925,7 @@ int32_t rwr_model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_
     if (K < 0) { set_error("%s: negative K", who); return RWR_E_INVALID; }
     if (K == 0) return RWR_OK;
     if (!sup_ptr || !rank_out) { set_error("%s: NULL sup_ptr or rank_out", who); return RWR_E_INVALID; }
-    if (run_mode != RWR_RUN_ITERATIONS && run_mode != RWR_RUN_THRESHOLD && run_mode != RWR_RUN_DEFAULT_THRESHOLD) {
-        set_error("%s: unknown run_mode %d", who, run_mode);
-        return RWR_E_INVALID;
-    }
+    RWR_TRY(check_run_mode(who, run_mode));
     RWR_TRY(check_restart_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start));
     RWR_BIND(g);
     return model_run_restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out);

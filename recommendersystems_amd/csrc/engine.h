@@ -259,7 +259,7 @@ void launch_restart_fold_cols(rwr_graph *g, int G, int32_t npairs, const int32_t
 void launch_restart_scatter_cols(rwr_graph *g, int G, int32_t npairs, const int32_t *pq, const int32_t *pr, const double *fold,
                                  double *Y, hipStream_t s);
 void launch_restart_init_cols(rwr_graph *g, int G, int tg, const int32_t *st, double *X, hipStream_t s);
-// model.hip pieces restart.hip runs as well.  A run's end condition (Model.run(int) / run(double) / run(), Model.cs:52-66):
+// model.hip pieces restart.hip runs as well (the loops around them: run_walk and GroupColumns, iterate.h).  A run's end condition (Model.run(int) / run(double) / run(), Model.cs:52-66):
 // T steps at most; !by_count: until checkConvergence's distance is < threshold, a failure after max_iters = RWR_MAX_ITERS steps
 struct RunEnd {
     bool by_count;
@@ -275,10 +275,6 @@ inline double *model_scalar(rwr_graph *g) { return g->d_part.p + MODEL_RED_PARTS
 void launch_restart_mass(rwr_graph *g, const double *X, double c1, double *total, hipStream_t s);
 void launch_l1(rwr_graph *g, const double *a, const double *b, int32_t n, double *total, hipStream_t s);
 void launch_absdiff(const double *a, const double *b, int32_t n, double *out, hipStream_t s);
-// ... per element of a tile group's [tile][n][G] matrices; the columns of X[tile][n][G] whose slot has row_of[slot] = j >= 0
-// into the row-major staging rows out[j * n ...] (the batches of Models: model.hip, restart_batch.hip)
-void launch_absdiff_mat(const double *a, const double *b, size_t elems, double *out, hipStream_t s);
-void launch_extract_cols(rwr_graph *g, int G, int tg, const double *X, const int32_t *row_of, double *out, hipStream_t s);
 // checkConvergence (Model.cs:110-115) of two rank vectors on g->stream, read back (one synchronisation): the reference's
 // sequential sum bit for bit (binade scan), or the tree sum (tolerance parity: global model, wide restart vectors)
 int32_t converge_exact(rwr_graph *g, const double *a, const double *b, double *dist);

@@ -1,9 +1,11 @@
-// What the API drivers (recommend.hip, model.hip, partition.hip, restart.hip) need from iterate.hip (internal): the
-// launchers of the step's kernels, the profile events of a call and one tile group's power iteration.
+// What the API drivers (recommend.hip, model.hip, partition.hip, restart.hip) need from iterate.hip (internal): the launchers of
+// the step's kernels, the profile events of a call, one tile group's power iteration; the run-loop pieces the Model drivers share.
 #pragma once
+#include "column_ends.h"
 #include "engine.h"
 #include "step_plan.h"
 
+#include <new>
 #include <optional>
 
 namespace rwr {
@@ -137,5 +139,71 @@ int resolve_G(const rwr_graph *g, int32_t K);
 int32_t ensure_workspace(rwr_graph *g, int G, int32_t K, int *TG_out, int extra_mats = 0);
 int32_t upload_seed_slots(rwr_graph *g, const int32_t *seeds, int32_t K, int G, std::vector<int32_t> *slot_k_out,
                           std::vector<int32_t> *slot_seed_out = nullptr);
+
+// ---- the run loop of the Model drivers (model.hip, restart.hip, restart_batch.hip) ----------------------------------------
+// scratch buffers of one call are released only after both streams are idle (also on error paths): declared after them
+struct StreamsIdle {
+    rwr_graph *g;
+    ~StreamsIdle() { (void)hipStreamSynchronize(g->stream); (void)hipStreamSynchronize(g->stream2); }
+};
+
+// no C++ exception crosses the C boundary
+template <class F>
+int32_t no_throw(const char *who, F &&body)
+{
+    try { return body(); }
+    catch (const std::bad_alloc &) { set_error("%s: host allocation failed", who); return RWR_E_NOMEM; }
+    catch (...) { set_error("%s: unexpected host exception", who); return RWR_E_HIP; }
+}
+
+// Model.run of one walk (Model.cs:52-66): step() = deliverRanks + updateRanks, converge(&dist) = checkConvergence read
+// back.  *done receives the steps made; a threshold run that is not below its threshold after end.T steps fails.
+template <class Step, class Converge>
+int32_t run_walk(const char *who, const RunEnd &end, int64_t *done, Step &&step, Converge &&converge)
+{
+    for (*done = 0; *done < end.T;) {
+        RWR_TRY(step());
+        ++*done;
+        if (end.by_count) continue;
+        double dist = 0;
+        RWR_TRY(converge(&dist));
+        if (dist < end.threshold) return RWR_OK;                     // Model.cs:64
+    }
+    if (end.by_count) return RWR_OK;
+    set_error("%s: no convergence within %lld iterations (RWR_MAX_ITERS)", who, (long long)end.max_iters);
+    return RWR_E_UNSUPPORTED;
+}
+
+// The device half of ColumnEnds (column_ends.h) for one tile group of K Models, on g->stream (model.hip).  The caller has
+// sized g->mb_row and g->cs_sums to the group's slots and g->cs_diff to one [tile][n][G] matrix.
+struct GroupColumns {
+    rwr_graph *g;
+    int G, tg;
+    const int64_t *evoff;        // the group's d_evoff slots (chain_scan_sum_cols)
+    double *rank_out;            // the call's K x n result: column k leaves as row k
+    int64_t *iters_out;
+    Profile &prof;
+    ColumnEnds ends;
+    std::vector<int32_t> row_of;
+    std::vector<double> dist;    // threshold modes: the slots' distances of the last step
+    GroupColumns(rwr_graph *g_, int G_, int tg_, const int32_t *slot_k, const int64_t *evoff_, const RunEnd &end, double *rank_out_,
+                 int64_t *iters_out_, Profile &prof_)
+        : g(g_), G(G_), tg(tg_), evoff(evoff_), rank_out(rank_out_), iters_out(iters_out_), prof(prof_),
+          ends(slot_k, (size_t)tg_ * G_, end.by_count, end.T, end.threshold), row_of(ends.nslots), dist(ends.nslots) {}
+    // The columns of X whose run ends after `steps` steps (ends.due(steps)) go to their caller rows: k_extract_cols into
+    // cs_diff (booked as ranking time), one D2H per row, one synchronisation.  Nothing when no column leaves.
+    int32_t emit(int64_t steps, const double *X);
+    // checkConvergence of every column after a step (Model.cs:110-115): |Y - X| and its exact column sums close the iter
+    // bracket that i0 began, then dist comes back with one synchronisation
+    int32_t measure(hipEvent_t i0, const double *Y, const double *X);
+    // the group is through after `steps` steps, dense_steps of them SpMMs over every row: its real columns' statistics
+    void count(int64_t steps, int64_t dense_steps) const
+    {
+        g->stats.spmm_seed_steps += (int64_t)ends.real * steps;
+        g->stats.spmm_dense_seed_steps += (int64_t)ends.real * dense_steps;
+    }
+};
+// The end of a batch call: both streams idle, the profile folded, the tile shape and the wall time since t_begin booked
+int32_t finish_model_batch(rwr_graph *g, Profile &prof, int G, int TG, double t_begin);
 
 }  // namespace rwr

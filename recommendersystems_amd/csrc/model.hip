@@ -1,11 +1,10 @@
 // Model.run / deliverRanks / checkConvergence (Model.cs:52-115) for one personalised or the global Model and for K
-// personalised Models in one call, driven over GroupIter (iterate.h); the reductions and the run-loop pieces that
-// restart.hip (caller-set restart vectors) shares.
+// personalised Models in one call, driven over GroupIter (iterate.h); the reductions that restart.hip (caller-set restart
+// vectors) shares and GroupColumns, the column ends of a tile group of Models, which restart_batch.hip drives as well.
 #include "iterate.h"
 
 #include <algorithm>
 #include <cstdlib>
-#include <new>
 
 namespace rwr {
 
@@ -159,23 +158,19 @@ int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double
     const RunEnd end(run_mode, value, n);
     RWR_TRY(g->d_part.ensure(RED_GRID + 8));
     int64_t done = 0;
-    bool converged = false;
     double *Xf = nullptr;
 
     if (seed >= 0) {
         RWR_TRY(upload_seed_slots(g, &seed, 1, 1, nullptr));
         GroupIter gi(g, G, 1, g->d_seeds.p, g->d_evoff.p, d);
         RWR_TRY(gi.init());
-        while (done < end.T) {
-            RWR_TRY(gi.step(plan_step(gi.cfg, gi.it, -1), prof));           // deliverRanks + updateRanks
-            ++done;
-            if (!end.by_count) {                                            // checkConvergence (Model.cs:58-65)
-                double diff = 0;
-                RWR_TRY(converge_exact(g, gi.Y, gi.X, &diff));
-                if (diff < end.threshold) { converged = true; break; }
-                prof.reset();                                               // (synchronised above: safe to recycle)
-            }
-        }
+        const auto step = [&] { return gi.step(plan_step(gi.cfg, gi.it, -1), prof); };   // deliverRanks + updateRanks
+        const auto converge = [&](double *dist) -> int32_t {                             // checkConvergence (Model.cs:58-65)
+            RWR_TRY(converge_exact(g, gi.Y, gi.X, dist));
+            prof.reset();                                                                // (synchronised above: safe to recycle)
+            return RWR_OK;
+        };
+        RWR_TRY(run_walk("rwr_model_run", end, &done, step, converge));
         Xf = gi.X;
     } else {
         RWR_TRY(ensure_in_w(g));   // (the global model runs the weighted kernels)
@@ -183,21 +178,13 @@ int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double
         hipLaunchKernelGGL(k_fill, dim3(cdiv((size_t)n, 256)), dim3(256), 0, s, X, n, 1.0);   // rank = 1 (Model.cs:14-31)
         int32_t no_seed = -1;
         RWR_HIP(hipMemcpyAsync(g->d_seeds.p, &no_seed, sizeof(int32_t), hipMemcpyHostToDevice, s));
-        while (done < end.T) {
+        const auto step = [&]() -> int32_t {
             RWR_TRY(global_model_step(g, X, Y, 1 - d, s));
-            { double *t = X; X = Y; Y = t; }
-            ++done;
-            if (!end.by_count) {
-                double diff = 0;
-                RWR_TRY(converge_tree(g, Y, X, &diff));
-                if (diff < end.threshold) { converged = true; break; }
-            }
-        }
+            std::swap(X, Y);
+            return RWR_OK;
+        };
+        RWR_TRY(run_walk("rwr_model_run", end, &done, step, [&](double *dist) { return converge_tree(g, Y, X, dist); }));
         Xf = X;
-    }
-    if (!end.by_count && !converged) {
-        set_error("rwr_model_run: no convergence within %lld iterations (RWR_MAX_ITERS)", (long long)end.max_iters);
-        return RWR_E_UNSUPPORTED;
     }
     RWR_HIP(hipMemcpyAsync(rank_out, Xf, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     RWR_HIP(hipStreamSynchronize(s));
@@ -287,14 +274,55 @@ __global__ __launch_bounds__(256) void k_extract_cols(int32_t n, const double *_
     }
 }
 
-void launch_absdiff_mat(const double *a, const double *b, size_t elems, double *out, hipStream_t s)
+static void launch_absdiff_mat(const double *a, const double *b, size_t elems, double *out, hipStream_t s)
 {
     hipLaunchKernelGGL(k_absdiff_mat, dim3(std::min<size_t>(cdiv(elems, 256), 16384)), dim3(256), 0, s, a, b, (int64_t)elems, out);
 }
-void launch_extract_cols(rwr_graph *g, int G, int tg, const double *X, const int32_t *row_of, double *out, hipStream_t s)
+static void launch_extract_cols(rwr_graph *g, int G, int tg, const double *X, const int32_t *row_of, double *out, hipStream_t s)
 {
     RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_extract_cols<GG>, dim3(cdiv((size_t)g->n, EX_ELEMS / GG), (unsigned)tg), dim3(256), 0, s,
                                          g->n, X, row_of, out));
+}
+
+int32_t GroupColumns::emit(int64_t steps, const double *X)
+{
+    const size_t n = (size_t)g->n;
+    hipStream_t s = g->stream;
+    if (ends.leaving(steps, dist.data(), row_of.data(), iters_out) == 0) return RWR_OK;
+    RWR_HIP(hipMemcpyAsync(g->mb_row.p, row_of.data(), ends.nslots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    hipEvent_t a; RWR_TRY(prof.record(a, s));
+    launch_extract_cols(g, G, tg, X, g->mb_row.p, g->cs_diff.p, s);
+    RWR_HIP(hipGetLastError());
+    RWR_TRY(prof.end(prof.rank, a, s));
+    for (size_t q = 0; q < ends.nslots; ++q)
+        if (row_of[q] >= 0)
+            RWR_HIP(hipMemcpyAsync(rank_out + (size_t)ends.slot_k[q] * n, g->cs_diff.p + (size_t)row_of[q] * n, sizeof(double) * n,
+                                   hipMemcpyDeviceToHost, s));
+    RWR_HIP(hipStreamSynchronize(s));
+    return prof.fold(g);
+}
+
+int32_t GroupColumns::measure(hipEvent_t i0, const double *Y, const double *X)
+{
+    hipStream_t s = g->stream;
+    launch_absdiff_mat(Y, X, ends.nslots * (size_t)g->n, g->cs_diff.p, s);
+    RWR_TRY(chain_scan_sum_cols(g, G, tg, g->cs_diff.p, evoff, g->cs_sums.p, s));
+    RWR_TRY(prof.end(prof.iter, i0, s));
+    RWR_HIP(hipMemcpyAsync(dist.data(), g->cs_sums.p, ends.nslots * sizeof(double), hipMemcpyDeviceToHost, s));
+    RWR_HIP(hipStreamSynchronize(s));
+    return prof.fold(g);
+}
+
+int32_t finish_model_batch(rwr_graph *g, Profile &prof, int G, int TG, double t_begin)
+{
+    RWR_HIP(hipStreamSynchronize(g->stream));
+    RWR_HIP(hipStreamSynchronize(g->stream2));
+    RWR_TRY(prof.fold(g));
+    if (prof.on) RWR_TRY(chain_scan_collect(g, g->stream));
+    g->stats.tile_seeds = G;
+    g->stats.tile_group = TG;
+    g->stats.total_wall_ms += now_ms() - t_begin;
+    return RWR_OK;
 }
 
 // Tile group by tile group: GroupIter (no frontier-list steps, no row lists: every step writes every row of X), then each
@@ -315,8 +343,6 @@ static int32_t model_run_batch_body(rwr_graph *g, const int32_t *seeds, int32_t 
         return RWR_OK;
     }
     const RunEnd end(run_mode, value, n);
-    const bool by_count = end.by_count;
-    const int64_t T = end.T;
     const int G = resolve_G(g, K);
     int TG = 1;
     RWR_TRY(ensure_workspace(g, G, K, &TG, 1));             // + cs_diff: differences, then staging of the extracted columns
@@ -326,96 +352,40 @@ static int32_t model_run_batch_body(rwr_graph *g, const int32_t *seeds, int32_t 
     RWR_TRY(g->cs_sums.ensure((size_t)TG * G));
     RWR_TRY(g->mb_row.ensure((size_t)TG * G));
     hipStream_t s = g->stream;
+    StreamsIdle idle{g};                                     // (also when a step fails or RWR_MAX_ITERS runs out)
     Profile prof(g);                                         // (column extraction counts as ranking time)
-    std::vector<int32_t> row_of;
-    std::vector<double> dist;
     for (int t0 = 0; t0 < ntiles; t0 += TG) {
         const int tg = (ntiles - t0 < TG) ? (ntiles - t0) : TG;
-        const size_t q0 = (size_t)t0 * G, nslots = (size_t)tg * G;
-        const int64_t *evoff = g->d_evoff.p + q0;
-        const size_t elems = nslots * (size_t)n;
-        int32_t live = 0;                                    // real slots whose column is not out yet
-        for (size_t q = 0; q < nslots; ++q) live += slot_k[q0 + q] >= 0;
-        const int32_t real = live;
-        std::vector<uint8_t> out_done(nslots, 0);
-        GroupIter gi(g, G, tg, g->d_seeds.p + q0, evoff, d);
+        const size_t q0 = (size_t)t0 * G;
+        GroupColumns cols(g, G, tg, slot_k.data() + q0, g->d_evoff.p + q0, end, rank_out, iters_out, prof);
+        GroupIter gi(g, G, tg, g->d_seeds.p + q0, cols.evoff, d);
         RWR_TRY(gi.init(true, true, /*ranking_only=*/false));
-        if (!by_count) RWR_TRY(chain_scan_sum_cols_prepare(g, G, tg, s));
+        if (!end.by_count) RWR_TRY(chain_scan_sum_cols_prepare(g, G, tg, s));
         int64_t steps = 0;
         for (;;) {
-            if (by_count ? steps == T : steps > 0) {
-                // the columns whose run ends here: every one after step T, the converged ones in threshold mode
-                row_of.assign(nslots, -1);
-                int32_t m = 0;
-                for (size_t q = 0; q < nslots; ++q) {
-                    const int32_t k = slot_k[q0 + q];
-                    if (k < 0 || out_done[q] || !(by_count || dist[q] < end.threshold)) continue;   // Model.cs:64
-                    row_of[q] = m++;
-                    out_done[q] = 1;
-                    if (iters_out) iters_out[k] = steps;
-                }
-                if (m > 0) {
-                    RWR_HIP(hipMemcpyAsync(g->mb_row.p, row_of.data(), nslots * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                    hipEvent_t a; RWR_TRY(prof.record(a, s));
-                    launch_extract_cols(g, G, tg, gi.X, g->mb_row.p, g->cs_diff.p, s);
-                    RWR_HIP(hipGetLastError());
-                    RWR_TRY(prof.end(prof.rank, a, s));
-                    for (size_t q = 0; q < nslots; ++q)
-                        if (row_of[q] >= 0)
-                            RWR_HIP(hipMemcpyAsync(rank_out + (size_t)slot_k[q0 + q] * n, g->cs_diff.p + (size_t)row_of[q] * n,
-                                                   sizeof(double) * n, hipMemcpyDeviceToHost, s));
-                    RWR_HIP(hipStreamSynchronize(s));
-                    RWR_TRY(prof.fold(g));
-                    live -= m;
-                }
-                if (live == 0) break;
+            if (cols.ends.due(steps)) {
+                RWR_TRY(cols.emit(steps, gi.X));
+                if (cols.ends.done()) break;
             }
-            if (steps == T) {
+            if (steps == end.T) {                            // RWR_MAX_ITERS steps made: the later groups do not run
                 set_error("rwr_model_run_batch: no convergence within %lld iterations (RWR_MAX_ITERS)", (long long)end.max_iters);
-                RWR_HIP(hipStreamSynchronize(g->stream2));
                 return RWR_E_UNSUPPORTED;
             }
             hipEvent_t i0; RWR_TRY(prof.record(i0, s));
-            RWR_TRY(gi.step(plan_step(gi.cfg, steps, by_count ? T : -1), prof));   // deliverRanks + updateRanks
+            RWR_TRY(gi.step(plan_step(gi.cfg, steps, end.by_count ? end.T : -1), prof));   // deliverRanks + updateRanks
             ++steps;
-            if (!by_count) {                                 // checkConvergence of every column (Model.cs:58-65, 110-115)
-                launch_absdiff_mat(gi.Y, gi.X, elems, g->cs_diff.p, s);
-                RWR_TRY(chain_scan_sum_cols(g, G, tg, g->cs_diff.p, evoff, g->cs_sums.p, s));
-            }
-            RWR_TRY(prof.end(prof.iter, i0, s));
-            if (!by_count) {
-                dist.resize(nslots);
-                RWR_HIP(hipMemcpyAsync(dist.data(), g->cs_sums.p, nslots * sizeof(double), hipMemcpyDeviceToHost, s));
-                RWR_HIP(hipStreamSynchronize(s));
-                RWR_TRY(prof.fold(g));
-            }
+            RWR_TRY(end.by_count ? prof.end(prof.iter, i0, s) : cols.measure(i0, gi.Y, gi.X));
         }
-        g->stats.spmm_seed_steps += (int64_t)real * steps;
-        g->stats.spmm_dense_seed_steps += (int64_t)real * gi.dense_steps;
+        cols.count(steps, gi.dense_steps);
     }
-    RWR_HIP(hipStreamSynchronize(s));
-    RWR_HIP(hipStreamSynchronize(g->stream2));
-    RWR_TRY(prof.fold(g));
-    if (prof.on) RWR_TRY(chain_scan_collect(g, s));
-    g->stats.tile_seeds = G;
-    g->stats.tile_group = TG;
-    g->stats.total_wall_ms += now_ms() - t_begin;
-    return RWR_OK;
+    return finish_model_batch(g, prof, G, TG, t_begin);
 }
 
-// no C++ exception crosses the C boundary
 int32_t model_run_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t run_mode, double value,
                         double *rank_out, int64_t *iters_out)
 {
-    try {
-        return model_run_batch_body(g, seeds, K, d, run_mode, value, rank_out, iters_out);
-    } catch (const std::bad_alloc &) {
-        set_error("rwr_model_run_batch: host allocation failed");
-        return RWR_E_NOMEM;
-    } catch (...) {
-        set_error("rwr_model_run_batch: unexpected host exception");
-        return RWR_E_HIP;
-    }
+    return no_throw("rwr_model_run_batch",
+                    [&] { return model_run_batch_body(g, seeds, K, d, run_mode, value, rank_out, iters_out); });
 }
 
 }  // namespace rwr

@@ -11,7 +11,6 @@
 //   |S| >  RWR_RESTART_EXACT_MAX   link-only SpMV + (tree-summed restart mass) * v[r], tolerance parity like the global model.
 #include <algorithm>
 #include <cmath>
-#include <new>
 
 #include "iterate.h"
 
@@ -225,18 +224,6 @@ __global__ void k_add_restart_vec(double *__restrict__ y, int32_t n, const doubl
     if (i < n) y[i] += *total * v[i];
 }
 
-namespace {
-// scratch buffers of one call are released only after both streams are idle (also on error paths): declared after them
-struct StreamsIdle {
-    rwr_graph *g;
-    ~StreamsIdle()
-    {
-        (void)hipStreamSynchronize(g->stream);
-        (void)hipStreamSynchronize(g->stream2);
-    }
-};
-}  // namespace
-
 static int32_t model_restart_body(rwr_graph *g, const double *v, const double *rank_in, double d, int32_t run_mode,
                                   double value, bool one_step, double *rank_out, int64_t *iters_out, const char *who)
 {
@@ -294,8 +281,7 @@ static int32_t model_restart_body(rwr_graph *g, const double *v, const double *r
     sp.seeds = g->d_seeds.p, sp.c1 = c1, sp.hub_scan = hub_scan;
     RWR_HIP(hipMemcpyAsync(X, rank_in, sizeof(double) * n, hipMemcpyHostToDevice, s));
     int64_t done = 0;
-    bool converged = false;
-    while (done < end.T) {
+    const auto step = [&]() -> int32_t {
         if (exact) {
             if (nsup > 0) {                                          // the support rows' chains beside the SpMV
                 RWR_HIP(hipEventRecord(g->ev_fork, s));
@@ -318,38 +304,23 @@ static int32_t model_restart_body(rwr_graph *g, const double *v, const double *r
             hipLaunchKernelGGL(k_add_restart_vec, dim3(cdiv((size_t)n, 256)), dim3(256), 0, s, Y, n, model_scalar(g), d_v.p);
         }
         RWR_HIP(hipGetLastError());
-        { double *t = X; X = Y; Y = t; }
-        ++done;
-        if (!end.by_count) {                                         // checkConvergence (Model.cs:58-65, 110-115)
-            // exact: the reference's sequential sum of |rank - nextRank|, bit for bit (same iteration count)
-            double diff = 0;
-            RWR_TRY(exact ? converge_exact(g, X, Y, &diff) : converge_tree(g, X, Y, &diff));
-            if (diff < end.threshold) { converged = true; break; }
-        }
-    }
-    if (!end.by_count && !converged) {
-        set_error("%s: no convergence within %lld iterations (RWR_MAX_ITERS)", who, (long long)end.max_iters);
-        return RWR_E_UNSUPPORTED;
-    }
+        std::swap(X, Y);
+        return RWR_OK;
+    };
+    // checkConvergence (Model.cs:58-65, 110-115); exact: the reference's sequential sum of |rank - nextRank|, bit for bit
+    // (same iteration count)
+    RWR_TRY(run_walk(who, end, &done, step,
+                     [&](double *dist) { return exact ? converge_exact(g, X, Y, dist) : converge_tree(g, X, Y, dist); }));
     RWR_HIP(hipMemcpyAsync(rank_out, X, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     RWR_HIP(hipStreamSynchronize(s));
     if (iters_out) *iters_out = done;
     return RWR_OK;
 }
 
-// no C++ exception crosses the C boundary
 static int32_t model_restart(rwr_graph *g, const double *v, const double *rank_in, double d, int32_t run_mode, double value,
                              bool one_step, double *rank_out, int64_t *iters_out, const char *who)
 {
-    try {
-        return model_restart_body(g, v, rank_in, d, run_mode, value, one_step, rank_out, iters_out, who);
-    } catch (const std::bad_alloc &) {
-        set_error("%s: host allocation failed", who);
-        return RWR_E_NOMEM;
-    } catch (...) {
-        set_error("%s: unexpected host exception", who);
-        return RWR_E_HIP;
-    }
+    return no_throw(who, [&] { return model_restart_body(g, v, rank_in, d, run_mode, value, one_step, rank_out, iters_out, who); });
 }
 
 int32_t model_run_restart(rwr_graph *g, const double *v, const double *rank_in, double d, int32_t run_mode, double value,

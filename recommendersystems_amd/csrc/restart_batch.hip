@@ -8,7 +8,7 @@
 //                  into a side buffer;
 //   main stream    after the join, k_restart_scatter_cols puts the folded rows over the link-only values.
 // Threshold modes sum |rank - nextRank| per column with the exact G-wide scan and stop each vector at its own step, as
-// model_run_batch does for seeds; the finished columns leave through k_extract_cols and one D2H per row.
+// model_run_batch does for seeds; the finished columns leave through k_extract_cols and one D2H per row (GroupColumns).
 //
 // The SpMM runs the weighted kernels (ensure_in_w, as restart.hip): the step lasts as long as its chains, which the SpMM
 // runs beside, so the value-free form's smaller matrix stream would shorten nothing (measured).
@@ -19,7 +19,6 @@
 // leave the device in place of K x n.  `Ranked` carries what that end needs; a call without one is the full-vector entry.
 #include <algorithm>
 #include <cstring>
-#include <new>
 
 #include "exclude_plan.h"
 #include "iterate.h"
@@ -27,16 +26,6 @@
 namespace rwr {
 
 namespace {
-// scratch buffers of one call are released only after both streams are idle (also on error paths): declared after them
-struct StreamsIdle {
-    rwr_graph *g;
-    ~StreamsIdle()
-    {
-        (void)hipStreamSynchronize(g->stream);
-        (void)hipStreamSynchronize(g->stream2);
-    }
-};
-
 // The ranked end of a call: the exclusion sets (CSR over batch positions), the lists' width and destination, and the device
 // copy of the exclusion plan.  Declared by the entry point before its StreamsIdle, so the buffers outlive the kernels.
 struct Ranked {
@@ -180,8 +169,6 @@ static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_pt
         return RWR_OK;
     }
     const RunEnd end(run_mode, value, n);
-    const bool by_count = end.by_count;
-    const int64_t T = end.T;
     const double c1 = 1 - d;                                   // Model.cs:84
     const int G = resolve_G(g, K);
     int TG = 1;
@@ -246,67 +233,35 @@ static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_pt
     RWR_HIP(hipStreamSynchronize(s));                           // (the host vectors above are pageable)
 
     Profile prof(g);                                            // (column extraction counts as ranking time)
-    std::vector<int32_t> row_of;
-    std::vector<double> dist;
     int32_t stuck = -1;                                         // threshold modes: smallest k that did not converge
     for (int t0 = 0, grp = 0; t0 < ntiles; t0 += TG, ++grp) {
         const int tg = (ntiles - t0 < TG) ? (ntiles - t0) : TG;
-        const size_t q0 = (size_t)t0 * G, nslots = (size_t)tg * G;
-        const size_t elems = nslots * (size_t)n;
+        const size_t q0 = (size_t)t0 * G;
         const int32_t npairs = (int32_t)(gp[(size_t)grp + 1] - gp[grp]);
         const int32_t *gq = d_pq.p + gp[grp], *gr = d_pr.p + gp[grp];
         const double *gv = d_pv.p + gp[grp];
         double *gf = d_fold.p + gp[grp];
-        int32_t live = 0;                                       // real slots whose column is not out yet
-        for (size_t q = 0; q < nslots; ++q) live += slot_k[q0 + q] >= 0;
-        const int32_t real = live;
-        std::vector<uint8_t> out_done(nslots, 0);
+        GroupColumns cols(g, G, tg, slot_k.data() + q0, g->d_evoff.p + q0, end, rank_out, iters_out, prof);
         double *X = g->X.p, *Y = g->Y.p;
         launch_restart_init_cols(g, G, tg, d_st.p + q0, X, s);  // Model ctor (Model.cs:25 / :44)
         RWR_HIP(hipGetLastError());
-        if (!by_count) RWR_TRY(chain_scan_sum_cols_prepare(g, G, tg, s));
+        if (!end.by_count) RWR_TRY(chain_scan_sum_cols_prepare(g, G, tg, s));
         SpmmArgs sp;                                            // link-only: no seed row, every row, no bitmaps, no row lists
         sp.seeds = g->d_seeds.p + q0, sp.c1 = c1;
         // restart.hip's rule, batch-wide: the constructors' ranks are >= 0 and stay so while every restart value is
         sp.hub_scan = v_nonneg;
         int64_t steps = 0;
         for (;;) {
-            if (rk && steps == T) {                             // every column ends here and stays on the device
+            if (rk && steps == end.T) {                         // every column ends here and stays on the device
                 RWR_TRY(ranked_finish_group(g, *rk, G, tg, grp, q0, X, prof, s));
                 break;
             }
-            if (by_count ? steps == T : steps > 0) {
-                // the columns whose run ends here: every one after step T, the converged ones in threshold mode
-                row_of.assign(nslots, -1);
-                int32_t m = 0;
-                for (size_t q = 0; q < nslots; ++q) {
-                    const int32_t k = slot_k[q0 + q];
-                    if (k < 0 || out_done[q] || !(by_count || dist[q] < end.threshold)) continue;   // Model.cs:64
-                    row_of[q] = m++;
-                    out_done[q] = 1;
-                    if (iters_out) iters_out[k] = steps;
-                }
-                if (m > 0) {
-                    RWR_HIP(hipMemcpyAsync(g->mb_row.p, row_of.data(), nslots * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                    hipEvent_t a; RWR_TRY(prof.record(a, s));
-                    launch_extract_cols(g, G, tg, X, g->mb_row.p, g->cs_diff.p, s);
-                    RWR_HIP(hipGetLastError());
-                    RWR_TRY(prof.end(prof.rank, a, s));
-                    for (size_t q = 0; q < nslots; ++q)
-                        if (row_of[q] >= 0)
-                            RWR_HIP(hipMemcpyAsync(rank_out + (size_t)slot_k[q0 + q] * n, g->cs_diff.p + (size_t)row_of[q] * n,
-                                                   sizeof(double) * n, hipMemcpyDeviceToHost, s));
-                    RWR_HIP(hipStreamSynchronize(s));
-                    RWR_TRY(prof.fold(g));
-                    live -= m;
-                }
-                if (live == 0) break;
+            if (cols.ends.due(steps)) {
+                RWR_TRY(cols.emit(steps, X));
+                if (cols.ends.done()) break;
             }
-            if (steps == T) {                                   // RWR_MAX_ITERS steps made: the later groups still decide the smallest k
-                for (size_t q = 0; q < nslots; ++q) {
-                    const int32_t k = slot_k[q0 + q];
-                    if (k >= 0 && !out_done[q] && (stuck < 0 || k < stuck)) stuck = k;
-                }
+            if (steps == end.T) {                               // RWR_MAX_ITERS steps made: the later groups still decide the smallest k
+                if (stuck < 0 || cols.ends.stuck() < stuck) stuck = cols.ends.stuck();
                 break;
             }
             hipEvent_t i0; RWR_TRY(prof.record(i0, s));
@@ -329,37 +284,20 @@ static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_pt
                 launch_restart_scatter_cols(g, G, npairs, gq, gr, gf, Y, s);
             }
             RWR_HIP(hipGetLastError());
-            { double *t = X; X = Y; Y = t; }                    // Model.updateRanks (Model.cs:103-108)
+            std::swap(X, Y);                                    // Model.updateRanks (Model.cs:103-108)
             ++steps;
             g->stats.spmm_launches += 1;
             g->stats.spmm_dense_launches += 1;
             g->stats.chain_launches += npairs > 0;
-            if (!by_count) {                                    // checkConvergence of every column (Model.cs:58-65, 110-115)
-                launch_absdiff_mat(Y, X, elems, g->cs_diff.p, s);
-                RWR_TRY(chain_scan_sum_cols(g, G, tg, g->cs_diff.p, g->d_evoff.p + q0, g->cs_sums.p, s));
-            }
-            RWR_TRY(prof.end(prof.iter, i0, s));
-            if (!by_count) {
-                dist.resize(nslots);
-                RWR_HIP(hipMemcpyAsync(dist.data(), g->cs_sums.p, nslots * sizeof(double), hipMemcpyDeviceToHost, s));
-                RWR_HIP(hipStreamSynchronize(s));
-                RWR_TRY(prof.fold(g));
-            }
+            RWR_TRY(end.by_count ? prof.end(prof.iter, i0, s) : cols.measure(i0, Y, X));
         }
-        g->stats.spmm_seed_steps += (int64_t)real * steps;
-        g->stats.spmm_dense_seed_steps += (int64_t)real * steps;
+        cols.count(steps, steps);
     }
     if (rk) {                                                   // one copy-back of K x top_n entries, as recommend_batch's
         RWR_TRY(copy_lists_back(g, K, rk->top_n, rk->ids, rk->scores, rk->counts, rk->top_n));
         g->stats.seeds_done += K;
     }
-    RWR_HIP(hipStreamSynchronize(s));
-    RWR_HIP(hipStreamSynchronize(s2));
-    RWR_TRY(prof.fold(g));
-    if (prof.on) RWR_TRY(chain_scan_collect(g, s));
-    g->stats.tile_seeds = G;
-    g->stats.tile_group = TG;
-    g->stats.total_wall_ms += now_ms() - t_begin;
+    RWR_TRY(finish_model_batch(g, prof, G, TG, t_begin));
     if (stuck >= 0) {
         set_error("%s: vector %d: no convergence within %lld iterations (RWR_MAX_ITERS)", who, stuck,
                   (long long)end.max_iters);
@@ -368,20 +306,13 @@ static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_pt
     return RWR_OK;
 }
 
-// no C++ exception crosses the C boundary
 static int32_t restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
                              const int32_t *start, double d, int32_t run_mode, double value, double *rank_out, int64_t *iters_out,
                              Ranked *rk, const char *who)
 {
-    try {
+    return no_throw(who, [&] {
         return restart_batch_body(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out, rk, who);
-    } catch (const std::bad_alloc &) {
-        set_error("%s: host allocation failed", who);
-        return RWR_E_NOMEM;
-    } catch (...) {
-        set_error("%s: unexpected host exception", who);
-        return RWR_E_HIP;
-    }
+    });
 }
 
 int32_t model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,

@@ -134,6 +134,23 @@ def test_threshold_modes_stop_per_seed(amd, setups, threshold):
             G.close()
 
 
+def test_threshold_mode_over_several_tile_groups(amd):
+    """Per-seed stopping with the batch spread over tile groups: 13 seeds in tiles of 4, one tile per group, so four groups
+    run their own threshold loops (the last one a tile with one seed and three padding slots).  The contraction by 1 - d
+    per step brings every seed below 1e-9 after a few hundred steps at the most; the dangling seed stops after step 1."""
+    g = gg.random_graph(11, n_users=40, n_items=90, n_likes=400, n_etc=3, n_friend=20, n_mention=15)
+    dangling = np.flatnonzero(np.diff(g["rowptr"]) == 0)
+    seeds = np.array(list(range(12)) + [int(dangling[0])], dtype=np.int32)
+    G = amd.Graph.from_flat(**g, tile_seeds=4, tile_group=1)
+    G.buildGraph()
+    got = amd.Model.RunBatch(G, D, seeds, 1e-9)
+    st = G.stats()
+    assert st["tile_seeds"] == 4 and st["tile_group"] == 1, "the batch did not run as four tile groups"
+    same(got, singles(amd, G, seeds, 1e-9, {}), "several tile groups")
+    assert got[1][-1] == 1 and len(set(got[1].tolist())) > 1
+    G.close()
+
+
 def test_default_threshold(amd):
     """run() (Model.cs:52-55): "until nothing changes", on a small graph where the reference converges for these seeds."""
     from recommendersystems_amd import _lib
