@@ -209,16 +209,21 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
     // and the rest of the step keeps only the rows that reach each seed's threshold.  By default from RANK_FUSED_MIN_ITEMS ITEM
     // rows on: below, the select's passes over the item block are cheaper than the second sort per seed and the
     // synchronising copy per group that the split adds (C3, 62 K items: -0.4 %).  RWR_RANK_FUSED=0: off, =2: whatever the size;
-    // RWR_RANK_FUSED_HEAD: H (default: the power of two at or above a sixteenth of the ITEM rows)
+    // RWR_RANK_FUSED_HEAD: H.  Default: the power of two at or above n_items / RANK_FUSED_HEAD_DIV on the value-free path, whose
+    // body is pruned by the head's thresholds (the head's rows are the ones with most in-links, and past the first 1-2 % of
+    // the rows the bound prunes nearly all of them: tools/rank_head_study.py, DESIGN §3.3.3 "A smaller head"); a sixteenth of
+    // the ITEM rows on the weighted path, whose body is not pruned -- a smaller head saves nothing there
     constexpr int32_t RANK_FUSED_MIN_ITEMS = 1 << 18;
+    constexpr int64_t RANK_FUSED_HEAD_DIV = 96, RANK_FUSED_HEAD_DIV_WEIGHTED = 16;
     static const int force_sort = [] { const char *e = RWR_TUNE_ENV("RWR_RANK_SORT"); return e ? atoi(e) : 0; }();
     static const int fused_env = [] { const char *e = getenv("RWR_RANK_FUSED"); return e ? atoi(e) : 1; }();
     static const long head_env = [] { const char *e = getenv("RWR_RANK_FUSED_HEAD"); return e ? atol(e) : 0L; }();
     const bool select_path = top_n <= rank_select_max_k() && !force_sort;
     int32_t head_rows = 0;
     if (fused_env && select_path && top_n >= 1 && g->n_items > 0 && (fused_env == 2 || g->n_items >= RANK_FUSED_MIN_ITEMS)) {
+        const int64_t div = g->vf ? RANK_FUSED_HEAD_DIV : RANK_FUSED_HEAD_DIV_WEIGHTED;
         int64_t h = 1;
-        while (h * 16 < (int64_t)g->n_items) h <<= 1;
+        while (h * div < (int64_t)g->n_items) h <<= 1;
         if (head_env > 0) h = head_env;
         head_rows = (int32_t)(h < (int64_t)g->n_items ? h : (int64_t)g->n_items);
     }
