@@ -211,18 +211,6 @@ int32_t eval_ranked(rwr_graph *g, int32_t cnt, const int64_t *test_sorted_host, 
                     double *sum_precision);
 int32_t eval_ranked_batch(rwr_graph *g, int32_t K, int64_t row_stride, const int64_t *test_ptr_host,
                           const int64_t *test_sorted_host, int64_t *n_hits, double *sum_precision);
-// rank.hip: the exclusion (k_exclude: X[tile][n][G], one seed per slot, -1 = none) and the ranking of a tile group / one tile
-void launch_exclude(rwr_graph *g, int G, int tg, double *X, const int32_t *d_seeds, hipStream_t s);
-// ... of a set of nodes per slot (k_exclude_segments): the segments exclude_plan.h cut the members' raw lists into
-void launch_exclude_segments(rwr_graph *g, int G, int32_t nseg, const int32_t *seg_slot, const int64_t *seg_p0,
-                             const int64_t *seg_p1, double *X, hipStream_t s);
-int32_t rank_group_select(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, const double *X,
-                          const int32_t *d_seeds, hipStream_t s, const int32_t *rows = nullptr, int32_t nrows = 0);
-int rank_select_max_k();
-int32_t emit_dangling(rwr_graph *g, const std::vector<int32_t> &rows, const std::vector<int32_t> &seeds, int32_t top_n,
-                      hipStream_t s);
-int32_t rank_tile(rwr_graph *g, int G, const int32_t *d_slot_k_tile, int32_t top_n, const double *X,
-                  const int32_t *d_seeds_tile, hipStream_t s);
 // partition.hip: the row-partitioned mode (rwr_part_*)
 int32_t part_begin(rwr_graph *g, int32_t lo, int32_t hi, const int32_t *seeds, int32_t K, double d, double *x,
                    int32_t *G_out);

@@ -3,6 +3,7 @@
 #pragma once
 #include "column_ends.h"
 #include "engine.h"
+#include "rank.h"
 #include "step_plan.h"
 
 #include <new>
@@ -118,20 +119,6 @@ struct SplitLast {
 };
 int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const int64_t *d_evoff, const int32_t *h_seeds,
                       double d, int64_t T, Profile &prof, double **final_X, int64_t *dense_steps, SplitLast *split = nullptr);
-
-// rank.hip, the ranking inside the last step: the candidate capacity per slot (SEL_SLOTS - top_n, or less:
-// RWR_RANK_FUSED_CAP); after the head's select, the group's thresholds and cleared cursors (fills *sink); after the
-// selecting launch, the merge of the head's lists with the candidates
-int rank_fused_capacity(int32_t top_n);
-int32_t rank_fused_prepare(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, SelSink *sink, hipStream_t s);
-int32_t rank_fused_merge(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, const int32_t *d_seeds, int32_t top_n,
-                         const SelSink &sink, hipStream_t s);
-// Pruning the body (rank_bound.h), after rank_fused_prepare and before the selecting launch over the `count` rows
-// of tail_rows[0] from `first` on: per tile the bound table of the source rows (Z: the z matrix the step gathers) and each
-// rows' keep bits, compacted into the tiles' row lists (sink->list); *pruned (device) receives the (row, tile) pairs the launch
-// will skip.  Leaves sink->list null when pruning is off (RWR_RANK_PRUNE=0) or its workspace cannot be had.
-int32_t rank_bound_prepare(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const double *Z, int32_t first, int32_t count,
-                           SelSink *sink, unsigned long long **pruned, hipStream_t s);
 
 // recommend.hip: seeds per tile, the batch workspace (extra_mats: further [tile][n][G] matrices the caller needs per tile),
 // the seeds dealt to tile slots (d_seeds, d_slot_k, d_evoff)

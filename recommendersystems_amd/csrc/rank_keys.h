@@ -1,0 +1,64 @@
+// What the kernels of rank.hip and rank_fused.hip share (device side): the geometry of the radix select, the 128-bit
+// (score, id) key of a candidate, and the one sort-and-emit every LDS-sorted list goes out through.
+#pragma once
+#include "common.h"
+
+namespace rwr {
+
+constexpr int SEL_MAX_K = 1024;
+constexpr int SEL_CAP = 3072;
+constexpr int SEL_SLOTS = 4096;      // >= SEL_MAX_K - 1 + SEL_CAP
+constexpr int SEL_LEVELS = 16;
+constexpr int SEL_ROWS_PER_BLOCK = 4096;
+constexpr int SEL_FUSED_LEVELS = 3;  // few seeds: levels decided by the histogram kernel's last workgroup (rank_group_select)
+
+// hi = f64_orderable(score), lo = i64_orderable(id); {0, 0} lies below every real key (scores are >= +0.0: hi >= 2^63)
+struct SelCand {
+    uint64_t hi, lo;
+};
+__device__ __forceinline__ void sel_decode(const SelCand &v, int64_t *id, double *score)
+{
+    *id = (int64_t)(v.lo ^ 0x8000000000000000ull);
+    const uint64_t u = (v.hi & 0x8000000000000000ull) ? (v.hi ^ 0x8000000000000000ull) : ~v.hi;
+    double s;
+    __builtin_memcpy(&s, &u, 8);
+    *score = s;
+}
+
+// the workgroup's N2 (a power of two) entries of sc sorted descending by (hi, lo) (bitonic).  The caller has synchronised after filling sc
+__device__ __forceinline__ void sel_sort(SelCand *sc, int N2)
+{
+    for (int size = 2; size <= N2; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < N2 / 2; t += blockDim.x) {
+                const int lo_i = 2 * t - (t & (stride - 1));
+                const int hi_i = lo_i + stride;
+                const bool desc = (lo_i & size) == 0;        // first half of each bitonic pair: descending
+                const SelCand a = sc[lo_i], b = sc[hi_i];
+                const bool a_lt_b = (a.hi < b.hi) || (a.hi == b.hi && a.lo < b.lo);
+                if (a_lt_b == desc) {
+                    sc[lo_i] = b;
+                    sc[hi_i] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+// the first min(cnt, top_n) entries of the sorted sc go out as row orow of the result tables
+__device__ __forceinline__ void sel_emit(const SelCand *sc, int cnt, int32_t orow, int32_t top_n, int64_t *__restrict__ out_id,
+                                         double *__restrict__ out_score, int32_t *__restrict__ out_counts)
+{
+    int take = cnt < top_n ? cnt : top_n;
+    if (threadIdx.x == 0) out_counts[orow] = take;
+    for (int i = threadIdx.x; i < take; i += blockDim.x)
+        sel_decode(sc[i], &out_id[(size_t)orow * top_n + i], &out_score[(size_t)orow * top_n + i]);
+}
+__device__ __forceinline__ void sel_sort_emit(SelCand *sc, int N2, int cnt, int32_t orow, int32_t top_n, int64_t *__restrict__ out_id,
+                                              double *__restrict__ out_score, int32_t *__restrict__ out_counts)
+{
+    sel_sort(sc, N2);
+    sel_emit(sc, cnt, orow, top_n, out_id, out_score, out_counts);
+}
+
+}  // namespace rwr

@@ -1,6 +1,6 @@
 // Recommender.Recommendation for a batch of seeds (rwr_recommend_batch and the entry points built on it): sizes the
 // workspace, deals the seeds to tiles and tile groups, runs each group's power iteration (iterate.hip: iterate_group), then
-// the exclusion and the ranking (rank.hip), and copies the lists back.
+// the exclusion and the ranking (rank.h), and copies the lists back.
 #include "iterate.h"
 
 #include <algorithm>
@@ -178,15 +178,7 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
     const bool any_dangling = !dang_seeds.empty();
     if (any_dangling) { seeds = live_seeds.data(); K = (int32_t)live_seeds.size(); }
     hipStream_t s = g->stream;
-    const size_t out_all = (size_t)K_all * (size_t)top_n;
-    // (every emitter indexes these tables by the caller's batch position < K_all: no padding rows are ever written)
-    RWR_TRY(g->d_out_id.ensure(out_all + 64));
-    RWR_TRY(g->d_out_score.ensure(out_all + 64));
-    RWR_TRY(g->d_counts.ensure((size_t)K_all + 64));
-    // output tables are indexed by the caller's batch position (K_all rows)
-    RWR_HIP(hipMemsetAsync(g->d_out_id.p, 0, out_all * sizeof(int64_t), s));
-    RWR_HIP(hipMemsetAsync(g->d_out_score.p, 0, out_all * sizeof(double), s));
-    RWR_HIP(hipMemsetAsync(g->d_counts.p, 0, (size_t)K_all * sizeof(int32_t), s));
+    RWR_TRY(ensure_out_tables(g, K_all, top_n, s));
     if (K == 0) {   // every seed of the batch is dangling
         RWR_TRY(emit_dangling(g, dang_rows, dang_seeds, top_n, s));
         RWR_TRY(copy_lists_back(g, K_all, top_n, ids, scores, counts, row_stride));
@@ -205,28 +197,9 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
         RWR_HIP(hipMemcpy(g->d_slot_k.p, slot_k.data(), slot_k.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
 
-    // Ranking inside the last step: the step runs over the first H rows of tail_rows[0], the select ranks those,
-    // and the rest of the step keeps only the rows that reach each seed's threshold.  By default from RANK_FUSED_MIN_ITEMS ITEM
-    // rows on: below, the select's passes over the item block are cheaper than the second sort per seed and the
-    // synchronising copy per group that the split adds (C3, 62 K items: -0.4 %).  RWR_RANK_FUSED=0: off, =2: whatever the size;
-    // RWR_RANK_FUSED_HEAD: H.  Default: the power of two at or above n_items / RANK_FUSED_HEAD_DIV on the value-free path, whose
-    // body is pruned by the head's thresholds (the head's rows are the ones with most in-links, and past the first 1-2 % of
-    // the rows the bound prunes nearly all of them: tools/rank_head_study.py, DESIGN §3.3.3 "A smaller head"); a sixteenth of
-    // the ITEM rows on the weighted path, whose body is not pruned -- a smaller head saves nothing there
-    constexpr int32_t RANK_FUSED_MIN_ITEMS = 1 << 18;
-    constexpr int64_t RANK_FUSED_HEAD_DIV = 96, RANK_FUSED_HEAD_DIV_WEIGHTED = 16;
-    static const int force_sort = [] { const char *e = RWR_TUNE_ENV("RWR_RANK_SORT"); return e ? atoi(e) : 0; }();
-    static const int fused_env = [] { const char *e = getenv("RWR_RANK_FUSED"); return e ? atoi(e) : 1; }();
-    static const long head_env = [] { const char *e = getenv("RWR_RANK_FUSED_HEAD"); return e ? atol(e) : 0L; }();
-    const bool select_path = top_n <= rank_select_max_k() && !force_sort;
-    int32_t head_rows = 0;
-    if (fused_env && select_path && top_n >= 1 && g->n_items > 0 && (fused_env == 2 || g->n_items >= RANK_FUSED_MIN_ITEMS)) {
-        const int64_t div = g->vf ? RANK_FUSED_HEAD_DIV : RANK_FUSED_HEAD_DIV_WEIGHTED;
-        int64_t h = 1;
-        while (h * div < (int64_t)g->n_items) h <<= 1;
-        if (head_env > 0) h = head_env;
-        head_rows = (int32_t)(h < (int64_t)g->n_items ? h : (int64_t)g->n_items);
-    }
+    // ranking inside the last step (rank_plan.h): the step runs over the first head_rows rows of tail_rows[0] only
+    const bool select_path = top_n <= rank_select_max_k() && !rank_knobs().sort;
+    const int32_t head_rows = fused_head_rows(g->n_items, g->vf != 0, top_n, select_path, rank_knobs());
 
     Profile prof(g);
     for (int t0 = 0; t0 < ntiles; t0 += TG) {
@@ -249,49 +222,8 @@ int32_t recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d,
         RWR_HIP(hipGetLastError());
         const int32_t *slot_k_g = g->d_slot_k.p + (size_t)t0 * G;
         bool ranked = false;
-        if (split.taken) {
-            // the head (in-degree-descending: tail_rows[0] is a stable partition of row_order) is ranked exactly; its top_n-th
-            // score bounds the final one from below, and the rest of the step selects by it while it computes
-            const int32_t n_tail = g->tail_n[0];
-            const int32_t H = head_rows < n_tail ? head_rows : n_tail;
-            RWR_TRY(rank_group_select(g, G, tg, slot_k_g, top_n, Xf, dseeds, s, g->tail_rows[0].p, H));
-            ranked = true;
-            if (H < n_tail) {
-                SelSink sink;
-                RWR_TRY(rank_fused_prepare(g, G, tg, slot_k_g, top_n, &sink, s));
-                // value-free path: the thresholds bound every body row's scores from one float per in-link, and the
-                // selecting launch walks only the rows some seed of the tile may still need (rank_bound.h)
-                unsigned long long *d_pruned = nullptr, pruned = 0;
-                hipEvent_t b0; RWR_TRY(prof.record(b0, s));
-                RWR_TRY(rank_bound_prepare(g, G, tg, dseeds, split.gi->Zn, H, n_tail - H, &sink, &d_pruned, s));
-                RWR_TRY(prof.end(prof.bound, b0, s));
-                RWR_TRY(split.gi->redo_rows(split.last, prof, H, n_tail - H, &sink));
-                RWR_TRY(rank_fused_merge(g, G, tg, slot_k_g, dseeds, top_n, sink, s));
-                int32_t overflow = 0;   // (one small synchronising copy per group)
-                RWR_HIP(hipMemcpyAsync(&overflow, sink.overflow, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                if (d_pruned) RWR_HIP(hipMemcpyAsync(&pruned, d_pruned, sizeof pruned, hipMemcpyDeviceToHost, s));
-                RWR_HIP(hipStreamSynchronize(s));
-                if (!overflow) g->stats.rank_pruned_rows += (int64_t)pruned;
-                if (overflow) {
-                    // some seed's candidates did not fit: the step again, whole (its inputs are intact), ranked as without the split
-                    RWR_TRY(split.gi->redo_rows(split.last, prof, 0, -1, nullptr));
-                    launch_exclude(g, G, tg, Xf, dseeds, s);
-                    RWR_HIP(hipGetLastError());
-                    g->stats.rank_fused_fallbacks += 1;
-                    ranked = false;
-                }
-            }
-            g->stats.rank_fused_groups += ranked;
-        }
-        if (ranked) {
-        } else if (select_path) {
-            RWR_TRY(rank_group_select(g, G, tg, slot_k_g, top_n, Xf, dseeds, s));
-        } else {
-            for (int t = 0; t < tg; ++t) {
-                RWR_TRY(rank_tile(g, G, g->d_slot_k.p + (size_t)(t0 + t) * G, top_n, Xf + (size_t)t * (size_t)n * G,
-                                  dseeds + (size_t)t * G, s));
-            }
-        }
+        if (split.taken) RWR_TRY(rank_group_fused(g, G, tg, slot_k_g, dseeds, top_n, Xf, split, prof, s, &ranked));
+        if (!ranked) RWR_TRY(rank_group(g, G, tg, slot_k_g, dseeds, top_n, Xf, s));
         RWR_TRY(prof.end(prof.rank, a, s));
     }
     if (any_dangling) RWR_TRY(emit_dangling(g, dang_rows, dang_seeds, top_n, s));

@@ -47,13 +47,8 @@ struct Ranked {
 static int32_t ranked_prepare(rwr_graph *g, Ranked &rk, int32_t K, const std::vector<int32_t> &slot_k, size_t slots_per_group,
                               hipStream_t s)
 {
-    const size_t out_all = (size_t)K * (size_t)rk.top_n, slots = slot_k.size();
-    RWR_TRY(g->d_out_id.ensure(out_all + 64));
-    RWR_TRY(g->d_out_score.ensure(out_all + 64));
-    RWR_TRY(g->d_counts.ensure((size_t)K + 64));
-    RWR_HIP(hipMemsetAsync(g->d_out_id.p, 0, out_all * sizeof(int64_t), s));
-    RWR_HIP(hipMemsetAsync(g->d_out_score.p, 0, out_all * sizeof(double), s));
-    RWR_HIP(hipMemsetAsync(g->d_counts.p, 0, (size_t)K * sizeof(int32_t), s));
+    const size_t slots = slot_k.size();
+    RWR_TRY(ensure_out_tables(g, K, rk.top_n, s));
     RWR_TRY(g->d_slot_k.ensure(slots));
     RWR_HIP(hipMemcpyAsync(g->d_slot_k.p, slot_k.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, s));
     rk.plan = exclude_plan(g->n, g->h_rowptr.data(), slots, slot_k.data(), slots_per_group, K, rk.set_ptr, rk.set_idx);
@@ -84,12 +79,7 @@ static int32_t ranked_finish_group(rwr_graph *g, const Ranked &rk, int G, int tg
     hipEvent_t a; RWR_TRY(prof.record(a, s));
     launch_exclude_segments(g, G, (int32_t)nseg, rk.d_seg_slot.p + j0, rk.d_seg_p0.p + j0, rk.d_seg_p1.p + j0, X, s);
     RWR_HIP(hipGetLastError());
-    if (rk.top_n <= rank_select_max_k()) {
-        RWR_TRY(rank_group_select(g, G, tg, slot_k, rk.top_n, X, slot_k, s));
-    } else {
-        for (int t = 0; t < tg; ++t)
-            RWR_TRY(rank_tile(g, G, slot_k + (size_t)t * G, rk.top_n, X + (size_t)t * (size_t)g->n * G, slot_k + (size_t)t * G, s));
-    }
+    RWR_TRY(rank_group(g, G, tg, slot_k, slot_k, rk.top_n, X, s));
     RWR_TRY(prof.end(prof.rank, a, s));
     return RWR_OK;
 }

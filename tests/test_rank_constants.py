@@ -12,8 +12,8 @@ from tests.test_gpu_rank_paths import EXPECTED_CONSTANTS
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "recommendersystems_amd", "csrc")
 
 WHERE = {
-    "SEL_MAX_K": "rank.hip", "SEL_CAP": "rank.hip", "SEL_SLOTS": "rank.hip", "SEL_ROWS_PER_BLOCK": "rank.hip",
-    "SEL_FUSED_LEVELS": "rank.hip", "SORT_CHUNK": "sort.hip", "SMALL_SORT_MAX": "sort_small.h",
+    "SEL_MAX_K": "rank_keys.h", "SEL_CAP": "rank_keys.h", "SEL_SLOTS": "rank_keys.h", "SEL_ROWS_PER_BLOCK": "rank_keys.h",
+    "SEL_FUSED_LEVELS": "rank_keys.h", "SORT_CHUNK": "sort.hip", "SMALL_SORT_MAX": "sort_small.h",
     "SM_MAX_ITEMS": "small.hip",
 }
 

@@ -35,7 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rank_prune_study import D, G, SLACK, T, TOP_N  # noqa: E402
 
-SEL_SLOTS = 4096                                   # rank.hip
+SEL_SLOTS = 4096                                   # rank_keys.h
 CAPACITY = SEL_SLOTS - TOP_N
 STAGE_MS = 3.5                                     # k_sel_bound_table, _compact, _flags, the merge: per extra stage
 H_MIN, H_MAX = 8192, 524288
