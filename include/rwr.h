@@ -130,6 +130,9 @@ typedef struct rwr_stats {
                                        a float bound over the row's in-list showed that no seed of the tile reaches its
                                        threshold there (groups that fell back count nothing); RWR_RANK_PRUNE=0: none */
     double  rank_bound_ms;          /* time of the bound tables and the rows' keep bits (part of rank_ms; profile only) */
+    int64_t x_clear_skipped;        /* tile groups of rwr_recommend_batch that started without clearing their rank matrix: the
+                                       fold beside step 2 read the frontier-list step's output through its bitmap (RWR_X_CLEAR=1:
+                                       none) */
 } rwr_stats;
 
 /* ---- library ------------------------------------------------------------------------- */

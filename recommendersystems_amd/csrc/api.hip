@@ -1058,6 +1058,7 @@ int32_t rwr_reset_stats(rwr_graph *g)
     s.rank_fused_groups = s.rank_fused_fallbacks = 0;
     s.rank_pruned_rows = 0;
     s.rank_bound_ms = 0;
+    s.x_clear_skipped = 0;
     return RWR_OK;
 }
 

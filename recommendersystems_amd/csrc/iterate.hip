@@ -548,12 +548,17 @@ constexpr int CH3_NSW = 6;                      // stager waves
 constexpr int CH3_NST = CH3_NSW * WAVE;         // stager threads
 constexpr int CH3_LPT = 16;                     // loads per stager thread and chunk
 constexpr int CH3_CE = CH3_NST * CH3_LPT;       // 6144 doubles per chunk (48 KiB)
-template <int G>
+// MASK: X was not cleared and the step before wrote only its frontier list's rows.  nz_x is the tile's bitmap
+// of the rows that step left non-zero; a row whose bit is clear is zero or stale, and the stagers take +0.0 for it -- by
+// selection, since a stale value may be anything, NaN included.  Its restart addend is then 0 - fl((1-d) 0) = +0.0, which
+// leaves the non-negative sum as it is: the fold is bitwise the one over the cleared matrix.  The folder does not change.
+template <int G, bool MASK>
 __global__ __launch_bounds__(WAVE + CH3_NST) void k_seed_chain_roles(
     int32_t n, const int64_t *__restrict__ in_ptr, const int32_t *__restrict__ in_src,
     const uint8_t *__restrict__ dangling, const double *__restrict__ X, double *__restrict__ Y,
     const int32_t *__restrict__ seeds, double c1, const int64_t *__restrict__ evoff,
-    const double *__restrict__ evterm, uint32_t *__restrict__ nz_out, unsigned int *__restrict__ gate)
+    const double *__restrict__ evterm, uint32_t *__restrict__ nz_out, unsigned int *__restrict__ gate,
+    const uint32_t *__restrict__ nz_x)
 {
     // check in: the main stream holds the SpMM back (k_gate) until the chain workgroups own their CUs
     if (threadIdx.x == 0 && gate) __hip_atomic_fetch_add(gate, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -565,13 +570,20 @@ __global__ __launch_bounds__(WAVE + CH3_NST) void k_seed_chain_roles(
     const int tid = threadIdx.x;
     const int64_t total = (int64_t)n * G;
     const int nchunks = (int)((total + CH3_CE - 1) / CH3_CE);
+    if (MASK) nz_x += (size_t)tile * (((size_t)n + 31) / 32);
 
     if (tid >= WAVE) {
         // ------------------------------------------------------------------ stagers
         const int st = tid - WAVE;
         double rega[CH3_LPT], regb[CH3_LPT];
         uint8_t dga[CH3_LPT], dgb[CH3_LPT];
-#define CH3_LOAD(R, D, C)                                                       \
+        // MASK: a chunk's rows start at a multiple of 32, so CR / 32 words of the bitmap cover it.  Every stager loads them all
+        // with the chunk's values (the addresses are the same in every lane) instead of one word per value: the stagers run at
+        // the rate their loads in flight allow, and a third load per value cost the fold 35 ms on C4
+        constexpr int NW = MASK ? CR / 32 : 1;
+        uint32_t bwa[NW], bwb[NW];
+        const int64_t nzw = ((int64_t)n + 31) / 32;
+#define CH3_LOAD(R, D, W, C)                                                    \
     {                                                                           \
         const int64_t base__ = (int64_t)(C) * CH3_CE;                           \
         _Pragma("unroll") for (int u = 0; u < CH3_LPT; ++u) {                   \
@@ -580,28 +592,44 @@ __global__ __launch_bounds__(WAVE + CH3_NST) void k_seed_chain_roles(
             R[u] = x[el];                                                       \
             D[u] = dangling[el / G];                                            \
         }                                                                       \
+        if (MASK) {                                                             \
+            _Pragma("unroll") for (int j = 0; j < NW; ++j) {                    \
+                int64_t wi__ = (int64_t)(C) * (CR / 32) + j;                    \
+                wi__ = wi__ < nzw ? wi__ : nzw - 1; /* (rows past n: staged as +0.0 whatever the word) */ \
+                W[j] = nz_x[wi__];                                              \
+            }                                                                   \
+        }                                                                       \
     }
-#define CH3_STAGE(R, D, C)                                                                              \
+#define CH3_STAGE(R, D, W, C)                                                                           \
     {                                                                                                   \
         const int64_t base__ = (int64_t)(C) * CH3_CE;                                                   \
         double *buf__ = rr + (size_t)((C) & 1) * CH3_CE;                                                \
         _Pragma("unroll") for (int u = 0; u < CH3_LPT; ++u) {                                           \
             const int off = u * CH3_NST + st;                                                           \
-            const double xv = (base__ + off < total) ? R[u] : 0.0; /* past the end: +0.0, no effect */  \
+            bool live__ = base__ + off < total;                                                         \
+            if (MASK) { /* the row's bit: its word is one of at most three, known once u is unrolled */ \
+                const int row__ = off / G, j0__ = (u * CH3_NST / G) >> 5;                               \
+                uint32_t wd__ = W[j0__];                                                                \
+                _Pragma("unroll") for (int dj = 1; dj <= 2; ++dj)                                       \
+                    if (j0__ + dj < NW && (row__ >> 5) == j0__ + dj) wd__ = W[j0__ + dj < NW ? j0__ + dj : 0]; \
+                live__ = live__ && ((wd__ >> (row__ & 31)) & 1u);                                       \
+            }                                                                                           \
+            const double xv = live__ ? R[u] : 0.0; /* past the end, outside the bitmap: +0.0, no effect */ \
             const double rw = c1 * xv;                                                                  \
             buf__[off] = D[u] ? xv : (xv - rw);                                                         \
         }                                                                                               \
     }
-        CH3_LOAD(rega, dga, 0)
-        if (nchunks > 1) CH3_LOAD(regb, dgb, 1)
+        static_assert(!MASK || (CH3_NST - 1) / G + 1 <= 64, "a thread's value of one load lies at most two bitmap words on");
+        CH3_LOAD(rega, dga, bwa, 0)
+        if (nchunks > 1) CH3_LOAD(regb, dgb, bwb, 1)
         for (int c = 0; c < nchunks; c += 2) {
-            CH3_STAGE(rega, dga, c)
-            if (c + 2 < nchunks) CH3_LOAD(rega, dga, c + 2)
+            CH3_STAGE(rega, dga, bwa, c)
+            if (c + 2 < nchunks) CH3_LOAD(rega, dga, bwa, c + 2)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
             __builtin_amdgcn_s_barrier();
             if (c + 1 < nchunks) {
-                CH3_STAGE(regb, dgb, c + 1)
-                if (c + 3 < nchunks) CH3_LOAD(regb, dgb, c + 3)
+                CH3_STAGE(regb, dgb, bwb, c + 1)
+                if (c + 3 < nchunks) CH3_LOAD(regb, dgb, bwb, c + 3)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
                 __builtin_amdgcn_s_barrier();
             }
@@ -777,6 +805,7 @@ static PlanInput read_plan_knobs()
     if ((e = RWR_TUNE_ENV("RWR_GATE"))) v.gate = atoi(e);
     if ((e = getenv("RWR_TAIL_ROWS"))) v.tail_rows = atoi(e);
     if ((e = RWR_TUNE_ENV("RWR_CHAIN_SERIAL"))) v.two_streams = atoi(e) == 0;
+    if ((e = getenv("RWR_X_CLEAR"))) v.x_clear = atoi(e);
     return v;
 }
 static const PlanInput &plan_knobs() { static const PlanInput k = read_plan_knobs(); return k; }
@@ -899,7 +928,7 @@ static void launch_seed_terms(rwr_graph *g, int tg, const double *X, const int32
 template <int G>
 static void launch_chain(rwr_graph *g, int tg, const double *X, double *Y, const int32_t *seeds, double c1,
                          const int64_t *evoff, uint32_t *nz_out, unsigned int *gate, hipStream_t s,
-                         Chain kind, const uint32_t *nz_x)
+                         Chain kind, const uint32_t *nz_x, bool masked)
 {
     if (kind == Chain::Sparse) {   // X still sparse: visit only the non-zero rows of its bitmap nz_x
         hipLaunchKernelGGL(k_seed_chain_sparse<G>, dim3(tg), dim3(64), 0, s, g->n, g->in_ptr.p, g->in_src.p,
@@ -910,9 +939,13 @@ static void launch_chain(rwr_graph *g, int tg, const double *X, double *Y, const
         constexpr size_t smem = 2 * CH3_CE * sizeof(double);
         // (per launch, not once per process: the attribute belongs to the current device, and one process may hold
         //  graphs on several devices)
-        (void)hipFuncSetAttribute((const void *)k_seed_chain_roles<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k_seed_chain_roles<G>, dim3(tg), dim3(WAVE + CH3_NST), smem, s, g->n, g->in_ptr.p,
-                           g->in_src.p, g->dangling.p, X, Y, seeds, c1, evoff, g->d_evterm.p, nz_out, gate);
+        bool_dispatch([&](auto m) {
+            constexpr bool MASK = decltype(m)::value && G >= 8;   // (frontier lists, hence stale rows, only at G >= 8)
+            (void)hipFuncSetAttribute((const void *)k_seed_chain_roles<G, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)smem);
+            hipLaunchKernelGGL((k_seed_chain_roles<G, MASK>), dim3(tg), dim3(WAVE + CH3_NST), smem, s, g->n, g->in_ptr.p,
+                               g->in_src.p, g->dangling.p, X, Y, seeds, c1, evoff, g->d_evterm.p, nz_out, gate, nz_x);
+        }, masked);
         return;
     }
     hipLaunchKernelGGL(k_seed_chain<G>, dim3(cdiv((size_t)tg * G, 64)), dim3(64), 0, s, g->n, tg, g->in_ptr.p,
@@ -967,13 +1000,17 @@ int32_t GroupIter::init(bool fresh, bool ranks_nonneg, bool ranking_only)
     in.scan_self = chain_scan_self_contained(G); in.G = G; in.tg = tg; in.c1 = c1;
     in.fresh = fresh; in.ranks_nonneg = ranks_nonneg; in.ranking_only = ranking_only;
     cfg = plan_config(in);
-    if (fresh) RWR_HIP(hipMemsetAsync(X, 0, elems * sizeof(double), s));
     if (!fresh && Zc) launch_make_z((int64_t)elems, G, X, Zc, g->w_src.p, c1, s);
     const size_t nzw = ((size_t)n + 31) / 32;
     if (cfg.flist && g->fl_rows.ensure((size_t)tg * (size_t)n + (size_t)tg) != RWR_OK) {
         (void)hipGetLastError();   // (no room for the lists: the bitmap-probing steps of before, which need none)
         cfg.flist = false;
+        cfg.clear_x = plan_clear_x(cfg);
     }
+    // X_0 is zero outside the seed rows.  On the frontier-list path every reader of steps 0 to 2 goes through the frontier
+    // bitmaps, so the seed rows (k_init_seeds) are all of X that must be valid: no clear
+    if (fresh && cfg.clear_x) RWR_HIP(hipMemsetAsync(X, 0, elems * sizeof(double), s));
+    if (fresh && !cfg.clear_x) g->stats.x_clear_skipped += 1;
     // Z is read only through the frontier bitmaps until a step has written it whole: on the frontier-list path the
     // seed rows (k_init_seeds) are all of it that must be valid
     if (fresh && Zc && !cfg.flist) RWR_HIP(hipMemsetAsync(Zc, 0, elems * sizeof(double), s));
@@ -1023,7 +1060,8 @@ int32_t GroupIter::step(const StepPlan &p, Profile &prof, int32_t row_first, int
             RWR_TRY(chain_scan_step(g, G, tg, X, Y, d_seeds, d_evoff, c1, nz_out, sc, p.chain_self ? Zc : nullptr,
                                     p.chain_self ? zout : nullptr));
         else
-            RWR_DISPATCH_G(G, launch_chain<GG>(g, tg, X, Y, d_seeds, c1, d_evoff, nz_out, gate_it, sc, p.chain, nz_in));
+            RWR_DISPATCH_G(G, launch_chain<GG>(g, tg, X, Y, d_seeds, c1, d_evoff, nz_out, gate_it, sc, p.chain, nz_in,
+                                                       p.chain_masked));
         RWR_TRY(prof.end(prof.chain, c0, sc));
         if (p.chain_side) RWR_HIP(hipEventRecord(g->ev_join, sc));
     }
@@ -1073,7 +1111,8 @@ int32_t iterate_group(rwr_graph *g, int G, int tg, const int32_t *d_seeds, const
                       double d, int64_t T, Profile &prof, double **final_X, int64_t *dense_steps, SplitLast *split)
 {
     GroupIter gi(g, G, tg, d_seeds, d_evoff, d);
-    RWR_TRY(gi.init(true, true, true));
+    // (a batch of no steps ranks X_0 itself: every row must be valid, so it takes the plan of a caller that reads the ranks)
+    RWR_TRY(gi.init(true, true, /*ranking_only=*/T >= 1));
     if (gi.cfg.tails) {
         RWR_TRY(tail_rows_prepare(g));
         gi.cfg.tail_depth = g->tail_depth;

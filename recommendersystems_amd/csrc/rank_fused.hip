@@ -274,27 +274,66 @@ __global__ __launch_bounds__(256) void k_sel_bound_rows(int tg, const int64_t *_
     if (lane == 0 && skipped) atomicAdd(pruned, skipped);
 }
 
-// the tiles' row lists from the keep bits: a wave takes 64 positions, counts the kept ones and reserves their places with one
-// integer atomicAdd; the order inside a list differs from run to run, the rows in it do not
-__global__ __launch_bounds__(256) void k_sel_bound_compact(const int32_t *__restrict__ rows, int32_t nrows,
-                                                           const uint32_t *__restrict__ keep, int32_t *__restrict__ list,
-                                                           int32_t *__restrict__ list_cnt)
+// the tiles' row lists from the keep bits, one pass over the keep words for all tiles of a block of BOUND_W.  A workgroup takes a
+// span of COMPACT_SPAN positions; a wave of it COMPACT_RPT runs of 64, so that every load is coalesced and the lanes' positions
+// ascend with (wave, run, lane).  Per tile the waves count their kept rows (ballots), one thread per tile reserves the
+// workgroup's places with ONE integer atomicAdd and deals them to the waves in order, and the waves write the row ids: inside a
+// workgroup's span a list keeps the rows' order in tail_rows[0] (in-degree-descending, which balances k_spmm_select's waves);
+// the order of the spans differs from run to run, the rows of a list do not.
+constexpr int COMPACT_RPT = 8, COMPACT_WAVES = 4, COMPACT_SPAN = COMPACT_WAVES * WAVE * COMPACT_RPT;
+__global__ __launch_bounds__(COMPACT_WAVES * WAVE) void k_sel_bound_compact(int tg, const int32_t *__restrict__ rows, int32_t nrows,
+                                                                            const uint32_t *__restrict__ keep,
+                                                                            int32_t *__restrict__ list, int32_t *__restrict__ list_cnt)
 {
-    const int tile = blockIdx.y;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const uint32_t *kw = keep + (size_t)(tile / BOUND_W) * (size_t)nrows;
-    int32_t *out = list + (size_t)tile * (size_t)nrows;
-    const int wpb = blockDim.x / WAVE;
-    const int64_t nwaves = (int64_t)gridDim.x * wpb;
-    for (int64_t b0 = ((int64_t)blockIdx.x * wpb + threadIdx.x / WAVE) * WAVE; b0 < nrows; b0 += nwaves * WAVE) {
-        const int64_t q = b0 + lane;
-        const bool kp = q < nrows && ((kw[q] >> (tile % BOUND_W)) & 1u);
-        const unsigned long long bal = __ballot(kp);
-        if (!bal) continue;
-        int32_t base = 0;
-        if (lane == 0) base = atomicAdd(&list_cnt[tile], (int32_t)__popcll(bal));
-        base = __shfl(base, 0);
-        if (kp) out[base + __popcll(bal & ((1ull << lane) - 1ull))] = rows[q];
+    static_assert(BOUND_W <= WAVE, "one lane per tile of the block");
+    __shared__ int32_t wcnt[COMPACT_WAVES][BOUND_W];   // kept rows per (wave, tile), then the wave's first place in the list
+    const int blk = blockIdx.y;
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    const uint32_t *kw = keep + (size_t)blk * (size_t)nrows;
+    const int64_t nspans = ((int64_t)nrows + COMPACT_SPAN - 1) / COMPACT_SPAN;
+    for (int64_t sp = blockIdx.x; sp < nspans; sp += gridDim.x) {
+        const int64_t q0 = sp * COMPACT_SPAN + (int64_t)wv * (WAVE * COMPACT_RPT) + lane;
+        uint32_t w[COMPACT_RPT];
+        int32_t id[COMPACT_RPT];
+#pragma unroll
+        for (int i = 0; i < COMPACT_RPT; ++i) {
+            const int64_t q = q0 + (int64_t)i * WAVE;
+            w[i] = q < nrows ? kw[q] : 0u;
+            id[i] = q < nrows ? rows[q] : 0;
+        }
+        int32_t mine = 0;   // lane t < BOUND_W: the wave's kept rows of tile t of the block
+        for (int t = 0; t < BOUND_W; ++t) {
+            int32_t c = 0;
+#pragma unroll
+            for (int i = 0; i < COMPACT_RPT; ++i) c += (int32_t)__popcll(__ballot((w[i] >> t) & 1u));
+            if (lane == t) mine = c;
+        }
+        if (lane < BOUND_W) wcnt[wv][lane] = mine;
+        __syncthreads();
+        if (threadIdx.x < BOUND_W) {
+            const int tile = blk * BOUND_W + (int)threadIdx.x;
+            int32_t c[COMPACT_WAVES], total = 0;
+#pragma unroll
+            for (int v = 0; v < COMPACT_WAVES; ++v) total += c[v] = wcnt[v][threadIdx.x];
+            int32_t at = (total && tile < tg) ? atomicAdd(&list_cnt[tile], total) : 0;   // (a tile past tg keeps no row)
+#pragma unroll
+            for (int v = 0; v < COMPACT_WAVES; ++v) { wcnt[v][threadIdx.x] = at; at += c[v]; }
+        }
+        __syncthreads();
+        for (int t = 0; t < BOUND_W; ++t) {
+            const int tile = blk * BOUND_W + t;
+            if (tile >= tg) break;
+            int32_t *out = list + (size_t)tile * (size_t)nrows;
+            int32_t at = wcnt[wv][t];
+#pragma unroll
+            for (int i = 0; i < COMPACT_RPT; ++i) {
+                const bool kp = (w[i] >> t) & 1u;
+                const unsigned long long bal = __ballot(kp);
+                if (kp) out[at + __popcll(bal & ((1ull << lane) - 1ull))] = id[i];
+                at += (int32_t)__popcll(bal);
+            }
+        }
+        __syncthreads();   // (wcnt is read until here)
     }
 }
 
@@ -349,9 +388,9 @@ static int32_t rank_bound_prepare(rwr_graph *g, int G, int tg, const int32_t *d_
     if (g->fl_rows.ensure((size_t)tg * (size_t)count) != RWR_OK) return give_up();
     int32_t *list_cnt = noprune + tg;
     RWR_HIP(hipMemsetAsync(list_cnt, 0, (size_t)tg * sizeof(int32_t), s));
-    const unsigned wc = cdiv((size_t)count, (size_t)WAVE * 4 * 4);
-    hipLaunchKernelGGL(k_sel_bound_compact, dim3(wc < 1u ? 1u : wc < 4096u ? wc : 4096u, (unsigned)tg), dim3(256), 0, s, rows, count,
-                       keep, g->fl_rows.p, list_cnt);
+    const size_t wc = cdiv((size_t)count, (size_t)COMPACT_SPAN);
+    hipLaunchKernelGGL(k_sel_bound_compact, dim3((unsigned)(wc < 65536 ? wc : 65536), (unsigned)nblk), dim3(COMPACT_WAVES * WAVE), 0,
+                       s, tg, rows, count, keep, g->fl_rows.p, list_cnt);
     RWR_HIP(hipGetLastError());
     sink->list = g->fl_rows.p, sink->list_cnt = list_cnt, sink->list_stride = count;
     *pruned = d_pruned;

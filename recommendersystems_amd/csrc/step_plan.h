@@ -9,9 +9,10 @@ namespace rwr {
 
 // What a group's plan depends on.  First the environment values (iterate.hip: plan_knobs; defaults: the shipped library's):
 // RWR_SPMM (0: plain kernel, no bitmaps), RWR_NZ_ITERS, RWR_ACT_ITERS (-1: by graph shape), RWR_ACT_MIN_N, RWR_FRONTIER_LIST,
-// RWR_CHAIN (0 simple, 1 auto, 2 scan, 3 role-specialised fold), RWR_SCAN_WORK, RWR_SCAN_SIDE, RWR_GATE, RWR_TAIL_ROWS.
+// RWR_CHAIN (0 simple, 1 auto, 2 scan, 3 role-specialised fold), RWR_SCAN_WORK, RWR_SCAN_SIDE, RWR_GATE, RWR_TAIL_ROWS,
+// RWR_X_CLEAR (1: clear X on every fresh batch).
 struct PlanInput {
-    int spmm = 1, nz_iters = 4, act_iters = -1, frontier_list = 1, chain = 1;
+    int spmm = 1, nz_iters = 4, act_iters = -1, frontier_list = 1, chain = 1, x_clear = 0;
     int64_t act_min_n = 200000; double scan_work = 10000.0;
     int scan_side = 1, gate = 1, tail_rows = 1;
     bool two_streams = true;      // a chain may run on the second stream (RWR_CHAIN_SERIAL=0)
@@ -39,7 +40,15 @@ struct PlanConfig {
     bool two_streams = true, gate = true;        // a fold runs on the second stream / the SpMM waits for its workgroups
     bool tails = false; int tail_depth = 0;   // the last steps may walk the tail row lists of this many levels (§3.3.1)
     unsigned need = 0;            // bit k: some seed of the group needs its chain at step T - 1 - k (the OR of h_tail_flag)
+    bool force_clear = false;     // RWR_X_CLEAR=1
+    bool clear_x = true;          // a fresh batch clears X before its seeds are written (plan_clear_x)
 };
+
+// Whether a fresh batch must clear X (§3.3.2).  A frontier-list step writes only its listed rows, and the chain of the step
+// after it may read every row (plan_step: chain_masked).  Without the clear the unlisted rows are stale, and that chain must
+// read through the bitmap the list step wrote: only the role-specialised fold has such a form.  The scan and the simple fold
+// keep the clear, and so does every group that never lists.  To be called again whenever flist changes.
+inline bool plan_clear_x(const PlanConfig &c) { return c.force_clear || !c.flist || c.scan || c.chain_kind == 0; }
 
 inline PlanConfig plan_config(const PlanInput &in)
 {
@@ -70,6 +79,8 @@ inline PlanConfig plan_config(const PlanInput &in)
     c.scan_side = in.scan_side != 0 && single && in.two_streams && in.n >= 100000;
     c.scan_self = in.scan_self, c.two_streams = in.two_streams, c.gate = in.gate != 0;
     c.tails = in.ranking_only && in.tail_rows != 0 && !single;   // (a single seed's SpMV walks every row)
+    c.force_clear = in.x_clear != 0;
+    c.clear_x = plan_clear_x(c);
     return c;
 }
 
@@ -86,6 +97,7 @@ struct StepPlan {
     bool mark = false;                        // k_mark_active marks the rows the step can reach (an act step)
     bool terms_nz = false;                    // k_seed_terms reads through the current bitmap (rows outside it may be stale)
     Chain chain = Chain::None;
+    bool chain_masked = false;                // the chain reads X through the current bitmap: rows outside it are stale (!clear_x)
     bool chain_side = false, gate = false;    // the chain runs on the second stream / the SpMM waits for it (k_gate)
     bool chain_self = false;                  // the scan gathers its terms from Z and forms the seed rows' next z
     bool form_z = false, seed_z = false;      // value-free path: the SpMM / k_seed_z forms the next z
@@ -103,6 +115,19 @@ inline int last_tail(const PlanConfig &c)
     return c.tails ? c.tail_depth - 1 : -1;
 }
 
+// Whether step `it` of T walks its tile's frontier list.  A frontier-list step writes only its frontier's rows of Y / Z.
+// Allowed where the next step reads the output only through the bitmap this step writes: it probes it and either is itself an
+// act step (bitmap-walking chain) or, at it = 1, writes over X_0, whose only non-zero rows -- the seed rows -- are listed: its
+// output is whole where X_0 was cleared, and is read through the bitmap where it was not (chain_masked).  Tail steps, the
+// last step and a run that may stop after any step never list.
+inline bool step_lists(const PlanConfig &c, int64_t it, int64_t T)
+{
+    const int64_t k = T - 1 - it;
+    if (!c.flist || T < 0 || it < 0 || k <= 0 || k <= last_tail(c)) return false;
+    const bool write_bits = it + 1 < c.nz_iters, mark = it < c.nz_iters && it < c.act_iters;
+    return mark && write_bits && (it + 1 < c.act_iters || it == 1);
+}
+
 // Step `it` of T (T < 0: a run whose end is not known in advance -- no step is the last and none walks a row list)
 inline StepPlan plan_step(const PlanConfig &c, int64_t it, int64_t T)
 {
@@ -113,19 +138,17 @@ inline StepPlan plan_step(const PlanConfig &c, int64_t it, int64_t T)
     p.write_bits = it + 1 < c.nz_iters;
     p.mark = p.probe && it < c.act_iters;
     p.terms_nz = c.flist && p.probe;
-    // A frontier-list step writes only its frontier's rows of Y / Z.  Allowed where the next step reads the output only through
-    // the bitmap this step writes: it probes it and either is itself an act step (bitmap-walking chain) or, at it = 1, writes
-    // over the cleared X_0, whose only non-zero rows -- the seed rows -- are listed, so that its output is whole for the chains
-    // that read every row.  Tail steps, the last step and a run that may stop after any step never list.
     if (tail)
         p.rows = {Rows::Tail, (int)k};
-    else if (c.flist && T >= 0 && !last && p.mark && p.write_bits && (it + 1 < c.act_iters || it == 1))
+    else if (step_lists(c, it, T))
         p.rows = {Rows::Frontier, 0};
     // (while X is sparse the bitmap-walking chain serves a whole tile at once; for a single seed the scan is cheaper)
     if (tail && !((c.need >> k) & 1u)) p.chain = Chain::None;
     else if (c.scan && (!p.mark || c.G == 1)) p.chain = c.scan_side ? Chain::ScanSide : Chain::Scan;
     else if (p.mark) p.chain = Chain::Sparse;
     else p.chain = c.chain_kind == 0 ? Chain::Simple : Chain::Roles;
+    // a chain that reads every row of a frontier-list step's output (the bitmap-walking one reads the listed rows only)
+    p.chain_masked = !c.clear_x && p.chain != Chain::None && p.chain != Chain::Sparse && step_lists(c, it - 1, T);
     const bool fold = p.chain != Chain::None && !p.scan();
     p.chain_side = p.chain == Chain::ScanSide || (fold && c.two_streams);
     p.gate = fold && c.two_streams && c.gate;
