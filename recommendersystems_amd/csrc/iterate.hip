@@ -26,6 +26,7 @@
 // steps for an entry point does NOT belong here -- the batched Recommendation is in recommend.hip, Model.run / deliverRanks
 // and the batch of Models in model.hip, the row-partitioned mode in partition.hip, the exclusion and ranking in rank.hip.
 #include "iterate.h"
+#include "spmm_chunk.h"
 
 #include <climits>
 #include <cstdlib>
@@ -106,6 +107,8 @@ __global__ __launch_bounds__(256) void k_spmm(int32_t n, const int64_t *__restri
 // to the whole group through the LDS crossbar (ds_bpermute), instead of G lanes loading the
 // same address per edge.  All G row gathers of a chunk are issued before the first add, so
 // each lane keeps up to G 8-byte gathers in flight; the adds then run in list order.
+// For G > 16 the load is wider than the gather depth: LW = min(G, 32) lanes load -- at 32 one whole 128-byte line of
+// in_src, cut by spmm_chunk.h so that each line is fetched once -- and the entries go out in LW / CH rounds of CH gathers.
 //
 // Frontier awareness for the first iterations (x starts as a single non-zero row per seed and stays
 // sparse for two or three steps): CHECK consults a per-tile bitmap "row of X has a non-zero" before a
@@ -133,6 +136,10 @@ __device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__re
     static_assert(G >= 8 && G <= 64, "chunked SpMM needs 8 <= G <= 64");
     static_assert(!SEL || (!CHECK && !WRITE), "the selecting form probes and writes no bitmap");
     constexpr int RPW = WAVE / G;
+    // entries per index load; CH = entries per gather round.  The weighted forms at G = 64 keep the 16-entry load: with two
+    // written-out rounds their probing forms need 98 and 102 instead of 96 and 100 SGPRs, one wave per SIMD fewer.
+    constexpr int LW = G <= 32 ? G : VF ? 32 : CH;
+    static_assert(LW % CH == 0 && CH <= LW, "an index load is a whole number of gather rounds");
     const int tile = blockIdx.y;
     const size_t toff = (size_t)tile * (size_t)n * G;
     X += toff;
@@ -168,8 +175,9 @@ __device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__re
         double acc = 0.0;
         // the wave iterates while ANY group still has entries; finished groups idle (cnt = 0)
         while (__any(p < e)) {
-            const int64_t left = e - p;
-            const int cnt = left > CH ? CH : (left > 0 ? (int)left : 0);
+            // one load of up to LW entries (spmm_chunk.h: a long list's loads start on 128-byte lines of in_src), then its
+            // gather rounds of CH entries each
+            const int cnt = spmm_next_load(p, e - p, LW);
             int32_t my_idx = 0;
             double my_w = 0.0;
             if (k < cnt) {
@@ -181,55 +189,64 @@ __device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__re
                 }
             }
             const int wlo = __double2loint(my_w), whi = __double2hiint(my_w);
+            unsigned long long um = 0;
             if (CHECK) {
-                // sparse frontier: entries whose source row is all-zero add +0.0 -- skip them wholesale.  `um` is
-                // the union over the wave's row groups of the chunk positions that are live in SOME group.
-                const unsigned long long lm = __ballot(k < cnt && my_idx >= 0);
-                unsigned long long um = lm;
+                // `um` is the union over the wave's row groups of the load's positions that are live in SOME group
+                um = __ballot(k < cnt && my_idx >= 0);
                 if (G < 64) {
 #pragma unroll
                     for (int sh = G; sh < 64; sh <<= 1) um |= um >> sh;
                     um &= (1ull << (G & 63)) - 1ull;
                 }
-                if (__popcll(um) <= 4) {
-                    while (um) {                                  // few live entries: take them one by one, in order
-                        const int t = __builtin_ctzll(um);
-                        um &= um - 1;
-                        const int idx = __builtin_amdgcn_ds_bpermute(gbase + (t << 2), my_idx);
-                        if (VF) {
-                            if (t < cnt && idx >= 0) acc += X[(size_t)idx * G + k];
-                        } else {
-                            const int lo = __builtin_amdgcn_ds_bpermute(gbase + (t << 2), wlo);
-                            const int hi = __builtin_amdgcn_ds_bpermute(gbase + (t << 2), whi);
-                            if (t < cnt && idx >= 0) {
-                                const double rw = c1 * X[(size_t)idx * G + k];   // Model.cs:84
-                                acc += rw * __hiloint2double(hi, lo);             // Model.cs:87
+            }
+            // the gather rounds of the load.  Rolled where lane groups share a wave: written out, the G = 32 kernels need 80
+            // instead of 56 registers.  Written out at G = 64: one group per wave, so every hand-out lane is then a constant
+            // (v_readlane, no LDS crossbar), as with 16-entry loads.
+#pragma unroll G == 64 ? LW / CH : 1
+            for (int r0 = 0; r0 < LW; r0 += CH) {
+                if (r0 > 0 && !__any(cnt > r0)) break;   // no group's load reaches this round
+                if (CHECK) {
+                    // sparse frontier: entries whose source row is all-zero add +0.0 -- skip them wholesale
+                    unsigned long long rm = (um >> r0) & ((1ull << CH) - 1ull);
+                    if (__popcll(rm) <= 4) {
+                        while (rm) {                                  // few live entries: take them one by one, in order
+                            const int t = r0 + __builtin_ctzll(rm);
+                            rm &= rm - 1;
+                            const int idx = __builtin_amdgcn_ds_bpermute(gbase + (t << 2), my_idx);
+                            if (VF) {
+                                if (t < cnt && idx >= 0) acc += X[(size_t)idx * G + k];
+                            } else {
+                                const int lo = __builtin_amdgcn_ds_bpermute(gbase + (t << 2), wlo);
+                                const int hi = __builtin_amdgcn_ds_bpermute(gbase + (t << 2), whi);
+                                if (t < cnt && idx >= 0) {
+                                    const double rw = c1 * X[(size_t)idx * G + k];   // Model.cs:84
+                                    acc += rw * __hiloint2double(hi, lo);             // Model.cs:87
+                                }
                             }
                         }
+                        continue;
                     }
-                    p += cnt;
-                    continue;
                 }
-            }
-            double xv[CH], wv[CH];
+                double xv[CH], wv[CH];
 #pragma unroll
-            for (int t = 0; t < CH; ++t) {
-                const int idx = __builtin_amdgcn_ds_bpermute(gbase + (t << 2), my_idx);
-                if (!VF) {
-                    const int lo = __builtin_amdgcn_ds_bpermute(gbase + (t << 2), wlo);
-                    const int hi = __builtin_amdgcn_ds_bpermute(gbase + (t << 2), whi);
-                    wv[t] = __hiloint2double(hi, lo);
+                for (int t = 0; t < CH; ++t) {
+                    const int idx = __builtin_amdgcn_ds_bpermute(gbase + ((r0 + t) << 2), my_idx);
+                    if (!VF) {
+                        const int lo = __builtin_amdgcn_ds_bpermute(gbase + ((r0 + t) << 2), wlo);
+                        const int hi = __builtin_amdgcn_ds_bpermute(gbase + ((r0 + t) << 2), whi);
+                        wv[t] = __hiloint2double(hi, lo);
+                    }
+                    xv[t] = (r0 + t < cnt && idx >= 0) ? X[(size_t)idx * G + k] : 0.0;
                 }
-                xv[t] = (t < cnt && idx >= 0) ? X[(size_t)idx * G + k] : 0.0;
-            }
 #pragma unroll
-            for (int t = 0; t < CH; ++t) {
-                if (t < cnt) {
-                    if (VF) {
-                        acc += xv[t];                // the source's z: fl(fl((1-d) x) * w), Model.cs:84,87
-                    } else {
-                        double rw = c1 * xv[t];      // Model.cs:84
-                        acc += rw * wv[t];           // Model.cs:87
+                for (int t = 0; t < CH; ++t) {
+                    if (r0 + t < cnt) {
+                        if (VF) {
+                            acc += xv[t];                // the source's z: fl(fl((1-d) x) * w), Model.cs:84,87
+                        } else {
+                            double rw = c1 * xv[t];      // Model.cs:84
+                            acc += rw * wv[t];           // Model.cs:87
+                        }
                     }
                 }
             }
