@@ -250,11 +250,7 @@ int32_t graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, cons
         RWR_HIP(hipStreamSynchronize(s));
         return RWR_OK;
     };
-    const int32_t merge_rc = merge();
-    if (merge_rc != RWR_OK) {
-        (void)hipStreamSynchronize(s);
-        return merge_rc;
-    }
+    RWR_TRY(idle_on_error(s, merge));
     AT("upload + merge kernels");
     // ---- phase 2: the handle takes the merged lists
     *swapped = true;

@@ -1,6 +1,7 @@
 // Device-resident graph and batch workspace (internal).
 #pragma once
 #include <cstdlib>
+#include <new>
 
 #include "common.h"
 
@@ -92,7 +93,7 @@ struct rwr_graph {
     rwr::DevBuf<int32_t> sm_tab;      // small.hip: places of the seed row's addends (per call)
     void *sm_pin = nullptr;           // small.hip: pinned host buffer the one-launch kernel writes the ranked list into
     void *sm_stage = nullptr;         // build.hip: pinned staging buffer of an ego-network-sized graph's upload / read-back
-    // a handle built as part of a batch (rwr_eval_graphs in api.hip; graphs_build_multi in build.hip, recommend_small_multi in
+    // a handle built as part of a batch (rwr_eval_graphs, eval_graphs.hip; graphs_build_multi in build.hip, recommend_small_multi in
     // small.hip): its staging slot and read-back area lie in the batch's pinned arena, the device-side landing area in the
     // batch's one buffer (one H2D copy for all graphs); none of them is owned by the handle
     uint8_t *sm_out = nullptr;
@@ -164,6 +165,32 @@ namespace rwr {
 
 double now_ms();   // recommend.hip: a steady clock, for the wall times of rwr_stats
 
+// scratch buffers of one call are released only after both streams are idle (also on error paths): declared after them
+struct StreamsIdle {
+    rwr_graph *g;
+    ~StreamsIdle() { (void)hipStreamSynchronize(g->stream); (void)hipStreamSynchronize(g->stream2); }
+};
+
+// ... and of a function that launches on one stream and ends in its own synchronisation: `body`, run with the scratch buffers
+// declared before it, may leave through RWR_HIP / RWR_TRY between a launch and that synchronisation; the stream is then drained
+// here, before the caller's scratch goes back to the block cache.  A body that returns RWR_OK costs nothing more.
+template <class F>
+int32_t idle_on_error(hipStream_t s, F &&body)
+{
+    const int32_t rc = body();
+    if (rc != RWR_OK) (void)hipStreamSynchronize(s);
+    return rc;
+}
+
+// no C++ exception crosses the C boundary
+template <class F>
+int32_t no_throw(const char *who, F &&body)
+{
+    try { return body(); }
+    catch (const std::bad_alloc &) { set_error("%s: host allocation failed", who); return RWR_E_NOMEM; }
+    catch (...) { set_error("%s: unexpected host exception", who); return RWR_E_HIP; }
+}
+
 // Node count from which a graph counts as "beyond the L2s" (its rank vector no longer fits them): two-phase row order of
 // the single-seed SpMV, one more frontier iteration, 32-seed tiles.
 // RWR_BIG_N overrides the default of 2 M so that small test graphs can reach the same code paths.
@@ -199,6 +226,10 @@ int32_t recommend_small_multi(rwr_graph **gs, const int32_t *seeds, int32_t coun
                               rwr::DevBuf<uint8_t> &args_keep);
 int32_t eval_ranked_multi(rwr_graph **gs, int32_t count, const int64_t *test_ptr_host, const int64_t *test_sorted_host,
                           int64_t *n_hits, double *sum_precision, int64_t *list_len, hipStream_t s);
+// eval_graphs.hip: the driver of rwr_eval_graphs over the three above (arguments as checked, outputs as zeroed by the entry point)
+int32_t eval_graphs(int32_t count, const rwr_graph_desc *graphs, const int32_t *seeds, float d, int32_t n_iter,
+                    const int64_t *test_ptr, const int64_t *test_ids, const rwr_opts *opts, int64_t *n_hits,
+                    double *sum_precision, int64_t *list_len);
 
 // recommend.hip: runs the power iteration for K seeds and leaves, per seed, the ranked list
 // (mode 0: top-k into host arrays; mode 1: full rank vector of one seed)
@@ -230,7 +261,7 @@ int32_t model_run_restart(rwr_graph *g, const double *v, const double *rank_in, 
                           double *rank_out, int64_t *iters_out);
 int32_t model_deliver_restart(rwr_graph *g, const double *v, double d, const double *rank_in, double *next_out);
 // restart_batch.hip: K Models with caller-set restart vectors in one call (rwr_model_run_restart_batch).  The
-// vectors arrive as validated CSR (api.hip: indices in range and distinct, values finite, start in [-1, n) or NULL)
+// vectors arrive as validated CSR (api.hip, check_restart_vectors: indices in range and distinct, values finite, start in [-1, n) or NULL)
 int32_t model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
                                 const int32_t *start, double d, int32_t run_mode, double value, double *rank_out,
                                 int64_t *iters_out);

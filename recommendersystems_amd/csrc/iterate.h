@@ -128,21 +128,6 @@ int32_t upload_seed_slots(rwr_graph *g, const int32_t *seeds, int32_t K, int G, 
                           std::vector<int32_t> *slot_seed_out = nullptr);
 
 // ---- the run loop of the Model drivers (model.hip, restart.hip, restart_batch.hip) ----------------------------------------
-// scratch buffers of one call are released only after both streams are idle (also on error paths): declared after them
-struct StreamsIdle {
-    rwr_graph *g;
-    ~StreamsIdle() { (void)hipStreamSynchronize(g->stream); (void)hipStreamSynchronize(g->stream2); }
-};
-
-// no C++ exception crosses the C boundary
-template <class F>
-int32_t no_throw(const char *who, F &&body)
-{
-    try { return body(); }
-    catch (const std::bad_alloc &) { set_error("%s: host allocation failed", who); return RWR_E_NOMEM; }
-    catch (...) { set_error("%s: unexpected host exception", who); return RWR_E_HIP; }
-}
-
 // Model.run of one walk (Model.cs:52-66): step() = deliverRanks + updateRanks, converge(&dist) = checkConvergence read
 // back.  *done receives the steps made; a threshold run that is not below its threshold after end.T steps fails.
 template <class Step, class Converge>

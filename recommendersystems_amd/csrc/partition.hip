@@ -183,25 +183,27 @@ int32_t part_rank(rwr_graph *g, double *x, int32_t top_n, int64_t *ids, double *
         if (g->part_seeds[k] >= g->part_lo && g->part_seeds[k] < g->part_hi) { own[k] = g->part_seeds[k]; slot_k[k] = k; }
     DevBuf<int32_t> d_own;
     RWR_TRY(d_own.alloc(G));
-    RWR_TRY(g->d_slot_k.ensure(G));
-    RWR_HIP(hipMemcpy(d_own.p, own.data(), G * sizeof(int32_t), hipMemcpyHostToDevice));
-    RWR_HIP(hipMemcpy(g->d_slot_k.p, slot_k.data(), G * sizeof(int32_t), hipMemcpyHostToDevice));
-    const size_t out_elems = (size_t)G * top_n;
-    RWR_TRY(g->d_out_id.ensure(out_elems));
-    RWR_TRY(g->d_out_score.ensure(out_elems));
-    RWR_TRY(g->d_counts.ensure(G));
-    RWR_HIP(hipMemsetAsync(g->d_out_id.p, 0, out_elems * sizeof(int64_t), s));
-    RWR_HIP(hipMemsetAsync(g->d_out_score.p, 0, out_elems * sizeof(double), s));
-    RWR_HIP(hipMemsetAsync(g->d_counts.p, 0, G * sizeof(int32_t), s));
-    launch_exclude(g, G, 1, x, d_own.p, s);
-    RWR_TRY(rank_group_select(g, G, 1, g->d_slot_k.p, top_n, x, d_own.p, s));
-    std::vector<int32_t> hc((size_t)G);
-    RWR_HIP(hipMemcpyAsync(hc.data(), g->d_counts.p, G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    RWR_HIP(hipMemcpyAsync(ids, g->d_out_id.p, (size_t)K * top_n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    RWR_HIP(hipMemcpyAsync(scores, g->d_out_score.p, (size_t)K * top_n * sizeof(double), hipMemcpyDeviceToHost, s));
-    RWR_HIP(hipStreamSynchronize(s));
-    for (int k = 0; k < K; ++k) counts[k] = own[k] >= 0 ? hc[k] : -1;
-    return RWR_OK;
+    return idle_on_error(s, [&]() -> int32_t {
+        RWR_TRY(g->d_slot_k.ensure(G));
+        RWR_HIP(hipMemcpy(d_own.p, own.data(), G * sizeof(int32_t), hipMemcpyHostToDevice));
+        RWR_HIP(hipMemcpy(g->d_slot_k.p, slot_k.data(), G * sizeof(int32_t), hipMemcpyHostToDevice));
+        const size_t out_elems = (size_t)G * top_n;
+        RWR_TRY(g->d_out_id.ensure(out_elems));
+        RWR_TRY(g->d_out_score.ensure(out_elems));
+        RWR_TRY(g->d_counts.ensure(G));
+        RWR_HIP(hipMemsetAsync(g->d_out_id.p, 0, out_elems * sizeof(int64_t), s));
+        RWR_HIP(hipMemsetAsync(g->d_out_score.p, 0, out_elems * sizeof(double), s));
+        RWR_HIP(hipMemsetAsync(g->d_counts.p, 0, G * sizeof(int32_t), s));
+        launch_exclude(g, G, 1, x, d_own.p, s);
+        RWR_TRY(rank_group_select(g, G, 1, g->d_slot_k.p, top_n, x, d_own.p, s));
+        std::vector<int32_t> hc((size_t)G);
+        RWR_HIP(hipMemcpyAsync(hc.data(), g->d_counts.p, G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        RWR_HIP(hipMemcpyAsync(ids, g->d_out_id.p, (size_t)K * top_n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        RWR_HIP(hipMemcpyAsync(scores, g->d_out_score.p, (size_t)K * top_n * sizeof(double), hipMemcpyDeviceToHost, s));
+        RWR_HIP(hipStreamSynchronize(s));
+        for (int k = 0; k < K; ++k) counts[k] = own[k] >= 0 ? hc[k] : -1;
+        return RWR_OK;
+    });
 }
 
 }  // namespace rwr

@@ -650,36 +650,38 @@ int32_t eval_ranked(rwr_graph *g, int32_t cnt, const int64_t *test_sorted_host, 
     RWR_TRY(d_terms.alloc((size_t)n_test));
     RWR_TRY(d_hits.alloc(1));
     RWR_TRY(d_sum.alloc(1));
-    // The test set and the two results cross through the handle's pinned buffer when it exists and they fit (an ego network's
-    // fold: a few dozen ids): a copy from / to pageable memory is staged by the runtime under a process-wide lock and waits for
-    // the device -- with the harness's ten threads (Program.cs:11) those copies, not the kernels, set the rate (8 K graphs/s
-    // whatever the thread count).  The buffer holds the ranked list of the call that has just ended (small.hip), which this
-    // entry point does not return: its score half is free.
-    int64_t *pin = (g->sm_pin && n_test + 4 <= small_pin_words()) ? reinterpret_cast<int64_t *>(small_pin_scratch(g)) : nullptr;
-    if (pin) {
-        if (n_test > 0) memcpy(pin, test_sorted_host, sizeof(int64_t) * (size_t)n_test);
-        if (n_test > 0) RWR_HIP(hipMemcpyAsync(d_test.p, pin, sizeof(int64_t) * (size_t)n_test, hipMemcpyHostToDevice, s));
-    } else if (n_test > 0) {
-        RWR_HIP(hipMemcpyAsync(d_test.p, test_sorted_host, sizeof(int64_t) * (size_t)n_test, hipMemcpyHostToDevice, s));
-    }
-    hipLaunchKernelGGL(k_eval_ranked, dim3(1), dim3(1024), 0, s, g->d_out_id.p, cnt, d_test.p, (int32_t)n_test, d_terms.p,
-                       d_hits.p, d_sum.p);
-    RWR_HIP(hipGetLastError());
-    if (pin) {
-        int64_t *o_hits = pin + n_test;
-        double *o_sum = reinterpret_cast<double *>(pin + n_test + 1);
-        RWR_HIP(hipMemcpyAsync(o_hits, d_hits.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        RWR_HIP(hipMemcpyAsync(o_sum, d_sum.p, sizeof(double), hipMemcpyDeviceToHost, s));
+    return idle_on_error(s, [&]() -> int32_t {
+        // The test set and the two results cross through the handle's pinned buffer when it exists and they fit (an ego network's
+        // fold: a few dozen ids): a copy from / to pageable memory is staged by the runtime under a process-wide lock and waits for
+        // the device -- with the harness's ten threads (Program.cs:11) those copies, not the kernels, set the rate (8 K graphs/s
+        // whatever the thread count).  The buffer holds the ranked list of the call that has just ended (small.hip), which this
+        // entry point does not return: its score half is free.
+        int64_t *pin = (g->sm_pin && n_test + 4 <= small_pin_words()) ? reinterpret_cast<int64_t *>(small_pin_scratch(g)) : nullptr;
+        if (pin) {
+            if (n_test > 0) memcpy(pin, test_sorted_host, sizeof(int64_t) * (size_t)n_test);
+            if (n_test > 0) RWR_HIP(hipMemcpyAsync(d_test.p, pin, sizeof(int64_t) * (size_t)n_test, hipMemcpyHostToDevice, s));
+        } else if (n_test > 0) {
+            RWR_HIP(hipMemcpyAsync(d_test.p, test_sorted_host, sizeof(int64_t) * (size_t)n_test, hipMemcpyHostToDevice, s));
+        }
+        hipLaunchKernelGGL(k_eval_ranked, dim3(1), dim3(1024), 0, s, g->d_out_id.p, cnt, d_test.p, (int32_t)n_test, d_terms.p,
+                           d_hits.p, d_sum.p);
+        RWR_HIP(hipGetLastError());
+        if (pin) {
+            int64_t *o_hits = pin + n_test;
+            double *o_sum = reinterpret_cast<double *>(pin + n_test + 1);
+            RWR_HIP(hipMemcpyAsync(o_hits, d_hits.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            RWR_HIP(hipMemcpyAsync(o_sum, d_sum.p, sizeof(double), hipMemcpyDeviceToHost, s));
+            RWR_HIP(hipStreamSynchronize(s));
+            *n_hits = *o_hits;
+            *sum_precision = *o_sum;
+            g->sm_pin_count = -1;                                  // (the list's score half is gone)
+            return RWR_OK;
+        }
+        RWR_HIP(hipMemcpyAsync(n_hits, d_hits.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        RWR_HIP(hipMemcpyAsync(sum_precision, d_sum.p, sizeof(double), hipMemcpyDeviceToHost, s));
         RWR_HIP(hipStreamSynchronize(s));
-        *n_hits = *o_hits;
-        *sum_precision = *o_sum;
-        g->sm_pin_count = -1;                                  // (the list's score half is gone)
         return RWR_OK;
-    }
-    RWR_HIP(hipMemcpyAsync(n_hits, d_hits.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    RWR_HIP(hipMemcpyAsync(sum_precision, d_sum.p, sizeof(double), hipMemcpyDeviceToHost, s));
-    RWR_HIP(hipStreamSynchronize(s));
-    return RWR_OK;
+    });
 }
 
 // K ranked lists (rows of d_out_id, `row_stride` apart, lengths in d_counts) against K test sets given in CSR form, each
@@ -696,15 +698,17 @@ int32_t eval_ranked_batch(rwr_graph *g, int32_t K, int64_t row_stride, const int
     RWR_TRY(d_ptr.alloc((size_t)K + 1));
     RWR_TRY(d_hits.alloc((size_t)K));
     RWR_TRY(d_sum.alloc((size_t)K));
-    if (total > 0) RWR_HIP(hipMemcpyAsync(d_test.p, test_sorted_host, sizeof(int64_t) * (size_t)total, hipMemcpyHostToDevice, s));
-    RWR_HIP(hipMemcpyAsync(d_ptr.p, test_ptr_host, sizeof(int64_t) * ((size_t)K + 1), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_eval_ranked_batch, dim3((unsigned)K), dim3(1024), 0, s, g->d_out_id.p, row_stride, g->d_counts.p, d_test.p,
-                       d_ptr.p, d_terms.p, d_hits.p, d_sum.p);
-    RWR_HIP(hipGetLastError());
-    RWR_HIP(hipMemcpyAsync(n_hits, d_hits.p, sizeof(int64_t) * (size_t)K, hipMemcpyDeviceToHost, s));
-    RWR_HIP(hipMemcpyAsync(sum_precision, d_sum.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, s));
-    RWR_HIP(hipStreamSynchronize(s));
-    return RWR_OK;
+    return idle_on_error(s, [&]() -> int32_t {
+        if (total > 0) RWR_HIP(hipMemcpyAsync(d_test.p, test_sorted_host, sizeof(int64_t) * (size_t)total, hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_ptr.p, test_ptr_host, sizeof(int64_t) * ((size_t)K + 1), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_eval_ranked_batch, dim3((unsigned)K), dim3(1024), 0, s, g->d_out_id.p, row_stride, g->d_counts.p, d_test.p,
+                           d_ptr.p, d_terms.p, d_hits.p, d_sum.p);
+        RWR_HIP(hipGetLastError());
+        RWR_HIP(hipMemcpyAsync(n_hits, d_hits.p, sizeof(int64_t) * (size_t)K, hipMemcpyDeviceToHost, s));
+        RWR_HIP(hipMemcpyAsync(sum_precision, d_sum.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, s));
+        RWR_HIP(hipStreamSynchronize(s));
+        return RWR_OK;
+    });
 }
 
 // one block per GRAPH of a batch (rwr_eval_graphs): each graph's own ranked list against its test set
@@ -743,34 +747,36 @@ int32_t eval_ranked_multi(rwr_graph **gs, int32_t count, const int64_t *test_ptr
     RWR_TRY(d_sum.alloc((size_t)count));
     RWR_TRY(d_len.alloc((size_t)count));
     RWR_TRY(d_args.alloc((size_t)count));
-    // every table goes through the thread's pinned buffers (build.hip: multi_pinned): [args][ptr][test ids] in, [hits][sums][len] out
-    const size_t b_args = sizeof(EvalMultiArgs) * (size_t)count, b_ptr = 8 * ((size_t)count + 1), b_test = 8 * (size_t)total;
-    void *in_v = nullptr, *out_v = nullptr;
-    RWR_TRY(multi_pinned(3, b_args + b_ptr + b_test + 64, &in_v));
-    RWR_TRY(multi_pinned(4, (size_t)count * 24 + 64, &out_v));
-    EvalMultiArgs *h = static_cast<EvalMultiArgs *>(in_v);
-    int64_t *h_ptr = reinterpret_cast<int64_t *>(static_cast<uint8_t *>(in_v) + b_args);
-    int64_t *h_test = h_ptr + count + 1;
-    int64_t *o_hits = static_cast<int64_t *>(out_v);
-    double *o_sum = reinterpret_cast<double *>(o_hits + count);
-    int32_t *h_len = reinterpret_cast<int32_t *>(o_sum + count);
-    for (int32_t i = 0; i < count; ++i) { h[i].ranked = gs[i]->d_out_id.p; h[i].count = gs[i]->d_counts.p; }
-    memcpy(h_ptr, test_ptr_host, b_ptr);
-    if (total > 0) memcpy(h_test, test_sorted_host, b_test);
-    if (total > 0) RWR_HIP(hipMemcpyAsync(d_test.p, h_test, b_test, hipMemcpyHostToDevice, s));
-    RWR_HIP(hipMemcpyAsync(d_ptr.p, h_ptr, b_ptr, hipMemcpyHostToDevice, s));
-    RWR_HIP(hipMemcpyAsync(d_args.p, h, b_args, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_eval_ranked_multi, dim3((unsigned)count), dim3(1024), 0, s, d_args.p, d_test.p, d_ptr.p, d_terms.p, d_hits.p,
-                       d_sum.p, d_len.p);
-    RWR_HIP(hipGetLastError());
-    RWR_HIP(hipMemcpyAsync(o_hits, d_hits.p, sizeof(int64_t) * (size_t)count, hipMemcpyDeviceToHost, s));
-    RWR_HIP(hipMemcpyAsync(o_sum, d_sum.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s));
-    RWR_HIP(hipMemcpyAsync(h_len, d_len.p, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, s));
-    RWR_HIP(hipStreamSynchronize(s));
-    memcpy(n_hits, o_hits, sizeof(int64_t) * (size_t)count);
-    memcpy(sum_precision, o_sum, sizeof(double) * (size_t)count);
-    if (list_len) for (int32_t i = 0; i < count; ++i) list_len[i] = h_len[i];
-    return RWR_OK;
+    return idle_on_error(s, [&]() -> int32_t {
+        // every table goes through the thread's pinned buffers (build.hip: multi_pinned): [args][ptr][test ids] in, [hits][sums][len] out
+        const size_t b_args = sizeof(EvalMultiArgs) * (size_t)count, b_ptr = 8 * ((size_t)count + 1), b_test = 8 * (size_t)total;
+        void *in_v = nullptr, *out_v = nullptr;
+        RWR_TRY(multi_pinned(3, b_args + b_ptr + b_test + 64, &in_v));
+        RWR_TRY(multi_pinned(4, (size_t)count * 24 + 64, &out_v));
+        EvalMultiArgs *h = static_cast<EvalMultiArgs *>(in_v);
+        int64_t *h_ptr = reinterpret_cast<int64_t *>(static_cast<uint8_t *>(in_v) + b_args);
+        int64_t *h_test = h_ptr + count + 1;
+        int64_t *o_hits = static_cast<int64_t *>(out_v);
+        double *o_sum = reinterpret_cast<double *>(o_hits + count);
+        int32_t *h_len = reinterpret_cast<int32_t *>(o_sum + count);
+        for (int32_t i = 0; i < count; ++i) { h[i].ranked = gs[i]->d_out_id.p; h[i].count = gs[i]->d_counts.p; }
+        memcpy(h_ptr, test_ptr_host, b_ptr);
+        if (total > 0) memcpy(h_test, test_sorted_host, b_test);
+        if (total > 0) RWR_HIP(hipMemcpyAsync(d_test.p, h_test, b_test, hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_ptr.p, h_ptr, b_ptr, hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_args.p, h, b_args, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_eval_ranked_multi, dim3((unsigned)count), dim3(1024), 0, s, d_args.p, d_test.p, d_ptr.p, d_terms.p, d_hits.p,
+                           d_sum.p, d_len.p);
+        RWR_HIP(hipGetLastError());
+        RWR_HIP(hipMemcpyAsync(o_hits, d_hits.p, sizeof(int64_t) * (size_t)count, hipMemcpyDeviceToHost, s));
+        RWR_HIP(hipMemcpyAsync(o_sum, d_sum.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s));
+        RWR_HIP(hipMemcpyAsync(h_len, d_len.p, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, s));
+        RWR_HIP(hipStreamSynchronize(s));
+        memcpy(n_hits, o_hits, sizeof(int64_t) * (size_t)count);
+        memcpy(sum_precision, o_sum, sizeof(double) * (size_t)count);
+        if (list_len) for (int32_t i = 0; i < count; ++i) list_len[i] = h_len[i];
+        return RWR_OK;
+    });
 }
 
 // A seed without explicit out-links is dangling (Graph.cs:64,86): all of its rank mass returns to it every iteration
@@ -820,18 +826,20 @@ int32_t emit_dangling(rwr_graph *g, const std::vector<int32_t> &rows, const std:
     DevBuf<int32_t> d_rows, d_seed;
     RWR_TRY(d_rows.alloc(n_d));
     RWR_TRY(d_seed.alloc(n_d));
-    RWR_HIP(hipMemcpyAsync(d_rows.p, rows.data(), n_d * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    RWR_HIP(hipMemcpyAsync(d_seed.p, seeds.data(), n_d * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    const int32_t cnt = top_n < g->n_items ? top_n : g->n_items;
-    for (int d0 = 0; d0 < n_d; d0 += 65535) {
-        const int nd = n_d - d0 < 65535 ? n_d - d0 : 65535;
-        hipLaunchKernelGGL(k_emit_dangling, dim3(cdiv((size_t)cnt, 256), nd), dim3(256), 0, s, nd, d_rows.p + d0,
-                           d_seed.p + d0, g->n, g->n_items, top_n, g->item_order.p, g->node_id.p, g->node_type.p,
-                           g->d_out_id.p, g->d_out_score.p, g->d_counts.p);
-    }
-    RWR_HIP(hipGetLastError());
-    RWR_HIP(hipStreamSynchronize(s));   // d_rows / d_seed are released on return
-    return RWR_OK;
+    return idle_on_error(s, [&]() -> int32_t {
+        RWR_HIP(hipMemcpyAsync(d_rows.p, rows.data(), n_d * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RWR_HIP(hipMemcpyAsync(d_seed.p, seeds.data(), n_d * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        const int32_t cnt = top_n < g->n_items ? top_n : g->n_items;
+        for (int d0 = 0; d0 < n_d; d0 += 65535) {
+            const int nd = n_d - d0 < 65535 ? n_d - d0 : 65535;
+            hipLaunchKernelGGL(k_emit_dangling, dim3(cdiv((size_t)cnt, 256), nd), dim3(256), 0, s, nd, d_rows.p + d0,
+                               d_seed.p + d0, g->n, g->n_items, top_n, g->item_order.p, g->node_id.p, g->node_type.p,
+                               g->d_out_id.p, g->d_out_score.p, g->d_counts.p);
+        }
+        RWR_HIP(hipGetLastError());
+        RWR_HIP(hipStreamSynchronize(s));   // d_rows / d_seed are released on return
+        return RWR_OK;
+    });
 }
 
 int rank_select_max_k() { return SEL_MAX_K; }

@@ -436,45 +436,47 @@ int32_t sweep_prepare(rwr_graph *g)
     RWR_TRY(tot.alloc(nw));
     RWR_TRY(base.alloc(nw));
     RWR_TRY(total.alloc(1));
-    RWR_TRY(g->sw_meta.ensure((size_t)nw * B));
-    RWR_TRY(g->sw_wgblk.ensure((size_t)nwg * (B + 1)));
-    const int32_t *order = g->sw_order.p;
-    hipLaunchKernelGGL(k_sw_count, dim3(cdiv((size_t)ns, 4)), dim3(256), 0, s, n_sw, ns, B, BN, order, g->in_ptr.p, g->in_src.p, scnt.p);
-    hipLaunchKernelGGL(k_sw_wave_prefix, dim3(cdiv((size_t)nw, 256)), dim3(256), 0, s, nw, nwg, wpg, K, ns, B, scnt.p, woff.p, tot.p);
-    hipLaunchKernelGGL(k_sw_scan, dim3(1), dim3(1024), 0, s, nw, tot.p, base.p, total.p);
-    hipLaunchKernelGGL(k_sw_meta, dim3(cdiv((size_t)nw * B, 256)), dim3(256), 0, s, nw, nwg, wpg, K, ns, B, scnt.p, woff.p, base.p,
-                       tot.p, g->sw_meta.p);
-    hipLaunchKernelGGL(k_sw_wglist, dim3(cdiv((size_t)nwg, 64)), dim3(64), 0, s, nwg, wpg, K, ns, B, scnt.p, g->sw_wgblk.p);
-    RWR_HIP(hipGetLastError());
-    unsigned long long h_total = 0;
-    std::vector<uint32_t> h_flags;
-    RWR_HIP(hipMemcpyAsync(&h_total, total.p, sizeof(h_total), hipMemcpyDeviceToHost, s));
-    if (partial) {
-        h_flags.resize((size_t)nwg * (B + 1));
-        RWR_HIP(hipMemcpyAsync(h_flags.data(), g->sw_wgblk.p, h_flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    }
-    RWR_HIP(hipStreamSynchronize(s));
-    if (h_total >= 0xFFFFFFFFull) return RWR_OK;            // word-row offsets are 32-bit
-    if (partial) {
-        // worth it only while the ITEM rows read few blocks (each refill costs every workgroup ~2.5 us)
-        size_t refills = 0;
-        for (int w = 0; w < nwg; ++w) refills += h_flags[(size_t)w * (B + 1)];
-        if (refills > (size_t)16 * nwg) return RWR_OK;
-    }
-    RWR_TRY(g->sw_ent.ensure((size_t)h_total * WAVE + WAVE));
-    hipLaunchKernelGGL(k_sw_fill, dim3(cdiv((size_t)ns, 4)), dim3(256), 0, s, n_sw, ns, nwg, wpg, B, BN, order, g->in_ptr.p, g->in_src.p,
-                       g->sw_meta.p, g->sw_ent.p);
-    RWR_HIP(hipGetLastError());
-    RWR_HIP(hipStreamSynchronize(s));
-    g->sw_B = B; g->sw_BN = BN; g->sw_K = K; g->sw_nwg = nwg; g->sw_wpg = wpg; g->sw_hub0 = hub0;
-    g->sw_rows = n_sw; g->sw_partial = partial;
-    g->sw_words = (int64_t)h_total * WAVE;
-    g->sw_state = 1;
+    return idle_on_error(s, [&]() -> int32_t {
+        RWR_TRY(g->sw_meta.ensure((size_t)nw * B));
+        RWR_TRY(g->sw_wgblk.ensure((size_t)nwg * (B + 1)));
+        const int32_t *order = g->sw_order.p;
+        hipLaunchKernelGGL(k_sw_count, dim3(cdiv((size_t)ns, 4)), dim3(256), 0, s, n_sw, ns, B, BN, order, g->in_ptr.p, g->in_src.p, scnt.p);
+        hipLaunchKernelGGL(k_sw_wave_prefix, dim3(cdiv((size_t)nw, 256)), dim3(256), 0, s, nw, nwg, wpg, K, ns, B, scnt.p, woff.p, tot.p);
+        hipLaunchKernelGGL(k_sw_scan, dim3(1), dim3(1024), 0, s, nw, tot.p, base.p, total.p);
+        hipLaunchKernelGGL(k_sw_meta, dim3(cdiv((size_t)nw * B, 256)), dim3(256), 0, s, nw, nwg, wpg, K, ns, B, scnt.p, woff.p, base.p,
+                           tot.p, g->sw_meta.p);
+        hipLaunchKernelGGL(k_sw_wglist, dim3(cdiv((size_t)nwg, 64)), dim3(64), 0, s, nwg, wpg, K, ns, B, scnt.p, g->sw_wgblk.p);
+        RWR_HIP(hipGetLastError());
+        unsigned long long h_total = 0;
+        std::vector<uint32_t> h_flags;
+        RWR_HIP(hipMemcpyAsync(&h_total, total.p, sizeof(h_total), hipMemcpyDeviceToHost, s));
+        if (partial) {
+            h_flags.resize((size_t)nwg * (B + 1));
+            RWR_HIP(hipMemcpyAsync(h_flags.data(), g->sw_wgblk.p, h_flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        }
+        RWR_HIP(hipStreamSynchronize(s));
+        if (h_total >= 0xFFFFFFFFull) return RWR_OK;            // word-row offsets are 32-bit
+        if (partial) {
+            // worth it only while the ITEM rows read few blocks (each refill costs every workgroup ~2.5 us)
+            size_t refills = 0;
+            for (int w = 0; w < nwg; ++w) refills += h_flags[(size_t)w * (B + 1)];
+            if (refills > (size_t)16 * nwg) return RWR_OK;
+        }
+        RWR_TRY(g->sw_ent.ensure((size_t)h_total * WAVE + WAVE));
+        hipLaunchKernelGGL(k_sw_fill, dim3(cdiv((size_t)ns, 4)), dim3(256), 0, s, n_sw, ns, nwg, wpg, B, BN, order, g->in_ptr.p, g->in_src.p,
+                           g->sw_meta.p, g->sw_ent.p);
+        RWR_HIP(hipGetLastError());
+        RWR_HIP(hipStreamSynchronize(s));
+        g->sw_B = B; g->sw_BN = BN; g->sw_K = K; g->sw_nwg = nwg; g->sw_wpg = wpg; g->sw_hub0 = hub0;
+        g->sw_rows = n_sw; g->sw_partial = partial;
+        g->sw_words = (int64_t)h_total * WAVE;
+        g->sw_state = 1;
 #ifdef RWR_EXPERIMENTS
-    fprintf(stderr, "[sweep] n %d hubs %d rows %d%s slots %d K %d blocks %d (BN %d) compute waves %d x %d words %lld (%.1f MB) nnz %lld\n", g->n, hub0,
-            n_sw, partial ? " (ITEM rows only)" : "", ns, K, B, BN, nwg, wpg, (long long)g->sw_words, g->sw_words * 8 / 1e6, (long long)g->nnz);
+        fprintf(stderr, "[sweep] n %d hubs %d rows %d%s slots %d K %d blocks %d (BN %d) compute waves %d x %d words %lld (%.1f MB) nnz %lld\n", g->n, hub0,
+                n_sw, partial ? " (ITEM rows only)" : "", ns, K, B, BN, nwg, wpg, (long long)g->sw_words, g->sw_words * 8 / 1e6, (long long)g->nnz);
 #endif
-    return RWR_OK;
+        return RWR_OK;
+    });
 }
 
 bool sweep_ready(const rwr_graph *g) { return g->sw_state == 1; }
