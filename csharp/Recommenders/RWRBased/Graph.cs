@@ -18,6 +18,9 @@ namespace Recommenders.RWRBased {
         internal GraphHandle handle;
         long[] rowptr; int[] dst; byte[] etype;
         long[] sentId; byte[] sentType; double[] sentW;   // what the device currently holds (for incremental rebuilds)
+        bool sentInOrder;   // the node dictionary enumerated its keys as 0, 1, ..., n-1 when that record was taken
+        // buildGraph() calls (all instances) that went through rwr_graph_append_nodes: nodes added at the end, lists that only grew
+        public static long NodeAppendRebuilds = 0;
 
         public Graph(Dictionary<int, Node> nodes, Dictionary<int, List<ForwardLink>> edges) {
             this.nodes = nodes;
@@ -59,11 +62,28 @@ namespace Recommenders.RWRBased {
                         asrc.Add(i); adst.Add(dst[p]); at.Add(etype[p]); aw.Add(w[p]);
                     }
                 Native.Check(Native.rwr_graph_append_links(handle, asrc.Count, asrc.ToArray(), adst.ToArray(), at.ToArray(), aw.ToArray(), null));
+            } else if (handle != null && !handle.IsInvalid && sentW != null && sentInOrder && KeysInOrder() &&
+                       GrownNodes(id, type, prevRowptr, prevDst, prevEtype, w)) {
+                // the node dictionary only gained keys at its end (old nodes unchanged and in the same order, the new keys
+                // continuing the index sequence), every old list a bitwise prefix of the new one => send only the new nodes
+                // and the new links (rwr_graph_append_nodes); the lists of the new nodes start empty
+                int nOld = sentId.Length;
+                var nid = new long[n - nOld]; var nty = new byte[n - nOld];
+                for (int j = 0; j < n - nOld; j++) { nid[j] = id[nOld + j]; nty[j] = type[nOld + j]; }
+                var asrc = new List<int>(); var adst = new List<int>(); var at = new List<byte>(); var aw = new List<double>();
+                for (int i = 0; i < n; i++) {
+                    long kept = i < nOld ? prevRowptr[i + 1] - prevRowptr[i] : 0;
+                    for (long p = rowptr[i] + kept; p < rowptr[i + 1]; p++) { asrc.Add(i); adst.Add(dst[p]); at.Add(etype[p]); aw.Add(w[p]); }
+                }
+                Native.Check(Native.rwr_graph_append_nodes(handle, n - nOld, nid, nty, asrc.Count, asrc.ToArray(), adst.ToArray(),
+                                                           at.ToArray(), aw.ToArray(), null));
+                NodeAppendRebuilds++;
             } else {
                 var opts = new RwrOpts { struct_size = 40, device = -1, mode = -1 };
                 Native.Check(Native.rwr_graph_create(n, id, type, rowptr, dst, etype, w, ref opts, out handle));
             }
             sentId = id; sentType = type; sentW = w;
+            sentInOrder = KeysInOrder();
             if (GraphFieldLimit > 0 && m <= GraphFieldLimit) LoadNormalizedGraph();
         }
 
@@ -88,6 +108,38 @@ namespace Recommenders.RWRBased {
                 for (long p = rowptr[i]; p < rowptr[i + 1]; p++) { nd[p + add[i]] = dst[p]; nt[p + add[i]] = etype[p]; nw[p + add[i]] = sentW[p]; }
             for (int q = 0; q < count; q++) { nd[pos[q]] = ad[q]; nt[pos[q]] = at[q]; nw[pos[q]] = aw[q]; }
             rowptr = rp; dst = nd; etype = nt; sentW = nw;
+            graph = null;
+            return pos;
+        }
+
+        // rwr_graph_append_nodes on a built graph: node j of `added` gets index nodes.Count + j and an empty list ON THE DEVICE
+        // (nodes.Add(n + j, ...); edges.Add(n + j, new List<ForwardLink>()), Graph.cs:39-40), then the links are appended as
+        // AppendLinks appends them, src and targets ranging over the grown node set; one device-side rebuild for both.  Returns
+        // the positions of the new links; the first new node has index nodes.Count.  The dictionaries are not touched: add the
+        // same nodes and links to `nodes` / `edges` BEFORE any other call on this object (it reads nodes.Count), and the next
+        // buildGraph() finds nothing more to send.
+        public long[] AppendNodes(Node[] added, int[] src, ForwardLink[] links) {
+            if (src.Length != links.Length) throw new System.ArgumentException("one source per link");
+            int nOld = sentId.Length, k = added.Length, n = nOld + k, count = src.Length;
+            var nid = new long[k]; var nty = new byte[k];
+            for (int j = 0; j < k; j++) { nid[j] = added[j].id; nty[j] = (byte)added[j].type; }
+            var ad = new int[count]; var at = new byte[count]; var aw = new double[count]; var pos = new long[count];
+            for (int q = 0; q < count; q++) { ad[q] = links[q].targetNode; at[q] = (byte)links[q].type; aw[q] = links[q].weight; }
+            Native.Check(Native.rwr_graph_append_nodes(handle, k, nid, nty, count, src, ad, at, aw, pos));
+            // the flat copies behind LoadNormalizedGraph() and the next buildGraph()'s diff follow
+            var id2 = new long[n]; var ty2 = new byte[n];
+            for (int i = 0; i < nOld; i++) { id2[i] = sentId[i]; ty2[i] = sentType[i]; }
+            for (int j = 0; j < k; j++) { id2[nOld + j] = nid[j]; ty2[nOld + j] = nty[j]; }
+            var add = new long[n + 1];
+            foreach (int s in src) add[s + 1]++;
+            for (int i = 0; i < n; i++) add[i + 1] += add[i];
+            var rp = new long[n + 1];
+            for (int i = 0; i <= n; i++) rp[i] = rowptr[i < nOld ? i : nOld] + add[i];
+            var nd = new int[rp[n]]; var nt = new byte[rp[n]]; var nw = new double[rp[n]];
+            for (int i = 0; i < nOld; i++)
+                for (long p = rowptr[i]; p < rowptr[i + 1]; p++) { nd[p + add[i]] = dst[p]; nt[p + add[i]] = etype[p]; nw[p + add[i]] = sentW[p]; }
+            for (int q = 0; q < count; q++) { nd[pos[q]] = ad[q]; nt[pos[q]] = at[q]; nw[pos[q]] = aw[q]; }
+            rowptr = rp; dst = nd; etype = nt; sentW = nw; sentId = id2; sentType = ty2;
             graph = null;
             return pos;
         }
@@ -121,6 +173,31 @@ namespace Recommenders.RWRBased {
             if (oldRowptr == null || oldRowptr.Length != rowptr.Length || sentId.Length != id.Length) return false;
             for (int i = 0; i < id.Length; i++) if (sentId[i] != id[i] || sentType[i] != type[i]) return false;
             for (int i = 0; i + 1 < rowptr.Length; i++) {
+                long len = oldRowptr[i + 1] - oldRowptr[i];
+                if (rowptr[i + 1] - rowptr[i] < len) return false;
+                for (long k = 0; k < len; k++) {
+                    long o = oldRowptr[i] + k, f = rowptr[i] + k;
+                    if (dst[f] != oldDst[o] || etype[f] != oldEtype[o] ||
+                        System.BitConverter.DoubleToInt64Bits(w[f]) != System.BitConverter.DoubleToInt64Bits(sentW[o])) return false;
+                }
+            }
+            return true;
+        }
+
+        // the node dictionary enumerates its keys as 0, 1, ..., n-1 (what a loader that only ever adds nodes leaves)
+        bool KeysInOrder() {
+            int k = 0;
+            foreach (int key in nodes.Keys) if (key != k++) return false;
+            return true;
+        }
+
+        // nodes were added behind the last recorded one, the recorded nodes are unchanged, and every recorded list is a bitwise
+        // prefix of the new one (the lists of the new nodes count as empty before)
+        bool GrownNodes(long[] id, byte[] type, long[] oldRowptr, int[] oldDst, byte[] oldEtype, double[] w) {
+            if (oldRowptr == null || sentId.Length >= id.Length) return false;
+            int nOld = sentId.Length;
+            for (int i = 0; i < nOld; i++) if (sentId[i] != id[i] || sentType[i] != type[i]) return false;
+            for (int i = 0; i < nOld; i++) {
                 long len = oldRowptr[i + 1] - oldRowptr[i];
                 if (rowptr[i + 1] - rowptr[i] < len) return false;
                 for (long k = 0; k < len; k++) {

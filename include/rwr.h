@@ -194,9 +194,9 @@ int32_t rwr_graph_update_links(rwr_graph *g, int64_t count, const int64_t *link_
  * list, for a later rwr_graph_update_links.  Positions handed out earlier move: the link at old
  * position e of row i is now at e + (number of appended links with src < i).
  * count == 0 just rebuilds, as rwr_graph_update_links does.
- * Not in scope: appending NODES (n and every n-sized array stay as they are: create a new graph)
- * and REMOVING links (relabel them to UNDEFINED through rwr_graph_update_links, which leaves the
- * walk bit for bit as if they were gone).
+ * Not in scope of THIS entry: appending NODES (rwr_graph_append_nodes, below, appends nodes and
+ * links in one call); not in scope at all: REMOVING links (relabel them to UNDEFINED through
+ * rwr_graph_update_links, which leaves the walk bit for bit as if they were gone).
  * Errors, all found on the host before any device work; they leave the graph exactly as it was:
  * RWR_E_INVALID (g NULL, count < 0, a NULL src/dst/etype/w with count > 0, a handle invalidated
  * earlier), RWR_E_RANGE (a src[q] or dst[q] outside [0, n); the message names q),
@@ -209,6 +209,37 @@ int32_t rwr_graph_update_links(rwr_graph *g, int64_t count, const int64_t *link_
  * destroyed.  Not to be called concurrently with other calls on the same handle. */
 int32_t rwr_graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, const int32_t *dst,
                                const uint8_t *etype, const double *w,
+                               int64_t *new_index_out /* count, may be NULL */);
+/* Appends nodes behind the last node of the resident graph, and links in the same call.  New node
+ * j gets index n + j, id node_id[j], type node_type[j] and an empty list, which is what
+ * nodes.Add(n + j, new Node(id, type)); edges.Add(n + j, new List<ForwardLink>()) does to the
+ * reference's dictionaries (Graph.cs:39-40).  The count links are then appended exactly as
+ * rwr_graph_append_links appends them, with src[q] and dst[q] ranging over [0, n + n_new): a new
+ * node may arrive with links to it and from it, and the call costs one rebuild.  Only the new
+ * nodes and links cross the boundary.  The resulting state -- normalised weights, dangling flags,
+ * in-neighbour lists, every processing order, both ITEM orders (equal ids rank in index order, as
+ * rwr_graph_create ranks them), rwr_graph_size, the n / nnz_raw / nnz / uniform / uniform_path
+ * statistics -- is bit for bit what rwr_graph_create would build from the grown arrays, and every
+ * later call behaves accordingly: a personalised Model starts at rank[seed] = n + n_new
+ * (Model.cs:44), so every score changes even when the new nodes have no links.  Node types are
+ * taken as rwr_graph_create takes them (unchecked; anything but ITEM is no candidate).
+ * n_new == 0 is rwr_graph_append_links, with identical results, positions and errors;
+ * n_new > 0 with count == 0 is legal.  new_index_out as in rwr_graph_append_links.
+ * A handle in row-partitioned use (rwr_part_begin was called) loses that state: the next
+ * rwr_part_* call other than rwr_part_begin fails with RWR_E_INVALID.
+ * Not in scope: REMOVING or renumbering nodes, and inserting a node anywhere but at the end
+ * (create a new graph).
+ * Errors, all found on the host before any device work; they leave the graph exactly as it was:
+ * RWR_E_INVALID (g NULL, n_new < 0, count < 0, a NULL node_id/node_type with n_new > 0, a NULL
+ * src/dst/etype/w with count > 0, a handle invalidated earlier), RWR_E_RANGE (a src[q] or dst[q]
+ * outside [0, n + n_new); the message names q and the new bound), RWR_E_UNSUPPORTED (n + n_new
+ * beyond INT32_MAX; nnz_raw + count beyond this build's limit of 2^32-2 links).
+ * Failures keep the two phases of rwr_graph_append_links: out of device memory before the swap
+ * returns RWR_E_NOMEM and leaves the graph untouched and usable; a failure after the swap
+ * invalidates the handle.  Not to be called concurrently with other calls on the same handle. */
+int32_t rwr_graph_append_nodes(rwr_graph *g, int32_t n_new, const int64_t *node_id,
+                               const uint8_t *node_type, int64_t count, const int32_t *src,
+                               const int32_t *dst, const uint8_t *etype, const double *w,
                                int64_t *new_index_out /* count, may be NULL */);
 /* Graph.size() (Graph.cs:91-93) plus link counts; any out pointer may be NULL */
 int32_t rwr_graph_size(const rwr_graph *g, int32_t *n, int64_t *nnz_raw, int64_t *nnz_explicit);

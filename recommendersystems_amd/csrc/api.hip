@@ -27,7 +27,7 @@ template <class F>
 static int32_t bound(const char *who, rwr_graph *g, F &&body)
 {
     if (g->poisoned) {
-        set_error("this graph handle was invalidated by a failed rebuild (rwr_graph_update_links / rwr_graph_append_links); destroy it");
+        set_error("this graph handle was invalidated by a failed rebuild (rwr_graph_update_links / rwr_graph_append_links / rwr_graph_append_nodes); destroy it");
         return RWR_E_INVALID;
     }
     DeviceGuard dev_guard(g->device);
@@ -166,10 +166,33 @@ int32_t rwr_graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, 
         return RWR_E_INVALID;
     }
     bool swapped = false;
-    const int32_t rc = bound("rwr_graph_append_links", g, [&] { return graph_append_links(g, count, src, dst, etype, w, new_index_out, &swapped); });
+    const int32_t rc = bound("rwr_graph_append_links", g, [&] { return graph_append(g, "rwr_graph_append_links", 0, nullptr, nullptr, count, src, dst, etype, w, new_index_out, &swapped); });
     // before the swap the handle still holds the old lists and everything derived from them; a failure after it leaves derived
     // arrays that no longer match the merged lists
     if (rc != RWR_OK && swapped) g->poisoned = 1;
+    return rc;
+}
+
+int32_t rwr_graph_append_nodes(rwr_graph *g, int32_t n_new, const int64_t *node_id, const uint8_t *node_type, int64_t count,
+                               const int32_t *src, const int32_t *dst, const uint8_t *etype, const double *w,
+                               int64_t *new_index_out)
+{
+    g_err[0] = 0;
+    if (!g) { set_error("rwr_graph_append_nodes: graph is NULL"); return RWR_E_INVALID; }
+    if (n_new < 0 || (n_new > 0 && (!node_id || !node_type))) {
+        set_error("rwr_graph_append_nodes: n_new must be >= 0 and node_id/node_type non-NULL when n_new > 0");
+        return RWR_E_INVALID;
+    }
+    if (count < 0 || (count > 0 && (!src || !dst || !etype || !w))) {
+        set_error("rwr_graph_append_nodes: count must be >= 0 and src/dst/etype/w non-NULL when count > 0");
+        return RWR_E_INVALID;
+    }
+    // (node types are taken as rwr_graph_create takes them: unchecked, anything but ITEM is no candidate)
+    bool swapped = false;
+    const int32_t rc = bound("rwr_graph_append_nodes", g, [&] {
+        return graph_append(g, "rwr_graph_append_nodes", n_new, node_id, node_type, count, src, dst, etype, w, new_index_out, &swapped);
+    });
+    if (rc != RWR_OK && swapped) g->poisoned = 1;   // (the two phases of rwr_graph_append_links)
     return rc;
 }
 

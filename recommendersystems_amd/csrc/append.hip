@@ -1,9 +1,11 @@
-// rwr_graph_append_links: links appended to the lists of a resident graph.  The host plan (append_plan.h) says
-// where everything goes; the kernels here merge the resident raw lists with the new links into NEW buffers, the handle takes
-// them, and build.hip's re-derive (the incremental rebuild with nothing to patch) rebuilds the walk's data from them -- the same
-// kernels in the same order as rwr_graph_create, hence the same bits.
+// rwr_graph_append_links / rwr_graph_append_nodes: links appended to the lists of a resident graph, and
+// nodes appended behind its last one.  The host plans (append_plan.h, node_append_plan.h) say where everything goes; the kernels
+// here merge the resident raw lists with the new links, and the resident ITEM order with the new ITEM rows, into NEW buffers, the
+// handle takes them, and build.hip's re-derive (the incremental rebuild with nothing to patch) rebuilds the walk's data from
+// them -- the same kernels in the same order as rwr_graph_create, hence the same bits.
 #include "engine.h"
 #include "append_plan.h"
+#include "node_append_plan.h"
 
 #include <chrono>
 #include <cstdio>
@@ -41,8 +43,9 @@ static double at_now()
 static const bool at_on = [] { const char *e = RWR_TUNE_ENV("RWR_APPEND_TIMING"); return e && atoi(e) != 0; }();
 #define AT(label) do { if (at_on) { const double t__ = at_now(); fprintf(stderr, "[append] %-28s %8.1f us\n", label, t__ - at_t); at_t = t__; } } while (0)
 
-// rowptr_new[i] = rowptr_old[i] + (appended links with src < i), i in [0, n]
-__global__ __launch_bounds__(256) void k_append_rowptr(int32_t n, int32_t nb, const int32_t *__restrict__ srcs,
+// rowptr_new[i] = rowptr_old[min(i, n_old)] + (appended links with src < i), i in [0, n]: the rows past n_old are the call's
+// new nodes, whose lists were empty before it
+__global__ __launch_bounds__(256) void k_append_rowptr(int32_t n, int32_t n_old, int32_t nb, const int32_t *__restrict__ srcs,
                                                        const int64_t *__restrict__ cum, const int64_t *__restrict__ rp_old,
                                                        int64_t *__restrict__ rp_new)
 {
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(256) void k_append_rowptr(int32_t n, int32_t nb, co
         if ((int64_t)srcs[mid] < i) lo = mid + 1;
         else hi = mid;
     }
-    rp_new[i] = rp_old[i] + (lo > 0 ? cum[lo - 1] : 0);
+    rp_new[i] = rp_old[i < n_old ? i : (int64_t)n_old] + (lo > 0 ? cum[lo - 1] : 0);
 }
 
 // one segment [a, b) of old positions, all moving by sh: three coalesced block copies by the whole workgroup
@@ -169,41 +172,85 @@ __global__ __launch_bounds__(256) void k_append_scatter(int64_t count, const int
     w_n[p] = w_a[k];
 }
 
-// Appends links to the resident raw lists and re-derives (rwr_graph_append_links).  Two phases: everything up to
-// the swap works on NEW buffers -- an argument error or a failed allocation leaves the graph as it was -- and from the swap on
-// (*swapped) a failure leaves raw and derived arrays out of step, as in graph_update_links.
-int32_t graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, const int32_t *dst, const uint8_t *etype,
-                           const double *w, int64_t *new_index_out, bool *swapped)
+// ---- rwr_graph_append_nodes: the resident ITEM order (ids descending) merged with the call's new ITEM rows.
+// A = the resident item_order, B = the new ITEM rows stably by id descending (node_append_plan.h, which also states the tie
+// rule: A wins).  One thread per output element; its destination is its own position plus the elements of the OTHER list that
+// stand before it, found by one bisection there.  Every destination in [0, no + nn) is written exactly once.
+__global__ __launch_bounds__(256) void k_item_order_merge(int32_t no, int32_t nn, const int32_t *__restrict__ A,
+                                                          const int32_t *__restrict__ B, const int64_t *__restrict__ node_id,
+                                                          int32_t *__restrict__ out)
 {
-    const int32_t n = g->n;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)no + nn) return;
+    if (t < no) {
+        const int32_t q = (int32_t)t, row = A[q];
+        out[nap_old_dest(q, node_id[row], nn, [&](int32_t r) { return node_id[B[r]]; })] = row;
+    } else {
+        const int32_t r = (int32_t)(t - no), row = B[r];
+        out[nap_new_dest(r, node_id[row], no, [&](int32_t q) { return node_id[A[q]]; })] = row;
+    }
+}
+
+// the host row pointers of a call that adds nodes are grown BEFORE the link plan reads them; a call that fails before the swap
+// gives the added entries back
+struct RowptrGrowth {
+    std::vector<int64_t> &rp;
+    size_t old_size;
+    bool keep = false;
+    ~RowptrGrowth() { if (!keep) rp.resize(old_size); }
+};
+
+// Appends nodes and links to the resident raw lists and re-derives (rwr_graph_append_links; rwr_graph_append_nodes,
+// §3.13).  Two phases: everything up to the swap works on NEW buffers -- an argument error or a failed allocation leaves the
+// graph as it was -- and from the swap on (*swapped) a failure leaves raw and derived arrays out of step, as in
+// graph_update_links.  With n_new == 0 this is the links-only append, launch for launch.
+int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t *node_id, const uint8_t *node_type,
+                     int64_t count, const int32_t *src, const int32_t *dst, const uint8_t *etype, const double *w,
+                     int64_t *new_index_out, bool *swapped)
+{
+    const int32_t n_old = g->n;
     hipStream_t s = g->stream;
     *swapped = false;
     double at_t = at_on ? at_now() : 0.0;
+    const NodeAppendPlan np = node_append_plan(n_old, n_new, node_id, node_type, (uint8_t)RWR_NODE_ITEM);
+    if (np.verdict == NODE_APPEND_TOO_MANY) {
+        set_error("%s: %d + %d nodes exceed this build's limit of 2^31-1", who, n_old, n_new);
+        return RWR_E_UNSUPPORTED;
+    }
+    const int32_t n = np.n_total;
+    const bool grow = n > n_old;
+    RowptrGrowth growth{g->h_rowptr, g->h_rowptr.size()};
+    if (grow) {
+        g->h_is_item.reserve((size_t)n);                        // (so that nothing on the host can fail after the swap)
+        node_append_extend_rowptr(g->h_rowptr, n_old, n);
+    }
     const AppendPlan plan = append_plan(n, g->h_rowptr.data(), count, src, dst);
     if (plan.verdict == APPEND_BAD_SRC) {
-        set_error("rwr_graph_append_links: src[%lld] = %d is outside [0, %d)", (long long)plan.bad_q, src[plan.bad_q], n);
+        set_error("%s: src[%lld] = %d is outside [0, %d)", who, (long long)plan.bad_q, src[plan.bad_q], n);
         return RWR_E_RANGE;
     }
     if (plan.verdict == APPEND_BAD_DST) {
-        set_error("rwr_graph_append_links: dst[%lld] = %d is outside [0, %d)", (long long)plan.bad_q, dst[plan.bad_q], n);
+        set_error("%s: dst[%lld] = %d is outside [0, %d)", who, (long long)plan.bad_q, dst[plan.bad_q], n);
         return RWR_E_RANGE;
     }
     if (plan.verdict == APPEND_TOO_MANY) {
-        set_error("rwr_graph_append_links: %lld + %lld links exceed this build's per-device limit of 2^32-2", (long long)plan.m_old,
+        set_error("%s: %lld + %lld links exceed this build's per-device limit of 2^32-2", who, (long long)plan.m_old,
                   (long long)count);
         return RWR_E_UNSUPPORTED;
     }
-    if (count <= 0) {
+    if (count <= 0 && !grow) {
         *swapped = true;               // (nothing to merge: a plain rebuild, with rwr_graph_update_links' failure rule)
         return graph_update_links(g, 0, nullptr, nullptr, nullptr);
     }
+    const bool links = count > 0;
     const int64_t m_old = plan.m_old, m_new = plan.m_new;
     const size_t nb = plan.srcs.size();
+    const int32_t ni_old = g->n_items, ni_new = np.n_new_items, ni = ni_old + ni_new;
     AT("plan (host)");
     // the new links in list order
-    std::vector<int32_t> h_dst((size_t)count);
-    std::vector<uint8_t> h_et((size_t)count);
-    std::vector<double> h_w((size_t)count);
+    std::vector<int32_t> h_dst((size_t)(links ? count : 0));
+    std::vector<uint8_t> h_et((size_t)(links ? count : 0));
+    std::vector<double> h_w((size_t)(links ? count : 0));
     for (int64_t k = 0; k < count; ++k) {
         const int64_t q = plan.order[(size_t)k];
         h_dst[(size_t)k] = dst[q];
@@ -217,59 +264,153 @@ int32_t graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, cons
     DevBuf<uint8_t> et_n, d_et;
     DevBuf<double> w_n, wn_n, d_w;
     RWR_TRY(rp_n.alloc((size_t)n + 1));
-    RWR_TRY(dst_n.alloc((size_t)m_new));
-    RWR_TRY(et_n.alloc((size_t)m_new));
-    RWR_TRY(w_n.alloc((size_t)m_new));
-    RWR_TRY(wn_n.alloc((size_t)m_new));
     RWR_TRY(d_srcs.alloc(nb));
-    RWR_TRY(d_brk.alloc(nb));
     RWR_TRY(d_cum.alloc(nb));
-    RWR_TRY(d_pos.alloc((size_t)count));
-    RWR_TRY(d_dst.alloc((size_t)count));
-    RWR_TRY(d_et.alloc((size_t)count));
-    RWR_TRY(d_w.alloc((size_t)count));
+    if (links) {
+        RWR_TRY(dst_n.alloc((size_t)m_new));
+        RWR_TRY(et_n.alloc((size_t)m_new));
+        RWR_TRY(w_n.alloc((size_t)m_new));
+        RWR_TRY(wn_n.alloc((size_t)m_new));
+        RWR_TRY(d_brk.alloc(nb));
+        RWR_TRY(d_pos.alloc((size_t)count));
+        RWR_TRY(d_dst.alloc((size_t)count));
+        RWR_TRY(d_et.alloc((size_t)count));
+        RWR_TRY(d_w.alloc((size_t)count));
+    }
+    // ... and of a call that adds nodes: the node SoA, the two ITEM orders, and every n-sized array the re-derive writes
+    // (it fills them whole, as the first build does with its own fresh allocations)
+    DevBuf<int64_t> nid_n, inp_n;
+    DevBuf<uint8_t> nty_n, dang_n;
+    DevBuf<double> wsrc_n;
+    DevBuf<int32_t> ro_n, rox_n, irows_n, iord_n, d_bsorted;
+    if (grow) {
+        RWR_TRY(nid_n.alloc((size_t)n));
+        RWR_TRY(nty_n.alloc((size_t)n));
+        RWR_TRY(dang_n.alloc((size_t)n));
+        RWR_TRY(wsrc_n.alloc((size_t)n));
+        RWR_TRY(inp_n.alloc((size_t)n + 1));
+        RWR_TRY(ro_n.alloc((size_t)n));
+        RWR_TRY(rox_n.alloc((size_t)n));
+        if (ni_new > 0) {
+            RWR_TRY(irows_n.alloc((size_t)ni));
+            RWR_TRY(iord_n.alloc((size_t)ni));
+            RWR_TRY(d_bsorted.alloc((size_t)ni_new));
+        }
+    }
     AT("allocate new buffers");
+    // the id range of the grown ITEM set (rwr_graph_create's sort-key parameters): the handle knows the largest resident id;
+    // the smallest one is the last entry of the resident order, read back once per handle
+    uint64_t key_lo = g->id_key_lo, key_hi = g->id_key_top;
+    bool lo_known = g->id_key_lo_known != 0;
+    if (grow && ni_new > 0 && ni_old > 0 && !lo_known) {
+        int32_t last_row = 0;
+        int64_t last_id = 0;
+        RWR_HIP(hipMemcpy(&last_row, g->item_order.p + (ni_old - 1), sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (last_row < 0 || last_row >= n_old) { set_error("%s: the resident ITEM order is damaged", who); return RWR_E_HIP; }
+        RWR_HIP(hipMemcpy(&last_id, g->node_id.p + last_row, sizeof(int64_t), hipMemcpyDeviceToHost));
+        key_lo = nap_orderable(last_id);
+        lo_known = true;
+        AT("read back the smallest id");
+    }
+    if (ni_new > 0) {
+        if (ni_old > 0) {
+            key_lo = np.key_lo < key_lo ? np.key_lo : key_lo;
+            key_hi = np.key_hi > key_hi ? np.key_hi : key_hi;
+        } else {
+            key_lo = np.key_lo;
+            key_hi = np.key_hi;
+            lo_known = true;
+        }
+    }
     // (a failure from here to the swap waits for the stream before it returns: the copies read this function's vectors and the
     //  kernels write its buffers, all of which go away on return -- and the handle, untouched, stays usable)
     auto merge = [&]() -> int32_t {
-        RWR_HIP(hipMemcpyAsync(d_srcs.p, plan.srcs.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, s));
-        RWR_HIP(hipMemcpyAsync(d_brk.p, plan.brk.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, s));
-        RWR_HIP(hipMemcpyAsync(d_cum.p, plan.cum.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, s));
-        RWR_HIP(hipMemcpyAsync(d_pos.p, plan.pos.data(), sizeof(int64_t) * (size_t)count, hipMemcpyHostToDevice, s));
-        RWR_HIP(hipMemcpyAsync(d_dst.p, h_dst.data(), sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, s));
-        RWR_HIP(hipMemcpyAsync(d_et.p, h_et.data(), (size_t)count, hipMemcpyHostToDevice, s));
-        RWR_HIP(hipMemcpyAsync(d_w.p, h_w.data(), sizeof(double) * (size_t)count, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_append_rowptr, dim3(cdiv((size_t)n + 1, 256)), dim3(256), 0, s, n, (int32_t)nb, d_srcs.p, d_cum.p,
-                           g->rowptr.p, rp_n.p);
-        if (m_old > 0)
-            hipLaunchKernelGGL(k_append_merge, dim3(cdiv((size_t)m_old, (size_t)AP_CHUNK)), dim3(AP_THREADS), 0, s, m_old,
-                               (int32_t)nb, d_brk.p, d_cum.p, g->dst.p, g->etype.p, g->w_raw.p, dst_n.p, et_n.p, w_n.p);
-        hipLaunchKernelGGL(k_append_scatter, dim3(cdiv((size_t)count, 256)), dim3(256), 0, s, count, d_pos.p, d_dst.p, d_et.p,
-                           d_w.p, dst_n.p, et_n.p, w_n.p);
+        if (nb > 0) {
+            RWR_HIP(hipMemcpyAsync(d_srcs.p, plan.srcs.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, s));
+            RWR_HIP(hipMemcpyAsync(d_cum.p, plan.cum.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, s));
+        }
+        if (links) {
+            RWR_HIP(hipMemcpyAsync(d_brk.p, plan.brk.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, s));
+            RWR_HIP(hipMemcpyAsync(d_pos.p, plan.pos.data(), sizeof(int64_t) * (size_t)count, hipMemcpyHostToDevice, s));
+            RWR_HIP(hipMemcpyAsync(d_dst.p, h_dst.data(), sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, s));
+            RWR_HIP(hipMemcpyAsync(d_et.p, h_et.data(), (size_t)count, hipMemcpyHostToDevice, s));
+            RWR_HIP(hipMemcpyAsync(d_w.p, h_w.data(), sizeof(double) * (size_t)count, hipMemcpyHostToDevice, s));
+        }
+        hipLaunchKernelGGL(k_append_rowptr, dim3(cdiv((size_t)n + 1, 256)), dim3(256), 0, s, n, n_old, (int32_t)nb, d_srcs.p,
+                           d_cum.p, g->rowptr.p, rp_n.p);
+        if (links) {
+            if (m_old > 0)
+                hipLaunchKernelGGL(k_append_merge, dim3(cdiv((size_t)m_old, (size_t)AP_CHUNK)), dim3(AP_THREADS), 0, s, m_old,
+                                   (int32_t)nb, d_brk.p, d_cum.p, g->dst.p, g->etype.p, g->w_raw.p, dst_n.p, et_n.p, w_n.p);
+            hipLaunchKernelGGL(k_append_scatter, dim3(cdiv((size_t)count, 256)), dim3(256), 0, s, count, d_pos.p, d_dst.p,
+                               d_et.p, d_w.p, dst_n.p, et_n.p, w_n.p);
+        }
+        if (grow) {
+            // node SoA: the resident part device to device, the new tail from the caller's arrays
+            RWR_HIP(hipMemcpyAsync(nid_n.p, g->node_id.p, sizeof(int64_t) * (size_t)n_old, hipMemcpyDeviceToDevice, s));
+            RWR_HIP(hipMemcpyAsync(nid_n.p + n_old, node_id, sizeof(int64_t) * (size_t)n_new, hipMemcpyHostToDevice, s));
+            RWR_HIP(hipMemcpyAsync(nty_n.p, g->node_type.p, (size_t)n_old, hipMemcpyDeviceToDevice, s));
+            RWR_HIP(hipMemcpyAsync(nty_n.p + n_old, node_type, (size_t)n_new, hipMemcpyHostToDevice, s));
+            if (ni_new > 0) {
+                if (ni_old > 0)
+                    RWR_HIP(hipMemcpyAsync(irows_n.p, g->item_rows.p, sizeof(int32_t) * (size_t)ni_old, hipMemcpyDeviceToDevice, s));
+                RWR_HIP(hipMemcpyAsync(irows_n.p + ni_old, np.new_item_rows.data(), sizeof(int32_t) * (size_t)ni_new,
+                                       hipMemcpyHostToDevice, s));
+                RWR_HIP(hipMemcpyAsync(d_bsorted.p, np.new_item_sorted.data(), sizeof(int32_t) * (size_t)ni_new,
+                                       hipMemcpyHostToDevice, s));
+                hipLaunchKernelGGL(k_item_order_merge, dim3(cdiv((size_t)ni, 256)), dim3(256), 0, s, ni_old, ni_new,
+                                   g->item_order.p, d_bsorted.p, nid_n.p, iord_n.p);
+            }
+        }
         RWR_HIP(hipGetLastError());
         RWR_HIP(hipStreamSynchronize(s));
         return RWR_OK;
     };
     RWR_TRY(idle_on_error(s, merge));
     AT("upload + merge kernels");
-    // ---- phase 2: the handle takes the merged lists
+    // ---- phase 2: the handle takes the merged lists and the grown node arrays
     *swapped = true;
+    growth.keep = true;
     swap_blocks(g->rowptr, rp_n);
-    swap_blocks(g->dst, dst_n);
-    swap_blocks(g->etype, et_n);
-    swap_blocks(g->w_raw, w_n);
-    swap_blocks(g->w_norm_raw, wn_n);
-    {
-        size_t j = 0;
-        for (int32_t i = 0; i <= n; ++i) {                      // h_rowptr[i] += appended links with src < i
-            while (j < nb && plan.srcs[j] < i) ++j;
-            g->h_rowptr[(size_t)i] += j > 0 ? plan.cum[j - 1] : 0;
-        }
+    if (links) {
+        swap_blocks(g->dst, dst_n);
+        swap_blocks(g->etype, et_n);
+        swap_blocks(g->w_raw, w_n);
+        swap_blocks(g->w_norm_raw, wn_n);
     }
+    node_append_shift_rowptr(g->h_rowptr, n, plan.srcs, plan.cum);
     g->nnz_raw = m_new;
     g->stats.nnz_raw = m_new;
     if (m_new > ONE_LAUNCH_MAX_M) g->staged = 0;                // past the one-launch build: the general derive from now on
-    if (new_index_out) memcpy(new_index_out, plan.new_index.data(), sizeof(int64_t) * (size_t)count);
+    if (grow) {
+        swap_blocks(g->node_id, nid_n);
+        swap_blocks(g->node_type, nty_n);
+        swap_blocks(g->dangling, dang_n);
+        swap_blocks(g->w_src, wsrc_n);
+        swap_blocks(g->in_ptr, inp_n);
+        swap_blocks(g->row_order, ro_n);
+        swap_blocks(g->row_order_x, rox_n);
+        if (ni_new > 0) {
+            swap_blocks(g->item_rows, irows_n);
+            swap_blocks(g->item_order, iord_n);
+            node_append_id_keys(true, key_lo, key_hi, &g->id_key_top, &g->id_key_bits);
+            g->id_key_lo = key_lo;
+            g->id_key_lo_known = lo_known ? 1 : 0;
+        }
+        g->h_is_item.resize((size_t)n, 0);                      // (reserved above)
+        for (int32_t r : np.new_item_rows) g->h_is_item[(size_t)r] = 1;
+        g->n = n;
+        g->n_items = ni;
+        g->stats.n = n;
+        // a staged graph's pinned read-back area is sized for ONE_LAUNCH_MAX_N nodes (build.hip)
+        if (n > ONE_LAUNCH_MAX_N) g->staged = 0;
+        // nothing cached for the old node count survives: the list a single-seed call left in pinned memory, and a
+        // row-partitioned run (the re-derive ends it; its slab and seeds go too, so that only rwr_part_begin restarts it)
+        g->sm_pin_count = -1;
+        g->part_lo = g->part_hi = g->part_K = g->part_steps = 0;
+        g->part_seeds.clear();
+    }
+    if (new_index_out && links) memcpy(new_index_out, plan.new_index.data(), sizeof(int64_t) * (size_t)count);
     AT("swap + host row pointers");
     const int32_t rc = graph_update_links(g, 0, nullptr, nullptr, nullptr);   // (count 0: the re-derive alone, build.hip)
     AT("re-derive");

@@ -1,5 +1,5 @@
 // Where the links of one rwr_graph_append_links call go, decided by append_plan() from the handle's host row
-// pointers and the call's src / dst arrays alone and carried out by graph_append_links (append.hip).  Plain C++17 without HIP,
+// pointers and the call's src / dst arrays alone and carried out by graph_append (append.hip).  Plain C++17 without HIP,
 // so that tests/cpp/append_plan_check.cpp checks it against a list-of-lists append on the host.
 //
 // Link q goes to the END of row src[q]; links of one row keep the order of q.  Let the distinct sources be s_0 < s_1 < ... with

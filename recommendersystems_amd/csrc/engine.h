@@ -13,6 +13,8 @@ struct rwr_graph {
     int32_t n_items = 0;     // nodes of type ITEM
     uint64_t id_key_top = 0; // largest ITEM id (order-preserving unsigned form) and the bits of the id range: sort keys of item_order
     int32_t id_key_bits = 64;
+    uint64_t id_key_lo = 0;  // smallest ITEM id in the same form, once rwr_graph_append_nodes has read it back (id_key_lo_known): the
+    int32_t id_key_lo_known = 0;   // build keeps only the range's bit count, and a grown id set needs the range itself
     int32_t uniform = 0;     // every row's explicit raw weights equal
     // Value-free matrix path (uniform && nonneg, RWR_VALUE_FREE != 0).  Every out-link of source i then carries the SAME
     // normalised weight w_src[i] (Graph.cs:79-81 divides equal raw weights by one sum), so the product Model.cs:87 adds,
@@ -208,10 +210,15 @@ int32_t graph_update_links(rwr_graph *g, int64_t count, const int64_t *idx, cons
 // one-launch build (build.hip keeps its own STAGE_MAX_M of the same value: that file is part of the benchmark's traffic
 // fingerprint and is not edited for a constant; small_build_ok re-checks nnz_raw against it on every build)
 constexpr int64_t ONE_LAUNCH_MAX_M = 65536;
-// rwr_graph_append_links: merges the links into the resident raw lists (new buffers, swapped in when all of them exist:
-// *swapped) and re-derives; the plan of the merge is append_plan.h's
-int32_t graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, const int32_t *dst, const uint8_t *etype,
-                           const double *w, int64_t *new_index_out, bool *swapped);
+// ... and the largest node count of the staged upload and the one-launch build (build.hip's STAGE_MAX_N, which sizes the pinned
+// read-back area of a staged graph: a graph that grows past it leaves the staged path, append.hip)
+constexpr int32_t ONE_LAUNCH_MAX_N = 8192;
+// rwr_graph_append_links (n_new == 0) and rwr_graph_append_nodes: grows the node arrays by n_new nodes with empty lists, merges
+// the links into the resident raw lists (new buffers, swapped in when all of them exist: *swapped) and re-derives; the plans are
+// node_append_plan.h's and append_plan.h's.  `who` names the entry point in the messages.
+int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t *node_id, const uint8_t *node_type,
+                     int64_t count, const int32_t *src, const int32_t *dst, const uint8_t *etype, const double *w,
+                     int64_t *new_index_out, bool *swapped);
 // value-free graphs: materialise in_w (= w_src[in_src]) for an entry point that runs the weighted kernels
 int32_t ensure_in_w(rwr_graph *g);
 // g->tail_rows / tail_n / tail_depth / h_tail_flag of the current matrix (built once per (re)build)

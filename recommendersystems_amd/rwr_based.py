@@ -92,6 +92,28 @@ def _grown_lists(old_flat, new_flat):
     return src, n_dst[added], n_et[added], n_w[added]
 
 
+def _extended_flat(flat, node_id, node_type):
+    """``flat`` with the nodes (node_id, node_type) behind its last node, each with an empty list: what
+    rwr_graph_append_nodes does to the node arrays and the row pointers.  The link arrays are shared, not copied."""
+    o_id, o_type, o_rp, o_dst, o_et, o_w = flat
+    k = int(node_id.shape[0])
+    return (np.concatenate([o_id, node_id]), np.concatenate([o_type, node_type]),
+            np.concatenate([o_rp, np.full(k, o_rp[-1], dtype=np.int64)]), o_dst, o_et, o_w)
+
+
+def _grown_nodes(old_flat, new_flat):
+    """``(n_old, (src, dst, etype, w))`` when ``new_flat`` is ``old_flat`` with nodes added behind its last one (the old
+    nodes unchanged) and every old list a bitwise prefix of the new one -- the links as ``_grown_lists`` returns them, with
+    the new nodes' lists starting empty; ``None`` otherwise, and when no node was added."""
+    o_id, o_type = old_flat[0], old_flat[1]
+    n_id, n_type = new_flat[0], new_flat[1]
+    n_old = int(o_id.shape[0])
+    if n_id.shape[0] <= n_old or not ((n_id[:n_old] == o_id).all() and (n_type[:n_old] == o_type).all()):
+        return None
+    grown = _grown_lists(_extended_flat(old_flat, n_id[n_old:], n_type[n_old:]), new_flat)
+    return None if grown is None else (n_old, grown)
+
+
 def _merged_flat(flat, src, dst, etype, w, pos):
     """``flat`` (as ``Graph._flatten`` returns it) with the links (src, dst, etype, w) at the positions ``pos`` that
     rwr_graph_append_links gave them: new arrays, the old links in their order in the places in between."""
@@ -118,6 +140,7 @@ class Graph:
 
     incremental_rebuilds = 0     # buildGraph() calls (all instances) that went through rwr_graph_update_links
     append_rebuilds = 0          # ... and those that went through rwr_graph_append_links (lists that only grew)
+    node_append_rebuilds = 0     # ... and through rwr_graph_append_nodes (nodes added at the end, lists that only grew)
 
     def __init__(self, nodes: Dict[int, Node], edges: Dict[int, List[ForwardLink]], *, mode: Optional[str] = None,
                  device: int = -1, tile_seeds: int = 0, tile_group: int = 0, profile: bool = False,
@@ -133,6 +156,7 @@ class Graph:
         self._flat = None
         self._desc = None       # (rwr_graph_desc bytes of _flat: _marshal_graphs)
         self._sent = None
+        self._sent_in_order = False   # the node dictionary enumerated its keys as 0, 1, ..., n-1 when _sent was taken
 
     # -- flat constructors (the layout of include/rwr.h), used by the bench for big graphs
     @classmethod
@@ -174,8 +198,10 @@ class Graph:
         Called again on the same object after the caller mutated its dictionaries (the harness relabels link types
         between runs, Experiment.cs:84-101): when nodes, list lengths and targets are unchanged, only the links whose
         type or weight differ are sent (rwr_graph_update_links); when the lists only grew at their ends, only the new links
-        (rwr_graph_append_links); lists that grew AND whose old links changed are sent whole.  The device state is the same
-        either way."""
+        (rwr_graph_append_links); when, besides, the node dictionary gained keys at its end -- the old nodes unchanged and in
+        the same order, the new keys continuing the index sequence -- only the new nodes and links (rwr_graph_append_nodes);
+        lists that grew AND whose old links changed, a changed old node or a reordered dictionary are sent whole.  The device
+        state is the same either way."""
         lib = _lib.load()
         flat = self._flat if self._flat is not None else self._flatten()
         node_id, node_type, rowptr, dst, etype, w = flat
@@ -199,6 +225,20 @@ class Graph:
                 self._graph_cache = None
                 Graph.append_rebuilds += 1
                 return
+            more = _grown_nodes(self._sent, flat) if self._sent_in_order and self._keys_in_order() else None
+            if more is not None:
+                n_old, (s, t, et, ww) = more
+                s, t, et, ww = (np.ascontiguousarray(a) for a in (s, t, et, ww))
+                ids, types = np.ascontiguousarray(node_id[n_old:]), np.ascontiguousarray(node_type[n_old:])
+                _lib.check(lib.rwr_graph_append_nodes(self._handle(), int(ids.shape[0]), _p(ids, C.c_int64), _p(types, C.c_uint8),
+                                                      int(s.shape[0]), _p(s, C.c_int32), _p(t, C.c_int32), _p(et, C.c_uint8),
+                                                      _p(ww, C.c_double), None))
+                self._n = int(node_id.shape[0])
+                self._rowptr = rowptr
+                self._sent = flat
+                self._graph_cache = None
+                Graph.node_append_rebuilds += 1
+                return
         if self._h:
             lib.rwr_graph_destroy(self._h)
             self._h = C.c_void_p()
@@ -208,7 +248,12 @@ class Graph:
                                         _p(rowptr, C.c_int64), _p(dst, C.c_int32), _p(etype, C.c_uint8),
                                         _p(w, C.c_double), C.byref(self._opts), C.byref(self._h)))
         self._sent = flat if self._flat is None else None     # (dictionary graphs: fresh arrays, kept for the next diff)
+        self._sent_in_order = self._flat is None and self._keys_in_order()
         self._graph_cache = None
+
+    def _keys_in_order(self) -> bool:
+        """The node dictionary enumerates its keys as 0, 1, ..., n-1 (what a loader that only ever adds nodes leaves)."""
+        return all(k == i for i, k in enumerate(self.nodes))
 
     def updateLinks(self, link_index, etype=None, w=None) -> None:
         """rwr_graph_update_links: new type / raw weight for the raw links at the given flattened positions, then the
@@ -253,6 +298,43 @@ class Graph:
             self._rowptr = rowptr
         self._graph_cache = None
         return pos
+
+    def appendNodes(self, nodes, src=(), dst=(), etype=(), w=()) -> Tuple[int, np.ndarray]:
+        """rwr_graph_append_nodes: node j of ``nodes`` (``Node`` objects or ``(id, type)`` pairs) gets index n + j and an empty
+        list (nodes.Add(n + j, ...); edges.Add(n + j, new List<ForwardLink>()), Graph.cs:39-40); then the links are appended
+        as appendLinks appends them, src and dst ranging over the grown node set; one device-side rebuild for both.  Returns
+        ``(first_index, positions)``: the index of the first new node and the positions of the new links in the new
+        flattened raw list.
+
+        The object's record of what the device holds follows, as for appendLinks: the caller of a dictionary graph adds the
+        same nodes and links to ``nodes`` / ``edges``; a flat graph continues with grown COPIES of its arrays."""
+        pairs = [(nd.id, int(nd.type)) if isinstance(nd, Node) else (int(nd[0]), int(nd[1])) for nd in nodes]
+        ids = np.ascontiguousarray([p[0] for p in pairs], dtype=np.int64)
+        types = np.ascontiguousarray([p[1] for p in pairs], dtype=np.uint8)
+        s = np.ascontiguousarray(src, dtype=np.int32)
+        t = np.ascontiguousarray(dst, dtype=np.int32)
+        et = np.ascontiguousarray(etype, dtype=np.uint8)
+        ww = np.ascontiguousarray(w, dtype=np.float64)
+        if s.ndim != 1 or t.shape != s.shape or et.shape != s.shape or ww.shape != s.shape:
+            raise ValueError("src / dst / etype / w must be one-dimensional and of one length")
+        first = self._n
+        pos = np.zeros(s.shape[0], dtype=np.int64)
+        _lib.check(_lib.load().rwr_graph_append_nodes(
+            self._handle(), int(ids.shape[0]), _p(ids, C.c_int64), _p(types, C.c_uint8), int(s.shape[0]), _p(s, C.c_int32),
+            _p(t, C.c_int32), _p(et, C.c_uint8), _p(ww, C.c_double), _p(pos, C.c_int64)))
+        self._n = first + int(ids.shape[0])
+        if self._flat is not None:
+            self._flat = _merged_flat(_extended_flat(self._flat, ids, types), s, t, et, ww, pos)
+            self._desc = None
+            self._rowptr = self._flat[2]
+        else:
+            if self._sent is not None:
+                self._sent = _merged_flat(_extended_flat(self._sent, ids, types), s, t, et, ww, pos)
+            rowptr = np.concatenate([self._rowptr, np.full(int(ids.shape[0]), self._rowptr[-1], dtype=np.int64)])
+            rowptr[1:] += np.cumsum(np.bincount(s, minlength=self._n).astype(np.int64))
+            self._rowptr = rowptr
+        self._graph_cache = None
+        return first, pos
 
     def size(self) -> int:
         """Graph.size() (Graph.cs:91-93)."""
