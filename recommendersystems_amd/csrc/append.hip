@@ -34,7 +34,7 @@ constexpr int AP_CHUNK = 8192;     // old positions per workgroup
 // of the chunk costs each element up to 13 uniform-ish loads from a table the whole workgroup keeps in cache.
 constexpr int AP_DENSE_BREAKS = 32;
 
-// the experiments build's wall-clock stamps (RWR_APPEND_TIMING=1), as RWR_BUILD_TIMING in build.hip: tools/append_latency.py
+// the experiments build's wall-clock stamps (RWR_APPEND_TIMING=1), as RWR_BUILD_TIMING in build.h: tools/append_latency.py
 static double at_now()
 {
     using namespace std::chrono;
@@ -402,7 +402,7 @@ int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t
         g->n = n;
         g->n_items = ni;
         g->stats.n = n;
-        // a staged graph's pinned read-back area is sized for ONE_LAUNCH_MAX_N nodes (build.hip)
+        // a staged graph's pinned read-back area is sized for ONE_LAUNCH_MAX_N nodes (stage_layout.h: STAGE_BYTES)
         if (n > ONE_LAUNCH_MAX_N) g->staged = 0;
         // nothing cached for the old node count survives: the list a single-seed call left in pinned memory, and a
         // row-partitioned run (the re-derive ends it; its slab and seeds go too, so that only rwr_part_begin restarts it)

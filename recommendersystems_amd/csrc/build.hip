@@ -8,16 +8,33 @@
 // The transpose is a STABLE sort of the raw link list by target: the raw list is in
 // (source asc, list position asc) order, so every in-neighbour list comes out in exactly
 // the order in which Model.deliverRanks adds into nextRank[target] (Model.cs:78,85-88).
-#include "engine.h"
+//
+// All device code of the build is here -- it decides the layout of in_ptr / in_src / in_w / row_order, which the batched SpMM
+// reads -- and so is the general multi-launch driver.  The host side of the one-launch build is build_small.hip.
+#include "build.h"
+#include "key_bits.h"
 #include "sort_small.h"
 
-#include <chrono>
-#include <mutex>
-#include <vector>
 #include <cstdlib>
 #include <cstring>
 
 namespace rwr {
+
+// one row's explicit weights summed LEFT TO RIGHT (Graph.cs:70-76), and what the build learns of the row on the way
+struct RowSum {
+    double sum = 0.0, first = 0.0;
+    int64_t n_explicit = 0;
+    bool uni = true, neg = false;    // all explicit weights equal; a negative or NaN one among them
+    __device__ __forceinline__ void add(uint8_t type, double wp)
+    {
+        if (type == RWR_EDGE_UNDEFINED) return;
+        if (n_explicit == 0) first = wp;
+        else if (wp != first) uni = false;
+        sum += wp;                       // Graph.cs:75, list order
+        ++n_explicit;
+        if (!(wp >= 0.0)) neg = true;
+    }
+};
 
 // Graph.buildGraph for 64 consecutive source rows per wave (their links are one contiguous range of the flat list).
 // The reference sums a row's explicit weights LEFT TO RIGHT (Graph.cs:70-76), so the adds of a row stay sequential -- one
@@ -43,7 +60,6 @@ __device__ __forceinline__ void row_prepare_body(
     int32_t *__restrict__ esrc, uint32_t *__restrict__ skey, uint32_t *__restrict__ sval,
     uint8_t *__restrict__ dangling, double *__restrict__ w_src, int *__restrict__ flags)
 {
-    constexpr int RP_CAP = CAP;
     if (r0 >= n) return;
     RP_STAMP(0)
     const int nrows = (n - r0) < WAVE ? (int)(n - r0) : WAVE;
@@ -57,11 +73,9 @@ __device__ __forceinline__ void row_prepare_body(
 
     RP_STAMP(1)
     // ---- sweep 1: every row's explicit weights summed in list order (Graph.cs:75)
-    double sum = 0.0, first = 0.0;
-    int64_t n_explicit = 0;
-    bool uni = true, neg = false;
+    RowSum rs;
     int64_t p = b;
-    if (L1 - L0 > 8 * (int64_t)RP_CAP) {
+    if (L1 - L0 > 8 * (int64_t)CAP) {
         // 64 LONG rows (hub items of a dense graph): a tile would hold a piece of one row only and the lanes would take
         // turns; here every lane walks its own row in global memory, eight entries in flight, all 64 rows side by side
         for (; p < e; p += 8) {
@@ -74,20 +88,12 @@ __device__ __forceinline__ void row_prepare_body(
                 tv[u] = etype[q];
             }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (p + u < e && tv[u] != RWR_EDGE_UNDEFINED) {
-                    const double wp = wv[u];
-                    if (n_explicit == 0) first = wp;
-                    else if (wp != first) uni = false;
-                    sum += wp;                           // Graph.cs:75, list order
-                    ++n_explicit;
-                    if (!(wp >= 0.0)) neg = true;
-                }
-            }
+            for (int u = 0; u < 8; ++u)
+                if (p + u < e) rs.add(tv[u], wv[u]);
         }
     }
-    for (int64_t T0 = L0; T0 < L1 && L1 - L0 <= 8 * (int64_t)RP_CAP; T0 += RP_CAP) {
-        const int64_t T1 = (T0 + RP_CAP < L1) ? T0 + RP_CAP : L1;
+    for (int64_t T0 = L0; T0 < L1 && L1 - L0 <= 8 * (int64_t)CAP; T0 += CAP) {
+        const int64_t T1 = (T0 + CAP < L1) ? T0 + CAP : L1;
         // (eight loads per lane in flight: as a plain copy loop every iteration waited for its own load, and in the
         //  one-launch build of an ego network -- one workgroup, nothing to hide latency behind -- that was 130 of 270 us)
         for (int64_t c0 = T0; c0 < T1; c0 += 8 * WAVE) {
@@ -117,35 +123,17 @@ __device__ __forceinline__ void row_prepare_body(
 #pragma unroll
             for (int u = 0; u < 4; ++u) { ty[u] = st[p - T0 + u]; wq[u] = sw[p - T0 + u]; }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (ty[u] != RWR_EDGE_UNDEFINED) {
-                    const double wp = wq[u];
-                    if (n_explicit == 0) first = wp;
-                    else if (wp != first) uni = false;
-                    sum += wp;                           // Graph.cs:75, list order
-                    ++n_explicit;
-                    if (!(wp >= 0.0)) neg = true;        // negative or NaN raw weight
-                }
-            }
+            for (int u = 0; u < 4; ++u) rs.add(ty[u], wq[u]);
         }
-        for (; p < pe; ++p) {
-            if (st[p - T0] != RWR_EDGE_UNDEFINED) {
-                const double wp = sw[p - T0];
-                if (n_explicit == 0) first = wp;
-                else if (wp != first) uni = false;
-                sum += wp;                               // Graph.cs:75, list order
-                ++n_explicit;
-                if (!(wp >= 0.0)) neg = true;            // negative or NaN raw weight
-            }
-        }
+        for (; p < pe; ++p) rs.add(st[p - T0], sw[p - T0]);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();                 // (the tile is overwritten next)
     }
     RP_STAMP(2)
-    ssum[lane] = sum;
+    ssum[lane] = rs.sum;
     if (lane < nrows) {
-        dangling[r0 + lane] = (n_explicit == 0) ? 1 : 0;             // Graph.cs:64,86
-        w_src[r0 + lane] = (n_explicit > 0) ? first / sum : 0.0;
+        dangling[r0 + lane] = (rs.n_explicit == 0) ? 1 : 0;             // Graph.cs:64,86
+        w_src[r0 + lane] = (rs.n_explicit > 0) ? rs.first / rs.sum : 0.0;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -186,9 +174,9 @@ __device__ __forceinline__ void row_prepare_body(
         }
     }
     RP_STAMP(3)
-    if (!uni) atomicOr(&flags[0], 1);
+    if (!rs.uni) atomicOr(&flags[0], 1);
     if (bad) atomicOr(&flags[1], 1);
-    if (lane < nrows && (neg || (n_explicit > 0 && !(sum > 0.0 && sum < __longlong_as_double(0x7ff0000000000000ll))))) atomicOr(&flags[3], 1);
+    if (lane < nrows && (rs.neg || (rs.n_explicit > 0 && !(rs.sum > 0.0 && rs.sum < __longlong_as_double(0x7ff0000000000000ll))))) atomicOr(&flags[3], 1);
 }
 
 __global__ __launch_bounds__(RP_WPB * WAVE) void k_row_prepare(
@@ -207,7 +195,7 @@ __global__ __launch_bounds__(RP_WPB * WAVE) void k_row_prepare(
 }
 
 // in_ptr[j] = first sorted position whose key >= j   (keys sorted ascending, sentinel n last)
-// (the element-wise bodies below are shared by the one-element-per-thread kernels of the general build and by the one-launch
+// (every element-wise *_body below is shared by a one-element-per-thread kernel of the general build and by the one-launch
 //  build of ego-network-sized graphs, k_build_small)
 __device__ __forceinline__ void in_ptr_body(int64_t p, const uint32_t *__restrict__ skey, int64_t m, int32_t n,
                                             int64_t *__restrict__ in_ptr)
@@ -224,20 +212,21 @@ __global__ __launch_bounds__(256) void k_in_ptr(const uint32_t *__restrict__ ske
     in_ptr_body((int64_t)blockIdx.x * blockDim.x + threadIdx.x, skey, m, n, in_ptr);
 }
 
-// (nnz_dev != nullptr: the number of explicit links is read on the device -- in_ptr[n] -- and `nnz` is only the launch's upper
-//  bound: ego-network-sized graphs are built without a host round trip in the middle)
-__global__ __launch_bounds__(256) void k_gather_in(const uint32_t *__restrict__ sval, int64_t nnz,
-                                                   const int32_t *__restrict__ esrc,
-                                                   const double *__restrict__ w_norm,
-                                                   int32_t *__restrict__ in_src, double *__restrict__ in_w,
-                                                   const int64_t *__restrict__ nnz_dev = nullptr)
+__device__ __forceinline__ void gather_in_body(int64_t p, const uint32_t *__restrict__ sval, int64_t nnz,
+                                               const int32_t *__restrict__ esrc, const double *__restrict__ w_norm,
+                                               int32_t *__restrict__ in_src, double *__restrict__ in_w)
 {
-    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (nnz_dev) nnz = *nnz_dev;
     if (p >= nnz) return;
     uint32_t e = sval[p];
     in_src[p] = esrc[e];
     if (in_w) in_w[p] = w_norm[e];     // (value-free graphs keep no per-entry weights)
+}
+__global__ __launch_bounds__(256) void k_gather_in(const uint32_t *__restrict__ sval, int64_t nnz,
+                                                   const int32_t *__restrict__ esrc,
+                                                   const double *__restrict__ w_norm,
+                                                   int32_t *__restrict__ in_src, double *__restrict__ in_w)
+{
+    gather_in_body((int64_t)blockIdx.x * blockDim.x + threadIdx.x, sval, nnz, esrc, w_norm, in_src, in_w);
 }
 
 // value-free graphs: the weight of entry p is the one weight of its source
@@ -249,24 +238,28 @@ __global__ __launch_bounds__(256) void k_fill_in_w(int64_t nnz, const int32_t *_
 }
 
 __device__ __forceinline__ void order_keys_body(int32_t i, int32_t n, const int64_t *__restrict__ in_ptr, uint32_t *__restrict__ dkey,
-                                                uint32_t *__restrict__ dval, int *__restrict__ maxdeg, int order_mode, uint32_t top)
+                                                uint32_t *__restrict__ dval, int order_mode, uint32_t top)
 {
     if (i >= n) return;
     uint32_t deg = (uint32_t)(in_ptr[i + 1] - in_ptr[i]);
-    // ascending sort of (top - deg) == in-degree descending (top = the link count, an upper bound of every in-degree: the
-    // keys then have only as many bits as the link count, and the radix sort as few passes); mode 2: by power-of-two
-    // degree class only (stable, so rows keep their natural order inside a class); mode 1: natural order
+    // ascending sort of (top - deg) == in-degree descending (top = any upper bound of the in-degrees: the general build takes
+    // the link count, so that the keys have only as many bits as it, and the radix sort as few passes; the one-launch build the
+    // largest in-degree itself); mode 2: by power-of-two degree class only (stable, so rows keep their natural order inside a
+    // class); mode 1: natural order
     dkey[i] = (order_mode == 1) ? 0u : (order_mode == 2) ? (uint32_t)__clz((int)deg) : (top - deg);
     dval[i] = (uint32_t)i;
-    atomicMax(maxdeg, (int)deg);
+}
+__device__ __forceinline__ void max_in_deg_body(int32_t i, int32_t n, const int64_t *__restrict__ in_ptr, int *__restrict__ maxdeg)
+{
+    if (i < n) atomicMax(maxdeg, (int)(in_ptr[i + 1] - in_ptr[i]));
 }
 __global__ __launch_bounds__(256) void k_order_keys(int32_t n, const int64_t *__restrict__ in_ptr,
-                                                    const uint8_t *__restrict__ node_type,
-                                                    const int64_t *__restrict__ node_id,
                                                     uint32_t *__restrict__ dkey, uint32_t *__restrict__ dval,
                                                     int *__restrict__ maxdeg, int order_mode, uint32_t top)
 {
-    order_keys_body(blockIdx.x * blockDim.x + threadIdx.x, n, in_ptr, dkey, dval, maxdeg, order_mode, top);
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    order_keys_body(i, n, in_ptr, dkey, dval, order_mode, top);
+    max_in_deg_body(i, n, in_ptr, maxdeg);
 }
 
 // single-seed SpMV order: phase (ITEM rows first) then in-degree descending
@@ -291,92 +284,33 @@ __global__ __launch_bounds__(256) void k_order_keys_phase(int32_t n, const int64
 // items by id descending: ascending sort of ~orderable(id) over the ITEM rows only (every 64-bit key value is a
 // legitimate id -- INT64_MIN maps to ~0 -- so non-items cannot be parked behind a sentinel key)
 // (keys are taken relative to the largest id, so that they have only as many bits as the id RANGE needs)
-__global__ void k_item_id_keys(int32_t n_items, const int32_t *__restrict__ item_rows, const int64_t *__restrict__ node_id,
-                               uint64_t *__restrict__ ikey, uint32_t *__restrict__ ival, uint64_t top)
+__device__ __forceinline__ void item_id_keys_body(int32_t q, int32_t n_items, const int32_t *__restrict__ item_rows,
+                                                  const int64_t *__restrict__ node_id, uint64_t *__restrict__ ikey,
+                                                  uint32_t *__restrict__ ival, uint64_t top)
 {
-    int32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n_items) return;
     const int32_t i = item_rows[q];
     ikey[q] = top - i64_orderable(node_id[i]);
     ival[q] = (uint32_t)i;
 }
-
-__global__ void k_item_flag_keys(int32_t n, const uint8_t *__restrict__ node_type, uint32_t *__restrict__ key,
-                                 uint32_t *__restrict__ val)
+__global__ void k_item_id_keys(int32_t n_items, const int32_t *__restrict__ item_rows, const int64_t *__restrict__ node_id,
+                               uint64_t *__restrict__ ikey, uint32_t *__restrict__ ival, uint64_t top)
 {
-    int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    item_id_keys_body(blockIdx.x * blockDim.x + threadIdx.x, n_items, item_rows, node_id, ikey, ival, top);
+}
+
+// ITEM rows in ascending row order: one stable pass on the flag (item ? 0 : 1)
+__device__ __forceinline__ void item_flag_keys_body(int32_t i, int32_t n, const uint8_t *__restrict__ node_type,
+                                                    uint32_t *__restrict__ key, uint32_t *__restrict__ val)
+{
     if (i >= n) return;
     key[i] = (node_type[i] == RWR_NODE_ITEM) ? 0u : 1u;
     val[i] = (uint32_t)i;
 }
-
-__global__ void k_u32_to_i32(const uint32_t *__restrict__ a, int32_t *__restrict__ b, int64_t m)
+__global__ void k_item_flag_keys(int32_t n, const uint8_t *__restrict__ node_type, uint32_t *__restrict__ key,
+                                 uint32_t *__restrict__ val)
 {
-    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < m) b[p] = (int32_t)a[p];
-}
-
-// rows of the batch's last steps (tail_rows_prepare): flag every source of an explicit link into a row of the previous
-// level, one wave per row of that level walking its transposed in-list -- the entries the SpMM gathers for that row
-__global__ __launch_bounds__(256) void k_tail_flag(int32_t nrows, const int32_t *__restrict__ rows,
-                                                   const int64_t *__restrict__ in_ptr, const int32_t *__restrict__ in_src,
-                                                   uint8_t *__restrict__ flag)
-{
-    const int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-    if (q >= nrows) return;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int32_t j = rows[q];
-    const int64_t p1 = in_ptr[j + 1];
-    for (int64_t p = in_ptr[j] + lane; p < p1; p += WAVE) flag[in_src[p]] = 1;
-}
-// ... the keys of a stable one-bit partition of row_order: rows whose flag equals `match` first; *count = how many, *links =
-// their in-links (what a launch over them gathers)
-__global__ __launch_bounds__(256) void k_tail_keys(int32_t n, const int32_t *__restrict__ row_order,
-                                                   const uint8_t *__restrict__ flag, uint8_t match,
-                                                   uint32_t *__restrict__ key, uint32_t *__restrict__ val, int *__restrict__ count,
-                                                   const int64_t *__restrict__ in_ptr, unsigned long long *__restrict__ links)
-{
-    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    bool in = false;
-    unsigned long long deg = 0;
-    if (r < n) {
-        const int32_t i = row_order[r];
-        in = flag[i] == match;
-        key[r] = in ? 0u : 1u;
-        val[r] = (uint32_t)i;
-        if (in) deg = (unsigned long long)(in_ptr[i + 1] - in_ptr[i]);
-    }
-    const unsigned long long b = __ballot(in);
-    for (int off = WAVE / 2; off > 0; off >>= 1) deg += __shfl_down(deg, off, WAVE);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && b) {
-        atomicAdd(count, (int)__popcll(b));
-        atomicAdd(links, deg);
-    }
-}
-// ... and the seed-row flag of step T - 1: node s has an explicit raw link into an ITEM row that is not also the target of
-// one of its raw LIKE links.  Only such a link carries s's rank at step T - 1 into a row the ranking reads: k_exclude drops
-// the targets of the LIKE links, and UNDEFINED links are no matrix entries.  One wave per node; a node with more than
-// TAIL_SCAN_MAX raw links is flagged without the pairwise search (a flag that need not be set only costs a chain)
-constexpr int64_t TAIL_SCAN_MAX = 4096;
-__global__ __launch_bounds__(256) void k_tail_seed_flag(int32_t n, const int64_t *__restrict__ rowptr,
-                                                        const int32_t *__restrict__ dst, const uint8_t *__restrict__ etype,
-                                                        const uint8_t *__restrict__ node_type, uint8_t *__restrict__ flag)
-{
-    const int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-    if (s >= n) return;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int64_t p0 = rowptr[s], p1 = rowptr[s + 1];
-    bool reach = false;
-    for (int64_t p = p0 + lane; p < p1; p += WAVE) {
-        const uint8_t ty = etype[p];
-        const int32_t t = dst[p];
-        if (ty == RWR_EDGE_UNDEFINED || ty == RWR_EDGE_LIKE || t < 0 || t >= n || node_type[t] != RWR_NODE_ITEM) continue;
-        bool liked = false;
-        if (p1 - p0 <= TAIL_SCAN_MAX)
-            for (int64_t q = p0; q < p1 && !liked; ++q) liked = etype[q] == RWR_EDGE_LIKE && dst[q] == t;
-        reach = reach || !liked;
-    }
-    if (__ballot(reach) && lane == 0) flag[s] = 1;
+    item_flag_keys_body(blockIdx.x * blockDim.x + threadIdx.x, n, node_type, key, val);
 }
 
 // incremental rebuild: overwrite type and/or weight of the listed raw links
@@ -391,80 +325,14 @@ __global__ __launch_bounds__(256) void k_patch_links(int64_t count, const int64_
     if (new_w) w[p] = new_w[q];
 }
 
-// Ego-network-sized graphs: the six raw arrays arrive as ONE copy out of a pinned staging buffer and are dealt to their
-// device arrays by this kernel (six pageable copies cost ~100 us of a ~0.5 ms build); what the host needs back (link count,
-// flags, in_ptr, dangling) is written by k_stage_out straight into pinned host memory.
-constexpr int32_t STAGE_MAX_N = 8192;
-constexpr int64_t STAGE_MAX_M = 65536;
-constexpr size_t STAGE_OUT_OFF = 1u << 20;                                    // inputs below, outputs above
-constexpr size_t STAGE_BYTES = STAGE_OUT_OFF + 8 * (size_t)(STAGE_MAX_N + 1) + STAGE_MAX_N + 256;
-struct StageLayout { size_t id, rp, w, dst, nt, et, total; };
-static StageLayout stage_layout(int32_t n, int64_t m)
-{
-    StageLayout L;
-    L.id = 0;
-    L.rp = L.id + 8 * (size_t)n;
-    L.w = L.rp + 8 * ((size_t)n + 1);
-    L.dst = L.w + 8 * (size_t)m;
-    L.nt = L.dst + ((4 * (size_t)m + 7) & ~(size_t)7);
-    L.et = L.nt + (((size_t)n + 7) & ~(size_t)7);
-    L.total = L.et + (size_t)m;
-    return L;
-}
-__global__ __launch_bounds__(256) void k_stage_in(int32_t n, int64_t m, const uint8_t *__restrict__ st, StageLayout L,
-                                                  int64_t *__restrict__ node_id, uint8_t *__restrict__ node_type,
-                                                  int64_t *__restrict__ rowptr, int32_t *__restrict__ dst,
-                                                  uint8_t *__restrict__ etype, double *__restrict__ w)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        node_id[i] = reinterpret_cast<const int64_t *>(st + L.id)[i];
-        node_type[i] = st[L.nt + i];
-    }
-    if (i <= n) rowptr[i] = reinterpret_cast<const int64_t *>(st + L.rp)[i];
-    if (i < m) {
-        w[i] = reinterpret_cast<const double *>(st + L.w)[i];
-        dst[i] = reinterpret_cast<const int32_t *>(st + L.dst)[i];
-        etype[i] = st[L.et + i];
-    }
-}
-// out: [0] link count (int64), [8..24) flags, [32 ...) in_ptr (n+1 int64) when `full`, then dangling (n bytes)
-__global__ __launch_bounds__(256) void k_stage_out(int32_t n, const int64_t *__restrict__ in_ptr, const int *__restrict__ flags,
-                                                   const uint8_t *__restrict__ dangling, uint8_t *__restrict__ out, int full)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) {
-        reinterpret_cast<int64_t *>(out)[0] = in_ptr[n];
-        for (int q = 0; q < 4; ++q) reinterpret_cast<int *>(out + 8)[q] = flags[q];
-    }
-    if (full) {
-        if (i <= n) reinterpret_cast<int64_t *>(out + 32)[i] = in_ptr[i];
-        if (i < n) (out + 32 + 8 * ((size_t)n + 1))[i] = dangling[i];
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Ego-network-sized graphs (n <= STAGE_MAX_N, m <= STAGE_MAX_M): the WHOLE device-side build -- unpack the staging copy,
+// Ego-network-sized graphs (stage_layout.h: n <= ONE_LAUNCH_MAX_N, m <= ONE_LAUNCH_MAX_M): the WHOLE device-side build -- unpack the staging copy,
 // Graph.buildGraph's row pass, the stable transpose, the processing orders, the read-back into pinned memory -- as ONE launch
 // of one 1024-thread workgroup, with workgroup barriers where the general build has 18 kernel boundaries.  The reference
 // rebuilds such a graph per fold and methodology (Experiment.cs:69-105); its build was launch-bound: 18 dependent launches
 // of a few microseconds of work each cost ~270 us, the work itself ~60.  Same element-wise bodies, same sorts, same order of
 // operations per element as the general path (k_row_prepare, k_in_ptr, k_gather_in, k_order_keys*, k_item_*): bit-identical
 // arrays (tests/test_gpu_parity.py: test_build_graph_bitwise, the golden fixtures, the hypothesis graphs, incremental rebuilds).
-struct BuildSmallArgs {
-    int32_t n, n_items, first, do_stage_in;
-    int32_t zero_flags, pad0;        // the kernel clears the flag words itself (batch builds: no memset per graph)
-    int64_t m;
-    const uint8_t *stage; StageLayout L;
-    int64_t *node_id; uint8_t *node_type; int64_t *rowptr; int32_t *dst; uint8_t *etype; double *w_raw;
-    double *w_norm; int32_t *esrc; uint32_t *skey, *skey2, *sval, *sval2; uint8_t *dangling; double *w_src; int *flags;
-    int64_t *in_ptr; int32_t *in_src; double *in_w;
-    int32_t *row_order, *row_order_x, *item_rows, *item_order;
-    uint64_t *ikey, *ikey2; uint32_t *ival, *ival2;
-    int order_mode; uint32_t top; int top_bits; uint32_t ptop; int ptop_bits; int n_bits; uint64_t id_key_top; int id_key_bits;
-    uint8_t *pin_out;
-    unsigned long long *stamps;      // experiments build: s_memrealtime (100 MHz) at the stage boundaries; nullptr otherwise
-};
 #ifdef RWR_EXPERIMENTS
 #define BS_STAMP(I) { if (a.stamps && tid == 0) a.stamps[(I)] = __builtin_amdgcn_s_memrealtime(); }
 #else
@@ -524,25 +392,17 @@ __device__ __forceinline__ void build_small_body(const BuildSmallArgs &a)
     for (int64_t p = tid; p <= m; p += NT) in_ptr_body(p, k_sorted, m, n, a.in_ptr);
     __syncthreads();
     const int64_t nnz = a.in_ptr[n];
-    for (int64_t p = tid; p < nnz; p += NT) {
-        const uint32_t e = v_sorted[p];
-        a.in_src[p] = a.esrc[e];
-        a.in_w[p] = a.w_norm[e];
-    }
+    for (int64_t p = tid; p < nnz; p += NT) gather_in_body(p, v_sorted, nnz, a.esrc, a.w_norm, a.in_src, a.in_w);
     __syncthreads();
     BS_STAMP(4)
     // ---- destination-row processing orders.  Same permutations as the general build's two sorts -- (top - deg) ascending,
     // stable, for any bound `top` of the in-degrees; (phase, top - deg) ascending, stable -- in fewer radix passes: the first
     // keyed on the graph's own largest in-degree (one 8-bit pass for most ego networks instead of two), the second as ONE
     // stable pass on the phase bit over the first one's result (LSD order: least significant key first).
-    for (int32_t i = tid; i < n; i += NT) atomicMax(a.flags + 2, (int)(a.in_ptr[i + 1] - a.in_ptr[i]));
+    for (int32_t i = tid; i < n; i += NT) max_in_deg_body(i, n, a.in_ptr, a.flags + 2);
     __syncthreads();
     const uint32_t maxdeg = (uint32_t)__hip_atomic_load(a.flags + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int32_t i = tid; i < n; i += NT) {
-        const uint32_t deg = (uint32_t)(a.in_ptr[i + 1] - a.in_ptr[i]);
-        a.skey[i] = (a.order_mode == 1) ? 0u : (a.order_mode == 2) ? (uint32_t)__clz((int)deg) : (maxdeg - deg);
-        a.sval[i] = (uint32_t)i;
-    }
+    for (int32_t i = tid; i < n; i += NT) order_keys_body(i, n, a.in_ptr, a.skey, a.sval, a.order_mode, maxdeg);
     __syncthreads();
     {
         int bits = 1;
@@ -564,20 +424,14 @@ __device__ __forceinline__ void build_small_body(const BuildSmallArgs &a)
     __syncthreads();
     BS_STAMP(5)
     if (a.first) {   // (the node arrays never change: an incremental rebuild keeps both item orders)
-        for (int32_t i = tid; i < n; i += NT) {
-            a.skey[i] = (a.node_type[i] == RWR_NODE_ITEM) ? 0u : 1u;
-            a.sval[i] = (uint32_t)i;
-        }
+        for (int32_t i = tid; i < n; i += NT) item_flag_keys_body(i, n, a.node_type, a.skey, a.sval);
         __syncthreads();
         sort_small_body<uint32_t>(sortlds, a.skey, a.skey2, a.sval, a.sval2, (uint32_t)n, 8);
         for (int32_t i = tid; i < a.n_items; i += NT) a.item_rows[i] = (int32_t)a.sval2[i];    // (one pass: the result is in the alternate buffer)
         __syncthreads();
         if (a.n_items > 0) {
-            for (int32_t q = tid; q < a.n_items; q += NT) {
-                const int32_t i = a.item_rows[q];
-                a.ikey[q] = a.id_key_top - i64_orderable(a.node_id[i]);
-                a.ival[q] = (uint32_t)i;
-            }
+            for (int32_t q = tid; q < a.n_items; q += NT)
+                item_id_keys_body(q, a.n_items, a.item_rows, a.node_id, a.ikey, a.ival, a.id_key_top);
             __syncthreads();
             sort_small_body<uint64_t>(sortlds, a.ikey, a.ikey2, a.ival, a.ival2, (uint32_t)a.n_items, a.id_key_bits);
             const uint32_t *res = (((a.id_key_bits + 7) / 8) & 1) ? a.ival2 : a.ival;
@@ -590,12 +444,12 @@ __device__ __forceinline__ void build_small_body(const BuildSmallArgs &a)
     __threadfence_block();
     __syncthreads();
     if (tid == 0) {
-        reinterpret_cast<int64_t *>(a.pin_out)[0] = a.in_ptr[n];
-        for (int q = 0; q < 4; ++q) reinterpret_cast<int *>(a.pin_out + 8)[q] = a.flags[q];
+        *reinterpret_cast<int64_t *>(a.pin_out + STAGE_OUT_NNZ) = a.in_ptr[n];
+        for (int q = 0; q < 4; ++q) reinterpret_cast<int *>(a.pin_out + STAGE_OUT_FLAGS)[q] = a.flags[q];
     }
     for (int64_t i = tid; i <= n; i += NT) {
-        reinterpret_cast<int64_t *>(a.pin_out + 32)[i] = a.in_ptr[i];
-        if (i < n) (a.pin_out + 32 + 8 * ((size_t)n + 1))[i] = a.dangling[i];
+        reinterpret_cast<int64_t *>(a.pin_out + STAGE_OUT_IN_PTR)[i] = a.in_ptr[i];
+        if (i < n) (a.pin_out + stage_out_dangling(n))[i] = a.dangling[i];
     }
     BS_STAMP(7)
 }
@@ -605,28 +459,26 @@ __global__ __launch_bounds__(SMALL_SORT_THREADS) void k_build_small_multi(const 
 {
     build_small_body(args[blockIdx.x]);
 }
-
-static int bit_length(uint64_t v)
+int32_t launch_build_small(const BuildSmallArgs &a, hipStream_t s)
 {
-    int b = 0;
-    while (v) { ++b; v >>= 1; }
-    return b;
+    hipLaunchKernelGGL(k_build_small, dim3(1), dim3(SMALL_SORT_THREADS), 0, s, a);
+    RWR_HIP(hipGetLastError());
+    return RWR_OK;
 }
-
-static int32_t graph_derive(rwr_graph *g, bool first);
-
-static double bt_now()
+int32_t launch_build_small_multi(const BuildSmallArgs *d_args, int32_t count, hipStream_t s)
 {
-    using namespace std::chrono;
-    return duration<double, std::micro>(steady_clock::now().time_since_epoch()).count();
+    hipLaunchKernelGGL(k_build_small_multi, dim3((unsigned)count), dim3(SMALL_SORT_THREADS), 0, s, d_args);
+    RWR_HIP(hipGetLastError());
+    return RWR_OK;
 }
-static const bool bt_on = [] { const char *e = RWR_TUNE_ENV("RWR_BUILD_TIMING"); return e && atoi(e) != 0; }();
-#define BT(label) do { if (bt_on) { const double t__ = bt_now(); fprintf(stderr, "[build] %-28s %8.1f us\n", label, t__ - bt_t); bt_t = t__; } } while (0)
+#ifdef RWR_EXPERIMENTS
+void row_pass_stamps(unsigned long long out[16]) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(rp_dbg), 16 * sizeof(unsigned long long)); }
+#endif
 
 // uploads the RAW lists (they stay resident: the exclusion list reads them, Recommender.cs:20-24, and an incremental
-// rebuild re-derives everything else from them), then derives the walk's data
-static int32_t graph_build_upload(rwr_graph *g, const int64_t *node_id, const uint8_t *node_type, const int64_t *rowptr,
-                                  const int32_t *dst, const uint8_t *etype, const double *w)
+// rebuild re-derives everything else from them)
+int32_t graph_build_upload(rwr_graph *g, const int64_t *node_id, const uint8_t *node_type, const int64_t *rowptr,
+                           const int32_t *dst, const uint8_t *etype, const double *w)
 {
     const int32_t n = g->n;
     const int64_t m = g->nnz_raw;
@@ -650,7 +502,7 @@ static int32_t graph_build_upload(rwr_graph *g, const int64_t *node_id, const ui
     // items by id DESCENDING = ascending (id_hi - key): as many key bits as the id range needs (ids of a loader are
     // small consecutive numbers: two radix passes instead of eight)
     g->id_key_top = n_items > 0 ? id_hi : 0;
-    g->id_key_bits = n_items > 0 ? (bit_length(id_hi - id_lo) > 0 ? bit_length(id_hi - id_lo) : 1) : 1;
+    g->id_key_bits = n_items > 0 ? key_bits(id_hi - id_lo) : 1;
 
     RWR_TRY(g->node_id.alloc(n));
     RWR_TRY(g->node_type.alloc(n));
@@ -670,8 +522,7 @@ static int32_t graph_build_upload(rwr_graph *g, const int64_t *node_id, const ui
     RWR_TRY(g->item_rows.alloc(n_items));
 
     BT("host prep + allocs");
-    static const int stage_env = [] { const char *e = RWR_TUNE_ENV("RWR_STAGE"); return e ? atoi(e) : 1; }();
-    g->staged = stage_env && n <= STAGE_MAX_N && m <= STAGE_MAX_M;
+    g->staged = graph_fits_small_build(n, m);   // (a staged upload is unpacked by the one-launch build alone)
     if (g->staged) {
         if (!g->sm_stage) RWR_HIP(hipHostMalloc(&g->sm_stage, STAGE_BYTES, hipHostMallocMapped | hipHostMallocPortable));
         const StageLayout L = stage_layout(n, m);
@@ -702,6 +553,8 @@ static int32_t graph_build_upload(rwr_graph *g, const int64_t *node_id, const ui
     BT("H2D enqueue");
     return RWR_OK;
 }
+
+static int32_t graph_derive(rwr_graph *g, bool first);
 
 int32_t graph_build(rwr_graph *g, const int64_t *node_id, const uint8_t *node_type, const int64_t *rowptr,
                     const int32_t *dst, const uint8_t *etype, const double *w)
@@ -746,8 +599,27 @@ int32_t graph_update_links(rwr_graph *g, int64_t count, const int64_t *idx, cons
     return graph_derive(g, false);
 }
 
-// host side of a finished build: bins of the in-degree orders, statistics
-static int32_t derive_finish(rwr_graph *g, const int *h_flags, hipEvent_t e0, hipEvent_t e1)
+int row_order_mode()
+{
+    static const int mode = [] { const char *e = RWR_TUNE_ENV("RWR_ROW_ORDER"); return e ? atoi(e) : 0; }();
+    return mode;
+}
+
+int32_t graph_apply_flags(rwr_graph *g, int64_t nnz, const int *h_flags)
+{
+    static const int vf_env = [] { const char *e = getenv("RWR_VALUE_FREE"); return e ? atoi(e) : 1; }();
+    if (h_flags[1]) {
+        set_error("rwr_graph_create: a link targets a node outside [0, %d)", g->n);
+        return RWR_E_RANGE;
+    }
+    g->nnz = nnz;
+    g->uniform = h_flags[0] ? 0 : 1;
+    g->nonneg = h_flags[3] ? 0 : 1;
+    g->vf = (g->uniform && g->nonneg && vf_env) ? 1 : 0;
+    return RWR_OK;
+}
+
+int32_t derive_finish(rwr_graph *g, const int *h_flags, hipEvent_t e0, hipEvent_t e1)
 {
     const int32_t n = g->n;
     double bt_t = bt_now();
@@ -780,85 +652,6 @@ static int32_t derive_finish(rwr_graph *g, const int *h_flags, hipEvent_t e0, hi
     return RWR_OK;
 }
 
-// ---- the one-launch build of an ego-network-sized graph, in two halves around its launch: a single graph launches
-// k_build_small in between (graph_derive), a batch of graphs one k_build_small_multi for all of them (graphs_build_multi)
-struct SmallBuild {
-    DevBuf<int32_t> esrc;
-    DevBuf<uint32_t> skey, skey2, sval, sval2, ival, ival2;
-    DevBuf<uint64_t> ikey, ikey2;
-    DevBuf<int> flags;
-    BuildSmallArgs a{};
-};
-static bool small_build_ok(const rwr_graph *g)
-{
-    static const bool by_degree = [] { const char *e = RWR_TUNE_ENV("RWR_ROW_ORDER"); return !e || atoi(e) == 0; }();
-    return g->staged && g->sm_stage && g->n <= STAGE_MAX_N && g->nnz_raw <= STAGE_MAX_M && by_degree;
-}
-static int32_t small_build_begin(rwr_graph *g, bool first, SmallBuild &b)
-{
-    const int32_t n = g->n;
-    const int64_t m = g->nnz_raw;
-    // the (key, value) buffers serve the link sort (m entries) AND, afterwards, the row-order / item sorts (n entries)
-    const size_t kv = (size_t)(m > (int64_t)n ? m : (int64_t)n);
-    RWR_TRY(b.esrc.alloc(m));
-    RWR_TRY(b.skey.alloc(kv));
-    RWR_TRY(b.skey2.alloc(kv));
-    RWR_TRY(b.sval.alloc(kv));
-    RWR_TRY(b.sval2.alloc(kv));
-    RWR_TRY(b.flags.alloc(4));
-    RWR_TRY(b.ikey.alloc(n));
-    RWR_TRY(b.ikey2.alloc(n));
-    RWR_TRY(b.ival.alloc(n));
-    RWR_TRY(b.ival2.alloc(n));
-    RWR_TRY(g->in_src.ensure((size_t)m + 64));
-    RWR_TRY(g->in_w.ensure((size_t)(m > 0 ? m : 1)));
-    BuildSmallArgs &a = b.a;
-    a = BuildSmallArgs{};
-    a.n = n; a.n_items = g->n_items; a.first = first ? 1 : 0; a.do_stage_in = g->stage_pending ? 1 : 0; a.m = m;
-    a.zero_flags = 1;
-    a.stage = g->stage_dev_ext ? g->stage_dev_ext : g->d_stage.p; a.L = stage_layout(n, m);
-    a.node_id = g->node_id.p; a.node_type = g->node_type.p; a.rowptr = g->rowptr.p; a.dst = g->dst.p; a.etype = g->etype.p;
-    a.w_raw = g->w_raw.p; a.w_norm = g->w_norm_raw.p; a.esrc = b.esrc.p; a.skey = b.skey.p; a.skey2 = b.skey2.p; a.sval = b.sval.p;
-    a.sval2 = b.sval2.p; a.dangling = g->dangling.p; a.w_src = g->w_src.p; a.flags = b.flags.p; a.in_ptr = g->in_ptr.p;
-    a.in_src = g->in_src.p; a.in_w = g->in_w.p; a.row_order = g->row_order.p; a.row_order_x = g->row_order_x.p;
-    a.item_rows = g->item_rows.p; a.item_order = g->item_order.p; a.ikey = b.ikey.p; a.ikey2 = b.ikey2.p; a.ival = b.ival.p;
-    a.ival2 = b.ival2.p;
-    a.order_mode = 0;
-    a.top = (uint32_t)m;                                   // (any bound of the in-degrees gives the same order)
-    a.top_bits = bit_length((uint64_t)m) > 0 ? bit_length((uint64_t)m) : 1;
-    a.ptop_bits = a.top_bits > 31 ? 31 : a.top_bits;
-    a.ptop = a.top_bits > 31 ? 0x7FFFFFFFu : a.top;
-    a.n_bits = bit_length((uint64_t)n);
-    a.id_key_top = g->id_key_top; a.id_key_bits = g->id_key_bits;
-    a.pin_out = g->sm_out ? g->sm_out : static_cast<uint8_t *>(g->sm_stage) + STAGE_OUT_OFF;
-    a.stamps = nullptr;
-    return RWR_OK;
-}
-// after the stream the build ran on has been synchronised
-static int32_t small_build_end(rwr_graph *g, SmallBuild &b, hipEvent_t e0, hipEvent_t e1)
-{
-    static const int vf_env_s = [] { const char *e = getenv("RWR_VALUE_FREE"); return e ? atoi(e) : 1; }();
-    const int32_t n = g->n;
-    const uint8_t *pin = b.a.pin_out;
-    int h_flags[4];
-    g->stage_pending = 0;
-    g->h_in_ptr.resize((size_t)n + 1);
-    g->h_dangling.resize((size_t)n);
-    const int64_t nnz_s = reinterpret_cast<const int64_t *>(pin)[0];
-    memcpy(h_flags, pin + 8, sizeof(h_flags));
-    memcpy(g->h_in_ptr.data(), pin + 32, sizeof(int64_t) * ((size_t)n + 1));
-    memcpy(g->h_dangling.data(), pin + 32 + 8 * ((size_t)n + 1), (size_t)n);
-    if (h_flags[1]) {
-        set_error("rwr_graph_create: a link targets a node outside [0, %d)", n);
-        return RWR_E_RANGE;
-    }
-    g->nnz = nnz_s;
-    g->uniform = h_flags[0] ? 0 : 1;
-    g->nonneg = h_flags[3] ? 0 : 1;
-    g->vf = (g->uniform && g->nonneg && vf_env_s) ? 1 : 0;   // (in_w stays: small.hip reads it)
-    return derive_finish(g, h_flags, e0, e1);
-}
-
 // Graph.buildGraph + transpose + processing orders, from the device-resident raw lists
 static int32_t graph_derive(rwr_graph *g, bool first)
 {
@@ -870,6 +663,7 @@ static int32_t graph_derive(rwr_graph *g, bool first)
     g->sw_partial = 0;
     g->tail_state = 0;   // a link's type or weight may have changed which rows link into ITEM rows
     g->part_G = 0;   // a row-partitioned run sized for the previous matrix is over: rwr_part_step asks for a new rwr_part_begin
+    if (small_build_ok(g)) return graph_derive_small(g, first);   // one launch, one synchronisation (build_small.hip)
 
     const int32_t n = g->n;
     const int64_t m = g->nnz_raw;
@@ -877,37 +671,6 @@ static int32_t graph_derive(rwr_graph *g, bool first)
     hipStream_t s = g->stream;
     double bt_t = bt_now();
     hipEvent_t e0 = g->ev_a, e1 = g->ev_b;
-    if (small_build_ok(g)) {
-        // ego-network-sized graph: the whole device-side build is ONE launch (k_build_small) and one synchronisation
-        SmallBuild b;
-        RWR_TRY(small_build_begin(g, first, b));
-        BT("derive allocs");
-#ifdef RWR_EXPERIMENTS
-        DevBuf<unsigned long long> stamps_d;
-        if (bt_on) { RWR_TRY(stamps_d.alloc(8)); b.a.stamps = stamps_d.p; }
-#endif
-        RWR_HIP(hipEventRecord(e0, s));
-        hipLaunchKernelGGL(k_build_small, dim3(1), dim3(SMALL_SORT_THREADS), 0, s, b.a);
-        RWR_HIP(hipGetLastError());
-        RWR_HIP(hipEventRecord(e1, s));
-        BT("enqueue one-launch build");
-        RWR_HIP(hipStreamSynchronize(s));                      // the ONE synchronisation of an ego-network-sized build
-        BT("sync (whole build)");
-#ifdef RWR_EXPERIMENTS
-        if (bt_on) {
-            unsigned long long hs[8];
-            RWR_HIP(hipMemcpy(hs, stamps_d.p, sizeof(hs), hipMemcpyDeviceToHost));
-            unsigned long long rp[16];
-            (void)hipMemcpyFromSymbol(rp, HIP_SYMBOL(rp_dbg), sizeof(rp));
-            fprintf(stderr, "[build] row pass of group 0 (us): setup %.1f sweep1 %.1f sweep2 %.1f; started %.1f after stage 1\n", (rp[1] - rp[0]) / 100.0,
-                    (rp[2] - rp[1]) / 100.0, (rp[3] - rp[2]) / 100.0, (rp[0] - hs[1]) / 100.0);
-            fprintf(stderr, "[build] k_build_small stages (us): unpack %.1f rows %.1f linksort %.1f in_ptr+gather %.1f orders %.1f items %.1f out %.1f\n",
-                    (hs[1] - hs[0]) / 100.0, (hs[2] - hs[1]) / 100.0, (hs[3] - hs[2]) / 100.0, (hs[4] - hs[3]) / 100.0, (hs[5] - hs[4]) / 100.0,
-                    (hs[6] - hs[5]) / 100.0, (hs[7] - hs[6]) / 100.0);
-        }
-#endif
-        return small_build_end(g, b, e0, e1);
-    }
     DevBuf<int32_t> esrc;
     DevBuf<uint32_t> skey, skey2, sval, sval2;
     DevBuf<uint8_t> temp;
@@ -930,15 +693,6 @@ static int32_t graph_derive(rwr_graph *g, bool first)
     BT("derive allocs");
     RWR_HIP(hipEventRecord(e0, s));
 
-    if (g->stage_pending) {   // (staged upload, general build: unpack the copy by its own kernel)
-        const StageLayout L = stage_layout(n, m);
-        const int64_t work = (m > (int64_t)n + 1) ? m : (int64_t)n + 1;
-        hipLaunchKernelGGL(k_stage_in, dim3(cdiv((size_t)work, 256)), dim3(256), 0, s, n, m, g->d_stage.p, L, g->node_id.p,
-                           g->node_type.p, g->rowptr.p, g->dst.p, g->etype.p, g->w_raw.p);
-        RWR_HIP(hipGetLastError());
-        g->stage_pending = 0;
-    }
-
     hipLaunchKernelGGL(k_row_prepare, dim3(cdiv(n, RP_WPB * WAVE)), dim3(RP_WPB * WAVE), 0, s, n, g->rowptr.p, g->dst.p, g->etype.p,
                        g->w_raw.p, g->w_norm_raw.p, esrc.p, skey.p, sval.p, g->dangling.p, g->w_src.p, flags.p);
     RWR_HIP(hipGetLastError());
@@ -952,123 +706,66 @@ static int32_t graph_derive(rwr_graph *g, bool first)
     hipLaunchKernelGGL(k_in_ptr, dim3(cdiv((size_t)m + 1, 256)), dim3(256), 0, s, k_sorted, m, n, g->in_ptr.p);
     RWR_HIP(hipGetLastError());
     int64_t nnz = 0;
-    const bool staged = g->staged && g->sm_stage;
-    uint8_t *pin_out = staged ? static_cast<uint8_t *>(g->sm_stage) + STAGE_OUT_OFF : nullptr;
-    static const int vf_env = [] { const char *e = getenv("RWR_VALUE_FREE"); return e ? atoi(e) : 1; }();
-    int64_t nnz_bound = 0;          // what the launches below are sized for
-    if (staged) {
-        // ego-network-sized graph: NO host round trip here.  The number of explicit links (<= m) stays on the device, the
-        // in-lists are sized for m, the per-entry weights are always built (such graphs carry MENTION weights, and the
-        // one-launch kernel of small.hip reads them anyway), and the checks wait for the one synchronisation at the end:
-        // a link with a bad target was keyed to the sentinel row and is harmless until then.  (The mid-way synchronisation
-        // cost ~45 us of host round trip and left the second half of the pipeline un-enqueued meanwhile.)
-        nnz_bound = m;
-        RWR_TRY(g->in_src.ensure((size_t)m + 64));
-        RWR_TRY(g->in_w.ensure((size_t)(m > 0 ? m : 1)));
-        if (m > 0) {
-            hipLaunchKernelGGL(k_gather_in, dim3(cdiv((size_t)m, 256)), dim3(256), 0, s, v_sorted, m, esrc.p, g->w_norm_raw.p,
-                               g->in_src.p, g->in_w.p, g->in_ptr.p + n);
-            RWR_HIP(hipGetLastError());
-        }
-        BT("enqueue row pass + link sort + gather");
-    } else {
-        RWR_HIP(hipMemcpyAsync(&nnz, g->in_ptr.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        RWR_HIP(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, s));
-        BT("enqueue row pass + link sort");
-        RWR_HIP(hipStreamSynchronize(s));
-        BT("sync 1 (H2D + row pass + sort)");
-        if (h_flags[1]) {
-            set_error("rwr_graph_create: a link targets a node outside [0, %d)", n);
-            return RWR_E_RANGE;
-        }
-        g->nnz = nnz;
-        g->uniform = h_flags[0] ? 0 : 1;
-        g->nonneg = h_flags[3] ? 0 : 1;
-        g->vf = (g->uniform && g->nonneg && vf_env) ? 1 : 0;
-        nnz_bound = nnz;
-        RWR_TRY(g->in_src.ensure((size_t)nnz + 64));   // (padded: wide index loads may run past a row's end)
-        if (g->vf) g->in_w.release();
-        else RWR_TRY(g->in_w.ensure((size_t)nnz));
-        if (nnz > 0) {
-            hipLaunchKernelGGL(k_gather_in, dim3(cdiv((size_t)nnz, 256)), dim3(256), 0, s, v_sorted, nnz, esrc.p,
-                               g->w_norm_raw.p, g->in_src.p, g->vf ? (double *)nullptr : g->in_w.p);
-            RWR_HIP(hipGetLastError());
-        }
+    RWR_HIP(hipMemcpyAsync(&nnz, g->in_ptr.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    RWR_HIP(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, s));
+    BT("enqueue row pass + link sort");
+    RWR_HIP(hipStreamSynchronize(s));
+    BT("sync 1 (H2D + row pass + sort)");
+    RWR_TRY(graph_apply_flags(g, nnz, h_flags));
+    RWR_TRY(g->in_src.ensure((size_t)nnz + 64));   // (padded: wide index loads may run past a row's end)
+    if (g->vf) g->in_w.release();
+    else RWR_TRY(g->in_w.ensure((size_t)nnz));
+    if (nnz > 0) {
+        hipLaunchKernelGGL(k_gather_in, dim3(cdiv((size_t)nnz, 256)), dim3(256), 0, s, v_sorted, nnz, esrc.p,
+                           g->w_norm_raw.p, g->in_src.p, g->vf ? (double *)nullptr : g->in_w.p);
+        RWR_HIP(hipGetLastError());
     }
 
     // destination-row processing order (in-degree descending) and ITEM rows by id descending
-    const char *om = RWR_TUNE_ENV("RWR_ROW_ORDER");
-    const int order_mode = om ? atoi(om) : 0;
+    const int order_mode = row_order_mode();
     DevBuf<uint64_t> ikey, ikey2;
     DevBuf<uint32_t> ival, ival2;
     RWR_TRY(ikey.alloc(n));
     RWR_TRY(ikey2.alloc(n));
     RWR_TRY(ival.alloc(n));
     RWR_TRY(ival2.alloc(n));
-    // (every in-degree is <= the number of explicit links: `top - deg` keys need bit_length(nnz) bits, not 32; any bound of
+    // (every in-degree is <= the number of explicit links: `top - deg` keys need key_bits(nnz) bits, not 32; any bound of
     //  the in-degrees gives the same order)
-    const uint32_t top = (uint32_t)nnz_bound;
-    const int top_bits = bit_length((uint64_t)nnz_bound) > 0 ? bit_length((uint64_t)nnz_bound) : 1;
-    hipLaunchKernelGGL(k_order_keys, dim3(cdiv(n, 256)), dim3(256), 0, s, n, g->in_ptr.p, g->node_type.p,
-                       g->node_id.p, skey.p, sval.p, flags.p + 2, order_mode, top);
+    const uint32_t top = (uint32_t)nnz;
+    const int top_bits = key_bits((uint64_t)nnz);
+    hipLaunchKernelGGL(k_order_keys, dim3(cdiv(n, 256)), dim3(256), 0, s, n, g->in_ptr.p, skey.p, sval.p, flags.p + 2,
+                       order_mode, top);
     RWR_HIP(hipGetLastError());
     RWR_TRY(radix_sort_pairs<uint32_t>(skey.p, skey2.p, sval.p, sval2.p, (size_t)n, 1, order_mode == 0 ? top_bits : 8, temp.p, s, &alt));
-    hipLaunchKernelGGL(k_u32_to_i32, dim3(cdiv(n, 256)), dim3(256), 0, s, alt ? sval2.p : sval.p, g->row_order.p,
-                       (int64_t)n);
+    launch_u32_to_i32(alt ? sval2.p : sval.p, g->row_order.p, n, s);
     // (from 2^31 links on the in-degree key is capped at 31 bits -- longer rows all sort first -- so that the phase bit fits)
     const int ptop_bits = top_bits > 31 ? 31 : top_bits;
     const uint32_t ptop = top_bits > 31 ? 0x7FFFFFFFu : top;
     hipLaunchKernelGGL(k_order_keys_phase, dim3(cdiv(n, 256)), dim3(256), 0, s, n, g->in_ptr.p, g->node_type.p, skey.p, sval.p,
                        ptop, ptop_bits);
     RWR_TRY(radix_sort_pairs<uint32_t>(skey.p, skey2.p, sval.p, sval2.p, (size_t)n, 1, ptop_bits + 1, temp.p, s, &alt));
-    hipLaunchKernelGGL(k_u32_to_i32, dim3(cdiv(n, 256)), dim3(256), 0, s, alt ? sval2.p : sval.p, g->row_order_x.p,
-                       (int64_t)n);
+    launch_u32_to_i32(alt ? sval2.p : sval.p, g->row_order_x.p, n, s);
     if (first) {   // (the node arrays never change: an incremental rebuild keeps both item orders)
-        // ITEM rows in ascending row order: one stable pass on the flag (item ? 0 : 1)
         hipLaunchKernelGGL(k_item_flag_keys, dim3(cdiv(n, 256)), dim3(256), 0, s, n, g->node_type.p, skey.p, sval.p);
         RWR_TRY(radix_sort_pairs<uint32_t>(skey.p, skey2.p, sval.p, sval2.p, (size_t)n, 1, 8, temp.p, s, &alt));
-        if (n_items > 0)
-            hipLaunchKernelGGL(k_u32_to_i32, dim3(cdiv(n_items, 256)), dim3(256), 0, s, alt ? sval2.p : sval.p,
-                               g->item_rows.p, (int64_t)n_items);
+        launch_u32_to_i32(alt ? sval2.p : sval.p, g->item_rows.p, n_items, s);
         if (n_items > 0) {
             hipLaunchKernelGGL(k_item_id_keys, dim3(cdiv(n_items, 256)), dim3(256), 0, s, n_items, g->item_rows.p,
                                g->node_id.p, ikey.p, ival.p, g->id_key_top);
             RWR_TRY(radix_sort_pairs<uint64_t>(ikey.p, ikey2.p, ival.p, ival2.p, (size_t)n_items, 1, g->id_key_bits, temp.p, s, &alt));
-            hipLaunchKernelGGL(k_u32_to_i32, dim3(cdiv(n_items, 256)), dim3(256), 0, s, alt ? ival2.p : ival.p,
-                               g->item_order.p, (int64_t)n_items);
+            launch_u32_to_i32(alt ? ival2.p : ival.p, g->item_order.p, n_items, s);
         }
     }
     RWR_HIP(hipGetLastError());
     g->h_in_ptr.resize((size_t)n + 1);
     g->h_dangling.resize((size_t)n);
-    if (staged) {
-        hipLaunchKernelGGL(k_stage_out, dim3(cdiv((size_t)n + 1, 256)), dim3(256), 0, s, n, g->in_ptr.p, flags.p, g->dangling.p,
-                           pin_out, 1);
-        RWR_HIP(hipEventRecord(e1, s));
-        BT("enqueue gather + orders");
-        RWR_HIP(hipStreamSynchronize(s));                   // the ONE synchronisation of an ego-network-sized build
-        nnz = reinterpret_cast<const int64_t *>(pin_out)[0];
-        memcpy(h_flags, pin_out + 8, sizeof(h_flags));
-        memcpy(g->h_in_ptr.data(), pin_out + 32, sizeof(int64_t) * ((size_t)n + 1));
-        memcpy(g->h_dangling.data(), pin_out + 32 + 8 * ((size_t)n + 1), (size_t)n);
-        BT("sync (whole build)");
-        if (h_flags[1]) {
-            set_error("rwr_graph_create: a link targets a node outside [0, %d)", n);
-            return RWR_E_RANGE;
-        }
-        g->nnz = nnz;
-        g->uniform = h_flags[0] ? 0 : 1;
-        g->nonneg = h_flags[3] ? 0 : 1;
-        g->vf = (g->uniform && g->nonneg && vf_env) ? 1 : 0;   // (in_w stays: see above)
-    } else {
-        RWR_HIP(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, s));
-        RWR_HIP(hipEventRecord(e1, s));
-        BT("enqueue gather + orders");
-        RWR_HIP(hipStreamSynchronize(s));
-        BT("sync 2 (orders)");
-        RWR_HIP(hipMemcpy(g->h_in_ptr.data(), g->in_ptr.p, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost));
-        RWR_HIP(hipMemcpy(g->h_dangling.data(), g->dangling.p, (size_t)n, hipMemcpyDeviceToHost));
-    }
+    RWR_HIP(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, s));
+    RWR_HIP(hipEventRecord(e1, s));
+    BT("enqueue gather + orders");
+    RWR_HIP(hipStreamSynchronize(s));
+    BT("sync 2 (orders)");
+    RWR_HIP(hipMemcpy(g->h_in_ptr.data(), g->in_ptr.p, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost));
+    RWR_HIP(hipMemcpy(g->h_dangling.data(), g->dangling.p, (size_t)n, hipMemcpyDeviceToHost));
     return derive_finish(g, h_flags, e0, e1);
 }
 
@@ -1082,231 +779,6 @@ int32_t ensure_in_w(rwr_graph *g)
                            g->w_src.p, g->in_w.p);
         RWR_HIP(hipGetLastError());
     }
-    return RWR_OK;
-}
-
-// The row lists of a batch's last steps, derived from the built matrix: a stable one-bit partition of
-// row_order each, so that every list keeps its in-degree-descending load balance; and the per-node chain flags of those steps.
-// Level k >= 2 is built only while a launch over it gathers at most 80 % of the matrix: past that it costs what a full launch
-// costs, and every deeper level walks at least as much on the graphs that get that far.  RWR_TAIL_DEPTH caps the levels.
-int32_t tail_rows_prepare(rwr_graph *g)
-{
-    if (g->tail_state == 1) return RWR_OK;
-    g->bound_first = -1;
-    static const int depth_env = [] {
-        const char *e = getenv("RWR_TAIL_DEPTH");
-        const int v = e ? atoi(e) : rwr_graph::TAIL_MAX;
-        return v < 1 ? 1 : v > rwr_graph::TAIL_MAX ? rwr_graph::TAIL_MAX : v;
-    }();
-    const int32_t n = g->n;
-    hipStream_t s = g->stream;
-    DevBuf<uint8_t> flag, temp;
-    DevBuf<uint32_t> key, key2, val, val2;
-    DevBuf<int> cnt;
-    DevBuf<unsigned long long> links;
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    RWR_TRY(flag.alloc(nn));
-    RWR_TRY(key.alloc(nn));
-    RWR_TRY(key2.alloc(nn));
-    RWR_TRY(val.alloc(nn));
-    RWR_TRY(val2.alloc(nn));
-    RWR_TRY(cnt.alloc(1));
-    RWR_TRY(links.alloc(1));
-    RWR_TRY(temp.alloc(radix_sort_temp_bytes(nn, 1)));
-    std::vector<uint8_t> h_flag((size_t)n);
-    g->h_tail_flag.assign((size_t)n, 0);
-    for (int32_t i = 0; i < n; ++i) g->h_tail_flag[i] = g->h_is_item[i];   // bit 0: the last step's chain of an ITEM seed
-    if (depth_env >= 2 && n > 0) {   // bit 1
-        RWR_HIP(hipMemsetAsync(flag.p, 0, nn, s));
-        hipLaunchKernelGGL(k_tail_seed_flag, dim3(cdiv((size_t)n, 256 / WAVE)), dim3(256), 0, s, n, g->rowptr.p, g->dst.p,
-                           g->etype.p, g->node_type.p, flag.p);
-        RWR_HIP(hipMemcpyAsync(h_flag.data(), flag.p, (size_t)n, hipMemcpyDeviceToHost, s));
-        RWR_HIP(hipStreamSynchronize(s));
-        for (int32_t i = 0; i < n; ++i) g->h_tail_flag[i] |= (uint8_t)(h_flag[i] << 1);
-    }
-    g->tail_depth = 0;
-    for (int l = 0; l < depth_env; ++l) {
-        int h_cnt = 0;
-        unsigned long long h_links = 0;
-        if (n > 0) {
-            if (l > 0) {   // the sources of the previous level's in-links
-                RWR_HIP(hipMemsetAsync(flag.p, 0, nn, s));
-                if (g->tail_n[l - 1] > 0)
-                    hipLaunchKernelGGL(k_tail_flag, dim3(cdiv((size_t)g->tail_n[l - 1], 256 / WAVE)), dim3(256), 0, s,
-                                       g->tail_n[l - 1], g->tail_rows[l - 1].p, g->in_ptr.p, g->in_src.p, flag.p);
-            }
-            RWR_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int), s));
-            RWR_HIP(hipMemsetAsync(links.p, 0, sizeof(unsigned long long), s));
-            hipLaunchKernelGGL(k_tail_keys, dim3(cdiv((size_t)n, 256)), dim3(256), 0, s, n, g->row_order.p,
-                               l == 0 ? g->node_type.p : flag.p, (uint8_t)(l == 0 ? RWR_NODE_ITEM : 1), key.p, val.p, cnt.p,
-                               g->in_ptr.p, links.p);
-            RWR_HIP(hipMemcpyAsync(&h_cnt, cnt.p, sizeof(int), hipMemcpyDeviceToHost, s));
-            RWR_HIP(hipMemcpyAsync(&h_links, links.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-            RWR_HIP(hipStreamSynchronize(s));
-            if (l >= 2 && h_links * 5 > (unsigned long long)g->nnz * 4) break;
-            bool alt = false;
-            RWR_TRY(radix_sort_pairs<uint32_t>(key.p, key2.p, val.p, val2.p, (size_t)n, 1, 1, temp.p, s, &alt));
-            RWR_TRY(g->tail_rows[l].alloc((size_t)(h_cnt > 0 ? h_cnt : 1)));
-            if (h_cnt > 0)
-                hipLaunchKernelGGL(k_u32_to_i32, dim3(cdiv((size_t)h_cnt, 256)), dim3(256), 0, s, alt ? val2.p : val.p,
-                                   g->tail_rows[l].p, (int64_t)h_cnt);
-            if (l >= 2) {   // bit l: the seed row is a source of level l - 1, whose rows step T - l + 1 produces
-                RWR_HIP(hipMemcpyAsync(h_flag.data(), flag.p, (size_t)n, hipMemcpyDeviceToHost, s));
-                RWR_HIP(hipStreamSynchronize(s));
-                for (int32_t i = 0; i < n; ++i) g->h_tail_flag[i] |= (uint8_t)(h_flag[i] << l);
-            }
-        }
-        g->tail_n[l] = h_cnt;
-        g->tail_depth = l + 1;
-    }
-    for (int l = g->tail_depth; l < rwr_graph::TAIL_MAX; ++l) { g->tail_rows[l].release(); g->tail_n[l] = 0; }
-    RWR_HIP(hipGetLastError());
-    RWR_HIP(hipStreamSynchronize(s));   // the scratch buffers are released on return
-    g->tail_state = 1;
-    return RWR_OK;
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// A batch of ego-network-sized graphs built with ONE launch (rwr_eval_graphs in api.hip: graphs_build_multi here, then
-// recommend_small_multi in small.hip and eval_ranked_multi in rank.hip).  The reference builds one such
-// graph per fold and methodology (Experiment.cs:69-105) and ten of its threads do so at once (Program.cs:11); handled one
-// graph per call that is two synchronisations and a dozen runtime calls per graph, and the threads queue up behind the
-// runtime rather than the GPU.  Here every graph of the batch gets a workgroup of k_build_small_multi: one H2D copy of all
-// staging slots, one launch, one synchronisation.
-//   caller_index[i]: the graph's number in the caller's batch (for error messages).
-// Pinned host buffers of one rwr_eval_graphs call, grown on demand: slot 0 the graphs' staging slots and read-back areas,
-// the others the small tables the batch kernels take (argument arrays, test sets, results).  Every host<->device copy of a
-// batch goes through pinned memory: an "asynchronous" copy from pageable memory is staged by the runtime under a process-wide
-// lock and waits for the device.  Allocating pinned memory costs milliseconds, so the sets are recycled through a process-wide
-// pool (a call takes one, gives it back at its end); the calling thread reaches its set through a thread-local pointer.
-constexpr int MULTI_SLOTS = 6;
-struct MultiPins {
-    void *pin[MULTI_SLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t cap[MULTI_SLOTS] = {0, 0, 0, 0, 0, 0};
-};
-static std::mutex g_pins_mutex;
-static std::vector<MultiPins *> g_pins;          // parked sets (never freed: a handful of MB per concurrent caller)
-static thread_local MultiPins *tl_pins = nullptr;
-void multi_pins_acquire()
-{
-    if (tl_pins) return;
-    {
-        std::lock_guard<std::mutex> lk(g_pins_mutex);
-        if (!g_pins.empty()) { tl_pins = g_pins.back(); g_pins.pop_back(); }
-    }
-    if (!tl_pins) tl_pins = new MultiPins();
-}
-void multi_pins_release()
-{
-    if (!tl_pins) return;
-    std::lock_guard<std::mutex> lk(g_pins_mutex);
-    g_pins.push_back(tl_pins);
-    tl_pins = nullptr;
-}
-int32_t multi_pinned(int slot, size_t bytes, void **out)
-{
-    if (!tl_pins) { set_error("multi_pinned: no pinned set acquired"); return RWR_E_INVALID; }
-    MultiPins &a = *tl_pins;
-    if (a.cap[slot] < bytes) {
-        if (a.pin[slot]) { (void)hipHostFree(a.pin[slot]); a.pin[slot] = nullptr; a.cap[slot] = 0; }
-        const size_t cap = bytes + bytes / 2 + 4096;
-        RWR_HIP(hipHostMalloc(&a.pin[slot], cap, hipHostMallocMapped | hipHostMallocPortable));
-        a.cap[slot] = cap;
-    }
-    *out = a.pin[slot];
-    return RWR_OK;
-}
-
-bool graph_fits_small_build(int32_t n, int64_t m)
-{
-    static const int stage_env = [] { const char *e = RWR_TUNE_ENV("RWR_STAGE"); return e ? atoi(e) : 1; }();
-    static const bool by_degree = [] { const char *e = RWR_TUNE_ENV("RWR_ROW_ORDER"); return !e || atoi(e) == 0; }();
-    return stage_env && by_degree && n > 0 && n <= STAGE_MAX_N && m >= 0 && m <= STAGE_MAX_M;
-}
-
-int32_t graphs_build_multi(rwr_graph **gs, int32_t count, const rwr_graph_desc *descs, const int32_t *caller_index, hipStream_t s)
-{
-    if (count <= 0) return RWR_OK;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    // arena: [staging slots of all graphs, contiguous][read-back areas]
-    std::vector<size_t> in_off((size_t)count + 1, 0), out_off((size_t)count + 1, 0);
-    for (int32_t i = 0; i < count; ++i) {
-        const int32_t n = descs[i].n_nodes;
-        const int64_t m = descs[i].rowptr[n];
-        in_off[(size_t)i + 1] = in_off[i] + up(stage_layout(n, m).total + 8);
-        out_off[(size_t)i + 1] = out_off[i] + up(32 + 8 * ((size_t)n + 1) + (size_t)n);
-    }
-    const size_t in_bytes = in_off[count], need = in_bytes + out_off[count];
-    void *pin_v = nullptr, *args_v = nullptr;
-    RWR_TRY(multi_pinned(0, need, &pin_v));
-    RWR_TRY(multi_pinned(1, sizeof(BuildSmallArgs) * (size_t)count, &args_v));
-    uint8_t *pin = static_cast<uint8_t *>(pin_v);
-    BuildSmallArgs *h_args = static_cast<BuildSmallArgs *>(args_v);
-    DevBuf<uint8_t> d_in;
-    DevBuf<BuildSmallArgs> d_args;
-    RWR_TRY(d_in.alloc(in_bytes));
-    RWR_TRY(d_args.alloc((size_t)count));
-    std::vector<SmallBuild> builds((size_t)count);
-#ifdef RWR_EXPERIMENTS
-    static const bool mt_on = [] { const char *e = getenv("RWR_X_MULTI_TIMING"); return e && atoi(e) != 0; }();
-    double mt0 = bt_now(), mt1 = 0, mt2 = 0, mt3 = 0, mt4 = 0, mt_up = 0, mt_begin = 0;
-#endif
-    for (int32_t i = 0; i < count; ++i) {
-        rwr_graph *g = gs[i];
-        g->sm_stage = pin + in_off[i];
-        g->sm_out = pin + in_bytes + out_off[i];
-        g->stage_dev_ext = d_in.p + in_off[i];
-        const rwr_graph_desc &D = descs[i];
-#ifdef RWR_EXPERIMENTS
-        const double u0 = bt_now();
-#endif
-        RWR_TRY(graph_build_upload(g, D.node_id, D.node_type, D.rowptr, D.dst, D.etype, D.w));
-        if (!small_build_ok(g)) { set_error("graphs_build_multi: graph %d does not qualify for the one-launch build", caller_index[i]); return RWR_E_INVALID; }
-#ifdef RWR_EXPERIMENTS
-        const double u1 = bt_now();
-        mt_up += u1 - u0;
-#endif
-        RWR_TRY(small_build_begin(g, true, builds[i]));
-#ifdef RWR_EXPERIMENTS
-        mt_begin += bt_now() - u1;
-#endif
-        h_args[i] = builds[i].a;
-    }
-#ifdef RWR_EXPERIMENTS
-    mt1 = bt_now();
-#endif
-    RWR_HIP(hipMemcpyAsync(d_in.p, pin, in_bytes, hipMemcpyHostToDevice, s));
-    RWR_HIP(hipMemcpyAsync(d_args.p, h_args, sizeof(BuildSmallArgs) * (size_t)count, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_build_small_multi, dim3((unsigned)count), dim3(SMALL_SORT_THREADS), 0, s, d_args.p);
-    RWR_HIP(hipGetLastError());
-#ifdef RWR_EXPERIMENTS
-    mt2 = bt_now();
-#endif
-    RWR_HIP(hipStreamSynchronize(s));
-#ifdef RWR_EXPERIMENTS
-    mt3 = bt_now();
-#endif
-    for (int32_t i = 0; i < count; ++i) {
-        rwr_graph *g = gs[i];
-        const int32_t rc = small_build_end(g, builds[i], nullptr, nullptr);
-        g->sm_stage = nullptr;            // (the arena belongs to the thread, not to the handle)
-        g->sm_out = nullptr;
-        g->stage_dev_ext = nullptr;
-        g->staged = 0;                    // an incremental rebuild of this handle, should one follow, takes the general build
-        if (rc != RWR_OK) {
-            char msg[512];
-            snprintf(msg, sizeof(msg), "%s", rwr_last_error());
-            set_error("graph %d of the batch: %s", caller_index[i], msg);
-            return rc;
-        }
-    }
-#ifdef RWR_EXPERIMENTS
-    mt4 = bt_now();
-    if (mt_on)
-        fprintf(stderr, "[multi build] %d graphs: prep %.0f us (upload %.0f, begin %.0f), enqueue %.0f, wait %.0f, finish %.0f\n", count, mt1 - mt0,
-                mt_up, mt_begin, mt2 - mt1, mt3 - mt2, mt4 - mt3);
-#endif
     return RWR_OK;
 }
 

@@ -57,7 +57,7 @@ __host__ __device__ static inline uint64_t i64_orderable(int64_t x)
 }
 
 // ------------------------------------------------------------------ device buffers
-// Device memory of up to 32 MB comes from a per-device cache of power-of-two blocks (api.hip): the reference's workload is
+// Device memory of up to 32 MB comes from a per-device cache of power-of-two blocks (pool.h): the reference's workload is
 // thousands of ego-network graphs, one Graph per fold from up to ten host threads (Program.cs:11, Experiment.cs:69-105),
 // and every hipMalloc / hipFree of the ~40 buffers of a handle is a device-wide synchronisation point that serialises
 // those threads.  A block is handed back only by code that has synchronised the stream(s) it was used on (handle

@@ -4,6 +4,7 @@
 #include <new>
 
 #include "common.h"
+#include "stage_layout.h"
 
 struct rwr_graph {
     int32_t device = 0;
@@ -27,7 +28,7 @@ struct rwr_graph {
     int32_t nonneg = 1;      // every normalised weight is a finite number >= 0 (raw weights >= 0, row sums in (0, inf)): ranks stay
                              // >= 0, which the zero-skipping frontier paths and the binade scan rely on; otherwise the general kernels run
     int32_t max_in_deg = 0;
-    int32_t staged = 0;      // ego-network-sized graph: raw arrays arrived through the pinned staging buffer (build.hip)
+    int32_t staged = 0;      // ego-network-sized graph: raw arrays arrived through the pinned staging buffer (stage_layout.h)
     int32_t stage_pending = 0;   // ... and the device-side copy of that buffer has not been unpacked into the arrays yet
     int32_t poisoned = 0;    // a failed incremental rebuild left raw and derived arrays out of step: every entry point refuses
     // rows of row_order (in-degree descending) with in-degree >= 128 / >= 32 / >= 4: lane-width bins of the K = 1 vector SpMV
@@ -94,8 +95,8 @@ struct rwr_graph {
     rwr::DevBuf<double> X, Y;         // rank matrices [tile][n][G]
     rwr::DevBuf<int32_t> sm_tab;      // small.hip: places of the seed row's addends (per call)
     void *sm_pin = nullptr;           // small.hip: pinned host buffer the one-launch kernel writes the ranked list into
-    void *sm_stage = nullptr;         // build.hip: pinned staging buffer of an ego-network-sized graph's upload / read-back
-    // a handle built as part of a batch (rwr_eval_graphs, eval_graphs.hip; graphs_build_multi in build.hip, recommend_small_multi in
+    void *sm_stage = nullptr;         // stage_layout.h: pinned staging buffer of an ego-network-sized graph's upload / read-back
+    // a handle built as part of a batch (rwr_eval_graphs, eval_graphs.hip; graphs_build_multi in build_small.hip, recommend_small_multi in
     // small.hip): its staging slot and read-back area lie in the batch's pinned arena, the device-side landing area in the
     // batch's one buffer (one H2D copy for all graphs); none of them is owned by the handle
     uint8_t *sm_out = nullptr;
@@ -206,13 +207,6 @@ int32_t graph_build(rwr_graph *g, const int64_t *node_id, const uint8_t *node_ty
                     const int32_t *dst, const uint8_t *etype, const double *w);
 
 int32_t graph_update_links(rwr_graph *g, int64_t count, const int64_t *idx, const uint8_t *etype, const double *w);
-// The largest link count the one-launch paths of an ego-network-sized graph take: small.hip's one-launch Recommendation and the
-// one-launch build (build.hip keeps its own STAGE_MAX_M of the same value: that file is part of the benchmark's traffic
-// fingerprint and is not edited for a constant; small_build_ok re-checks nnz_raw against it on every build)
-constexpr int64_t ONE_LAUNCH_MAX_M = 65536;
-// ... and the largest node count of the staged upload and the one-launch build (build.hip's STAGE_MAX_N, which sizes the pinned
-// read-back area of a staged graph: a graph that grows past it leaves the staged path, append.hip)
-constexpr int32_t ONE_LAUNCH_MAX_N = 8192;
 // rwr_graph_append_links (n_new == 0) and rwr_graph_append_nodes: grows the node arrays by n_new nodes with empty lists, merges
 // the links into the resident raw lists (new buffers, swapped in when all of them exist: *swapped) and re-derives; the plans are
 // node_append_plan.h's and append_plan.h's.  `who` names the entry point in the messages.
@@ -221,10 +215,14 @@ int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t
                      int64_t *new_index_out, bool *swapped);
 // value-free graphs: materialise in_w (= w_src[in_src]) for an entry point that runs the weighted kernels
 int32_t ensure_in_w(rwr_graph *g);
-// g->tail_rows / tail_n / tail_depth / h_tail_flag of the current matrix (built once per (re)build)
+// sort.hip: m sorted payload words as the int32 row list their readers take (no launch for m <= 0)
+void launch_u32_to_i32(const uint32_t *a, int32_t *b, int64_t m, hipStream_t s);
+// tail_rows.hip: g->tail_rows / tail_n / tail_depth / h_tail_flag of the current matrix (built once per (re)build)
 int32_t tail_rows_prepare(rwr_graph *g);
-// many ego-network-sized graphs at once (rwr_eval_graphs): one build launch, one call launch, one evaluation launch
+// build_small.hip: does a graph take the staged upload and the one-launch build (stage_layout.h: the limits)
 bool graph_fits_small_build(int32_t n, int64_t m);
+// many ego-network-sized graphs at once (rwr_eval_graphs): one build launch, one call launch, one evaluation launch
+// (pool.hip: the thread's pinned buffers)
 void multi_pins_acquire();    // a set of pinned buffers for this thread's rwr_eval_graphs call (from a process-wide pool) ...
 void multi_pins_release();    // ... and back
 int32_t multi_pinned(int slot, size_t bytes, void **out);   // buffer number `slot` (0..5) of the acquired set, at least `bytes` long

@@ -1,5 +1,5 @@
 // The driver of rwr_eval_graphs: many ego-network-sized graphs built, walked and evaluated in chunks of 256 -- one build launch
-// (graphs_build_multi, build.hip), one call launch (recommend_small_multi, small.hip) and one evaluation launch
+// (graphs_build_multi, build_small.hip), one call launch (recommend_small_multi, small.hip) and one evaluation launch
 // (eval_ranked_multi, rank.hip) per chunk --, the graphs these paths cannot take one by one through the public single-graph calls.
 #include <algorithm>
 #include <new>

@@ -23,6 +23,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "key_bits.h"
+
 #if defined(__HIPCC__)
 #define NAP_HD __host__ __device__
 #else
@@ -77,13 +79,6 @@ struct NodeAppendPlan {
     uint64_t key_lo = ~0ull, key_hi = 0;
 };
 
-inline int nap_bit_length(uint64_t v)
-{
-    int b = 0;
-    while (v) { ++b; v >>= 1; }
-    return b;
-}
-
 // rows (ascending) stably by id descending: a least-significant-digit radix sort of key_hi - orderable(id), 11 bits a pass over
 // the bits the id RANGE needs (consecutive ids of a loader: two passes for 100 000 items).  Every pass is a counting sort,
 // which keeps equal digits in their order.  id_of(row) = the id of a row in `rows`.
@@ -94,7 +89,7 @@ inline void node_append_sort_new(std::vector<int32_t> &rows, uint64_t key_lo, ui
     constexpr uint64_t MASK = (1u << BITS) - 1;
     const size_t cnt = rows.size();
     if (cnt < 2) return;
-    const int bits = nap_bit_length(key_hi - key_lo);
+    const int bits = bit_length(key_hi - key_lo);
     std::vector<uint64_t> key(cnt), key2(cnt);
     std::vector<int32_t> other(cnt);
     std::vector<size_t> head((size_t)MASK + 1);
@@ -142,7 +137,7 @@ inline NodeAppendPlan node_append_plan(int32_t n_old, int32_t n_new, const int64
 inline void node_append_id_keys(bool any, uint64_t lo, uint64_t hi, uint64_t *top, int32_t *bits)
 {
     *top = any ? hi : 0;
-    *bits = any ? (nap_bit_length(hi - lo) > 0 ? nap_bit_length(hi - lo) : 1) : 1;
+    *bits = any ? key_bits(hi - lo) : 1;
 }
 
 // the host row pointers grown to n_total rows (the new rows are empty); capacity for them must not be a surprise to the

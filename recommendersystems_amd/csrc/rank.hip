@@ -748,7 +748,7 @@ int32_t eval_ranked_multi(rwr_graph **gs, int32_t count, const int64_t *test_ptr
     RWR_TRY(d_len.alloc((size_t)count));
     RWR_TRY(d_args.alloc((size_t)count));
     return idle_on_error(s, [&]() -> int32_t {
-        // every table goes through the thread's pinned buffers (build.hip: multi_pinned): [args][ptr][test ids] in, [hits][sums][len] out
+        // every table goes through the thread's pinned buffers (pool.hip: multi_pinned): [args][ptr][test ids] in, [hits][sums][len] out
         const size_t b_args = sizeof(EvalMultiArgs) * (size_t)count, b_ptr = 8 * ((size_t)count + 1), b_test = 8 * (size_t)total;
         void *in_v = nullptr, *out_v = nullptr;
         RWR_TRY(multi_pinned(3, b_args + b_ptr + b_test + 64, &in_v));

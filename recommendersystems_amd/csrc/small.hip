@@ -320,7 +320,7 @@ bool small_path_ok(const rwr_graph *g)
     // one workgroup walks every link once per step: beyond ~65 K links the general path's whole-chip kernels are ahead
     // (measured, round 3: 4 000 nodes / 52 K links 0.54 vs 0.61 ms, 4 700 nodes / 76 K links 0.80 vs 0.66 ms, 5 500 nodes / 92 K links
     //  0.95 vs 0.60 ms; round 2, before the general path's chain was rebuilt: 55 K links 0.77 vs 1.37 ms) -- which is also the
-    // largest graph the one-launch build takes (build.hip: STAGE_MAX_M)
+    // largest graph the one-launch build takes (stage_layout.h)
     return env && g->n <= SM_MAX_N && g->n_items <= SM_MAX_ITEMS && g->n_items > 0 && g->nonneg && g->nnz <= ONE_LAUNCH_MAX_M;
 }
 
@@ -396,7 +396,7 @@ int32_t recommend_small_multi(rwr_graph **gs, const int32_t *seeds, int32_t coun
         }
     }
     void *h_v = nullptr;
-    RWR_TRY(multi_pinned(2, sizeof(SmallRwrArgs) * (size_t)count, &h_v));      // (pinned: see build.hip, multi_pinned)
+    RWR_TRY(multi_pinned(2, sizeof(SmallRwrArgs) * (size_t)count, &h_v));      // (pinned: see pool.hip, multi_pinned)
     SmallRwrArgs *h = static_cast<SmallRwrArgs *>(h_v);
     for (int32_t i = 0; i < count; ++i) {
         rwr_graph *g = gs[i];

@@ -223,4 +223,15 @@ template int32_t radix_sort_pairs<uint32_t>(uint32_t *, uint32_t *, uint32_t *, 
 template int32_t radix_sort_pairs<uint64_t>(uint64_t *, uint64_t *, uint32_t *, uint32_t *, size_t, int, int,
                                             void *, hipStream_t, bool *);
 
+// a sort's payload is row numbers: the sorted payload as the int32 row list its readers take
+__global__ void k_u32_to_i32(const uint32_t *__restrict__ a, int32_t *__restrict__ b, int64_t m)
+{
+    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < m) b[p] = (int32_t)a[p];
+}
+void launch_u32_to_i32(const uint32_t *a, int32_t *b, int64_t m, hipStream_t s)
+{
+    if (m > 0) hipLaunchKernelGGL(k_u32_to_i32, dim3(cdiv((size_t)m, 256)), dim3(256), 0, s, a, b, m);
+}
+
 }  // namespace rwr
