@@ -72,6 +72,12 @@ namespace Recommenders.RWRBased {
             double[] sup_val, int[] start, long[] excl_ptr, int[] excl_idx, double d, int n_iter, int top_n, long[] ids,
             double[] scores, int[] counts);
 
+        // the same K walks evaluated on the device: Hits and the running-precision sum (Experiment.cs:121-128) of every vector's
+        // list (its first top_n entries when top_n > 0) against test set k (test_ptr / test_ids in CSR form); no list is written
+        [DllImport(Lib)] public static extern int rwr_recommend_restart_eval_batch(GraphHandle g, int K, long[] sup_ptr, int[] sup_idx,
+            double[] sup_val, int[] start, long[] excl_ptr, int[] excl_idx, double d, int n_iter, int top_n, long[] test_ptr,
+            long[] test_ids, long[] n_hits, double[] sum_precision, long[] list_len);
+
         [DllImport(Lib)] public static extern int rwr_model_run_restart(GraphHandle g, double[] restart, double[] rank_in, double d,
             int run_mode, double value, double[] rank_out, out long iters_out);
 

@@ -114,5 +114,46 @@ namespace Recommenders.RWRBased {
             }
             return all;
         }
+
+        // addition: Hits and the running-precision sum (Experiment.cs:121-128) of the same K walks against one test set each,
+        // evaluated on the device without writing a ranked list (rwr_recommend_restart_eval_batch).  nodes, weights, start and
+        // exclude as in RecommendationRestartBatch; topN > 0 evaluates the first topN entries of every list, topN <= 0 the whole
+        // list.  nHits[k] / sumPrecision[k] / listLen[k] are what the harness computes over list k
+        public void RecommendationRestartEvalBatch(int[][] nodes, double[][] weights, int[] start, double dampingFactor,
+                                                   int nIteration, HashSet<long>[] testSets, out long[] nHits,
+                                                   out double[] sumPrecision, out long[] listLen, int topN = 0,
+                                                   int[][] exclude = null) {
+            int K = nodes.Length;
+            if (weights.Length != K || testSets.Length != K || (start != null && start.Length != K) ||
+                (exclude != null && exclude.Length != K))
+                throw new System.ArgumentException("nodes, weights, start, testSets and exclude must hold one entry per vector");
+            var ptr = new long[K + 1];
+            for (int k = 0; k < K; k++) {
+                if (nodes[k].Length != weights[k].Length)
+                    throw new System.ArgumentException("a restart vector's nodes and weights differ in length");
+                ptr[k + 1] = ptr[k] + nodes[k].Length;
+            }
+            var idx = new int[ptr[K]];
+            var val = new double[ptr[K]];
+            for (int k = 0; k < K; k++) {
+                System.Array.Copy(nodes[k], 0, idx, ptr[k], nodes[k].Length);
+                System.Array.Copy(weights[k], 0, val, ptr[k], weights[k].Length);
+            }
+            long[] exclPtr = null;
+            int[] exclIdx = null;
+            if (exclude != null) {
+                exclPtr = new long[K + 1];
+                for (int k = 0; k < K; k++) exclPtr[k + 1] = exclPtr[k] + exclude[k].Length;
+                exclIdx = new int[exclPtr[K]];
+                for (int k = 0; k < K; k++) System.Array.Copy(exclude[k], 0, exclIdx, exclPtr[k], exclude[k].Length);
+            }
+            var testPtr = new long[K + 1];
+            for (int k = 0; k < K; k++) testPtr[k + 1] = testPtr[k] + testSets[k].Count;
+            var testIds = new long[testPtr[K]];
+            for (int k = 0; k < K; k++) testSets[k].CopyTo(testIds, (int)testPtr[k]);
+            nHits = new long[K]; sumPrecision = new double[K]; listLen = new long[K];
+            Native.Check(Native.rwr_recommend_restart_eval_batch(graph.handle, K, ptr, idx, val, start, exclPtr, exclIdx, dampingFactor,
+                                                                 nIteration, topN, testPtr, testIds, nHits, sumPrecision, listLen));
+        }
     }
 }

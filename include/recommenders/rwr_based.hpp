@@ -425,6 +425,45 @@ public:
         return out;
     }
 
+    // addition: Hits and the running-precision sum (Experiment.cs:121-128) of the same K walks against one test set each,
+    // evaluated on the device without writing a ranked list (rwr_recommend_restart_eval_batch).  topN > 0 evaluates the first
+    // topN entries of every list, topN <= 0 the whole list
+    struct RestartEval {
+        std::vector<int64_t> nHits;
+        std::vector<double> sumPrecision;
+        std::vector<int64_t> listLen;
+    };
+    RestartEval recommendRestartEvalBatch(const std::vector<std::vector<int>> &nodes, const std::vector<std::vector<double>> &weights,
+                                          const std::vector<int> &start, double dampingFactor, int nIteration,
+                                          const std::vector<std::vector<int64_t>> &testSets, int topN = 0,
+                                          const std::vector<std::vector<int>> *exclude = nullptr)
+    {
+        const int32_t K = (int32_t)nodes.size();
+        if (weights.size() != nodes.size() || testSets.size() != nodes.size() || (!start.empty() && start.size() != nodes.size()) ||
+            (exclude && exclude->size() != nodes.size()))
+            throw std::invalid_argument("recommendRestartEvalBatch: nodes, weights, start, testSets and exclude must hold one entry per vector");
+        std::vector<int64_t> ptr((size_t)K + 1, 0), eptr((size_t)K + 1, 0), tptr((size_t)K + 1, 0), tids;
+        std::vector<int32_t> idx, eidx;
+        std::vector<double> val;
+        for (int32_t k = 0; k < K; ++k) {
+            if (nodes[k].size() != weights[k].size())
+                throw std::invalid_argument("recommendRestartEvalBatch: a restart vector's nodes and weights differ in length");
+            idx.insert(idx.end(), nodes[k].begin(), nodes[k].end());
+            val.insert(val.end(), weights[k].begin(), weights[k].end());
+            ptr[(size_t)k + 1] = (int64_t)idx.size();
+            if (exclude) eidx.insert(eidx.end(), (*exclude)[k].begin(), (*exclude)[k].end());
+            eptr[(size_t)k + 1] = (int64_t)eidx.size();
+            tids.insert(tids.end(), testSets[k].begin(), testSets[k].end());
+            tptr[(size_t)k + 1] = (int64_t)tids.size();
+        }
+        std::vector<int32_t> st(start.begin(), start.end());
+        RestartEval out{std::vector<int64_t>((size_t)K), std::vector<double>((size_t)K), std::vector<int64_t>((size_t)K)};
+        check(rwr_recommend_restart_eval_batch(graph_.handle(), K, ptr.data(), idx.data(), val.data(), st.empty() ? nullptr : st.data(),
+                                               exclude ? eptr.data() : nullptr, eidx.data(), dampingFactor, nIteration, topN,
+                                               tptr.data(), tids.data(), out.nHits.data(), out.sumPrecision.data(), out.listLen.data()));
+        return out;
+    }
+
 private:
     Graph &graph_;
 };

@@ -404,6 +404,26 @@ int32_t rwr_recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_
                                     const double *sup_val, const int32_t *start, const int64_t *excl_ptr,
                                     const int32_t *excl_idx, double d, int32_t n_iter, int32_t top_n,
                                     int64_t *ids, double *scores, int32_t *counts);
+/* The same K walks evaluated on the device: Hits and the running-precision sum of every vector's list against a test set
+ * (Experiment.cs:121-128), without the list ever being written.  Vectors, starts, exclusion sets, d, n_iter and the domain
+ * exactly as in rwr_recommend_restart_batch.  Test set k is test_ids[test_ptr[k] .. test_ptr[k+1]) with HashSet<long>
+ * semantics: duplicates change nothing, ids that no node carries are legal, a set may be empty.
+ * Result k: let L_k be the WHOLE list rwr_recommend_restart_batch defines for vector k (top_n = number of items), cut to its
+ * first top_n entries if top_n > 0 (Hits@N / AP@N) and kept whole if top_n <= 0.  n_hits[k] and sum_precision[k] are what
+ * Experiment.cs:121-128 computes over that list -- hits numbered in rank order, the addends (double)nHits / (i + 1) summed in
+ * rank order -- and list_len[k] (may be NULL) is the list's length.  The integers are equal to that composition and
+ * sum_precision bitwise equal to it, for every vector (the fallback classes of rwr_model_run_restart_batch included).
+ * Item ids need not be unique (rwr_graph_append_nodes): every ITEM node that carries a test id is a hit.
+ *   - Argument errors, all found before any device work: everything rwr_recommend_restart_batch reports for the vectors and
+ *     the exclusion sets, with the same status and batch position; NULL test_ptr, n_hits or sum_precision (K > 0), a test_ptr
+ *     that does not start at 0 or that decreases, a NULL test_ids while test_ptr[K] > 0 give RWR_E_INVALID; a set of more
+ *     than INT32_MAX ids gives RWR_E_UNSUPPORTED.  A NULL g is refused first; K == 0 is a no-op (RWR_OK).  A refused call
+ *     writes nothing. */
+int32_t rwr_recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                         const double *sup_val, const int32_t *start, const int64_t *excl_ptr,
+                                         const int32_t *excl_idx, double d, int32_t n_iter, int32_t top_n,
+                                         const int64_t *test_ptr, const int64_t *test_ids, int64_t *n_hits,
+                                         double *sum_precision, int64_t *list_len /* may be NULL */);
 
 /* ---- row-partitioned mode (graphs beyond one GPU; BASELINE.json config 5) ------------
  * An ADDITION: the reference has no distributed mode.  The transition matrix is partitioned by SOURCE rows

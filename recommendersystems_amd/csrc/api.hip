@@ -6,6 +6,7 @@
 #include <vector>
 #include <string.h>
 
+#include "eval_plan.h"
 #include "exclude_plan.h"
 #include "handle.h"
 
@@ -113,6 +114,56 @@ static int32_t check_restart_vectors(const char *who, int32_t n, int32_t K, cons
     } catch (const std::bad_alloc &) {
         set_error("%s: host allocation failed", who);
         return RWR_E_NOMEM;
+    }
+    return RWR_OK;
+}
+
+// The vectors and exclusion sets of a ranked restart batch, as rwr_recommend_restart_batch and rwr_recommend_restart_eval_batch
+// take them: what check_restart_vectors reports, then the first negative value, then exclude_check's verdict
+static int32_t check_ranked_vectors(const char *who, int32_t n, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                    const double *sup_val, const int32_t *start, const int64_t *excl_ptr, const int32_t *excl_idx)
+{
+    RWR_TRY(check_restart_vectors(who, n, K, sup_ptr, sup_idx, sup_val, start));
+    // the domain of the Recommendation entries: the exclusion marker (-1) and the ranking keys assume scores >= 0
+    for (int32_t k = 0; k < K; ++k)
+        for (int64_t q = sup_ptr[k]; q < sup_ptr[k + 1]; ++q)
+            if (sup_val[q] < 0.0) {
+                set_error("%s: restart[%d] = %g (batch position %d) is negative: ranks could go negative; "
+                          "rwr_model_run_restart_batch runs signed vectors", who, sup_idx[q], sup_val[q], k);
+                return RWR_E_UNSUPPORTED;
+            }
+    if (excl_ptr) {
+        const ExcludeCheck c = exclude_check(n, K, excl_ptr, excl_idx);
+        switch (c.verdict) {
+            case EXCLUDE_OK: break;
+            case EXCLUDE_BAD_PTR0:
+                set_error("%s: excl_ptr[0] = %lld, not 0", who, (long long)excl_ptr[0]);
+                return RWR_E_INVALID;
+            case EXCLUDE_PTR_DECREASES:
+                set_error("%s: excl_ptr decreases at batch position %d", who, c.bad_k);
+                return RWR_E_INVALID;
+            case EXCLUDE_NULL_IDX:
+                set_error("%s: NULL excl_idx", who);
+                return RWR_E_INVALID;
+            case EXCLUDE_BAD_INDEX:
+                set_error("%s: exclusion index %d (batch position %d) is outside [0, %d)", who, c.bad_index, c.bad_k, n);
+                return RWR_E_RANGE;
+        }
+    }
+    return RWR_OK;
+}
+
+// ... and the graph and damping factor of the Recommendation entries
+static int32_t check_ranked_domain(const char *who, const rwr_graph *g, double d)
+{
+    if (!g->nonneg) {
+        set_error("%s: Recommendation needs non-negative finite link weights and positive row sums; "
+                  "rwr_model_run_restart_batch accepts such graphs", who);
+        return RWR_E_UNSUPPORTED;
+    }
+    if (!(d >= 0.0 && d <= 1.0)) {
+        set_error("%s: Recommendation needs a damping factor in [0, 1] (got %g); rwr_model_run_restart_batch accepts any value", who, d);
+        return RWR_E_UNSUPPORTED;
     }
     return RWR_OK;
 }
@@ -460,47 +511,57 @@ int32_t rwr_recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_
     if (K == 0) return RWR_OK;
     if (!sup_ptr || !ids || !scores || !counts) { set_error("%s: NULL sup_ptr, ids, scores or counts", who); return RWR_E_INVALID; }
     if (top_n < 1) { set_error("%s: top_n must be >= 1", who); return RWR_E_INVALID; }
-    RWR_TRY(check_restart_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start));
-    // the domain of the Recommendation entries: the exclusion marker (-1) and the ranking keys assume scores >= 0
-    for (int32_t k = 0; k < K; ++k)
-        for (int64_t q = sup_ptr[k]; q < sup_ptr[k + 1]; ++q)
-            if (sup_val[q] < 0.0) {
-                set_error("%s: restart[%d] = %g (batch position %d) is negative: ranks could go negative; "
-                          "rwr_model_run_restart_batch runs signed vectors", who, sup_idx[q], sup_val[q], k);
-                return RWR_E_UNSUPPORTED;
-            }
-    if (excl_ptr) {
-        const ExcludeCheck c = exclude_check(g->n, K, excl_ptr, excl_idx);
-        switch (c.verdict) {
-            case EXCLUDE_OK: break;
-            case EXCLUDE_BAD_PTR0:
-                set_error("%s: excl_ptr[0] = %lld, not 0", who, (long long)excl_ptr[0]);
-                return RWR_E_INVALID;
-            case EXCLUDE_PTR_DECREASES:
-                set_error("%s: excl_ptr decreases at batch position %d", who, c.bad_k);
-                return RWR_E_INVALID;
-            case EXCLUDE_NULL_IDX:
-                set_error("%s: NULL excl_idx", who);
-                return RWR_E_INVALID;
-            case EXCLUDE_BAD_INDEX:
-                set_error("%s: exclusion index %d (batch position %d) is outside [0, %d)", who, c.bad_index, c.bad_k, g->n);
-                return RWR_E_RANGE;
-        }
-    }
-    if (!g->nonneg) {
-        set_error("%s: Recommendation needs non-negative finite link weights and positive row sums; "
-                  "rwr_model_run_restart_batch accepts such graphs", who);
-        return RWR_E_UNSUPPORTED;
-    }
-    if (!(d >= 0.0 && d <= 1.0)) {
-        set_error("%s: Recommendation needs a damping factor in [0, 1] (got %g); rwr_model_run_restart_batch accepts any value", who, d);
-        return RWR_E_UNSUPPORTED;
-    }
+    RWR_TRY(check_ranked_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start, excl_ptr, excl_idx));
+    RWR_TRY(check_ranked_domain(who, g, d));
     if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
     // excl_ptr == NULL: set k is the indices of vector k's support, whatever their values
     return bound(who, g, [&] {
         return recommend_restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, excl_ptr ? excl_ptr : sup_ptr,
                                        excl_ptr ? excl_idx : sup_idx, d, n_iter, top_n, ids, scores, counts);
+    });
+}
+
+int32_t rwr_recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                         const double *sup_val, const int32_t *start, const int64_t *excl_ptr,
+                                         const int32_t *excl_idx, double d, int32_t n_iter, int32_t top_n,
+                                         const int64_t *test_ptr, const int64_t *test_ids, int64_t *n_hits,
+                                         double *sum_precision, int64_t *list_len)
+{
+    static const char *const who = "rwr_recommend_restart_eval_batch";
+    g_err[0] = 0;
+    if (!g) { set_error("%s: NULL graph", who); return RWR_E_INVALID; }
+    if (K < 0) { set_error("%s: negative K", who); return RWR_E_INVALID; }
+    if (K == 0) return RWR_OK;
+    if (!sup_ptr) { set_error("%s: NULL sup_ptr", who); return RWR_E_INVALID; }
+    RWR_TRY(check_ranked_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start, excl_ptr, excl_idx));
+    const EvalCheck c = eval_check(K, test_ptr, test_ids, n_hits, sum_precision);
+    switch (c.verdict) {
+        case EVAL_OK: break;
+        case EVAL_NULL_PTR:
+            set_error("%s: NULL test_ptr", who);
+            return RWR_E_INVALID;
+        case EVAL_NULL_OUT:
+            set_error("%s: NULL n_hits or sum_precision", who);
+            return RWR_E_INVALID;
+        case EVAL_BAD_PTR0:
+            set_error("%s: test_ptr[0] = %lld, not 0", who, (long long)test_ptr[0]);
+            return RWR_E_INVALID;
+        case EVAL_PTR_DECREASES:
+            set_error("%s: test_ptr decreases at batch position %d", who, c.bad_k);
+            return RWR_E_INVALID;
+        case EVAL_NULL_IDS:
+            set_error("%s: NULL test_ids", who);
+            return RWR_E_INVALID;
+        case EVAL_SET_TOO_LARGE:
+            set_error("%s: test set %d holds more than INT32_MAX ids", who, c.bad_k);
+            return RWR_E_UNSUPPORTED;
+    }
+    RWR_TRY(check_ranked_domain(who, g, d));
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    return bound(who, g, [&] {
+        return recommend_restart_eval_batch(g, K, sup_ptr, sup_idx, sup_val, start, excl_ptr ? excl_ptr : sup_ptr,
+                                            excl_ptr ? excl_idx : sup_idx, d, n_iter, top_n, test_ptr, test_ids, n_hits,
+                                            sum_precision, list_len);
     });
 }
 

@@ -275,6 +275,12 @@ int32_t model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr,
 int32_t recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
                                 const int32_t *start, const int64_t *set_ptr, const int32_t *set_idx, double d, int32_t n_iter,
                                 int32_t top_n, int64_t *ids, double *scores, int32_t *counts);
+// ... or evaluated there (rwr_recommend_restart_eval_batch): Hits / average precision of every vector's list, cut
+// to top_n when top_n > 0, against test set k (test_ptr / test_ids, validated by eval_check) -- by counting, no list is written
+int32_t recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
+                                     const int32_t *start, const int64_t *set_ptr, const int32_t *set_idx, double d, int32_t n_iter,
+                                     int32_t top_n, const int64_t *test_ptr, const int64_t *test_ids, int64_t *n_hits,
+                                     double *sum_precision, int64_t *list_len);
 // ... and its kernels (restart.hip, beside the fold they share with the single call).  Pair j = support row pr[j] with
 // restart value pv[j] of the vector in slot pq[j] = tile * G + lane of the group's X[tile][n][G]; fold[j] receives the
 // row's next rank; st[slot]: the constructor's start node, -1 = every rank 1, -2 = padding slot

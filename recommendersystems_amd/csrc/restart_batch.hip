@@ -17,9 +17,13 @@
 // another end of a tile group: after step T the raw LIKE links of every vector's exclusion set are marked in X
 // (k_exclude_segments over exclude_plan.h's segments) and the group is ranked where it lies (rank.hip), so K x top_n entries
 // leave the device in place of K x n.  `Ranked` carries what that end needs; a call without one is the full-vector entry.
+//
+// rwr_recommend_restart_eval_batch is the ranked end in its second form: after the exclusion the group is
+// evaluated against the vectors' test sets by counting (eval_count.hip) instead of ranked, and one record per vector leaves.
 #include <algorithm>
 #include <cstring>
 
+#include "eval_count.h"
 #include "exclude_plan.h"
 #include "iterate.h"
 
@@ -27,7 +31,8 @@ namespace rwr {
 
 namespace {
 // The ranked end of a call: the exclusion sets (CSR over batch positions), the lists' width and destination, and the device
-// copy of the exclusion plan.  Declared by the entry point before its StreamsIdle, so the buffers outlive the kernels.
+// copy of the exclusion plan.  ev != nullptr: the evaluating form -- no list tables, the group's tail is eval_group.
+// Declared by the entry point before its StreamsIdle, so the buffers outlive the kernels.
 struct Ranked {
     const int64_t *set_ptr;
     const int32_t *set_idx;
@@ -38,6 +43,8 @@ struct Ranked {
     ExcludePlan plan;
     DevBuf<int32_t> d_seg_slot;
     DevBuf<int64_t> d_seg_p0, d_seg_p1;
+    EvalEnd *ev = nullptr;
+    const char *who = "rwr_recommend_restart_batch";
 };
 }  // namespace
 
@@ -48,16 +55,17 @@ static int32_t ranked_prepare(rwr_graph *g, Ranked &rk, int32_t K, const std::ve
                               hipStream_t s)
 {
     const size_t slots = slot_k.size();
-    RWR_TRY(ensure_out_tables(g, K, rk.top_n, s));
+    if (rk.ev) RWR_TRY(eval_prepare(g, *rk.ev, K, slot_k, slots_per_group, rk.who, s));
+    else RWR_TRY(ensure_out_tables(g, K, rk.top_n, s));
     RWR_TRY(g->d_slot_k.ensure(slots));
     RWR_HIP(hipMemcpyAsync(g->d_slot_k.p, slot_k.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, s));
     rk.plan = exclude_plan(g->n, g->h_rowptr.data(), slots, slot_k.data(), slots_per_group, K, rk.set_ptr, rk.set_idx);
     if (rk.plan.check.verdict != EXCLUDE_OK) {                  // (api.hip refuses such sets before the call gets here)
-        set_error("rwr_recommend_restart_batch: exclusion sets failed their check (verdict %d)", (int)rk.plan.check.verdict);
+        set_error("%s: exclusion sets failed their check (verdict %d)", rk.who, (int)rk.plan.check.verdict);
         return RWR_E_INVALID;
     }
     const size_t nseg = rk.plan.seg_slot.size();
-    if (nseg > 0x7FFFFFFFull) { set_error("rwr_recommend_restart_batch: too many exclusion segments"); return RWR_E_UNSUPPORTED; }
+    if (nseg > 0x7FFFFFFFull) { set_error("%s: too many exclusion segments", rk.who); return RWR_E_UNSUPPORTED; }
     if (nseg > 0) {
         RWR_TRY(rk.d_seg_slot.alloc(nseg));
         RWR_TRY(rk.d_seg_p0.alloc(nseg));
@@ -70,7 +78,8 @@ static int32_t ranked_prepare(rwr_graph *g, Ranked &rk, int32_t K, const std::ve
 }
 
 // Tile group grp (tg tiles of G slots from slot q0 on) holds its final ranks in X: the exclusion, then the ranking as
-// recommend_batch runs it, the slots' batch positions standing in for the seeds (>= 0: a live slot)
+// recommend_batch runs it, the slots' batch positions standing in for the seeds (>= 0: a live slot) -- or, in the evaluating
+// form, the four stages of eval_count.hip
 static int32_t ranked_finish_group(rwr_graph *g, const Ranked &rk, int G, int tg, int grp, size_t q0, double *X, Profile &prof,
                                    hipStream_t s)
 {
@@ -79,9 +88,17 @@ static int32_t ranked_finish_group(rwr_graph *g, const Ranked &rk, int G, int tg
     hipEvent_t a; RWR_TRY(prof.record(a, s));
     launch_exclude_segments(g, G, (int32_t)nseg, rk.d_seg_slot.p + j0, rk.d_seg_p0.p + j0, rk.d_seg_p1.p + j0, X, s);
     RWR_HIP(hipGetLastError());
-    RWR_TRY(rank_group(g, G, tg, slot_k, slot_k, rk.top_n, X, s));
+    if (rk.ev) RWR_TRY(eval_group(g, *rk.ev, G, tg, q0, X, s));
+    else RWR_TRY(rank_group(g, G, tg, slot_k, slot_k, rk.top_n, X, s));
     RWR_TRY(prof.end(prof.rank, a, s));
     return RWR_OK;
+}
+
+// after the last group: K x top_n list entries, or the K evaluation records
+static int32_t ranked_copy_back(rwr_graph *g, Ranked &rk, int32_t K)
+{
+    if (rk.ev) return eval_copy_back(g, *rk.ev, K, rk.who, g->stream);
+    return copy_lists_back(g, K, rk.top_n, rk.ids, rk.scores, rk.counts, rk.top_n);
 }
 
 // Outside the batched domain: rwr_model_run_restart per vector, on the dense vector and the constructor's rank.  rk: each
@@ -152,7 +169,7 @@ static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_pt
     if (K == 1 || wide || !g->nonneg || !(d >= 0.0 && d <= 1.0)) {
         RWR_TRY(run_vector_by_vector(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out, rk, who));
         if (rk) {
-            RWR_TRY(copy_lists_back(g, K, rk->top_n, rk->ids, rk->scores, rk->counts, rk->top_n));
+            RWR_TRY(ranked_copy_back(g, *rk, K));
             g->stats.seeds_done += K;
         }
         g->stats.total_wall_ms += now_ms() - t_begin;
@@ -283,8 +300,8 @@ static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_pt
         }
         cols.count(steps, steps);
     }
-    if (rk) {                                                   // one copy-back of K x top_n entries, as recommend_batch's
-        RWR_TRY(copy_lists_back(g, K, rk->top_n, rk->ids, rk->scores, rk->counts, rk->top_n));
+    if (rk) {                                                   // one copy-back of K x top_n entries, as recommend_batch's (or of K records)
+        RWR_TRY(ranked_copy_back(g, *rk, K));
         g->stats.seeds_done += K;
     }
     RWR_TRY(finish_model_batch(g, prof, G, TG, t_begin));
@@ -321,6 +338,20 @@ int32_t recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr,
     StreamsIdle idle{g};                                        // (the plan's device copy outlives the kernels that read it)
     return restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, d, RWR_RUN_ITERATIONS, (double)n_iter, nullptr, nullptr, &rk,
                          "rwr_recommend_restart_batch");
+}
+
+int32_t recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
+                                     const int32_t *start, const int64_t *set_ptr, const int32_t *set_idx, double d, int32_t n_iter,
+                                     int32_t top_n, const int64_t *test_ptr, const int64_t *test_ids, int64_t *n_hits,
+                                     double *sum_precision, int64_t *list_len)
+{
+    static const char *const who = "rwr_recommend_restart_eval_batch";
+    EvalEnd ev;
+    ev.test_ptr = test_ptr, ev.test_ids = test_ids, ev.top_n = top_n;
+    ev.n_hits = n_hits, ev.sum_precision = sum_precision, ev.list_len = list_len;
+    Ranked rk{set_ptr, set_idx, top_n, nullptr, nullptr, nullptr, {}, {}, {}, {}, &ev, who};
+    StreamsIdle idle{g};
+    return restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, d, RWR_RUN_ITERATIONS, (double)n_iter, nullptr, nullptr, &rk, who);
 }
 
 }  // namespace rwr

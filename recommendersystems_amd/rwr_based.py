@@ -767,3 +767,37 @@ class Recommender:
                                                    int(nIteration), topN, _p(ids, C.c_int64), _p(sc, C.c_double),
                                                    _p(counts, C.c_int32)))
         return ids, sc, counts
+
+    def RecommendationRestartEvalBatch(self, restarts, starts, dampingFactor: float, nIteration: int, testSets, topN: int = 0,
+                                       exclude=None):
+        """Hits and the running-precision sum (Experiment.cs:121-128) of K walks with caller-set restart vectors against one
+        test set each, evaluated on the device without writing a ranked list (rwr_recommend_restart_eval_batch, an addition,
+        see include/rwr.h): (nHits[K], sumPrecision[K], listLen[K]).  restarts, starts and exclude as in
+        RecommendationRestartBatch; testSets: a sequence of K collections of item ids; topN > 0 evaluates the first topN
+        entries of every list (Hits@N / AP@N), topN <= 0 the whole list."""
+        lib = _lib.load()
+        K, sup_ptr, sup_idx, sup_val, st = _pack_restarts(restarts, starts)
+        ep = ei = None
+        if exclude is not None:
+            sets = [np.asarray(e, dtype=np.int32).reshape(-1) for e in exclude]
+            if len(sets) != K:
+                raise ValueError(f"exclude must hold {K} node lists")
+            ep = np.zeros(K + 1, dtype=np.int64)
+            ep[1:] = np.cumsum([len(e) for e in sets])
+            ei = np.ascontiguousarray(np.concatenate(sets) if K else np.zeros(0, dtype=np.int32), dtype=np.int32)
+        tests = [np.asarray(list(t), dtype=np.int64).reshape(-1) for t in testSets]
+        if len(tests) != K:
+            raise ValueError(f"testSets must hold {K} id collections")
+        tp = np.zeros(K + 1, dtype=np.int64)
+        tp[1:] = np.cumsum([len(t) for t in tests])
+        ti = np.ascontiguousarray(np.concatenate(tests) if K else np.zeros(0, dtype=np.int64), dtype=np.int64)
+        hits = np.zeros(K, dtype=np.int64)
+        sp = np.zeros(K, dtype=np.float64)
+        ln = np.zeros(K, dtype=np.int64)
+        _lib.check(lib.rwr_recommend_restart_eval_batch(self.graph._handle(), K, _p(sup_ptr, C.c_int64), _p(sup_idx, C.c_int32),
+                                                        _p(sup_val, C.c_double), None if st is None else _p(st, C.c_int32),
+                                                        None if ep is None else _p(ep, C.c_int64),
+                                                        None if ei is None else _p(ei, C.c_int32), float(dampingFactor),
+                                                        int(nIteration), int(topN), _p(tp, C.c_int64), _p(ti, C.c_int64),
+                                                        _p(hits, C.c_int64), _p(sp, C.c_double), _p(ln, C.c_int64)))
+        return hits, sp, ln
