@@ -44,6 +44,10 @@ namespace Recommenders.RWRBased {
             long[] out_id, double[] out_score, ref long inout_count);
         [DllImport(Lib)] public static extern int rwr_recommend_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,
             int top_n, long[] ids, double[] scores, int[] counts);
+        // top_n (id, score) entries per seed among the nodes of type cand_type; the targets of the seed's raw links whose type has
+        // its bit in excl_edge_mask are left out, and the seed itself when exclude_self != 0 (Recommender.RecommendationTypedBatch)
+        [DllImport(Lib)] public static extern int rwr_recommend_typed_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,
+            int top_n, int cand_type, uint excl_edge_mask, int exclude_self, long[] ids, double[] scores, int[] counts);
         // Hits / sum of precisions of Experiment.cs:121-128 computed on the device (the ranked list never crosses): one seed,
         // or K seeds with K test sets in CSR form (test set k = test_ids[test_ptr[k] .. test_ptr[k + 1]))
         [DllImport(Lib)] public static extern int rwr_recommend_eval(GraphHandle g, int seed, float d, int n_iter, long[] test_ids,

@@ -72,6 +72,34 @@ namespace Recommenders.RWRBased {
             return all;
         }
 
+        // addition: the top-N lists of K seeds among the nodes of ONE node type (rwr_recommend_typed_batch).  candType: the
+        // candidates' type; exclEdgeTypes: the targets of the seed's raw links of these types are no candidates (null: none);
+        // excludeSelf: neither is the seed.  "Who to follow" is (NodeType.USER, {FRIENDSHIP, FOLLOW}, true); (NodeType.ITEM,
+        // {LIKE}, false) is RecommendationBatch
+        public List<KeyValuePair<long, double>>[] RecommendationTypedBatch(int[] seeds, float dampingFactor, int nIteration, int topN,
+                                                                           NodeType candType, IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                           bool excludeSelf = false) {
+            if (topN < 1) throw new System.ArgumentOutOfRangeException("topN", "RecommendationTypedBatch needs topN >= 1");
+            int K = seeds.Length;
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            var ids = new long[(long)K * topN]; var scores = new double[(long)K * topN]; var counts = new int[K];
+            Native.Check(Native.rwr_recommend_typed_batch(graph.handle, seeds, K, dampingFactor, nIteration, topN, (int)candType, mask, excludeSelf ? 1 : 0, ids, scores, counts));
+            var all = new List<KeyValuePair<long, double>>[K];
+            for (int k = 0; k < K; k++) {
+                all[k] = new List<KeyValuePair<long, double>>(counts[k]);
+                for (int q = 0; q < counts[k]; q++) all[k].Add(new KeyValuePair<long, double>(ids[(long)k * topN + q], scores[(long)k * topN + q]));
+            }
+            return all;
+        }
+
+        // ... and for one seed
+        public List<KeyValuePair<long, double>> RecommendationTyped(int idxTargetNode, float dampingFactor, int nIteration, int topN,
+                                                                    NodeType candType, IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                    bool excludeSelf = false) {
+            return RecommendationTypedBatch(new[] { idxTargetNode }, dampingFactor, nIteration, topN, candType, exclEdgeTypes, excludeSelf)[0];
+        }
+
         // addition: the top-N lists of K walks with caller-set restart vectors (Model.restart), ranked on the device
         // (rwr_recommend_restart_batch).  Vector k has restart[nodes[k][j]] = weights[k][j] >= 0 and zero elsewhere; start as in
         // Model.RunRestartBatch.  exclude[k]: the nodes whose LIKEd items are not candidates of vector k (Recommender.cs:20-24

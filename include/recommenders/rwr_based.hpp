@@ -387,6 +387,30 @@ public:
         return out;
     }
 
+    // addition: the top-N lists of K seeds among the nodes of ONE node type (rwr_recommend_typed_batch).  candType: the
+    // candidates' type; exclEdgeTypes: the targets of the seed's raw links of these types are no candidates; excludeSelf: neither
+    // is the seed.  "Who to follow" is (NodeType::USER, {FRIENDSHIP, FOLLOW}, true)
+    std::vector<std::vector<std::pair<int64_t, double>>> recommendTypedBatch(const std::vector<int> &seeds, float dampingFactor,
+                                                                             int nIteration, int topN, NodeType candType,
+                                                                             const std::vector<EdgeType> &exclEdgeTypes = {},
+                                                                             bool excludeSelf = false)
+    {
+        const int32_t K = (int32_t)seeds.size();
+        if (topN < 1) throw std::invalid_argument("recommendTypedBatch: topN must be >= 1");
+        uint32_t mask = 0;
+        for (EdgeType t : exclEdgeTypes) mask |= 1u << (unsigned)t;
+        std::vector<int32_t> sd(seeds.begin(), seeds.end());
+        std::vector<int64_t> ids((size_t)K * (size_t)topN);
+        std::vector<double> scores((size_t)K * (size_t)topN);
+        std::vector<int32_t> counts((size_t)K);
+        check(rwr_recommend_typed_batch(graph_.handle(), sd.data(), K, dampingFactor, nIteration, topN, (int32_t)candType, mask, excludeSelf ? 1 : 0, ids.data(), scores.data(), counts.data()));
+        std::vector<std::vector<std::pair<int64_t, double>>> out((size_t)K);
+        for (int32_t k = 0; k < K; ++k)
+            for (int32_t q = 0; q < counts[k]; ++q)
+                out[k].emplace_back(ids[(size_t)k * (size_t)topN + q], scores[(size_t)k * (size_t)topN + q]);
+        return out;
+    }
+
     // addition: the top-N lists of K walks with caller-set restart vectors, ranked on the device (rwr_recommend_restart_batch).
     // nodes / weights (>= 0) / start as in Model::runRestartBatch.  exclude[k]: the nodes whose LIKEd items are not candidates
     // of vector k (Recommender.cs:20-24 for each of them); exclude == nullptr: the nodes of vector k's own support

@@ -312,6 +312,35 @@ int32_t rwr_eval_graphs(int32_t count, const rwr_graph_desc *graphs, const int32
  * row is id 0 / score 0).  Result k is exactly rwr_recommend(seeds[k], d, n_iter, top_n). */
 int32_t rwr_recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter,
                             int32_t top_n, int64_t *ids, double *scores, int32_t *counts);
+/* Recommendation among the nodes of ANY node type -- an addition beside the reference surface, whose Recommendation
+ * (Recommender.cs:20-31) ranks ITEM nodes the seed does not LIKE and nothing else, while its loader links USER nodes by
+ * FRIENDSHIP, FOLLOW and MENTION as well (DataLoader.cs:331-341, 359-360, 392): "who to follow" is candidates USER, mask
+ * FRIENDSHIP | FOLLOW, exclude_self; "similar items" is candidates ITEM from an item seed, mask 0.
+ * Result k: the rank row that rwr_model_run(g, seeds[k], (double)d, RWR_RUN_ITERATIONS, n_iter, ...) returns (d is widened
+ * as Recommender.cs:16 widens it; a negative n_iter runs no step); of it
+ *   - the candidates are the nodes with node_type == cand_type (any value 0..255: node types are unchecked at create);
+ *   - a candidate is dropped when it is the target of a RAW out-link of the seed whose type t has bit (1u << t) set in
+ *     excl_edge_mask (Recommender.cs:20-24 with the link type as a set; RWR_EDGE_UNDEFINED's bit is legal and drops the
+ *     targets of UNDEFINED raw links), and the seed itself is dropped when exclude_self != 0;
+ *   - the rest is ordered by score descending, then id descending (Recommender.cs:35-38); the first top_n of them go into
+ *     row k of ids / scores (K x top_n, row-major), counts[k] = entries written, the rest of the row id 0 / score 0.
+ * Ids are identical to that composition and scores bitwise equal to it, for every seed: duplicate seeds, dangling seeds and
+ * seeds of another type than cand_type are allowed and give what the composition gives.
+ *   - cand_type = RWR_NODE_ITEM, excl_edge_mask = 1u << RWR_EDGE_LIKE, exclude_self = 0 is rwr_recommend_batch: the same ids,
+ *     scores and counts.
+ *   - The domain is that of the Recommendation entries: a graph with a negative weight or d outside [0, 1] gives
+ *     RWR_E_UNSUPPORTED (the ranking marks exclusions with -1 and relies on scores >= 0).
+ *   - top_n in [1, 1024]: a larger top_n gives RWR_E_UNSUPPORTED with the limit in the message (whole lists of a node type
+ *     are not implemented).
+ *   - Argument errors, all found before any device work: a NULL g is refused first; K == 0 is a no-op (RWR_OK); K < 0, NULL
+ *     seeds / ids / scores / counts, top_n < 1, cand_type outside [0, 255] or a mask bit >= 8 give RWR_E_INVALID; a seed
+ *     outside [0, n) gives RWR_E_RANGE with its batch position in the message.  A refused call writes nothing.
+ *   - The candidate list of a node type is built on the device by the first call that names it and kept with the handle
+ *     (four types at most; rwr_graph_append_nodes makes the next call rebuild it).
+ *   - opts.tile_seeds, tile_group and workspace_bytes keep their meaning (the seeds run as tiles of the batched SpMM). */
+int32_t rwr_recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                  int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,
+                                  int64_t *ids, double *scores, int32_t *counts);
 
 /* ---- Model ---------------------------------------------------------------------------
  * Backs the public class Model: ctor (Model.cs:33-50 personalised, seed >= 0;

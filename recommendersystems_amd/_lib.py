@@ -21,7 +21,7 @@ EXPORTS = [
     "rwr_graph_create", "rwr_graph_update_links", "rwr_graph_append_links", "rwr_graph_append_nodes", "rwr_graph_destroy", "rwr_graph_size", "rwr_graph_get_normalized",
     "rwr_recommend", "rwr_recommend_eval", "rwr_recommend_eval_batch", "rwr_eval_graphs", "rwr_recommend_batch", "rwr_model_run", "rwr_model_deliver",
     "rwr_model_run_restart", "rwr_model_deliver_restart", "rwr_model_run_batch", "rwr_model_run_restart_batch",
-    "rwr_recommend_restart_batch", "rwr_recommend_restart_eval_batch",
+    "rwr_recommend_restart_batch", "rwr_recommend_restart_eval_batch", "rwr_recommend_typed_batch",
     "rwr_part_begin", "rwr_part_step", "rwr_part_local_step", "rwr_part_finish_step", "rwr_part_rank",
     "rwr_get_stats", "rwr_reset_stats",
 ]
@@ -106,6 +106,9 @@ def load():
     lib.rwr_recommend_batch.restype = C.c_int32
     lib.rwr_recommend_batch.argtypes = [C.c_void_p, p(C.c_int32), C.c_int32, C.c_float, C.c_int32, C.c_int32,
                                         p(C.c_int64), p(C.c_double), p(C.c_int32)]
+    lib.rwr_recommend_typed_batch.restype = C.c_int32
+    lib.rwr_recommend_typed_batch.argtypes = [C.c_void_p, p(C.c_int32), C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_uint32, C.c_int32, p(C.c_int64), p(C.c_double), p(C.c_int32)]
     lib.rwr_model_run.restype = C.c_int32
     lib.rwr_model_run.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_double, p(C.c_double),
                                   p(C.c_int64)]

@@ -9,6 +9,7 @@
 #include "eval_plan.h"
 #include "exclude_plan.h"
 #include "handle.h"
+#include "rank.h"
 
 namespace rwr {
 
@@ -311,6 +312,60 @@ int32_t rwr_recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float
     if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
     // Recommender.cs:14,16 -> Model.cs:33: the float is widened to double
     return bound("rwr_recommend_batch", g, [&] { return recommend_batch(g, seeds, K, (double)d, n_iter, top_n, ids, scores, counts, top_n); });
+}
+
+int32_t rwr_recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                  int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t *ids, double *scores,
+                                  int32_t *counts)
+{
+    static const char *const who = "rwr_recommend_typed_batch";
+    g_err[0] = 0;
+    const TypedCheck c = typed_check(g != nullptr, g ? g->n : 0, seeds, K, top_n, rank_select_max_k(), cand_type, excl_edge_mask,
+                                     ids && scores && counts);
+    switch (c.verdict) {
+        case TYPED_OK: break;
+        case TYPED_NOOP: return RWR_OK;
+        case TYPED_NULL_GRAPH:
+            set_error("%s: NULL graph", who);
+            return RWR_E_INVALID;
+        case TYPED_NEGATIVE_K:
+            set_error("%s: negative K", who);
+            return RWR_E_INVALID;
+        case TYPED_NULL_ARG:
+            set_error("%s: NULL seeds, ids, scores or counts", who);
+            return RWR_E_INVALID;
+        case TYPED_BAD_TOP_N:
+            set_error("%s: top_n must be >= 1", who);
+            return RWR_E_INVALID;
+        case TYPED_BAD_CAND_TYPE:
+            set_error("%s: cand_type %d is outside [0, 255]", who, cand_type);
+            return RWR_E_INVALID;
+        case TYPED_BAD_MASK:
+            set_error("%s: excl_edge_mask 0x%x has a bit beyond the %u edge types", who, excl_edge_mask, TYPED_EDGE_TYPES);
+            return RWR_E_INVALID;
+        case TYPED_SEED_RANGE:
+            set_error("%s: seed %d (batch position %d) is outside [0, %d)", who, c.bad_seed, c.bad_k, g->n);
+            return RWR_E_RANGE;
+        case TYPED_TOP_N_LIMIT:
+            set_error("%s: top_n %d is beyond the select path's limit of %d entries (whole lists of a node type are not "
+                      "implemented)", who, top_n, rank_select_max_k());
+            return RWR_E_UNSUPPORTED;
+    }
+    // the domain of the Recommendation entries: the exclusion marker (-1) and the ranking keys assume scores >= 0
+    if (!g->nonneg) {
+        set_error("%s: Recommendation needs non-negative finite link weights and positive row sums; rwr_model_run_batch "
+                  "accepts such graphs", who);
+        return RWR_E_UNSUPPORTED;
+    }
+    if (!((double)d >= 0.0 && (double)d <= 1.0)) {
+        set_error("%s: Recommendation needs a damping factor in [0, 1] (got %g); rwr_model_run_batch accepts any value", who, (double)d);
+        return RWR_E_UNSUPPORTED;
+    }
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    // Recommender.cs:14,16 -> Model.cs:33: the float is widened to double
+    return bound(who, g, [&] {
+        return recommend_typed_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, ids, scores, counts);
+    });
 }
 
 int32_t rwr_recommend(rwr_graph *g, int32_t seed, float d, int32_t n_iter, int32_t top_n, int64_t *out_id,

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <new>
 
+#include "cand_plan.h"
 #include "common.h"
 #include "stage_layout.h"
 
@@ -79,6 +80,12 @@ struct rwr_graph {
     int32_t tail_depth = 0;
     std::vector<uint8_t> h_tail_flag;
     int32_t tail_state = 0;
+    // candidate rows by node type (rwr_recommend_typed_batch): cand_rows[e] = the rows with node_type ==
+    // cand_entry[e].type by row index ascending, compacted on the device on first use (typed.hip).  An entry is valid while
+    // cand_entry[e].n == n (cand_plan.h: node types never change, nodes are only appended), so no (re)build resets it
+    rwr::DevBuf<int32_t> cand_rows[rwr::CAND_CACHE];
+    rwr::CandEntry cand_entry[rwr::CAND_CACHE];
+    uint64_t cand_calls = 0;          // typed calls so far: the entries' use stamps
 
     // single-seed SpMV of value-free graphs as a source-block sweep with z staged through LDS (sweep.hip): 0 = not decided
     // yet, 1 = tables built, -1 = this graph does not qualify; re-decided after every (re)build
@@ -289,6 +296,12 @@ void launch_restart_fold_cols(rwr_graph *g, int G, int32_t npairs, const int32_t
 void launch_restart_scatter_cols(rwr_graph *g, int G, int32_t npairs, const int32_t *pq, const int32_t *pr, const double *fold,
                                  double *Y, hipStream_t s);
 void launch_restart_init_cols(rwr_graph *g, int G, int tg, const int32_t *st, double *X, hipStream_t s);
+// typed.hip: K personalised walks ranked among the nodes of one type (rwr_recommend_typed_batch): candidates =
+// rows of type cand_type, the seed's raw out-links whose type has its bit in excl_edge_mask excluded, the seed too when
+// exclude_self; T whole steps; arguments as cand_plan.h's typed_check passed them, a nonneg graph and d in [0, 1]
+int32_t recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
+                              int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t *ids, double *scores,
+                              int32_t *counts);
 // model.hip pieces restart.hip runs as well (the loops around them: run_walk and GroupColumns, iterate.h).  A run's end condition (Model.run(int) / run(double) / run(), Model.cs:52-66):
 // T steps at most; !by_count: until checkConvergence's distance is < threshold, a failure after max_iters = RWR_MAX_ITERS steps
 struct RunEnd {

@@ -741,6 +741,35 @@ class Recommender:
                                            _p(counts, C.c_int32)))
         return ids, sc, counts
 
+    def RecommendationTypedBatch(self, seeds, dampingFactor: float, nIteration: int, topN: int, candType,
+                                 exclEdgeTypes=(), excludeSelf: bool = False):
+        """Top-N lists among the nodes of one node type for K seeds (rwr_recommend_typed_batch, an addition, see
+        include/rwr.h): (ids[K,topN], scores[K,topN], counts[K]).  candType: the candidates' NodeType; exclEdgeTypes: an
+        iterable of EdgeType -- the targets of the seed's raw links of those types are no candidates; excludeSelf: neither is
+        the seed.  "Who to follow" is (NodeType.USER, (EdgeType.FRIENDSHIP, EdgeType.FOLLOW), True)."""
+        lib = _lib.load()
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        K = int(seeds.shape[0])
+        mask = 0
+        for t in exclEdgeTypes:
+            mask |= 1 << int(EdgeType(t))
+        topN = int(topN)
+        ids = np.zeros((K, max(topN, 0)), dtype=np.int64)
+        sc = np.zeros((K, max(topN, 0)), dtype=np.float64)
+        counts = np.zeros(K, dtype=np.int32)
+        _lib.check(lib.rwr_recommend_typed_batch(self.graph._handle(), _p(seeds, C.c_int32), K, C.c_float(dampingFactor),
+                                                 int(nIteration), topN, int(candType), mask, 1 if excludeSelf else 0,
+                                                 _p(ids, C.c_int64), _p(sc, C.c_double), _p(counts, C.c_int32)))
+        return ids, sc, counts
+
+    def RecommendationTyped(self, idxTargetNode: int, dampingFactor: float, nIteration: int, topN: int, candType,
+                            exclEdgeTypes=(), excludeSelf: bool = False) -> List[Tuple[int, float]]:
+        """RecommendationTypedBatch for one seed, as Recommendation returns its list: [(node id, score), ...]."""
+        ids, sc, counts = self.RecommendationTypedBatch([int(idxTargetNode)], dampingFactor, nIteration, topN, candType,
+                                                        exclEdgeTypes, excludeSelf)
+        c = int(counts[0])
+        return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist()))
+
     def RecommendationRestartBatch(self, restarts, starts, dampingFactor: float, nIteration: int, topN: int, exclude=None):
         """Top-N lists of K walks with caller-set restart vectors, ranked on the device (rwr_recommend_restart_batch, an
         addition, see include/rwr.h): (ids[K,topN], scores[K,topN], counts[K]).  restarts and starts as in

@@ -1,0 +1,260 @@
+// Host-side check of the typed recommendation's plan (recommendersystems_amd/csrc/cand_plan.h), built against the header alone
+// by tests/test_cand_plan.py: the block geometry and the block offsets of the candidate compaction against a direct count,
+// the cache's choice over sequences of (type, n) requests against a brute-force model of the rule, and every argument verdict
+// in its order.  Prints every failure and exits non-zero if there is one.
+#include "cand_plan.h"
+
+#include <cstdio>
+#include <random>
+#include <string>
+#include <vector>
+
+using namespace rwr;
+
+static int failures = 0;
+
+static void fail(const std::string &what)
+{
+    if (++failures <= 40) std::printf("FAIL %s\n", what.c_str());
+}
+
+// ---- geometry and block offsets ------------------------------------------------------------------------------------------------
+
+static void check_offsets(const std::string &name, const std::vector<uint8_t> &types, int32_t t)
+{
+    const int32_t n = (int32_t)types.size();
+    const int32_t nb = cand_blocks(n);
+    if ((int64_t)nb * CAND_BLOCK < n || (nb > 0 && (int64_t)(nb - 1) * CAND_BLOCK >= n)) fail(name + ": block count");
+    // the blocks tile [0, n) in order, each of at most CAND_BLOCK rows and none empty
+    int32_t at = 0;
+    for (int32_t b = 0; b < nb; ++b) {
+        const int32_t lo = cand_block_lo(b), hi = cand_block_hi(b, n);
+        if (lo != at || hi <= lo || hi - lo > CAND_BLOCK || hi > n) { fail(name + ": block " + std::to_string(b) + " bounds"); return; }
+        at = hi;
+    }
+    if (at != n) fail(name + ": blocks do not cover the rows");
+    const std::vector<int32_t> off = cand_block_offsets(types.empty() ? nullptr : types.data(), n, t);
+    if (off.size() != (size_t)nb + 1) { fail(name + ": offset table length"); return; }
+    // brute force: matches below every block's first row; the list a scatter by these offsets builds is the ascending one
+    std::vector<int32_t> want_list, got_list;
+    for (int32_t i = 0; i < n; ++i)
+        if (types[(size_t)i] == t) want_list.push_back(i);
+    for (int32_t b = 0; b <= nb; ++b) {
+        int32_t below = 0;
+        const int32_t end = b < nb ? cand_block_lo(b) : n;
+        for (int32_t i = 0; i < end; ++i) below += types[(size_t)i] == t;
+        if (off[(size_t)b] != below) { fail(name + ": offset of block " + std::to_string(b)); return; }
+    }
+    got_list.assign((size_t)off[(size_t)nb], -1);
+    for (int32_t b = 0; b < nb; ++b) {
+        int32_t pos = off[(size_t)b];
+        for (int32_t i = cand_block_lo(b); i < cand_block_hi(b, n); ++i)
+            if (types[(size_t)i] == t) {
+                if (pos >= off[(size_t)b + 1]) { fail(name + ": a block writes past its share"); return; }
+                got_list[(size_t)pos++] = i;
+            }
+    }
+    if (got_list != want_list) fail(name + ": the scattered list is not the ascending list of matches");
+}
+
+static void check_all_offsets()
+{
+    const int32_t B = CAND_BLOCK;
+    std::mt19937_64 rng(3);
+    for (int32_t n : {0, 1, B - 1, B, B + 1, 3 * B + 7}) {
+        const std::string at = "n=" + std::to_string(n);
+        check_offsets(at + " none", std::vector<uint8_t>((size_t)n, 2), 1);
+        check_offsets(at + " all", std::vector<uint8_t>((size_t)n, 1), 1);
+        for (int32_t only = 0; only < n; only += (n > 8 ? n / 7 : 1)) {      // one match, at several places and at the end
+            std::vector<uint8_t> v((size_t)n, 0);
+            v[(size_t)only] = 3;
+            check_offsets(at + " one at " + std::to_string(only), v, 3);
+        }
+        if (n > 0) {
+            std::vector<uint8_t> v((size_t)n, 0);
+            v[(size_t)n - 1] = 255;
+            check_offsets(at + " last row, type 255", v, 255);
+            for (int it = 0; it < 6; ++it) {
+                for (auto &x : v) x = (uint8_t)(rng() % 4);
+                check_offsets(at + " random " + std::to_string(it), v, (int32_t)(rng() % 5));
+            }
+        }
+    }
+    // more blocks than the scan takes per trip: the carry crosses chunks
+    {
+        const int32_t n = (CAND_SCAN_CHUNK + 3) * B + 5;
+        std::vector<uint8_t> v((size_t)n);
+        for (auto &x : v) x = (uint8_t)(rng() % 3);
+        check_offsets("two scan chunks", v, 1);
+        check_offsets("two scan chunks, no match", v, 9);
+    }
+}
+
+// ---- the cache -------------------------------------------------------------------------------------------------------------------
+
+// the rule spelled out over plain arrays: which entry, and whether its list is reused
+static void model_choose(const int32_t *type, const int32_t *built_n, const uint64_t *used, int32_t want, int32_t n, int *entry,
+                         bool *hit)
+{
+    *hit = false;
+    for (int i = 0; i < CAND_CACHE; ++i)
+        if (type[i] == want) { *entry = i; *hit = built_n[i] == n; return; }
+    for (int i = 0; i < CAND_CACHE; ++i)
+        if (type[i] < 0) { *entry = i; return; }
+    for (int i = 0; i < CAND_CACHE; ++i)
+        if (built_n[i] != n) { *entry = i; return; }
+    *entry = 0;
+    for (int i = 1; i < CAND_CACHE; ++i)
+        if (used[i] < used[*entry]) *entry = i;
+}
+
+struct Request { int32_t type, n; };
+
+// plays the requests as the driver does (choose, rebuild on a miss, stamp the use) and checks every choice against the model,
+// and the two properties the driver relies on: a hit's list was built for the type and for n, and no type sits in two entries
+static void check_sequence(const std::string &name, const std::vector<Request> &reqs, int want_hits)
+{
+    CandEntry e[CAND_CACHE];
+    int32_t type[CAND_CACHE], built_n[CAND_CACHE];
+    uint64_t used[CAND_CACHE], clock = 0;
+    for (int i = 0; i < CAND_CACHE; ++i) type[i] = -1, built_n[i] = -1, used[i] = 0;
+    int hits = 0;
+    for (size_t r = 0; r < reqs.size(); ++r) {
+        const CandChoice c = cand_cache_choose(e, reqs[r].type, reqs[r].n);
+        int me = 0;
+        bool mh = false;
+        model_choose(type, built_n, used, reqs[r].type, reqs[r].n, &me, &mh);
+        if (c.entry != me || c.hit != mh || c.entry < 0 || c.entry >= CAND_CACHE) {
+            fail(name + ": request " + std::to_string(r) + " chose entry " + std::to_string(c.entry) + (c.hit ? " (hit)" : " (miss)"));
+            return;
+        }
+        if (c.hit && (e[c.entry].type != reqs[r].type || e[c.entry].n != reqs[r].n)) fail(name + ": a hit on a list of another type or node count");
+        hits += c.hit;
+        ++clock;
+        if (!c.hit) {
+            e[c.entry] = CandEntry{};
+            e[c.entry].type = reqs[r].type, e[c.entry].n = reqs[r].n, e[c.entry].rows = (int32_t)r;
+        }
+        e[c.entry].used = clock;
+        type[c.entry] = reqs[r].type, built_n[c.entry] = reqs[r].n, used[c.entry] = clock;
+        for (int i = 0; i < CAND_CACHE; ++i)
+            for (int j = i + 1; j < CAND_CACHE; ++j)
+                if (e[i].type >= 0 && e[i].type == e[j].type) fail(name + ": one type in two entries");
+    }
+    if (want_hits >= 0 && hits != want_hits) fail(name + ": " + std::to_string(hits) + " hits, " + std::to_string(want_hits) + " expected");
+}
+
+static void check_cache()
+{
+    check_sequence("first use, then reuse", {{1, 100}, {1, 100}, {1, 100}}, 2);
+    check_sequence("growth of n rebuilds in place", {{1, 100}, {1, 101}, {1, 101}, {1, 100}}, 1);
+    check_sequence("four types fit", {{0, 50}, {1, 50}, {2, 50}, {3, 50}, {0, 50}, {1, 50}, {2, 50}, {3, 50}}, 4);
+    // a fifth type evicts the one used longest ago (type 0); type 0 then evicts type 1, and so on: no hit in a cycle of five
+    check_sequence("cycle of five", {{0, 50}, {1, 50}, {2, 50}, {3, 50}, {4, 50}, {0, 50}, {1, 50}, {2, 50}}, 0);
+    // ... but a recently used one survives the eviction
+    check_sequence("recent use survives", {{0, 50}, {1, 50}, {2, 50}, {3, 50}, {0, 50}, {4, 50}, {0, 50}, {1, 50}}, 2);
+    // after growth the stale lists go first, whatever their age
+    check_sequence("stale before old", {{0, 50}, {1, 50}, {2, 50}, {3, 50}, {3, 60}, {4, 60}, {3, 60}, {5, 60}, {4, 60}}, 2);
+    check_sequence("type 255 and type 0", {{255, 7}, {0, 7}, {255, 7}, {0, 7}}, 2);
+    std::mt19937_64 rng(11);
+    for (int it = 0; it < 200; ++it) {
+        std::vector<Request> reqs;
+        int32_t n = 10;
+        const int ntypes = 2 + (int)(rng() % 6);
+        for (int r = 0; r < 60; ++r) {
+            if (rng() % 9 == 0) n += 1 + (int32_t)(rng() % 3);
+            reqs.push_back({(int32_t)(rng() % (uint64_t)ntypes), n});
+        }
+        check_sequence("random " + std::to_string(it), reqs, -1);
+    }
+}
+
+// ---- the argument verdicts ---------------------------------------------------------------------------------------------------------
+
+struct Args {
+    bool graph = true;
+    int32_t n = 10;
+    std::vector<int32_t> seeds = {0, 9, 3};
+    bool null_seeds = false;
+    int32_t K = 3, top_n = 5, top_n_max = 1024, cand_type = 1;
+    uint32_t mask = 0x0c;
+    bool outs = true;
+};
+
+// the verdict by a plain restatement of the header comment of rwr_recommend_typed_batch, first finding first
+static TypedVerdict model_verdict(const Args &a, int32_t *bad_k)
+{
+    *bad_k = -1;
+    if (!a.graph) return TYPED_NULL_GRAPH;
+    if (a.K < 0) return TYPED_NEGATIVE_K;
+    if (a.K == 0) return TYPED_NOOP;
+    if (a.null_seeds || !a.outs) return TYPED_NULL_ARG;
+    if (a.top_n < 1) return TYPED_BAD_TOP_N;
+    if (a.cand_type < 0 || a.cand_type > 255) return TYPED_BAD_CAND_TYPE;
+    for (uint32_t bit = 8; bit < 32; ++bit)
+        if (a.mask & (1u << bit)) return TYPED_BAD_MASK;
+    for (int32_t k = 0; k < a.K; ++k)
+        if (a.seeds[(size_t)k] < 0 || a.seeds[(size_t)k] >= a.n) { *bad_k = k; return TYPED_SEED_RANGE; }
+    if (a.top_n > a.top_n_max) return TYPED_TOP_N_LIMIT;
+    return TYPED_OK;
+}
+
+static void check_args(const std::string &name, const Args &a, int want /* -1: the model decides */)
+{
+    int32_t bad_k = -1;
+    const TypedVerdict m = model_verdict(a, &bad_k);
+    const TypedCheck c = typed_check(a.graph, a.n, a.null_seeds ? nullptr : a.seeds.data(), a.K, a.top_n, a.top_n_max, a.cand_type,
+                                     a.mask, a.outs);
+    if (c.verdict != m || (want >= 0 && (int)c.verdict != want)) fail(name + ": verdict " + std::to_string((int)c.verdict));
+    if (m == TYPED_SEED_RANGE && (c.bad_k != bad_k || c.bad_seed != a.seeds[(size_t)bad_k])) fail(name + ": the offending seed");
+}
+
+static void check_verdicts()
+{
+    Args ok;
+    check_args("ok", ok, TYPED_OK);
+    { Args a; a.graph = false; a.K = -1; a.top_n = 0; a.cand_type = 900; check_args("NULL graph first", a, TYPED_NULL_GRAPH); }
+    { Args a; a.K = -1; a.null_seeds = true; check_args("negative K", a, TYPED_NEGATIVE_K); }
+    { Args a; a.K = 0; a.null_seeds = true; a.outs = false; a.top_n = 0; a.cand_type = -1; check_args("K = 0 is a no-op", a, TYPED_NOOP); }
+    { Args a; a.null_seeds = true; check_args("NULL seeds", a, TYPED_NULL_ARG); }
+    { Args a; a.outs = false; check_args("NULL outputs", a, TYPED_NULL_ARG); }
+    { Args a; a.top_n = 0; check_args("top_n 0", a, TYPED_BAD_TOP_N); }
+    { Args a; a.top_n = -3; check_args("top_n < 0", a, TYPED_BAD_TOP_N); }
+    { Args a; a.cand_type = -1; check_args("cand_type -1", a, TYPED_BAD_CAND_TYPE); }
+    { Args a; a.cand_type = 256; check_args("cand_type 256", a, TYPED_BAD_CAND_TYPE); }
+    { Args a; a.cand_type = 0; check_args("cand_type 0", a, TYPED_OK); }
+    { Args a; a.cand_type = 255; check_args("cand_type 255", a, TYPED_OK); }
+    { Args a; a.mask = 0; check_args("mask 0", a, TYPED_OK); }
+    { Args a; a.mask = 0xff; check_args("every legal bit", a, TYPED_OK); }
+    { Args a; a.mask = 1u; check_args("UNDEFINED's bit", a, TYPED_OK); }
+    { Args a; a.mask = 0x100; check_args("bit 8", a, TYPED_BAD_MASK); }
+    { Args a; a.mask = 0x80000002u; check_args("bit 31", a, TYPED_BAD_MASK); }
+    { Args a; a.seeds = {0, 10, -1}; check_args("seed n", a, TYPED_SEED_RANGE); }
+    { Args a; a.seeds = {0, 9, -1}; check_args("seed -1", a, TYPED_SEED_RANGE); }
+    { Args a; a.seeds = {4, 4, 4}; check_args("duplicate seeds", a, TYPED_OK); }
+    { Args a; a.top_n = 1024; check_args("top_n at the limit", a, TYPED_OK); }
+    { Args a; a.top_n = 1025; check_args("top_n beyond the limit", a, TYPED_TOP_N_LIMIT); }
+    { Args a; a.top_n = 1025; a.seeds = {0, 99, 1}; check_args("a bad seed before the limit", a, TYPED_SEED_RANGE); }
+    // every combination of one good and one bad value per argument: the first finding in the documented order wins
+    for (int bits = 0; bits < (1 << 8); ++bits) {
+        Args a;
+        a.graph = !(bits & 1);
+        a.K = (bits & 2) ? -2 : 3;
+        a.null_seeds = (bits & 4) != 0;
+        a.top_n = (bits & 8) ? 0 : 5;
+        a.cand_type = (bits & 16) ? 300 : 2;
+        a.mask = (bits & 32) ? 0x200 : 0x6;
+        if (bits & 64) a.seeds[1] = 10;
+        a.outs = !(bits & 128);
+        check_args("combination " + std::to_string(bits), a, -1);
+    }
+}
+
+int main()
+{
+    check_all_offsets();
+    check_cache();
+    check_verdicts();
+    std::printf("%d failures\n", failures);
+    return failures ? 1 : 0;
+}
