@@ -133,6 +133,8 @@ typedef struct rwr_stats {
     int64_t x_clear_skipped;        /* tile groups of rwr_recommend_batch that started without clearing their rank matrix: the
                                        fold beside step 2 read the frontier-list step's output through its bitmap (RWR_X_CLEAR=1:
                                        none) */
+    int64_t entry_live_launches;    /* SpMM launches of rwr_recommend_batch's bitmap-probing steps that read the step's per-link
+                                       tile masks instead of probing the frontier bitmaps per entry (RWR_ENTRY_LIVE=0: none) */
 } rwr_stats;
 
 /* ---- library ------------------------------------------------------------------------- */

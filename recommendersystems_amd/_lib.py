@@ -49,7 +49,8 @@ class rwr_stats(C.Structure):
                 ("spmm_dense_ms", C.c_double), ("spmm_dense_launches", C.c_int64), ("spmm_dense_seed_steps", C.c_int64),
                 ("uniform_path", C.c_int32), ("reserved1", C.c_int32), ("frontier_list_launches", C.c_int64),
                 ("rank_fused_groups", C.c_int64), ("rank_fused_fallbacks", C.c_int64),
-                ("rank_pruned_rows", C.c_int64), ("rank_bound_ms", C.c_double), ("x_clear_skipped", C.c_int64)]
+                ("rank_pruned_rows", C.c_int64), ("rank_bound_ms", C.c_double), ("x_clear_skipped", C.c_int64),
+                ("entry_live_launches", C.c_int64)]
 
 
 class RwrError(RuntimeError):

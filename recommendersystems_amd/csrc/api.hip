@@ -687,6 +687,7 @@ int32_t rwr_reset_stats(rwr_graph *g)
     s.rank_pruned_rows = 0;
     s.rank_bound_ms = 0;
     s.x_clear_skipped = 0;
+    s.entry_live_launches = 0;
     return RWR_OK;
 }
 

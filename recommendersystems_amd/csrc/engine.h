@@ -117,6 +117,10 @@ struct rwr_graph {
     rwr::DevBuf<unsigned int> d_gate;   // exact mode: check-in counter of the resident chain workgroups
     rwr::DevBuf<uint32_t> d_nz;       // [2][tile][ceil(n/32)] bitmaps: row of X / Y has a non-zero (first iterations)
     rwr::DevBuf<int32_t> fl_rows;     // [tile][n] frontier row lists of a batch's first steps, then [tile] their lengths
+    // per-link tile masks of a batch's bitmap-probing steps, rewritten by every such step: ent_nzT =
+    // [slab][n] the group's frontier bitmaps node-major (bit t & 31 of slab t >> 5 = node live in tile t), ent_live =
+    // [slab][nnz] that word of every link's source, in the order of in_src
+    rwr::DevBuf<uint32_t> ent_nzT, ent_live;
     rwr::DevBuf<int64_t> d_evoff;     // exact mode: per seed slot, offset of its in-link terms in d_evterm
     rwr::DevBuf<double> d_evterm;     // exact mode: ((1-d) x_src) * w of every link INTO a seed, list order
     // exact mode, parallel seed-row chain (chain_scan.hip): per (tile, block, seed) approximate block sum,

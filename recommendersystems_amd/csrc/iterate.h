@@ -49,6 +49,9 @@ struct SpmmArgs {
     RowSource rows{};
     int32_t row_first = 0, row_count = -1;   // a tail level's rows [row_first, row_first + row_count) only (-1: to the end)
     const SelSink *sel = nullptr;            // the launch writes no Y: it appends the rows that reach tau (k_spmm_select)
+    // a probing launch over every row (nz_in set): the step's per-link tile masks [slab][nnz] (launch_entry_live), which it
+    // reads instead of probing nz_in; nullptr: the bitmap probe
+    const uint32_t *ent_live = nullptr;
 };
 void launch_spmm(rwr_graph *g, int G, int tg, const SpmmArgs &a, hipStream_t s);
 // k_init_seeds (Model ctor), k_make_z (z of `elems` elements of X, w_src[0] belonging to X's first row), k_make_z_nz (z and

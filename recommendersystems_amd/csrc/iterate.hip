@@ -120,7 +120,10 @@ __global__ __launch_bounds__(256) void k_spmm(int32_t n, const int64_t *__restri
 // that kernel traces and counter passes tell these launches from the dense ones
 // SEL: the selecting form of a ranking-only batch's last step (k_spmm_select): no Y, no z -- a lane of a real
 // slot whose sum reaches the slot's threshold appends (row, sum) to the slot's candidate buffer (one integer atomicAdd)
-template <int G, int CH, bool CHECK, bool WRITE, bool VF, bool SEL = false>
+// LIVE: a CHECK form whose liveness comes from the step's per-link tile masks (k_entry_live) -- the lane that
+// loads in_src[p + k] loads ent_live[p + k] beside it, on the same lines, and tests its tile's bit, instead of probing the
+// tile's bitmap at a scattered address.  The bit is the one the probe would have read; everything after it is the same code
+template <int G, int CH, bool CHECK, bool WRITE, bool VF, bool SEL = false, bool LIVE = false>
 __device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__restrict__ in_ptr,
                                                   const int32_t *__restrict__ in_src,
                                                   const double *__restrict__ in_w,
@@ -131,10 +134,12 @@ __device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__re
                                                   uint32_t *__restrict__ nz_out,
                                                   const uint32_t *__restrict__ act,
                                                   const double *__restrict__ w_src, double *__restrict__ Zout,
-                                                  const SelSink sink = SelSink{})
+                                                  const SelSink sink = SelSink{},
+                                                  const uint32_t *__restrict__ ent_live = nullptr)
 {
     static_assert(G >= 8 && G <= 64, "chunked SpMM needs 8 <= G <= 64");
     static_assert(!SEL || (!CHECK && !WRITE), "the selecting form probes and writes no bitmap");
+    static_assert(!LIVE || CHECK, "the per-link masks replace the bitmap probe");
     constexpr int RPW = WAVE / G;
     // entries per index load; CH = entries per gather round.  The weighted forms at G = 64 keep the 16-entry load: with two
     // written-out rounds their probing forms need 98 and 102 instead of 96 and 100 SGPRs, one wave per SIMD fewer.
@@ -146,7 +151,7 @@ __device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__re
     if (!SEL) Y += toff;
     if (VF && Zout) Zout += toff;
     const size_t nzw = ((size_t)n + 31) / 32;
-    if (CHECK) nz_in += (size_t)tile * nzw;
+    if (CHECK && !LIVE) nz_in += (size_t)tile * nzw;
     if (WRITE) nz_out += (size_t)tile * nzw;
     if (CHECK && act) act += (size_t)tile * nzw;
     const int lane = threadIdx.x & (WAVE - 1);
@@ -183,7 +188,9 @@ __device__ __forceinline__ void spmm_chunked_body(int32_t n, const int64_t *__re
             if (k < cnt) {
                 my_idx = in_src[p + k];
                 if (!VF) my_w = in_w[p + k];
-                if (CHECK) {   // one bitmap probe per entry (by the lane that fetched it); dead rows get the sign bit
+                if (LIVE) {    // the link's tile mask, beside its index; dead rows get the sign bit
+                    if (!((ent_live[p + k] >> (tile & 31)) & 1u)) my_idx |= (int32_t)0x80000000;
+                } else if (CHECK) {   // one bitmap probe per entry (by the lane that fetched it); dead rows get the sign bit
                     const uint32_t wd = nz_in[(uint32_t)my_idx >> 5];
                     if (!((wd >> (my_idx & 31)) & 1u)) my_idx |= (int32_t)0x80000000;
                 }
@@ -324,6 +331,64 @@ __global__ __launch_bounds__(256) void k_spmm_frontier(int32_t n, const int64_t 
     const int tile = blockIdx.y;
     spmm_chunked_body<G, CH, true, true, VF>(n, in_ptr, in_src, in_w, fl_rows + (size_t)tile * (size_t)n, fl_cnt[tile], X, Y,
                                              seeds, c1, skip_seed_row, nz_in, nz_out, nullptr, w_src, Zout);
+}
+
+// Per-link tile masks for a probing step that walks every row.  "Is source s live in tile t" is one bit per
+// (tile, node) in the frontier bitmaps, which the SpMM would probe once per entry AND tile at a scattered address.  Instead,
+// once per step: k_nz_transpose turns the group's bitmaps node-major -- nzT[slab][node], bit t & 31 = node is live in tile
+// 32 * slab + (t & 31), tiles past the group's last read as 0 --, and k_entry_live gathers that word once per link, in link
+// order: live[slab][e] = nzT[slab][in_src[e]].  A tile's SpMM then reads its slab of `live` beside `in_src`.
+// One thread per node and slab: the 32 lanes of a bitmap word read the same word of each tile (one request per wave and tile)
+__global__ __launch_bounds__(256) void k_nz_transpose(int32_t n, int tg, const uint32_t *__restrict__ nz, uint32_t *__restrict__ nzT)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t nzw = ((size_t)n + 31) / 32;
+    const int slab = blockIdx.y;
+    uint32_t out = 0;
+#pragma unroll 8
+    for (int t = 0; t < 32; ++t) {
+        const int tile = slab * 32 + t;
+        if (tile < tg) out |= ((nz[(size_t)tile * nzw + (size_t)(i >> 5)] >> (i & 31)) & 1u) << t;
+    }
+    nzT[(size_t)slab * (size_t)n + (size_t)i] = out;
+}
+// in_src and live stream; one 4-byte gather per link and slab from the 4 n-byte table of the slab
+__global__ __launch_bounds__(256) void k_entry_live(int64_t nnz, int32_t n, int slabs, const int32_t *__restrict__ in_src,
+                                                    const uint32_t *__restrict__ nzT, uint32_t *__restrict__ live)
+{
+    constexpr int U = 4;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e0 < nnz; e0 += U * stride) {
+        int32_t src[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) src[u] = e0 + u * stride < nnz ? in_src[e0 + u * stride] : -1;
+        for (int sl = 0; sl < slabs; ++sl) {
+            uint32_t v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) v[u] = src[u] >= 0 ? nzT[(size_t)sl * (size_t)n + (size_t)src[u]] : 0u;
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (src[u] >= 0) live[(size_t)sl * (size_t)nnz + (size_t)(e0 + u * stride)] = v[u];
+        }
+    }
+}
+// ... and the probing SpMM over every row that reads them: the k_spmm_chunked body with its liveness from the tile's slab
+template <int G, int CH, bool WRITE, bool VF>
+__global__ __launch_bounds__(256) void k_spmm_entry_live(int32_t n, const int64_t *__restrict__ in_ptr,
+                                                         const int32_t *__restrict__ in_src,
+                                                         const double *__restrict__ in_w,
+                                                         const int32_t *__restrict__ row_order, int32_t nrows,
+                                                         const double *__restrict__ X, double *__restrict__ Y,
+                                                         const int32_t *__restrict__ seeds, double c1,
+                                                         int skip_seed_row, uint32_t *__restrict__ nz_out,
+                                                         const uint32_t *__restrict__ act,
+                                                         const double *__restrict__ w_src, double *__restrict__ Zout,
+                                                         const uint32_t *__restrict__ live, int64_t nnz)
+{
+    spmm_chunked_body<G, CH, true, WRITE, VF, false, true>(n, in_ptr, in_src, in_w, row_order, nrows, X, Y, seeds, c1,
+                                                           skip_seed_row, nullptr, nz_out, act, w_src, Zout, SelSink{},
+                                                           live + (size_t)(blockIdx.y >> 5) * (size_t)nnz);
 }
 
 // First iterations: destination rows that can become non-zero = out-neighbours (explicit links) of the rows of X
@@ -823,9 +888,21 @@ static PlanInput read_plan_knobs()
     if ((e = getenv("RWR_TAIL_ROWS"))) v.tail_rows = atoi(e);
     if ((e = RWR_TUNE_ENV("RWR_CHAIN_SERIAL"))) v.two_streams = atoi(e) == 0;
     if ((e = getenv("RWR_X_CLEAR"))) v.x_clear = atoi(e);
+    if ((e = getenv("RWR_ENTRY_LIVE"))) v.entry_live = atoi(e);
     return v;
 }
 static const PlanInput &plan_knobs() { static const PlanInput k = read_plan_knobs(); return k; }
+// the most a group's per-link tile masks may take (RWR_ENTRY_LIVE_CAP_MB, default 4 GB: C4's one slab takes 0.8 GB, C3's six
+// 1.2 GB); a group past it keeps the bitmap probe
+static size_t entry_live_cap_bytes()
+{
+    static const size_t v = [] {
+        const char *e = getenv("RWR_ENTRY_LIVE_CAP_MB");
+        const long long mb = e ? atoll(e) : 4096;
+        return (size_t)(mb > 0 ? mb : 0) << 20;
+    }();
+    return v;
+}
 
 // f(std::true_type or std::false_type, ...) for runtime bools: one instantiation of f per combination
 template <class F> static void bool_dispatch(F &&f) { f(); }
@@ -881,6 +958,16 @@ static void launch_spmm_g(rwr_graph *g, int tg, const SpmmArgs &a, hipStream_t s
                 hipLaunchKernelGGL((k_spmm_select<G, CH, decltype(v)::value>), dim3(gx, tg), dim3(256), 0, s, g->n, g->in_ptr.p,
                                    g->in_src.p, g->in_w.p, order, nrows, GS, a.seeds, a.c1, sink);
             }, vf);
+            return;
+        }
+    }
+    if constexpr (G >= 8) {
+        if (a.ent_live && a.nz_in && !listed && plan_knobs().spmm != 0) {   // a probing step over every row, masks built
+            bool_dispatch([&](auto wr, auto v) {
+                hipLaunchKernelGGL((k_spmm_entry_live<G, CH, decltype(wr)::value, decltype(v)::value>), dim3(gx, tg), dim3(256), 0,
+                                   s, g->n, g->in_ptr.p, g->in_src.p, g->in_w.p, order, nrows, GS, a.Y, a.seeds, a.c1, skip,
+                                   a.nz_out, a.act, g->w_src.p, a.Zout, a.ent_live, g->nnz);
+            }, a.nz_out != nullptr, vf);
             return;
         }
     }
@@ -1024,6 +1111,14 @@ int32_t GroupIter::init(bool fresh, bool ranks_nonneg, bool ranking_only)
         cfg.flist = false;
         cfg.clear_x = plan_clear_x(cfg);
     }
+    if (cfg.entry_live) {   // the group's per-link tile masks: one word per link and 32 tiles, and the node-major bitmaps
+        const size_t slabs = ((size_t)tg + 31) / 32, words = slabs * (size_t)g->nnz;
+        if (g->nnz <= 0 || words > entry_live_cap_bytes() / sizeof(uint32_t) || g->ent_nzT.ensure(slabs * (size_t)n) != RWR_OK ||
+            g->ent_live.ensure(words) != RWR_OK) {
+            (void)hipGetLastError();   // (past the cap, or no room: the per-entry bitmap probe of before, which needs neither)
+            cfg.entry_live = false;
+        }
+    }
     // X_0 is zero outside the seed rows.  On the frontier-list path every reader of steps 0 to 2 goes through the frontier
     // bitmaps, so the seed rows (k_init_seeds) are all of X that must be valid: no clear
     if (fresh && cfg.clear_x) RWR_HIP(hipMemsetAsync(X, 0, elems * sizeof(double), s));
@@ -1060,6 +1155,19 @@ int32_t GroupIter::step(const StepPlan &p, Profile &prof, int32_t row_first, int
         if (fl_cnt) RWR_HIP(hipMemsetAsync(fl_cnt, 0, (size_t)tg * sizeof(int32_t), s));
         launch_mark_active(g, G, tg, nz_in, act, d_seeds, fl_rows, fl_cnt, s);
     }
+    // Per-link tile masks of this step's frontier, on the main stream.  Every writer of nz_cur is behind this
+    // point of it: init's memset and k_init_seeds, or the step before -- its memset, its SpMM (WRITE) and its chain, whose
+    // second stream that step joined (ev_join) before it returned.  Nothing in this step writes nz_cur
+    const uint32_t *ent_live = nullptr;
+    if (p.entry_live && nz_in) {
+        const int slabs = (tg + 31) / 32;
+        hipLaunchKernelGGL(k_nz_transpose, dim3(cdiv((size_t)n, 256), slabs), dim3(256), 0, s, n, tg, nz_in, g->ent_nzT.p);
+        const unsigned want = cdiv((size_t)g->nnz, 256 * 4);
+        hipLaunchKernelGGL(k_entry_live, dim3(want < 1u ? 1u : want < (1u << 20) ? want : (1u << 20)), dim3(256), 0, s, g->nnz, n,
+                           slabs, g->in_src.p, g->ent_nzT.p, g->ent_live.p);
+        ent_live = g->ent_live.p;
+        g->stats.entry_live_launches += 1;
+    }
     const uint32_t *nz_terms = p.terms_nz ? nz_in : nullptr;
     double *zout = (Zc && p.form_z) ? Zn : nullptr;
     hipStream_t sc = p.chain_side ? g->stream2 : s;   // the chain's stream
@@ -1089,6 +1197,7 @@ int32_t GroupIter::step(const StepPlan &p, Profile &prof, int32_t row_first, int
     sp.nz_in = nz_in, sp.nz_out = nz_out, sp.act = act, sp.Zin = Zc, sp.Zout = zout;
     sp.hub_scan = cfg.addends_nonneg, sp.rows = p.rows;
     sp.row_first = row_first, sp.row_count = row_count;
+    sp.ent_live = ent_live;
     launch_spmm(g, G, tg, sp, s);
     RWR_TRY(prof.end(prof.spmm, a, s));
     if (prof.on) prof.dense.push_back(p.dense());

@@ -7,10 +7,14 @@
 
 namespace rwr {
 
+// Per-link tile masks (§3.3.2): graphs of fewer links keep the per-entry bitmap probe (the measurements behind the figure: §3.3.2)
+constexpr int64_t ENTRY_LIVE_MIN_NNZ = 100000000;
+
 // What a group's plan depends on.  First the environment values (iterate.hip: plan_knobs; defaults: the shipped library's):
 // RWR_SPMM (0: plain kernel, no bitmaps), RWR_NZ_ITERS, RWR_ACT_ITERS (-1: by graph shape), RWR_ACT_MIN_N, RWR_FRONTIER_LIST,
 // RWR_CHAIN (0 simple, 1 auto, 2 scan, 3 role-specialised fold), RWR_SCAN_WORK, RWR_SCAN_SIDE, RWR_GATE, RWR_TAIL_ROWS,
-// RWR_X_CLEAR (1: clear X on every fresh batch).
+// RWR_X_CLEAR (1: clear X on every fresh batch), RWR_ENTRY_LIVE (0: every probing step probes the bitmaps per entry and tile,
+// 1: per-link tile masks where the graph is large enough, 2: wherever the rule's other conditions hold).
 struct PlanInput {
     int spmm = 1, nz_iters = 4, act_iters = -1, frontier_list = 1, chain = 1, x_clear = 0;
     int64_t act_min_n = 200000; double scan_work = 10000.0;
@@ -25,6 +29,8 @@ struct PlanInput {
     bool fresh = true;            // Model ctor ranks; false: X holds caller-supplied ranks, whose frontier is unknown
     bool ranks_nonneg = true;     // the caller-supplied ranks are >= 0
     bool ranking_only = false;    // the caller reads only the ranking (recommend_batch): row-list steps allowed
+    int entry_live = 1;           // RWR_ENTRY_LIVE
+    int64_t entry_live_min_nnz = ENTRY_LIVE_MIN_NNZ;
 };
 
 // Everything fixed for one tile group
@@ -42,6 +48,7 @@ struct PlanConfig {
     unsigned need = 0;            // bit k: some seed of the group needs its chain at step T - 1 - k (the OR of h_tail_flag)
     bool force_clear = false;     // RWR_X_CLEAR=1
     bool clear_x = true;          // a fresh batch clears X before its seeds are written (plan_clear_x)
+    bool entry_live = false;      // the probing steps that walk every row read per-link tile masks (§3.3.2, plan_entry_live)
 };
 
 // Whether a fresh batch must clear X (§3.3.2).  A frontier-list step writes only its listed rows, and the chain of the step
@@ -49,6 +56,15 @@ struct PlanConfig {
 // read through the bitmap the list step wrote: only the role-specialised fold has such a form.  The scan and the simple fold
 // keep the clear, and so does every group that never lists.  To be called again whenever flist changes.
 inline bool plan_clear_x(const PlanConfig &c) { return c.force_clear || !c.flist || c.scan || c.chain_kind == 0; }
+
+// Whether a group's probing steps may read per-link tile masks instead of probing the frontier bitmaps per entry and tile:
+// only recommend_batch's groups (fresh ranks, ranking only) on the chunked kernels, with bitmaps at all, and -- unless
+// RWR_ENTRY_LIVE=2 -- on a graph whose pass over all links pays.  GroupIter::init withdraws it when the masks get no memory.
+inline bool plan_entry_live(const PlanInput &in, const PlanConfig &c)
+{
+    if (in.entry_live == 0 || !in.ranking_only || !in.fresh || in.G < 8 || c.nz_iters <= 0) return false;
+    return in.entry_live == 2 || in.nnz >= in.entry_live_min_nnz;
+}
 
 inline PlanConfig plan_config(const PlanInput &in)
 {
@@ -81,6 +97,7 @@ inline PlanConfig plan_config(const PlanInput &in)
     c.tails = in.ranking_only && in.tail_rows != 0 && !single;   // (a single seed's SpMV walks every row)
     c.force_clear = in.x_clear != 0;
     c.clear_x = plan_clear_x(c);
+    c.entry_live = plan_entry_live(in, c);
     return c;
 }
 
@@ -101,6 +118,7 @@ struct StepPlan {
     bool chain_side = false, gate = false;    // the chain runs on the second stream / the SpMM waits for it (k_gate)
     bool chain_self = false;                  // the scan gathers its terms from Z and forms the seed rows' next z
     bool form_z = false, seed_z = false;      // value-free path: the SpMM / k_seed_z forms the next z
+    bool entry_live = false;                  // the SpMM reads the step's per-link tile masks instead of probing (k_entry_live)
     bool dense() const { return !probe && rows.kind == Rows::All; }
     bool scan() const { return chain == Chain::Scan || chain == Chain::ScanSide; }
 };
@@ -155,6 +173,8 @@ inline StepPlan plan_step(const PlanConfig &c, int64_t it, int64_t T)
     p.chain_self = p.scan() && c.scan_self;
     p.form_z = !last;
     p.seed_z = p.form_z && p.chain != Chain::None && !p.chain_self;
+    // a frontier list or a tail list visits too few links to pay for a pass over all of them
+    p.entry_live = c.entry_live && c.G >= 8 && p.probe && p.rows.kind == Rows::All;
     return p;
 }
 
