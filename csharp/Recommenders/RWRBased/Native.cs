@@ -48,6 +48,11 @@ namespace Recommenders.RWRBased {
         // its bit in excl_edge_mask are left out, and the seed itself when exclude_self != 0 (Recommender.RecommendationTypedBatch)
         [DllImport(Lib)] public static extern int rwr_recommend_typed_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,
             int top_n, int cand_type, uint excl_edge_mask, int exclude_self, long[] ids, double[] scores, int[] counts);
+        // the same K walks evaluated on the device: Hits and the running-precision sum (Experiment.cs:121-128) of every seed's WHOLE
+        // list of type cand_type (its first top_n entries when top_n > 0, any value) against test set k; no list is written
+        [DllImport(Lib)] public static extern int rwr_recommend_typed_eval_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,
+            int top_n, int cand_type, uint excl_edge_mask, int exclude_self, long[] test_ptr, long[] test_ids, long[] n_hits,
+            double[] sum_precision, long[] list_len);
         // Hits / sum of precisions of Experiment.cs:121-128 computed on the device (the ranked list never crosses): one seed,
         // or K seeds with K test sets in CSR form (test set k = test_ids[test_ptr[k] .. test_ptr[k + 1]))
         [DllImport(Lib)] public static extern int rwr_recommend_eval(GraphHandle g, int seed, float d, int n_iter, long[] test_ids,
@@ -75,6 +80,12 @@ namespace Recommenders.RWRBased {
         [DllImport(Lib)] public static extern int rwr_recommend_restart_batch(GraphHandle g, int K, long[] sup_ptr, int[] sup_idx,
             double[] sup_val, int[] start, long[] excl_ptr, int[] excl_idx, double d, int n_iter, int top_n, long[] ids,
             double[] scores, int[] counts);
+
+        // ... ranked among the nodes of type cand_type: the targets of the raw links whose type has its bit in excl_edge_mask of
+        // every member of exclusion set k left out, and the members themselves when exclude_members != 0
+        [DllImport(Lib)] public static extern int rwr_recommend_restart_typed_batch(GraphHandle g, int K, long[] sup_ptr, int[] sup_idx,
+            double[] sup_val, int[] start, long[] excl_ptr, int[] excl_idx, double d, int n_iter, int top_n, int cand_type,
+            uint excl_edge_mask, int exclude_members, long[] ids, double[] scores, int[] counts);
 
         // the same K walks evaluated on the device: Hits and the running-precision sum (Experiment.cs:121-128) of every vector's
         // list (its first top_n entries when top_n > 0) against test set k (test_ptr / test_ids in CSR form); no list is written

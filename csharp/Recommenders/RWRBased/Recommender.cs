@@ -100,6 +100,80 @@ namespace Recommenders.RWRBased {
             return RecommendationTypedBatch(new[] { idxTargetNode }, dampingFactor, nIteration, topN, candType, exclEdgeTypes, excludeSelf)[0];
         }
 
+        // addition: Hits and the running-precision sum (Experiment.cs:121-128) of K seeds' WHOLE lists among the nodes of one node
+        // type against one test set each, evaluated on the device without writing a ranked list (rwr_recommend_typed_eval_batch).
+        // candType, exclEdgeTypes and excludeSelf as in RecommendationTypedBatch; topN > 0 evaluates the first topN entries of
+        // every list (any value), topN <= 0 the whole list
+        public void RecommendationTypedEvalBatch(int[] seeds, float dampingFactor, int nIteration, HashSet<long>[] testSets,
+                                                 NodeType candType, out long[] nHits, out double[] sumPrecision, out long[] listLen,
+                                                 IEnumerable<EdgeType> exclEdgeTypes = null, bool excludeSelf = false, int topN = 0) {
+            int K = seeds.Length;
+            if (testSets.Length != K) throw new System.ArgumentException("testSets must hold one entry per seed");
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            var testPtr = new long[K + 1];
+            for (int k = 0; k < K; k++) testPtr[k + 1] = testPtr[k] + testSets[k].Count;
+            var testIds = new long[testPtr[K]];
+            for (int k = 0; k < K; k++) testSets[k].CopyTo(testIds, (int)testPtr[k]);
+            nHits = new long[K]; sumPrecision = new double[K]; listLen = new long[K];
+            Native.Check(Native.rwr_recommend_typed_eval_batch(graph.handle, seeds, K, dampingFactor, nIteration, topN, (int)candType, mask, excludeSelf ? 1 : 0, testPtr, testIds, nHits, sumPrecision, listLen));
+        }
+
+        // ... and for one seed
+        public void RecommendationTypedEval(int idxTargetNode, float dampingFactor, int nIteration, HashSet<long> testSet,
+                                            NodeType candType, out long nHits, out double sumPrecision, out long listLen,
+                                            IEnumerable<EdgeType> exclEdgeTypes = null, bool excludeSelf = false, int topN = 0) {
+            long[] h; double[] sp; long[] ln;
+            RecommendationTypedEvalBatch(new[] { idxTargetNode }, dampingFactor, nIteration, new[] { testSet }, candType, out h, out sp, out ln,
+                                         exclEdgeTypes, excludeSelf, topN);
+            nHits = h[0]; sumPrecision = sp[0]; listLen = ln[0];
+        }
+
+        // addition: the top-N lists of K walks with caller-set restart vectors among the nodes of ONE node type
+        // (rwr_recommend_restart_typed_batch).  nodes, weights, start and exclude as in RecommendationRestartBatch; candType and
+        // exclEdgeTypes as in RecommendationTypedBatch, applied to every member of exclusion set k; excludeMembers: the members
+        // themselves are no candidates.  "Whom should this group follow" is (NodeType.USER, {FRIENDSHIP, FOLLOW}, true)
+        public List<KeyValuePair<long, double>>[] RecommendationRestartTypedBatch(int[][] nodes, double[][] weights, int[] start,
+                                                                                  double dampingFactor, int nIteration, int topN,
+                                                                                  NodeType candType,
+                                                                                  IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                                  bool excludeMembers = false, int[][] exclude = null) {
+            if (topN < 1) throw new System.ArgumentOutOfRangeException("topN", "RecommendationRestartTypedBatch needs topN >= 1");
+            int K = nodes.Length;
+            if (weights.Length != K || (start != null && start.Length != K) || (exclude != null && exclude.Length != K))
+                throw new System.ArgumentException("nodes, weights, start and exclude must hold one entry per vector");
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            var ptr = new long[K + 1];
+            for (int k = 0; k < K; k++) {
+                if (nodes[k].Length != weights[k].Length)
+                    throw new System.ArgumentException("a restart vector's nodes and weights differ in length");
+                ptr[k + 1] = ptr[k] + nodes[k].Length;
+            }
+            var idx = new int[ptr[K]];
+            var val = new double[ptr[K]];
+            for (int k = 0; k < K; k++) {
+                System.Array.Copy(nodes[k], 0, idx, ptr[k], nodes[k].Length);
+                System.Array.Copy(weights[k], 0, val, ptr[k], weights[k].Length);
+            }
+            long[] exclPtr = null;
+            int[] exclIdx = null;
+            if (exclude != null) {
+                exclPtr = new long[K + 1];
+                for (int k = 0; k < K; k++) exclPtr[k + 1] = exclPtr[k] + exclude[k].Length;
+                exclIdx = new int[exclPtr[K]];
+                for (int k = 0; k < K; k++) System.Array.Copy(exclude[k], 0, exclIdx, exclPtr[k], exclude[k].Length);
+            }
+            var ids = new long[(long)K * topN]; var scores = new double[(long)K * topN]; var counts = new int[K];
+            Native.Check(Native.rwr_recommend_restart_typed_batch(graph.handle, K, ptr, idx, val, start, exclPtr, exclIdx, dampingFactor, nIteration, topN, (int)candType, mask, excludeMembers ? 1 : 0, ids, scores, counts));
+            var all = new List<KeyValuePair<long, double>>[K];
+            for (int k = 0; k < K; k++) {
+                all[k] = new List<KeyValuePair<long, double>>(counts[k]);
+                for (int q = 0; q < counts[k]; q++) all[k].Add(new KeyValuePair<long, double>(ids[(long)k * topN + q], scores[(long)k * topN + q]));
+            }
+            return all;
+        }
+
         // addition: the top-N lists of K walks with caller-set restart vectors (Model.restart), ranked on the device
         // (rwr_recommend_restart_batch).  Vector k has restart[nodes[k][j]] = weights[k][j] >= 0 and zero elsewhere; start as in
         // Model.RunRestartBatch.  exclude[k]: the nodes whose LIKEd items are not candidates of vector k (Recommender.cs:20-24

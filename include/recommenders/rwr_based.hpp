@@ -411,6 +411,74 @@ public:
         return out;
     }
 
+    // addition: Hits and the running-precision sum (Experiment.cs:121-128) of K seeds' WHOLE lists among the nodes of one node
+    // type against one test set each, evaluated on the device without writing a ranked list (rwr_recommend_typed_eval_batch).
+    // candType, exclEdgeTypes and excludeSelf as in recommendTypedBatch; topN > 0 evaluates the first topN entries of every
+    // list (any value), topN <= 0 the whole list
+    struct TypedEval {
+        std::vector<int64_t> nHits;
+        std::vector<double> sumPrecision;
+        std::vector<int64_t> listLen;
+    };
+    TypedEval recommendTypedEvalBatch(const std::vector<int> &seeds, float dampingFactor, int nIteration,
+                                      const std::vector<std::vector<int64_t>> &testSets, NodeType candType,
+                                      const std::vector<EdgeType> &exclEdgeTypes = {}, bool excludeSelf = false, int topN = 0)
+    {
+        const int32_t K = (int32_t)seeds.size();
+        if (testSets.size() != seeds.size()) throw std::invalid_argument("recommendTypedEvalBatch: testSets must hold one entry per seed");
+        uint32_t mask = 0;
+        for (EdgeType t : exclEdgeTypes) mask |= 1u << (unsigned)t;
+        std::vector<int32_t> sd(seeds.begin(), seeds.end());
+        std::vector<int64_t> tptr((size_t)K + 1, 0), tids;
+        for (int32_t k = 0; k < K; ++k) {
+            tids.insert(tids.end(), testSets[k].begin(), testSets[k].end());
+            tptr[(size_t)k + 1] = (int64_t)tids.size();
+        }
+        TypedEval out{std::vector<int64_t>((size_t)K), std::vector<double>((size_t)K), std::vector<int64_t>((size_t)K)};
+        check(rwr_recommend_typed_eval_batch(graph_.handle(), sd.data(), K, dampingFactor, nIteration, topN, (int32_t)candType, mask, excludeSelf ? 1 : 0, tptr.data(), tids.data(), out.nHits.data(), out.sumPrecision.data(), out.listLen.data()));
+        return out;
+    }
+
+    // addition: the top-N lists of K walks with caller-set restart vectors among the nodes of ONE node type
+    // (rwr_recommend_restart_typed_batch).  nodes / weights / start / exclude as in recommendRestartBatch; candType and
+    // exclEdgeTypes as in recommendTypedBatch, applied to every member of exclusion set k; excludeMembers: the members
+    // themselves are no candidates.  "Whom should this group follow" is (NodeType::USER, {FRIENDSHIP, FOLLOW}, true)
+    std::vector<std::vector<std::pair<int64_t, double>>> recommendRestartTypedBatch(
+        const std::vector<std::vector<int>> &nodes, const std::vector<std::vector<double>> &weights, const std::vector<int> &start,
+        double dampingFactor, int nIteration, int topN, NodeType candType, const std::vector<EdgeType> &exclEdgeTypes = {},
+        bool excludeMembers = false, const std::vector<std::vector<int>> *exclude = nullptr)
+    {
+        const int32_t K = (int32_t)nodes.size();
+        if (topN < 1) throw std::invalid_argument("recommendRestartTypedBatch: topN must be >= 1");
+        if (weights.size() != nodes.size() || (!start.empty() && start.size() != nodes.size()) ||
+            (exclude && exclude->size() != nodes.size()))
+            throw std::invalid_argument("recommendRestartTypedBatch: nodes, weights, start and exclude must hold one entry per vector");
+        uint32_t mask = 0;
+        for (EdgeType t : exclEdgeTypes) mask |= 1u << (unsigned)t;
+        std::vector<int64_t> ptr((size_t)K + 1, 0), eptr((size_t)K + 1, 0);
+        std::vector<int32_t> idx, eidx;
+        std::vector<double> val;
+        for (int32_t k = 0; k < K; ++k) {
+            if (nodes[k].size() != weights[k].size())
+                throw std::invalid_argument("recommendRestartTypedBatch: a restart vector's nodes and weights differ in length");
+            idx.insert(idx.end(), nodes[k].begin(), nodes[k].end());
+            val.insert(val.end(), weights[k].begin(), weights[k].end());
+            ptr[(size_t)k + 1] = (int64_t)idx.size();
+            if (exclude) eidx.insert(eidx.end(), (*exclude)[k].begin(), (*exclude)[k].end());
+            eptr[(size_t)k + 1] = (int64_t)eidx.size();
+        }
+        std::vector<int32_t> st(start.begin(), start.end());
+        std::vector<int64_t> ids((size_t)K * (size_t)topN);
+        std::vector<double> scores((size_t)K * (size_t)topN);
+        std::vector<int32_t> counts((size_t)K);
+        check(rwr_recommend_restart_typed_batch(graph_.handle(), K, ptr.data(), idx.data(), val.data(), st.empty() ? nullptr : st.data(), exclude ? eptr.data() : nullptr, eidx.data(), dampingFactor, nIteration, topN, (int32_t)candType, mask, excludeMembers ? 1 : 0, ids.data(), scores.data(), counts.data()));
+        std::vector<std::vector<std::pair<int64_t, double>>> out((size_t)K);
+        for (int32_t k = 0; k < K; ++k)
+            for (int32_t q = 0; q < counts[k]; ++q)
+                out[k].emplace_back(ids[(size_t)k * (size_t)topN + q], scores[(size_t)k * (size_t)topN + q]);
+        return out;
+    }
+
     // addition: the top-N lists of K walks with caller-set restart vectors, ranked on the device (rwr_recommend_restart_batch).
     // nodes / weights (>= 0) / start as in Model::runRestartBatch.  exclude[k]: the nodes whose LIKEd items are not candidates
     // of vector k (Recommender.cs:20-24 for each of them); exclude == nullptr: the nodes of vector k's own support

@@ -333,7 +333,7 @@ int32_t rwr_recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float
  *   - The domain is that of the Recommendation entries: a graph with a negative weight or d outside [0, 1] gives
  *     RWR_E_UNSUPPORTED (the ranking marks exclusions with -1 and relies on scores >= 0).
  *   - top_n in [1, 1024]: a larger top_n gives RWR_E_UNSUPPORTED with the limit in the message (whole lists of a node type
- *     are not implemented).
+ *     are evaluated, not returned: rwr_recommend_typed_eval_batch).
  *   - Argument errors, all found before any device work: a NULL g is refused first; K == 0 is a no-op (RWR_OK); K < 0, NULL
  *     seeds / ids / scores / counts, top_n < 1, cand_type outside [0, 255] or a mask bit >= 8 give RWR_E_INVALID; a seed
  *     outside [0, n) gives RWR_E_RANGE with its batch position in the message.  A refused call writes nothing.
@@ -343,6 +343,32 @@ int32_t rwr_recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float
 int32_t rwr_recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
                                   int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,
                                   int64_t *ids, double *scores, int32_t *counts);
+/* The same K walks evaluated on the device: Hits and the running-precision sum of every seed's list of one node type against
+ * a test set (Experiment.cs:121-128), without the list ever being written -- "who to follow" scored against held-out FOLLOW
+ * links.  seeds, d, n_iter, cand_type, excl_edge_mask, exclude_self and the domain exactly as in rwr_recommend_typed_batch.
+ * Test set k is test_ids[test_ptr[k] .. test_ptr[k+1]) with HashSet<long> semantics, exactly as in
+ * rwr_recommend_restart_eval_batch: duplicates change nothing, ids that no node carries are legal, a set may be empty.
+ * Result k: let L_k be the WHOLE list rwr_recommend_typed_batch defines for seed k -- the same candidates, mask and self
+ * exclusion, the same order, not cut at 1024 -- cut to its first top_n entries if top_n > 0 (any positive value, 1025
+ * included) and kept whole if top_n <= 0.  n_hits[k] and sum_precision[k] are what Experiment.cs:121-128 computes over that
+ * list -- hits numbered in rank order, the addends (double)nHits / (i + 1) summed in rank order -- and list_len[k] (may be
+ * NULL) is the list's length.  The integers are equal to that composition and sum_precision bitwise equal to it, for every
+ * seed: duplicate seeds, dangling seeds and seeds of another type than cand_type included.  Ids need not be unique among
+ * nodes (rwr_graph_append_nodes): every candidate that carries a test id is a hit.
+ *   - cand_type = RWR_NODE_ITEM, excl_edge_mask = 1u << RWR_EDGE_LIKE, exclude_self = 0, top_n <= 0 is
+ *     rwr_recommend_eval_batch: the same integers, the same sums bit for bit.
+ *   - A cand_type that no node carries gives n_hits 0, sum_precision +0.0, list_len 0 and RWR_OK.
+ *   - Argument errors, all found before any device work and in this order: a NULL g is refused first; K == 0 is a no-op
+ *     (RWR_OK); then everything rwr_recommend_typed_batch reports for K, the seeds, cand_type and the mask, with the same
+ *     status and batch position (top_n has no bound here); then everything rwr_recommend_restart_eval_batch reports for
+ *     test_ptr / test_ids / n_hits / sum_precision, with the same status and batch position; then the domain
+ *     (RWR_E_UNSUPPORTED).  A refused call writes nothing.
+ *   - The candidate list is the handle's cached one (rwr_recommend_typed_batch); opts.tile_seeds, tile_group and
+ *     workspace_bytes keep their meaning. */
+int32_t rwr_recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                       int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,
+                                       const int64_t *test_ptr, const int64_t *test_ids,
+                                       int64_t *n_hits, double *sum_precision, int64_t *list_len /* may be NULL */);
 
 /* ---- Model ---------------------------------------------------------------------------
  * Backs the public class Model: ctor (Model.cs:33-50 personalised, seed >= 0;
@@ -435,6 +461,31 @@ int32_t rwr_recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_
                                     const double *sup_val, const int32_t *start, const int64_t *excl_ptr,
                                     const int32_t *excl_idx, double d, int32_t n_iter, int32_t top_n,
                                     int64_t *ids, double *scores, int32_t *counts);
+/* The same K walks ranked among the nodes of ANY node type: "whom should this group follow".  Vectors, starts, n_iter, the
+ * exclusion sets (excl_ptr == NULL: set k is the indices of vector k's support) and the domain exactly as in
+ * rwr_recommend_restart_batch; cand_type and excl_edge_mask as in rwr_recommend_typed_batch.
+ * Result k: the rank row that rwr_model_run_restart(g, dense(v_k), rank0_k, d, RWR_RUN_ITERATIONS, n_iter, ...) returns; of it
+ *   - the candidates are the nodes with node_type == cand_type;
+ *   - a candidate is dropped when it is the target of a RAW out-link of a member of set k whose type t has bit (1u << t) set
+ *     in excl_edge_mask;
+ *   - when exclude_members != 0 every member of set k is dropped as well (a group is not recommended its own members);
+ *     start nodes are dropped only if they are members;
+ *   - the rest is ordered by score descending, then id descending; the first top_n of them go into row k of ids / scores
+ *     (K x top_n, row-major), counts[k] = entries written, the rest of the row id 0 / score 0.
+ * Ids are identical to that composition and scores bitwise equal to it, for every vector (K == 1 and a vector with more than
+ * RWR_RESTART_EXACT_MAX non-zero entries run vector by vector through that very call).  A node may appear twice in a set; an
+ * empty set is legal; a member without raw links is still dropped by exclude_members.
+ *   - cand_type = RWR_NODE_ITEM, excl_edge_mask = 1u << RWR_EDGE_LIKE, exclude_members = 0 is rwr_recommend_restart_batch: the
+ *     same ids, scores and counts.
+ *   - top_n in [1, 1024]: a larger top_n gives RWR_E_UNSUPPORTED with the limit in the message, as the typed seed entry.
+ *   - Argument errors, all found before any device work: those of rwr_recommend_restart_batch, with the same status and batch
+ *     position; cand_type outside [0, 255] or a mask bit >= 8 give RWR_E_INVALID.  A NULL g is refused first; K == 0 is a
+ *     no-op (RWR_OK).  A refused call writes nothing. */
+int32_t rwr_recommend_restart_typed_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                          const double *sup_val, const int32_t *start, const int64_t *excl_ptr,
+                                          const int32_t *excl_idx, double d, int32_t n_iter, int32_t top_n,
+                                          int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_members,
+                                          int64_t *ids, double *scores, int32_t *counts);
 /* The same K walks evaluated on the device: Hits and the running-precision sum of every vector's list against a test set
  * (Experiment.cs:121-128), without the list ever being written.  Vectors, starts, exclusion sets, d, n_iter and the domain
  * exactly as in rwr_recommend_restart_batch.  Test set k is test_ids[test_ptr[k] .. test_ptr[k+1]) with HashSet<long>

@@ -9,6 +9,7 @@
 #include "eval_plan.h"
 #include "exclude_plan.h"
 #include "handle.h"
+#include "member_plan.h"
 #include "rank.h"
 
 namespace rwr {
@@ -150,6 +151,33 @@ static int32_t check_ranked_vectors(const char *who, int32_t n, int32_t K, const
                 set_error("%s: exclusion index %d (batch position %d) is outside [0, %d)", who, c.bad_index, c.bad_k, n);
                 return RWR_E_RANGE;
         }
+    }
+    return RWR_OK;
+}
+
+// eval_check's verdict on the test sets and result arrays of an evaluating entry, as status and message
+static int32_t eval_verdict_status(const char *who, const EvalCheck &c, const int64_t *test_ptr)
+{
+    switch (c.verdict) {
+        case EVAL_OK: break;
+        case EVAL_NULL_PTR:
+            set_error("%s: NULL test_ptr", who);
+            return RWR_E_INVALID;
+        case EVAL_NULL_OUT:
+            set_error("%s: NULL n_hits or sum_precision", who);
+            return RWR_E_INVALID;
+        case EVAL_BAD_PTR0:
+            set_error("%s: test_ptr[0] = %lld, not 0", who, (long long)test_ptr[0]);
+            return RWR_E_INVALID;
+        case EVAL_PTR_DECREASES:
+            set_error("%s: test_ptr decreases at batch position %d", who, c.bad_k);
+            return RWR_E_INVALID;
+        case EVAL_NULL_IDS:
+            set_error("%s: NULL test_ids", who);
+            return RWR_E_INVALID;
+        case EVAL_SET_TOO_LARGE:
+            set_error("%s: test set %d holds more than INT32_MAX ids", who, c.bad_k);
+            return RWR_E_UNSUPPORTED;
     }
     return RWR_OK;
 }
@@ -347,8 +375,8 @@ int32_t rwr_recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K,
             set_error("%s: seed %d (batch position %d) is outside [0, %d)", who, c.bad_seed, c.bad_k, g->n);
             return RWR_E_RANGE;
         case TYPED_TOP_N_LIMIT:
-            set_error("%s: top_n %d is beyond the select path's limit of %d entries (whole lists of a node type are not "
-                      "implemented)", who, top_n, rank_select_max_k());
+            set_error("%s: top_n %d is beyond the select path's limit of %d entries (rwr_recommend_typed_eval_batch evaluates "
+                      "whole lists of a node type)", who, top_n, rank_select_max_k());
             return RWR_E_UNSUPPORTED;
     }
     // the domain of the Recommendation entries: the exclusion marker (-1) and the ranking keys assume scores >= 0
@@ -365,6 +393,58 @@ int32_t rwr_recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K,
     // Recommender.cs:14,16 -> Model.cs:33: the float is widened to double
     return bound(who, g, [&] {
         return recommend_typed_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, ids, scores, counts);
+    });
+}
+
+int32_t rwr_recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                       int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
+                                       const int64_t *test_ids, int64_t *n_hits, double *sum_precision, int64_t *list_len)
+{
+    static const char *const who = "rwr_recommend_typed_eval_batch";
+    g_err[0] = 0;
+    const TypedEvalCheck c = typed_eval_check(g != nullptr, g ? g->n : 0, seeds, K, cand_type, excl_edge_mask, test_ptr, test_ids,
+                                              n_hits, sum_precision);
+    switch (c.typed.verdict) {
+        case TYPED_OK: break;
+        case TYPED_NOOP: return RWR_OK;
+        case TYPED_NULL_GRAPH:
+            set_error("%s: NULL graph", who);
+            return RWR_E_INVALID;
+        case TYPED_NEGATIVE_K:
+            set_error("%s: negative K", who);
+            return RWR_E_INVALID;
+        case TYPED_NULL_ARG:
+            set_error("%s: NULL seeds", who);
+            return RWR_E_INVALID;
+        case TYPED_BAD_CAND_TYPE:
+            set_error("%s: cand_type %d is outside [0, 255]", who, cand_type);
+            return RWR_E_INVALID;
+        case TYPED_BAD_MASK:
+            set_error("%s: excl_edge_mask 0x%x has a bit beyond the %u edge types", who, excl_edge_mask, TYPED_EDGE_TYPES);
+            return RWR_E_INVALID;
+        case TYPED_SEED_RANGE:
+            set_error("%s: seed %d (batch position %d) is outside [0, %d)", who, c.typed.bad_seed, c.typed.bad_k, g->n);
+            return RWR_E_RANGE;
+        case TYPED_BAD_TOP_N:
+        case TYPED_TOP_N_LIMIT:                                  // (top_n has no bound here: typed_eval_check gives neither)
+            set_error("%s: unexpected verdict %d", who, (int)c.typed.verdict);
+            return RWR_E_INVALID;
+    }
+    RWR_TRY(eval_verdict_status(who, c.eval, test_ptr));
+    // the domain of the Recommendation entries: the exclusion marker (-1) and the ranking keys assume scores >= 0
+    if (!g->nonneg) {
+        set_error("%s: Recommendation needs non-negative finite link weights and positive row sums; rwr_model_run_batch "
+                  "accepts such graphs", who);
+        return RWR_E_UNSUPPORTED;
+    }
+    if (!((double)d >= 0.0 && (double)d <= 1.0)) {
+        set_error("%s: Recommendation needs a damping factor in [0, 1] (got %g); rwr_model_run_batch accepts any value", who, (double)d);
+        return RWR_E_UNSUPPORTED;
+    }
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    return bound(who, g, [&] {
+        return recommend_typed_eval_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, test_ptr,
+                                          test_ids, n_hits, sum_precision, list_len);
     });
 }
 
@@ -576,6 +656,44 @@ int32_t rwr_recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_
     });
 }
 
+int32_t rwr_recommend_restart_typed_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                          const double *sup_val, const int32_t *start, const int64_t *excl_ptr,
+                                          const int32_t *excl_idx, double d, int32_t n_iter, int32_t top_n, int32_t cand_type,
+                                          uint32_t excl_edge_mask, int32_t exclude_members, int64_t *ids, double *scores,
+                                          int32_t *counts)
+{
+    static const char *const who = "rwr_recommend_restart_typed_batch";
+    g_err[0] = 0;
+    if (!g) { set_error("%s: NULL graph", who); return RWR_E_INVALID; }
+    if (K < 0) { set_error("%s: negative K", who); return RWR_E_INVALID; }
+    if (K == 0) return RWR_OK;
+    if (!sup_ptr || !ids || !scores || !counts) { set_error("%s: NULL sup_ptr, ids, scores or counts", who); return RWR_E_INVALID; }
+    switch (restart_typed_check(top_n, rank_select_max_k(), cand_type, excl_edge_mask)) {
+        case TYPED_BAD_TOP_N:
+            set_error("%s: top_n must be >= 1", who);
+            return RWR_E_INVALID;
+        case TYPED_BAD_CAND_TYPE:
+            set_error("%s: cand_type %d is outside [0, 255]", who, cand_type);
+            return RWR_E_INVALID;
+        case TYPED_BAD_MASK:
+            set_error("%s: excl_edge_mask 0x%x has a bit beyond the %u edge types", who, excl_edge_mask, TYPED_EDGE_TYPES);
+            return RWR_E_INVALID;
+        case TYPED_TOP_N_LIMIT:
+            set_error("%s: top_n %d is beyond the select path's limit of %d entries", who, top_n, rank_select_max_k());
+            return RWR_E_UNSUPPORTED;
+        default: break;
+    }
+    RWR_TRY(check_ranked_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start, excl_ptr, excl_idx));
+    RWR_TRY(check_ranked_domain(who, g, d));
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    // excl_ptr == NULL: set k is the indices of vector k's support, whatever their values
+    return bound(who, g, [&] {
+        return recommend_restart_typed_batch(g, K, sup_ptr, sup_idx, sup_val, start, excl_ptr ? excl_ptr : sup_ptr,
+                                             excl_ptr ? excl_idx : sup_idx, d, n_iter, top_n, cand_type, excl_edge_mask,
+                                             exclude_members, ids, scores, counts);
+    });
+}
+
 int32_t rwr_recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
                                          const double *sup_val, const int32_t *start, const int64_t *excl_ptr,
                                          const int32_t *excl_idx, double d, int32_t n_iter, int32_t top_n,
@@ -589,28 +707,7 @@ int32_t rwr_recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t 
     if (K == 0) return RWR_OK;
     if (!sup_ptr) { set_error("%s: NULL sup_ptr", who); return RWR_E_INVALID; }
     RWR_TRY(check_ranked_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start, excl_ptr, excl_idx));
-    const EvalCheck c = eval_check(K, test_ptr, test_ids, n_hits, sum_precision);
-    switch (c.verdict) {
-        case EVAL_OK: break;
-        case EVAL_NULL_PTR:
-            set_error("%s: NULL test_ptr", who);
-            return RWR_E_INVALID;
-        case EVAL_NULL_OUT:
-            set_error("%s: NULL n_hits or sum_precision", who);
-            return RWR_E_INVALID;
-        case EVAL_BAD_PTR0:
-            set_error("%s: test_ptr[0] = %lld, not 0", who, (long long)test_ptr[0]);
-            return RWR_E_INVALID;
-        case EVAL_PTR_DECREASES:
-            set_error("%s: test_ptr decreases at batch position %d", who, c.bad_k);
-            return RWR_E_INVALID;
-        case EVAL_NULL_IDS:
-            set_error("%s: NULL test_ids", who);
-            return RWR_E_INVALID;
-        case EVAL_SET_TOO_LARGE:
-            set_error("%s: test set %d holds more than INT32_MAX ids", who, c.bad_k);
-            return RWR_E_UNSUPPORTED;
-    }
+    RWR_TRY(eval_verdict_status(who, eval_check(K, test_ptr, test_ids, n_hits, sum_precision), test_ptr));
     RWR_TRY(check_ranked_domain(who, g, d));
     if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
     return bound(who, g, [&] {

@@ -306,6 +306,26 @@ void launch_restart_init_cols(rwr_graph *g, int G, int tg, const int32_t *st, do
 int32_t recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
                               int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t *ids, double *scores,
                               int32_t *counts);
+// ... or evaluated there (rwr_recommend_typed_eval_batch): Hits / average precision of every seed's WHOLE list
+// of that type, cut to top_n when top_n > 0 (any value), against test set k -- eval_count.hip over the candidate list
+int32_t recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
+                                   int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
+                                   const int64_t *test_ids, int64_t *n_hits, double *sum_precision, int64_t *list_len);
+// ... and the pieces restart_batch.hip's typed end shares with it.  The device list of the rows with node_type == type,
+// ascending, cached per handle (cand_plan.h); call it on an idle stream and before the workspace is sized
+int32_t cand_rows_get(rwr_graph *g, int32_t type, const int32_t **rows, int32_t *nrows);
+// k_exclude_typed over exclude_plan.h's segments (slots relative to X's first tile): the targets of the raw links whose type
+// has its bit in mask; k_exclude_members over member_plan.h's pairs: the members' own rows
+void launch_exclude_typed(rwr_graph *g, int G, int32_t nseg, const int32_t *seg_slot, const int64_t *seg_p0, const int64_t *seg_p1,
+                          uint32_t mask, double *X, hipStream_t s);
+void launch_exclude_members(rwr_graph *g, int G, int32_t npairs, const int32_t *pair_slot, const int32_t *pair_row, double *X,
+                            hipStream_t s);
+// ... the restart-vector walks of rwr_recommend_restart_batch ranked among the nodes of one type
+// (rwr_recommend_restart_typed_batch): top_n <= the select path's limit
+int32_t recommend_restart_typed_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                      const double *sup_val, const int32_t *start, const int64_t *set_ptr, const int32_t *set_idx,
+                                      double d, int32_t n_iter, int32_t top_n, int32_t cand_type, uint32_t excl_edge_mask,
+                                      int32_t exclude_members, int64_t *ids, double *scores, int32_t *counts);
 // model.hip pieces restart.hip runs as well (the loops around them: run_walk and GroupColumns, iterate.h).  A run's end condition (Model.run(int) / run(double) / run(), Model.cs:52-66):
 // T steps at most; !by_count: until checkConvergence's distance is < threshold, a failure after max_iters = RWR_MAX_ITERS steps
 struct RunEnd {

@@ -13,7 +13,7 @@ struct EvalOut {
     int64_t list_len;
 };
 
-// The evaluating end of a restart batch: the caller's test sets and result arrays, the host plan, its device copy and the
+// The evaluating end of a restart batch or of a typed seed batch: the caller's test sets and result arrays, the host plan, its device copy and the
 // per-group scratch.  Declared by the entry point before its StreamsIdle, so the buffers outlive the kernels that read them.
 struct EvalEnd {
     const int64_t *test_ptr = nullptr, *test_ids = nullptr;
@@ -41,8 +41,10 @@ struct EvalEnd {
 int32_t eval_prepare(rwr_graph *g, EvalEnd &ev, int32_t K, const std::vector<int32_t> &slot_k, size_t slots_per_group,
                      const char *who, hipStream_t s);
 // A tile group (tg tiles of G slots from slot q0 on) holds its final ranks in X, the excluded elements at -1: hits, sort,
-// count, finish.  g->d_slot_k holds the slots' batch positions.  Synchronises s once (the slots' hit counts).
-int32_t eval_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const double *X, hipStream_t s);
+// count, finish over the candidate rows rows[0 .. nrows) (a device list: the ITEM rows, or those of another node type).
+// g->d_slot_k holds the slots' batch positions.  Synchronises s once (the slots' hit counts).
+int32_t eval_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const double *X, const int32_t *rows, int32_t nrows,
+                   hipStream_t s);
 // after the last group: the K records into the caller's arrays (one copy, one synchronisation)
 int32_t eval_copy_back(rwr_graph *g, EvalEnd &ev, int32_t K, const char *who, hipStream_t s);
 

@@ -3,15 +3,16 @@
 // Experiment.cs:121-128 walks a ranked list and adds (double)nHits / (i + 1) at every hit.  The position i of a hit is the
 // number of candidates that rank before it, and the candidates between two hits need no order among themselves: so the group
 // is evaluated by
-//   1. hits     every candidate (ITEM row whose element of X is not the exclusion marker) looks its node id up in its slot's
+//   1. hits     every candidate (row of the candidate list whose element of X is not the exclusion marker) looks its node id up in its slot's
 //               sorted test set; a hit appends its 128-bit (score, id) key to the slot's list, sized exactly by a counting launch;
 //   2. sort     the slots' hit keys descending: sel_sort in one workgroup up to SEL_SLOTS keys, sort.hip's radix sort above;
 //   3. count    every candidate finds by binary search how many hit keys are >= its own and adds one to that interval's
 //               counter (LDS-private per workgroup while the tile's lists fit, global otherwise);
 //   4. finish   one workgroup per slot: a prefix sum over the intervals gives every hit its position; one thread adds the
 //               addends in rank order (eval_ranked_body's division and summation order).
-// Integer counting only: the result does not depend on scheduling.  Stages 1 and 3 read the group's ITEM rows of X once each;
-// nothing of size K x n_items is written.
+// Integer counting only: the result does not depend on scheduling.  Stages 1 and 3 read the group's candidate rows of X once
+// each; nothing of size K x candidates is written.  The candidate list is the caller's: the ITEM rows for the restart batch,
+// the cached rows of a node type for rwr_recommend_typed_eval_batch.
 #include "eval_count.h"
 #include "rank_keys.h"
 
@@ -27,7 +28,7 @@ __device__ __forceinline__ bool key_ge(const SelCand &a, const SelCand &b)
 // Stage 1.  Thread = (lane k of the tile, row lane rl): the G slots of a row read consecutive elements of X.  FILL = false
 // counts the hits of every slot into cnt; FILL = true appends their keys at hits[hit_off[slot] + cursor[slot]++].
 template <int G, bool FILL>
-__global__ __launch_bounds__(256) void k_eval_hits(int32_t n, int32_t n_items, const int32_t *__restrict__ item_rows,
+__global__ __launch_bounds__(256) void k_eval_hits(int32_t n, int32_t nrows, const int32_t *__restrict__ rows,
                                                    const int64_t *__restrict__ node_id, const double *__restrict__ X,
                                                    const int32_t *__restrict__ slot_k, const int64_t *__restrict__ ids,
                                                    const int64_t *__restrict__ slot_off, int32_t *__restrict__ cnt,
@@ -45,10 +46,10 @@ __global__ __launch_bounds__(256) void k_eval_hits(int32_t n, int32_t n_items, c
     const int64_t *ts = ids + t0;
     const double *x = X + (size_t)tile * (size_t)n * G;
     const int32_t q0 = blockIdx.x * SEL_ROWS_PER_BLOCK;
-    const int32_t q1 = (q0 + SEL_ROWS_PER_BLOCK < n_items) ? q0 + SEL_ROWS_PER_BLOCK : n_items;
+    const int32_t q1 = (q0 + SEL_ROWS_PER_BLOCK < nrows) ? q0 + SEL_ROWS_PER_BLOCK : nrows;
     int32_t mine = 0;
     for (int32_t q = q0 + rl; q < q1; q += RL) {
-        const int32_t row = item_rows[q];
+        const int32_t row = rows[q];
         const double s = x[(size_t)row * G + k];
         if (!(s >= 0.0)) continue;                                   // excluded (Recommender.cs:29)
         const int64_t id = node_id[row];
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(256) void k_eval_radix_gather(const SelCand *__rest
 // list): the candidates that rank strictly before hit i are those of the intervals 0 .. f, f being the first hit with hit i's
 // key.  A thread keeps the run of its last interval in a register: most candidates of a slot fall below its last hit.
 template <int G>
-__global__ __launch_bounds__(256) void k_eval_count(int32_t n, int32_t n_items, const int32_t *__restrict__ item_rows,
+__global__ __launch_bounds__(256) void k_eval_count(int32_t n, int32_t nrows, const int32_t *__restrict__ rows,
                                                     const int64_t *__restrict__ node_id, const double *__restrict__ X,
                                                     const int32_t *__restrict__ slot_k, const int64_t *__restrict__ hit_off,
                                                     const SelCand *__restrict__ sorted, const uint8_t *__restrict__ tile_lds,
@@ -137,11 +138,11 @@ __global__ __launch_bounds__(256) void k_eval_count(int32_t n, int32_t n_items, 
         uint32_t *cn = (in_lds ? lds_cnt : gcnt) + my0 + k;          // my_h + 1 counters
         const double *x = X + (size_t)tile * (size_t)n * G;
         const int32_t q0 = blockIdx.x * SEL_ROWS_PER_BLOCK;
-        const int32_t q1 = (q0 + SEL_ROWS_PER_BLOCK < n_items) ? q0 + SEL_ROWS_PER_BLOCK : n_items;
+        const int32_t q1 = (q0 + SEL_ROWS_PER_BLOCK < nrows) ? q0 + SEL_ROWS_PER_BLOCK : nrows;
         int32_t run_j = 0;
         uint32_t run_n = 0;
         for (int32_t q = q0 + rl; q < q1; q += RL) {
-            const int32_t row = item_rows[q];
+            const int32_t row = rows[q];
             const double s = x[(size_t)row * G + k];
             if (!(s >= 0.0)) continue;
             int32_t lo = 0, hi = my_h;
@@ -270,9 +271,10 @@ static int32_t sort_long(rwr_graph *g, const SelCand *hits, int32_t cnt, SelCand
     return RWR_OK;
 }
 
-int32_t eval_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const double *X, hipStream_t s)
+int32_t eval_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const double *X, const int32_t *rows, int32_t nrows,
+                   hipStream_t s)
 {
-    const int32_t m = g->n_items;
+    const int32_t m = nrows;
     if (m == 0) return RWR_OK;                                      // no candidate anywhere: the zeroed records stand
     const size_t S = (size_t)tg * G;
     const int32_t *slot_k = g->d_slot_k.p + q0;
@@ -280,7 +282,7 @@ int32_t eval_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const do
     const dim3 grid(cdiv((size_t)m, SEL_ROWS_PER_BLOCK), (unsigned)tg);
     // 1. the slots' hit counts, then the exact layout of the group's lists and counters
     RWR_HIP(hipMemsetAsync(ev.d_cnt.p, 0, S * sizeof(int32_t), s));
-    RWR_DISPATCH_G(G, hipLaunchKernelGGL((k_eval_hits<GG, false>), grid, dim3(256), 0, s, g->n, m, g->item_rows.p, g->node_id.p, X,
+    RWR_DISPATCH_G(G, hipLaunchKernelGGL((k_eval_hits<GG, false>), grid, dim3(256), 0, s, g->n, m, rows, g->node_id.p, X,
                                          slot_k, ev.d_ids.p, slot_off, ev.d_cnt.p, (const int64_t *)nullptr,
                                          (int32_t *)nullptr, (SelCand *)nullptr, (int32_t *)nullptr));
     RWR_HIP(hipGetLastError());
@@ -299,7 +301,7 @@ int32_t eval_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const do
     RWR_HIP(hipMemcpyAsync(ev.d_tile_lds.p, L.tile_lds.data(), (size_t)tg, hipMemcpyHostToDevice, s));
     if (L.n_hits > 0) {
         RWR_HIP(hipMemsetAsync(ev.d_cursor.p, 0, S * sizeof(int32_t), s));
-        RWR_DISPATCH_G(G, hipLaunchKernelGGL((k_eval_hits<GG, true>), grid, dim3(256), 0, s, g->n, m, g->item_rows.p, g->node_id.p,
+        RWR_DISPATCH_G(G, hipLaunchKernelGGL((k_eval_hits<GG, true>), grid, dim3(256), 0, s, g->n, m, rows, g->node_id.p,
                                              X, slot_k, ev.d_ids.p, slot_off, (int32_t *)nullptr, ev.d_hit_off.p,
                                              ev.d_cursor.p, hits, ev.d_flag.p));
         // 2. sorted descending
@@ -328,7 +330,7 @@ int32_t eval_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const do
         }
     RWR_DISPATCH_G(G, {
         (void)hipFuncSetAttribute((const void *)k_eval_count<GG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EVAL_LDS_BYTES);
-        hipLaunchKernelGGL(k_eval_count<GG>, grid, dim3(256), lds, s, g->n, m, g->item_rows.p, g->node_id.p, X, slot_k,
+        hipLaunchKernelGGL(k_eval_count<GG>, grid, dim3(256), lds, s, g->n, m, rows, g->node_id.p, X, slot_k,
                            ev.d_hit_off.p, sorted, ev.d_tile_lds.p, ev.d_counters.p);
     });
     // 4. positions, addends in rank order, the records at the vectors' batch positions

@@ -23,9 +23,14 @@
 #include <algorithm>
 #include <cstring>
 
+//
+// rwr_recommend_restart_typed_batch is the ranked end with its ITEM / LIKE constants as arguments: the
+// exclusion is typed.hip's k_exclude_typed over the same segments with an edge-type mask, the members' own rows are marked on
+// request (k_exclude_members over member_plan.h's pairs), and the select ranks the cached rows of the candidate type.
 #include "eval_count.h"
 #include "exclude_plan.h"
 #include "iterate.h"
+#include "member_plan.h"
 
 namespace rwr {
 
@@ -45,6 +50,15 @@ struct Ranked {
     DevBuf<int64_t> d_seg_p0, d_seg_p1;
     EvalEnd *ev = nullptr;
     const char *who = "rwr_recommend_restart_batch";
+    // typed: the candidates are rows[0 .. nrows) (typed.hip's cached list of a node type) in place of the ITEM rows, the
+    // excluded links those whose type has its bit in mask in place of LIKE, and, with members set, the sets' nodes themselves
+    bool typed = false;
+    const int32_t *rows = nullptr;
+    int32_t nrows = 0;
+    uint32_t mask = 0;
+    bool members = false;
+    MemberPlan mplan{};
+    DevBuf<int32_t> d_pair_slot{}, d_pair_row{};
 };
 }  // namespace
 
@@ -74,6 +88,21 @@ static int32_t ranked_prepare(rwr_graph *g, Ranked &rk, int32_t K, const std::ve
         RWR_HIP(hipMemcpyAsync(rk.d_seg_p0.p, rk.plan.seg_p0.data(), nseg * sizeof(int64_t), hipMemcpyHostToDevice, s));
         RWR_HIP(hipMemcpyAsync(rk.d_seg_p1.p, rk.plan.seg_p1.data(), nseg * sizeof(int64_t), hipMemcpyHostToDevice, s));
     }
+    if (rk.typed && rk.members) {
+        rk.mplan = member_plan(g->n, slots, slot_k.data(), slots_per_group, K, rk.set_ptr, rk.set_idx);
+        if (rk.mplan.check.verdict != EXCLUDE_OK) {
+            set_error("%s: exclusion sets failed their check (verdict %d)", rk.who, (int)rk.mplan.check.verdict);
+            return RWR_E_INVALID;
+        }
+        const size_t npairs = rk.mplan.pair_slot.size();
+        if (npairs > 0x7FFFFFFFull) { set_error("%s: too many set members", rk.who); return RWR_E_UNSUPPORTED; }
+        if (npairs > 0) {
+            RWR_TRY(rk.d_pair_slot.alloc(npairs));
+            RWR_TRY(rk.d_pair_row.alloc(npairs));
+            RWR_HIP(hipMemcpyAsync(rk.d_pair_slot.p, rk.mplan.pair_slot.data(), npairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            RWR_HIP(hipMemcpyAsync(rk.d_pair_row.p, rk.mplan.pair_row.data(), npairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        }
+    }
     return RWR_OK;
 }
 
@@ -86,9 +115,20 @@ static int32_t ranked_finish_group(rwr_graph *g, const Ranked &rk, int G, int tg
     const int64_t j0 = rk.plan.group_off[(size_t)grp], nseg = rk.plan.group_off[(size_t)grp + 1] - j0;
     const int32_t *slot_k = g->d_slot_k.p + q0;
     hipEvent_t a; RWR_TRY(prof.record(a, s));
+    if (rk.typed) {                                             // (top_n <= the select path's limit: api.hip)
+        launch_exclude_typed(g, G, (int32_t)nseg, rk.d_seg_slot.p + j0, rk.d_seg_p0.p + j0, rk.d_seg_p1.p + j0, rk.mask, X, s);
+        if (rk.members) {
+            const int64_t m0 = rk.mplan.group_off[(size_t)grp], npairs = rk.mplan.group_off[(size_t)grp + 1] - m0;
+            launch_exclude_members(g, G, (int32_t)npairs, rk.d_pair_slot.p + m0, rk.d_pair_row.p + m0, X, s);
+        }
+        RWR_HIP(hipGetLastError());
+        if (rk.nrows > 0) RWR_TRY(rank_group_select(g, G, tg, slot_k, rk.top_n, X, slot_k, s, rk.rows, rk.nrows));
+        RWR_TRY(prof.end(prof.rank, a, s));                     // (no candidate: the zeroed tables stand)
+        return RWR_OK;
+    }
     launch_exclude_segments(g, G, (int32_t)nseg, rk.d_seg_slot.p + j0, rk.d_seg_p0.p + j0, rk.d_seg_p1.p + j0, X, s);
     RWR_HIP(hipGetLastError());
-    if (rk.ev) RWR_TRY(eval_group(g, *rk.ev, G, tg, q0, X, s));
+    if (rk.ev) RWR_TRY(eval_group(g, *rk.ev, G, tg, q0, X, g->item_rows.p, g->n_items, s));
     else RWR_TRY(rank_group(g, G, tg, slot_k, slot_k, rk.top_n, X, s));
     RWR_TRY(prof.end(prof.rank, a, s));
     return RWR_OK;
@@ -338,6 +378,22 @@ int32_t recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr,
     StreamsIdle idle{g};                                        // (the plan's device copy outlives the kernels that read it)
     return restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, d, RWR_RUN_ITERATIONS, (double)n_iter, nullptr, nullptr, &rk,
                          "rwr_recommend_restart_batch");
+}
+
+int32_t recommend_restart_typed_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                      const double *sup_val, const int32_t *start, const int64_t *set_ptr, const int32_t *set_idx,
+                                      double d, int32_t n_iter, int32_t top_n, int32_t cand_type, uint32_t excl_edge_mask,
+                                      int32_t exclude_members, int64_t *ids, double *scores, int32_t *counts)
+{
+    static const char *const who = "rwr_recommend_restart_typed_batch";
+    Ranked rk{set_ptr, set_idx, top_n, ids, scores, counts, {}, {}, {}, {}, nullptr, who};
+    rk.typed = true, rk.mask = excl_edge_mask, rk.members = exclude_members != 0;
+    StreamsIdle idle{g};                                        // (the plans' device copies outlive the kernels that read them)
+    return no_throw(who, [&] {
+        RWR_TRY(cand_rows_get(g, cand_type, &rk.rows, &rk.nrows));   // (before the workspace is sized from what is free)
+        return restart_batch_body(g, K, sup_ptr, sup_idx, sup_val, start, d, RWR_RUN_ITERATIONS, (double)n_iter, nullptr, nullptr,
+                                  &rk, who);
+    });
 }
 
 int32_t recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,

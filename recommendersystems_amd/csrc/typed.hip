@@ -11,6 +11,12 @@
 //     without raw links has no segment);
 //   - the ranking is rank.hip's radix select over the candidate list of the type (top_n <= SEL_MAX_K).
 // The candidate list is compacted on the device on first use and cached per handle (cand_plan.h: geometry and cache rule).
+//
+// rwr_recommend_typed_eval_batch is the same driver with the evaluating end: after the exclusion kernels the
+// group is evaluated against the seeds' test sets by counting (eval_count.hip over the candidate list) instead of ranked, one
+// record per seed leaves, and no list is written -- so top_n has no limit there.  The exclusion kernels serve
+// rwr_recommend_restart_typed_batch as well (restart_batch.hip), through the launch_ wrappers below.
+#include "eval_count.h"
 #include "exclude_plan.h"
 #include "iterate.h"
 
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(CAND_BLOCK) void k_cand_scatter(int32_t n, const ui
 
 // The candidate list of node type `type` on the handle's current node set: the cached one, or built now into the entry
 // cand_cache_choose names.  The stream is idle on entry (every entry point ends synchronised) and on return.
-static int32_t cand_rows_get(rwr_graph *g, int32_t type, const int32_t **rows, int32_t *nrows)
+int32_t cand_rows_get(rwr_graph *g, int32_t type, const int32_t **rows, int32_t *nrows)
 {
     const CandChoice ch = cand_cache_choose(g->cand_entry, type, g->n);
     CandEntry &e = g->cand_entry[ch.entry];
@@ -158,12 +164,40 @@ __global__ __launch_bounds__(64) void k_exclude_self(int32_t n, int G, int nslot
     X[(size_t)(q / G) * (size_t)n * G + (size_t)s * G + (q % G)] = -1.0;
 }
 
+void launch_exclude_typed(rwr_graph *g, int G, int32_t nseg, const int32_t *seg_slot, const int64_t *seg_p0, const int64_t *seg_p1,
+                          uint32_t mask, double *X, hipStream_t s)
+{
+    if (nseg <= 0 || mask == 0) return;
+    hipLaunchKernelGGL(k_exclude_typed, dim3((unsigned)nseg), dim3(64), 0, s, g->n, G, nseg, seg_slot, seg_p0, seg_p1, g->dst.p,
+                       g->etype.p, mask, X);
+}
+
+// exclude_members (rwr_recommend_restart_typed_batch): one thread per (slot, member) pair of the group (member_plan.h) marks
+// the member's own row in its vector's column -- also of a member without raw links.  A member listed twice, or that is a
+// masked target as well, simply receives its -1 twice.
+__global__ __launch_bounds__(256) void k_exclude_members(int32_t n, int G, int32_t npairs, const int32_t *__restrict__ pair_slot,
+                                                         const int32_t *__restrict__ pair_row, double *__restrict__ X)
+{
+    const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= npairs) return;
+    const int32_t q = pair_slot[j], row = pair_row[j];
+    if (row < 0 || row >= n) return;                             // (member_plan.h plans rows of [0, n) only)
+    X[(size_t)(q / G) * (size_t)n * G + (size_t)row * G + (q % G)] = -1.0;
+}
+void launch_exclude_members(rwr_graph *g, int G, int32_t npairs, const int32_t *pair_slot, const int32_t *pair_row, double *X,
+                            hipStream_t s)
+{
+    if (npairs <= 0) return;
+    hipLaunchKernelGGL(k_exclude_members, dim3(cdiv((size_t)npairs, 256)), dim3(256), 0, s, g->n, G, npairs, pair_slot, pair_row, X);
+}
+
 // ---- the driver --------------------------------------------------------------------------------------------------------------
 
+// ev != nullptr: the evaluating form -- no list tables, the group's end is eval_group, K records leave
 static int32_t typed_body(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
-                          int32_t cand_type, uint32_t mask, int32_t exclude_self, int64_t *ids, double *scores, int32_t *counts)
+                          int32_t cand_type, uint32_t mask, int32_t exclude_self, int64_t *ids, double *scores, int32_t *counts,
+                          EvalEnd *ev, const char *who)
 {
-    static const char *const who = "rwr_recommend_typed_batch";
     const double t_begin = now_ms();
     const int64_t T = n_iter;
     hipStream_t s = g->stream;
@@ -202,7 +236,8 @@ static int32_t typed_body(rwr_graph *g, const int32_t *seeds, int32_t K, double 
         RWR_HIP(hipMemcpyAsync(d_seg_p0.p, plan.seg_p0.data(), nseg_all * sizeof(int64_t), hipMemcpyHostToDevice, s));
         RWR_HIP(hipMemcpyAsync(d_seg_p1.p, plan.seg_p1.data(), nseg_all * sizeof(int64_t), hipMemcpyHostToDevice, s));
     }
-    RWR_TRY(ensure_out_tables(g, K, top_n, s));
+    if (ev) RWR_TRY(eval_prepare(g, *ev, K, slot_k, (size_t)TG * G, who, s));
+    else RWR_TRY(ensure_out_tables(g, K, top_n, s));
 
     Profile prof(g);
     for (int t0 = 0, grp = 0; t0 < ntiles; t0 += TG, ++grp) {
@@ -229,10 +264,12 @@ static int32_t typed_body(rwr_graph *g, const int32_t *seeds, int32_t K, double 
         if (exclude_self)
             hipLaunchKernelGGL(k_exclude_self, dim3(cdiv((size_t)tg * G, 64)), dim3(64), 0, s, g->n, G, tg * G, dseeds, gi.X);
         RWR_HIP(hipGetLastError());
-        if (nrows > 0) RWR_TRY(rank_group_select(g, G, tg, g->d_slot_k.p + q0, top_n, gi.X, dseeds, s, rows, nrows));
+        if (ev) RWR_TRY(eval_group(g, *ev, G, tg, q0, gi.X, rows, nrows, s));   // (no candidate: the zeroed records stand)
+        else if (nrows > 0) RWR_TRY(rank_group_select(g, G, tg, g->d_slot_k.p + q0, top_n, gi.X, dseeds, s, rows, nrows));
         RWR_TRY(prof.end(prof.rank, a, s));
     }
-    RWR_TRY(copy_lists_back(g, K, top_n, ids, scores, counts, top_n));
+    if (ev) RWR_TRY(eval_copy_back(g, *ev, K, who, s));
+    else RWR_TRY(copy_lists_back(g, K, top_n, ids, scores, counts, top_n));
     g->stats.seeds_done += K;
     return finish_model_batch(g, prof, G, TG, t_begin);
 }
@@ -241,8 +278,22 @@ int32_t recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K, dou
                               int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t *ids, double *scores,
                               int32_t *counts)
 {
-    return no_throw("rwr_recommend_typed_batch", [&] {
-        return typed_body(g, seeds, K, d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, ids, scores, counts);
+    static const char *const who = "rwr_recommend_typed_batch";
+    return no_throw(who, [&] {
+        return typed_body(g, seeds, K, d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, ids, scores, counts, nullptr, who);
+    });
+}
+
+int32_t recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
+                                   int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
+                                   const int64_t *test_ids, int64_t *n_hits, double *sum_precision, int64_t *list_len)
+{
+    static const char *const who = "rwr_recommend_typed_eval_batch";
+    EvalEnd ev;                                                  // (declared before the body's StreamsIdle: the buffers outlive the kernels)
+    ev.test_ptr = test_ptr, ev.test_ids = test_ids, ev.top_n = top_n;
+    ev.n_hits = n_hits, ev.sum_precision = sum_precision, ev.list_len = list_len;
+    return no_throw(who, [&] {
+        return typed_body(g, seeds, K, d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, nullptr, nullptr, nullptr, &ev, who);
     });
 }
 

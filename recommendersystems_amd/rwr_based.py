@@ -770,6 +770,74 @@ class Recommender:
         c = int(counts[0])
         return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist()))
 
+    def RecommendationTypedEvalBatch(self, seeds, dampingFactor: float, nIteration: int, testSets, candType, exclEdgeTypes=(),
+                                     excludeSelf: bool = False, topN: int = 0):
+        """Hits and the running-precision sum (Experiment.cs:121-128) of K seeds' WHOLE lists among the nodes of one node type
+        against one test set each, evaluated on the device without writing a ranked list (rwr_recommend_typed_eval_batch, an
+        addition, see include/rwr.h): (nHits[K], sumPrecision[K], listLen[K]).  candType, exclEdgeTypes and excludeSelf as in
+        RecommendationTypedBatch; testSets: a sequence of K collections of node ids; topN > 0 evaluates the first topN entries
+        of every list (any value: there is no 1024 limit here), topN <= 0 the whole list."""
+        lib = _lib.load()
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        K = int(seeds.shape[0])
+        mask = 0
+        for t in exclEdgeTypes:
+            mask |= 1 << int(EdgeType(t))
+        tests = [np.asarray(list(t), dtype=np.int64).reshape(-1) for t in testSets]
+        if len(tests) != K:
+            raise ValueError(f"testSets must hold {K} id collections")
+        tp = np.zeros(K + 1, dtype=np.int64)
+        tp[1:] = np.cumsum([len(t) for t in tests])
+        ti = np.ascontiguousarray(np.concatenate(tests) if K else np.zeros(0, dtype=np.int64), dtype=np.int64)
+        hits = np.zeros(K, dtype=np.int64)
+        sp = np.zeros(K, dtype=np.float64)
+        ln = np.zeros(K, dtype=np.int64)
+        _lib.check(lib.rwr_recommend_typed_eval_batch(self.graph._handle(), _p(seeds, C.c_int32), K, C.c_float(dampingFactor),
+                                                      int(nIteration), int(topN), int(candType), mask, 1 if excludeSelf else 0,
+                                                      _p(tp, C.c_int64), _p(ti, C.c_int64), _p(hits, C.c_int64),
+                                                      _p(sp, C.c_double), _p(ln, C.c_int64)))
+        return hits, sp, ln
+
+    def RecommendationTypedEval(self, idxTargetNode: int, dampingFactor: float, nIteration: int, testSet, candType,
+                                exclEdgeTypes=(), excludeSelf: bool = False, topN: int = 0) -> Tuple[int, float, int]:
+        """RecommendationTypedEvalBatch for one seed, as RecommendationEval returns: (nHits, sumPrecision, len(list))."""
+        hits, sp, ln = self.RecommendationTypedEvalBatch([int(idxTargetNode)], dampingFactor, nIteration, [testSet], candType,
+                                                         exclEdgeTypes, excludeSelf, topN)
+        return int(hits[0]), float(sp[0]), int(ln[0])
+
+    def RecommendationRestartTypedBatch(self, restarts, starts, dampingFactor: float, nIteration: int, topN: int, candType,
+                                        exclEdgeTypes=(), excludeMembers: bool = False, exclude=None):
+        """Top-N lists among the nodes of one node type for K walks with caller-set restart vectors
+        (rwr_recommend_restart_typed_batch, an addition, see include/rwr.h): (ids[K,topN], scores[K,topN], counts[K]).
+        restarts, starts and exclude as in RecommendationRestartBatch; candType and exclEdgeTypes as in
+        RecommendationTypedBatch -- the targets of the raw links of those types of every member of set k are no candidates;
+        excludeMembers: neither are the members themselves.  "Whom should this group follow" is (NodeType.USER,
+        (EdgeType.FRIENDSHIP, EdgeType.FOLLOW), True)."""
+        lib = _lib.load()
+        K, sup_ptr, sup_idx, sup_val, st = _pack_restarts(restarts, starts)
+        ep = ei = None
+        if exclude is not None:
+            sets = [np.asarray(e, dtype=np.int32).reshape(-1) for e in exclude]
+            if len(sets) != K:
+                raise ValueError(f"exclude must hold {K} node lists")
+            ep = np.zeros(K + 1, dtype=np.int64)
+            ep[1:] = np.cumsum([len(e) for e in sets])
+            ei = np.ascontiguousarray(np.concatenate(sets) if K else np.zeros(0, dtype=np.int32), dtype=np.int32)
+        mask = 0
+        for t in exclEdgeTypes:
+            mask |= 1 << int(EdgeType(t))
+        topN = int(topN)
+        ids = np.zeros((K, max(topN, 0)), dtype=np.int64)
+        sc = np.zeros((K, max(topN, 0)), dtype=np.float64)
+        counts = np.zeros(K, dtype=np.int32)
+        _lib.check(lib.rwr_recommend_restart_typed_batch(self.graph._handle(), K, _p(sup_ptr, C.c_int64), _p(sup_idx, C.c_int32),
+                                                         _p(sup_val, C.c_double), None if st is None else _p(st, C.c_int32),
+                                                         None if ep is None else _p(ep, C.c_int64),
+                                                         None if ei is None else _p(ei, C.c_int32), float(dampingFactor),
+                                                         int(nIteration), topN, int(candType), mask, 1 if excludeMembers else 0,
+                                                         _p(ids, C.c_int64), _p(sc, C.c_double), _p(counts, C.c_int32)))
+        return ids, sc, counts
+
     def RecommendationRestartBatch(self, restarts, starts, dampingFactor: float, nIteration: int, topN: int, exclude=None):
         """Top-N lists of K walks with caller-set restart vectors, ranked on the device (rwr_recommend_restart_batch, an
         addition, see include/rwr.h): (ids[K,topN], scores[K,topN], counts[K]).  restarts and starts as in
