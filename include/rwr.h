@@ -517,8 +517,12 @@ int32_t rwr_recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t 
  *     (caller)               all-reduce(sum) of y and r over the ranks  -- RCCL over xGMI, torch.distributed
  *     rwr_part_finish_step   y[seed_k][k] += r[k]      (Model.cs:91-93,96-97)
  * after which y is the next x.  dev_* are DEVICE pointers owned by the caller (n*G, n*G and G doubles).
- * Partial sums re-associate across ranks: parity with the single-GPU result is to tolerance (scores
- * within 1e-6; identical top-k lists in the tests), never bitwise.  rwr_part_rank ranks the seeds whose row
+ * A rank's link-only partial y IS bitwise, for any x and whichever step of the walk it is: every row the list-order
+ * sum, from 0.0, of the addends fl(fl((1-d) x[i][k]) * w) of its in-links from the slab (source ascending, list
+ * position ascending; no FMA) -- the arithmetic of the batch path; rows no in-slab source reaches and the padding
+ * columns are +0.0, and only the slab's rows of x are read.  What re-associates is the restart mass r (a tree sum
+ * over the slab's rows) and the sum over the ranks: parity of the WALK with the single-GPU result is therefore to
+ * tolerance (scores within 1e-6; identical top-k lists in the tests).  rwr_part_rank ranks the seeds whose row
  * this rank owns (only the owner holds the seed's raw LIKE links for the exclusion list,
  * Recommender.cs:20-24) and reports counts[k] = -1 for the others. */
 int32_t rwr_part_begin(rwr_graph *g, int32_t slab_lo, int32_t slab_hi, const int32_t *seeds, int32_t K, double d,

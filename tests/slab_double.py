@@ -7,14 +7,32 @@ import torch
 from oracle.c_oracle import FlatGraph
 
 
+def slab_partial(F, lo, hi, c1, X, reverse=False):
+    """One rank's share of a step for ANY rank matrix X[n][G] (padding columns included; rows outside [lo, hi) may hold
+    anything, NaN included: F has out-links for the slab's rows only, so they are never read).  F = FlatGraph of the slab
+    graph.  Returns
+      Y[n][G]      the link-only partial (1-d) P_slab^T X: from 0.0, the addends (c1 * X[src]) * w_norm of the slab's explicit
+                   links added to Y[dst] one by one, source ascending, list position ascending (np.add.at is unbuffered and
+                   takes its indices in order) -- per destination row the order, and so the bits, of the device's list-order
+                   sum.  reverse = True adds the same addends in the opposite order (a test's counter-example).
+      terms[hi-lo][G]  the rows' restart terms, dangling ? x : x - c1 * x."""
+    X = np.asarray(X, dtype=np.float64)
+    e = np.flatnonzero(F.etype != 0)                      # CSR order: source ascending, list position ascending
+    if reverse:
+        e = e[::-1]
+    src = np.repeat(np.arange(F.n), np.diff(F.rowptr))[e]
+    Y = np.zeros_like(X)
+    np.add.at(Y, F.dst[e], (c1 * X[src]) * F.w_norm[e][:, None])
+    xs = X[lo:hi]
+    terms = np.where(F.dangling[lo:hi].astype(bool)[:, None], xs, xs - c1 * xs)
+    return Y, terms
+
+
 class NumpySlabBackend:
     def __init__(self, local_flat, lo, hi, **opts):
         self.lo, self.hi = lo, hi
         self.F = FlatGraph(**local_flat)          # Graph.buildGraph on the slab's links
         self.n = self.F.n
-        rp, dst = self.F.rowptr, self.F.dst
-        self.src = np.repeat(np.arange(self.n), np.diff(rp))
-        self.expl = self.F.etype != 0
 
     def begin(self, seeds, d):
         self.seeds, self.c1 = np.asarray(seeds), 1 - d
@@ -25,15 +43,9 @@ class NumpySlabBackend:
 
     def local_step(self, x, y, r):
         K = len(self.seeds)
-        X = x.view(self.n, K).numpy()
-        Y = np.zeros_like(X)
-        m = self.expl
-        np.add.at(Y, self.F.dst[m], (self.c1 * X[self.src[m]]) * self.F.w_norm[m][:, None])
+        Y, terms = slab_partial(self.F, self.lo, self.hi, self.c1, x.view(self.n, K).numpy())
         y.view(self.n, K)[:] = torch.from_numpy(Y)
-        sl = slice(self.lo, self.hi)
-        dang = self.F.dangling[sl].astype(bool)[:, None]
-        rr = np.where(dang, X[sl], X[sl] - self.c1 * X[sl])
-        r[:] = torch.from_numpy(rr.sum(axis=0))
+        r[:] = torch.from_numpy(terms.sum(axis=0))
 
     def step(self, x, y):
         # partial y over all rows + this slab's restart mass at the seeds' rows (rwr_part_step)
