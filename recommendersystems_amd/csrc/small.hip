@@ -11,13 +11,17 @@
 //     the seed (Model.cs:84,87) and drops them at their place of the seed row's addend sequence M (LDS) -- for node i
 //     ascending: first i's links into the seed in list order, then i's restart addend (Model.cs:85-93,96-97); the places
 //     depend on the graph and the seed only and are computed once;
-//   * wave 0 then folds M strictly in order: the first 1024 addends with real fp64 adds, the rest as an exact parallel
-//     reduction inside the current binade (pf.h; chain_scan.hip explains the arithmetic) with real adds wherever the
+//   * wave 0 then folds M strictly in order: the first SM_SEQ (256) addends with real fp64 adds, the rest in passes of
+//     SM_PASS (1024) addends as an exact parallel reduction inside the current binade (pf.h; chain_scan.hip explains the arithmetic) with real adds wherever the
 //     running sum leaves a binade -- bit for bit the sequential chain;
 //   * waves 1-7 meanwhile sum every other row in list order (weighted form, Model.cs:84,87): rows of >= 128 in-links
 //     (the ego itself, hub items) by a whole wave -- parallel loads and products, sequential adds --, the rest a lane each;
 //   * ranking: bitonic sort of the <= 4096 candidates on the 128-bit key (score, id) in LDS, as k_rank_small.
 // Results are bitwise those of the general EXACT path (tests/test_gpu_parity.py runs both and compares with the oracle).
+// tests/test_gpu_small_edges.py holds this kernel (and k_small_rwr_multi) to the oracle's bits at the edges of its own packing:
+// sequences of 255 .. 257, 1279 .. 1281 and 2304 / 2305 addends, the last one that fits M (SM_MCAP = 12288) and the first that
+// does not, ties / crossings / subnormal sums inside the passes, long rows of 127 .. 257 in-links; tests/test_small_cases.py
+// proves on the CPU that those graphs are what they claim to be.
 #include "engine.h"
 #include "pf.h"
 
