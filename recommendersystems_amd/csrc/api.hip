@@ -182,16 +182,60 @@ static int32_t eval_verdict_status(const char *who, const EvalCheck &c, const in
     return RWR_OK;
 }
 
-// ... and the graph and damping factor of the Recommendation entries
-static int32_t check_ranked_domain(const char *who, const rwr_graph *g, double d)
+// A TypedCheck's verdict on the arguments of a typed entry, as status and message (TYPED_NOOP is the caller's: it returns
+// RWR_OK at once).  null_arg: the pointers TYPED_NULL_ARG names for this entry; top_n_hint: what the entry appends to
+// TYPED_TOP_N_LIMIT's text, nullptr: its check gives no top_n verdict
+static int32_t typed_verdict_status(const char *who, const TypedCheck &c, int32_t n, int32_t top_n, int32_t cand_type,
+                                    uint32_t excl_edge_mask, const char *null_arg, const char *top_n_hint)
+{
+    switch (c.verdict) {
+        case TYPED_OK:
+        case TYPED_NOOP: break;
+        case TYPED_NULL_GRAPH:
+            set_error("%s: NULL graph", who);
+            return RWR_E_INVALID;
+        case TYPED_NEGATIVE_K:
+            set_error("%s: negative K", who);
+            return RWR_E_INVALID;
+        case TYPED_NULL_ARG:
+            set_error("%s: NULL %s", who, null_arg);
+            return RWR_E_INVALID;
+        case TYPED_BAD_CAND_TYPE:
+            set_error("%s: cand_type %d is outside [0, 255]", who, cand_type);
+            return RWR_E_INVALID;
+        case TYPED_BAD_MASK:
+            set_error("%s: excl_edge_mask 0x%x has a bit beyond the %u edge types", who, excl_edge_mask, TYPED_EDGE_TYPES);
+            return RWR_E_INVALID;
+        case TYPED_SEED_RANGE:
+            set_error("%s: seed %d (batch position %d) is outside [0, %d)", who, c.bad_seed, c.bad_k, n);
+            return RWR_E_RANGE;
+        case TYPED_BAD_TOP_N:
+        case TYPED_TOP_N_LIMIT:
+            if (!top_n_hint) {
+                set_error("%s: unexpected verdict %d", who, (int)c.verdict);
+                return RWR_E_INVALID;
+            }
+            if (c.verdict == TYPED_BAD_TOP_N) {
+                set_error("%s: top_n must be >= 1", who);
+                return RWR_E_INVALID;
+            }
+            set_error("%s: top_n %d is beyond the select path's limit of %d entries%s", who, top_n, rank_select_max_k(), top_n_hint);
+            return RWR_E_UNSUPPORTED;
+    }
+    return RWR_OK;
+}
+
+// ... and the graph and damping factor of the Recommendation entries: the exclusion marker (-1) and the ranking keys assume
+// scores >= 0.  model_entry: the entry that runs what this one refuses
+static int32_t check_ranked_domain(const char *who, const rwr_graph *g, double d, const char *model_entry)
 {
     if (!g->nonneg) {
-        set_error("%s: Recommendation needs non-negative finite link weights and positive row sums; "
-                  "rwr_model_run_restart_batch accepts such graphs", who);
+        set_error("%s: Recommendation needs non-negative finite link weights and positive row sums; %s accepts such graphs", who,
+                  model_entry);
         return RWR_E_UNSUPPORTED;
     }
     if (!(d >= 0.0 && d <= 1.0)) {
-        set_error("%s: Recommendation needs a damping factor in [0, 1] (got %g); rwr_model_run_restart_batch accepts any value", who, d);
+        set_error("%s: Recommendation needs a damping factor in [0, 1] (got %g); %s accepts any value", who, d, model_entry);
         return RWR_E_UNSUPPORTED;
     }
     return RWR_OK;
@@ -350,45 +394,10 @@ int32_t rwr_recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K,
     g_err[0] = 0;
     const TypedCheck c = typed_check(g != nullptr, g ? g->n : 0, seeds, K, top_n, rank_select_max_k(), cand_type, excl_edge_mask,
                                      ids && scores && counts);
-    switch (c.verdict) {
-        case TYPED_OK: break;
-        case TYPED_NOOP: return RWR_OK;
-        case TYPED_NULL_GRAPH:
-            set_error("%s: NULL graph", who);
-            return RWR_E_INVALID;
-        case TYPED_NEGATIVE_K:
-            set_error("%s: negative K", who);
-            return RWR_E_INVALID;
-        case TYPED_NULL_ARG:
-            set_error("%s: NULL seeds, ids, scores or counts", who);
-            return RWR_E_INVALID;
-        case TYPED_BAD_TOP_N:
-            set_error("%s: top_n must be >= 1", who);
-            return RWR_E_INVALID;
-        case TYPED_BAD_CAND_TYPE:
-            set_error("%s: cand_type %d is outside [0, 255]", who, cand_type);
-            return RWR_E_INVALID;
-        case TYPED_BAD_MASK:
-            set_error("%s: excl_edge_mask 0x%x has a bit beyond the %u edge types", who, excl_edge_mask, TYPED_EDGE_TYPES);
-            return RWR_E_INVALID;
-        case TYPED_SEED_RANGE:
-            set_error("%s: seed %d (batch position %d) is outside [0, %d)", who, c.bad_seed, c.bad_k, g->n);
-            return RWR_E_RANGE;
-        case TYPED_TOP_N_LIMIT:
-            set_error("%s: top_n %d is beyond the select path's limit of %d entries (rwr_recommend_typed_eval_batch evaluates "
-                      "whole lists of a node type)", who, top_n, rank_select_max_k());
-            return RWR_E_UNSUPPORTED;
-    }
-    // the domain of the Recommendation entries: the exclusion marker (-1) and the ranking keys assume scores >= 0
-    if (!g->nonneg) {
-        set_error("%s: Recommendation needs non-negative finite link weights and positive row sums; rwr_model_run_batch "
-                  "accepts such graphs", who);
-        return RWR_E_UNSUPPORTED;
-    }
-    if (!((double)d >= 0.0 && (double)d <= 1.0)) {
-        set_error("%s: Recommendation needs a damping factor in [0, 1] (got %g); rwr_model_run_batch accepts any value", who, (double)d);
-        return RWR_E_UNSUPPORTED;
-    }
+    if (c.verdict == TYPED_NOOP) return RWR_OK;
+    RWR_TRY(typed_verdict_status(who, c, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds, ids, scores or counts",
+                                 " (rwr_recommend_typed_eval_batch evaluates whole lists of a node type)"));
+    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
     if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
     // Recommender.cs:14,16 -> Model.cs:33: the float is widened to double
     return bound(who, g, [&] {
@@ -404,43 +413,11 @@ int32_t rwr_recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32
     g_err[0] = 0;
     const TypedEvalCheck c = typed_eval_check(g != nullptr, g ? g->n : 0, seeds, K, cand_type, excl_edge_mask, test_ptr, test_ids,
                                               n_hits, sum_precision);
-    switch (c.typed.verdict) {
-        case TYPED_OK: break;
-        case TYPED_NOOP: return RWR_OK;
-        case TYPED_NULL_GRAPH:
-            set_error("%s: NULL graph", who);
-            return RWR_E_INVALID;
-        case TYPED_NEGATIVE_K:
-            set_error("%s: negative K", who);
-            return RWR_E_INVALID;
-        case TYPED_NULL_ARG:
-            set_error("%s: NULL seeds", who);
-            return RWR_E_INVALID;
-        case TYPED_BAD_CAND_TYPE:
-            set_error("%s: cand_type %d is outside [0, 255]", who, cand_type);
-            return RWR_E_INVALID;
-        case TYPED_BAD_MASK:
-            set_error("%s: excl_edge_mask 0x%x has a bit beyond the %u edge types", who, excl_edge_mask, TYPED_EDGE_TYPES);
-            return RWR_E_INVALID;
-        case TYPED_SEED_RANGE:
-            set_error("%s: seed %d (batch position %d) is outside [0, %d)", who, c.typed.bad_seed, c.typed.bad_k, g->n);
-            return RWR_E_RANGE;
-        case TYPED_BAD_TOP_N:
-        case TYPED_TOP_N_LIMIT:                                  // (top_n has no bound here: typed_eval_check gives neither)
-            set_error("%s: unexpected verdict %d", who, (int)c.typed.verdict);
-            return RWR_E_INVALID;
-    }
+    if (c.typed.verdict == TYPED_NOOP) return RWR_OK;
+    // (top_n has no bound here: typed_eval_check gives neither top_n verdict)
+    RWR_TRY(typed_verdict_status(who, c.typed, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds", nullptr));
     RWR_TRY(eval_verdict_status(who, c.eval, test_ptr));
-    // the domain of the Recommendation entries: the exclusion marker (-1) and the ranking keys assume scores >= 0
-    if (!g->nonneg) {
-        set_error("%s: Recommendation needs non-negative finite link weights and positive row sums; rwr_model_run_batch "
-                  "accepts such graphs", who);
-        return RWR_E_UNSUPPORTED;
-    }
-    if (!((double)d >= 0.0 && (double)d <= 1.0)) {
-        set_error("%s: Recommendation needs a damping factor in [0, 1] (got %g); rwr_model_run_batch accepts any value", who, (double)d);
-        return RWR_E_UNSUPPORTED;
-    }
+    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
     if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
     return bound(who, g, [&] {
         return recommend_typed_eval_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, test_ptr,
@@ -647,7 +624,7 @@ int32_t rwr_recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_
     if (!sup_ptr || !ids || !scores || !counts) { set_error("%s: NULL sup_ptr, ids, scores or counts", who); return RWR_E_INVALID; }
     if (top_n < 1) { set_error("%s: top_n must be >= 1", who); return RWR_E_INVALID; }
     RWR_TRY(check_ranked_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start, excl_ptr, excl_idx));
-    RWR_TRY(check_ranked_domain(who, g, d));
+    RWR_TRY(check_ranked_domain(who, g, d, "rwr_model_run_restart_batch"));
     if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
     // excl_ptr == NULL: set k is the indices of vector k's support, whatever their values
     return bound(who, g, [&] {
@@ -668,23 +645,11 @@ int32_t rwr_recommend_restart_typed_batch(rwr_graph *g, int32_t K, const int64_t
     if (K < 0) { set_error("%s: negative K", who); return RWR_E_INVALID; }
     if (K == 0) return RWR_OK;
     if (!sup_ptr || !ids || !scores || !counts) { set_error("%s: NULL sup_ptr, ids, scores or counts", who); return RWR_E_INVALID; }
-    switch (restart_typed_check(top_n, rank_select_max_k(), cand_type, excl_edge_mask)) {
-        case TYPED_BAD_TOP_N:
-            set_error("%s: top_n must be >= 1", who);
-            return RWR_E_INVALID;
-        case TYPED_BAD_CAND_TYPE:
-            set_error("%s: cand_type %d is outside [0, 255]", who, cand_type);
-            return RWR_E_INVALID;
-        case TYPED_BAD_MASK:
-            set_error("%s: excl_edge_mask 0x%x has a bit beyond the %u edge types", who, excl_edge_mask, TYPED_EDGE_TYPES);
-            return RWR_E_INVALID;
-        case TYPED_TOP_N_LIMIT:
-            set_error("%s: top_n %d is beyond the select path's limit of %d entries", who, top_n, rank_select_max_k());
-            return RWR_E_UNSUPPORTED;
-        default: break;
-    }
+    TypedCheck c;                                                // (the graph, K and the pointers were looked at above)
+    c.verdict = restart_typed_check(top_n, rank_select_max_k(), cand_type, excl_edge_mask);
+    RWR_TRY(typed_verdict_status(who, c, g->n, top_n, cand_type, excl_edge_mask, "", ""));
     RWR_TRY(check_ranked_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start, excl_ptr, excl_idx));
-    RWR_TRY(check_ranked_domain(who, g, d));
+    RWR_TRY(check_ranked_domain(who, g, d, "rwr_model_run_restart_batch"));
     if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
     // excl_ptr == NULL: set k is the indices of vector k's support, whatever their values
     return bound(who, g, [&] {
@@ -708,7 +673,7 @@ int32_t rwr_recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t 
     if (!sup_ptr) { set_error("%s: NULL sup_ptr", who); return RWR_E_INVALID; }
     RWR_TRY(check_ranked_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start, excl_ptr, excl_idx));
     RWR_TRY(eval_verdict_status(who, eval_check(K, test_ptr, test_ids, n_hits, sum_precision), test_ptr));
-    RWR_TRY(check_ranked_domain(who, g, d));
+    RWR_TRY(check_ranked_domain(who, g, d, "rwr_model_run_restart_batch"));
     if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
     return bound(who, g, [&] {
         return recommend_restart_eval_batch(g, K, sup_ptr, sup_idx, sup_val, start, excl_ptr ? excl_ptr : sup_ptr,

@@ -311,15 +311,10 @@ int32_t recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K, dou
 int32_t recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
                                    int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
                                    const int64_t *test_ids, int64_t *n_hits, double *sum_precision, int64_t *list_len);
-// ... and the pieces restart_batch.hip's typed end shares with it.  The device list of the rows with node_type == type,
-// ascending, cached per handle (cand_plan.h); call it on an idle stream and before the workspace is sized
+// ... and the candidates restart_batch.hip's typed end shares with it: the device list of the rows with node_type == type,
+// ascending, cached per handle (cand_plan.h); call it on an idle stream and before the workspace is sized.  (The end of a
+// tile group itself -- exclusion, ranking or evaluation, copy-back -- is ranked_end.h's, for both drivers.)
 int32_t cand_rows_get(rwr_graph *g, int32_t type, const int32_t **rows, int32_t *nrows);
-// k_exclude_typed over exclude_plan.h's segments (slots relative to X's first tile): the targets of the raw links whose type
-// has its bit in mask; k_exclude_members over member_plan.h's pairs: the members' own rows
-void launch_exclude_typed(rwr_graph *g, int G, int32_t nseg, const int32_t *seg_slot, const int64_t *seg_p0, const int64_t *seg_p1,
-                          uint32_t mask, double *X, hipStream_t s);
-void launch_exclude_members(rwr_graph *g, int G, int32_t npairs, const int32_t *pair_slot, const int32_t *pair_row, double *X,
-                            hipStream_t s);
 // ... the restart-vector walks of rwr_recommend_restart_batch ranked among the nodes of one type
 // (rwr_recommend_restart_typed_batch): top_n <= the select path's limit
 int32_t recommend_restart_typed_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,

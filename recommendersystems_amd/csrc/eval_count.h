@@ -13,8 +13,8 @@ struct EvalOut {
     int64_t list_len;
 };
 
-// The evaluating end of a restart batch or of a typed seed batch: the caller's test sets and result arrays, the host plan, its device copy and the
-// per-group scratch.  Declared by the entry point before its StreamsIdle, so the buffers outlive the kernels that read them.
+// The evaluating destination of a RankedEnd (ranked_end.h, whose lifetime rule it shares): the caller's test sets and result
+// arrays, the host plan, its device copy and the per-group scratch.
 struct EvalEnd {
     const int64_t *test_ptr = nullptr, *test_ids = nullptr;
     int32_t top_n = 0;                 // > 0: Hits@N / AP@N; <= 0: the whole list

@@ -1,6 +1,6 @@
 // Which raw links one rwr_recommend_restart_batch call looks at to mark its non-candidates, decided by
 // exclude_plan() from the handle's host row pointers, the batch's slot assignment and the K exclusion sets alone and carried out
-// by k_exclude_segments (rank.hip).  Plain C++17 without HIP, so that tests/cpp/exclude_plan_check.cpp checks it against a
+// by k_exclude_typed (ranked_end.hip).  Plain C++17 without HIP, so that tests/cpp/exclude_plan_check.cpp checks it against a
 // direct walk over the members' raw lists on the host.
 //
 // Set k is the node list set_idx[set_ptr[k] .. set_ptr[k + 1]): the RAW out-links of type LIKE of every member are not

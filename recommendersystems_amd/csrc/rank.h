@@ -13,9 +13,6 @@ const RankKnobs &rank_knobs();   // the ranking's environment values, read once 
 int rank_select_max_k();         // the largest top_n of the select path (SEL_MAX_K)
 // the exclusion (k_exclude: X[tile][n][G], one seed per slot, -1 = none)
 void launch_exclude(rwr_graph *g, int G, int tg, double *X, const int32_t *d_seeds, hipStream_t s);
-// ... of a set of nodes per slot (k_exclude_segments): the segments exclude_plan.h cut the members' raw lists into
-void launch_exclude_segments(rwr_graph *g, int G, int32_t nseg, const int32_t *seg_slot, const int64_t *seg_p0,
-                             const int64_t *seg_p1, double *X, hipStream_t s);
 // the zeroed result tables of a call: K rows of top_n entries, indexed by the caller's batch position
 int32_t ensure_out_tables(rwr_graph *g, int32_t K, int32_t top_n, hipStream_t s);
 // one tile by the full sort (any top_n); a tile group by the radix select (top_n <= SEL_MAX_K) over `rows` (nullptr: the ITEM rows)

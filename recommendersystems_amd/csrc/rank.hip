@@ -429,31 +429,6 @@ void launch_exclude(rwr_graph *g, int G, int tg, double *X, const int32_t *d_see
                        d_seeds);
 }
 
-// The exclusion of a set of nodes per slot (rwr_recommend_restart_batch): Recommender.cs:20-24 applied to every
-// member of the slot's set.  The members' raw lists arrive cut into segments of at most EXCLUDE_SEG_MAX links (exclude_plan.h);
-// one wave per segment, the lanes at consecutive links.  Segments of one slot may name the same item (two members that like
-// it, a member listed twice): every one of them stores the same -1.
-__global__ __launch_bounds__(64) void k_exclude_segments(int32_t n, int G, int32_t nseg, const int32_t *__restrict__ seg_slot,
-                                                         const int64_t *__restrict__ seg_p0, const int64_t *__restrict__ seg_p1,
-                                                         const int32_t *__restrict__ dst, const uint8_t *__restrict__ etype,
-                                                         double *__restrict__ X)
-{
-    const int32_t j = blockIdx.x;
-    if (j >= nseg) return;
-    const int32_t q = seg_slot[j];
-    double *x = X + (size_t)(q / G) * (size_t)n * G + (q % G);
-    const int64_t p1 = seg_p1[j];
-    for (int64_t p = seg_p0[j] + threadIdx.x; p < p1; p += WAVE)
-        if (etype[p] == RWR_EDGE_LIKE) x[(size_t)dst[p] * G] = -1.0;
-}
-void launch_exclude_segments(rwr_graph *g, int G, int32_t nseg, const int32_t *seg_slot, const int64_t *seg_p0,
-                             const int64_t *seg_p1, double *X, hipStream_t s)
-{
-    if (nseg <= 0) return;
-    hipLaunchKernelGGL(k_exclude_segments, dim3((unsigned)nseg), dim3(64), 0, s, g->n, G, nseg, seg_slot, seg_p0, seg_p1, g->dst.p,
-                       g->etype.p, X);
-}
-
 int32_t rank_tile(rwr_graph *g, int G, const int32_t *d_slot_k_tile, int32_t top_n, const double *X,
                   const int32_t *d_seeds_tile, hipStream_t s)
 {

@@ -13,140 +13,25 @@
 // The SpMM runs the weighted kernels (ensure_in_w, as restart.hip): the step lasts as long as its chains, which the SpMM
 // runs beside, so the value-free form's smaller matrix stream would shorten nothing (measured).
 //
-// rwr_recommend_restart_batch is the same driver -- slot dealing, pair upload, step loop, statistics -- with
-// another end of a tile group: after step T the raw LIKE links of every vector's exclusion set are marked in X
-// (k_exclude_segments over exclude_plan.h's segments) and the group is ranked where it lies (rank.hip), so K x top_n entries
-// leave the device in place of K x n.  `Ranked` carries what that end needs; a call without one is the full-vector entry.
-//
-// rwr_recommend_restart_eval_batch is the ranked end in its second form: after the exclusion the group is
-// evaluated against the vectors' test sets by counting (eval_count.hip) instead of ranked, and one record per vector leaves.
+// rwr_recommend_restart_batch, rwr_recommend_restart_eval_batch (3.15) and rwr_recommend_restart_typed_batch
+// (3.17) are the same driver -- slot dealing, pair upload, step loop, statistics -- with another end of a tile group: after
+// step T every vector's exclusion set is marked in X and the group is ranked or evaluated where it lies, so K x top_n entries
+// or K records leave the device in place of K x n.  A RankedEnd (ranked_end.h) says which candidates, which exclusion and
+// which destination, and does that work; the entries below only fill it in.  A call without one is the full-vector entry.
 #include <algorithm>
 #include <cstring>
 
-//
-// rwr_recommend_restart_typed_batch is the ranked end with its ITEM / LIKE constants as arguments: the
-// exclusion is typed.hip's k_exclude_typed over the same segments with an edge-type mask, the members' own rows are marked on
-// request (k_exclude_members over member_plan.h's pairs), and the select ranks the cached rows of the candidate type.
-#include "eval_count.h"
-#include "exclude_plan.h"
 #include "iterate.h"
-#include "member_plan.h"
+#include "ranked_end.h"
 
 namespace rwr {
-
-namespace {
-// The ranked end of a call: the exclusion sets (CSR over batch positions), the lists' width and destination, and the device
-// copy of the exclusion plan.  ev != nullptr: the evaluating form -- no list tables, the group's tail is eval_group.
-// Declared by the entry point before its StreamsIdle, so the buffers outlive the kernels.
-struct Ranked {
-    const int64_t *set_ptr;
-    const int32_t *set_idx;
-    int32_t top_n;
-    int64_t *ids;
-    double *scores;
-    int32_t *counts;
-    ExcludePlan plan;
-    DevBuf<int32_t> d_seg_slot;
-    DevBuf<int64_t> d_seg_p0, d_seg_p1;
-    EvalEnd *ev = nullptr;
-    const char *who = "rwr_recommend_restart_batch";
-    // typed: the candidates are rows[0 .. nrows) (typed.hip's cached list of a node type) in place of the ITEM rows, the
-    // excluded links those whose type has its bit in mask in place of LIKE, and, with members set, the sets' nodes themselves
-    bool typed = false;
-    const int32_t *rows = nullptr;
-    int32_t nrows = 0;
-    uint32_t mask = 0;
-    bool members = false;
-    MemberPlan mplan{};
-    DevBuf<int32_t> d_pair_slot{}, d_pair_row{};
-};
-}  // namespace
-
-// The zeroed output tables of the call (indexed by batch position), the slots' batch positions in g->d_slot_k -- the ranking's
-// output-row table and, read through its `seeds` parameter, its liveness array -- and the exclusion plan of that slot
-// assignment (slots_per_group slots form a tile group).  The host vectors are pageable: the caller synchronises s.
-static int32_t ranked_prepare(rwr_graph *g, Ranked &rk, int32_t K, const std::vector<int32_t> &slot_k, size_t slots_per_group,
-                              hipStream_t s)
-{
-    const size_t slots = slot_k.size();
-    if (rk.ev) RWR_TRY(eval_prepare(g, *rk.ev, K, slot_k, slots_per_group, rk.who, s));
-    else RWR_TRY(ensure_out_tables(g, K, rk.top_n, s));
-    RWR_TRY(g->d_slot_k.ensure(slots));
-    RWR_HIP(hipMemcpyAsync(g->d_slot_k.p, slot_k.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    rk.plan = exclude_plan(g->n, g->h_rowptr.data(), slots, slot_k.data(), slots_per_group, K, rk.set_ptr, rk.set_idx);
-    if (rk.plan.check.verdict != EXCLUDE_OK) {                  // (api.hip refuses such sets before the call gets here)
-        set_error("%s: exclusion sets failed their check (verdict %d)", rk.who, (int)rk.plan.check.verdict);
-        return RWR_E_INVALID;
-    }
-    const size_t nseg = rk.plan.seg_slot.size();
-    if (nseg > 0x7FFFFFFFull) { set_error("%s: too many exclusion segments", rk.who); return RWR_E_UNSUPPORTED; }
-    if (nseg > 0) {
-        RWR_TRY(rk.d_seg_slot.alloc(nseg));
-        RWR_TRY(rk.d_seg_p0.alloc(nseg));
-        RWR_TRY(rk.d_seg_p1.alloc(nseg));
-        RWR_HIP(hipMemcpyAsync(rk.d_seg_slot.p, rk.plan.seg_slot.data(), nseg * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        RWR_HIP(hipMemcpyAsync(rk.d_seg_p0.p, rk.plan.seg_p0.data(), nseg * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        RWR_HIP(hipMemcpyAsync(rk.d_seg_p1.p, rk.plan.seg_p1.data(), nseg * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    }
-    if (rk.typed && rk.members) {
-        rk.mplan = member_plan(g->n, slots, slot_k.data(), slots_per_group, K, rk.set_ptr, rk.set_idx);
-        if (rk.mplan.check.verdict != EXCLUDE_OK) {
-            set_error("%s: exclusion sets failed their check (verdict %d)", rk.who, (int)rk.mplan.check.verdict);
-            return RWR_E_INVALID;
-        }
-        const size_t npairs = rk.mplan.pair_slot.size();
-        if (npairs > 0x7FFFFFFFull) { set_error("%s: too many set members", rk.who); return RWR_E_UNSUPPORTED; }
-        if (npairs > 0) {
-            RWR_TRY(rk.d_pair_slot.alloc(npairs));
-            RWR_TRY(rk.d_pair_row.alloc(npairs));
-            RWR_HIP(hipMemcpyAsync(rk.d_pair_slot.p, rk.mplan.pair_slot.data(), npairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            RWR_HIP(hipMemcpyAsync(rk.d_pair_row.p, rk.mplan.pair_row.data(), npairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        }
-    }
-    return RWR_OK;
-}
-
-// Tile group grp (tg tiles of G slots from slot q0 on) holds its final ranks in X: the exclusion, then the ranking as
-// recommend_batch runs it, the slots' batch positions standing in for the seeds (>= 0: a live slot) -- or, in the evaluating
-// form, the four stages of eval_count.hip
-static int32_t ranked_finish_group(rwr_graph *g, const Ranked &rk, int G, int tg, int grp, size_t q0, double *X, Profile &prof,
-                                   hipStream_t s)
-{
-    const int64_t j0 = rk.plan.group_off[(size_t)grp], nseg = rk.plan.group_off[(size_t)grp + 1] - j0;
-    const int32_t *slot_k = g->d_slot_k.p + q0;
-    hipEvent_t a; RWR_TRY(prof.record(a, s));
-    if (rk.typed) {                                             // (top_n <= the select path's limit: api.hip)
-        launch_exclude_typed(g, G, (int32_t)nseg, rk.d_seg_slot.p + j0, rk.d_seg_p0.p + j0, rk.d_seg_p1.p + j0, rk.mask, X, s);
-        if (rk.members) {
-            const int64_t m0 = rk.mplan.group_off[(size_t)grp], npairs = rk.mplan.group_off[(size_t)grp + 1] - m0;
-            launch_exclude_members(g, G, (int32_t)npairs, rk.d_pair_slot.p + m0, rk.d_pair_row.p + m0, X, s);
-        }
-        RWR_HIP(hipGetLastError());
-        if (rk.nrows > 0) RWR_TRY(rank_group_select(g, G, tg, slot_k, rk.top_n, X, slot_k, s, rk.rows, rk.nrows));
-        RWR_TRY(prof.end(prof.rank, a, s));                     // (no candidate: the zeroed tables stand)
-        return RWR_OK;
-    }
-    launch_exclude_segments(g, G, (int32_t)nseg, rk.d_seg_slot.p + j0, rk.d_seg_p0.p + j0, rk.d_seg_p1.p + j0, X, s);
-    RWR_HIP(hipGetLastError());
-    if (rk.ev) RWR_TRY(eval_group(g, *rk.ev, G, tg, q0, X, g->item_rows.p, g->n_items, s));
-    else RWR_TRY(rank_group(g, G, tg, slot_k, slot_k, rk.top_n, X, s));
-    RWR_TRY(prof.end(prof.rank, a, s));
-    return RWR_OK;
-}
-
-// after the last group: K x top_n list entries, or the K evaluation records
-static int32_t ranked_copy_back(rwr_graph *g, Ranked &rk, int32_t K)
-{
-    if (rk.ev) return eval_copy_back(g, *rk.ev, K, rk.who, g->stream);
-    return copy_lists_back(g, K, rk.top_n, rk.ids, rk.scores, rk.counts, rk.top_n);
-}
 
 // Outside the batched domain: rwr_model_run_restart per vector, on the dense vector and the constructor's rank.  rk: each
 // row goes back to the device as a tile of one lane -- vector k its own tile group of one slot -- for the same exclusion and
 // ranking as a batched group's
 static int32_t run_vector_by_vector(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
                                     const int32_t *start, double d, int32_t run_mode, double value, double *rank_out,
-                                    int64_t *iters_out, Ranked *rk, const char *who)
+                                    int64_t *iters_out, RankedEnd *rk, const char *who)
 {
     const int32_t n = g->n;
     hipStream_t s = g->stream;
@@ -155,7 +40,9 @@ static int32_t run_vector_by_vector(rwr_graph *g, int32_t K, const int64_t *sup_
     if (rk) {
         std::vector<int32_t> slot_k((size_t)K);
         for (int32_t k = 0; k < K; ++k) slot_k[(size_t)k] = k;
-        RWR_TRY(ranked_prepare(g, *rk, K, slot_k, 1, s));
+        RWR_TRY(g->d_slot_k.ensure((size_t)K));
+        RWR_HIP(hipMemcpyAsync(g->d_slot_k.p, slot_k.data(), (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RWR_TRY(rk->prepare(g, K, slot_k, 1, s));
         RWR_HIP(hipStreamSynchronize(s));
     }
     for (int32_t k = 0; k < K; ++k) {
@@ -175,7 +62,7 @@ static int32_t run_vector_by_vector(rwr_graph *g, int32_t K, const int64_t *sup_
         if (rk) {
             RWR_TRY(g->X.ensure((size_t)n));
             RWR_HIP(hipMemcpyAsync(g->X.p, row.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-            RWR_TRY(ranked_finish_group(g, *rk, 1, 1, k, (size_t)k, g->X.p, prof, s));
+            RWR_TRY(rk->finish_group(g, 1, 1, k, (size_t)k, g->X.p, prof, s));
             RWR_HIP(hipStreamSynchronize(s));                   // (the next vector's run reuses row and X)
             RWR_TRY(prof.fold(g));
         }
@@ -188,7 +75,7 @@ static int32_t run_vector_by_vector(rwr_graph *g, int32_t K, const int64_t *sup_
 // the finished groups are ranked on the device and the lists copied back once, after the last group
 static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
                                   const double *sup_val, const int32_t *start, double d, int32_t run_mode,
-                                  double value, double *rank_out, int64_t *iters_out, Ranked *rk, const char *who)
+                                  double value, double *rank_out, int64_t *iters_out, RankedEnd *rk, const char *who)
 {
     const double t_begin = now_ms();
     const int32_t n = g->n;
@@ -209,7 +96,7 @@ static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_pt
     if (K == 1 || wide || !g->nonneg || !(d >= 0.0 && d <= 1.0)) {
         RWR_TRY(run_vector_by_vector(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out, rk, who));
         if (rk) {
-            RWR_TRY(ranked_copy_back(g, *rk, K));
+            RWR_TRY(rk->copy_back(g, K));
             g->stats.seeds_done += K;
         }
         g->stats.total_wall_ms += now_ms() - t_begin;
@@ -276,7 +163,11 @@ static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_pt
         RWR_HIP(hipMemcpyAsync(d_pr.p, pr.data(), npairs_all * sizeof(int32_t), hipMemcpyHostToDevice, s));
         RWR_HIP(hipMemcpyAsync(d_pv.p, pv.data(), npairs_all * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    if (rk) RWR_TRY(ranked_prepare(g, *rk, K, slot_k, (size_t)TG * G, s));
+    if (rk) {                                                   // (d_slot_k: the ranking's output-row table and liveness array)
+        RWR_TRY(g->d_slot_k.ensure(slots));
+        RWR_HIP(hipMemcpyAsync(g->d_slot_k.p, slot_k.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RWR_TRY(rk->prepare(g, K, slot_k, (size_t)TG * G, s));
+    }
     RWR_HIP(hipStreamSynchronize(s));                           // (the host vectors above are pageable)
 
     Profile prof(g);                                            // (column extraction counts as ranking time)
@@ -300,7 +191,7 @@ static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_pt
         int64_t steps = 0;
         for (;;) {
             if (rk && steps == end.T) {                         // every column ends here and stays on the device
-                RWR_TRY(ranked_finish_group(g, *rk, G, tg, grp, q0, X, prof, s));
+                RWR_TRY(rk->finish_group(g, G, tg, grp, q0, X, prof, s));
                 break;
             }
             if (cols.ends.due(steps)) {
@@ -341,7 +232,7 @@ static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_pt
         cols.count(steps, steps);
     }
     if (rk) {                                                   // one copy-back of K x top_n entries, as recommend_batch's (or of K records)
-        RWR_TRY(ranked_copy_back(g, *rk, K));
+        RWR_TRY(rk->copy_back(g, K));
         g->stats.seeds_done += K;
     }
     RWR_TRY(finish_model_batch(g, prof, G, TG, t_begin));
@@ -353,31 +244,38 @@ static int32_t restart_batch_body(rwr_graph *g, int32_t K, const int64_t *sup_pt
     return RWR_OK;
 }
 
-static int32_t restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
-                             const int32_t *start, double d, int32_t run_mode, double value, double *rank_out, int64_t *iters_out,
-                             Ranked *rk, const char *who)
-{
-    return no_throw(who, [&] {
-        return restart_batch_body(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out, rk, who);
-    });
-}
-
 int32_t model_run_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
                                 const int32_t *start, double d, int32_t run_mode, double value, double *rank_out,
                                 int64_t *iters_out)
 {
-    return restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out, nullptr,
-                         "rwr_model_run_restart_batch");
+    static const char *const who = "rwr_model_run_restart_batch";
+    return no_throw(who, [&] {
+        return restart_batch_body(g, K, sup_ptr, sup_idx, sup_val, start, d, run_mode, value, rank_out, iters_out, nullptr, who);
+    });
+}
+
+// the ranked entries: T steps, then the end they describe
+static int32_t restart_ranked(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
+                              const int32_t *start, double d, int32_t n_iter, RankedEnd &end, int32_t cand_type = -1)
+{
+    StreamsIdle idle{g};                                        // (declared after end: ranked_end.h)
+    return no_throw(end.who, [&] {
+        // (a type's list is fetched before the workspace is sized from what is free)
+        if (cand_type >= 0) RWR_TRY(cand_rows_get(g, cand_type, &end.rows, &end.nrows));
+        return restart_batch_body(g, K, sup_ptr, sup_idx, sup_val, start, d, RWR_RUN_ITERATIONS, (double)n_iter, nullptr, nullptr,
+                                  &end, end.who);
+    });
 }
 
 int32_t recommend_restart_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
                                 const int32_t *start, const int64_t *set_ptr, const int32_t *set_idx, double d, int32_t n_iter,
                                 int32_t top_n, int64_t *ids, double *scores, int32_t *counts)
 {
-    Ranked rk{set_ptr, set_idx, top_n, ids, scores, counts, {}, {}, {}, {}};
-    StreamsIdle idle{g};                                        // (the plan's device copy outlives the kernels that read it)
-    return restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, d, RWR_RUN_ITERATIONS, (double)n_iter, nullptr, nullptr, &rk,
-                         "rwr_recommend_restart_batch");
+    RankedEnd end;                                              // the ITEM rows, the sets' raw LIKE links, lists
+    end.who = "rwr_recommend_restart_batch";
+    end.set_ptr = set_ptr, end.set_idx = set_idx, end.mask = 1u << RWR_EDGE_LIKE;
+    end.top_n = top_n, end.ids = ids, end.scores = scores, end.counts = counts;
+    return restart_ranked(g, K, sup_ptr, sup_idx, sup_val, start, d, n_iter, end);
 }
 
 int32_t recommend_restart_typed_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
@@ -385,15 +283,11 @@ int32_t recommend_restart_typed_batch(rwr_graph *g, int32_t K, const int64_t *su
                                       double d, int32_t n_iter, int32_t top_n, int32_t cand_type, uint32_t excl_edge_mask,
                                       int32_t exclude_members, int64_t *ids, double *scores, int32_t *counts)
 {
-    static const char *const who = "rwr_recommend_restart_typed_batch";
-    Ranked rk{set_ptr, set_idx, top_n, ids, scores, counts, {}, {}, {}, {}, nullptr, who};
-    rk.typed = true, rk.mask = excl_edge_mask, rk.members = exclude_members != 0;
-    StreamsIdle idle{g};                                        // (the plans' device copies outlive the kernels that read them)
-    return no_throw(who, [&] {
-        RWR_TRY(cand_rows_get(g, cand_type, &rk.rows, &rk.nrows));   // (before the workspace is sized from what is free)
-        return restart_batch_body(g, K, sup_ptr, sup_idx, sup_val, start, d, RWR_RUN_ITERATIONS, (double)n_iter, nullptr, nullptr,
-                                  &rk, who);
-    });
+    RankedEnd end;                                              // the rows of a type, the links of the mask and the members, lists
+    end.who = "rwr_recommend_restart_typed_batch";
+    end.set_ptr = set_ptr, end.set_idx = set_idx, end.mask = excl_edge_mask, end.members = exclude_members != 0;
+    end.top_n = top_n, end.ids = ids, end.scores = scores, end.counts = counts;
+    return restart_ranked(g, K, sup_ptr, sup_idx, sup_val, start, d, n_iter, end, cand_type);
 }
 
 int32_t recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx, const double *sup_val,
@@ -401,13 +295,14 @@ int32_t recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t *sup
                                      int32_t top_n, const int64_t *test_ptr, const int64_t *test_ids, int64_t *n_hits,
                                      double *sum_precision, int64_t *list_len)
 {
-    static const char *const who = "rwr_recommend_restart_eval_batch";
     EvalEnd ev;
     ev.test_ptr = test_ptr, ev.test_ids = test_ids, ev.top_n = top_n;
     ev.n_hits = n_hits, ev.sum_precision = sum_precision, ev.list_len = list_len;
-    Ranked rk{set_ptr, set_idx, top_n, nullptr, nullptr, nullptr, {}, {}, {}, {}, &ev, who};
-    StreamsIdle idle{g};
-    return restart_batch(g, K, sup_ptr, sup_idx, sup_val, start, d, RWR_RUN_ITERATIONS, (double)n_iter, nullptr, nullptr, &rk, who);
+    RankedEnd end;                                              // the ITEM rows, the sets' raw LIKE links, records
+    end.who = "rwr_recommend_restart_eval_batch";
+    end.set_ptr = set_ptr, end.set_idx = set_idx, end.mask = 1u << RWR_EDGE_LIKE;
+    end.ev = &ev;
+    return restart_ranked(g, K, sup_ptr, sup_idx, sup_val, start, d, n_iter, end);
 }
 
 }  // namespace rwr

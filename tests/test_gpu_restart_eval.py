@@ -13,7 +13,7 @@ import pytest
 
 from oracle.rwr_oracle import evaluate
 from tests import graphgen as gg
-from tests.test_gpu_restart_rank import D, EXACT_MAX, Case, _liked, _ranked, _single_row, _with_hub, bits
+from tests.test_gpu_restart_rank import D, EXACT_MAX, Case, OddTypes, _liked, _ranked, _single_row, _with_hub, bits
 
 pytestmark = pytest.mark.gpu
 
@@ -184,6 +184,22 @@ def test_top_n_on_and_one_past_a_hit(big):
     _check(below, c.want_eval(K, T, p, True, shift), ("top_n = position", p))
     _check(at, c.want_eval(K, T, p + 1, True, shift), ("top_n = position + 1", p))
     assert below[0][k] == 3 and at[0][k] == 4 and below[2][k] == p and at[2][k] == p + 1
+
+
+def test_unnamed_link_types_are_not_excluded(amd):
+    """tests/test_gpu_restart_rank.py's case through the evaluating end: every vector's test set is the five targets of u's
+    links of types LIKE, 2, 7, 8 and 255; where u is in the set four of them are hits, at the positions of the host's list"""
+    c = OddTypes(amd)
+    try:
+        tests = [c.g["node_id"][c.targets]] * 3
+        for top_n in (0, 10):
+            got = amd.Recommender(c.H).RecommendationRestartEvalBatch(c.restarts, c.starts, D, c.T, tests, topN=top_n, exclude=c.sets)
+            _check(got, [_want(c.lists[k][0], tests[k], top_n) for k in range(3)], ("odd types", top_n))
+            if top_n == 0:                                          # the whole lists: the LIKE target alone is missing
+                assert got[0].tolist() == [4, 5, 4]
+                assert got[2].tolist() == [c.n_items - 1, c.n_items, len(c.lists[2][0])]
+    finally:
+        c.close()
 
 
 def test_weighted_graph(amd):

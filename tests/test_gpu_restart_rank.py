@@ -299,6 +299,61 @@ def test_hub_user_spans_two_segments(amd):
         c.close()
 
 
+class OddTypes:
+    """A graph of 30 nodes whose user `u` has exactly five raw links, of types LIKE, 2, 7, 8 and 255, to five different items
+    (the exclusion's mask has a bit for 1, 2 and 7, none for 8 and 255); three vectors with u in the sets of the first and the
+    last; their rows from rwr_model_run_restart_batch on a handle of tile width 2: two tiles, one padding slot."""
+    TYPES = (gg.EDGE_LIKE, 2, 7, 8, 255)
+    T = 4
+
+    def __init__(self, amd):
+        g = gg.random_graph(36, n_users=10, n_items=20, n_likes=70, uniform=True)
+        deg = np.diff(g["rowptr"])
+        u = next(i for i in range(10) if deg[i] >= 5)
+        lo, hi = int(g["rowptr"][u]), int(g["rowptr"][u + 1])
+        keep = np.r_[0:lo + 5, hi:len(g["dst"])]                    # u keeps its first five links
+        rowptr = g["rowptr"].copy()
+        rowptr[u + 1:] -= hi - (lo + 5)
+        etype = g["etype"][keep].copy()
+        etype[lo:lo + 5] = self.TYPES
+        self.g = dict(g, rowptr=rowptr, dst=g["dst"][keep], etype=etype, w=g["w"][keep])
+        self.u, self.targets = u, self.g["dst"][lo:lo + 5].astype(np.int64)
+        assert len(set(self.targets.tolist())) == 5 and (self.g["node_type"][self.targets] == gg.NODE_ITEM).all()
+        self.n_items = 20
+        # a second user with links, none of them to u's five items: its set membership hides none of them
+        v = next(i for i in range(10) if i != u and deg[i] > 0 and not np.isin(_liked(self.g, [i]), self.targets).any())
+        self.restarts = [{u: 1.0}, {v: 1.0}, {u: 0.5, v: 0.5}]
+        self.starts = np.array([u, -1, v], dtype=np.int32)
+        self.sets = [np.array([u], dtype=np.int32), np.zeros(0, dtype=np.int32), np.array([v, u], dtype=np.int32)]
+        self.H = amd.Graph.from_flat(**self.g, tile_seeds=2, tile_group=1)
+        self.H.buildGraph()
+        self.rows, _ = amd.Model.RunRestartBatch(self.H, D, self.restarts, self.starts, self.T)
+        self.lists = [_ranked(self.g, self.rows[k], self.sets[k]) for k in range(3)]
+
+    def close(self):
+        self.H.close()
+
+
+def test_unnamed_link_types_are_not_excluded(amd):
+    """the untyped end runs the typed exclusion kernel with the mask 1 << LIKE: of a member's links of types LIKE, 2, 7, 8 and
+    255 only the LIKE target leaves the list (8 and 255 have no bit in the mask: a shift by them must not happen)"""
+    c = OddTypes(amd)
+    try:
+        ids_of = c.g["node_id"][c.targets]
+        for top_n in (c.n_items + 5, 1025):                         # the select and the sort
+            ids, sc, cnt = amd.Recommender(c.H).RecommendationRestartBatch(c.restarts, c.starts, D, c.T, top_n, exclude=c.sets)
+            _check((ids, sc, cnt), _packed(c.lists, top_n), ("odd types", top_n))
+            assert cnt.tolist() == [c.n_items - 1, c.n_items, len(c.lists[2][0])]
+            for k in (0, 2):
+                got = dict(zip(ids[k, :cnt[k]].tolist(), bits(sc[k, :cnt[k]]).tolist()))
+                assert int(ids_of[0]) not in got, (k, "the LIKE target is in the list")
+                for t, i in zip(c.targets[1:], ids_of[1:]):
+                    assert got.get(int(i)) == int(bits(c.rows[k, t:t + 1])[0]), (k, int(t))
+            assert set(ids_of.tolist()) <= set(ids[1, :cnt[1]].tolist())   # the set without u excludes none of them
+    finally:
+        c.close()
+
+
 def test_against_the_python_oracle(small):
     """the literal oracle's Model with the sparse-restart idiom of tests/test_gpu_restart_batch.py, and a Python sort"""
     from tests.test_gpu_restart_batch import _oracle_graph, _oracle_model

@@ -203,6 +203,30 @@ def test_one_seed_mirror(amd, mixed):
     G.close()
 
 
+@pytest.mark.parametrize("which", ["weighted", "value_free"])
+def test_own_rows_with_a_padding_slot_and_a_repeated_seed(amd, mixed, unit, which):
+    """exclude_self with an empty mask -- no link is looked at, the seeds' own rows are the whole exclusion -- at K = 3 on
+    tiles of two slots (two tiles, one padding slot), two batch positions holding the same seed.  The rows are
+    rwr_model_run_batch's, ranked here."""
+    g, _ = mixed if which == "weighted" else unit
+    G = built(amd, g, tile_seeds=2, tile_group=1)
+    seeds, T, top_n = [5, 9, 5], 6, int((g["node_type"] == gg.NODE_USER).sum()) + 3
+    rows, _ = amd.Model.RunBatch(G, po.widen_float(D), seeds, T)
+    ids, sc, cnt = np.zeros((3, top_n), dtype=np.int64), np.zeros((3, top_n)), np.zeros(3, dtype=np.int32)
+    for k, s in enumerate(seeds):
+        L = expected_list(g, rows[k], s, gg.NODE_USER, set(), True)
+        assert g["node_type"][s] == gg.NODE_USER and len(L) == top_n - 4   # every user but the seed
+        cnt[k], ids[k, :len(L)], sc[k, :len(L)] = len(L), [c[0] for c in L], [c[1] for c in L]
+    got = typed(amd, G, seeds, T, top_n, gg.NODE_USER, (), True)
+    check(got, (ids, sc, cnt), ("own rows", which))
+    for k, s in enumerate(seeds):
+        mine = got[0][k, :got[2][k]].tolist()
+        assert int(g["node_id"][s]) not in mine, (k, "the seed is in its own list")
+        other = 9 if s == 5 else 5                                  # ... and another slot's seed is not marked in this one
+        assert int(g["node_id"][other]) in mine, (k, "another position's seed is missing")
+    G.close()
+
+
 # ---- 3. boundaries of the new kernels -----------------------------------------------------------------------------------------
 
 def test_candidate_counts_and_top_n(amd, mixed):
