@@ -4,7 +4,7 @@
 // Model.deliverRanks (Model.cs:76-100) adds into nextRank[seed], for i ascending: i's links into the seed
 // (Model.cs:85-88), then the restart addend  rank[i] - rw  (Model.cs:91-93) or  rank[i]  (dangling,
 // Model.cs:96-97).  That is an n-term fp64 chain  s <- fl(s + a)  per seed; folded literally it runs at the
-// dependent-add latency (k_seed_chain_roles in iterate.hip: ~20 cycles per row, 50 ms per step on a 6 M-node
+// dependent-add latency (k_seed_chain_roles in seed_chain.hip:~20 cycles per row, 50 ms per step on a 6 M-node
 // graph), which is hidden behind the SpMM of a large batch but IS the run time of a single-seed call.
 //
 // Binade scan.  All addends are >= 0 (0 <= d <= 1, ranks >= 0), so s only grows.  While s stays inside one
@@ -30,8 +30,8 @@
 //                        wave, and the carry goes on behind it; writes Y[seed]
 // once per batch: k_cs_links (where each block's share of the seed's in-link list starts).
 // Per-(seed, block) cells are laid out [slot][block] so that a window is one coalesced load.
-#include "engine.h"
 #include "pf.h"
+#include "seed_row.h"
 
 #include <cstdlib>
 
@@ -220,11 +220,6 @@ __global__ __launch_bounds__(64) void k_cs_plan(int nchunks, const int32_t *__re
     }
 }
 
-__device__ __forceinline__ double cs_from_m(int eb, long long M)
-{
-    return __longlong_as_double((long long)(((unsigned long long)eb << 52) | ((unsigned long long)M - CS_HID)));
-}
-
 // One wave redoes block c of seed kk exactly.  The block's CH rows are dealt to the lanes in runs of R = CH / 64
 // consecutive rows.  Under the CURRENT binade every lane composes its run's parity functions (a row's links into the
 // seed first, then its restart addend), one wave scan composes the runs, and the block is accepted up to the first
@@ -331,11 +326,11 @@ __device__ double cs_redo_block(double s, int32_t n, int nchunks, int c, int til
             const long long M = m + ((m & 1) ? f.d1 : f.d0);
             const unsigned long long cross = __ballot(M >= CS_BIG);
             if (!cross) {
-                s = cs_from_m(eb, __shfl(M, WAVE - 1, WAVE));
+                s = pf_from_m(eb, __shfl(M, WAVE - 1, WAVE));
                 break;
             }
             L = __builtin_ctzll(cross);
-            if (L > 0) s = cs_from_m(eb, __shfl(M, L - 1, WAVE));   // the runs before the crossing (lanes < start hold m itself)
+            if (L > 0) s = pf_from_m(eb, __shfl(M, L - 1, WAVE));   // the runs before the crossing (lanes < start hold m itself)
         }
         double t = s;
         if (lane == L) {
@@ -430,14 +425,14 @@ __global__ __launch_bounds__(64) void k_cs_carry(int32_t n, int nchunks, const u
         const long long M = m + ((m & 1) ? f.d1 : f.d0);
         const unsigned long long bad = __ballot(nz && (!normal || ep != eb || M >= CS_BIG));
         if (!bad) {
-            if (normal) s = cs_from_m(eb, __shfl(M, WAVE - 1, WAVE));
+            if (normal) s = pf_from_m(eb, __shfl(M, WAVE - 1, WAVE));
             c += WAVE;
             done = 0;
             ap = apn; ep = epn; f0 = f0n; f1 = f1n;
             continue;
         }
         const int L = __builtin_ctzll(bad);
-        if (L > 0 && normal) s = cs_from_m(eb, __shfl(M, L - 1, WAVE));   // the blocks before it (carried ones are identities)
+        if (L > 0 && normal) s = pf_from_m(eb, __shfl(M, L - 1, WAVE));   // the blocks before it (carried ones are identities)
         s = cs_redo_block<G>(s, n, nchunks, c + L, tile, k, dangling, X, seeds, c1, in_ptr, in_src, evoff, evterm, lnk);
         ++redo;
         done = L + 1;
@@ -885,7 +880,7 @@ __global__ __launch_bounds__(256, 6) void k_cs_block1(int32_t n, int nchunks, co
     }
     // two crossings (the sum more than doubles inside the block: the ranks are still concentrated): the second run is located
     // the same way, under e + 1, from the approximate sum behind the first run
-    double s1 = cs_from_m(epre, mt + before.d0);
+    double s1 = pf_from_m(epre, mt + before.d0);
 #pragma unroll
     for (int q = 0; q < CS_RUN_ADDENDS; ++q) s1 += run1[q];
     const unsigned long long s1b = (unsigned long long)__double_as_longlong(s1);
@@ -995,14 +990,14 @@ __global__ __launch_bounds__(64) void k_cs_carry1(int32_t n, int nchunks, const 
         const long long M = m + ((m & 1) ? f.d1 : f.d0);
         const unsigned long long bad = __ballot(nz && (kind != CS_PLAIN || !normal || ep != eb || M >= CS_BIG));
         if (!bad) {
-            if (normal) s = cs_from_m(eb, __shfl(M, WAVE - 1, WAVE));
+            if (normal) s = pf_from_m(eb, __shfl(M, WAVE - 1, WAVE));
             c += WAVE;
             done = 0;
             cur = nxt;
             continue;
         }
         const int L = __builtin_ctzll(bad);
-        if (L > 0 && normal) s = cs_from_m(eb, __shfl(M, L - 1, WAVE));   // the blocks before it (carried ones are identities)
+        if (L > 0 && normal) s = pf_from_m(eb, __shfl(M, L - 1, WAVE));   // the blocks before it (carried ones are identities)
         // block c + L: its cells, wave-uniform
         const int kL = __shfl(kind, L, WAVE), eL = __shfl(ep, L, WAVE);
         b = (unsigned long long)__double_as_longlong(s);
@@ -1027,7 +1022,7 @@ __global__ __launch_bounds__(64) void k_cs_carry1(int32_t n, int nchunks, const 
             m = (long long)((b & CS_FRAC) | CS_HID);
             const long long M1 = m + ((m & 1) ? before.d1 : before.d0);
             if (M1 < CS_BIG) {                            // still inside the binade in front of the run
-                double t = add_run(cs_from_m(eb, M1), cur.a01, cur.a23, cur.a45, cur.a67);
+                double t = add_run(pf_from_m(eb, M1), cur.a01, cur.a23, cur.a45, cur.a67);
                 unsigned long long tb = (unsigned long long)__double_as_longlong(t);
                 if ((int)((tb >> 52) & 0x7ff) == eb + 1) {
                     const PF mid = pf_at(cur.af);
@@ -1035,17 +1030,17 @@ __global__ __launch_bounds__(64) void k_cs_carry1(int32_t n, int nchunks, const 
                     const long long M2 = m2 + ((m2 & 1) ? mid.d1 : mid.d0);
                     if (M2 < CS_BIG) {
                         if (kL == CS_SPLIT) {
-                            s = cs_from_m(eb + 1, M2);
+                            s = pf_from_m(eb + 1, M2);
                             handled = true;
                         } else {
-                            t = add_run(cs_from_m(eb + 1, M2), cur.b01, cur.b23, cur.b45, cur.b67);
+                            t = add_run(pf_from_m(eb + 1, M2), cur.b01, cur.b23, cur.b45, cur.b67);
                             tb = (unsigned long long)__double_as_longlong(t);
                             if ((int)((tb >> 52) & 0x7ff) == eb + 2) {
                                 const PF aft = pf_at(cur.bf);
                                 const long long m3 = (long long)((tb & CS_FRAC) | CS_HID);
                                 const long long M3 = m3 + ((m3 & 1) ? aft.d1 : aft.d0);
                                 if (M3 < CS_BIG) {
-                                    s = cs_from_m(eb + 2, M3);
+                                    s = pf_from_m(eb + 2, M3);
                                     handled = true;
                                 }
                             }
@@ -1094,53 +1089,148 @@ __global__ __launch_bounds__(64) void k_cs_carry1(int32_t n, int nchunks, const 
 static inline int cs_block_elems(int G) { return G == 1 ? CsGeom<1>::E : (G >= 16 ? CsGeom<16>::E : CsGeom<2>::E); }
 static inline int cs_nchunks(int32_t n, int G) { return (int)(((int64_t)n * G + cs_block_elems(G) - 1) / cs_block_elems(G)); }
 
-#define CS_DISPATCH_G(G, CALL)                            \
-    switch (G) {                                          \
-        case 1: { constexpr int GG = 1; CALL; } break;    \
-        case 2: { constexpr int GG = 2; CALL; } break;    \
-        case 4: { constexpr int GG = 4; CALL; } break;    \
-        case 8: { constexpr int GG = 8; CALL; } break;    \
-        case 16: { constexpr int GG = 16; CALL; } break;  \
-        case 32: { constexpr int GG = 32; CALL; } break;  \
-        default: { constexpr int GG = 64; CALL; } break;  \
-    }
-
-// once per tile group: buffers + the per-block offsets into each seed's in-link list
-int32_t chain_scan_prepare(rwr_graph *g, int G, int tg, const int32_t *d_seeds, hipStream_t s)
+// The scan's environment values, read once per process (the RWR_TUNE_ENV ones only by the experiments build)
+struct ScanKnobs {
+    bool split = true;     // RWR_SCAN_SPLIT: a single seed per tile takes the block1 / carry1 form
+    int direct_max = 8;    // RWR_SCAN_DIRECT_BLOCKS: up to so many blocks the carry walks them itself
+    int own_max = 48;      // RWR_SCAN_OWN_SUMS_BLOCKS: up to so many blocks k_cs_block1 forms the approximate sums itself
+    int carry_dbg = 0;     // RWR_X_CARRY_DBG (experiments build): the carry prints what it did with its blocks
+};
+static ScanKnobs read_scan_knobs()
 {
-    const int nchunks = cs_nchunks(g->n, G);
-    const size_t cells = (size_t)tg * nchunks * G;
+    ScanKnobs v;
+    const char *e;
+    if ((e = RWR_TUNE_ENV("RWR_SCAN_SPLIT"))) v.split = atoi(e) != 0;
+    if ((e = RWR_TUNE_ENV("RWR_SCAN_DIRECT_BLOCKS"))) v.direct_max = atoi(e);
+    if ((e = RWR_TUNE_ENV("RWR_SCAN_OWN_SUMS_BLOCKS"))) v.own_max = atoi(e);
+#ifdef RWR_EXPERIMENTS
+    if ((e = getenv("RWR_X_CARRY_DBG"))) v.carry_dbg = atoi(e);
+#endif
+    return v;
+}
+static const ScanKnobs &scan_knobs() { static const ScanKnobs k = read_scan_knobs(); return k; }
+
+// single seed per tile: the chain gathers the link terms itself on value-free graphs (no k_seed_terms launch) and writes the
+// seed row's z for the next step (no k_seed_z launch)
+bool chain_scan_self_contained(int G) { return G == 1 && scan_knobs().split; }
+
+// The scan workspace for `slots` seed slots of tile width G: the one place that sizes it.  Its users share the buffers and
+// differ in geometry -- a tile group's steps and the column sums of a batch of Models or restart vectors (tg * G slots),
+// Model.run's convergence sum (G = 1, one slot) -- so every prepare grows what its call finds too small.  Per (slot, block)
+// cell: approximate sum, predicted exponent, parity-function pair; single seed per tile (block1 / carry1): the cell's side
+// words and one scratch row per slot; once per handle: the redo counter.
+static int32_t cs_workspace_ensure(rwr_graph *g, int G, size_t slots, hipStream_t s)
+{
+    const size_t cells = slots * (size_t)cs_nchunks(g->n, G);
     RWR_TRY(g->cs_approx.ensure(cells));
     RWR_TRY(g->cs_e.ensure(cells));
     RWR_TRY(g->cs_d0.ensure(cells));
     RWR_TRY(g->cs_d1.ensure(cells));
     if (G == 1) RWR_TRY(g->cs_side.ensure(cells * CS_SIDE_WORDS));
-    if (G == 1) RWR_TRY(g->cs_mx.ensure((size_t)tg * (size_t)(CsGeom<1>::CH + CS_MX_LINKS)));
-    RWR_TRY(g->cs_lnk.ensure((size_t)tg * G * (size_t)(nchunks + 1)));
+    if (G == 1) RWR_TRY(g->cs_mx.ensure(slots * (size_t)(CsGeom<1>::CH + CS_MX_LINKS)));
     if (!g->cs_redo.p) {
         RWR_TRY(g->cs_redo.alloc(1));
         RWR_HIP(hipMemsetAsync(g->cs_redo.p, 0, sizeof(unsigned long long), s));
     }
-    hipLaunchKernelGGL(k_cs_links, dim3(cdiv((size_t)nchunks + 1, 256), (unsigned)(tg * G)), dim3(256), 0, s, nchunks,
-                       cs_block_elems(G) / G, g->in_ptr.p, g->in_src.p, d_seeds, g->cs_lnk.p);
-    RWR_HIP(hipGetLastError());
     return RWR_OK;
+}
+
+// One chain per slot over the rows of X, three launch forms.  `self` (single seed per tile, chain_scan_self_contained): the link
+// terms are gathered from the z matrix when the caller hands it over (evoff = nullptr tells the kernels) and the carry writes
+// the seed row's next z.
+struct ScanCall {
+    rwr_graph *g;
+    int tg, nchunks;
+    const double *X;
+    double *Y;
+    const int32_t *seeds;
+    const int64_t *evoff;
+    const double *evterm;
+    double c1;
+    uint32_t *nz_out;
+    const int32_t *lnk;
+    hipStream_t s;
+    double *zout, *sums;
+    dim3 grid() const { return dim3((unsigned)nchunks, (unsigned)tg); }
+};
+// direct walk: the carry alone, which redoes every block itself
+static void cs_launch_direct(const ScanCall &c, int G)
+{
+    rwr_graph *g = c.g;
+    RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_cs_carry<GG>, dim3((unsigned)(c.tg * G)), dim3(64), 0, c.s, g->n, c.nchunks, g->dangling.p, c.X,
+                                         c.Y, c.seeds, c.c1, g->in_ptr.p, g->in_src.p, c.evoff, c.evterm, c.lnk, g->cs_approx.p,
+                                         g->cs_e.p, g->cs_d0.p, g->cs_d1.p, c.nz_out, g->cs_redo.p, 1, c.zout, g->w_src.p, c.sums));
+}
+// single seed: prediction, split and exact-start blocks in one pass (k_cs_block1, behind the plain block sums where it does not
+// form them itself); the carry applies them from registers
+static void cs_launch_single(const ScanCall &c)
+{
+    rwr_graph *g = c.g;
+    const int own_sums = c.nchunks <= scan_knobs().own_max ? 1 : 0;
+    if (!own_sums)
+        hipLaunchKernelGGL((k_cs_block<1, false>), c.grid(), dim3(256), 0, c.s, g->n, c.nchunks, g->dangling.p, c.X, c.seeds, c.c1,
+                           g->in_ptr.p, g->in_src.p, c.evoff, c.evterm, c.lnk, (const int32_t *)nullptr, g->cs_approx.p,
+                           (long long *)nullptr, (long long *)nullptr);
+    hipLaunchKernelGGL(k_cs_block1, c.grid(), dim3(256), 0, c.s, g->n, c.nchunks, g->dangling.p, c.X, c.seeds, c.c1, g->in_ptr.p,
+                       g->in_src.p, c.evoff, c.evterm, c.lnk, g->cs_approx.p, g->cs_e.p, g->cs_d0.p, g->cs_d1.p, g->cs_side.p, own_sums,
+                       g->cs_mx.p);
+    hipLaunchKernelGGL(k_cs_carry1, dim3((unsigned)c.tg), dim3(64), 0, c.s, g->n, c.nchunks, g->dangling.p, c.X, c.Y, c.seeds, c.c1,
+                       g->in_ptr.p, g->in_src.p, c.evoff, c.evterm, c.lnk, g->cs_approx.p, g->cs_e.p, g->cs_d0.p, g->cs_d1.p,
+                       g->cs_side.p, c.nz_out, g->cs_redo.p, c.zout, g->w_src.p, c.sums);
+}
+// G-wide: block sums, predicted binades, block functions, carry (the pipeline of the file header)
+static void cs_launch_wide(const ScanCall &c, int G)
+{
+    rwr_graph *g = c.g;
+    RWR_DISPATCH_G(G, hipLaunchKernelGGL((k_cs_block<GG, false>), c.grid(), dim3(256), 0, c.s, g->n, c.nchunks, g->dangling.p, c.X,
+                                         c.seeds, c.c1, g->in_ptr.p, g->in_src.p, c.evoff, c.evterm, c.lnk,
+                                         (const int32_t *)nullptr, g->cs_approx.p, (long long *)nullptr, (long long *)nullptr));
+    hipLaunchKernelGGL(k_cs_plan, dim3((unsigned)(c.tg * G)), dim3(64), 0, c.s, c.nchunks, c.seeds, g->cs_approx.p, g->cs_e.p);
+    RWR_DISPATCH_G(G, hipLaunchKernelGGL((k_cs_block<GG, true>), c.grid(), dim3(256), 0, c.s, g->n, c.nchunks, g->dangling.p, c.X,
+                                         c.seeds, c.c1, g->in_ptr.p, g->in_src.p, c.evoff, c.evterm, c.lnk, g->cs_e.p,
+                                         (double *)nullptr, g->cs_d0.p, g->cs_d1.p));
+    RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_cs_carry<GG>, dim3((unsigned)(c.tg * G)), dim3(64), 0, c.s, g->n, c.nchunks, g->dangling.p, c.X,
+                                         c.Y, c.seeds, c.c1, g->in_ptr.p, g->in_src.p, c.evoff, c.evterm, c.lnk, g->cs_approx.p,
+                                         g->cs_e.p, g->cs_d0.p, g->cs_d1.p, c.nz_out, g->cs_redo.p, 0, (double *)nullptr,
+                                         (const double *)nullptr, c.sums));
 }
 
 // one step's seed-row chain for a tile group (the link terms d_evterm must already be on the stream)
 static int32_t chain_scan_launch(rwr_graph *g, int G, int tg, const double *X, double *Y, const int32_t *d_seeds,
                                  const int64_t *d_evoff, double c1, uint32_t *nz_out, const int32_t *lnk, hipStream_t s,
-                                 const double *zterms = nullptr, double *zout = nullptr, double *sums = nullptr);
-
-static bool cs_split_enabled()
+                                 const double *zterms = nullptr, double *zout = nullptr, double *sums = nullptr)
 {
-    static const int split_env = [] { const char *e = RWR_TUNE_ENV("RWR_SCAN_SPLIT"); return e ? atoi(e) : 1; }();
-    return split_env != 0;
+    const bool self = chain_scan_self_contained(G), own_terms = self && zterms;
+#ifdef RWR_EXPERIMENTS
+    static const int dbg_once = [] {
+        const int v = scan_knobs().carry_dbg;
+        if (v) (void)hipMemcpyToSymbol(HIP_SYMBOL(cs_carry_dbg), &v, sizeof(v));
+        return v;
+    }();
+    (void)dbg_once;
+#endif
+    const ScanCall c{g, tg, cs_nchunks(g->n, G), X, Y, d_seeds, own_terms ? nullptr : d_evoff, own_terms ? zterms : g->d_evterm.p,
+                     c1, nz_out, lnk, s, self ? zout : nullptr, sums};
+    // (a single seed takes the direct walk for one block only: with the crossings predicted the two-launch form costs ~20 us per
+    //  step whatever the blocks hold, the direct walk 8-9 us per redone block -- 7 500 nodes: 1.83 -> 0.58 ms per call)
+    if (c.nchunks <= (self ? 1 : scan_knobs().direct_max)) cs_launch_direct(c, G);
+    else if (self) cs_launch_single(c);
+    else cs_launch_wide(c, G);
+    RWR_HIP(hipGetLastError());
+    return RWR_OK;
 }
-// single seed per tile: the chain gathers the link terms itself on value-free graphs (no k_seed_terms launch) and writes the
-// seed row's z for the next step (no k_seed_z launch)
-bool chain_scan_self_contained(int G) { return G == 1 && cs_split_enabled(); }
 
+// once per tile group: the workspace + the per-block offsets into each seed's in-link list
+int32_t chain_scan_prepare(rwr_graph *g, int G, int tg, const int32_t *d_seeds, hipStream_t s)
+{
+    const int nchunks = cs_nchunks(g->n, G);
+    RWR_TRY(cs_workspace_ensure(g, G, (size_t)tg * G, s));
+    RWR_TRY(g->cs_lnk.ensure((size_t)tg * G * (size_t)(nchunks + 1)));
+    hipLaunchKernelGGL(k_cs_links, dim3(cdiv((size_t)nchunks + 1, 256), (unsigned)(tg * G)), dim3(256), 0, s, nchunks,
+                       cs_block_elems(G) / G, g->in_ptr.p, g->in_src.p, d_seeds, g->cs_lnk.p);
+    RWR_HIP(hipGetLastError());
+    return RWR_OK;
+}
 int32_t chain_scan_step(rwr_graph *g, int G, int tg, const double *X, double *Y, const int32_t *d_seeds,
                         const int64_t *d_evoff, double c1, uint32_t *nz_out, hipStream_t s, const double *zterms, double *zout)
 {
@@ -1149,49 +1239,16 @@ int32_t chain_scan_step(rwr_graph *g, int G, int tg, const double *X, double *Y,
 
 // The reference's checkConvergence (Model.cs:110-115) is the same kind of chain: diff += |rank[i] - nextRank[i]| over
 // all nodes in order, non-negative addends.  The scan machinery reproduces that sequential fp64 sum bit for bit:
-// D holds the addends; with (1-d) := 0 a row's addend is D[i] - 0*D[i] = D[i], the link table is all zero (no in-link
-// terms) and the "seed" slot 0 only names where the sum is written (*out).
-int32_t chain_scan_sum(rwr_graph *g, const double *D, double *out, hipStream_t s)
-{
-    const int nchunks = cs_nchunks(g->n, 1);
-    const size_t cells = (size_t)nchunks;
-    RWR_TRY(g->cs_approx.ensure(cells));
-    RWR_TRY(g->cs_e.ensure(cells));
-    RWR_TRY(g->cs_d0.ensure(cells));
-    RWR_TRY(g->cs_d1.ensure(cells));
-    RWR_TRY(g->cs_side.ensure(cells * CS_SIDE_WORDS));
-    RWR_TRY(g->cs_mx.ensure((size_t)(CsGeom<1>::CH + CS_MX_LINKS)));
-    RWR_TRY(g->cs_lnk0.ensure((size_t)nchunks + 2));
-    if (!g->cs_redo.p) {
-        RWR_TRY(g->cs_redo.alloc(1));
-        RWR_HIP(hipMemsetAsync(g->cs_redo.p, 0, sizeof(unsigned long long), s));
-    }
-    // words [0, nchunks]: the all-zero link table; word nchunks + 1: the slot's "seed" (node 0)
-    RWR_HIP(hipMemsetAsync(g->cs_lnk0.p, 0, ((size_t)nchunks + 2) * sizeof(int32_t), s));
-    RWR_TRY(g->d_evoff.ensure(2));
-    return chain_scan_launch(g, 1, 1, D, out, g->cs_lnk0.p + nchunks + 1, g->d_evoff.p, 0.0, nullptr, g->cs_lnk0.p, s);
-}
-
-// The same, G columns per tile and tg tiles at once (K Models in one call, rwr_model_run_batch): D is a tile group's
-// [tile][n][G] matrix of |rank - nextRank|, every slot's "seed" is node 0 and its link table is all zero, so that column k
-// of tile t is summed in row order by slot t * G + k; the carry writes the sum to sums[t * G + k] instead of a row of Y.
-// cs_lnk0 = [tg * G][nchunks + 1] zero link counts, then tg * G zero seeds.
+// D holds the addends; with (1-d) := 0 a row's addend is D[i] - 0*D[i] = D[i], every slot's "seed" is node 0 and only names
+// where its sum is written, and its link table is all zero (no in-link terms).
+// cs_lnk0 = [tg * G][nchunks + 1] zero link counts, then tg * G zero seeds: G columns per tile and tg tiles at once (K Models
+// in one call, rwr_model_run_batch) -- D is then a tile group's [tile][n][G] matrix of |rank - nextRank|, column k of tile t is
+// summed in row order by slot t * G + k, and the carry writes the sum to sums[t * G + k] instead of a row of Y.
 int32_t chain_scan_sum_cols_prepare(rwr_graph *g, int G, int tg, hipStream_t s)
 {
-    const int nchunks = cs_nchunks(g->n, G);
-    const size_t slots = (size_t)tg * G, cells = slots * nchunks;
-    RWR_TRY(g->cs_approx.ensure(cells));
-    RWR_TRY(g->cs_e.ensure(cells));
-    RWR_TRY(g->cs_d0.ensure(cells));
-    RWR_TRY(g->cs_d1.ensure(cells));
-    if (G == 1) RWR_TRY(g->cs_side.ensure(cells * CS_SIDE_WORDS));
-    if (G == 1) RWR_TRY(g->cs_mx.ensure((size_t)tg * (size_t)(CsGeom<1>::CH + CS_MX_LINKS)));
-    const size_t words = slots * ((size_t)nchunks + 1) + slots;
+    const size_t slots = (size_t)tg * G, words = slots * ((size_t)cs_nchunks(g->n, G) + 1) + slots;
+    RWR_TRY(cs_workspace_ensure(g, G, slots, s));
     RWR_TRY(g->cs_lnk0.ensure(words));
-    if (!g->cs_redo.p) {
-        RWR_TRY(g->cs_redo.alloc(1));
-        RWR_HIP(hipMemsetAsync(g->cs_redo.p, 0, sizeof(unsigned long long), s));
-    }
     RWR_HIP(hipMemsetAsync(g->cs_lnk0.p, 0, words * sizeof(int32_t), s));
     return RWR_OK;
 }
@@ -1201,67 +1258,12 @@ int32_t chain_scan_sum_cols(rwr_graph *g, int G, int tg, const double *D, const 
     const int32_t *zero_seeds = g->cs_lnk0.p + slots * ((size_t)cs_nchunks(g->n, G) + 1);
     return chain_scan_launch(g, G, tg, D, nullptr, zero_seeds, evoff, 0.0, nullptr, g->cs_lnk0.p, s, nullptr, nullptr, sums);
 }
-
-static int32_t chain_scan_launch(rwr_graph *g, int G, int tg, const double *X, double *Y, const int32_t *d_seeds,
-                                 const int64_t *d_evoff, double c1, uint32_t *nz_out, const int32_t *lnk, hipStream_t s,
-                                 const double *zterms, double *zout, double *sums)
+// One vector (Model.run): one slot at G = 1, the sum written to *out as the "row" of node 0
+int32_t chain_scan_sum(rwr_graph *g, const double *D, double *out, hipStream_t s)
 {
-    const int nchunks = cs_nchunks(g->n, G);
-    const dim3 grid((unsigned)nchunks, (unsigned)tg);
-    static const int direct_max = [] { const char *e = RWR_TUNE_ENV("RWR_SCAN_DIRECT_BLOCKS"); return e ? atoi(e) : 8; }();
-    // single seed per tile: link terms gathered from the z matrix when the caller hands it over (evoff = nullptr tells the
-    // kernels), the seed row's next z written by the carry
-    const bool self = chain_scan_self_contained(G);
-#ifdef RWR_EXPERIMENTS
-    static const int dbg_once = [] {
-        const char *e = getenv("RWR_X_CARRY_DBG");
-        const int v = e ? atoi(e) : 0;
-        if (v) (void)hipMemcpyToSymbol(HIP_SYMBOL(cs_carry_dbg), &v, sizeof(v));
-        return v;
-    }();
-    (void)dbg_once;
-#endif
-    const int64_t *evo = (self && zterms) ? nullptr : d_evoff;
-    const double *evt = (self && zterms) ? zterms : g->d_evterm.p;
-    // (a single seed takes the direct walk for one block only: with the crossings predicted the two-launch form costs ~20 us per
-    //  step whatever the blocks hold, the direct walk 8-9 us per redone block -- 7 500 nodes: 1.83 -> 0.58 ms per call)
-    if (nchunks <= (self ? 1 : direct_max)) {
-        CS_DISPATCH_G(G, hipLaunchKernelGGL(k_cs_carry<GG>, dim3((unsigned)(tg * G)), dim3(64), 0, s, g->n, nchunks, g->dangling.p, X, Y,
-                                            d_seeds, c1, g->in_ptr.p, g->in_src.p, evo, evt, lnk,
-                                            g->cs_approx.p, g->cs_e.p, g->cs_d0.p, g->cs_d1.p, nz_out, g->cs_redo.p, 1,
-                                            self ? zout : (double *)nullptr, g->w_src.p, sums));
-        RWR_HIP(hipGetLastError());
-        return RWR_OK;
-    }
-    if (self) {
-        // prediction, split and exact-start blocks in one pass; the carry applies them from registers
-        static const int own_max = [] { const char *e = RWR_TUNE_ENV("RWR_SCAN_OWN_SUMS_BLOCKS"); return e ? atoi(e) : 48; }();
-        const int own_sums = nchunks <= own_max ? 1 : 0;
-        if (!own_sums)
-            hipLaunchKernelGGL((k_cs_block<1, false>), grid, dim3(256), 0, s, g->n, nchunks, g->dangling.p, X, d_seeds, c1, g->in_ptr.p,
-                               g->in_src.p, evo, evt, lnk, (const int32_t *)nullptr, g->cs_approx.p, (long long *)nullptr,
-                               (long long *)nullptr);
-        hipLaunchKernelGGL(k_cs_block1, grid, dim3(256), 0, s, g->n, nchunks, g->dangling.p, X, d_seeds, c1, g->in_ptr.p, g->in_src.p,
-                           evo, evt, lnk, g->cs_approx.p, g->cs_e.p, g->cs_d0.p, g->cs_d1.p, g->cs_side.p, own_sums, g->cs_mx.p);
-        hipLaunchKernelGGL(k_cs_carry1, dim3((unsigned)tg), dim3(64), 0, s, g->n, nchunks, g->dangling.p, X, Y, d_seeds, c1, g->in_ptr.p,
-                           g->in_src.p, evo, evt, lnk, g->cs_approx.p, g->cs_e.p, g->cs_d0.p, g->cs_d1.p, g->cs_side.p, nz_out,
-                           g->cs_redo.p, zout, g->w_src.p, sums);
-        RWR_HIP(hipGetLastError());
-        return RWR_OK;
-    }
-    CS_DISPATCH_G(G, hipLaunchKernelGGL((k_cs_block<GG, false>), grid, dim3(256), 0, s, g->n, nchunks, g->dangling.p, X,
-                                        d_seeds, c1, g->in_ptr.p, g->in_src.p, d_evoff, g->d_evterm.p, lnk,
-                                        (const int32_t *)nullptr, g->cs_approx.p, (long long *)nullptr, (long long *)nullptr));
-    hipLaunchKernelGGL(k_cs_plan, dim3((unsigned)(tg * G)), dim3(64), 0, s, nchunks, d_seeds, g->cs_approx.p, g->cs_e.p);
-    CS_DISPATCH_G(G, hipLaunchKernelGGL((k_cs_block<GG, true>), grid, dim3(256), 0, s, g->n, nchunks, g->dangling.p, X,
-                                        d_seeds, c1, g->in_ptr.p, g->in_src.p, d_evoff, g->d_evterm.p, lnk,
-                                        g->cs_e.p, (double *)nullptr, g->cs_d0.p, g->cs_d1.p));
-    CS_DISPATCH_G(G, hipLaunchKernelGGL(k_cs_carry<GG>, dim3((unsigned)(tg * G)), dim3(64), 0, s, g->n, nchunks, g->dangling.p, X, Y,
-                                        d_seeds, c1, g->in_ptr.p, g->in_src.p, d_evoff, g->d_evterm.p, lnk,
-                                        g->cs_approx.p, g->cs_e.p, g->cs_d0.p, g->cs_d1.p, nz_out, g->cs_redo.p, 0,
-                                        (double *)nullptr, (const double *)nullptr, sums));
-    RWR_HIP(hipGetLastError());
-    return RWR_OK;
+    RWR_TRY(chain_scan_sum_cols_prepare(g, 1, 1, s));
+    RWR_TRY(g->d_evoff.ensure(2));
+    return chain_scan_launch(g, 1, 1, D, out, g->cs_lnk0.p + cs_nchunks(g->n, 1) + 1, g->d_evoff.p, 0.0, nullptr, g->cs_lnk0.p, s);
 }
 
 // after the caller has synchronised the stream: fold the redo counter into the statistics

@@ -363,18 +363,6 @@ const int64_t *small_pin_ids(const rwr_graph *g);      // the list of the last r
 const double *small_pin_scores(const rwr_graph *g);
 int32_t recommend_small(rwr_graph *g, int32_t seed, double d, int32_t n_iter, int32_t top_n, int64_t *ids, double *scores,
                         int32_t *count);
-// chain_scan.hip: the exact seed-row chain as a parallel binade scan
-int32_t chain_scan_prepare(rwr_graph *g, int G, int tg, const int32_t *d_seeds, hipStream_t s);
-int32_t chain_scan_step(rwr_graph *g, int G, int tg, const double *X, double *Y, const int32_t *d_seeds,
-                        const int64_t *d_evoff, double c1, uint32_t *nz_out, hipStream_t s, const double *zterms = nullptr,
-                        double *zout = nullptr);
-bool chain_scan_self_contained(int G);   // G == 1: no k_seed_terms / k_seed_z launches around the step
-int32_t chain_scan_collect(rwr_graph *g, hipStream_t s);
-int32_t chain_scan_sum(rwr_graph *g, const double *D, double *out, hipStream_t s);   // exact sequential sum of n addends >= 0
-// ... of every column of a tile group's [tile][n][G] matrix of addends >= 0: sums[tile * G + k].  _prepare once per tile group
-// (scratch cells and the all-zero link table; evoff: the group's d_evoff slots, never dereferenced past their pointer)
-int32_t chain_scan_sum_cols_prepare(rwr_graph *g, int G, int tg, hipStream_t s);
-int32_t chain_scan_sum_cols(rwr_graph *g, int G, int tg, const double *D, const int64_t *evoff, double *sums, hipStream_t s);
-
+// (the exact seed-row chain -- the folds and the binade scan -- is declared in seed_row.h)
 
 }  // namespace rwr

@@ -4,6 +4,7 @@
 #include "column_ends.h"
 #include "engine.h"
 #include "rank.h"
+#include "seed_row.h"
 #include "step_plan.h"
 
 #include <new>

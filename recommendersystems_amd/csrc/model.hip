@@ -2,6 +2,7 @@
 // personalised Models in one call, driven over GroupIter (iterate.h); the reductions that restart.hip (caller-set restart
 // vectors) shares and GroupColumns, the column ends of a tile group of Models, which restart_batch.hip drives as well.
 #include "iterate.h"
+#include "seed_row.h"
 
 #include <algorithm>
 #include <cstdlib>

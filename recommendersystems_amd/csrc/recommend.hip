@@ -2,6 +2,7 @@
 // workspace, deals the seeds to tiles and tile groups, runs each group's power iteration (iterate.hip: iterate_group), then
 // the exclusion and the ranking (rank.h), and copies the lists back.
 #include "iterate.h"
+#include "seed_row.h"
 
 #include <algorithm>
 #include <chrono>
@@ -49,7 +50,7 @@ int32_t ensure_workspace(rwr_graph *g, int G, int32_t K, int *TG_out, int extra_
     if (TG < 1) TG = 1;
     if (TG > ntiles) TG = ntiles;
     if (TG > 65535 / G) TG = 65535 / G;   // grid.y of the per-slot kernels is TG * G
-    // exact mode: every tile's chain workgroup must be resident beside the SpMM (one per CU, see k_gate)
+    // exact mode: every tile's chain workgroup must be resident beside the SpMM (one per CU, see k_gate in seed_chain.hip)
     if (g->opts.tile_group <= 0 && TG > 192) TG = 192;
     // the rank matrices: if the device cannot give what the sizing above asked for (other handles of the process -- the
     // reference runs up to ten host threads, Program.cs:11 -- may have taken their share since hipMemGetInfo was read),

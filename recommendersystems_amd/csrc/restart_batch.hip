@@ -23,6 +23,7 @@
 
 #include "iterate.h"
 #include "ranked_end.h"
+#include "seed_row.h"
 
 namespace rwr {
 

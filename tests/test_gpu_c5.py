@@ -41,7 +41,7 @@ def test_c5_full_size_on_one_gpu(c5):
     rp, dst = flat["rowptr"], flat["dst"]
 
     out = {}
-    for kern in ("scan", "fold"):               # two implementations of the same seed-row arithmetic (iterate.hip / chain_scan.hip)
+    for kern in ("scan", "fold"):               # two implementations of the same seed-row arithmetic (chain_scan.hip / seed_chain.hip)
         G = amd.Graph.from_flat(**flat, seed_row_kernel=kern)
         G.buildGraph()
         assert G.stats()["uniform"] == 1 and G.stats()["nnz"] == int(rp[-1])
