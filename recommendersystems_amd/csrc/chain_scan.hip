@@ -461,14 +461,18 @@ __global__ __launch_bounds__(64) void k_cs_carry(int32_t n, int nchunks, const u
 //   * block 0 (more generally the first block holding a non-zero addend) starts from exactly +0.0, so its workgroup adds it
 //     up sequentially -- literally the reference's loop -- and hands the carry the exact sum behind it         (CS_EXACT);
 //   * a block whose approximate incoming and outgoing sums lie in adjacent binades e, e + 1 is SPLIT: the approximate
-//     incoming mantissa locates the 4-row run in which the sum crosses; the block hands over the composed function of
-//     the runs before it (under e), the run's four addends, and the composed function of the runs behind it (under
-//     e + 1).  The carry applies function, four real adds, function -- and CHECKS each part (sum still inside e before
-//     the run, inside e + 1 after the four adds and at the block's end).  A row's addend is ~10^10 ulps of the sum while
-//     the approximate prefix is good to ~10^3, so the run is the right one except with probability ~10^-7; then, as for
-//     any failed check, the block is redone exactly by the carry wave (cs_redo_block)                           (CS_SPLIT);
-//   * anything else -- two crossings in a block behind the first, a link into the seed inside the split run, a subnormal
-//     incoming sum -- is left to the carry's redo                                                               (CS_REDO).
+//     incoming mantissa locates the ROW in which the sum crosses; the block hands over the composed function of the rows
+//     before it (under e), that row's addends -- its links into the seed in list order, then its restart addend, up to
+//     CS_RUN_ADDENDS in all -- and the composed function of the rows behind it (under e + 1).  The carry applies function,
+//     real adds, function -- and CHECKS each part (sum still inside e before the row, inside e + 1 after its adds and at
+//     the block's end).  A row's addend is ~10^10 ulps of the sum while the approximate prefix is good to ~10^3, so the row
+//     is the right one except with probability ~10^-7; then, as for any failed check, the block is redone exactly by the
+//     carry wave (cs_redo_block)                                                                                (CS_SPLIT);
+//   * two crossings in one block are located the same way, the second under e + 1 from the approximate sum behind the
+//     first crossing row                                                                                        (CS_SPLIT2);
+//   * anything else -- more than two crossings in a block behind the first, a crossing row with more than CS_RUN_ADDENDS
+//     addends, a subnormal incoming sum -- is left to the carry's redo                                          (CS_REDO).
+// tests/chain_cases.py holds one crafted rank vector per branch and an executable model of these decisions.
 // The prediction (k_cs_plan) is folded into the block kernel: every workgroup sums the approximate block sums in front of it.
 constexpr int CS_PLAIN = 0, CS_SPLIT = 1, CS_EXACT = 2, CS_REDO = 3, CS_SPLIT2 = 4;
 #ifdef RWR_EXPERIMENTS

@@ -190,6 +190,7 @@ int32_t model_run(rwr_graph *g, int32_t seed, double d, int32_t run_mode, double
     RWR_HIP(hipMemcpyAsync(rank_out, Xf, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     RWR_HIP(hipStreamSynchronize(s));
     RWR_HIP(hipStreamSynchronize(g->stream2));
+    if (prof.on) RWR_TRY(chain_scan_collect(g, s));
     if (iters_out) *iters_out = done;
     return RWR_OK;
 }
@@ -219,6 +220,7 @@ int32_t model_deliver(rwr_graph *g, int32_t seed, double d, const double *rank_i
         RWR_TRY(gi.step(plan_step(gi.cfg, 0, -1), prof));
         RWR_HIP(hipStreamSynchronize(s));
         RWR_HIP(hipStreamSynchronize(g->stream2));
+        if (prof.on) RWR_TRY(chain_scan_collect(g, s));
         out = gi.X;                                   // (step() swapped: X holds nextRank)
     } else {
         RWR_TRY(ensure_in_w(g));

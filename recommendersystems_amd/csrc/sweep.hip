@@ -218,7 +218,7 @@ __global__ __launch_bounds__(512) void k_sweep_lds(int32_t n, int32_t n_sw, int 
 #endif
     if (tid == 0) zs[BN] = 0.0;
     // pieces of 1 KB (128 doubles, 16 bytes per lane); lanes behind the vector's end re-read its last pair (the LDS slots
-    // they fill are never referenced).  (Bare s_barrier, not __syncthreads(): its fence would be the same vmcnt(0), but the
+    // they fill are never referenced -- but for the last element of an odd n, which one thread then puts right).  (Bare s_barrier, not __syncthreads(): its fence would be the same vmcnt(0), but the
     // LDS-only fences keep the compiler from adding more.)
     const int64_t last_pair = n >= 2 ? (((int64_t)n - 2) & ~(int64_t)1) : 0;
 #define SW_ENTER_BLOCK()                                                                                                  \
@@ -238,6 +238,13 @@ __global__ __launch_bounds__(512) void k_sweep_lds(int32_t n, int32_t n_sw, int 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                  \
         __builtin_amdgcn_s_barrier();                                  /* the block has landed */                         \
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");                                                   \
+        if ((n & 1) && lo__ + cnt__ == (int64_t)n) {                   /* (workgroup-uniform) */                          \
+            /* the last element of an odd vector has no whole pair: the clamped lanes left z[n - 3] in its slot */        \
+            if (tid == 0) zs[cnt__ - 1] = z[n - 1];                                                                       \
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");                                               \
+            __builtin_amdgcn_s_barrier();                                                                                 \
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");                                               \
+        }                                                                                                                 \
         SW_TOC()                                                                                                          \
     }
 
