@@ -53,6 +53,11 @@ namespace Recommenders.RWRBased {
         [DllImport(Lib)] public static extern int rwr_recommend_typed_eval_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,
             int top_n, int cand_type, uint excl_edge_mask, int exclude_self, long[] test_ptr, long[] test_ids, long[] n_hits,
             double[] sum_precision, long[] list_len);
+        // ... and of every test entry its 0-based position and its score in the seed's WHOLE list of type cand_type (-1 / +0.0:
+        // the list does not hold the id); pos_out and score_out are test_ptr[K] long, in the caller's order, list_len is K long
+        [DllImport(Lib)] public static extern int rwr_recommend_typed_positions_batch(GraphHandle g, int[] seeds, int K, float d,
+            int n_iter, int cand_type, uint excl_edge_mask, int exclude_self, long[] test_ptr, long[] test_ids, long[] pos_out,
+            double[] score_out, long[] list_len);
         // Hits / sum of precisions of Experiment.cs:121-128 computed on the device (the ranked list never crosses): one seed,
         // or K seeds with K test sets in CSR form (test set k = test_ids[test_ptr[k] .. test_ptr[k + 1]))
         [DllImport(Lib)] public static extern int rwr_recommend_eval(GraphHandle g, int seed, float d, int n_iter, long[] test_ids,
@@ -92,6 +97,12 @@ namespace Recommenders.RWRBased {
         [DllImport(Lib)] public static extern int rwr_recommend_restart_eval_batch(GraphHandle g, int K, long[] sup_ptr, int[] sup_idx,
             double[] sup_val, int[] start, long[] excl_ptr, int[] excl_idx, double d, int n_iter, int top_n, long[] test_ptr,
             long[] test_ids, long[] n_hits, double[] sum_precision, long[] list_len);
+
+        // the positions and scores of the test entries in the WHOLE lists rwr_recommend_restart_typed_batch defines
+        [DllImport(Lib)] public static extern int rwr_recommend_restart_typed_positions_batch(GraphHandle g, int K, long[] sup_ptr,
+            int[] sup_idx, double[] sup_val, int[] start, long[] excl_ptr, int[] excl_idx, double d, int n_iter, int cand_type,
+            uint excl_edge_mask, int exclude_members, long[] test_ptr, long[] test_ids, long[] pos_out, double[] score_out,
+            long[] list_len);
 
         [DllImport(Lib)] public static extern int rwr_model_run_restart(GraphHandle g, double[] restart, double[] rank_in, double d,
             int run_mode, double value, double[] rank_out, out long iters_out);

@@ -129,6 +129,95 @@ namespace Recommenders.RWRBased {
             nHits = h[0]; sumPrecision = sp[0]; listLen = ln[0];
         }
 
+        // K id arrays in the caller's order as CSR
+        static void PackTests(long[][] testIds, int K, out long[] testPtr, out long[] flat) {
+            if (testIds.Length != K) throw new System.ArgumentException("testIds must hold one entry per walk");
+            testPtr = new long[K + 1];
+            for (int k = 0; k < K; k++) testPtr[k + 1] = testPtr[k] + testIds[k].Length;
+            flat = new long[testPtr[K]];
+            for (int k = 0; k < K; k++) System.Array.Copy(testIds[k], 0, flat, testPtr[k], testIds[k].Length);
+        }
+
+        // ... and the flat result arrays of a positions entry cut back into K arrays aligned with them
+        static void SplitTests(long[] testPtr, long[] pos, double[] score, out long[][] positions, out double[][] scores) {
+            int K = testPtr.Length - 1;
+            positions = new long[K][]; scores = new double[K][];
+            for (int k = 0; k < K; k++) {
+                long len = testPtr[k + 1] - testPtr[k];
+                positions[k] = new long[len]; scores[k] = new double[len];
+                System.Array.Copy(pos, testPtr[k], positions[k], 0, len);
+                System.Array.Copy(score, testPtr[k], scores[k], 0, len);
+            }
+        }
+
+        // addition: the 0-based position and the score of every test id in K seeds' WHOLE lists among the nodes of one node type,
+        // found on the device by counting, no list written (rwr_recommend_typed_positions_batch).  positions[k][j] / scores[k][j]
+        // answer testIds[k][j] -- the caller's order, duplicates kept; -1 / +0.0 where the list does not hold the id.  candType,
+        // exclEdgeTypes and excludeSelf as in RecommendationTypedBatch.  MRR, NDCG@k, recall@k and AUC follow on the host
+        public void RecommendationTypedPositionsBatch(int[] seeds, float dampingFactor, int nIteration, long[][] testIds,
+                                                      NodeType candType, out long[][] positions, out double[][] scores,
+                                                      out long[] listLen, IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                      bool excludeSelf = false) {
+            int K = seeds.Length;
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            long[] testPtr, flat;
+            PackTests(testIds, K, out testPtr, out flat);
+            var pos = new long[System.Math.Max(testPtr[K], 1)]; var score = new double[pos.Length]; listLen = new long[K];
+            Native.Check(Native.rwr_recommend_typed_positions_batch(graph.handle, seeds, K, dampingFactor, nIteration, (int)candType, mask, excludeSelf ? 1 : 0, testPtr, flat, pos, score, listLen));
+            SplitTests(testPtr, pos, score, out positions, out scores);
+        }
+
+        // ... and for one seed
+        public void RecommendationTypedPositions(int idxTargetNode, float dampingFactor, int nIteration, long[] testIds,
+                                                 NodeType candType, out long[] positions, out double[] scores, out long listLen,
+                                                 IEnumerable<EdgeType> exclEdgeTypes = null, bool excludeSelf = false) {
+            long[][] p; double[][] s; long[] ln;
+            RecommendationTypedPositionsBatch(new[] { idxTargetNode }, dampingFactor, nIteration, new[] { testIds }, candType, out p, out s,
+                                              out ln, exclEdgeTypes, excludeSelf);
+            positions = p[0]; scores = s[0]; listLen = ln[0];
+        }
+
+        // addition: the same for K walks with caller-set restart vectors, in the whole lists RecommendationRestartTypedBatch defines
+        // (rwr_recommend_restart_typed_positions_batch).  nodes, weights, start, candType, exclEdgeTypes, excludeMembers and
+        // exclude as there
+        public void RecommendationRestartTypedPositionsBatch(int[][] nodes, double[][] weights, int[] start, double dampingFactor,
+                                                             int nIteration, long[][] testIds, NodeType candType,
+                                                             out long[][] positions, out double[][] scores, out long[] listLen,
+                                                             IEnumerable<EdgeType> exclEdgeTypes = null, bool excludeMembers = false,
+                                                             int[][] exclude = null) {
+            int K = nodes.Length;
+            if (weights.Length != K || (start != null && start.Length != K) || (exclude != null && exclude.Length != K))
+                throw new System.ArgumentException("nodes, weights, start and exclude must hold one entry per vector");
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            var ptr = new long[K + 1];
+            for (int k = 0; k < K; k++) {
+                if (nodes[k].Length != weights[k].Length)
+                    throw new System.ArgumentException("a restart vector's nodes and weights differ in length");
+                ptr[k + 1] = ptr[k] + nodes[k].Length;
+            }
+            var idx = new int[ptr[K]];
+            var val = new double[ptr[K]];
+            for (int k = 0; k < K; k++) {
+                System.Array.Copy(nodes[k], 0, idx, ptr[k], nodes[k].Length);
+                System.Array.Copy(weights[k], 0, val, ptr[k], weights[k].Length);
+            }
+            long[] exclPtr = null;
+            int[] exclIdx = null;
+            if (exclude != null) {
+                exclPtr = new long[K + 1];
+                for (int k = 0; k < K; k++) exclPtr[k + 1] = exclPtr[k] + exclude[k].Length;
+                exclIdx = new int[exclPtr[K]];
+                for (int k = 0; k < K; k++) System.Array.Copy(exclude[k], 0, exclIdx, exclPtr[k], exclude[k].Length);
+            }
+            long[] testPtr, flat;
+            PackTests(testIds, K, out testPtr, out flat);
+            var pos = new long[System.Math.Max(testPtr[K], 1)]; var score = new double[pos.Length]; listLen = new long[K];
+            Native.Check(Native.rwr_recommend_restart_typed_positions_batch(graph.handle, K, ptr, idx, val, start, exclPtr, exclIdx, dampingFactor, nIteration, (int)candType, mask, excludeMembers ? 1 : 0, testPtr, flat, pos, score, listLen));
+            SplitTests(testPtr, pos, score, out positions, out scores);
+        }
+
         // addition: the top-N lists of K walks with caller-set restart vectors among the nodes of ONE node type
         // (rwr_recommend_restart_typed_batch).  nodes, weights, start and exclude as in RecommendationRestartBatch; candType and
         // exclEdgeTypes as in RecommendationTypedBatch, applied to every member of exclusion set k; excludeMembers: the members

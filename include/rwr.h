@@ -369,6 +369,39 @@ int32_t rwr_recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32
                                        int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,
                                        const int64_t *test_ptr, const int64_t *test_ids,
                                        int64_t *n_hits, double *sum_precision, int64_t *list_len /* may be NULL */);
+/* The same K walks, and of every test id its position and score in the seed's WHOLE list -- what MRR, NDCG@k, recall@k for
+ * several k, AUC or "at which rank does item j appear for user u" are computed from on the host.  The counting of
+ * rwr_recommend_typed_eval_batch knows every hit's position before it folds them into one sum; this entry returns them, and
+ * still no list is written.  seeds, d, n_iter, cand_type, excl_edge_mask, exclude_self and the domain exactly as in
+ * rwr_recommend_typed_batch; test_ptr / test_ids as in rwr_recommend_typed_eval_batch, but the entries are answered one by one.
+ * Let L_k be the WHOLE list rwr_recommend_typed_batch defines for seed k -- the same candidates, mask and self exclusion, the
+ * same order (score descending, then id descending, Recommender.cs:35-38), not cut anywhere: there is no top_n, the caller
+ * cuts.  For every test entry j in [test_ptr[k], test_ptr[k+1]), in the caller's order and with duplicates kept:
+ *   - pos_out[j] is the 0-based index in L_k of the FIRST entry whose id is test_ids[j], or -1 when L_k holds no such entry
+ *     (no node carries the id, the node is of another type, or the candidate is excluded by the mask or as the seed itself);
+ *   - score_out[j] (score_out may be NULL) is that entry's score, bitwise, and +0.0 when pos_out[j] == -1;
+ *   - duplicate test entries receive the same answer; node ids need not be unique (rwr_graph_append_nodes): of several
+ *     candidates carrying the id, the best-ranked one answers;
+ *   - list_len[k] (list_len may be NULL) is the length of L_k.
+ * The integers are identical, and the scores bitwise equal, to ranking the row that rwr_model_run(g, seeds[k], (double)d,
+ * RWR_RUN_ITERATIONS, n_iter, ...) returns, for every seed: duplicate seeds (each with its own test entries), dangling seeds
+ * and seeds of another type than cand_type included.  The result does not depend on scheduling: the same call gives the same
+ * arrays.
+ *   - cand_type = RWR_NODE_ITEM, excl_edge_mask = 1u << RWR_EDGE_LIKE, exclude_self = 0 gives the positions in rwr_recommend's
+ *     whole list (top_n <= 0).
+ *   - A cand_type that no node carries gives every pos_out -1, every score_out +0.0, list_len 0 and RWR_OK.
+ *   - Argument errors, all found before any device work and in this order: a NULL g is refused first; K == 0 is a no-op
+ *     (RWR_OK); then everything rwr_recommend_typed_batch reports for K, the seeds, cand_type and the mask, with the same
+ *     status and batch position; then everything rwr_recommend_typed_eval_batch reports for test_ptr / test_ids, with pos_out
+ *     in the place of its result arrays (a NULL pos_out with K > 0 gives RWR_E_INVALID); then the domain
+ *     (RWR_E_UNSUPPORTED).  A refused call writes nothing.
+ *   - test_ptr[K] x 16 bytes come back from the device; the candidate list is the handle's cached one
+ *     (rwr_recommend_typed_batch); opts.tile_seeds, tile_group and workspace_bytes keep their meaning. */
+int32_t rwr_recommend_typed_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter,
+                                            int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,
+                                            const int64_t *test_ptr, const int64_t *test_ids,
+                                            int64_t *pos_out /* test_ptr[K] */, double *score_out /* test_ptr[K], may be NULL */,
+                                            int64_t *list_len /* K, may be NULL */);
 
 /* ---- Model ---------------------------------------------------------------------------
  * Backs the public class Model: ctor (Model.cs:33-50 personalised, seed >= 0;
@@ -506,6 +539,28 @@ int32_t rwr_recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t 
                                          const int32_t *excl_idx, double d, int32_t n_iter, int32_t top_n,
                                          const int64_t *test_ptr, const int64_t *test_ids, int64_t *n_hits,
                                          double *sum_precision, int64_t *list_len /* may be NULL */);
+/* The positions and scores of test ids in the WHOLE typed lists of K restart-vector walks: rwr_recommend_typed_positions_batch
+ * for the walks of rwr_recommend_restart_typed_batch.  Vectors, starts, n_iter, the exclusion sets (excl_ptr == NULL: set k is
+ * the indices of vector k's support), cand_type, excl_edge_mask, exclude_members and the domain exactly as in
+ * rwr_recommend_restart_typed_batch; L_k is the whole list that entry defines for vector k, not cut anywhere (no top_n).
+ * test_ptr, test_ids, pos_out, score_out (may be NULL) and list_len (may be NULL) exactly as in
+ * rwr_recommend_typed_positions_batch: first entry carrying the id, -1 / +0.0 when there is none, duplicates answered alike,
+ * the best-ranked of several candidates with one id.  The integers are identical, and the scores bitwise equal, to ranking
+ * the row that rwr_model_run_restart(g, dense(v_k), rank0_k, d, RWR_RUN_ITERATIONS, n_iter, ...) returns, for every vector
+ * (K == 1 and a vector with more than RWR_RESTART_EXACT_MAX non-zero entries run vector by vector through that very call).
+ *   - A cand_type that no node carries gives every pos_out -1, every score_out +0.0, list_len 0 and RWR_OK.
+ *   - Argument errors, all found before any device work and in this order: a NULL g is refused first; K == 0 is a no-op
+ *     (RWR_OK); then K < 0 and a NULL sup_ptr (RWR_E_INVALID); cand_type outside [0, 255] or a mask bit >= 8
+ *     (RWR_E_INVALID); everything rwr_recommend_restart_batch reports for the vectors and the exclusion sets, with the same
+ *     status and batch position; everything rwr_recommend_restart_eval_batch reports for test_ptr / test_ids, with pos_out in
+ *     the place of its result arrays (a NULL pos_out gives RWR_E_INVALID); then the domain (RWR_E_UNSUPPORTED).  A refused
+ *     call writes nothing. */
+int32_t rwr_recommend_restart_typed_positions_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                                    const double *sup_val, const int32_t *start, const int64_t *excl_ptr,
+                                                    const int32_t *excl_idx, double d, int32_t n_iter, int32_t cand_type,
+                                                    uint32_t excl_edge_mask, int32_t exclude_members,
+                                                    const int64_t *test_ptr, const int64_t *test_ids, int64_t *pos_out,
+                                                    double *score_out /* may be NULL */, int64_t *list_len /* may be NULL */);
 
 /* ---- row-partitioned mode (graphs beyond one GPU; BASELINE.json config 5) ------------
  * An ADDITION: the reference has no distributed mode.  The transition matrix is partitioned by SOURCE rows

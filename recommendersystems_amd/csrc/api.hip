@@ -155,8 +155,10 @@ static int32_t check_ranked_vectors(const char *who, int32_t n, int32_t K, const
     return RWR_OK;
 }
 
-// eval_check's verdict on the test sets and result arrays of an evaluating entry, as status and message
-static int32_t eval_verdict_status(const char *who, const EvalCheck &c, const int64_t *test_ptr)
+// eval_check's verdict on the test sets and result arrays of an evaluating entry, as status and message; outs: the result
+// arrays EVAL_NULL_OUT names for this entry
+static int32_t eval_verdict_status(const char *who, const EvalCheck &c, const int64_t *test_ptr,
+                                   const char *outs = "n_hits or sum_precision")
 {
     switch (c.verdict) {
         case EVAL_OK: break;
@@ -164,7 +166,7 @@ static int32_t eval_verdict_status(const char *who, const EvalCheck &c, const in
             set_error("%s: NULL test_ptr", who);
             return RWR_E_INVALID;
         case EVAL_NULL_OUT:
-            set_error("%s: NULL n_hits or sum_precision", who);
+            set_error("%s: NULL %s", who, outs);
             return RWR_E_INVALID;
         case EVAL_BAD_PTR0:
             set_error("%s: test_ptr[0] = %lld, not 0", who, (long long)test_ptr[0]);
@@ -425,6 +427,26 @@ int32_t rwr_recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32
     });
 }
 
+int32_t rwr_recommend_typed_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t cand_type,
+                                            uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
+                                            const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len)
+{
+    static const char *const who = "rwr_recommend_typed_positions_batch";
+    g_err[0] = 0;
+    // (pos_out stands where the evaluating entry has its two result arrays)
+    const TypedEvalCheck c = typed_eval_check(g != nullptr, g ? g->n : 0, seeds, K, cand_type, excl_edge_mask, test_ptr, test_ids,
+                                              pos_out, pos_out);
+    if (c.typed.verdict == TYPED_NOOP) return RWR_OK;
+    RWR_TRY(typed_verdict_status(who, c.typed, g ? g->n : 0, 0, cand_type, excl_edge_mask, "seeds", nullptr));
+    RWR_TRY(eval_verdict_status(who, c.eval, test_ptr, "pos_out"));
+    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    return bound(who, g, [&] {
+        return recommend_typed_positions_batch(g, seeds, K, (double)d, n_iter, cand_type, excl_edge_mask, exclude_self, test_ptr,
+                                               test_ids, pos_out, score_out, list_len);
+    });
+}
+
 int32_t rwr_recommend(rwr_graph *g, int32_t seed, float d, int32_t n_iter, int32_t top_n, int64_t *out_id,
                       double *out_score, int64_t *inout_count)
 {
@@ -679,6 +701,33 @@ int32_t rwr_recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t 
         return recommend_restart_eval_batch(g, K, sup_ptr, sup_idx, sup_val, start, excl_ptr ? excl_ptr : sup_ptr,
                                             excl_ptr ? excl_idx : sup_idx, d, n_iter, top_n, test_ptr, test_ids, n_hits,
                                             sum_precision, list_len);
+    });
+}
+
+int32_t rwr_recommend_restart_typed_positions_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                                    const double *sup_val, const int32_t *start, const int64_t *excl_ptr,
+                                                    const int32_t *excl_idx, double d, int32_t n_iter, int32_t cand_type,
+                                                    uint32_t excl_edge_mask, int32_t exclude_members, const int64_t *test_ptr,
+                                                    const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len)
+{
+    static const char *const who = "rwr_recommend_restart_typed_positions_batch";
+    g_err[0] = 0;
+    if (!g) { set_error("%s: NULL graph", who); return RWR_E_INVALID; }
+    if (K < 0) { set_error("%s: negative K", who); return RWR_E_INVALID; }
+    if (K == 0) return RWR_OK;
+    if (!sup_ptr) { set_error("%s: NULL sup_ptr", who); return RWR_E_INVALID; }
+    TypedCheck c;                                                // (no top_n here: the whole lists)
+    c.verdict = restart_typed_check(1, 1, cand_type, excl_edge_mask);
+    RWR_TRY(typed_verdict_status(who, c, g->n, 0, cand_type, excl_edge_mask, "", nullptr));
+    RWR_TRY(check_ranked_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start, excl_ptr, excl_idx));
+    RWR_TRY(eval_verdict_status(who, eval_check(K, test_ptr, test_ids, pos_out, pos_out), test_ptr, "pos_out"));
+    RWR_TRY(check_ranked_domain(who, g, d, "rwr_model_run_restart_batch"));
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    // excl_ptr == NULL: set k is the indices of vector k's support, whatever their values
+    return bound(who, g, [&] {
+        return recommend_restart_typed_positions_batch(g, K, sup_ptr, sup_idx, sup_val, start, excl_ptr ? excl_ptr : sup_ptr,
+                                                       excl_ptr ? excl_idx : sup_idx, d, n_iter, cand_type, excl_edge_mask,
+                                                       exclude_members, test_ptr, test_ids, pos_out, score_out, list_len);
     });
 }
 

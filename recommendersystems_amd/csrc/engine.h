@@ -321,6 +321,16 @@ int32_t recommend_restart_typed_batch(rwr_graph *g, int32_t K, const int64_t *su
                                       const double *sup_val, const int32_t *start, const int64_t *set_ptr, const int32_t *set_idx,
                                       double d, int32_t n_iter, int32_t top_n, int32_t cand_type, uint32_t excl_edge_mask,
                                       int32_t exclude_members, int64_t *ids, double *scores, int32_t *counts);
+// ... and the positions and scores of test ids in the WHOLE lists of both typed entries (rwr_recommend_typed_positions_batch,
+// rwr_recommend_restart_typed_positions_batch): eval_count.hip's counting, finished by eval_pos.hip
+int32_t recommend_typed_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type,
+                                        uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
+                                        const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len);
+int32_t recommend_restart_typed_positions_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                                const double *sup_val, const int32_t *start, const int64_t *set_ptr,
+                                                const int32_t *set_idx, double d, int32_t n_iter, int32_t cand_type,
+                                                uint32_t excl_edge_mask, int32_t exclude_members, const int64_t *test_ptr,
+                                                const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len);
 // model.hip pieces restart.hip runs as well (the loops around them: run_walk and GroupColumns, iterate.h).  A run's end condition (Model.run(int) / run(double) / run(), Model.cs:52-66):
 // T steps at most; !by_count: until checkConvergence's distance is < threshold, a failure after max_iters = RWR_MAX_ITERS steps
 struct RunEnd {

@@ -9,7 +9,8 @@
 //   3. count    every candidate finds by binary search how many hit keys are >= its own and adds one to that interval's
 //               counter (LDS-private per workgroup while the tile's lists fit, global otherwise);
 //   4. finish   one workgroup per slot: a prefix sum over the intervals gives every hit its position; one thread adds the
-//               addends in rank order (eval_ranked_body's division and summation order).
+//               addends in rank order (eval_ranked_body's division and summation order).  The positions destination
+//               (eval_pos.hip) runs stages 1-3 as they are (eval_count_group) and a finish of its own.
 // Integer counting only: the result does not depend on scheduling.  Stages 1 and 3 read the group's candidate rows of X once
 // each; nothing of size K x candidates is written.  The candidate list is the caller's: the ITEM rows for the restart batch,
 // the cached rows of a node type for rwr_recommend_typed_eval_batch.
@@ -187,23 +188,8 @@ __global__ __launch_bounds__(256) void k_eval_finish(const int32_t *__restrict__
     uint32_t *c = counters + h0 + slot;
     const SelCand *keys = sorted + h0;
     double *tm = terms + h0;
-    if (tid == 0) { carry = 0; kept = 0; }
-    __syncthreads();
-    for (int32_t base = 0; base <= h; base += 256) {
-        const int32_t i = base + tid;
-        sh[tid] = (i <= h) ? c[i] : 0u;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const uint32_t t = tid >= off ? sh[tid - off] : 0u;
-            __syncthreads();
-            sh[tid] += t;
-            __syncthreads();
-        }
-        if (i <= h) c[i] = carry + sh[tid];
-        __syncthreads();
-        if (tid == 255) carry += sh[255];
-        __syncthreads();
-    }
+    if (tid == 0) kept = 0;
+    eval_prefix_counters(c, h, sh, &carry);
     int mine = 0;
     for (int32_t i = tid; i < h; i += 256) {
         int32_t f = i;
@@ -224,17 +210,16 @@ __global__ __launch_bounds__(256) void k_eval_finish(const int32_t *__restrict__
     }
 }
 
-int32_t eval_prepare(rwr_graph *g, EvalEnd &ev, int32_t K, const std::vector<int32_t> &slot_k, size_t slots_per_group,
-                     const char *who, hipStream_t s)
+int32_t eval_plan_upload(EvalEnd &ev, int32_t K, const std::vector<int32_t> &slot_k, size_t slots_per_group, const void *out_a,
+                         const void *out_b, const char *who, hipStream_t s)
 {
-    ev.plan = eval_plan(slot_k.size(), slot_k.data(), slots_per_group, K, ev.test_ptr, ev.test_ids, ev.n_hits, ev.sum_precision);
+    ev.plan = eval_plan(slot_k.size(), slot_k.data(), slots_per_group, K, ev.test_ptr, ev.test_ids, out_a, out_b);
     if (ev.plan.check.verdict != EVAL_OK) {                        // (api.hip refuses such sets before the call gets here)
         set_error("%s: test sets failed their check (verdict %d)", who, (int)ev.plan.check.verdict);
         return RWR_E_INVALID;
     }
     RWR_TRY(ev.d_ids.alloc(ev.plan.n_ids));
     RWR_TRY(ev.d_slot_off.alloc(ev.plan.n_off));
-    RWR_TRY(ev.d_out.alloc(ev.plan.n_out));
     RWR_TRY(ev.d_flag.alloc(1));
     RWR_TRY(ev.d_cnt.alloc(ev.plan.n_group_slots));
     RWR_TRY(ev.d_cursor.alloc(ev.plan.n_group_slots));
@@ -243,8 +228,16 @@ int32_t eval_prepare(rwr_graph *g, EvalEnd &ev, int32_t K, const std::vector<int
     if (ev.plan.n_ids > 0)
         RWR_HIP(hipMemcpyAsync(ev.d_ids.p, ev.plan.ids.data(), ev.plan.n_ids * sizeof(int64_t), hipMemcpyHostToDevice, s));
     RWR_HIP(hipMemcpyAsync(ev.d_slot_off.p, ev.plan.slot_off.data(), ev.plan.n_off * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    RWR_HIP(hipMemsetAsync(ev.d_out.p, 0, ev.plan.n_out * sizeof(EvalOut), s));
     RWR_HIP(hipMemsetAsync(ev.d_flag.p, 0, sizeof(int32_t), s));
+    return RWR_OK;
+}
+
+int32_t eval_prepare(rwr_graph *g, EvalEnd &ev, int32_t K, const std::vector<int32_t> &slot_k, size_t slots_per_group,
+                     const char *who, hipStream_t s)
+{
+    RWR_TRY(eval_plan_upload(ev, K, slot_k, slots_per_group, ev.n_hits, ev.sum_precision, who, s));
+    RWR_TRY(ev.d_out.alloc(ev.plan.n_out));
+    RWR_HIP(hipMemsetAsync(ev.d_out.p, 0, ev.plan.n_out * sizeof(EvalOut), s));
     return RWR_OK;
 }
 
@@ -271,11 +264,10 @@ static int32_t sort_long(rwr_graph *g, const SelCand *hits, int32_t cnt, SelCand
     return RWR_OK;
 }
 
-int32_t eval_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const double *X, const int32_t *rows, int32_t nrows,
-                   hipStream_t s)
+int32_t eval_count_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const double *X, const int32_t *rows, int32_t nrows,
+                         hipStream_t s)
 {
     const int32_t m = nrows;
-    if (m == 0) return RWR_OK;                                      // no candidate anywhere: the zeroed records stand
     const size_t S = (size_t)tg * G;
     const int32_t *slot_k = g->d_slot_k.p + q0;
     const int64_t *slot_off = ev.d_slot_off.p + q0;
@@ -294,7 +286,6 @@ int32_t eval_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const do
     if (L.bad || L.n_counters > 0xFFFFFFFFll) { set_error("evaluation: a tile group's hit lists are out of range"); return RWR_E_UNSUPPORTED; }
     RWR_TRY(ev.d_hits.ensure((size_t)L.n_hits * sizeof(SelCand)));
     RWR_TRY(ev.d_sorted.ensure((size_t)L.n_hits * sizeof(SelCand)));
-    RWR_TRY(ev.d_terms.ensure((size_t)L.n_hits));
     RWR_TRY(ev.d_counters.ensure((size_t)L.n_counters));
     SelCand *hits = (SelCand *)ev.d_hits.p, *sorted = (SelCand *)ev.d_sorted.p;
     RWR_HIP(hipMemcpyAsync(ev.d_hit_off.p, L.hit_off.data(), (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
@@ -333,9 +324,19 @@ int32_t eval_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const do
         hipLaunchKernelGGL(k_eval_count<GG>, grid, dim3(256), lds, s, g->n, m, rows, g->node_id.p, X, slot_k,
                            ev.d_hit_off.p, sorted, ev.d_tile_lds.p, ev.d_counters.p);
     });
+    RWR_HIP(hipGetLastError());
+    return RWR_OK;
+}
+
+int32_t eval_group(rwr_graph *g, EvalEnd &ev, int G, int tg, size_t q0, const double *X, const int32_t *rows, int32_t nrows,
+                   hipStream_t s)
+{
+    if (nrows == 0) return RWR_OK;                                  // no candidate anywhere: the zeroed records stand
+    RWR_TRY(eval_count_group(g, ev, G, tg, q0, X, rows, nrows, s));
     // 4. positions, addends in rank order, the records at the vectors' batch positions
-    hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)S), dim3(256), 0, s, slot_k, ev.d_hit_off.p, sorted, ev.d_counters.p,
-                       ev.d_terms.p, ev.top_n, ev.d_out.p);
+    RWR_TRY(ev.d_terms.ensure((size_t)ev.layout.n_hits));
+    hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)tg * G), dim3(256), 0, s, g->d_slot_k.p + q0, ev.d_hit_off.p,
+                       (const SelCand *)ev.d_sorted.p, ev.d_counters.p, ev.d_terms.p, ev.top_n, ev.d_out.p);
     RWR_HIP(hipGetLastError());
     return RWR_OK;
 }

@@ -1,13 +1,14 @@
 // The ranked end of a batch (internal; ranked_end.hip): what the typed seed driver (typed.hip) and the
 // restart-vector driver (restart_batch.hip) do with a tile group whose walks are finished.  The excluded elements of the
-// group's X[tile][n][G] are marked with -1; then the candidates are ranked into K x top_n lists or evaluated against test
-// sets by counting; after the last group the result is copied back once.  Three independent descriptions say which end:
-// the candidates, the exclusion, the destination.
+// group's X[tile][n][G] are marked with -1; then the candidates are ranked into K x top_n lists, evaluated against test
+// sets by counting, or the test ids' positions in the whole lists are found by the same counting; after the last group the
+// result is copied back once.  Three independent descriptions say which end: the candidates, the exclusion, the destination.
 //
-// Lifetime: the object (and the EvalEnd it points to) is declared before the driver's StreamsIdle, so the device copies of
+// Lifetime: the object (and the EvalEnd or PosEnd it points to) is declared before the driver's StreamsIdle, so the device copies of
 // its plans outlive the kernels that read them, on error paths too.
 #pragma once
 #include "eval_count.h"
+#include "eval_pos.h"
 #include "exclude_plan.h"
 #include "member_plan.h"
 
@@ -30,12 +31,14 @@ struct RankedEnd {
     // sets of exactly one member per slot may name them by a device array over the slots instead (-1: a padding slot): the
     // members' rows are then marked from it and no pairs are planned or uploaded (measured)
     const int32_t *slot_member = nullptr;
-    // the destination: the caller's list tables, top_n wide, or (ev != nullptr) the evaluation records
+    // the destination: the caller's list tables, top_n wide, or (ev != nullptr) the evaluation records, or (pos != nullptr)
+    // the positions and scores of the test ids; at most one of ev and pos is set
     int32_t top_n = 0;
     int64_t *ids = nullptr;
     double *scores = nullptr;
     int32_t *counts = nullptr;
     EvalEnd *ev = nullptr;
+    PosEnd *pos = nullptr;
 
     // The zeroed output tables (or records) of the call and the plans of this slot assignment: slot_k[slot] = batch position,
     // -1 = padding; slots_per_group slots form a tile group.  The driver has put slot_k into g->d_slot_k -- the ranking's
@@ -44,7 +47,7 @@ struct RankedEnd {
     // Tile group grp (tg tiles of G slots from slot q0 on) holds its final ranks in X: the exclusion, then the ranking or
     // the evaluation, booked as prof.rank
     int32_t finish_group(rwr_graph *g, int G, int tg, int grp, size_t q0, double *X, Profile &prof, hipStream_t s);
-    // after the last group: K x top_n list entries, or the K evaluation records
+    // after the last group: K x top_n list entries, the K evaluation records, or the test ids' positions and scores
     int32_t copy_back(rwr_graph *g, int32_t K);
 
 private:

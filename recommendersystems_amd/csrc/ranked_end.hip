@@ -66,6 +66,7 @@ static int32_t upload(DevBuf<T> &d, const std::vector<T> &h, hipStream_t s)
 int32_t RankedEnd::prepare(rwr_graph *g, int32_t K, const std::vector<int32_t> &slot_k, size_t slots_per_group, hipStream_t s)
 {
     if (ev) RWR_TRY(eval_prepare(g, *ev, K, slot_k, slots_per_group, who, s));
+    else if (pos) RWR_TRY(pos_prepare(g, *pos, K, slot_k, slots_per_group, who, s));
     else RWR_TRY(ensure_out_tables(g, K, top_n, s));
     if (mask != 0) {                                            // (mask 0 looks at no link)
         plan = exclude_plan(g->n, g->h_rowptr.data(), slot_k.size(), slot_k.data(), slots_per_group, K, set_ptr, set_idx);
@@ -111,6 +112,7 @@ int32_t RankedEnd::finish_group(rwr_graph *g, int G, int tg, int grp, size_t q0,
     }
     RWR_HIP(hipGetLastError());
     if (ev) RWR_TRY(eval_group(g, *ev, G, tg, q0, X, rows ? rows : g->item_rows.p, rows ? nrows : g->n_items, s));
+    else if (pos) RWR_TRY(pos_group(g, *pos, G, tg, q0, X, rows ? rows : g->item_rows.p, rows ? nrows : g->n_items, s));
     else if (!rows) RWR_TRY(rank_group(g, G, tg, slot_k, slot_k, top_n, X, s));
     else if (nrows > 0) RWR_TRY(rank_group_select(g, G, tg, slot_k, top_n, X, slot_k, s, rows, nrows));   // (top_n <= its limit: api.hip)
     RWR_TRY(prof.end(prof.rank, a, s));                         // (no candidate: the zeroed tables stand)
@@ -120,6 +122,7 @@ int32_t RankedEnd::finish_group(rwr_graph *g, int G, int tg, int grp, size_t q0,
 int32_t RankedEnd::copy_back(rwr_graph *g, int32_t K)
 {
     if (ev) return eval_copy_back(g, *ev, K, who, g->stream);
+    if (pos) return pos_copy_back(g, *pos, K, who, g->stream);
     return copy_lists_back(g, K, top_n, ids, scores, counts, top_n);
 }
 

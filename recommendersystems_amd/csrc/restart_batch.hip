@@ -14,9 +14,10 @@
 // runs beside, so the value-free form's smaller matrix stream would shorten nothing (measured).
 //
 // rwr_recommend_restart_batch, rwr_recommend_restart_eval_batch (3.15) and rwr_recommend_restart_typed_batch
-// (3.17) are the same driver -- slot dealing, pair upload, step loop, statistics -- with another end of a tile group: after
-// step T every vector's exclusion set is marked in X and the group is ranked or evaluated where it lies, so K x top_n entries
-// or K records leave the device in place of K x n.  A RankedEnd (ranked_end.h) says which candidates, which exclusion and
+// (3.17) and rwr_recommend_restart_typed_positions_batch (3.19) are the same driver -- slot dealing, pair upload, step loop,
+// statistics -- with another end of a tile group: after step T every vector's exclusion set is marked in X and the group is
+// ranked or evaluated where it lies, so K x top_n entries, K records or the test ids' positions leave the device in place of
+// K x n.  A RankedEnd (ranked_end.h) says which candidates, which exclusion and
 // which destination, and does that work; the entries below only fill it in.  A call without one is the full-vector entry.
 #include <algorithm>
 #include <cstring>
@@ -304,6 +305,22 @@ int32_t recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t *sup
     end.set_ptr = set_ptr, end.set_idx = set_idx, end.mask = 1u << RWR_EDGE_LIKE;
     end.ev = &ev;
     return restart_ranked(g, K, sup_ptr, sup_idx, sup_val, start, d, n_iter, end);
+}
+
+int32_t recommend_restart_typed_positions_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
+                                                const double *sup_val, const int32_t *start, const int64_t *set_ptr,
+                                                const int32_t *set_idx, double d, int32_t n_iter, int32_t cand_type,
+                                                uint32_t excl_edge_mask, int32_t exclude_members, const int64_t *test_ptr,
+                                                const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len)
+{
+    PosEnd pe;
+    pe.ev.test_ptr = test_ptr, pe.ev.test_ids = test_ids;
+    pe.pos_out = pos_out, pe.score_out = score_out, pe.list_len = list_len;
+    RankedEnd end;                                              // the rows of a type, the links of the mask and the members, positions
+    end.who = "rwr_recommend_restart_typed_positions_batch";
+    end.set_ptr = set_ptr, end.set_idx = set_idx, end.mask = excl_edge_mask, end.members = exclude_members != 0;
+    end.pos = &pe;
+    return restart_ranked(g, K, sup_ptr, sup_idx, sup_val, start, d, n_iter, end, cand_type);
 }
 
 }  // namespace rwr

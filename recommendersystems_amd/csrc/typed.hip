@@ -14,7 +14,8 @@
 //
 // rwr_recommend_typed_eval_batch is the same driver with the evaluating destination: after the exclusion the
 // group is evaluated against the seeds' test sets by counting (eval_count.hip over the candidate list) instead of ranked, one
-// record per seed leaves, and no list is written -- so top_n has no limit there.
+// record per seed leaves, and no list is written -- so top_n has no limit there.  rwr_recommend_typed_positions_batch
+//  is the third destination: the same counting, the position and score of every test id in the whole list.
 #include "iterate.h"
 #include "ranked_end.h"
 
@@ -194,6 +195,19 @@ int32_t recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32_t K
     RankedEnd end;
     end.who = "rwr_recommend_typed_eval_batch";
     end.ev = &ev;
+    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end); });
+}
+
+int32_t recommend_typed_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type,
+                                        uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
+                                        const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len)
+{
+    PosEnd pe;
+    pe.ev.test_ptr = test_ptr, pe.ev.test_ids = test_ids;
+    pe.pos_out = pos_out, pe.score_out = score_out, pe.list_len = list_len;
+    RankedEnd end;
+    end.who = "rwr_recommend_typed_positions_batch";
+    end.pos = &pe;
     return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end); });
 }
 

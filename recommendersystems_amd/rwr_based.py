@@ -68,6 +68,23 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def _pack_tests(testSets, K):
+    """K collections of test ids in the caller's order as CSR, and the result arrays of a positions entry: one position and
+    one score per entry (at least one element behind each pointer), one list length per batch position"""
+    tests = [np.asarray(list(t), dtype=np.int64).reshape(-1) for t in testSets]
+    if len(tests) != K:
+        raise ValueError(f"testSets must hold {K} id collections")
+    tp = np.zeros(K + 1, dtype=np.int64)
+    tp[1:] = np.cumsum([len(t) for t in tests])
+    ti = np.ascontiguousarray(np.concatenate(tests) if K else np.zeros(0, dtype=np.int64), dtype=np.int64)
+    total = max(int(tp[K]), 1)
+    return tp, ti, np.full(total, -1, dtype=np.int64), np.zeros(total, dtype=np.float64), np.zeros(K, dtype=np.int64)
+
+
+def _split_tests(tp, flat):
+    return [flat[int(tp[k]):int(tp[k + 1])].copy() for k in range(len(tp) - 1)]
+
+
 def _grown_lists(old_flat, new_flat):
     """The links by which the lists of ``new_flat`` exceed those of ``old_flat`` (both as ``Graph._flatten`` returns them):
     ``(src, dst, etype, w)`` of the appended links, row by row in list order, when the node arrays are equal and every old
@@ -804,6 +821,62 @@ class Recommender:
         hits, sp, ln = self.RecommendationTypedEvalBatch([int(idxTargetNode)], dampingFactor, nIteration, [testSet], candType,
                                                          exclEdgeTypes, excludeSelf, topN)
         return int(hits[0]), float(sp[0]), int(ln[0])
+
+    def RecommendationTypedPositionsBatch(self, seeds, dampingFactor: float, nIteration: int, testSets, candType,
+                                          exclEdgeTypes=(), excludeSelf: bool = False):
+        """The 0-based position and the score of every test id in K seeds' WHOLE lists among the nodes of one node type, found
+        on the device by counting, no list written (rwr_recommend_typed_positions_batch, an addition, see include/rwr.h):
+        (positions, scores, listLen[K]).  positions and scores are lists of K arrays aligned with testSets -- entry by entry,
+        in the caller's order, duplicates kept; -1 / +0.0 where the list does not hold the id.  candType, exclEdgeTypes and
+        excludeSelf as in RecommendationTypedBatch.  Any ranking metric follows on the host, for instance
+        MRR = mean(1 / (p[p >= 0].min() + 1)) and NDCG@10 = sum(1 / log2(p[(p >= 0) & (p < 10)] + 2)) / ideal."""
+        lib = _lib.load()
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        K = int(seeds.shape[0])
+        mask = 0
+        for t in exclEdgeTypes:
+            mask |= 1 << int(EdgeType(t))
+        tp, ti, pos, sc, ln = _pack_tests(testSets, K)
+        _lib.check(lib.rwr_recommend_typed_positions_batch(self.graph._handle(), _p(seeds, C.c_int32), K, C.c_float(dampingFactor),
+                                                           int(nIteration), int(candType), mask, 1 if excludeSelf else 0,
+                                                           _p(tp, C.c_int64), _p(ti, C.c_int64), _p(pos, C.c_int64),
+                                                           _p(sc, C.c_double), _p(ln, C.c_int64)))
+        return _split_tests(tp, pos), _split_tests(tp, sc), ln
+
+    def RecommendationTypedPositions(self, idxTargetNode: int, dampingFactor: float, nIteration: int, testSet, candType,
+                                     exclEdgeTypes=(), excludeSelf: bool = False):
+        """RecommendationTypedPositionsBatch for one seed: (positions, scores, len(list)), the arrays aligned with testSet."""
+        pos, sc, ln = self.RecommendationTypedPositionsBatch([int(idxTargetNode)], dampingFactor, nIteration, [testSet], candType,
+                                                             exclEdgeTypes, excludeSelf)
+        return pos[0], sc[0], int(ln[0])
+
+    def RecommendationRestartTypedPositionsBatch(self, restarts, starts, dampingFactor: float, nIteration: int, testSets, candType,
+                                                 exclEdgeTypes=(), excludeMembers: bool = False, exclude=None):
+        """RecommendationTypedPositionsBatch for K walks with caller-set restart vectors
+        (rwr_recommend_restart_typed_positions_batch, an addition, see include/rwr.h): (positions, scores, listLen[K]) in the
+        whole lists RecommendationRestartTypedBatch defines.  restarts, starts, candType, exclEdgeTypes, excludeMembers and
+        exclude as there; testSets as in RecommendationTypedPositionsBatch."""
+        lib = _lib.load()
+        K, sup_ptr, sup_idx, sup_val, st = _pack_restarts(restarts, starts)
+        ep = ei = None
+        if exclude is not None:
+            sets = [np.asarray(e, dtype=np.int32).reshape(-1) for e in exclude]
+            if len(sets) != K:
+                raise ValueError(f"exclude must hold {K} node lists")
+            ep = np.zeros(K + 1, dtype=np.int64)
+            ep[1:] = np.cumsum([len(e) for e in sets])
+            ei = np.ascontiguousarray(np.concatenate(sets) if K else np.zeros(0, dtype=np.int32), dtype=np.int32)
+        mask = 0
+        for t in exclEdgeTypes:
+            mask |= 1 << int(EdgeType(t))
+        tp, ti, pos, sc, ln = _pack_tests(testSets, K)
+        _lib.check(lib.rwr_recommend_restart_typed_positions_batch(
+            self.graph._handle(), K, _p(sup_ptr, C.c_int64), _p(sup_idx, C.c_int32), _p(sup_val, C.c_double),
+            None if st is None else _p(st, C.c_int32), None if ep is None else _p(ep, C.c_int64),
+            None if ei is None else _p(ei, C.c_int32), float(dampingFactor), int(nIteration), int(candType), mask,
+            1 if excludeMembers else 0, _p(tp, C.c_int64), _p(ti, C.c_int64), _p(pos, C.c_int64), _p(sc, C.c_double),
+            _p(ln, C.c_int64)))
+        return _split_tests(tp, pos), _split_tests(tp, sc), ln
 
     def RecommendationRestartTypedBatch(self, restarts, starts, dampingFactor: float, nIteration: int, topN: int, candType,
                                         exclEdgeTypes=(), excludeMembers: bool = False, exclude=None):
