@@ -58,6 +58,16 @@ namespace Recommenders.RWRBased {
         [DllImport(Lib)] public static extern int rwr_recommend_typed_positions_batch(GraphHandle g, int[] seeds, int K, float d,
             int n_iter, int cand_type, uint excl_edge_mask, int exclude_self, long[] test_ptr, long[] test_ids, long[] pos_out,
             double[] score_out, long[] list_len);
+        // the typed walks ranked within the caller's pool of node indices (pool_count < 0: no pool, pool_idx null; 0: an empty
+        // pool) and with deny list k = deny_idx[deny_ptr[k] .. deny_ptr[k + 1]) never shown to seed k (deny_ptr null: none);
+        // cand_type -1: nodes of any type (Recommender.RecommendationFilteredBatch)
+        [DllImport(Lib)] public static extern int rwr_recommend_filtered_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,
+            int top_n, int cand_type, uint excl_edge_mask, int exclude_self, long pool_count, int[] pool_idx, long[] deny_ptr,
+            int[] deny_idx, long[] ids, double[] scores, int[] counts);
+        // ... and the positions and scores of the test entries in the WHOLE filtered lists
+        [DllImport(Lib)] public static extern int rwr_recommend_filtered_positions_batch(GraphHandle g, int[] seeds, int K, float d,
+            int n_iter, int cand_type, uint excl_edge_mask, int exclude_self, long pool_count, int[] pool_idx, long[] deny_ptr,
+            int[] deny_idx, long[] test_ptr, long[] test_ids, long[] pos_out, double[] score_out, long[] list_len);
         // Hits / sum of precisions of Experiment.cs:121-128 computed on the device (the ranked list never crosses): one seed,
         // or K seeds with K test sets in CSR form (test set k = test_ids[test_ptr[k] .. test_ptr[k + 1]))
         [DllImport(Lib)] public static extern int rwr_recommend_eval(GraphHandle g, int seed, float d, int n_iter, long[] test_ids,

@@ -178,6 +178,75 @@ namespace Recommenders.RWRBased {
             positions = p[0]; scores = s[0]; listLen = ln[0];
         }
 
+        // K deny lists (node indices) as CSR; null: none
+        static void PackDeny(int[][] deny, int K, out long[] denyPtr, out int[] denyIdx) {
+            denyPtr = null; denyIdx = null;
+            if (deny == null) return;
+            if (deny.Length != K) throw new System.ArgumentException("deny must hold one entry per seed");
+            denyPtr = new long[K + 1];
+            for (int k = 0; k < K; k++) denyPtr[k + 1] = denyPtr[k] + deny[k].Length;
+            denyIdx = new int[System.Math.Max(denyPtr[K], 1)];
+            for (int k = 0; k < K; k++) System.Array.Copy(deny[k], 0, denyIdx, denyPtr[k], deny[k].Length);
+        }
+
+        // addition: the top-N lists of K seeds within a candidate pool the caller sets and with a deny list per seed
+        // (rwr_recommend_filtered_batch).  candType: the candidates' type, null: nodes of any type; exclEdgeTypes and excludeSelf
+        // as in RecommendationTypedBatch; pool: node INDICES in any order, duplicates allowed -- only these are ranked, for every
+        // seed (null: no pool, an empty array: an empty pool, every list empty); deny[k]: node indices never shown to seed k
+        // (null: none)
+        public List<KeyValuePair<long, double>>[] RecommendationFilteredBatch(int[] seeds, float dampingFactor, int nIteration, int topN,
+                                                                              NodeType? candType = null,
+                                                                              IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                              bool excludeSelf = false, int[] pool = null,
+                                                                              int[][] deny = null) {
+            if (topN < 1) throw new System.ArgumentOutOfRangeException("topN", "RecommendationFilteredBatch needs topN >= 1");
+            int K = seeds.Length;
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            long[] denyPtr; int[] denyIdx;
+            PackDeny(deny, K, out denyPtr, out denyIdx);
+            long poolCount = pool == null ? -1 : pool.Length;
+            int[] poolIdx = (pool != null && pool.Length == 0) ? new int[1] : pool;
+            var ids = new long[(long)K * topN]; var scores = new double[(long)K * topN]; var counts = new int[K];
+            Native.Check(Native.rwr_recommend_filtered_batch(graph.handle, seeds, K, dampingFactor, nIteration, topN, candType.HasValue ? (int)candType.Value : -1, mask, excludeSelf ? 1 : 0, poolCount, poolIdx, denyPtr, denyIdx, ids, scores, counts));
+            var all = new List<KeyValuePair<long, double>>[K];
+            for (int k = 0; k < K; k++) {
+                all[k] = new List<KeyValuePair<long, double>>(counts[k]);
+                for (int q = 0; q < counts[k]; q++) all[k].Add(new KeyValuePair<long, double>(ids[(long)k * topN + q], scores[(long)k * topN + q]));
+            }
+            return all;
+        }
+
+        // ... and for one seed (deny: its one deny list)
+        public List<KeyValuePair<long, double>> RecommendationFiltered(int idxTargetNode, float dampingFactor, int nIteration, int topN,
+                                                                       NodeType? candType = null,
+                                                                       IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                       bool excludeSelf = false, int[] pool = null, int[] deny = null) {
+            return RecommendationFilteredBatch(new[] { idxTargetNode }, dampingFactor, nIteration, topN, candType, exclEdgeTypes, excludeSelf,
+                                               pool, deny == null ? null : new[] { deny })[0];
+        }
+
+        // addition: the 0-based position and the score of every test id in K seeds' WHOLE filtered lists
+        // (rwr_recommend_filtered_positions_batch): RecommendationTypedPositionsBatch over the lists RecommendationFilteredBatch
+        // defines.  A denied id, an id outside the pool and an id no node carries answer -1 / +0.0
+        public void RecommendationFilteredPositionsBatch(int[] seeds, float dampingFactor, int nIteration, long[][] testIds,
+                                                         out long[][] positions, out double[][] scores, out long[] listLen,
+                                                         NodeType? candType = null, IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                         bool excludeSelf = false, int[] pool = null, int[][] deny = null) {
+            int K = seeds.Length;
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            long[] denyPtr; int[] denyIdx;
+            PackDeny(deny, K, out denyPtr, out denyIdx);
+            long poolCount = pool == null ? -1 : pool.Length;
+            int[] poolIdx = (pool != null && pool.Length == 0) ? new int[1] : pool;
+            long[] testPtr, flat;
+            PackTests(testIds, K, out testPtr, out flat);
+            var pos = new long[System.Math.Max(testPtr[K], 1)]; var score = new double[pos.Length]; listLen = new long[K];
+            Native.Check(Native.rwr_recommend_filtered_positions_batch(graph.handle, seeds, K, dampingFactor, nIteration, candType.HasValue ? (int)candType.Value : -1, mask, excludeSelf ? 1 : 0, poolCount, poolIdx, denyPtr, denyIdx, testPtr, flat, pos, score, listLen));
+            SplitTests(testPtr, pos, score, out positions, out scores);
+        }
+
         // addition: the same for K walks with caller-set restart vectors, in the whole lists RecommendationRestartTypedBatch defines
         // (rwr_recommend_restart_typed_positions_batch).  nodes, weights, start, candType, exclEdgeTypes, excludeMembers and
         // exclude as there

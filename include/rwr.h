@@ -402,6 +402,63 @@ int32_t rwr_recommend_typed_positions_batch(rwr_graph *g, const int32_t *seeds, 
                                             const int64_t *test_ptr, const int64_t *test_ids,
                                             int64_t *pos_out /* test_ptr[K] */, double *score_out /* test_ptr[K], may be NULL */,
                                             int64_t *list_len /* K, may be NULL */);
+/* The typed walks ranked within a candidate pool the CALLER sets, and with a deny list per seed -- the two filters a serving
+ * caller asks for first and that are not links of the graph: "rank only items published today / in stock / of one language"
+ * (one pool for all seeds of the call, another one in the next call) and "never show seed k these nodes" (impressions already
+ * served, blocked accounts, dismissed items).  Both are applied on the device, to the finished walk: the walk itself is that
+ * of rwr_recommend_typed_batch, and so are seeds, d, n_iter, top_n, excl_edge_mask, exclude_self and the domain.
+ * Result k starts from the rank row that rwr_model_run(g, seeds[k], (double)d, RWR_RUN_ITERATIONS, n_iter, ...) returns; of it
+ *   - node i is a candidate when cand_type == -1 (nodes of ANY type) or node_type[i] == cand_type (0..255), AND pool_count < 0
+ *     (no pool) or i occurs in pool_idx[0 .. pool_count).  The pool holds node INDICES, in any order, and may hold
+ *     duplicates: a node listed twice is one candidate.  pool_count == 0 is an empty pool: every list is empty (counts 0) and
+ *     the call returns RWR_OK;
+ *   - a candidate is dropped when it is the target of a RAW out-link of the seed whose type has its bit in excl_edge_mask, or
+ *     it is the seed and exclude_self != 0 (both exactly as in rwr_recommend_typed_batch), or it occurs in
+ *     deny_idx[deny_ptr[k] .. deny_ptr[k+1]) (node indices; deny_ptr has K + 1 entries; deny_ptr == NULL: no deny lists).  A
+ *     deny list may hold duplicates, the seed, nodes outside the pool and nodes of another type, and may be empty; duplicate
+ *     seeds each keep their own deny list;
+ *   - the rest is ordered by score descending, then id descending; the first top_n of them go into row k of ids / scores
+ *     (K x top_n, row-major), counts[k] = entries written, the rest of the row id 0 / score 0.
+ * Ids are identical to that composition and scores bitwise equal to it, for every seed; the same call gives the same arrays
+ * twice (no atomic decides a position of the candidate list).
+ *   - pool_count < 0, deny_ptr == NULL and cand_type >= 0 is rwr_recommend_typed_batch: the same ids, scores and counts.
+ *   - top_n in [1, 1024]: a larger top_n gives RWR_E_UNSUPPORTED with the limit in the message, as the typed entry.
+ *   - Argument errors, all found on the host before any device work and in this order: a NULL g is refused first; K == 0 is a
+ *     no-op (RWR_OK); then everything rwr_recommend_typed_batch reports for K, the pointers, top_n < 1, cand_type (now
+ *     [-1, 255]), the mask and the seeds, with the same status and batch position; pool_count > 0 with a NULL pool_idx
+ *     (RWR_E_INVALID); a pool index outside [0, n) (RWR_E_RANGE, its position in the message); a deny_ptr that does not start
+ *     at 0 or that decreases, a NULL deny_idx while deny_ptr[K] > 0 (RWR_E_INVALID); a deny index outside [0, n) (RWR_E_RANGE
+ *     with its batch position); top_n's limit; the domain (RWR_E_UNSUPPORTED).  A refused call writes nothing.
+ *   - The pool's candidate list is built on the device by every call that names a pool or cand_type -1 and dropped when the
+ *     call ends: the handle's cached per-type lists (rwr_recommend_typed_batch) are neither read nor evicted by it, and a call
+ *     without a pool and with cand_type >= 0 takes the cached list exactly as the typed entry does.
+ *   - Not here: restart-vector walks; a Hits / AP destination of its own (the positions below give every metric); a pool per
+ *     seed; pools given as node ids instead of indices (the host mirrors can map ids). */
+int32_t rwr_recommend_filtered_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                     int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,
+                                     int64_t pool_count, const int32_t *pool_idx,
+                                     const int64_t *deny_ptr /* K + 1, may be NULL */, const int32_t *deny_idx,
+                                     int64_t *ids, double *scores, int32_t *counts);
+/* ... and the positions and scores of test ids in the WHOLE filtered lists: rwr_recommend_typed_positions_batch over the lists
+ * rwr_recommend_filtered_batch defines -- the same candidates (cand_type, the pool), the same exclusion (mask, self, deny
+ * lists), the same order, not cut anywhere.  test_ptr, test_ids, pos_out, score_out (may be NULL) and list_len (may be NULL)
+ * exactly as in rwr_recommend_typed_positions_batch: every test entry is answered in the caller's order, by the first list
+ * entry carrying its id; a denied id, an id outside the pool and an id that no node carries answer -1 / +0.0; list_len[k] is
+ * the length of the filtered list.  An empty pool gives every pos_out -1, every score_out +0.0, list_len 0 and RWR_OK.  The
+ * integers are identical, and the scores bitwise equal, to ranking the row rwr_model_run returns.
+ *   - pool_count < 0, deny_ptr == NULL and cand_type >= 0 is rwr_recommend_typed_positions_batch: the same arrays.
+ *   - Argument errors, on the host before any device work and in this order: those of rwr_recommend_filtered_batch up to and
+ *     including the deny lists (there is no top_n; the pointers are seeds); then everything
+ *     rwr_recommend_typed_positions_batch reports for test_ptr / test_ids / pos_out; then the domain.  A refused call writes
+ *     nothing.
+ *   - Not here: what rwr_recommend_filtered_batch names. */
+int32_t rwr_recommend_filtered_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter,
+                                               int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,
+                                               int64_t pool_count, const int32_t *pool_idx,
+                                               const int64_t *deny_ptr /* K + 1, may be NULL */, const int32_t *deny_idx,
+                                               const int64_t *test_ptr, const int64_t *test_ids,
+                                               int64_t *pos_out /* test_ptr[K] */, double *score_out /* test_ptr[K], may be NULL */,
+                                               int64_t *list_len /* K, may be NULL */);
 
 /* ---- Model ---------------------------------------------------------------------------
  * Backs the public class Model: ctor (Model.cs:33-50 personalised, seed >= 0;

@@ -8,6 +8,7 @@
 
 #include "eval_plan.h"
 #include "exclude_plan.h"
+#include "filter_plan.h"
 #include "handle.h"
 #include "member_plan.h"
 #include "rank.h"
@@ -223,6 +224,55 @@ static int32_t typed_verdict_status(const char *who, const TypedCheck &c, int32_
             }
             set_error("%s: top_n %d is beyond the select path's limit of %d entries%s", who, top_n, rank_select_max_k(), top_n_hint);
             return RWR_E_UNSUPPORTED;
+    }
+    return RWR_OK;
+}
+
+// A FilterCheck's verdict on the arguments of a filtered entry, as status and message (FILTER_NOOP is the caller's).  The typed
+// part goes through typed_verdict_status, except the candidate type, whose range has grown by FILTER_ANY_TYPE here.
+static int32_t filter_verdict_status(const char *who, const FilterCheck &c, int32_t n, int32_t top_n, int32_t cand_type,
+                                     uint32_t excl_edge_mask, const char *null_arg, const char *top_n_hint, const int64_t *deny_ptr,
+                                     const int64_t *test_ptr)
+{
+    switch (c.verdict) {
+        case FILTER_OK:
+        case FILTER_NOOP: break;
+        case FILTER_TYPED:
+            if (c.typed.verdict == TYPED_BAD_CAND_TYPE) {
+                set_error("%s: cand_type %d is outside [-1, 255]", who, cand_type);
+                return RWR_E_INVALID;
+            }
+            return typed_verdict_status(who, c.typed, n, top_n, cand_type, excl_edge_mask, null_arg, top_n_hint);
+        case FILTER_NULL_POOL:
+            set_error("%s: NULL pool_idx", who);
+            return RWR_E_INVALID;
+        case FILTER_POOL_RANGE:
+            set_error("%s: pool index %d (pool position %lld) is outside [0, %d)", who, c.bad_index, (long long)c.bad_pos, n);
+            return RWR_E_RANGE;
+        case FILTER_DENY:
+            switch (c.deny.verdict) {
+                case EXCLUDE_OK: break;
+                case EXCLUDE_BAD_PTR0:
+                    set_error("%s: deny_ptr[0] = %lld, not 0", who, (long long)deny_ptr[0]);
+                    return RWR_E_INVALID;
+                case EXCLUDE_PTR_DECREASES:
+                    set_error("%s: deny_ptr decreases at batch position %d", who, c.deny.bad_k);
+                    return RWR_E_INVALID;
+                case EXCLUDE_NULL_IDX:
+                    set_error("%s: NULL deny_idx", who);
+                    return RWR_E_INVALID;
+                case EXCLUDE_BAD_INDEX:
+                    set_error("%s: deny index %d (batch position %d) is outside [0, %d)", who, c.deny.bad_index, c.deny.bad_k, n);
+                    return RWR_E_RANGE;
+            }
+            break;
+        case FILTER_TEST:
+            return eval_verdict_status(who, c.test, test_ptr, "pos_out");
+        case FILTER_TOP_N_LIMIT: {
+            TypedCheck t;
+            t.verdict = TYPED_TOP_N_LIMIT;
+            return typed_verdict_status(who, t, n, top_n, cand_type, excl_edge_mask, null_arg, top_n_hint);
+        }
     }
     return RWR_OK;
 }
@@ -444,6 +494,46 @@ int32_t rwr_recommend_typed_positions_batch(rwr_graph *g, const int32_t *seeds, 
     return bound(who, g, [&] {
         return recommend_typed_positions_batch(g, seeds, K, (double)d, n_iter, cand_type, excl_edge_mask, exclude_self, test_ptr,
                                                test_ids, pos_out, score_out, list_len);
+    });
+}
+
+int32_t rwr_recommend_filtered_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                     int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count,
+                                     const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, int64_t *ids,
+                                     double *scores, int32_t *counts)
+{
+    static const char *const who = "rwr_recommend_filtered_batch";
+    g_err[0] = 0;
+    const FilterCheck c = filter_check(g != nullptr, g ? g->n : 0, seeds, K, top_n, rank_select_max_k(), cand_type, excl_edge_mask,
+                                       ids && scores && counts, pool_count, pool_idx, deny_ptr, deny_idx);
+    if (c.verdict == FILTER_NOOP) return RWR_OK;
+    RWR_TRY(filter_verdict_status(who, c, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds, ids, scores or counts",
+                                  " (rwr_recommend_filtered_positions_batch answers for whole lists)", deny_ptr, nullptr));
+    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    return bound(who, g, [&] {
+        return recommend_filtered_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, pool_count,
+                                        pool_idx, deny_ptr, deny_idx, ids, scores, counts);
+    });
+}
+
+int32_t rwr_recommend_filtered_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter,
+                                               int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count,
+                                               const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx,
+                                               const int64_t *test_ptr, const int64_t *test_ids, int64_t *pos_out, double *score_out,
+                                               int64_t *list_len)
+{
+    static const char *const who = "rwr_recommend_filtered_positions_batch";
+    g_err[0] = 0;
+    const FilterCheck c = filter_positions_check(g != nullptr, g ? g->n : 0, seeds, K, cand_type, excl_edge_mask, pool_count, pool_idx,
+                                                 deny_ptr, deny_idx, test_ptr, test_ids, pos_out);
+    if (c.verdict == FILTER_NOOP) return RWR_OK;
+    RWR_TRY(filter_verdict_status(who, c, g ? g->n : 0, 0, cand_type, excl_edge_mask, "seeds", nullptr, deny_ptr, test_ptr));
+    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    return bound(who, g, [&] {
+        return recommend_filtered_positions_batch(g, seeds, K, (double)d, n_iter, cand_type, excl_edge_mask, exclude_self, pool_count,
+                                                  pool_idx, deny_ptr, deny_idx, test_ptr, test_ids, pos_out, score_out, list_len);
     });
 }
 

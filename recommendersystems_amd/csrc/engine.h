@@ -331,6 +331,18 @@ int32_t recommend_restart_typed_positions_batch(rwr_graph *g, int32_t K, const i
                                                 const int32_t *set_idx, double d, int32_t n_iter, int32_t cand_type,
                                                 uint32_t excl_edge_mask, int32_t exclude_members, const int64_t *test_ptr,
                                                 const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len);
+// filter.hip: the typed seed walks ranked within a caller-set pool and with per-seed deny lists (rwr_recommend_filtered_batch,
+// rwr_recommend_filtered_positions_batch): candidates = rows of cand_type (-1: of any type) that the pool lists
+// (pool_count < 0: no pool), the rows of deny list k dropped beside the typed entries' exclusion; arguments as
+// filter_plan.h's checks passed them
+int32_t recommend_filtered_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
+                                 int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count,
+                                 const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, int64_t *ids,
+                                 double *scores, int32_t *counts);
+int32_t recommend_filtered_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type,
+                                           uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count, const int32_t *pool_idx,
+                                           const int64_t *deny_ptr, const int32_t *deny_idx, const int64_t *test_ptr,
+                                           const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len);
 // model.hip pieces restart.hip runs as well (the loops around them: run_walk and GroupColumns, iterate.h).  A run's end condition (Model.run(int) / run(double) / run(), Model.cs:52-66):
 // T steps at most; !by_count: until checkConvergence's distance is < threshold, a failure after max_iters = RWR_MAX_ITERS steps
 struct RunEnd {

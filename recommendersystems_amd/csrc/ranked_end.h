@@ -2,7 +2,8 @@
 // restart-vector driver (restart_batch.hip) do with a tile group whose walks are finished.  The excluded elements of the
 // group's X[tile][n][G] are marked with -1; then the candidates are ranked into K x top_n lists, evaluated against test
 // sets by counting, or the test ids' positions in the whole lists are found by the same counting; after the last group the
-// result is copied back once.  Three independent descriptions say which end: the candidates, the exclusion, the destination.
+// result is copied back once.  Three independent descriptions say which end: the candidates, the exclusion, the destination;
+// the filtered entries add a fourth, the seeds' deny lists.
 //
 // Lifetime: the object (and the EvalEnd or PosEnd it points to) is declared before the driver's StreamsIdle, so the device copies of
 // its plans outlive the kernels that read them, on error paths too.
@@ -31,6 +32,12 @@ struct RankedEnd {
     // sets of exactly one member per slot may name them by a device array over the slots instead (-1: a padding slot): the
     // members' rows are then marked from it and no pairs are planned or uploaded (measured)
     const int32_t *slot_member = nullptr;
+    // the deny lists (the filtered entries): a second set description, independent of the one above -- set k
+    // (CSR over batch positions, host) loses the rows deny_idx[deny_ptr[k] .. deny_ptr[k + 1]) themselves, whatever their
+    // links or types; marked after the exclusion above, before the destination.  deny_ptr == nullptr: nothing is planned,
+    // nothing launched
+    const int64_t *deny_ptr = nullptr;
+    const int32_t *deny_idx = nullptr;
     // the destination: the caller's list tables, top_n wide, or (ev != nullptr) the evaluation records, or (pos != nullptr)
     // the positions and scores of the test ids; at most one of ev and pos is set
     int32_t top_n = 0;
@@ -56,6 +63,8 @@ private:
     DevBuf<int64_t> d_seg_p0, d_seg_p1;
     MemberPlan mplan;
     DevBuf<int32_t> d_pair_slot, d_pair_row;
+    MemberPlan dplan;                  // the deny lists' (slot, row) pairs
+    DevBuf<int32_t> d_deny_slot, d_deny_row;
 };
 
 }  // namespace rwr

@@ -89,6 +89,16 @@ int32_t RankedEnd::prepare(rwr_graph *g, int32_t K, const std::vector<int32_t> &
         RWR_TRY(upload(d_pair_slot, mplan.pair_slot, s));
         RWR_TRY(upload(d_pair_row, mplan.pair_row, s));
     }
+    if (deny_ptr) {
+        dplan = member_plan(g->n, slot_k.size(), slot_k.data(), slots_per_group, K, deny_ptr, deny_idx);
+        if (dplan.check.verdict != EXCLUDE_OK) {                // (api.hip refuses such lists before the call gets here)
+            set_error("%s: deny lists failed their check (verdict %d)", who, (int)dplan.check.verdict);
+            return RWR_E_INVALID;
+        }
+        if (dplan.pair_slot.size() > 0x7FFFFFFFull) { set_error("%s: too many denied nodes", who); return RWR_E_UNSUPPORTED; }
+        RWR_TRY(upload(d_deny_slot, dplan.pair_slot, s));
+        RWR_TRY(upload(d_deny_row, dplan.pair_row, s));
+    }
     return RWR_OK;
 }
 
@@ -109,6 +119,12 @@ int32_t RankedEnd::finish_group(rwr_graph *g, int G, int tg, int grp, size_t q0,
         if (npairs > 0)
             hipLaunchKernelGGL(k_exclude_members, dim3(cdiv((size_t)npairs, 256)), dim3(256), 0, s, g->n, G, (int32_t)npairs,
                                d_pair_slot.p + m0, d_pair_row.p + m0, X);
+    }
+    if (deny_ptr) {
+        const int64_t m0 = dplan.group_off[(size_t)grp], npairs = dplan.group_off[(size_t)grp + 1] - m0;
+        if (npairs > 0)
+            hipLaunchKernelGGL(k_exclude_members, dim3(cdiv((size_t)npairs, 256)), dim3(256), 0, s, g->n, G, (int32_t)npairs,
+                               d_deny_slot.p + m0, d_deny_row.p + m0, X);
     }
     RWR_HIP(hipGetLastError());
     if (ev) RWR_TRY(eval_group(g, *ev, G, tg, q0, X, rows ? rows : g->item_rows.p, rows ? nrows : g->n_items, s));

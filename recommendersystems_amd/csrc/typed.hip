@@ -16,8 +16,10 @@
 // group is evaluated against the seeds' test sets by counting (eval_count.hip over the candidate list) instead of ranked, one
 // record per seed leaves, and no list is written -- so top_n has no limit there.  rwr_recommend_typed_positions_batch
 //  is the third destination: the same counting, the position and score of every test id in the whole list.
-#include "iterate.h"
-#include "ranked_end.h"
+//
+// rwr_recommend_filtered_batch and rwr_recommend_filtered_positions_batch (filter.hip) run this driver with a
+// CallFilter: the candidates narrowed to the caller's pool, the seeds' deny lists marked after the link exclusion.
+#include "filter.h"
 
 namespace rwr {
 
@@ -91,6 +93,12 @@ __global__ __launch_bounds__(CAND_BLOCK) void k_cand_scatter(int32_t n, const ui
     if (pos < total) rows[pos] = cand_block_lo(blockIdx.x) + (int32_t)threadIdx.x;
 }
 
+// ... for filter.hip's call-scoped lists, which are compacted the same way
+void launch_cand_scan(int32_t nb, int32_t *off, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_cand_scan, dim3(1), dim3(CAND_SCAN_CHUNK), 0, s, nb, off);
+}
+
 // The candidate list of node type `type` on the handle's current node set: the cached one, or built now into the entry
 // cand_cache_choose names.  The stream is idle on entry (every entry point ends synchronised) and on return.
 int32_t cand_rows_get(rwr_graph *g, int32_t type, const int32_t **rows, int32_t *nrows)
@@ -132,14 +140,26 @@ int32_t cand_rows_get(rwr_graph *g, int32_t type, const int32_t **rows, int32_t 
 // ---- the driver --------------------------------------------------------------------------------------------------------------
 
 // end: its destination filled in by the entry; the candidates and the exclusion are this call's -- the list of cand_type,
-// the sets {seeds[k]}, the mask, and the seeds' own rows on request (a seed without raw links has no link to mark it by)
-static int32_t typed_body(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type, uint32_t mask,
-                          int32_t exclude_self, RankedEnd &end)
+// the sets {seeds[k]}, the mask, and the seeds' own rows on request (a seed without raw links has no link to mark it by).
+// flt (the filtered entries, filter.hip; nullptr: none): a pool or cand_type FILTER_ANY_TYPE puts the call's own list
+// (filter_rows_build) in the place of the handle's cached one, which is then neither read nor evicted; the deny lists go to
+// the end as its second set description
+int32_t typed_body(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type, uint32_t mask,
+                   int32_t exclude_self, RankedEnd &end, const CallFilter *flt)
 {
     const double t_begin = now_ms();
     const int64_t T = n_iter;
     hipStream_t s = g->stream;
-    RWR_TRY(cand_rows_get(g, cand_type, &end.rows, &end.nrows));   // (before the workspace is sized from what is free)
+    Profile prof(g);
+    DevBuf<int32_t> own_rows;                                    // (declared before idle: released after the call's last synchronisation)
+    // (either list before the workspace is sized from what is free)
+    if (flt && (flt->pool_count >= 0 || cand_type == FILTER_ANY_TYPE)) {
+        RWR_TRY(filter_rows_build(g, cand_type, flt->pool_count, flt->pool_idx, own_rows, &end.nrows, prof));
+        end.rows = own_rows.p;
+    } else {
+        RWR_TRY(cand_rows_get(g, cand_type, &end.rows, &end.nrows));
+    }
+    if (flt) end.deny_ptr = flt->deny_ptr, end.deny_idx = flt->deny_idx;
     const int G = resolve_G(g, K);
     int TG = 1;
     RWR_TRY(ensure_workspace(g, G, K, &TG));
@@ -155,7 +175,6 @@ static int32_t typed_body(rwr_graph *g, const int32_t *seeds, int32_t K, double 
     StreamsIdle idle{g};                                         // (declared after end: ranked_end.h)
     RWR_TRY(end.prepare(g, K, slot_k, (size_t)TG * G, s));
 
-    Profile prof(g);
     for (int t0 = 0, grp = 0; t0 < ntiles; t0 += TG, ++grp) {
         const int tg = (ntiles - t0 < TG) ? (ntiles - t0) : TG;
         const size_t q0 = (size_t)t0 * G;
@@ -182,7 +201,7 @@ int32_t recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K, dou
     RankedEnd end;
     end.who = "rwr_recommend_typed_batch";
     end.top_n = top_n, end.ids = ids, end.scores = scores, end.counts = counts;
-    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end); });
+    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end, nullptr); });
 }
 
 int32_t recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
@@ -195,7 +214,7 @@ int32_t recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32_t K
     RankedEnd end;
     end.who = "rwr_recommend_typed_eval_batch";
     end.ev = &ev;
-    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end); });
+    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end, nullptr); });
 }
 
 int32_t recommend_typed_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type,
@@ -208,7 +227,7 @@ int32_t recommend_typed_positions_batch(rwr_graph *g, const int32_t *seeds, int3
     RankedEnd end;
     end.who = "rwr_recommend_typed_positions_batch";
     end.pos = &pe;
-    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end); });
+    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end, nullptr); });
 }
 
 }  // namespace rwr

@@ -81,6 +81,33 @@ def _pack_tests(testSets, K):
     return tp, ti, np.full(total, -1, dtype=np.int64), np.zeros(total, dtype=np.float64), np.zeros(K, dtype=np.int64)
 
 
+def _pack_filter(pool, deny, K):
+    """The pool and the K deny lists of a filtered entry as it takes them: (pool_count, pool_idx, deny_ptr, deny_idx).
+    pool None: count -1 and no array, an empty pool: count 0; deny None: no arrays, else CSR over the batch positions (at
+    least one element behind each pointer that is passed)"""
+    def idx32(a):                                                # (an array is taken as it is: no trip through a Python list)
+        a = a if isinstance(a, np.ndarray) else np.asarray(list(a), dtype=np.int64)
+        if a.dtype != np.int32 and a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise OverflowError("a node index does not fit int32")
+        return np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+
+    pc, pi, dp, di = -1, None, None, None
+    if pool is not None:
+        flat = idx32(pool)
+        pc = int(flat.shape[0])
+        pi = flat if pc else np.zeros(1, dtype=np.int32)
+    if deny is not None:
+        sets = [idx32(e) for e in deny]
+        if len(sets) != K:
+            raise ValueError(f"deny must hold {K} node lists")
+        dp = np.zeros(K + 1, dtype=np.int64)
+        dp[1:] = np.cumsum([len(e) for e in sets])
+        di = np.ascontiguousarray(np.concatenate(sets + [np.zeros(0, dtype=np.int32)]), dtype=np.int32)
+        if di.shape[0] == 0:
+            di = np.zeros(1, dtype=np.int32)
+    return pc, pi, dp, di
+
+
 def _split_tests(tp, flat):
     return [flat[int(tp[k]):int(tp[k + 1])].copy() for k in range(len(tp) - 1)]
 
@@ -849,6 +876,62 @@ class Recommender:
         pos, sc, ln = self.RecommendationTypedPositionsBatch([int(idxTargetNode)], dampingFactor, nIteration, [testSet], candType,
                                                              exclEdgeTypes, excludeSelf)
         return pos[0], sc[0], int(ln[0])
+
+    def RecommendationFilteredBatch(self, seeds, dampingFactor: float, nIteration: int, topN: int, candType=None,
+                                    exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None):
+        """Top-N lists for K seeds within a candidate pool the caller sets and with a deny list per seed
+        (rwr_recommend_filtered_batch, an addition, see include/rwr.h): (ids[K,topN], scores[K,topN], counts[K]).  candType: the
+        candidates' NodeType, None: nodes of any type; exclEdgeTypes and excludeSelf as in RecommendationTypedBatch; pool: an
+        iterable of node INDICES, any order, duplicates allowed -- only these are ranked, for every seed (None: no pool, []: an
+        empty pool, every list empty); deny: K iterables of node indices, list k never shown to seed k (None: none)."""
+        lib = _lib.load()
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        K = int(seeds.shape[0])
+        mask = 0
+        for t in exclEdgeTypes:
+            mask |= 1 << int(EdgeType(t))
+        pc, pi, dp, di = _pack_filter(pool, deny, K)
+        topN = int(topN)
+        ids = np.zeros((K, max(topN, 0)), dtype=np.int64)
+        sc = np.zeros((K, max(topN, 0)), dtype=np.float64)
+        counts = np.zeros(K, dtype=np.int32)
+        _lib.check(lib.rwr_recommend_filtered_batch(self.graph._handle(), _p(seeds, C.c_int32), K, C.c_float(dampingFactor),
+                                                    int(nIteration), topN, -1 if candType is None else int(candType), mask,
+                                                    1 if excludeSelf else 0, pc, None if pi is None else _p(pi, C.c_int32),
+                                                    None if dp is None else _p(dp, C.c_int64),
+                                                    None if di is None else _p(di, C.c_int32), _p(ids, C.c_int64),
+                                                    _p(sc, C.c_double), _p(counts, C.c_int32)))
+        return ids, sc, counts
+
+    def RecommendationFiltered(self, idxTargetNode: int, dampingFactor: float, nIteration: int, topN: int, candType=None,
+                               exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None) -> List[Tuple[int, float]]:
+        """RecommendationFilteredBatch for one seed, as Recommendation returns its list: [(node id, score), ...]; deny: the
+        seed's one deny list (an iterable of node indices) or None."""
+        ids, sc, counts = self.RecommendationFilteredBatch([int(idxTargetNode)], dampingFactor, nIteration, topN, candType,
+                                                           exclEdgeTypes, excludeSelf, pool, None if deny is None else [deny])
+        c = int(counts[0])
+        return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist()))
+
+    def RecommendationFilteredPositionsBatch(self, seeds, dampingFactor: float, nIteration: int, testSets, candType=None,
+                                             exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None):
+        """The 0-based position and the score of every test id in K seeds' WHOLE filtered lists
+        (rwr_recommend_filtered_positions_batch, an addition, see include/rwr.h): (positions, scores, listLen[K]) as
+        RecommendationTypedPositionsBatch returns them, over the lists RecommendationFilteredBatch defines.  A denied id, an id
+        outside the pool and an id no node carries answer -1 / +0.0."""
+        lib = _lib.load()
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        K = int(seeds.shape[0])
+        mask = 0
+        for t in exclEdgeTypes:
+            mask |= 1 << int(EdgeType(t))
+        pc, pi, dp, di = _pack_filter(pool, deny, K)
+        tp, ti, pos, sc, ln = _pack_tests(testSets, K)
+        _lib.check(lib.rwr_recommend_filtered_positions_batch(
+            self.graph._handle(), _p(seeds, C.c_int32), K, C.c_float(dampingFactor), int(nIteration),
+            -1 if candType is None else int(candType), mask, 1 if excludeSelf else 0, pc, None if pi is None else _p(pi, C.c_int32),
+            None if dp is None else _p(dp, C.c_int64), None if di is None else _p(di, C.c_int32), _p(tp, C.c_int64),
+            _p(ti, C.c_int64), _p(pos, C.c_int64), _p(sc, C.c_double), _p(ln, C.c_int64)))
+        return _split_tests(tp, pos), _split_tests(tp, sc), ln
 
     def RecommendationRestartTypedPositionsBatch(self, restarts, starts, dampingFactor: float, nIteration: int, testSets, candType,
                                                  exclEdgeTypes=(), excludeMembers: bool = False, exclude=None):
