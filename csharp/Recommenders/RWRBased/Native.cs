@@ -68,6 +68,16 @@ namespace Recommenders.RWRBased {
         [DllImport(Lib)] public static extern int rwr_recommend_filtered_positions_batch(GraphHandle g, int[] seeds, int K, float d,
             int n_iter, int cand_type, uint excl_edge_mask, int exclude_self, long pool_count, int[] pool_idx, long[] deny_ptr,
             int[] deny_idx, long[] test_ptr, long[] test_ids, long[] pos_out, double[] score_out, long[] list_len);
+        // the filtered walks with at most group_cap entries per group of nodes in every list: group_of = one label per node
+        // (n values; < 0: never capped; null: no cap, group_cap ignored), group_cap in [1, 8] (Recommender.RecommendationCappedBatch)
+        [DllImport(Lib)] public static extern int rwr_recommend_capped_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,
+            int top_n, int cand_type, uint excl_edge_mask, int exclude_self, long pool_count, int[] pool_idx, long[] deny_ptr,
+            int[] deny_idx, int[] group_of, int group_cap, long[] ids, double[] scores, int[] counts);
+        // ... and the positions and scores of the test entries in the WHOLE capped lists
+        [DllImport(Lib)] public static extern int rwr_recommend_capped_positions_batch(GraphHandle g, int[] seeds, int K, float d,
+            int n_iter, int cand_type, uint excl_edge_mask, int exclude_self, long pool_count, int[] pool_idx, long[] deny_ptr,
+            int[] deny_idx, int[] group_of, int group_cap, long[] test_ptr, long[] test_ids, long[] pos_out, double[] score_out,
+            long[] list_len);
         // Hits / sum of precisions of Experiment.cs:121-128 computed on the device (the ranked list never crosses): one seed,
         // or K seeds with K test sets in CSR form (test set k = test_ids[test_ptr[k] .. test_ptr[k + 1]))
         [DllImport(Lib)] public static extern int rwr_recommend_eval(GraphHandle g, int seed, float d, int n_iter, long[] test_ids,

@@ -247,6 +247,65 @@ namespace Recommenders.RWRBased {
             SplitTests(testPtr, pos, score, out positions, out scores);
         }
 
+        // addition: RecommendationFilteredBatch with a diversity cap -- at most groupCap entries per group of nodes in every list
+        // (rwr_recommend_capped_batch).  groupOf: one label per node of the graph (appended nodes included), any value >= 0 a
+        // group, a negative value "never capped"; null: no cap, the filtered call.  groupCap in [1, 8].  Candidates the mask,
+        // excludeSelf, the pool or a deny list remove do not use up a group's allowance
+        public List<KeyValuePair<long, double>>[] RecommendationCappedBatch(int[] seeds, float dampingFactor, int nIteration, int topN,
+                                                                            NodeType? candType = null,
+                                                                            IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                            bool excludeSelf = false, int[] pool = null,
+                                                                            int[][] deny = null, int[] groupOf = null, int groupCap = 1) {
+            if (topN < 1) throw new System.ArgumentOutOfRangeException("topN", "RecommendationCappedBatch needs topN >= 1");
+            int K = seeds.Length;
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            long[] denyPtr; int[] denyIdx;
+            PackDeny(deny, K, out denyPtr, out denyIdx);
+            long poolCount = pool == null ? -1 : pool.Length;
+            int[] poolIdx = (pool != null && pool.Length == 0) ? new int[1] : pool;
+            var ids = new long[(long)K * topN]; var scores = new double[(long)K * topN]; var counts = new int[K];
+            Native.Check(Native.rwr_recommend_capped_batch(graph.handle, seeds, K, dampingFactor, nIteration, topN, candType.HasValue ? (int)candType.Value : -1, mask, excludeSelf ? 1 : 0, poolCount, poolIdx, denyPtr, denyIdx, groupOf, groupCap, ids, scores, counts));
+            var all = new List<KeyValuePair<long, double>>[K];
+            for (int k = 0; k < K; k++) {
+                all[k] = new List<KeyValuePair<long, double>>(counts[k]);
+                for (int q = 0; q < counts[k]; q++) all[k].Add(new KeyValuePair<long, double>(ids[(long)k * topN + q], scores[(long)k * topN + q]));
+            }
+            return all;
+        }
+
+        // ... and for one seed (deny: its one deny list)
+        public List<KeyValuePair<long, double>> RecommendationCapped(int idxTargetNode, float dampingFactor, int nIteration, int topN,
+                                                                     NodeType? candType = null,
+                                                                     IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                     bool excludeSelf = false, int[] pool = null, int[] deny = null,
+                                                                     int[] groupOf = null, int groupCap = 1) {
+            return RecommendationCappedBatch(new[] { idxTargetNode }, dampingFactor, nIteration, topN, candType, exclEdgeTypes, excludeSelf,
+                                             pool, deny == null ? null : new[] { deny }, groupOf, groupCap)[0];
+        }
+
+        // addition: the 0-based position and the score of every test id in K seeds' WHOLE capped lists
+        // (rwr_recommend_capped_positions_batch): RecommendationFilteredPositionsBatch over the lists RecommendationCappedBatch
+        // defines.  An id the cap drops answers -1 / +0.0, like a denied one; listLen[k] is the capped list's length
+        public void RecommendationCappedPositionsBatch(int[] seeds, float dampingFactor, int nIteration, long[][] testIds,
+                                                       out long[][] positions, out double[][] scores, out long[] listLen,
+                                                       NodeType? candType = null, IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                       bool excludeSelf = false, int[] pool = null, int[][] deny = null,
+                                                       int[] groupOf = null, int groupCap = 1) {
+            int K = seeds.Length;
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            long[] denyPtr; int[] denyIdx;
+            PackDeny(deny, K, out denyPtr, out denyIdx);
+            long poolCount = pool == null ? -1 : pool.Length;
+            int[] poolIdx = (pool != null && pool.Length == 0) ? new int[1] : pool;
+            long[] testPtr, flat;
+            PackTests(testIds, K, out testPtr, out flat);
+            var pos = new long[System.Math.Max(testPtr[K], 1)]; var score = new double[pos.Length]; listLen = new long[K];
+            Native.Check(Native.rwr_recommend_capped_positions_batch(graph.handle, seeds, K, dampingFactor, nIteration, candType.HasValue ? (int)candType.Value : -1, mask, excludeSelf ? 1 : 0, poolCount, poolIdx, denyPtr, denyIdx, groupOf, groupCap, testPtr, flat, pos, score, listLen));
+            SplitTests(testPtr, pos, score, out positions, out scores);
+        }
+
         // addition: the same for K walks with caller-set restart vectors, in the whole lists RecommendationRestartTypedBatch defines
         // (rwr_recommend_restart_typed_positions_batch).  nodes, weights, start, candType, exclEdgeTypes, excludeMembers and
         // exclude as there

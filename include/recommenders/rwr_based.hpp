@@ -411,6 +411,44 @@ public:
         return out;
     }
 
+    // addition: the same lists within a candidate pool, with a deny list per seed and with a diversity cap -- at most groupCap
+    // entries per group of nodes in every list (rwr_recommend_capped_batch).  candType < 0: nodes of any type; pool == nullptr:
+    // no pool, else node INDICES in any order; deny == nullptr: no deny lists, else one list of node indices per seed; groupOf
+    // == nullptr: no cap, else one label per node of the graph (a negative label: never capped); groupCap in [1, 8].
+    // Candidates the mask, excludeSelf, the pool or a deny list remove do not use up a group's allowance
+    std::vector<std::vector<std::pair<int64_t, double>>> recommendCappedBatch(const std::vector<int> &seeds, float dampingFactor,
+                                                                              int nIteration, int topN, int candType,
+                                                                              const std::vector<EdgeType> &exclEdgeTypes,
+                                                                              bool excludeSelf, const std::vector<int32_t> *pool,
+                                                                              const std::vector<std::vector<int32_t>> *deny,
+                                                                              const std::vector<int32_t> *groupOf, int groupCap)
+    {
+        const int32_t K = (int32_t)seeds.size();
+        if (topN < 1) throw std::invalid_argument("recommendCappedBatch: topN must be >= 1");
+        if (deny && deny->size() != seeds.size()) throw std::invalid_argument("recommendCappedBatch: deny must hold one entry per seed");
+        uint32_t mask = 0;
+        for (EdgeType t : exclEdgeTypes) mask |= 1u << (unsigned)t;
+        std::vector<int32_t> sd(seeds.begin(), seeds.end());
+        std::vector<int64_t> dptr((size_t)K + 1, 0);
+        std::vector<int32_t> didx;
+        if (deny)
+            for (int32_t k = 0; k < K; ++k) {
+                didx.insert(didx.end(), (*deny)[(size_t)k].begin(), (*deny)[(size_t)k].end());
+                dptr[(size_t)k + 1] = (int64_t)didx.size();
+            }
+        didx.push_back(0);                                       // (at least one element behind the pointer)
+        const int32_t none = 0;
+        std::vector<int64_t> ids((size_t)K * (size_t)topN);
+        std::vector<double> scores((size_t)K * (size_t)topN);
+        std::vector<int32_t> counts((size_t)K);
+        check(rwr_recommend_capped_batch(graph_.handle(), sd.data(), K, dampingFactor, nIteration, topN, candType < 0 ? -1 : candType, mask, excludeSelf ? 1 : 0, pool ? (int64_t)pool->size() : -1, pool ? (pool->empty() ? &none : pool->data()) : nullptr, deny ? dptr.data() : nullptr, deny ? didx.data() : nullptr, groupOf ? groupOf->data() : nullptr, groupCap, ids.data(), scores.data(), counts.data()));
+        std::vector<std::vector<std::pair<int64_t, double>>> out((size_t)K);
+        for (int32_t k = 0; k < K; ++k)
+            for (int32_t q = 0; q < counts[k]; ++q)
+                out[k].emplace_back(ids[(size_t)k * (size_t)topN + q], scores[(size_t)k * (size_t)topN + q]);
+        return out;
+    }
+
     // addition: Hits and the running-precision sum (Experiment.cs:121-128) of K seeds' WHOLE lists among the nodes of one node
     // type against one test set each, evaluated on the device without writing a ranked list (rwr_recommend_typed_eval_batch).
     // candType, exclEdgeTypes and excludeSelf as in recommendTypedBatch; topN > 0 evaluates the first topN entries of every

@@ -460,6 +460,59 @@ int32_t rwr_recommend_filtered_positions_batch(rwr_graph *g, const int32_t *seed
                                                int64_t *pos_out /* test_ptr[K] */, double *score_out /* test_ptr[K], may be NULL */,
                                                int64_t *list_len /* K, may be NULL */);
 
+/* The filtered walks with a diversity cap: at most group_cap entries per caller-set group of nodes in every seed's list -- "at
+ * most 2 items per author", "at most 3 per category", "at most 1 per thread".  A group is neither a node type nor a link, and
+ * over-fetching cannot stand in for it: one prolific author may fill every entry a call can return.  Everything but the two
+ * new arguments is rwr_recommend_filtered_batch's, the walk, the domain and the layout of the result included.
+ * group_of holds n int32 values, n the graph's current node count (appended nodes included): group_of[i] >= 0 is node i's
+ * group label (any value, labels need not be dense), a negative value means "no group": that node is never capped.
+ * Result k: let F_k be the WHOLE list rwr_recommend_filtered_batch defines for seed k -- the same candidates (cand_type, the
+ * pool), the same exclusions (the link mask, self, the deny list), the same order (score descending, then id descending),
+ * not cut anywhere.  F_k is walked from the top with a counter per label: an entry is kept when its label is negative or its
+ * label's counter is below group_cap, and is then counted; otherwise it is dropped.  The kept entries are C_k; its first
+ * top_n go into row k of ids / scores, counts[k] = entries written.  Ids are identical, and scores bitwise equal, to ranking
+ * the row rwr_model_run returns; the same call gives the same arrays twice.
+ *   - Candidates that the mask, self, the deny list or the pool remove do NOT use up a group's allowance: they are not in F_k,
+ *     and the allowance goes to the group's next candidate.
+ *   - The walk is "keep a candidate iff fewer than group_cap candidates of its label rank before it in F_k": a per-group,
+ *     per-seed top-m, which is the form the device computes.
+ *   - Two candidates of one group may be equal in score AND id (possible after rwr_graph_append_nodes; the rankers leave
+ *     their mutual order unspecified): the cap keeps the one with the smaller node index.  The identity with the greedy walk
+ *     is therefore promised only when (score, id) pairs are distinct within a group.
+ *   - group_of == NULL (group_cap is ignored) is rwr_recommend_filtered_batch: the same arrays.  So is a group_cap of at
+ *     least the largest group's size.  With pool_count < 0, deny_ptr == NULL and cand_type >= 0 as well it is
+ *     rwr_recommend_typed_batch.
+ *   - group_cap in [1, RWR_GROUP_CAP_MAX]: the selection keeps a column's best group_cap keys in registers.
+ *   - Argument errors, all found on the host before any device work and in this order: everything
+ *     rwr_recommend_filtered_batch reports up to and including the deny lists; group_of != NULL with group_cap < 1
+ *     (RWR_E_INVALID); the limits -- top_n as there, then group_cap > RWR_GROUP_CAP_MAX (both RWR_E_UNSUPPORTED with the
+ *     limit in the message); the domain.  A refused call writes nothing.
+ *   - Not here: restart-vector walks; a Hits / AP destination of its own (the positions below give every metric); a cap per
+ *     group or several labellings at once; labels kept with the handle. */
+#define RWR_GROUP_CAP_MAX 8
+int32_t rwr_recommend_capped_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                   int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,
+                                   int64_t pool_count, const int32_t *pool_idx,
+                                   const int64_t *deny_ptr /* K + 1, may be NULL */, const int32_t *deny_idx,
+                                   const int32_t *group_of /* n, may be NULL */, int32_t group_cap,
+                                   int64_t *ids, double *scores, int32_t *counts);
+/* ... and the positions and scores of test ids in the WHOLE capped lists C_k: rwr_recommend_filtered_positions_batch over the
+ * lists rwr_recommend_capped_batch defines.  A candidate the cap drops answers -1 / +0.0, like a denied one; a kept one
+ * answers its position in C_k; list_len[k] = |C_k|.
+ *   - group_of == NULL is rwr_recommend_filtered_positions_batch: the same arrays.
+ *   - Argument errors, on the host before any device work and in this order: those of rwr_recommend_filtered_positions_batch
+ *     up to and including the test sets; group_of != NULL with group_cap < 1 (RWR_E_INVALID); group_cap >
+ *     RWR_GROUP_CAP_MAX (RWR_E_UNSUPPORTED); the domain.  A refused call writes nothing.
+ *   - Not here: what rwr_recommend_capped_batch names. */
+int32_t rwr_recommend_capped_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter,
+                                             int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,
+                                             int64_t pool_count, const int32_t *pool_idx,
+                                             const int64_t *deny_ptr /* K + 1, may be NULL */, const int32_t *deny_idx,
+                                             const int32_t *group_of /* n, may be NULL */, int32_t group_cap,
+                                             const int64_t *test_ptr, const int64_t *test_ids,
+                                             int64_t *pos_out /* test_ptr[K] */, double *score_out /* test_ptr[K], may be NULL */,
+                                             int64_t *list_len /* K, may be NULL */);
+
 /* ---- Model ---------------------------------------------------------------------------
  * Backs the public class Model: ctor (Model.cs:33-50 personalised, seed >= 0;
  * Model.cs:14-31 global, seed == -1), run(int) / run(double) / run() (Model.cs:68-73,

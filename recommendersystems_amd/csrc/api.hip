@@ -6,6 +6,7 @@
 #include <vector>
 #include <string.h>
 
+#include "cap_plan.h"
 #include "eval_plan.h"
 #include "exclude_plan.h"
 #include "filter_plan.h"
@@ -277,6 +278,33 @@ static int32_t filter_verdict_status(const char *who, const FilterCheck &c, int3
     return RWR_OK;
 }
 
+// A CapCheck's verdict on the arguments of a capped entry (CAP_NOOP is the caller's): the filtered part through
+// filter_verdict_status, then the cap's own two refusals around top_n's limit
+static int32_t cap_verdict_status(const char *who, const CapCheck &c, int32_t n, int32_t top_n, int32_t cand_type,
+                                  uint32_t excl_edge_mask, const char *null_arg, const char *top_n_hint, const int64_t *deny_ptr,
+                                  const int64_t *test_ptr, int32_t group_cap)
+{
+    switch (c.verdict) {
+        case CAP_OK:
+        case CAP_NOOP: break;
+        case CAP_FILTER:
+            return filter_verdict_status(who, c.filter, n, top_n, cand_type, excl_edge_mask, null_arg, top_n_hint, deny_ptr, test_ptr);
+        case CAP_BAD_CAP:
+            set_error("%s: group_cap %d is below 1", who, group_cap);
+            return RWR_E_INVALID;
+        case CAP_TOP_N_LIMIT: {
+            FilterCheck f;
+            f.verdict = FILTER_TOP_N_LIMIT;
+            return filter_verdict_status(who, f, n, top_n, cand_type, excl_edge_mask, null_arg, top_n_hint, deny_ptr, test_ptr);
+        }
+        case CAP_CAP_LIMIT:
+            set_error("%s: group_cap %d is beyond the limit of RWR_GROUP_CAP_MAX = %d entries per group", who, group_cap,
+                      (int)RWR_GROUP_CAP_MAX);
+            return RWR_E_UNSUPPORTED;
+    }
+    return RWR_OK;
+}
+
 // ... and the graph and damping factor of the Recommendation entries: the exclusion marker (-1) and the ranking keys assume
 // scores >= 0.  model_entry: the entry that runs what this one refuses
 static int32_t check_ranked_domain(const char *who, const rwr_graph *g, double d, const char *model_entry)
@@ -534,6 +562,47 @@ int32_t rwr_recommend_filtered_positions_batch(rwr_graph *g, const int32_t *seed
     return bound(who, g, [&] {
         return recommend_filtered_positions_batch(g, seeds, K, (double)d, n_iter, cand_type, excl_edge_mask, exclude_self, pool_count,
                                                   pool_idx, deny_ptr, deny_idx, test_ptr, test_ids, pos_out, score_out, list_len);
+    });
+}
+
+int32_t rwr_recommend_capped_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                   int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count,
+                                   const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of,
+                                   int32_t group_cap, int64_t *ids, double *scores, int32_t *counts)
+{
+    static const char *const who = "rwr_recommend_capped_batch";
+    g_err[0] = 0;
+    const CapCheck c = cap_check(g != nullptr, g ? g->n : 0, seeds, K, top_n, rank_select_max_k(), cand_type, excl_edge_mask,
+                                 ids && scores && counts, pool_count, pool_idx, deny_ptr, deny_idx, group_of, group_cap);
+    if (c.verdict == CAP_NOOP) return RWR_OK;
+    RWR_TRY(cap_verdict_status(who, c, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds, ids, scores or counts",
+                               " (rwr_recommend_capped_positions_batch answers for whole lists)", deny_ptr, nullptr, group_cap));
+    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    return bound(who, g, [&] {
+        return recommend_capped_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, pool_count,
+                                      pool_idx, deny_ptr, deny_idx, group_of, group_cap, ids, scores, counts);
+    });
+}
+
+int32_t rwr_recommend_capped_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter,
+                                             int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count,
+                                             const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx,
+                                             const int32_t *group_of, int32_t group_cap, const int64_t *test_ptr,
+                                             const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len)
+{
+    static const char *const who = "rwr_recommend_capped_positions_batch";
+    g_err[0] = 0;
+    const CapCheck c = cap_positions_check(g != nullptr, g ? g->n : 0, seeds, K, cand_type, excl_edge_mask, pool_count, pool_idx,
+                                           deny_ptr, deny_idx, test_ptr, test_ids, pos_out, group_of, group_cap);
+    if (c.verdict == CAP_NOOP) return RWR_OK;
+    RWR_TRY(cap_verdict_status(who, c, g ? g->n : 0, 0, cand_type, excl_edge_mask, "seeds", nullptr, deny_ptr, test_ptr, group_cap));
+    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    return bound(who, g, [&] {
+        return recommend_capped_positions_batch(g, seeds, K, (double)d, n_iter, cand_type, excl_edge_mask, exclude_self, pool_count,
+                                                pool_idx, deny_ptr, deny_idx, group_of, group_cap, test_ptr, test_ids, pos_out, score_out,
+                                                list_len);
     });
 }
 

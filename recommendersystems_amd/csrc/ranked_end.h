@@ -3,7 +3,7 @@
 // group's X[tile][n][G] are marked with -1; then the candidates are ranked into K x top_n lists, evaluated against test
 // sets by counting, or the test ids' positions in the whole lists are found by the same counting; after the last group the
 // result is copied back once.  Three independent descriptions say which end: the candidates, the exclusion, the destination;
-// the filtered entries add a fourth, the seeds' deny lists.
+// the filtered entries add a fourth, the seeds' deny lists, the capped entries a fifth, the group cap.
 //
 // Lifetime: the object (and the EvalEnd or PosEnd it points to) is declared before the driver's StreamsIdle, so the device copies of
 // its plans outlive the kernels that read them, on error paths too.
@@ -16,6 +16,7 @@
 namespace rwr {
 
 struct Profile;   // iterate.h
+struct GroupCap;  // group_cap.h
 
 struct RankedEnd {
     const char *who = "";              // the entry point, for the messages
@@ -38,6 +39,10 @@ struct RankedEnd {
     // nothing launched
     const int64_t *deny_ptr = nullptr;
     const int32_t *deny_idx = nullptr;
+    // the group cap (the capped entries): at most m candidates per caller-set group in every slot's list -- the
+    // cells outside their group's best m of a column are marked after the deny lists, before the destination.  The driver
+    // builds the object's tables (cap_build) once the candidate list exists.  nullptr: nothing is built, nothing launched
+    GroupCap *cap = nullptr;
     // the destination: the caller's list tables, top_n wide, or (ev != nullptr) the evaluation records, or (pos != nullptr)
     // the positions and scores of the test ids; at most one of ev and pos is set
     int32_t top_n = 0;

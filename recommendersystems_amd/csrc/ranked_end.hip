@@ -1,6 +1,7 @@
 // The ranked end of a batch (ranked_end.h): the exclusion kernels, and the three operations around a driver's group loop.
 #include "ranked_end.h"
 
+#include "group_cap.h"
 #include "iterate.h"
 
 namespace rwr {
@@ -127,6 +128,7 @@ int32_t RankedEnd::finish_group(rwr_graph *g, int G, int tg, int grp, size_t q0,
                                d_deny_slot.p + m0, d_deny_row.p + m0, X);
     }
     RWR_HIP(hipGetLastError());
+    if (cap) RWR_TRY(cap_group(g, *cap, G, tg, slot_k, X, s));
     if (ev) RWR_TRY(eval_group(g, *ev, G, tg, q0, X, rows ? rows : g->item_rows.p, rows ? nrows : g->n_items, s));
     else if (pos) RWR_TRY(pos_group(g, *pos, G, tg, q0, X, rows ? rows : g->item_rows.p, rows ? nrows : g->n_items, s));
     else if (!rows) RWR_TRY(rank_group(g, G, tg, slot_k, slot_k, top_n, X, s));

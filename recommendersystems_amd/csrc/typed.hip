@@ -19,7 +19,10 @@
 //
 // rwr_recommend_filtered_batch and rwr_recommend_filtered_positions_batch (filter.hip) run this driver with a
 // CallFilter: the candidates narrowed to the caller's pool, the seeds' deny lists marked after the link exclusion.
+// rwr_recommend_capped_batch and rwr_recommend_capped_positions_batch (group_cap.hip) add a GroupCap to the
+// end: built here once the candidate list exists, applied by the end after the deny marks.
 #include "filter.h"
+#include "group_cap.h"
 
 namespace rwr {
 
@@ -143,7 +146,8 @@ int32_t cand_rows_get(rwr_graph *g, int32_t type, const int32_t **rows, int32_t 
 // the sets {seeds[k]}, the mask, and the seeds' own rows on request (a seed without raw links has no link to mark it by).
 // flt (the filtered entries, filter.hip; nullptr: none): a pool or cand_type FILTER_ANY_TYPE puts the call's own list
 // (filter_rows_build) in the place of the handle's cached one, which is then neither read nor evicted; the deny lists go to
-// the end as its second set description
+// the end as its second set description.  end.cap (the capped entries, group_cap.hip; nullptr: none): its tables are built from
+// whichever list serves the call -- the cached one is only read
 int32_t typed_body(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type, uint32_t mask,
                    int32_t exclude_self, RankedEnd &end, const CallFilter *flt)
 {
@@ -162,6 +166,10 @@ int32_t typed_body(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int3
     if (flt) end.deny_ptr = flt->deny_ptr, end.deny_idx = flt->deny_idx;
     const int G = resolve_G(g, K);
     int TG = 1;
+    if (end.cap) {                                               // (a tile group holds at most this many tiles: ensure_workspace)
+        const int ntiles_all = (int)cdiv((size_t)K, (size_t)G), most = g->opts.tile_group > 0 ? g->opts.tile_group : 192;
+        RWR_TRY(cap_build(g, *end.cap, end.rows, end.nrows, G, ntiles_all < most ? ntiles_all : most, prof));
+    }
     RWR_TRY(ensure_workspace(g, G, K, &TG));
     const int ntiles = (int)cdiv((size_t)K, (size_t)G);
     std::vector<int32_t> slot_k;

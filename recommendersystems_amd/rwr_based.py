@@ -108,6 +108,18 @@ def _pack_filter(pool, deny, K):
     return pc, pi, dp, di
 
 
+def _pack_groups(groupOf):
+    """The labels of a capped entry as it takes them: an int32 array of one label per node (an array is taken as it is, no
+    trip through a Python list), or None for no cap"""
+    if groupOf is None:
+        return None
+    a = groupOf if isinstance(groupOf, np.ndarray) else np.asarray(list(groupOf), dtype=np.int64)
+    if a.dtype != np.int32 and a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise OverflowError("a group label does not fit int32")
+    a = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    return a if a.size else np.zeros(1, dtype=np.int32)
+
+
 def _split_tests(tp, flat):
     return [flat[int(tp[k]):int(tp[k + 1])].copy() for k in range(len(tp) - 1)]
 
@@ -931,6 +943,73 @@ class Recommender:
             -1 if candType is None else int(candType), mask, 1 if excludeSelf else 0, pc, None if pi is None else _p(pi, C.c_int32),
             None if dp is None else _p(dp, C.c_int64), None if di is None else _p(di, C.c_int32), _p(tp, C.c_int64),
             _p(ti, C.c_int64), _p(pos, C.c_int64), _p(sc, C.c_double), _p(ln, C.c_int64)))
+        return _split_tests(tp, pos), _split_tests(tp, sc), ln
+
+    def RecommendationCappedBatch(self, seeds, dampingFactor: float, nIteration: int, topN: int, candType=None, exclEdgeTypes=(),
+                                  excludeSelf: bool = False, pool=None, deny=None, groupOf=None, groupCap: int = 1):
+        """RecommendationFilteredBatch with a diversity cap: at most groupCap entries per group of nodes in every list
+        (rwr_recommend_capped_batch, an addition, see include/rwr.h): (ids[K,topN], scores[K,topN], counts[K]).  groupOf: one
+        int label per node of the graph (appended nodes included), any value >= 0 a group, a negative value "never capped";
+        None: no cap, the filtered call.  groupCap in [1, 8].  Candidates the mask, excludeSelf, the pool or a deny list remove
+        do not use up a group's allowance."""
+        lib = _lib.load()
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        K = int(seeds.shape[0])
+        mask = 0
+        for t in exclEdgeTypes:
+            mask |= 1 << int(EdgeType(t))
+        pc, pi, dp, di = _pack_filter(pool, deny, K)
+        go = _pack_groups(groupOf)
+        if go is not None and go.shape[0] < self.graph.stats()["n"]:
+            raise ValueError("groupOf must hold one label per node of the graph")
+        topN = int(topN)
+        ids = np.zeros((K, max(topN, 0)), dtype=np.int64)
+        sc = np.zeros((K, max(topN, 0)), dtype=np.float64)
+        counts = np.zeros(K, dtype=np.int32)
+        _lib.check(lib.rwr_recommend_capped_batch(self.graph._handle(), _p(seeds, C.c_int32), K, C.c_float(dampingFactor),
+                                                  int(nIteration), topN, -1 if candType is None else int(candType), mask,
+                                                  1 if excludeSelf else 0, pc, None if pi is None else _p(pi, C.c_int32),
+                                                  None if dp is None else _p(dp, C.c_int64),
+                                                  None if di is None else _p(di, C.c_int32),
+                                                  None if go is None else _p(go, C.c_int32), int(groupCap), _p(ids, C.c_int64),
+                                                  _p(sc, C.c_double), _p(counts, C.c_int32)))
+        return ids, sc, counts
+
+    def RecommendationCapped(self, idxTargetNode: int, dampingFactor: float, nIteration: int, topN: int, candType=None,
+                             exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None, groupOf=None,
+                             groupCap: int = 1) -> List[Tuple[int, float]]:
+        """RecommendationCappedBatch for one seed, as Recommendation returns its list: [(node id, score), ...]; deny: the
+        seed's one deny list (an iterable of node indices) or None."""
+        ids, sc, counts = self.RecommendationCappedBatch([int(idxTargetNode)], dampingFactor, nIteration, topN, candType,
+                                                         exclEdgeTypes, excludeSelf, pool, None if deny is None else [deny],
+                                                         groupOf, groupCap)
+        c = int(counts[0])
+        return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist()))
+
+    def RecommendationCappedPositionsBatch(self, seeds, dampingFactor: float, nIteration: int, testSets, candType=None,
+                                           exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None, groupOf=None,
+                                           groupCap: int = 1):
+        """The 0-based position and the score of every test id in K seeds' WHOLE capped lists
+        (rwr_recommend_capped_positions_batch, an addition, see include/rwr.h): (positions, scores, listLen[K]) as
+        RecommendationFilteredPositionsBatch returns them, over the lists RecommendationCappedBatch defines.  An id the cap
+        drops answers -1 / +0.0, like a denied one; listLen[k] is the capped list's length."""
+        lib = _lib.load()
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        K = int(seeds.shape[0])
+        mask = 0
+        for t in exclEdgeTypes:
+            mask |= 1 << int(EdgeType(t))
+        pc, pi, dp, di = _pack_filter(pool, deny, K)
+        go = _pack_groups(groupOf)
+        if go is not None and go.shape[0] < self.graph.stats()["n"]:
+            raise ValueError("groupOf must hold one label per node of the graph")
+        tp, ti, pos, sc, ln = _pack_tests(testSets, K)
+        _lib.check(lib.rwr_recommend_capped_positions_batch(
+            self.graph._handle(), _p(seeds, C.c_int32), K, C.c_float(dampingFactor), int(nIteration),
+            -1 if candType is None else int(candType), mask, 1 if excludeSelf else 0, pc, None if pi is None else _p(pi, C.c_int32),
+            None if dp is None else _p(dp, C.c_int64), None if di is None else _p(di, C.c_int32),
+            None if go is None else _p(go, C.c_int32), int(groupCap), _p(tp, C.c_int64), _p(ti, C.c_int64), _p(pos, C.c_int64),
+            _p(sc, C.c_double), _p(ln, C.c_int64)))
         return _split_tests(tp, pos), _split_tests(tp, sc), ln
 
     def RecommendationRestartTypedPositionsBatch(self, restarts, starts, dampingFactor: float, nIteration: int, testSets, candType,

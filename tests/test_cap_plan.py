@@ -1,0 +1,22 @@
+"""CPU-side check of the group cap's host plan (recommendersystems_amd/csrc/cap_plan.h): the order of the sort keys
+(label << 32 | row), the chunk and segment tables for segment lengths 0, 1, m, m + 1, CAP_CHUNK - 1, CAP_CHUNK, CAP_CHUNK + 1 and
+3 x CAP_CHUNK + 1 (and at small chunks), all labels negative / one label for everything / every row its own label, the selection
+model against a brute-force sort for m = 1..8 (all-zero columns: ties by id; equal (score, id) pairs: ties by row), and the
+verdicts on the arguments of rwr_recommend_capped_batch and rwr_recommend_capped_positions_batch in their documented order with
+all later faults present.  tests/cpp/cap_plan_check.cpp, a program of its own built against the header alone with the address
+and undefined-behaviour sanitizers, compares all of them with brute-force loops.  No library, no Python extension and no GPU
+are involved."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_cap_plan(tmp_path):
+    exe = tmp_path / "cap_plan_check"
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-I",
+                           os.path.join(ROOT, "recommendersystems_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "cap_plan_check.cpp"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip().endswith("0 failures"), r.stdout
