@@ -73,6 +73,12 @@ namespace Recommenders.RWRBased {
         [DllImport(Lib)] public static extern int rwr_recommend_capped_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,
             int top_n, int cand_type, uint excl_edge_mask, int exclude_self, long pool_count, int[] pool_idx, long[] deny_ptr,
             int[] deny_idx, int[] group_of, int group_cap, long[] ids, double[] scores, int[] counts);
+        // the capped lists with the reasons of every entry: nodes (K x top_n, may be null), why_src / why_term (K x top_n x n_why,
+        // n_why in [0, 8]), why_total (K x top_n, may be null) (Recommender.RecommendationExplainedBatch)
+        [DllImport(Lib)] public static extern int rwr_recommend_explained_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,
+            int top_n, int cand_type, uint excl_edge_mask, int exclude_self, long pool_count, int[] pool_idx, long[] deny_ptr,
+            int[] deny_idx, int[] group_of, int group_cap, int n_why, long[] ids, double[] scores, int[] counts, int[] nodes,
+            int[] why_src, double[] why_term, long[] why_total);
         // ... and the positions and scores of the test entries in the WHOLE capped lists
         [DllImport(Lib)] public static extern int rwr_recommend_capped_positions_batch(GraphHandle g, int[] seeds, int K, float d,
             int n_iter, int cand_type, uint excl_edge_mask, int exclude_self, long pool_count, int[] pool_idx, long[] deny_ptr,

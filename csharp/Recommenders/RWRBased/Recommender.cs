@@ -284,6 +284,51 @@ namespace Recommenders.RWRBased {
                                              pool, deny == null ? null : new[] { deny }, groupOf, groupCap)[0];
         }
 
+        // addition: RecommendationCappedBatch with the reasons of every list entry (rwr_recommend_explained_batch).  nodes[k * topN + j]:
+        // the node index of entry j of seed k (-1 behind the list's end); whySrc / whyTerm[(k * topN + j) * nWhy + i]: the source node
+        // and the value of the entry's i-th largest in-link addend fl(fl((1 - d) * previousRank[u]) * weight(u -> v)) (-1 / +0.0
+        // where fewer are positive); whyTotal[k * topN + j]: the number of positive addends.  nWhy in [0, 8]
+        public List<KeyValuePair<long, double>>[] RecommendationExplainedBatch(int[] seeds, float dampingFactor, int nIteration, int topN,
+                                                                               int nWhy, out int[] nodes, out int[] whySrc,
+                                                                               out double[] whyTerm, out long[] whyTotal,
+                                                                               NodeType? candType = null,
+                                                                               IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                               bool excludeSelf = false, int[] pool = null,
+                                                                               int[][] deny = null, int[] groupOf = null, int groupCap = 1) {
+            if (topN < 1) throw new System.ArgumentOutOfRangeException("topN", "RecommendationExplainedBatch needs topN >= 1");
+            if (nWhy < 0 || nWhy > 8) throw new System.ArgumentOutOfRangeException("nWhy", "RecommendationExplainedBatch needs nWhy in [0, 8]");
+            int K = seeds.Length;
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            long[] denyPtr; int[] denyIdx;
+            PackDeny(deny, K, out denyPtr, out denyIdx);
+            long poolCount = pool == null ? -1 : pool.Length;
+            int[] poolIdx = (pool != null && pool.Length == 0) ? new int[1] : pool;
+            var ids = new long[(long)K * topN]; var scores = new double[(long)K * topN]; var counts = new int[K];
+            nodes = new int[(long)K * topN]; whyTotal = new long[(long)K * topN];
+            whySrc = new int[(long)K * topN * nWhy + 1]; whyTerm = new double[(long)K * topN * nWhy + 1];
+            Native.Check(Native.rwr_recommend_explained_batch(graph.handle, seeds, K, dampingFactor, nIteration, topN, candType.HasValue ? (int)candType.Value : -1, mask, excludeSelf ? 1 : 0, poolCount, poolIdx, denyPtr, denyIdx, groupOf, groupCap, nWhy, ids, scores, counts, nodes, whySrc, whyTerm, whyTotal));
+            System.Array.Resize(ref whySrc, K * topN * nWhy); System.Array.Resize(ref whyTerm, K * topN * nWhy);
+            var all = new List<KeyValuePair<long, double>>[K];
+            for (int k = 0; k < K; k++) {
+                all[k] = new List<KeyValuePair<long, double>>(counts[k]);
+                for (int q = 0; q < counts[k]; q++) all[k].Add(new KeyValuePair<long, double>(ids[(long)k * topN + q], scores[(long)k * topN + q]));
+            }
+            return all;
+        }
+
+        // ... and for one seed (deny: its one deny list)
+        public List<KeyValuePair<long, double>> RecommendationExplained(int idxTargetNode, float dampingFactor, int nIteration, int topN,
+                                                                        int nWhy, out int[] nodes, out int[] whySrc, out double[] whyTerm,
+                                                                        out long[] whyTotal, NodeType? candType = null,
+                                                                        IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                        bool excludeSelf = false, int[] pool = null, int[] deny = null,
+                                                                        int[] groupOf = null, int groupCap = 1) {
+            return RecommendationExplainedBatch(new[] { idxTargetNode }, dampingFactor, nIteration, topN, nWhy, out nodes, out whySrc,
+                                                out whyTerm, out whyTotal, candType, exclEdgeTypes, excludeSelf, pool,
+                                                deny == null ? null : new[] { deny }, groupOf, groupCap)[0];
+        }
+
         // addition: the 0-based position and the score of every test id in K seeds' WHOLE capped lists
         // (rwr_recommend_capped_positions_batch): RecommendationFilteredPositionsBatch over the lists RecommendationCappedBatch
         // defines.  An id the cap drops answers -1 / +0.0, like a denied one; listLen[k] is the capped list's length

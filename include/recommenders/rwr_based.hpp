@@ -449,6 +449,47 @@ public:
         return out;
     }
 
+    // addition: recommendCappedBatch with the reasons of every list entry (rwr_recommend_explained_batch): per entry its node
+    // index, the source node and the value of its nWhy (0 to 8) largest in-link addends fl(fl((1 - d) * previousRank[u]) *
+    // weight(u -> v)), largest first (-1 / +0.0 where fewer are positive), and the number of positive addends.  All tables are
+    // K x topN (x nWhy) row-major, cells behind a list's end hold -1 / -1 / +0.0 / 0.  The other arguments as in
+    // recommendCappedBatch
+    struct Explained {
+        std::vector<int64_t> ids;
+        std::vector<double> scores;
+        std::vector<int32_t> counts, nodes, whySrc;
+        std::vector<double> whyTerm;
+        std::vector<int64_t> whyTotal;
+    };
+    Explained recommendExplainedBatch(const std::vector<int> &seeds, float dampingFactor, int nIteration, int topN, int nWhy, int candType,
+                                      const std::vector<EdgeType> &exclEdgeTypes, bool excludeSelf, const std::vector<int32_t> *pool,
+                                      const std::vector<std::vector<int32_t>> *deny, const std::vector<int32_t> *groupOf, int groupCap)
+    {
+        const int32_t K = (int32_t)seeds.size();
+        if (topN < 1) throw std::invalid_argument("recommendExplainedBatch: topN must be >= 1");
+        if (nWhy < 0 || nWhy > RWR_WHY_MAX) throw std::invalid_argument("recommendExplainedBatch: nWhy must lie in [0, 8]");
+        if (deny && deny->size() != seeds.size()) throw std::invalid_argument("recommendExplainedBatch: deny must hold one entry per seed");
+        uint32_t mask = 0;
+        for (EdgeType t : exclEdgeTypes) mask |= 1u << (unsigned)t;
+        std::vector<int32_t> sd(seeds.begin(), seeds.end());
+        std::vector<int64_t> dptr((size_t)K + 1, 0);
+        std::vector<int32_t> didx;
+        if (deny)
+            for (int32_t k = 0; k < K; ++k) {
+                didx.insert(didx.end(), (*deny)[(size_t)k].begin(), (*deny)[(size_t)k].end());
+                dptr[(size_t)k + 1] = (int64_t)didx.size();
+            }
+        didx.push_back(0);                                       // (at least one element behind the pointer)
+        const int32_t none = 0;
+        const size_t cells = (size_t)K * (size_t)topN;
+        Explained e;
+        e.ids.resize(cells), e.scores.resize(cells), e.counts.resize((size_t)K), e.nodes.resize(cells), e.whyTotal.resize(cells);
+        e.whySrc.resize(cells * (size_t)nWhy + 1), e.whyTerm.resize(cells * (size_t)nWhy + 1);
+        check(rwr_recommend_explained_batch(graph_.handle(), sd.data(), K, dampingFactor, nIteration, topN, candType < 0 ? -1 : candType, mask, excludeSelf ? 1 : 0, pool ? (int64_t)pool->size() : -1, pool ? (pool->empty() ? &none : pool->data()) : nullptr, deny ? dptr.data() : nullptr, deny ? didx.data() : nullptr, groupOf ? groupOf->data() : nullptr, groupCap, nWhy, e.ids.data(), e.scores.data(), e.counts.data(), e.nodes.data(), e.whySrc.data(), e.whyTerm.data(), e.whyTotal.data()));
+        e.whySrc.resize(cells * (size_t)nWhy), e.whyTerm.resize(cells * (size_t)nWhy);
+        return e;
+    }
+
     // addition: Hits and the running-precision sum (Experiment.cs:121-128) of K seeds' WHOLE lists among the nodes of one node
     // type against one test set each, evaluated on the device without writing a ranked list (rwr_recommend_typed_eval_batch).
     // candType, exclEdgeTypes and excludeSelf as in recommendTypedBatch; topN > 0 evaluates the first topN entries of every

@@ -513,6 +513,49 @@ int32_t rwr_recommend_capped_positions_batch(rwr_graph *g, const int32_t *seeds,
                                              int64_t *pos_out /* test_ptr[K] */, double *score_out /* test_ptr[K], may be NULL */,
                                              int64_t *list_len /* K, may be NULL */);
 
+/* "Why is this entry here?" -- the capped lists with, per entry, its node index, its largest in-link addends and the number
+ * of positive ones: "because users like you liked it", "liked by 37 users in your neighbourhood".  Everything up to group_cap
+ * is rwr_recommend_capped_batch's: the walk, the domain, the candidates, every exclusion, the cap, the order and the layout of
+ * ids / scores / counts, which are always bitwise those of the capped entry.  So the one entry also covers the filtered and
+ * the typed lists (group_of == NULL, pool_count < 0, deny_ptr == NULL).
+ *   - nodes[k * top_n + j] = the node index of list entry j of seed k (ids need not be unique, so the index cannot be
+ *     recovered from the id).  Among candidates of one column with bitwise equal score and equal id the smaller node index
+ *     ranks first -- the cap's choice -- which makes the order total: the same call gives the same arrays twice.  Cells at
+ *     j >= counts[k] hold -1.
+ *   - The in-list of an entry: let T = n_iter, v = nodes[k][j], y = the rank row rwr_model_run(g, seeds[k], (double)d,
+ *     RWR_RUN_ITERATIONS, T - 1, ...) returns and c1 = 1 - (double)d.  The in-entries of v are the explicit links u -> v in
+ *     the order source ascending, then list position ascending (the addend order of Model.deliverRanks).  Parallel links are
+ *     separate entries; UNDEFINED links are not entries.  In-entry e has the addend a_e = fl(fl(c1 * y[u_e]) * w_e), w_e the
+ *     normalised weight: two separately rounded products, no FMA.  For v other than the seed, scores[k][j] is the in-order
+ *     sum of the a_e, bit for bit.
+ *   - The reasons of (k, j) are the in-entries with a_e > 0, ordered by a_e descending, then in-list position ascending.  The
+ *     first n_why of them go to why_src[(k * top_n + j) * n_why + .] (the source's node index) and why_term[...] (a_e,
+ *     bitwise); unused cells hold -1 / +0.0.  why_total[k * top_n + j] = the number of in-entries with a_e > 0.
+ *   - T <= 0: no step ran, so there are no reasons -- every why_total is 0 and every cell unused; the lists are still the
+ *     capped entry's.
+ *   - When v is the seed itself (exclude_self == 0 and a matching candidate type) the reasons cover its link addends only:
+ *     the restart share of the seed's rank (Model.cs:91-97) is not a link and is not listed.
+ *   - n_why in [0, RWR_WHY_MAX].  n_why == 0 ignores why_src and why_term, which may be NULL; nodes and why_total may be
+ *     NULL.  With n_why == 0, nodes == NULL and why_total == NULL the entry is rwr_recommend_capped_batch, launch for launch.
+ *   - Argument errors, all found on the host before any device work and in this order: everything
+ *     rwr_recommend_capped_batch reports up to and including group_cap < 1; n_why < 0, or a NULL why_src / why_term with
+ *     n_why > 0 (RWR_E_INVALID); the limits -- top_n, group_cap, then n_why > RWR_WHY_MAX (each RWR_E_UNSUPPORTED with the
+ *     limit in the message); the domain.  A refused call writes nothing.
+ *   - Not here: restart-vector walks; two-hop reasons ("because you liked A"); the edge type of a reason (the caller has
+ *     why_src and its own lists); reasons for the evaluating and the positions destinations. */
+#define RWR_WHY_MAX 8
+int32_t rwr_recommend_explained_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                      int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,
+                                      int64_t pool_count, const int32_t *pool_idx,
+                                      const int64_t *deny_ptr /* K + 1, may be NULL */, const int32_t *deny_idx,
+                                      const int32_t *group_of /* n, may be NULL */, int32_t group_cap,
+                                      int32_t n_why,
+                                      int64_t *ids, double *scores, int32_t *counts,
+                                      int32_t *nodes      /* K x top_n, may be NULL */,
+                                      int32_t *why_src    /* K x top_n x n_why */,
+                                      double  *why_term   /* K x top_n x n_why */,
+                                      int64_t *why_total  /* K x top_n, may be NULL */);
+
 /* ---- Model ---------------------------------------------------------------------------
  * Backs the public class Model: ctor (Model.cs:33-50 personalised, seed >= 0;
  * Model.cs:14-31 global, seed == -1), run(int) / run(double) / run() (Model.cs:68-73,

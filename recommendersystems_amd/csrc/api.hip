@@ -9,6 +9,7 @@
 #include "cap_plan.h"
 #include "eval_plan.h"
 #include "exclude_plan.h"
+#include "explain_plan.h"
 #include "filter_plan.h"
 #include "handle.h"
 #include "member_plan.h"
@@ -603,6 +604,48 @@ int32_t rwr_recommend_capped_positions_batch(rwr_graph *g, const int32_t *seeds,
         return recommend_capped_positions_batch(g, seeds, K, (double)d, n_iter, cand_type, excl_edge_mask, exclude_self, pool_count,
                                                 pool_idx, deny_ptr, deny_idx, group_of, group_cap, test_ptr, test_ids, pos_out, score_out,
                                                 list_len);
+    });
+}
+
+int32_t rwr_recommend_explained_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                      int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count,
+                                      const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of,
+                                      int32_t group_cap, int32_t n_why, int64_t *ids, double *scores, int32_t *counts, int32_t *nodes,
+                                      int32_t *why_src, double *why_term, int64_t *why_total)
+{
+    static const char *const who = "rwr_recommend_explained_batch";
+    g_err[0] = 0;
+    const ExplainCheck c = explain_check(g != nullptr, g ? g->n : 0, seeds, K, top_n, rank_select_max_k(), cand_type, excl_edge_mask,
+                                         ids && scores && counts, pool_count, pool_idx, deny_ptr, deny_idx, group_of, group_cap, n_why,
+                                         why_src, why_term);
+    CapCheck limit;                                              // (the two limits the capped entry words)
+    switch (c.verdict) {
+        case EXPLAIN_OK: break;
+        case EXPLAIN_NOOP: return RWR_OK;
+        case EXPLAIN_CAP:
+            return cap_verdict_status(who, c.cap, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds, ids, scores or counts", "",
+                                      deny_ptr, nullptr, group_cap);
+        case EXPLAIN_BAD_N_WHY:
+            set_error("%s: n_why %d is below 0", who, n_why);
+            return RWR_E_INVALID;
+        case EXPLAIN_NULL_WHY:
+            set_error("%s: NULL why_src or why_term with n_why %d", who, n_why);
+            return RWR_E_INVALID;
+        case EXPLAIN_TOP_N_LIMIT:
+        case EXPLAIN_CAP_LIMIT:
+            limit.verdict = c.verdict == EXPLAIN_TOP_N_LIMIT ? CAP_TOP_N_LIMIT : CAP_CAP_LIMIT;
+            return cap_verdict_status(who, limit, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds, ids, scores or counts", "",
+                                      deny_ptr, nullptr, group_cap);
+        case EXPLAIN_WHY_LIMIT:
+            set_error("%s: n_why %d is beyond the limit of RWR_WHY_MAX = %d reasons per entry", who, n_why, (int)RWR_WHY_MAX);
+            return RWR_E_UNSUPPORTED;
+    }
+    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    return bound(who, g, [&] {
+        return recommend_explained_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, pool_count,
+                                         pool_idx, deny_ptr, deny_idx, group_of, group_cap, n_why, ids, scores, counts, nodes, why_src,
+                                         why_term, why_total);
     });
 }
 

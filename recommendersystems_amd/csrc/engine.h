@@ -355,6 +355,14 @@ int32_t recommend_capped_positions_batch(rwr_graph *g, const int32_t *seeds, int
                                          const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of, int32_t group_cap,
                                          const int64_t *test_ptr, const int64_t *test_ids, int64_t *pos_out, double *score_out,
                                          int64_t *list_len);
+// explain.hip: the capped lists with, per entry, its node index, its best n_why in-link addends over the previous ranks and the
+// number of positive ones (rwr_recommend_explained_batch); arguments as explain_plan.h's check passed them; with
+// n_why == 0 and neither nodes nor why_total it is recommend_capped_batch
+int32_t recommend_explained_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
+                                  int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count,
+                                  const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of,
+                                  int32_t group_cap, int32_t n_why, int64_t *ids, double *scores, int32_t *counts, int32_t *nodes,
+                                  int32_t *why_src, double *why_term, int64_t *why_total);
 // model.hip pieces restart.hip runs as well (the loops around them: run_walk and GroupColumns, iterate.h).  A run's end condition (Model.run(int) / run(double) / run(), Model.cs:52-66):
 // T steps at most; !by_count: until checkConvergence's distance is < threshold, a failure after max_iters = RWR_MAX_ITERS steps
 struct RunEnd {

@@ -94,28 +94,7 @@ __global__ __launch_bounds__(256) void k_rank_emit(int32_t n_items, int G, const
 // top_n entries of the full (score desc, id desc) order of Recommender.cs:35-38.
 // Typical depth is two levels (sign/exponent byte, then 4 exponent + 4 mantissa bits).
 // ---------------------------------------------------------------------------------------
-struct SelState {
-    uint64_t ph, pl;     // prefix: nbits <= 64: ph holds the top nbits of the score key (right-aligned);
-                         // nbits > 64: ph = full score key, pl = top (nbits-64) bits of the id key
-    int32_t nbits;       // bits decided so far
-    int32_t k_rem;       // entries still to take from inside the prefix bin
-    int32_t total;       // candidates of the segment (set at level 0)
-    int32_t done;
-    int32_t cand_cnt;    // collect cursor
-    int32_t pad;
-};
-
-__device__ static inline int sel_cmp(uint64_t hi, uint64_t lo, const SelState &st)
-{
-    if (st.nbits == 0) return 0;
-    if (st.nbits <= 64) {
-        const uint64_t a = hi >> (64 - st.nbits);
-        return a > st.ph ? 1 : (a < st.ph ? -1 : 0);
-    }
-    if (hi != st.ph) return hi > st.ph ? 1 : -1;
-    const uint64_t b = lo >> (128 - st.nbits);
-    return b > st.pl ? 1 : (b < st.pl ? -1 : 0);
-}
+// (SelState and sel_cmp: rank_keys.h -- explain.hip's row-carrying collect reads the same thresholds)
 
 __global__ void k_sel_init(int nseg, int32_t top_n, const int32_t *__restrict__ seeds, SelState *__restrict__ st)
 {
@@ -469,24 +448,23 @@ int32_t rank_tile(rwr_graph *g, int G, const int32_t *d_slot_k_tile, int32_t top
     return RWR_OK;
 }
 
-// top-k for a whole tile group in one go (select path; top_n <= SEL_MAX_K)
-// rows / nrows: the rows to rank, in any order (nullptr: the ITEM rows, g->item_rows)
-int32_t rank_group_select(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, const double *X,
-                          const int32_t *d_seeds, hipStream_t s, const int32_t *rows, int32_t nrows)
+// The histogram / decide levels of a tile group's select over the m rows of `rows`: they fix the thresholds in *st_out (nseg states); *cand_out = room for SEL_SLOTS
+// candidates of cand_size bytes per segment, for the collect and the sort-and-emit that follow (here, or explain.hip's
+// row-carrying pair)
+int32_t rank_group_levels(rwr_graph *g, int G, int tg, int32_t top_n, const double *X, const int32_t *d_seeds, hipStream_t s,
+                          const int32_t *rows, int32_t m, size_t cand_size, SelState **st_out, void **cand_out)
 {
-    const int32_t m = rows ? nrows : g->n_items;
-    if (!rows) rows = g->item_rows.p;
-    if (m == 0) return RWR_OK;
     const int nseg = tg * G;
     const size_t st_bytes = (size_t)nseg * sizeof(SelState);
     const size_t hist_bytes = (size_t)nseg * 256 * sizeof(uint32_t);
-    const size_t cand_bytes = (size_t)nseg * SEL_SLOTS * sizeof(SelCand);
+    const size_t cand_bytes = (size_t)nseg * SEL_SLOTS * cand_size;
     const size_t ticket_bytes = SEL_LEVELS * sizeof(unsigned int);
     RWR_TRY(g->sort_temp.ensure(st_bytes + hist_bytes + ticket_bytes + cand_bytes + 64));
     SelState *st = (SelState *)g->sort_temp.p;
     uint32_t *ghist = (uint32_t *)(g->sort_temp.p + st_bytes);
     unsigned int *ticket = (unsigned int *)(g->sort_temp.p + st_bytes + hist_bytes);
-    SelCand *cand = (SelCand *)(g->sort_temp.p + st_bytes + hist_bytes + ticket_bytes);
+    *st_out = st;
+    *cand_out = g->sort_temp.p + st_bytes + hist_bytes + ticket_bytes;   // (16-byte aligned: every part is a multiple of 16)
     RWR_HIP(hipMemsetAsync(ghist, 0, hist_bytes + ticket_bytes, s));
     hipLaunchKernelGGL(k_sel_init, dim3(cdiv((size_t)nseg, 64)), dim3(64), 0, s, nseg, top_n, d_seeds, st);
     const unsigned nblk = cdiv((size_t)m, SEL_ROWS_PER_BLOCK);
@@ -508,6 +486,24 @@ int32_t rank_group_select(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, 
             hipLaunchKernelGGL(k_sel_decide, dim3(cdiv((size_t)nseg, 64)), dim3(64), 0, s, nseg, st, ghist, level);
         }
     }
+    RWR_HIP(hipGetLastError());
+    return RWR_OK;
+}
+
+// top-k for a whole tile group in one go (select path; top_n <= SEL_MAX_K)
+// rows / nrows: the rows to rank, in any order (nullptr: the ITEM rows, g->item_rows)
+int32_t rank_group_select(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, const double *X,
+                          const int32_t *d_seeds, hipStream_t s, const int32_t *rows, int32_t nrows)
+{
+    const int32_t m = rows ? nrows : g->n_items;
+    if (!rows) rows = g->item_rows.p;
+    if (m == 0) return RWR_OK;
+    const int nseg = tg * G;
+    SelState *st = nullptr;
+    void *cand_v = nullptr;
+    RWR_TRY(rank_group_levels(g, G, tg, top_n, X, d_seeds, s, rows, m, sizeof(SelCand), &st, &cand_v));
+    SelCand *cand = (SelCand *)cand_v;
+    const unsigned nblk = cdiv((size_t)m, SEL_ROWS_PER_BLOCK);
     RWR_DISPATCH_G(G, hipLaunchKernelGGL(k_sel_collect<GG>, dim3(nblk, tg), dim3(256), 0, s, g->n, m, rows,
                                          g->node_id.p, X, st, d_seeds, cand));
     (void)hipFuncSetAttribute((const void *)k_sel_sort_emit, hipFuncAttributeMaxDynamicSharedMemorySize,

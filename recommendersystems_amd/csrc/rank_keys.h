@@ -25,8 +25,46 @@ __device__ __forceinline__ void sel_decode(const SelCand &v, int64_t *id, double
     *score = s;
 }
 
-// the workgroup's N2 (a power of two) entries of sc sorted descending by (hi, lo) (bitonic).  The caller has synchronised after filling sc
-__device__ __forceinline__ void sel_sort(SelCand *sc, int N2)
+__device__ __forceinline__ bool sel_lt(const SelCand &a, const SelCand &b) { return (a.hi < b.hi) || (a.hi == b.hi && a.lo < b.lo); }
+
+// ... with the candidate's row (explain.hip): among equal (score, id) pairs the smaller row ranks first, which
+// makes the order total.  {0, 0, 0x7FFFFFFF} lies below every real key
+struct SelCandRow {
+    uint64_t hi, lo;
+    int32_t row, pad;
+};
+__device__ __forceinline__ bool sel_lt(const SelCandRow &a, const SelCandRow &b)
+{
+    return a.hi != b.hi ? a.hi < b.hi : a.lo != b.lo ? a.lo < b.lo : a.row > b.row;
+}
+
+// The state of one segment's radix select (rank.hip: the levels that fix it; the collects read it as their threshold)
+struct SelState {
+    uint64_t ph, pl;     // prefix: nbits <= 64: ph holds the top nbits of the score key (right-aligned);
+                         // nbits > 64: ph = full score key, pl = top (nbits-64) bits of the id key
+    int32_t nbits;       // bits decided so far
+    int32_t k_rem;       // entries still to take from inside the prefix bin
+    int32_t total;       // candidates of the segment (set at level 0)
+    int32_t done;
+    int32_t cand_cnt;    // collect cursor
+    int32_t pad;
+};
+
+__device__ static inline int sel_cmp(uint64_t hi, uint64_t lo, const SelState &st)
+{
+    if (st.nbits == 0) return 0;
+    if (st.nbits <= 64) {
+        const uint64_t a = hi >> (64 - st.nbits);
+        return a > st.ph ? 1 : (a < st.ph ? -1 : 0);
+    }
+    if (hi != st.ph) return hi > st.ph ? 1 : -1;
+    const uint64_t b = lo >> (128 - st.nbits);
+    return b > st.pl ? 1 : (b < st.pl ? -1 : 0);
+}
+
+// the workgroup's N2 (a power of two) entries of sc sorted descending by sel_lt (bitonic).  The caller has synchronised after filling sc
+template <class C>
+__device__ __forceinline__ void sel_sort(C *sc, int N2)
 {
     for (int size = 2; size <= N2; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
@@ -34,8 +72,8 @@ __device__ __forceinline__ void sel_sort(SelCand *sc, int N2)
                 const int lo_i = 2 * t - (t & (stride - 1));
                 const int hi_i = lo_i + stride;
                 const bool desc = (lo_i & size) == 0;        // first half of each bitonic pair: descending
-                const SelCand a = sc[lo_i], b = sc[hi_i];
-                const bool a_lt_b = (a.hi < b.hi) || (a.hi == b.hi && a.lo < b.lo);
+                const C a = sc[lo_i], b = sc[hi_i];
+                const bool a_lt_b = sel_lt(a, b);
                 if (a_lt_b == desc) {
                     sc[lo_i] = b;
                     sc[hi_i] = a;

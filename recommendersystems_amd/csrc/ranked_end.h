@@ -3,7 +3,8 @@
 // group's X[tile][n][G] are marked with -1; then the candidates are ranked into K x top_n lists, evaluated against test
 // sets by counting, or the test ids' positions in the whole lists are found by the same counting; after the last group the
 // result is copied back once.  Three independent descriptions say which end: the candidates, the exclusion, the destination;
-// the filtered entries add a fourth, the seeds' deny lists, the capped entries a fifth, the group cap.
+// the filtered entries add a fourth, the seeds' deny lists, the capped entries a fifth, the group cap, the explained entry a
+// sixth, the reasons of the list's entries.
 //
 // Lifetime: the object (and the EvalEnd or PosEnd it points to) is declared before the driver's StreamsIdle, so the device copies of
 // its plans outlive the kernels that read them, on error paths too.
@@ -17,6 +18,7 @@ namespace rwr {
 
 struct Profile;   // iterate.h
 struct GroupCap;  // group_cap.h
+struct WhyEnd;    // explain.h
 
 struct RankedEnd {
     const char *who = "";              // the entry point, for the messages
@@ -51,14 +53,20 @@ struct RankedEnd {
     int32_t *counts = nullptr;
     EvalEnd *ev = nullptr;
     PosEnd *pos = nullptr;
+    // the reasons (the explained entry; the list destination only): the lists keep their entries' rows -- the
+    // select's last two launches are explain.hip's row-carrying pair -- and every entry's best in-link addends over the
+    // group's previous ranks are found after the ranking.  nullptr: the stock launches, nothing more
+    WhyEnd *why = nullptr;
 
     // The zeroed output tables (or records) of the call and the plans of this slot assignment: slot_k[slot] = batch position,
     // -1 = padding; slots_per_group slots form a tile group.  The driver has put slot_k into g->d_slot_k -- the ranking's
     // output-row table and its liveness array (>= 0: a live slot).  The host vectors are pageable: the caller synchronises s.
     int32_t prepare(rwr_graph *g, int32_t K, const std::vector<int32_t> &slot_k, size_t slots_per_group, hipStream_t s);
     // Tile group grp (tg tiles of G slots from slot q0 on) holds its final ranks in X: the exclusion, then the ranking or
-    // the evaluation, booked as prof.rank
-    int32_t finish_group(rwr_graph *g, int G, int tg, int grp, size_t q0, double *X, Profile &prof, hipStream_t s);
+    // the evaluation, booked as prof.rank.  Y: the group's previous ranks (GroupIter's Y after the last step), which only `why`
+    // reads
+    int32_t finish_group(rwr_graph *g, int G, int tg, int grp, size_t q0, double *X, Profile &prof, hipStream_t s,
+                         const double *Y = nullptr);
     // after the last group: K x top_n list entries, the K evaluation records, or the test ids' positions and scores
     int32_t copy_back(rwr_graph *g, int32_t K);
 

@@ -1,6 +1,7 @@
 // The ranked end of a batch (ranked_end.h): the exclusion kernels, and the three operations around a driver's group loop.
 #include "ranked_end.h"
 
+#include "explain.h"
 #include "group_cap.h"
 #include "iterate.h"
 
@@ -69,6 +70,7 @@ int32_t RankedEnd::prepare(rwr_graph *g, int32_t K, const std::vector<int32_t> &
     if (ev) RWR_TRY(eval_prepare(g, *ev, K, slot_k, slots_per_group, who, s));
     else if (pos) RWR_TRY(pos_prepare(g, *pos, K, slot_k, slots_per_group, who, s));
     else RWR_TRY(ensure_out_tables(g, K, top_n, s));
+    if (why && !ev && !pos) RWR_TRY(why_prepare(g, *why, K, top_n, s));
     if (mask != 0) {                                            // (mask 0 looks at no link)
         plan = exclude_plan(g->n, g->h_rowptr.data(), slot_k.size(), slot_k.data(), slots_per_group, K, set_ptr, set_idx);
         if (plan.check.verdict != EXCLUDE_OK) {                 // (api.hip refuses such sets before the call gets here)
@@ -103,7 +105,8 @@ int32_t RankedEnd::prepare(rwr_graph *g, int32_t K, const std::vector<int32_t> &
     return RWR_OK;
 }
 
-int32_t RankedEnd::finish_group(rwr_graph *g, int G, int tg, int grp, size_t q0, double *X, Profile &prof, hipStream_t s)
+int32_t RankedEnd::finish_group(rwr_graph *g, int G, int tg, int grp, size_t q0, double *X, Profile &prof, hipStream_t s,
+                                const double *Y)
 {
     const int32_t *slot_k = g->d_slot_k.p + q0;                 // (the rankers read it for liveness as well: a sign test)
     hipEvent_t a; RWR_TRY(prof.record(a, s));
@@ -131,6 +134,13 @@ int32_t RankedEnd::finish_group(rwr_graph *g, int G, int tg, int grp, size_t q0,
     if (cap) RWR_TRY(cap_group(g, *cap, G, tg, slot_k, X, s));
     if (ev) RWR_TRY(eval_group(g, *ev, G, tg, q0, X, rows ? rows : g->item_rows.p, rows ? nrows : g->n_items, s));
     else if (pos) RWR_TRY(pos_group(g, *pos, G, tg, q0, X, rows ? rows : g->item_rows.p, rows ? nrows : g->n_items, s));
+    else if (why) {                                             // (a candidate list and top_n <= the select's limit: explain.hip's entry)
+        if (!rows) { set_error("%s: reasons need a candidate list", who); return RWR_E_INVALID; }
+        if (nrows > 0) {
+            RWR_TRY(why_rank_group(g, *why, G, tg, slot_k, top_n, X, s, rows, nrows));
+            RWR_TRY(why_group(g, *why, G, tg, slot_k, top_n, Y, s));
+        }
+    }
     else if (!rows) RWR_TRY(rank_group(g, G, tg, slot_k, slot_k, top_n, X, s));
     else if (nrows > 0) RWR_TRY(rank_group_select(g, G, tg, slot_k, top_n, X, slot_k, s, rows, nrows));   // (top_n <= its limit: api.hip)
     RWR_TRY(prof.end(prof.rank, a, s));                         // (no candidate: the zeroed tables stand)
@@ -141,7 +151,8 @@ int32_t RankedEnd::copy_back(rwr_graph *g, int32_t K)
 {
     if (ev) return eval_copy_back(g, *ev, K, who, g->stream);
     if (pos) return pos_copy_back(g, *pos, K, who, g->stream);
-    return copy_lists_back(g, K, top_n, ids, scores, counts, top_n);
+    RWR_TRY(copy_lists_back(g, K, top_n, ids, scores, counts, top_n));
+    return why ? why_copy_back(g, *why, K, top_n) : RWR_OK;
 }
 
 }  // namespace rwr

@@ -21,6 +21,7 @@
 // CallFilter: the candidates narrowed to the caller's pool, the seeds' deny lists marked after the link exclusion.
 // rwr_recommend_capped_batch and rwr_recommend_capped_positions_batch (group_cap.hip) add a GroupCap to the
 // end: built here once the candidate list exists, applied by the end after the deny marks.
+// rwr_recommend_explained_batch (explain.hip) adds a WhyEnd: the end then also reads the group's previous ranks.
 #include "filter.h"
 #include "group_cap.h"
 
@@ -195,7 +196,7 @@ int32_t typed_body(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int3
         for (size_t q = q0; q < q0 + (size_t)tg * G; ++q) real += slot_k[q] >= 0;
         g->stats.spmm_seed_steps += (int64_t)real * (T > 0 ? T : 0);
         g->stats.spmm_dense_seed_steps += (int64_t)real * gi.dense_steps;
-        RWR_TRY(end.finish_group(g, G, tg, grp, q0, gi.X, prof, s));
+        RWR_TRY(end.finish_group(g, G, tg, grp, q0, gi.X, prof, s, gi.Y));   // (Y: the ranks the last step read, whole)
     }
     RWR_TRY(end.copy_back(g, K));
     g->stats.seeds_done += K;

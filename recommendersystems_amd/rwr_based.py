@@ -986,6 +986,55 @@ class Recommender:
         c = int(counts[0])
         return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist()))
 
+    def RecommendationExplainedBatch(self, seeds, dampingFactor: float, nIteration: int, topN: int, nWhy: int = 3, candType=None,
+                                     exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None, groupOf=None,
+                                     groupCap: int = 1, wantNodes: bool = True, wantTotal: bool = True):
+        """RecommendationCappedBatch with the reasons of every list entry (rwr_recommend_explained_batch, an addition, see
+        include/rwr.h): (ids[K,topN], scores[K,topN], counts[K], nodes[K,topN], whySrc[K,topN,nWhy], whyTerm[K,topN,nWhy],
+        whyTotal[K,topN]).  nodes: the entries' node indices (-1 behind a list's end); whySrc / whyTerm: the source node and the
+        value of each entry's nWhy largest in-link addends fl(fl((1 - d) * previousRank[u]) * weight(u -> v)), largest first,
+        -1 / +0.0 where an entry has fewer positive addends; whyTotal: the number of positive addends.  nWhy in [0, 8].
+        wantNodes / wantTotal False: that table is not computed and None is returned in its place; with nWhy 0 and both False
+        the call is the capped call."""
+        lib = _lib.load()
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        K = int(seeds.shape[0])
+        mask = 0
+        for t in exclEdgeTypes:
+            mask |= 1 << int(EdgeType(t))
+        pc, pi, dp, di = _pack_filter(pool, deny, K)
+        go = _pack_groups(groupOf)
+        if go is not None and go.shape[0] < self.graph.stats()["n"]:
+            raise ValueError("groupOf must hold one label per node of the graph")
+        topN, nWhy = int(topN), int(nWhy)
+        width, r = max(topN, 0), min(max(nWhy, 0), 8)
+        ids = np.zeros((K, width), dtype=np.int64)
+        sc = np.zeros((K, width), dtype=np.float64)
+        counts = np.zeros(K, dtype=np.int32)
+        nodes = np.full((K, width), -1, dtype=np.int32) if wantNodes else None
+        src = np.full((K, width, r), -1, dtype=np.int32)
+        term = np.zeros((K, width, r), dtype=np.float64)
+        total = np.zeros((K, width), dtype=np.int64) if wantTotal else None
+        _lib.check(lib.rwr_recommend_explained_batch(
+            self.graph._handle(), _p(seeds, C.c_int32), K, C.c_float(dampingFactor), int(nIteration), topN,
+            -1 if candType is None else int(candType), mask, 1 if excludeSelf else 0, pc, None if pi is None else _p(pi, C.c_int32),
+            None if dp is None else _p(dp, C.c_int64), None if di is None else _p(di, C.c_int32),
+            None if go is None else _p(go, C.c_int32), int(groupCap), nWhy, _p(ids, C.c_int64), _p(sc, C.c_double),
+            _p(counts, C.c_int32), None if nodes is None else _p(nodes, C.c_int32), _p(src, C.c_int32), _p(term, C.c_double),
+            None if total is None else _p(total, C.c_int64)))
+        return ids, sc, counts, nodes, src, term, total
+
+    def RecommendationExplained(self, idxTargetNode: int, dampingFactor: float, nIteration: int, topN: int, nWhy: int = 3,
+                                candType=None, exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None, groupOf=None,
+                                groupCap: int = 1):
+        """RecommendationExplainedBatch for one seed: ([(node id, score), ...], nodes[count], whySrc[count,nWhy],
+        whyTerm[count,nWhy], whyTotal[count]); deny: the seed's one deny list (an iterable of node indices) or None."""
+        ids, sc, counts, nodes, src, term, total = self.RecommendationExplainedBatch(
+            [int(idxTargetNode)], dampingFactor, nIteration, topN, nWhy, candType, exclEdgeTypes, excludeSelf, pool,
+            None if deny is None else [deny], groupOf, groupCap)
+        c = int(counts[0])
+        return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist())), nodes[0, :c], src[0, :c], term[0, :c], total[0, :c]
+
     def RecommendationCappedPositionsBatch(self, seeds, dampingFactor: float, nIteration: int, testSets, candType=None,
                                            exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None, groupOf=None,
                                            groupCap: int = 1):
