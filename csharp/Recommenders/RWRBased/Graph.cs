@@ -226,6 +226,14 @@ namespace Recommenders.RWRBased {
             graph = normalized;
         }
 
+        // addition: the library's counters for this graph (rwr_get_stats), e.g. which kernels served the single-seed SpMV steps
+        public RwrStats Stats() {
+            var st = new RwrStats { struct_size = System.Runtime.InteropServices.Marshal.SizeOf(typeof(RwrStats)) };
+            Native.Check(Native.rwr_get_stats(handle, ref st));
+            return st;
+        }
+        public void ResetStats() { Native.Check(Native.rwr_reset_stats(handle)); }
+
         public int size() { return nodes.Count; }
     }
 }

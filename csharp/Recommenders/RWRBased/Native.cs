@@ -40,6 +40,8 @@ namespace Recommenders.RWRBased {
             long count, int[] src, int[] dst, byte[] etype, double[] w, long[] new_index_out);
         [DllImport(Lib)] public static extern int rwr_graph_destroy(IntPtr g);
         [DllImport(Lib)] public static extern int rwr_graph_get_normalized(GraphHandle g, double[] w_out, byte[] dangling_out);
+        [DllImport(Lib)] public static extern int rwr_get_stats(GraphHandle g, ref RwrStats stats_out);
+        [DllImport(Lib)] public static extern int rwr_reset_stats(GraphHandle g);
         [DllImport(Lib)] public static extern int rwr_recommend(GraphHandle g, int seed, float d, int n_iter, int top_n,
             long[] out_id, double[] out_score, ref long inout_count);
         [DllImport(Lib)] public static extern int rwr_recommend_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,

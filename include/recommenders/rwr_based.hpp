@@ -163,6 +163,17 @@ public:
     }
 
     int size() const { return (int)nodes.size(); }             // Graph.cs:91-93
+    // addition: the library's counters for this graph (rwr_get_stats) -- among them which kernels served the single-seed SpMV
+    // steps (spmv_sweep_launches / spmv_hub_launches / spmv_binned_launches) and the sweep's geometry (sweep_k, sweep_blocks,
+    // sweep_wgs, sweep_partial; all 0 when the graph does not take the sweep)
+    rwr_stats stats() const
+    {
+        rwr_stats st{};
+        st.struct_size = (int32_t)sizeof(st);
+        check(rwr_get_stats(handle(), &st));
+        return st;
+    }
+    void resetStats() { check(rwr_reset_stats(handle())); }
     rwr_graph *handle() const
     {
         if (!h_) throw std::runtime_error("Graph.buildGraph() has not been called");

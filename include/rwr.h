@@ -135,6 +135,19 @@ typedef struct rwr_stats {
                                        none) */
     int64_t entry_live_launches;    /* SpMM launches of rwr_recommend_batch's bitmap-probing steps that read the step's per-link
                                        tile masks instead of probing the frontier bitmaps per entry (RWR_ENTRY_LIVE=0: none) */
+    /* which kernels served the single-seed SpMV steps (one rank vector: rwr_model_run / rwr_model_deliver and every
+     * single-seed ranked call): launches of the source-block sweep, of the hub-row kernel (rows of >= RWR_HUB_T in-links)
+     * and of the row-binned kernel.  Host-side counts; a step may launch all three */
+    int64_t spmv_sweep_launches;
+    int64_t spmv_hub_launches;
+    int64_t spmv_binned_launches;
+    /* the sweep's geometry as last decided for this graph (all 0 while undecided, after a rebuild, or when the graph does
+     * not take the sweep; rwr_reset_stats leaves them, as it leaves n and uniform_path): slots of 64 rows per wave,
+     * source blocks, workgroups, and 1 when the sweep serves the ITEM rows only (the other rows: the row-binned kernel) */
+    int32_t sweep_k;
+    int32_t sweep_blocks;
+    int32_t sweep_wgs;
+    int32_t sweep_partial;
 } rwr_stats;
 
 /* ---- library ------------------------------------------------------------------------- */

@@ -56,7 +56,9 @@ class rwr_stats(C.Structure):
                 ("uniform_path", C.c_int32), ("reserved1", C.c_int32), ("frontier_list_launches", C.c_int64),
                 ("rank_fused_groups", C.c_int64), ("rank_fused_fallbacks", C.c_int64),
                 ("rank_pruned_rows", C.c_int64), ("rank_bound_ms", C.c_double), ("x_clear_skipped", C.c_int64),
-                ("entry_live_launches", C.c_int64)]
+                ("entry_live_launches", C.c_int64),
+                ("spmv_sweep_launches", C.c_int64), ("spmv_hub_launches", C.c_int64), ("spmv_binned_launches", C.c_int64),
+                ("sweep_k", C.c_int32), ("sweep_blocks", C.c_int32), ("sweep_wgs", C.c_int32), ("sweep_partial", C.c_int32)]
 
 
 class RwrError(RuntimeError):

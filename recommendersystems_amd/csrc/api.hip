@@ -982,6 +982,7 @@ int32_t rwr_get_stats(rwr_graph *g, rwr_stats *out)
     size_t sz = out->struct_size > 0 ? (size_t)out->struct_size : sizeof(rwr_stats);
     if (sz > sizeof(rwr_stats)) sz = sizeof(rwr_stats);
     rwr_stats s = g->stats;
+    if (!sweep_ready(g)) s.sweep_k = s.sweep_blocks = s.sweep_wgs = s.sweep_partial = 0;   // (a rebuild drops the tables: undecided again)
     s.struct_size = (int32_t)sz;
     memcpy(out, &s, sz);
     return RWR_OK;
@@ -1001,6 +1002,7 @@ int32_t rwr_reset_stats(rwr_graph *g)
     s.rank_bound_ms = 0;
     s.x_clear_skipped = 0;
     s.entry_live_launches = 0;
+    s.spmv_sweep_launches = s.spmv_hub_launches = s.spmv_binned_launches = 0;   // (sweep_*: the graph's geometry, kept)
     return RWR_OK;
 }
 

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void k_spmv_exact_binned(int nb0, int nb1, int
 // that one row.  When every addend is known to be >= 0 (weights, ranks, 1-d: `hub_scan`), the chain is an INTEGER sum
 // inside each binade of the running sum (pf.h; chain_scan.hip explains the arithmetic), so it reduces in parallel and is
 // still bit for bit the sequential result: the first few hundred entries are added one by one as above (the sum crosses a binade
-// every few entries while it is small), the rest in passes of 1024 -- lane l fetches ITS 16 consecutive entries (64
+// every few entries while it is small), the rest in passes of HS_PASS = 512 -- lane l fetches ITS 8 consecutive entries (32
 // contiguous bytes of indices), gathers their values, and wave_fold_exact composes the 64 runs.  One wave per row; the
 // kernel runs beside k_spmv_exact_binned on a stream of its own.
 constexpr int HS_R = 8;    // (8, not 16: at 16 the kernel needs 244 registers per lane and cannot share a SIMD with the sweep kernel's waves)
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(WAVE, 3) void k_spmv_exact_hub(int32_t r0, int32_t 
             }
             p = ea;
         }
-        // the rest in passes of HS_PASS: every lane's 16 consecutive entries, then the exact parallel fold.  Three passes are
+        // the rest in passes of HS_PASS: every lane's HS_R = 8 consecutive entries, then the exact parallel fold.  Three passes are
         // in flight: the indices of pass k+2 and the gathers of pass k+1 are requested before pass k is folded, so the fold
         // (the only sequential part: it needs the running sum) never waits for memory -- the longest row of the
         // MovieLens-shaped graph (29 000 in-links) bounds the whole step, and it was spending two memory round trips per pass.
@@ -399,6 +399,7 @@ void launch_spmv_exact(rwr_graph *g, const double *X, double *Y, const int32_t *
         // workgroup (160 - 128 KB), so that the hub rows run on the CUs the sweep leaves free (sweep.hip: RWR_SWEEP_WGS)
         static const int hub_lds_env = [] { const char *e = RWR_TUNE_ENV("RWR_HUB_LDS"); return e ? atoi(e) : 36864; }();
         const size_t hub_lds = (sweep && !g->sw_partial) ? (size_t)hub_lds_env : 0;   // (partial: the sweep holds every CU)
+        g->stats.spmv_hub_launches += 1;
         if (vf)
             hipLaunchKernelGGL(k_spmv_exact_hub<true>, dim3(grid), dim3(WAVE), hub_lds, sh, ra, ra + nh, g->in_ptr.p, g->in_src.p,
                                g->in_w.p, order, gs, Y, seeds, c1, skip, g->w_src.p, zout, prefix, act, nz_out);
@@ -422,6 +423,7 @@ void launch_spmv_exact(rwr_graph *g, const double *X, double *Y, const int32_t *
         const int32_t rend = ra + rows;
         const int nb0 = blocks_for(b0 - ra, 64), nb1 = blocks_for(b1 - b0, 16), nb2 = blocks_for(b2 - b1, 4), nb3 = blocks_for(rend - b2, 1);
         if (nb0 + nb1 + nb2 + nb3 <= 0) return;
+        g->stats.spmv_binned_launches += 1;
         if (vf)
             hipLaunchKernelGGL(k_spmv_exact_binned<true>, dim3((unsigned)(nb0 + nb1 + nb2 + nb3)), dim3(256), 0, sb, nb0, nb1, nb2, nb3, ra, b0,
                                b1, b2, rend, g->in_ptr.p, g->in_src.p, g->in_w.p, order, gs, Y, seeds, c1, skip, act, nz_out, g->w_src.p, zout);

@@ -385,6 +385,7 @@ int32_t sweep_prepare(rwr_graph *g)
 {
     if (g->sw_state != 0) return RWR_OK;
     g->sw_state = -1;
+    g->stats.sweep_k = g->stats.sweep_blocks = g->stats.sweep_wgs = g->stats.sweep_partial = 0;
     static const int enable = [] { const char *e = getenv("RWR_SWEEP"); return e ? atoi(e) : 1; }();
     static const int64_t min_n = [] { const char *e = getenv("RWR_SWEEP_MIN_N"); return e ? atol(e) : 50000l; }();
     static const int bn_env = [] { const char *e = getenv("RWR_SWEEP_BN"); return e ? atoi(e) : 16384; }();
@@ -478,6 +479,7 @@ int32_t sweep_prepare(rwr_graph *g)
         g->sw_rows = n_sw; g->sw_partial = partial;
         g->sw_words = (int64_t)h_total * WAVE;
         g->sw_state = 1;
+        g->stats.sweep_k = K; g->stats.sweep_blocks = B; g->stats.sweep_wgs = nwg; g->stats.sweep_partial = partial;
 #ifdef RWR_EXPERIMENTS
         fprintf(stderr, "[sweep] n %d hubs %d rows %d%s slots %d K %d blocks %d (BN %d) compute waves %d x %d words %lld (%.1f MB) nnz %lld\n", g->n, hub0,
                 n_sw, partial ? " (ITEM rows only)" : "", ns, K, B, BN, nwg, wpg, (long long)g->sw_words, g->sw_words * 8 / 1e6, (long long)g->nnz);
@@ -496,6 +498,7 @@ void launch_sweep(rwr_graph *g, const double *zin, double *Y, double *zout, cons
     const int32_t *order = g->sw_order.p;
     const uint4 *meta = g->sw_meta.p;
     const uint2 *ents = g->sw_ent.p;
+    g->stats.spmv_sweep_launches += 1;
 #ifdef RWR_SWEEP_STAMPS
     static unsigned long long *stamp_dev = nullptr;
     static int stamp_launch = 0;
