@@ -6,14 +6,11 @@
 #include <vector>
 #include <string.h>
 
-#include "cap_plan.h"
 #include "eval_plan.h"
 #include "exclude_plan.h"
-#include "explain_plan.h"
-#include "filter_plan.h"
 #include "handle.h"
-#include "member_plan.h"
 #include "rank.h"
+#include "typed_call.h"
 
 namespace rwr {
 
@@ -158,152 +155,11 @@ static int32_t check_ranked_vectors(const char *who, int32_t n, int32_t K, const
     return RWR_OK;
 }
 
-// eval_check's verdict on the test sets and result arrays of an evaluating entry, as status and message; outs: the result
-// arrays EVAL_NULL_OUT names for this entry
-static int32_t eval_verdict_status(const char *who, const EvalCheck &c, const int64_t *test_ptr,
-                                   const char *outs = "n_hits or sum_precision")
+// a refusal worded on the host (typed_call.h) into the thread's error string; RWR_OK passes through
+static int32_t report(const CallStatus &st)
 {
-    switch (c.verdict) {
-        case EVAL_OK: break;
-        case EVAL_NULL_PTR:
-            set_error("%s: NULL test_ptr", who);
-            return RWR_E_INVALID;
-        case EVAL_NULL_OUT:
-            set_error("%s: NULL %s", who, outs);
-            return RWR_E_INVALID;
-        case EVAL_BAD_PTR0:
-            set_error("%s: test_ptr[0] = %lld, not 0", who, (long long)test_ptr[0]);
-            return RWR_E_INVALID;
-        case EVAL_PTR_DECREASES:
-            set_error("%s: test_ptr decreases at batch position %d", who, c.bad_k);
-            return RWR_E_INVALID;
-        case EVAL_NULL_IDS:
-            set_error("%s: NULL test_ids", who);
-            return RWR_E_INVALID;
-        case EVAL_SET_TOO_LARGE:
-            set_error("%s: test set %d holds more than INT32_MAX ids", who, c.bad_k);
-            return RWR_E_UNSUPPORTED;
-    }
-    return RWR_OK;
-}
-
-// A TypedCheck's verdict on the arguments of a typed entry, as status and message (TYPED_NOOP is the caller's: it returns
-// RWR_OK at once).  null_arg: the pointers TYPED_NULL_ARG names for this entry; top_n_hint: what the entry appends to
-// TYPED_TOP_N_LIMIT's text, nullptr: its check gives no top_n verdict
-static int32_t typed_verdict_status(const char *who, const TypedCheck &c, int32_t n, int32_t top_n, int32_t cand_type,
-                                    uint32_t excl_edge_mask, const char *null_arg, const char *top_n_hint)
-{
-    switch (c.verdict) {
-        case TYPED_OK:
-        case TYPED_NOOP: break;
-        case TYPED_NULL_GRAPH:
-            set_error("%s: NULL graph", who);
-            return RWR_E_INVALID;
-        case TYPED_NEGATIVE_K:
-            set_error("%s: negative K", who);
-            return RWR_E_INVALID;
-        case TYPED_NULL_ARG:
-            set_error("%s: NULL %s", who, null_arg);
-            return RWR_E_INVALID;
-        case TYPED_BAD_CAND_TYPE:
-            set_error("%s: cand_type %d is outside [0, 255]", who, cand_type);
-            return RWR_E_INVALID;
-        case TYPED_BAD_MASK:
-            set_error("%s: excl_edge_mask 0x%x has a bit beyond the %u edge types", who, excl_edge_mask, TYPED_EDGE_TYPES);
-            return RWR_E_INVALID;
-        case TYPED_SEED_RANGE:
-            set_error("%s: seed %d (batch position %d) is outside [0, %d)", who, c.bad_seed, c.bad_k, n);
-            return RWR_E_RANGE;
-        case TYPED_BAD_TOP_N:
-        case TYPED_TOP_N_LIMIT:
-            if (!top_n_hint) {
-                set_error("%s: unexpected verdict %d", who, (int)c.verdict);
-                return RWR_E_INVALID;
-            }
-            if (c.verdict == TYPED_BAD_TOP_N) {
-                set_error("%s: top_n must be >= 1", who);
-                return RWR_E_INVALID;
-            }
-            set_error("%s: top_n %d is beyond the select path's limit of %d entries%s", who, top_n, rank_select_max_k(), top_n_hint);
-            return RWR_E_UNSUPPORTED;
-    }
-    return RWR_OK;
-}
-
-// A FilterCheck's verdict on the arguments of a filtered entry, as status and message (FILTER_NOOP is the caller's).  The typed
-// part goes through typed_verdict_status, except the candidate type, whose range has grown by FILTER_ANY_TYPE here.
-static int32_t filter_verdict_status(const char *who, const FilterCheck &c, int32_t n, int32_t top_n, int32_t cand_type,
-                                     uint32_t excl_edge_mask, const char *null_arg, const char *top_n_hint, const int64_t *deny_ptr,
-                                     const int64_t *test_ptr)
-{
-    switch (c.verdict) {
-        case FILTER_OK:
-        case FILTER_NOOP: break;
-        case FILTER_TYPED:
-            if (c.typed.verdict == TYPED_BAD_CAND_TYPE) {
-                set_error("%s: cand_type %d is outside [-1, 255]", who, cand_type);
-                return RWR_E_INVALID;
-            }
-            return typed_verdict_status(who, c.typed, n, top_n, cand_type, excl_edge_mask, null_arg, top_n_hint);
-        case FILTER_NULL_POOL:
-            set_error("%s: NULL pool_idx", who);
-            return RWR_E_INVALID;
-        case FILTER_POOL_RANGE:
-            set_error("%s: pool index %d (pool position %lld) is outside [0, %d)", who, c.bad_index, (long long)c.bad_pos, n);
-            return RWR_E_RANGE;
-        case FILTER_DENY:
-            switch (c.deny.verdict) {
-                case EXCLUDE_OK: break;
-                case EXCLUDE_BAD_PTR0:
-                    set_error("%s: deny_ptr[0] = %lld, not 0", who, (long long)deny_ptr[0]);
-                    return RWR_E_INVALID;
-                case EXCLUDE_PTR_DECREASES:
-                    set_error("%s: deny_ptr decreases at batch position %d", who, c.deny.bad_k);
-                    return RWR_E_INVALID;
-                case EXCLUDE_NULL_IDX:
-                    set_error("%s: NULL deny_idx", who);
-                    return RWR_E_INVALID;
-                case EXCLUDE_BAD_INDEX:
-                    set_error("%s: deny index %d (batch position %d) is outside [0, %d)", who, c.deny.bad_index, c.deny.bad_k, n);
-                    return RWR_E_RANGE;
-            }
-            break;
-        case FILTER_TEST:
-            return eval_verdict_status(who, c.test, test_ptr, "pos_out");
-        case FILTER_TOP_N_LIMIT: {
-            TypedCheck t;
-            t.verdict = TYPED_TOP_N_LIMIT;
-            return typed_verdict_status(who, t, n, top_n, cand_type, excl_edge_mask, null_arg, top_n_hint);
-        }
-    }
-    return RWR_OK;
-}
-
-// A CapCheck's verdict on the arguments of a capped entry (CAP_NOOP is the caller's): the filtered part through
-// filter_verdict_status, then the cap's own two refusals around top_n's limit
-static int32_t cap_verdict_status(const char *who, const CapCheck &c, int32_t n, int32_t top_n, int32_t cand_type,
-                                  uint32_t excl_edge_mask, const char *null_arg, const char *top_n_hint, const int64_t *deny_ptr,
-                                  const int64_t *test_ptr, int32_t group_cap)
-{
-    switch (c.verdict) {
-        case CAP_OK:
-        case CAP_NOOP: break;
-        case CAP_FILTER:
-            return filter_verdict_status(who, c.filter, n, top_n, cand_type, excl_edge_mask, null_arg, top_n_hint, deny_ptr, test_ptr);
-        case CAP_BAD_CAP:
-            set_error("%s: group_cap %d is below 1", who, group_cap);
-            return RWR_E_INVALID;
-        case CAP_TOP_N_LIMIT: {
-            FilterCheck f;
-            f.verdict = FILTER_TOP_N_LIMIT;
-            return filter_verdict_status(who, f, n, top_n, cand_type, excl_edge_mask, null_arg, top_n_hint, deny_ptr, test_ptr);
-        }
-        case CAP_CAP_LIMIT:
-            set_error("%s: group_cap %d is beyond the limit of RWR_GROUP_CAP_MAX = %d entries per group", who, group_cap,
-                      (int)RWR_GROUP_CAP_MAX);
-            return RWR_E_UNSUPPORTED;
-    }
-    return RWR_OK;
+    if (st.status != RWR_OK) set_error("%s", st.text);
+    return st.status;
 }
 
 // ... and the graph and damping factor of the Recommendation entries: the exclusion marker (-1) and the ranking keys assume
@@ -320,6 +176,21 @@ static int32_t check_ranked_domain(const char *who, const rwr_graph *g, double d
         return RWR_E_UNSUPPORTED;
     }
     return RWR_OK;
+}
+
+// What every seed-driven typed entry does with the call it has filled in: typed_call.h's ladder, the no-op, the refusal, the
+// domain, and the one driver
+static int32_t typed_entry(const char *who, rwr_graph *g, const TypedCall &call, float d, int32_t n_iter)
+{
+    g_err[0] = 0;
+    const int32_t n = g ? g->n : 0;
+    const CallCheck c = typed_call_check(call, g != nullptr, n, rank_select_max_k());
+    if (c.verdict == CALL_NOOP) return RWR_OK;
+    RWR_TRY(report(call_status(who, c, call, n, rank_select_max_k())));
+    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
+    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
+    // Recommender.cs:14,16 -> Model.cs:33: the float is widened to double
+    return bound(who, g, [&] { return typed_body(g, call, (double)d, n_iter, who); });
 }
 
 }  // namespace rwr
@@ -471,59 +342,33 @@ int32_t rwr_recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K,
                                   int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t *ids, double *scores,
                                   int32_t *counts)
 {
-    static const char *const who = "rwr_recommend_typed_batch";
-    g_err[0] = 0;
-    const TypedCheck c = typed_check(g != nullptr, g ? g->n : 0, seeds, K, top_n, rank_select_max_k(), cand_type, excl_edge_mask,
-                                     ids && scores && counts);
-    if (c.verdict == TYPED_NOOP) return RWR_OK;
-    RWR_TRY(typed_verdict_status(who, c, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds, ids, scores or counts",
-                                 " (rwr_recommend_typed_eval_batch evaluates whole lists of a node type)"));
-    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
-    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
-    // Recommender.cs:14,16 -> Model.cs:33: the float is widened to double
-    return bound(who, g, [&] {
-        return recommend_typed_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, ids, scores, counts);
-    });
+    TypedCall c;
+    c.seeds = seeds, c.K = K, c.cand_type = cand_type, c.excl_edge_mask = excl_edge_mask, c.exclude_self = exclude_self;
+    c.top_n = top_n, c.ids = ids, c.scores = scores, c.counts = counts;
+    c.top_n_hint = " (rwr_recommend_typed_eval_batch evaluates whole lists of a node type)";
+    return typed_entry("rwr_recommend_typed_batch", g, c, d, n_iter);
 }
 
 int32_t rwr_recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
                                        int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
                                        const int64_t *test_ids, int64_t *n_hits, double *sum_precision, int64_t *list_len)
 {
-    static const char *const who = "rwr_recommend_typed_eval_batch";
-    g_err[0] = 0;
-    const TypedEvalCheck c = typed_eval_check(g != nullptr, g ? g->n : 0, seeds, K, cand_type, excl_edge_mask, test_ptr, test_ids,
-                                              n_hits, sum_precision);
-    if (c.typed.verdict == TYPED_NOOP) return RWR_OK;
-    // (top_n has no bound here: typed_eval_check gives neither top_n verdict)
-    RWR_TRY(typed_verdict_status(who, c.typed, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds", nullptr));
-    RWR_TRY(eval_verdict_status(who, c.eval, test_ptr));
-    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
-    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
-    return bound(who, g, [&] {
-        return recommend_typed_eval_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, test_ptr,
-                                          test_ids, n_hits, sum_precision, list_len);
-    });
+    TypedCall c;
+    c.seeds = seeds, c.K = K, c.cand_type = cand_type, c.excl_edge_mask = excl_edge_mask, c.exclude_self = exclude_self;
+    c.dest = CALL_EVAL, c.top_n = top_n;                         // (no list is written: top_n has no bound here)
+    c.test_ptr = test_ptr, c.test_ids = test_ids, c.n_hits = n_hits, c.sum_precision = sum_precision, c.list_len = list_len;
+    return typed_entry("rwr_recommend_typed_eval_batch", g, c, d, n_iter);
 }
 
 int32_t rwr_recommend_typed_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t cand_type,
                                             uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
                                             const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len)
 {
-    static const char *const who = "rwr_recommend_typed_positions_batch";
-    g_err[0] = 0;
-    // (pos_out stands where the evaluating entry has its two result arrays)
-    const TypedEvalCheck c = typed_eval_check(g != nullptr, g ? g->n : 0, seeds, K, cand_type, excl_edge_mask, test_ptr, test_ids,
-                                              pos_out, pos_out);
-    if (c.typed.verdict == TYPED_NOOP) return RWR_OK;
-    RWR_TRY(typed_verdict_status(who, c.typed, g ? g->n : 0, 0, cand_type, excl_edge_mask, "seeds", nullptr));
-    RWR_TRY(eval_verdict_status(who, c.eval, test_ptr, "pos_out"));
-    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
-    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
-    return bound(who, g, [&] {
-        return recommend_typed_positions_batch(g, seeds, K, (double)d, n_iter, cand_type, excl_edge_mask, exclude_self, test_ptr,
-                                               test_ids, pos_out, score_out, list_len);
-    });
+    TypedCall c;
+    c.seeds = seeds, c.K = K, c.cand_type = cand_type, c.excl_edge_mask = excl_edge_mask, c.exclude_self = exclude_self;
+    c.dest = CALL_POSITIONS;
+    c.test_ptr = test_ptr, c.test_ids = test_ids, c.pos_out = pos_out, c.score_out = score_out, c.list_len = list_len;
+    return typed_entry("rwr_recommend_typed_positions_batch", g, c, d, n_iter);
 }
 
 int32_t rwr_recommend_filtered_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
@@ -531,19 +376,12 @@ int32_t rwr_recommend_filtered_batch(rwr_graph *g, const int32_t *seeds, int32_t
                                      const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, int64_t *ids,
                                      double *scores, int32_t *counts)
 {
-    static const char *const who = "rwr_recommend_filtered_batch";
-    g_err[0] = 0;
-    const FilterCheck c = filter_check(g != nullptr, g ? g->n : 0, seeds, K, top_n, rank_select_max_k(), cand_type, excl_edge_mask,
-                                       ids && scores && counts, pool_count, pool_idx, deny_ptr, deny_idx);
-    if (c.verdict == FILTER_NOOP) return RWR_OK;
-    RWR_TRY(filter_verdict_status(who, c, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds, ids, scores or counts",
-                                  " (rwr_recommend_filtered_positions_batch answers for whole lists)", deny_ptr, nullptr));
-    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
-    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
-    return bound(who, g, [&] {
-        return recommend_filtered_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, pool_count,
-                                        pool_idx, deny_ptr, deny_idx, ids, scores, counts);
-    });
+    TypedCall c;
+    c.seeds = seeds, c.K = K, c.cand_type = cand_type, c.excl_edge_mask = excl_edge_mask, c.exclude_self = exclude_self;
+    c.any_type = true, c.pool_count = pool_count, c.pool_idx = pool_idx, c.deny_ptr = deny_ptr, c.deny_idx = deny_idx;
+    c.top_n = top_n, c.ids = ids, c.scores = scores, c.counts = counts;
+    c.top_n_hint = " (rwr_recommend_filtered_positions_batch answers for whole lists)";
+    return typed_entry("rwr_recommend_filtered_batch", g, c, d, n_iter);
 }
 
 int32_t rwr_recommend_filtered_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter,
@@ -552,18 +390,12 @@ int32_t rwr_recommend_filtered_positions_batch(rwr_graph *g, const int32_t *seed
                                                const int64_t *test_ptr, const int64_t *test_ids, int64_t *pos_out, double *score_out,
                                                int64_t *list_len)
 {
-    static const char *const who = "rwr_recommend_filtered_positions_batch";
-    g_err[0] = 0;
-    const FilterCheck c = filter_positions_check(g != nullptr, g ? g->n : 0, seeds, K, cand_type, excl_edge_mask, pool_count, pool_idx,
-                                                 deny_ptr, deny_idx, test_ptr, test_ids, pos_out);
-    if (c.verdict == FILTER_NOOP) return RWR_OK;
-    RWR_TRY(filter_verdict_status(who, c, g ? g->n : 0, 0, cand_type, excl_edge_mask, "seeds", nullptr, deny_ptr, test_ptr));
-    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
-    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
-    return bound(who, g, [&] {
-        return recommend_filtered_positions_batch(g, seeds, K, (double)d, n_iter, cand_type, excl_edge_mask, exclude_self, pool_count,
-                                                  pool_idx, deny_ptr, deny_idx, test_ptr, test_ids, pos_out, score_out, list_len);
-    });
+    TypedCall c;
+    c.seeds = seeds, c.K = K, c.cand_type = cand_type, c.excl_edge_mask = excl_edge_mask, c.exclude_self = exclude_self;
+    c.any_type = true, c.pool_count = pool_count, c.pool_idx = pool_idx, c.deny_ptr = deny_ptr, c.deny_idx = deny_idx;
+    c.dest = CALL_POSITIONS;
+    c.test_ptr = test_ptr, c.test_ids = test_ids, c.pos_out = pos_out, c.score_out = score_out, c.list_len = list_len;
+    return typed_entry("rwr_recommend_filtered_positions_batch", g, c, d, n_iter);
 }
 
 int32_t rwr_recommend_capped_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
@@ -571,19 +403,13 @@ int32_t rwr_recommend_capped_batch(rwr_graph *g, const int32_t *seeds, int32_t K
                                    const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of,
                                    int32_t group_cap, int64_t *ids, double *scores, int32_t *counts)
 {
-    static const char *const who = "rwr_recommend_capped_batch";
-    g_err[0] = 0;
-    const CapCheck c = cap_check(g != nullptr, g ? g->n : 0, seeds, K, top_n, rank_select_max_k(), cand_type, excl_edge_mask,
-                                 ids && scores && counts, pool_count, pool_idx, deny_ptr, deny_idx, group_of, group_cap);
-    if (c.verdict == CAP_NOOP) return RWR_OK;
-    RWR_TRY(cap_verdict_status(who, c, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds, ids, scores or counts",
-                               " (rwr_recommend_capped_positions_batch answers for whole lists)", deny_ptr, nullptr, group_cap));
-    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
-    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
-    return bound(who, g, [&] {
-        return recommend_capped_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, pool_count,
-                                      pool_idx, deny_ptr, deny_idx, group_of, group_cap, ids, scores, counts);
-    });
+    TypedCall c;
+    c.seeds = seeds, c.K = K, c.cand_type = cand_type, c.excl_edge_mask = excl_edge_mask, c.exclude_self = exclude_self;
+    c.any_type = true, c.pool_count = pool_count, c.pool_idx = pool_idx, c.deny_ptr = deny_ptr, c.deny_idx = deny_idx;
+    c.group_of = group_of, c.group_cap = group_cap;
+    c.top_n = top_n, c.ids = ids, c.scores = scores, c.counts = counts;
+    c.top_n_hint = " (rwr_recommend_capped_positions_batch answers for whole lists)";
+    return typed_entry("rwr_recommend_capped_batch", g, c, d, n_iter);
 }
 
 int32_t rwr_recommend_capped_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter,
@@ -592,19 +418,13 @@ int32_t rwr_recommend_capped_positions_batch(rwr_graph *g, const int32_t *seeds,
                                              const int32_t *group_of, int32_t group_cap, const int64_t *test_ptr,
                                              const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len)
 {
-    static const char *const who = "rwr_recommend_capped_positions_batch";
-    g_err[0] = 0;
-    const CapCheck c = cap_positions_check(g != nullptr, g ? g->n : 0, seeds, K, cand_type, excl_edge_mask, pool_count, pool_idx,
-                                           deny_ptr, deny_idx, test_ptr, test_ids, pos_out, group_of, group_cap);
-    if (c.verdict == CAP_NOOP) return RWR_OK;
-    RWR_TRY(cap_verdict_status(who, c, g ? g->n : 0, 0, cand_type, excl_edge_mask, "seeds", nullptr, deny_ptr, test_ptr, group_cap));
-    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
-    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
-    return bound(who, g, [&] {
-        return recommend_capped_positions_batch(g, seeds, K, (double)d, n_iter, cand_type, excl_edge_mask, exclude_self, pool_count,
-                                                pool_idx, deny_ptr, deny_idx, group_of, group_cap, test_ptr, test_ids, pos_out, score_out,
-                                                list_len);
-    });
+    TypedCall c;
+    c.seeds = seeds, c.K = K, c.cand_type = cand_type, c.excl_edge_mask = excl_edge_mask, c.exclude_self = exclude_self;
+    c.any_type = true, c.pool_count = pool_count, c.pool_idx = pool_idx, c.deny_ptr = deny_ptr, c.deny_idx = deny_idx;
+    c.group_of = group_of, c.group_cap = group_cap;
+    c.dest = CALL_POSITIONS;
+    c.test_ptr = test_ptr, c.test_ids = test_ids, c.pos_out = pos_out, c.score_out = score_out, c.list_len = list_len;
+    return typed_entry("rwr_recommend_capped_positions_batch", g, c, d, n_iter);
 }
 
 int32_t rwr_recommend_explained_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
@@ -613,40 +433,13 @@ int32_t rwr_recommend_explained_batch(rwr_graph *g, const int32_t *seeds, int32_
                                       int32_t group_cap, int32_t n_why, int64_t *ids, double *scores, int32_t *counts, int32_t *nodes,
                                       int32_t *why_src, double *why_term, int64_t *why_total)
 {
-    static const char *const who = "rwr_recommend_explained_batch";
-    g_err[0] = 0;
-    const ExplainCheck c = explain_check(g != nullptr, g ? g->n : 0, seeds, K, top_n, rank_select_max_k(), cand_type, excl_edge_mask,
-                                         ids && scores && counts, pool_count, pool_idx, deny_ptr, deny_idx, group_of, group_cap, n_why,
-                                         why_src, why_term);
-    CapCheck limit;                                              // (the two limits the capped entry words)
-    switch (c.verdict) {
-        case EXPLAIN_OK: break;
-        case EXPLAIN_NOOP: return RWR_OK;
-        case EXPLAIN_CAP:
-            return cap_verdict_status(who, c.cap, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds, ids, scores or counts", "",
-                                      deny_ptr, nullptr, group_cap);
-        case EXPLAIN_BAD_N_WHY:
-            set_error("%s: n_why %d is below 0", who, n_why);
-            return RWR_E_INVALID;
-        case EXPLAIN_NULL_WHY:
-            set_error("%s: NULL why_src or why_term with n_why %d", who, n_why);
-            return RWR_E_INVALID;
-        case EXPLAIN_TOP_N_LIMIT:
-        case EXPLAIN_CAP_LIMIT:
-            limit.verdict = c.verdict == EXPLAIN_TOP_N_LIMIT ? CAP_TOP_N_LIMIT : CAP_CAP_LIMIT;
-            return cap_verdict_status(who, limit, g ? g->n : 0, top_n, cand_type, excl_edge_mask, "seeds, ids, scores or counts", "",
-                                      deny_ptr, nullptr, group_cap);
-        case EXPLAIN_WHY_LIMIT:
-            set_error("%s: n_why %d is beyond the limit of RWR_WHY_MAX = %d reasons per entry", who, n_why, (int)RWR_WHY_MAX);
-            return RWR_E_UNSUPPORTED;
-    }
-    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
-    if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
-    return bound(who, g, [&] {
-        return recommend_explained_batch(g, seeds, K, (double)d, n_iter, top_n, cand_type, excl_edge_mask, exclude_self, pool_count,
-                                         pool_idx, deny_ptr, deny_idx, group_of, group_cap, n_why, ids, scores, counts, nodes, why_src,
-                                         why_term, why_total);
-    });
+    TypedCall c;
+    c.seeds = seeds, c.K = K, c.cand_type = cand_type, c.excl_edge_mask = excl_edge_mask, c.exclude_self = exclude_self;
+    c.any_type = true, c.pool_count = pool_count, c.pool_idx = pool_idx, c.deny_ptr = deny_ptr, c.deny_idx = deny_idx;
+    c.group_of = group_of, c.group_cap = group_cap;
+    c.top_n = top_n, c.ids = ids, c.scores = scores, c.counts = counts;
+    c.n_why = n_why, c.nodes = nodes, c.why_src = why_src, c.why_term = why_term, c.why_total = why_total;
+    return typed_entry("rwr_recommend_explained_batch", g, c, d, n_iter);
 }
 
 int32_t rwr_recommend(rwr_graph *g, int32_t seed, float d, int32_t n_iter, int32_t top_n, int64_t *out_id,
@@ -869,9 +662,11 @@ int32_t rwr_recommend_restart_typed_batch(rwr_graph *g, int32_t K, const int64_t
     if (K < 0) { set_error("%s: negative K", who); return RWR_E_INVALID; }
     if (K == 0) return RWR_OK;
     if (!sup_ptr || !ids || !scores || !counts) { set_error("%s: NULL sup_ptr, ids, scores or counts", who); return RWR_E_INVALID; }
-    TypedCheck c;                                                // (the graph, K and the pointers were looked at above)
+    TypedCall t;                                                 // (the graph, K and the pointers were looked at above)
+    t.top_n = top_n, t.cand_type = cand_type, t.excl_edge_mask = excl_edge_mask;
+    CallCheck c;
     c.verdict = restart_typed_check(top_n, rank_select_max_k(), cand_type, excl_edge_mask);
-    RWR_TRY(typed_verdict_status(who, c, g->n, top_n, cand_type, excl_edge_mask, "", ""));
+    RWR_TRY(report(call_status(who, c, t, g->n, rank_select_max_k())));
     RWR_TRY(check_ranked_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start, excl_ptr, excl_idx));
     RWR_TRY(check_ranked_domain(who, g, d, "rwr_model_run_restart_batch"));
     if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
@@ -896,7 +691,7 @@ int32_t rwr_recommend_restart_eval_batch(rwr_graph *g, int32_t K, const int64_t 
     if (K == 0) return RWR_OK;
     if (!sup_ptr) { set_error("%s: NULL sup_ptr", who); return RWR_E_INVALID; }
     RWR_TRY(check_ranked_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start, excl_ptr, excl_idx));
-    RWR_TRY(eval_verdict_status(who, eval_check(K, test_ptr, test_ids, n_hits, sum_precision), test_ptr));
+    RWR_TRY(report(eval_status(who, eval_check(K, test_ptr, test_ids, n_hits, sum_precision), test_ptr, "n_hits or sum_precision")));
     RWR_TRY(check_ranked_domain(who, g, d, "rwr_model_run_restart_batch"));
     if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
     return bound(who, g, [&] {
@@ -918,11 +713,13 @@ int32_t rwr_recommend_restart_typed_positions_batch(rwr_graph *g, int32_t K, con
     if (K < 0) { set_error("%s: negative K", who); return RWR_E_INVALID; }
     if (K == 0) return RWR_OK;
     if (!sup_ptr) { set_error("%s: NULL sup_ptr", who); return RWR_E_INVALID; }
-    TypedCheck c;                                                // (no top_n here: the whole lists)
+    TypedCall t;                                                 // (no top_n here: the whole lists)
+    t.cand_type = cand_type, t.excl_edge_mask = excl_edge_mask;
+    CallCheck c;
     c.verdict = restart_typed_check(1, 1, cand_type, excl_edge_mask);
-    RWR_TRY(typed_verdict_status(who, c, g->n, 0, cand_type, excl_edge_mask, "", nullptr));
+    RWR_TRY(report(call_status(who, c, t, g->n, rank_select_max_k())));
     RWR_TRY(check_ranked_vectors(who, g->n, K, sup_ptr, sup_idx, sup_val, start, excl_ptr, excl_idx));
-    RWR_TRY(eval_verdict_status(who, eval_check(K, test_ptr, test_ids, pos_out, pos_out), test_ptr, "pos_out"));
+    RWR_TRY(report(eval_status(who, eval_check(K, test_ptr, test_ids, pos_out, pos_out), test_ptr, "pos_out")));
     RWR_TRY(check_ranked_domain(who, g, d, "rwr_model_run_restart_batch"));
     if (n_iter < 0) n_iter = 0;   // Model.run(int): a non-positive count runs no iteration (Model.cs:69)
     // excl_ptr == NULL: set k is the indices of vector k's support, whatever their values

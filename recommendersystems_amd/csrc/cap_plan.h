@@ -1,8 +1,8 @@
-// What one rwr_recommend_capped_batch / rwr_recommend_capped_positions_batch call decides on the host: the
-// verdict on its arguments, the sort key of a labelled candidate, the geometry of the segments and chunks the device-side
-// selection works on, and a host model of that selection -- carried out by group_cap.hip.  Plain C++17 without HIP (the few
-// functions the kernels share carry CAP_HD), so that tests/cpp/cap_plan_check.cpp checks all of it against brute-force loops
-// on the host.
+// What one rwr_recommend_capped_batch / rwr_recommend_capped_positions_batch call decides on the host about its cap (DESIGN
+// §3.21): the sort key of a labelled candidate, the geometry of the segments and chunks the device-side selection works on,
+// and a host model of that selection -- carried out by group_cap.hip.  (The verdict on the arguments is typed_call.h's.)
+// Plain C++17 without HIP (the few functions the kernels share carry CAP_HD), so that tests/cpp/cap_plan_check.cpp checks all
+// of it against brute-force loops on the host.
 //
 // The cap keeps, per seed, at most m = group_cap candidates of every group: a candidate stays iff fewer than m candidates of
 // its label rank before it in that seed's list.  On the device that is a per-group, per-column top-m over the rank matrix:
@@ -197,60 +197,6 @@ inline CapKey cap_threshold(const double *col, size_t stride, const int64_t *nod
         cap_list_merge(seg, l);
     }
     return cap_list_threshold(seg);
-}
-
-// ---- the arguments of the two capped entries ---------------------------------------------------------------------------------------
-enum CapVerdict : int32_t {
-    CAP_OK = 0,
-    CAP_NOOP = 1,             // K == 0 with a graph: nothing to do, RWR_OK
-    CAP_FILTER = 2,           // filter.verdict says what: everything the filtered entry reports, its top_n limit excepted
-    CAP_BAD_CAP = 3,          // group_of != NULL with group_cap < 1                       (RWR_E_INVALID)
-    CAP_TOP_N_LIMIT = 4,      // top_n > top_n_max: the select path's limit                (RWR_E_UNSUPPORTED)
-    CAP_CAP_LIMIT = 5,        // group_of != NULL with group_cap > CAP_MAX                 (RWR_E_UNSUPPORTED)
-};
-
-struct CapCheck {
-    CapVerdict verdict = CAP_OK;
-    FilterCheck filter;
-};
-
-// group_of == nullptr: no cap, group_cap is not looked at
-inline void cap_limits_check(CapCheck &c, int32_t top_n, int32_t top_n_max, const int32_t *group_of, int32_t group_cap)
-{
-    if (group_of && group_cap < 1) { c.verdict = CAP_BAD_CAP; return; }
-    if (top_n > top_n_max) { c.verdict = CAP_TOP_N_LIMIT; return; }
-    if (group_of && group_cap > CAP_MAX) c.verdict = CAP_CAP_LIMIT;
-}
-
-// rwr_recommend_capped_batch.  In this order: what filter_check reports up to and including the deny lists; group_cap's
-// lower bound; top_n's limit; group_cap's limit.
-inline CapCheck cap_check(bool have_graph, int32_t n, const int32_t *seeds, int32_t K, int32_t top_n, int32_t top_n_max,
-                          int32_t cand_type, uint32_t excl_edge_mask, bool have_outputs, int64_t pool_count, const int32_t *pool_idx,
-                          const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of, int32_t group_cap)
-{
-    CapCheck c;
-    c.filter = filter_check(have_graph, n, seeds, K, top_n, 0x7FFFFFFF, cand_type, excl_edge_mask, have_outputs, pool_count, pool_idx,
-                            deny_ptr, deny_idx);
-    if (c.filter.verdict == FILTER_NOOP) { c.verdict = CAP_NOOP; return c; }
-    if (c.filter.verdict != FILTER_OK) { c.verdict = CAP_FILTER; return c; }
-    cap_limits_check(c, top_n, top_n_max, group_of, group_cap);
-    return c;
-}
-
-// rwr_recommend_capped_positions_batch: filter_positions_check (the test sets after the deny lists), then group_cap's lower
-// bound and its limit; there is no top_n.
-inline CapCheck cap_positions_check(bool have_graph, int32_t n, const int32_t *seeds, int32_t K, int32_t cand_type,
-                                    uint32_t excl_edge_mask, int64_t pool_count, const int32_t *pool_idx, const int64_t *deny_ptr,
-                                    const int32_t *deny_idx, const int64_t *test_ptr, const int64_t *test_ids, const void *pos_out,
-                                    const int32_t *group_of, int32_t group_cap)
-{
-    CapCheck c;
-    c.filter = filter_positions_check(have_graph, n, seeds, K, cand_type, excl_edge_mask, pool_count, pool_idx, deny_ptr, deny_idx,
-                                      test_ptr, test_ids, pos_out);
-    if (c.filter.verdict == FILTER_NOOP) { c.verdict = CAP_NOOP; return c; }
-    if (c.filter.verdict != FILTER_OK) { c.verdict = CAP_FILTER; return c; }
-    cap_limits_check(c, 0, 0, group_of, group_cap);
-    return c;
 }
 
 }  // namespace rwr

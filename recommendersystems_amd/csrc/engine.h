@@ -6,6 +6,7 @@
 #include "cand_plan.h"
 #include "common.h"
 #include "stage_layout.h"
+#include "typed_call.h"
 
 struct rwr_graph {
     int32_t device = 0;
@@ -300,17 +301,13 @@ void launch_restart_fold_cols(rwr_graph *g, int G, int32_t npairs, const int32_t
 void launch_restart_scatter_cols(rwr_graph *g, int G, int32_t npairs, const int32_t *pq, const int32_t *pr, const double *fold,
                                  double *Y, hipStream_t s);
 void launch_restart_init_cols(rwr_graph *g, int G, int tg, const int32_t *st, double *X, hipStream_t s);
-// typed.hip: K personalised walks ranked among the nodes of one type (rwr_recommend_typed_batch): candidates =
-// rows of type cand_type, the seed's raw out-links whose type has its bit in excl_edge_mask excluded, the seed too when
-// exclude_self; T whole steps; arguments as cand_plan.h's typed_check passed them, a nonneg graph and d in [0, 1]
-int32_t recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
-                              int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t *ids, double *scores,
-                              int32_t *counts);
-// ... or evaluated there (rwr_recommend_typed_eval_batch): Hits / average precision of every seed's WHOLE list
-// of that type, cut to top_n when top_n > 0 (any value), against test set k -- eval_count.hip over the candidate list
-int32_t recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
-                                   int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
-                                   const int64_t *test_ids, int64_t *n_hits, double *sum_precision, int64_t *list_len);
+// typed.hip: the one driver of the eight seed-driven typed entries (rwr_recommend_typed_batch, _typed_eval_batch,
+// _typed_positions_batch, _filtered_batch, _filtered_positions_batch, _capped_batch, _capped_positions_batch, _explained_batch;
+// DESIGN §3.16-3.22).  K personalised walks of T whole steps ranked among the call's candidates -- the rows of cand_type (-1:
+// of any type) that the pool lists -- the seed's raw out-links whose type has its bit in excl_edge_mask excluded, the seed too
+// when exclude_self, the rows of deny list k dropped, at most group_cap candidates per group kept; then the destination the
+// call names.  `call` as typed_call.h's typed_call_check passed it, a nonneg graph and d in [0, 1]; `who` names the entry
+int32_t typed_body(rwr_graph *g, const TypedCall &call, double d, int32_t n_iter, const char *who);
 // ... and the candidates restart_batch.hip's typed end shares with it: the device list of the rows with node_type == type,
 // ascending, cached per handle (cand_plan.h); call it on an idle stream and before the workspace is sized.  (The end of a
 // tile group itself -- exclusion, ranking or evaluation, copy-back -- is ranked_end.h's, for both drivers.)
@@ -321,48 +318,13 @@ int32_t recommend_restart_typed_batch(rwr_graph *g, int32_t K, const int64_t *su
                                       const double *sup_val, const int32_t *start, const int64_t *set_ptr, const int32_t *set_idx,
                                       double d, int32_t n_iter, int32_t top_n, int32_t cand_type, uint32_t excl_edge_mask,
                                       int32_t exclude_members, int64_t *ids, double *scores, int32_t *counts);
-// ... and the positions and scores of test ids in the WHOLE lists of both typed entries (rwr_recommend_typed_positions_batch,
-// rwr_recommend_restart_typed_positions_batch): eval_count.hip's counting, finished by eval_pos.hip
-int32_t recommend_typed_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type,
-                                        uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
-                                        const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len);
+// ... and the positions and scores of test ids in their WHOLE lists (rwr_recommend_restart_typed_positions_batch, DESIGN
+// §3.19): eval_count.hip's counting, finished by eval_pos.hip
 int32_t recommend_restart_typed_positions_batch(rwr_graph *g, int32_t K, const int64_t *sup_ptr, const int32_t *sup_idx,
                                                 const double *sup_val, const int32_t *start, const int64_t *set_ptr,
                                                 const int32_t *set_idx, double d, int32_t n_iter, int32_t cand_type,
                                                 uint32_t excl_edge_mask, int32_t exclude_members, const int64_t *test_ptr,
                                                 const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len);
-// filter.hip: the typed seed walks ranked within a caller-set pool and with per-seed deny lists (rwr_recommend_filtered_batch,
-// rwr_recommend_filtered_positions_batch): candidates = rows of cand_type (-1: of any type) that the pool lists
-// (pool_count < 0: no pool), the rows of deny list k dropped beside the typed entries' exclusion; arguments as
-// filter_plan.h's checks passed them
-int32_t recommend_filtered_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
-                                 int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count,
-                                 const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, int64_t *ids,
-                                 double *scores, int32_t *counts);
-int32_t recommend_filtered_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type,
-                                           uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count, const int32_t *pool_idx,
-                                           const int64_t *deny_ptr, const int32_t *deny_idx, const int64_t *test_ptr,
-                                           const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len);
-// group_cap.hip: the filtered walks with at most group_cap candidates per caller-set group in every list
-// (rwr_recommend_capped_batch, rwr_recommend_capped_positions_batch): group_of = n host labels (< 0: never
-// capped; nullptr: no cap, the filtered entry); arguments as cap_plan.h's checks passed them
-int32_t recommend_capped_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n, int32_t cand_type,
-                               uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count, const int32_t *pool_idx,
-                               const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of, int32_t group_cap, int64_t *ids,
-                               double *scores, int32_t *counts);
-int32_t recommend_capped_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type,
-                                         uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count, const int32_t *pool_idx,
-                                         const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of, int32_t group_cap,
-                                         const int64_t *test_ptr, const int64_t *test_ids, int64_t *pos_out, double *score_out,
-                                         int64_t *list_len);
-// explain.hip: the capped lists with, per entry, its node index, its best n_why in-link addends over the previous ranks and the
-// number of positive ones (rwr_recommend_explained_batch); arguments as explain_plan.h's check passed them; with
-// n_why == 0 and neither nodes nor why_total it is recommend_capped_batch
-int32_t recommend_explained_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
-                                  int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count,
-                                  const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of,
-                                  int32_t group_cap, int32_t n_why, int64_t *ids, double *scores, int32_t *counts, int32_t *nodes,
-                                  int32_t *why_src, double *why_term, int64_t *why_total);
 // model.hip pieces restart.hip runs as well (the loops around them: run_walk and GroupColumns, iterate.h).  A run's end condition (Model.run(int) / run(double) / run(), Model.cs:52-66):
 // T steps at most; !by_count: until checkConvergence's distance is < threshold, a failure after max_iters = RWR_MAX_ITERS steps
 struct RunEnd {

@@ -15,8 +15,6 @@
 // Value-free graphs have no in_w: the weight of every link of source u is w_src[u], the same double.
 #include "explain.h"
 
-#include "filter.h"
-#include "group_cap.h"
 #include "rank_keys.h"
 #include "ranked_end.h"
 
@@ -223,29 +221,6 @@ int32_t why_copy_back(rwr_graph *g, WhyEnd &w, int32_t K, int32_t top_n)
     if (w.why_total) RWR_HIP(hipMemcpyAsync(w.why_total, w.d_total.p, cells * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     RWR_HIP(hipStreamSynchronize(s));
     return RWR_OK;
-}
-
-// ---- the entry --------------------------------------------------------------------------------------------------------------------
-
-int32_t recommend_explained_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
-                                  int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count,
-                                  const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of,
-                                  int32_t group_cap, int32_t n_why, int64_t *ids, double *scores, int32_t *counts, int32_t *nodes,
-                                  int32_t *why_src, double *why_term, int64_t *why_total)
-{
-    CallFilter flt;
-    flt.pool_count = pool_count, flt.pool_idx = pool_idx, flt.deny_ptr = deny_ptr, flt.deny_idx = deny_idx;
-    GroupCap cap;
-    cap.group_of = group_of, cap.m = group_cap;
-    WhyEnd why;
-    why.n_why = n_why, why.T = n_iter, why.c1 = 1 - d;           // (GroupIter's c1: Model.cs:84)
-    why.nodes = nodes, why.why_src = why_src, why.why_term = why_term, why.why_total = why_total;
-    RankedEnd end;
-    end.who = "rwr_recommend_explained_batch";
-    end.top_n = top_n, end.ids = ids, end.scores = scores, end.counts = counts;
-    if (group_of) end.cap = &cap;
-    if (n_why > 0 || nodes || why_total) end.why = &why;         // (nothing asked for: the capped entry, launch for launch)
-    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end, &flt); });
 }
 
 }  // namespace rwr

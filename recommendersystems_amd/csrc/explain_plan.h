@@ -1,8 +1,8 @@
-// What one rwr_recommend_explained_batch call decides on the host: the verdict on its arguments, the sizes of
-// its extra tables, and a host model of the selection explain.hip carries out per list entry -- the best n_why in-link
-// addends by (value bits descending, in-list position ascending) and the number of positive addends.  Plain C++17 without
-// HIP (the functions the kernel shares carry WHY_HD), so that tests/cpp/explain_plan_check.cpp checks all of it against
-// brute-force loops on the host.
+// What one rwr_recommend_explained_batch call decides on the host about its reasons: the sizes of its extra
+// tables, and a host model of the selection explain.hip carries out per list entry -- the best n_why in-link addends by
+// (value bits descending, in-list position ascending) and the number of positive addends.  (The verdict on the arguments is
+// typed_call.h's.)  Plain C++17 without HIP (the functions the kernel shares carry WHY_HD), so that
+// tests/cpp/explain_plan_check.cpp checks all of it against brute-force loops on the host.
 //
 // The reasons of list entry v of a column: in-entry e (position e of v's in-list, the addend order of Model.deliverRanks)
 // has the addend a_e = fl(fl(c1 * y[u_e]) * w_e) -- why_addend() -- and is a reason iff a_e > 0.  Addends are >= +0.0, so
@@ -132,43 +132,5 @@ inline int64_t why_select(int64_t deg, double c1, Y &&y, W &&w, int32_t r, int32
 inline size_t why_entry_cells(int32_t K, int32_t top_n) { return (size_t)K * (size_t)top_n; }
 inline size_t why_reason_cells(int32_t K, int32_t top_n, int32_t n_why) { return why_entry_cells(K, top_n) * (size_t)n_why; }
 WHY_HD size_t why_offset(int32_t k, int32_t j, int32_t top_n, int32_t n_why) { return ((size_t)k * (size_t)top_n + (size_t)j) * (size_t)n_why; }
-
-// ---- the arguments ----------------------------------------------------------------------------------------------------------------
-enum ExplainVerdict : int32_t {
-    EXPLAIN_OK = 0,
-    EXPLAIN_NOOP = 1,            // K == 0 with a graph: nothing to do, RWR_OK
-    EXPLAIN_CAP = 2,             // cap.verdict says what: everything the capped entry reports up to and including group_cap < 1
-    EXPLAIN_BAD_N_WHY = 3,       // n_why < 0                                               (RWR_E_INVALID)
-    EXPLAIN_NULL_WHY = 4,        // n_why > 0 with a NULL why_src or why_term               (RWR_E_INVALID)
-    EXPLAIN_TOP_N_LIMIT = 5,     // top_n > top_n_max: the select path's limit              (RWR_E_UNSUPPORTED)
-    EXPLAIN_CAP_LIMIT = 6,       // group_of != NULL with group_cap > CAP_MAX               (RWR_E_UNSUPPORTED)
-    EXPLAIN_WHY_LIMIT = 7,       // n_why > WHY_MAX                                         (RWR_E_UNSUPPORTED)
-};
-
-struct ExplainCheck {
-    ExplainVerdict verdict = EXPLAIN_OK;
-    CapCheck cap;
-};
-
-// In this order: what cap_check reports up to and including group_cap's lower bound; n_why's lower bound and its tables; the
-// limits of top_n, group_cap, n_why.  (The graph's and the damping factor's domain come after all of them: api.hip.)
-inline ExplainCheck explain_check(bool have_graph, int32_t n, const int32_t *seeds, int32_t K, int32_t top_n, int32_t top_n_max,
-                                  int32_t cand_type, uint32_t excl_edge_mask, bool have_outputs, int64_t pool_count,
-                                  const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of,
-                                  int32_t group_cap, int32_t n_why, const void *why_src, const void *why_term)
-{
-    ExplainCheck c;
-    // (limits out of the way: cap_check reports them in front of ours otherwise)
-    c.cap = cap_check(have_graph, n, seeds, K, top_n, 0x7FFFFFFF, cand_type, excl_edge_mask, have_outputs, pool_count, pool_idx, deny_ptr,
-                      deny_idx, group_of, group_cap);
-    if (c.cap.verdict == CAP_NOOP) { c.verdict = EXPLAIN_NOOP; return c; }
-    if (c.cap.verdict == CAP_FILTER || c.cap.verdict == CAP_BAD_CAP) { c.verdict = EXPLAIN_CAP; return c; }
-    if (n_why < 0) { c.verdict = EXPLAIN_BAD_N_WHY; return c; }
-    if (n_why > 0 && (!why_src || !why_term)) { c.verdict = EXPLAIN_NULL_WHY; return c; }
-    if (top_n > top_n_max) { c.verdict = EXPLAIN_TOP_N_LIMIT; return c; }
-    if (group_of && group_cap > CAP_MAX) { c.verdict = EXPLAIN_CAP_LIMIT; return c; }
-    if (n_why > WHY_MAX) c.verdict = EXPLAIN_WHY_LIMIT;
-    return c;
-}
 
 }  // namespace rwr

@@ -10,7 +10,7 @@ namespace rwr {
 // The cap of one call.  The object is declared before the driver's StreamsIdle (ranked_end.h's lifetime rule): its device
 // buffers outlive the kernels that read them, on error paths too.
 struct GroupCap {
-    const int32_t *group_of = nullptr;     // host, n labels as cap_check passed them; < 0: the node is never capped
+    const int32_t *group_of = nullptr;     // host, n labels as typed_call_check passed them; < 0: the node is never capped
     int32_t m = 0;                         // group_cap, in [1, CAP_MAX]
 
     // cap_build: the sorted keys of the call's labelled candidates and cap_plan.h's tables over them

@@ -389,42 +389,4 @@ int32_t cap_group(rwr_graph *g, GroupCap &c, int G, int tg, const int32_t *slot_
     return RWR_OK;
 }
 
-// ---- the entries ------------------------------------------------------------------------------------------------------------------
-
-int32_t recommend_capped_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n, int32_t cand_type,
-                               uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count, const int32_t *pool_idx,
-                               const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of, int32_t group_cap, int64_t *ids,
-                               double *scores, int32_t *counts)
-{
-    CallFilter flt;
-    flt.pool_count = pool_count, flt.pool_idx = pool_idx, flt.deny_ptr = deny_ptr, flt.deny_idx = deny_idx;
-    GroupCap cap;
-    cap.group_of = group_of, cap.m = group_cap;
-    RankedEnd end;
-    end.who = "rwr_recommend_capped_batch";
-    end.top_n = top_n, end.ids = ids, end.scores = scores, end.counts = counts;
-    if (group_of) end.cap = &cap;
-    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end, &flt); });
-}
-
-int32_t recommend_capped_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type,
-                                         uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count, const int32_t *pool_idx,
-                                         const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of, int32_t group_cap,
-                                         const int64_t *test_ptr, const int64_t *test_ids, int64_t *pos_out, double *score_out,
-                                         int64_t *list_len)
-{
-    CallFilter flt;
-    flt.pool_count = pool_count, flt.pool_idx = pool_idx, flt.deny_ptr = deny_ptr, flt.deny_idx = deny_idx;
-    GroupCap cap;
-    cap.group_of = group_of, cap.m = group_cap;
-    PosEnd pe;
-    pe.ev.test_ptr = test_ptr, pe.ev.test_ids = test_ids;
-    pe.pos_out = pos_out, pe.score_out = score_out, pe.list_len = list_len;
-    RankedEnd end;
-    end.who = "rwr_recommend_capped_positions_batch";
-    end.pos = &pe;
-    if (group_of) end.cap = &cap;
-    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end, &flt); });
-}
-
 }  // namespace rwr

@@ -1,8 +1,7 @@
 // What the two typed ends of DESIGN §3.17 decide on the host beside the plans they share with their neighbours: the
-// (slot, member) pairs whose own rows rwr_recommend_restart_typed_batch marks when exclude_members is set, and the verdicts on
-// the arguments that rwr_recommend_typed_eval_batch and rwr_recommend_restart_typed_batch add to those of the entries they
-// extend.  Plain C++17 without HIP, so that tests/cpp/member_plan_check.cpp checks all three against brute-force loops on the
-// host.
+// (slot, member) pairs whose own rows rwr_recommend_restart_typed_batch marks when exclude_members is set.  (The verdicts on
+// the arguments that rwr_recommend_typed_eval_batch and rwr_recommend_restart_typed_batch add are typed_call.h's.)  Plain
+// C++17 without HIP, so that tests/cpp/member_plan_check.cpp checks the pairs against brute-force loops on the host.
 //
 // Exclusion set k is the node list set_idx[set_ptr[k] .. set_ptr[k + 1]) (exclude_plan.h: the same sets, the same slot walk).
 // A group is not recommended its own members: every member's row of its vector's column is a non-candidate.  The pairs come
@@ -16,8 +15,6 @@
 #include <cstdint>
 #include <vector>
 
-#include "cand_plan.h"
-#include "eval_plan.h"
 #include "exclude_plan.h"
 
 namespace rwr {
@@ -50,37 +47,6 @@ inline MemberPlan member_plan(int32_t n, size_t nslots, const int32_t *slot_k, s
         p.group_off[grp + 1] = (int64_t)p.pair_slot.size();
     }
     return p;
-}
-
-// ---- the arguments of rwr_recommend_typed_eval_batch ------------------------------------------------------------------------
-// typed_check's verdicts on the graph, K, the seeds, the candidate type and the mask, in its order (top_n has no bound here
-// and the result arrays are eval_check's concern: BAD_TOP_N and TOP_N_LIMIT never come out, NULL_ARG means NULL seeds);
-// only when those pass, eval_check's verdict on the test sets and the result arrays.
-struct TypedEvalCheck {
-    TypedCheck typed;
-    EvalCheck eval;
-};
-
-inline TypedEvalCheck typed_eval_check(bool have_graph, int32_t n, const int32_t *seeds, int32_t K, int32_t cand_type,
-                                       uint32_t excl_edge_mask, const int64_t *test_ptr, const int64_t *test_ids,
-                                       const void *n_hits, const void *sum_precision)
-{
-    TypedEvalCheck c;
-    c.typed = typed_check(have_graph, n, seeds, K, 1, 1, cand_type, excl_edge_mask, true);
-    if (c.typed.verdict == TYPED_OK) c.eval = eval_check(K, test_ptr, test_ids, n_hits, sum_precision);
-    return c;
-}
-
-// ---- the arguments rwr_recommend_restart_typed_batch adds to rwr_recommend_restart_batch's -----------------------------------
-// After the graph, K and the pointers' presence, before the vectors and the sets are looked at: top_n's lower bound, the
-// candidate type, the mask, top_n's limit (the select path's, as the typed seed entry).  The verdicts are typed_check's.
-inline TypedVerdict restart_typed_check(int32_t top_n, int32_t top_n_max, int32_t cand_type, uint32_t excl_edge_mask)
-{
-    if (top_n < 1) return TYPED_BAD_TOP_N;
-    if (cand_type < 0 || cand_type > 255) return TYPED_BAD_CAND_TYPE;
-    if (excl_edge_mask >> TYPED_EDGE_TYPES) return TYPED_BAD_MASK;
-    if (top_n > top_n_max) return TYPED_TOP_N_LIMIT;
-    return TYPED_OK;
 }
 
 }  // namespace rwr

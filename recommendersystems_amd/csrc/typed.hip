@@ -18,24 +18,27 @@
 //  is the third destination: the same counting, the position and score of every test id in the whole list.
 //
 // rwr_recommend_filtered_batch and rwr_recommend_filtered_positions_batch (filter.hip) run this driver with a
-// CallFilter: the candidates narrowed to the caller's pool, the seeds' deny lists marked after the link exclusion.
-// rwr_recommend_capped_batch and rwr_recommend_capped_positions_batch (group_cap.hip) add a GroupCap to the
-// end: built here once the candidate list exists, applied by the end after the deny marks.
-// rwr_recommend_explained_batch (explain.hip) adds a WhyEnd: the end then also reads the group's previous ranks.
+// pool or deny lists in their TypedCall (typed_call.h): the candidates narrowed to the caller's pool, the seeds' deny lists
+// marked after the link exclusion.  rwr_recommend_capped_batch and rwr_recommend_capped_positions_batch (group_cap.hip,
+// DESIGN.md 3.21) add group labels, from which a GroupCap joins the end: built here once the candidate list exists, applied
+// by the end after the deny marks.  rwr_recommend_explained_batch (explain.hip) adds a WhyEnd: the end then
+// also reads the group's previous ranks.  All eight entries come in through the one typed_body().
+#include "explain.h"
 #include "filter.h"
 #include "group_cap.h"
 
 namespace rwr {
 
-// ---- candidate rows of a node type: count per block, scan of the counts, ordered scatter (cand_plan.h) -------------------------
+// ---- candidate rows: count per block, scan of the counts, ordered scatter (cand_plan.h, filter_plan.h) -------------------------
+// One compaction for the handle's per-type lists (no bitmap) and a call's own list (the pool's bitmap, any type).
 
 // does this thread's row match, and the wave's matches as a ballot; wc[w] = matches of wave w of the workgroup
-__device__ __forceinline__ bool cand_match(int32_t n, const uint8_t *__restrict__ node_type, int32_t t, int32_t *wc,
-                                           unsigned long long *bal)
+__device__ __forceinline__ bool cand_match(int32_t n, const uint8_t *__restrict__ node_type, int32_t t,
+                                           const uint32_t *__restrict__ bitmap, int32_t *wc, unsigned long long *bal)
 {
     const int32_t b = blockIdx.x;
     const int32_t i = cand_block_lo(b) + (int32_t)threadIdx.x;
-    const bool m = i < cand_block_hi(b, n) && node_type[i] == t;
+    const bool m = i < cand_block_hi(b, n) && filter_match(node_type, t, bitmap, i);
     *bal = __ballot(m);
     if ((threadIdx.x & (WAVE - 1)) == 0) wc[threadIdx.x / WAVE] = __popcll(*bal);
     __syncthreads();
@@ -43,11 +46,11 @@ __device__ __forceinline__ bool cand_match(int32_t n, const uint8_t *__restrict_
 }
 
 __global__ __launch_bounds__(CAND_BLOCK) void k_cand_count(int32_t n, const uint8_t *__restrict__ node_type, int32_t t,
-                                                           int32_t *__restrict__ block_cnt)
+                                                           const uint32_t *__restrict__ bitmap, int32_t *__restrict__ block_cnt)
 {
     __shared__ int32_t wc[CAND_BLOCK / WAVE];
     unsigned long long bal;
-    cand_match(n, node_type, t, wc, &bal);
+    cand_match(n, node_type, t, bitmap, wc, &bal);
     if (threadIdx.x == 0) {
         int32_t c = 0;
         for (int w = 0; w < CAND_BLOCK / WAVE; ++w) c += wc[w];
@@ -84,23 +87,42 @@ __global__ __launch_bounds__(CAND_SCAN_CHUNK) void k_cand_scan(int32_t nb, int32
 }
 
 __global__ __launch_bounds__(CAND_BLOCK) void k_cand_scatter(int32_t n, const uint8_t *__restrict__ node_type, int32_t t,
-                                                             const int32_t *__restrict__ off, int32_t total,
-                                                             int32_t *__restrict__ rows)
+                                                             const uint32_t *__restrict__ bitmap, const int32_t *__restrict__ off,
+                                                             int32_t total, int32_t *__restrict__ rows)
 {
     __shared__ int32_t wc[CAND_BLOCK / WAVE];
     unsigned long long bal;
-    if (!cand_match(n, node_type, t, wc, &bal)) return;
+    if (!cand_match(n, node_type, t, bitmap, wc, &bal)) return;
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
     int32_t pos = off[blockIdx.x];
     for (int q = 0; q < wv; ++q) pos += wc[q];
     pos += __popcll(bal & ((1ull << lane) - 1ull));
-    if (pos < total) rows[pos] = cand_block_lo(blockIdx.x) + (int32_t)threadIdx.x;
+    if (pos >= 0 && pos < total) rows[pos] = cand_block_lo(blockIdx.x) + (int32_t)threadIdx.x;
 }
 
-// ... for filter.hip's call-scoped lists, which are compacted the same way
+// ... for group_cap.hip's key and segment-head lists, which are compacted the same way
 void launch_cand_scan(int32_t nb, int32_t *off, hipStream_t s)
 {
     hipLaunchKernelGGL(k_cand_scan, dim3(1), dim3(CAND_SCAN_CHUNK), 0, s, nb, off);
+}
+
+int32_t cand_compact(rwr_graph *g, int32_t type, const uint32_t *bitmap, int32_t *off, DevBuf<int32_t> &list, int32_t *nrows)
+{
+    hipStream_t s = g->stream;
+    const int32_t n = g->n, nb = cand_blocks(n);
+    int32_t total = 0;
+    if (nb > 0) hipLaunchKernelGGL(k_cand_count, dim3((unsigned)nb), dim3(CAND_BLOCK), 0, s, n, g->node_type.p, type, bitmap, off);
+    launch_cand_scan(nb, off, s);
+    RWR_HIP(hipGetLastError());
+    RWR_HIP(hipMemcpyAsync(&total, off + nb, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    RWR_HIP(hipStreamSynchronize(s));
+    if (total < 0 || total > n) { set_error("candidate list build: %d rows of %d", total, n); return RWR_E_HIP; }
+    RWR_TRY(list.alloc((size_t)total));
+    if (total > 0)
+        hipLaunchKernelGGL(k_cand_scatter, dim3((unsigned)nb), dim3(CAND_BLOCK), 0, s, n, g->node_type.p, type, bitmap, off, total, list.p);
+    RWR_HIP(hipGetLastError());
+    *nrows = total;
+    return RWR_OK;
 }
 
 // The candidate list of node type `type` on the handle's current node set: the cached one, or built now into the entry
@@ -114,26 +136,15 @@ int32_t cand_rows_get(rwr_graph *g, int32_t type, const int32_t **rows, int32_t 
     if (!ch.hit) {
         e = CandEntry{};                                         // (a failure below leaves the entry empty)
         list.release();
-        hipStream_t s = g->stream;
-        const int32_t n = g->n, nb = cand_blocks(n);
         DevBuf<int32_t> off;
-        RWR_TRY(off.alloc((size_t)nb + 1));
+        RWR_TRY(off.alloc((size_t)cand_blocks(g->n) + 1));
         int32_t total = 0;
-        RWR_TRY(idle_on_error(s, [&]() -> int32_t {
-            if (nb > 0) hipLaunchKernelGGL(k_cand_count, dim3((unsigned)nb), dim3(CAND_BLOCK), 0, s, n, g->node_type.p, type, off.p);
-            hipLaunchKernelGGL(k_cand_scan, dim3(1), dim3(CAND_SCAN_CHUNK), 0, s, nb, off.p);
-            RWR_HIP(hipGetLastError());
-            RWR_HIP(hipMemcpyAsync(&total, off.p + nb, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            RWR_HIP(hipStreamSynchronize(s));
-            RWR_TRY(list.alloc((size_t)total));
-            if (total > 0)
-                hipLaunchKernelGGL(k_cand_scatter, dim3((unsigned)nb), dim3(CAND_BLOCK), 0, s, n, g->node_type.p, type, off.p, total,
-                                   list.p);
-            RWR_HIP(hipGetLastError());
-            RWR_HIP(hipStreamSynchronize(s));                    // (off goes back to the block cache on return)
+        RWR_TRY(idle_on_error(g->stream, [&]() -> int32_t {
+            RWR_TRY(cand_compact(g, type, nullptr, off.p, list, &total));
+            RWR_HIP(hipStreamSynchronize(g->stream));            // (off goes back to the block cache on return)
             return RWR_OK;
         }));
-        e.type = type, e.n = n, e.rows = total;
+        e.type = type, e.n = g->n, e.rows = total;
     }
     e.used = g->cand_calls;
     *rows = list.p;
@@ -143,44 +154,69 @@ int32_t cand_rows_get(rwr_graph *g, int32_t type, const int32_t **rows, int32_t 
 
 // ---- the driver --------------------------------------------------------------------------------------------------------------
 
-// end: its destination filled in by the entry; the candidates and the exclusion are this call's -- the list of cand_type,
-// the sets {seeds[k]}, the mask, and the seeds' own rows on request (a seed without raw links has no link to mark it by).
-// flt (the filtered entries, filter.hip; nullptr: none): a pool or cand_type FILTER_ANY_TYPE puts the call's own list
-// (filter_rows_build) in the place of the handle's cached one, which is then neither read nor evicted; the deny lists go to
-// the end as its second set description.  end.cap (the capped entries, group_cap.hip; nullptr: none): its tables are built from
-// whichever list serves the call -- the cached one is only read
-int32_t typed_body(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type, uint32_t mask,
-                   int32_t exclude_self, RankedEnd &end, const CallFilter *flt)
+// The one driver of the eight seed-driven typed entries: `call` as typed_call_check passed it, a nonneg graph, d in [0, 1],
+// n_iter >= 0.  The candidates and the exclusion: the list of cand_type, the sets {seeds[k]}, the mask, and the seeds' own
+// rows on request (a seed without raw links has no link to mark it by).  A pool or cand_type FILTER_ANY_TYPE puts the call's
+// own list (filter_rows_build) in the place of the handle's cached one, which is then neither read nor evicted; the deny
+// lists go to the end as its second set description.  group_of != nullptr: the cap's tables are built from whichever list
+// serves the call -- the cached one is only read.  Reasons: only when something of them is asked for -- with n_why == 0 and
+// neither nodes nor why_total the explained entry is the capped one, launch for launch.
+int32_t typed_body(rwr_graph *g, const TypedCall &call, double d, int32_t n_iter, const char *who)
 {
     const double t_begin = now_ms();
     const int64_t T = n_iter;
+    const int32_t K = call.K;
     hipStream_t s = g->stream;
+    // (the end and what it points to are declared before idle: ranked_end.h's lifetime rule)
+    GroupCap cap;
+    cap.group_of = call.group_of, cap.m = call.group_cap;
+    WhyEnd why;
+    why.n_why = call.n_why, why.T = T, why.c1 = 1 - d;           // (GroupIter's c1: Model.cs:84)
+    why.nodes = call.nodes, why.why_src = call.why_src, why.why_term = call.why_term, why.why_total = call.why_total;
+    EvalEnd ev;
+    ev.test_ptr = call.test_ptr, ev.test_ids = call.test_ids, ev.top_n = call.top_n;
+    ev.n_hits = call.n_hits, ev.sum_precision = call.sum_precision, ev.list_len = call.list_len;
+    PosEnd pe;
+    pe.ev.test_ptr = call.test_ptr, pe.ev.test_ids = call.test_ids;
+    pe.pos_out = call.pos_out, pe.score_out = call.score_out, pe.list_len = call.list_len;
+    RankedEnd end;
+    end.who = who;
+    if (call.dest == CALL_LISTS) {
+        end.top_n = call.top_n, end.ids = call.ids, end.scores = call.scores, end.counts = call.counts;
+        if (call.n_why > 0 || call.nodes || call.why_total) end.why = &why;
+    } else if (call.dest == CALL_EVAL) {
+        end.ev = &ev;
+    } else {
+        end.pos = &pe;
+    }
+    if (call.group_of) end.cap = &cap;
+    end.deny_ptr = call.deny_ptr, end.deny_idx = call.deny_idx;
+
     Profile prof(g);
     DevBuf<int32_t> own_rows;                                    // (declared before idle: released after the call's last synchronisation)
     // (either list before the workspace is sized from what is free)
-    if (flt && (flt->pool_count >= 0 || cand_type == FILTER_ANY_TYPE)) {
-        RWR_TRY(filter_rows_build(g, cand_type, flt->pool_count, flt->pool_idx, own_rows, &end.nrows, prof));
+    if (call.pool_count >= 0 || call.cand_type == FILTER_ANY_TYPE) {
+        RWR_TRY(filter_rows_build(g, call.cand_type, call.pool_count, call.pool_idx, own_rows, &end.nrows, prof));
         end.rows = own_rows.p;
     } else {
-        RWR_TRY(cand_rows_get(g, cand_type, &end.rows, &end.nrows));
+        RWR_TRY(cand_rows_get(g, call.cand_type, &end.rows, &end.nrows));
     }
-    if (flt) end.deny_ptr = flt->deny_ptr, end.deny_idx = flt->deny_idx;
     const int G = resolve_G(g, K);
     int TG = 1;
     if (end.cap) {                                               // (a tile group holds at most this many tiles: ensure_workspace)
         const int ntiles_all = (int)cdiv((size_t)K, (size_t)G), most = g->opts.tile_group > 0 ? g->opts.tile_group : 192;
-        RWR_TRY(cap_build(g, *end.cap, end.rows, end.nrows, G, ntiles_all < most ? ntiles_all : most, prof));
+        RWR_TRY(cap_build(g, cap, end.rows, end.nrows, G, ntiles_all < most ? ntiles_all : most, prof));
     }
     RWR_TRY(ensure_workspace(g, G, K, &TG));
     const int ntiles = (int)cdiv((size_t)K, (size_t)G);
     std::vector<int32_t> slot_k;
-    RWR_TRY(upload_seed_slots(g, seeds, K, G, &slot_k));
+    RWR_TRY(upload_seed_slots(g, call.seeds, K, G, &slot_k));
 
     // set k = {seeds[k]}, its one member per slot in d_seeds
     std::vector<int64_t> set_ptr((size_t)K + 1);
     for (int32_t k = 0; k <= K; ++k) set_ptr[(size_t)k] = k;
-    end.set_ptr = set_ptr.data(), end.set_idx = seeds;
-    end.mask = mask, end.members = exclude_self != 0, end.slot_member = g->d_seeds.p;
+    end.set_ptr = set_ptr.data(), end.set_idx = call.seeds;
+    end.mask = call.excl_edge_mask, end.members = call.exclude_self != 0, end.slot_member = g->d_seeds.p;
     StreamsIdle idle{g};                                         // (declared after end: ranked_end.h)
     RWR_TRY(end.prepare(g, K, slot_k, (size_t)TG * G, s));
 
@@ -203,40 +239,5 @@ int32_t typed_body(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int3
     return finish_model_batch(g, prof, G, TG, t_begin);
 }
 
-int32_t recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
-                              int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t *ids, double *scores,
-                              int32_t *counts)
-{
-    RankedEnd end;
-    end.who = "rwr_recommend_typed_batch";
-    end.top_n = top_n, end.ids = ids, end.scores = scores, end.counts = counts;
-    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end, nullptr); });
-}
-
-int32_t recommend_typed_eval_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t top_n,
-                                   int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
-                                   const int64_t *test_ids, int64_t *n_hits, double *sum_precision, int64_t *list_len)
-{
-    EvalEnd ev;
-    ev.test_ptr = test_ptr, ev.test_ids = test_ids, ev.top_n = top_n;
-    ev.n_hits = n_hits, ev.sum_precision = sum_precision, ev.list_len = list_len;
-    RankedEnd end;
-    end.who = "rwr_recommend_typed_eval_batch";
-    end.ev = &ev;
-    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end, nullptr); });
-}
-
-int32_t recommend_typed_positions_batch(rwr_graph *g, const int32_t *seeds, int32_t K, double d, int32_t n_iter, int32_t cand_type,
-                                        uint32_t excl_edge_mask, int32_t exclude_self, const int64_t *test_ptr,
-                                        const int64_t *test_ids, int64_t *pos_out, double *score_out, int64_t *list_len)
-{
-    PosEnd pe;
-    pe.ev.test_ptr = test_ptr, pe.ev.test_ids = test_ids;
-    pe.pos_out = pos_out, pe.score_out = score_out, pe.list_len = list_len;
-    RankedEnd end;
-    end.who = "rwr_recommend_typed_positions_batch";
-    end.pos = &pe;
-    return no_throw(end.who, [&] { return typed_body(g, seeds, K, d, n_iter, cand_type, excl_edge_mask, exclude_self, end, nullptr); });
-}
-
 }  // namespace rwr
+

@@ -1,8 +1,10 @@
-// Host-side check of the typed recommendation's plan (recommendersystems_amd/csrc/cand_plan.h), built against the header alone
-// by tests/test_cand_plan.py: the block geometry and the block offsets of the candidate compaction against a direct count,
-// the cache's choice over sequences of (type, n) requests against a brute-force model of the rule, and every argument verdict
-// in its order.  Prints every failure and exits non-zero if there is one.
+// Host-side check of the typed recommendation's plan (recommendersystems_amd/csrc/cand_plan.h), built against the headers alone
+// by tests/test_cand_plan.py: the block geometry and the block offsets of the candidate compaction (the one host model,
+// filter_plan.h's, without a pool) against a direct count, and the cache's choice over sequences of (type, n) requests against
+// a brute-force model of the rule.  (The argument verdicts: tests/cpp/typed_call_check.cpp.)  Prints every failure and exits
+// non-zero if there is one.
 #include "cand_plan.h"
+#include "filter_plan.h"
 
 #include <cstdio>
 #include <random>
@@ -33,7 +35,7 @@ static void check_offsets(const std::string &name, const std::vector<uint8_t> &t
         at = hi;
     }
     if (at != n) fail(name + ": blocks do not cover the rows");
-    const std::vector<int32_t> off = cand_block_offsets(types.empty() ? nullptr : types.data(), n, t);
+    const std::vector<int32_t> off = filter_block_offsets(types.empty() ? nullptr : types.data(), n, t, nullptr);
     if (off.size() != (size_t)nb + 1) { fail(name + ": offset table length"); return; }
     // brute force: matches below every block's first row; the list a scatter by these offsets builds is the ascending one
     std::vector<int32_t> want_list, got_list;
@@ -55,6 +57,7 @@ static void check_offsets(const std::string &name, const std::vector<uint8_t> &t
             }
     }
     if (got_list != want_list) fail(name + ": the scattered list is not the ascending list of matches");
+    if (filter_list(types.empty() ? nullptr : types.data(), n, t, nullptr, off) != want_list) fail(name + ": the model's list");
 }
 
 static void check_all_offsets()
@@ -169,92 +172,10 @@ static void check_cache()
     }
 }
 
-// ---- the argument verdicts ---------------------------------------------------------------------------------------------------------
-
-struct Args {
-    bool graph = true;
-    int32_t n = 10;
-    std::vector<int32_t> seeds = {0, 9, 3};
-    bool null_seeds = false;
-    int32_t K = 3, top_n = 5, top_n_max = 1024, cand_type = 1;
-    uint32_t mask = 0x0c;
-    bool outs = true;
-};
-
-// the verdict by a plain restatement of the header comment of rwr_recommend_typed_batch, first finding first
-static TypedVerdict model_verdict(const Args &a, int32_t *bad_k)
-{
-    *bad_k = -1;
-    if (!a.graph) return TYPED_NULL_GRAPH;
-    if (a.K < 0) return TYPED_NEGATIVE_K;
-    if (a.K == 0) return TYPED_NOOP;
-    if (a.null_seeds || !a.outs) return TYPED_NULL_ARG;
-    if (a.top_n < 1) return TYPED_BAD_TOP_N;
-    if (a.cand_type < 0 || a.cand_type > 255) return TYPED_BAD_CAND_TYPE;
-    for (uint32_t bit = 8; bit < 32; ++bit)
-        if (a.mask & (1u << bit)) return TYPED_BAD_MASK;
-    for (int32_t k = 0; k < a.K; ++k)
-        if (a.seeds[(size_t)k] < 0 || a.seeds[(size_t)k] >= a.n) { *bad_k = k; return TYPED_SEED_RANGE; }
-    if (a.top_n > a.top_n_max) return TYPED_TOP_N_LIMIT;
-    return TYPED_OK;
-}
-
-static void check_args(const std::string &name, const Args &a, int want /* -1: the model decides */)
-{
-    int32_t bad_k = -1;
-    const TypedVerdict m = model_verdict(a, &bad_k);
-    const TypedCheck c = typed_check(a.graph, a.n, a.null_seeds ? nullptr : a.seeds.data(), a.K, a.top_n, a.top_n_max, a.cand_type,
-                                     a.mask, a.outs);
-    if (c.verdict != m || (want >= 0 && (int)c.verdict != want)) fail(name + ": verdict " + std::to_string((int)c.verdict));
-    if (m == TYPED_SEED_RANGE && (c.bad_k != bad_k || c.bad_seed != a.seeds[(size_t)bad_k])) fail(name + ": the offending seed");
-}
-
-static void check_verdicts()
-{
-    Args ok;
-    check_args("ok", ok, TYPED_OK);
-    { Args a; a.graph = false; a.K = -1; a.top_n = 0; a.cand_type = 900; check_args("NULL graph first", a, TYPED_NULL_GRAPH); }
-    { Args a; a.K = -1; a.null_seeds = true; check_args("negative K", a, TYPED_NEGATIVE_K); }
-    { Args a; a.K = 0; a.null_seeds = true; a.outs = false; a.top_n = 0; a.cand_type = -1; check_args("K = 0 is a no-op", a, TYPED_NOOP); }
-    { Args a; a.null_seeds = true; check_args("NULL seeds", a, TYPED_NULL_ARG); }
-    { Args a; a.outs = false; check_args("NULL outputs", a, TYPED_NULL_ARG); }
-    { Args a; a.top_n = 0; check_args("top_n 0", a, TYPED_BAD_TOP_N); }
-    { Args a; a.top_n = -3; check_args("top_n < 0", a, TYPED_BAD_TOP_N); }
-    { Args a; a.cand_type = -1; check_args("cand_type -1", a, TYPED_BAD_CAND_TYPE); }
-    { Args a; a.cand_type = 256; check_args("cand_type 256", a, TYPED_BAD_CAND_TYPE); }
-    { Args a; a.cand_type = 0; check_args("cand_type 0", a, TYPED_OK); }
-    { Args a; a.cand_type = 255; check_args("cand_type 255", a, TYPED_OK); }
-    { Args a; a.mask = 0; check_args("mask 0", a, TYPED_OK); }
-    { Args a; a.mask = 0xff; check_args("every legal bit", a, TYPED_OK); }
-    { Args a; a.mask = 1u; check_args("UNDEFINED's bit", a, TYPED_OK); }
-    { Args a; a.mask = 0x100; check_args("bit 8", a, TYPED_BAD_MASK); }
-    { Args a; a.mask = 0x80000002u; check_args("bit 31", a, TYPED_BAD_MASK); }
-    { Args a; a.seeds = {0, 10, -1}; check_args("seed n", a, TYPED_SEED_RANGE); }
-    { Args a; a.seeds = {0, 9, -1}; check_args("seed -1", a, TYPED_SEED_RANGE); }
-    { Args a; a.seeds = {4, 4, 4}; check_args("duplicate seeds", a, TYPED_OK); }
-    { Args a; a.top_n = 1024; check_args("top_n at the limit", a, TYPED_OK); }
-    { Args a; a.top_n = 1025; check_args("top_n beyond the limit", a, TYPED_TOP_N_LIMIT); }
-    { Args a; a.top_n = 1025; a.seeds = {0, 99, 1}; check_args("a bad seed before the limit", a, TYPED_SEED_RANGE); }
-    // every combination of one good and one bad value per argument: the first finding in the documented order wins
-    for (int bits = 0; bits < (1 << 8); ++bits) {
-        Args a;
-        a.graph = !(bits & 1);
-        a.K = (bits & 2) ? -2 : 3;
-        a.null_seeds = (bits & 4) != 0;
-        a.top_n = (bits & 8) ? 0 : 5;
-        a.cand_type = (bits & 16) ? 300 : 2;
-        a.mask = (bits & 32) ? 0x200 : 0x6;
-        if (bits & 64) a.seeds[1] = 10;
-        a.outs = !(bits & 128);
-        check_args("combination " + std::to_string(bits), a, -1);
-    }
-}
-
 int main()
 {
     check_all_offsets();
     check_cache();
-    check_verdicts();
     std::printf("%d failures\n", failures);
     return failures ? 1 : 0;
 }

@@ -1,7 +1,7 @@
 // Host-side check of the group cap's plan (recommendersystems_amd/csrc/cap_plan.h), built against the header alone by
 // tests/test_cap_plan.py: the order of the sort keys, the chunk and segment tables at the segment lengths that matter, the
-// selection model against a brute-force sort for every m, and every argument verdict in its order.  Prints every failure and
-// exits non-zero if there is one.
+// selection model against a brute-force sort for every m.  (The argument verdicts: tests/cpp/typed_call_check.cpp.)  Prints
+// every failure and exits non-zero if there is one.
 #include "cap_plan.h"
 
 #include <algorithm>
@@ -208,107 +208,11 @@ static void check_selection()
     if (!cap_better(top, hi) || !cap_better(lo, bottom) || !cap_is_top(top) || cap_is_top(hi)) fail("sentinels");
 }
 
-// ---- the verdicts -------------------------------------------------------------------------------------------------------------------
-
-static void check_verdicts()
-{
-    const int32_t n = 50, K = 3;
-    const int32_t seeds[] = {1, 2, 3}, bad_seeds[] = {1, 50, 3};
-    const int32_t pool[] = {4, 5}, bad_pool[] = {4, 50};
-    const int64_t dp[] = {0, 1, 1, 2}, bad_dp[] = {0, 2, 1, 2};
-    const int32_t di[] = {7, 8}, bad_di[] = {7, -1};
-    const int64_t tp[] = {0, 1, 2, 3}, bad_tp[] = {0, 2, 1, 3}, ti[] = {10, 11, 12};
-    std::vector<int32_t> group_of((size_t)n, 0);
-    const int32_t *go = group_of.data();
-    int64_t pos[3];
-    const int32_t TOP_MAX = 1024;
-
-    // the ranked entry: every fault beside all LATER ones
-    struct R { bool graph; const int32_t *s; int32_t K, top, cand; uint32_t mask; bool out; int64_t pc; const int32_t *pi; const int64_t *dp; const int32_t *di; const int32_t *go; int32_t cap; };
-    const R ok{true, seeds, K, 10, 1, 1u, true, 2, pool, dp, di, go, 2};
-    auto run = [&](const R &r) { return cap_check(r.graph, n, r.s, r.K, r.top, TOP_MAX, r.cand, r.mask, r.out, r.pc, r.pi, r.dp, r.di, r.go, r.cap); };
-    if (run(ok).verdict != CAP_OK) fail("ranked: a valid call");
-    // later faults, last first: cap limit, top_n limit, bad cap (cannot ride with the cap limit: one argument), deny, pool, typed
-    R r = ok;
-    r.cap = CAP_MAX + 1;
-    if (run(r).verdict != CAP_CAP_LIMIT) fail("ranked: cap limit");
-    r.top = TOP_MAX + 1;
-    if (run(r).verdict != CAP_TOP_N_LIMIT) fail("ranked: top_n limit before the cap limit");
-    R q = r; q.cap = 0;
-    if (run(q).verdict != CAP_BAD_CAP) fail("ranked: group_cap < 1 before top_n's limit");
-    q.cap = -5;
-    if (run(q).verdict != CAP_BAD_CAP) fail("ranked: negative group_cap");
-    for (R *x : {&r, &q}) {
-        R f = *x; f.di = bad_di;
-        CapCheck c = run(f);
-        if (c.verdict != CAP_FILTER || c.filter.verdict != FILTER_DENY || c.filter.deny.verdict != EXCLUDE_BAD_INDEX) fail("ranked: deny index before the cap");
-        f.dp = bad_dp; c = run(f);
-        if (c.verdict != CAP_FILTER || c.filter.verdict != FILTER_DENY || c.filter.deny.verdict != EXCLUDE_PTR_DECREASES) fail("ranked: deny_ptr");
-        f.pi = bad_pool; c = run(f);
-        if (c.verdict != CAP_FILTER || c.filter.verdict != FILTER_POOL_RANGE || c.filter.bad_pos != 1) fail("ranked: pool range");
-        f.pi = nullptr; c = run(f);
-        if (c.verdict != CAP_FILTER || c.filter.verdict != FILTER_NULL_POOL) fail("ranked: NULL pool");
-        f.s = bad_seeds; c = run(f);
-        if (c.verdict != CAP_FILTER || c.filter.verdict != FILTER_TYPED || c.filter.typed.verdict != TYPED_SEED_RANGE || c.filter.typed.bad_k != 1) fail("ranked: seed range");
-        f.mask = 1u << 8; c = run(f);
-        if (c.verdict != CAP_FILTER || c.filter.typed.verdict != TYPED_BAD_MASK) fail("ranked: mask");
-        f.cand = -2; c = run(f);
-        if (c.verdict != CAP_FILTER || c.filter.typed.verdict != TYPED_BAD_CAND_TYPE) fail("ranked: cand_type");
-        R t0 = f; t0.top = 0; c = run(t0);
-        if (c.verdict != CAP_FILTER || c.filter.typed.verdict != TYPED_BAD_TOP_N) fail("ranked: top_n < 1");
-        f.out = false; c = run(f);
-        if (c.verdict != CAP_FILTER || c.filter.typed.verdict != TYPED_NULL_ARG) fail("ranked: NULL outputs");
-        f.K = -1; c = run(f);
-        if (c.verdict != CAP_FILTER || c.filter.typed.verdict != TYPED_NEGATIVE_K) fail("ranked: negative K");
-        f.graph = false; c = run(f);
-        if (c.verdict != CAP_FILTER || c.filter.typed.verdict != TYPED_NULL_GRAPH) fail("ranked: NULL graph first");
-    }
-    // K == 0 is a no-op whatever else is there; no labels: group_cap is not looked at, top_n's limit stands
-    R z = q; z.K = 0;
-    if (run(z).verdict != CAP_NOOP) fail("ranked: K == 0");
-    R nl = ok; nl.go = nullptr; nl.cap = -3;
-    if (run(nl).verdict != CAP_OK) fail("ranked: group_cap without labels is ignored");
-    nl.cap = 99;
-    if (run(nl).verdict != CAP_OK) fail("ranked: a large group_cap without labels is ignored");
-    nl.top = TOP_MAX + 1;
-    if (run(nl).verdict != CAP_TOP_N_LIMIT) fail("ranked: top_n limit without labels");
-    for (int32_t cap = 1; cap <= CAP_MAX; ++cap) {
-        R g = ok; g.cap = cap;
-        if (run(g).verdict != CAP_OK) fail("ranked: group_cap " + std::to_string(cap));
-    }
-
-    // the positions entry: the test sets stand between the deny lists and the cap
-    struct P { const int64_t *dp; const int32_t *di; const int64_t *tp; const int64_t *ti; const void *out; const int32_t *go; int32_t cap; };
-    auto runp = [&](const P &p) { return cap_positions_check(true, n, seeds, K, 1, 1u, 2, pool, p.dp, p.di, p.tp, p.ti, p.out, p.go, p.cap); };
-    const P pok{dp, di, tp, ti, pos, go, 3};
-    if (runp(pok).verdict != CAP_OK) fail("positions: a valid call");
-    P p = pok; p.cap = CAP_MAX + 1;
-    if (runp(p).verdict != CAP_CAP_LIMIT) fail("positions: cap limit");
-    P p0 = pok; p0.cap = 0;
-    if (runp(p0).verdict != CAP_BAD_CAP) fail("positions: group_cap < 1");
-    for (P *x : {&p, &p0}) {
-        P f = *x; f.ti = nullptr;
-        CapCheck c = runp(f);
-        if (c.verdict != CAP_FILTER || c.filter.verdict != FILTER_TEST) fail("positions: NULL test_ids before the cap");
-        f.tp = bad_tp; c = runp(f);
-        if (c.verdict != CAP_FILTER || c.filter.verdict != FILTER_TEST) fail("positions: test_ptr before the cap");
-        f.out = nullptr; c = runp(f);
-        if (c.verdict != CAP_FILTER || c.filter.verdict != FILTER_TEST) fail("positions: NULL pos_out before the cap");
-        f.di = bad_di; c = runp(f);
-        if (c.verdict != CAP_FILTER || c.filter.verdict != FILTER_DENY) fail("positions: deny lists before the test sets");
-    }
-    P pn = pok; pn.go = nullptr; pn.cap = 0;
-    if (runp(pn).verdict != CAP_OK) fail("positions: group_cap without labels is ignored");
-    if (cap_positions_check(true, n, nullptr, 0, 1, 1u, 2, nullptr, bad_dp, nullptr, nullptr, nullptr, nullptr, go, 0).verdict != CAP_NOOP) fail("positions: K == 0");
-    if (cap_positions_check(false, n, seeds, K, 1, 1u, 2, pool, dp, di, tp, ti, pos, go, 0).verdict != CAP_FILTER) fail("positions: NULL graph");
-}
-
 int main()
 {
     check_keys();
     check_all_tables();
     check_selection();
-    check_verdicts();
     std::printf("%d failures\n", failures);
     return failures != 0;
 }

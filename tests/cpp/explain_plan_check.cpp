@@ -1,7 +1,7 @@
 // Host-side check of the explained entry's plan (recommendersystems_amd/csrc/explain_plan.h), built against the header alone
 // by tests/test_explain_plan.py: the addend's two roundings, the selection model against a brute-force sort for every n_why
-// and lane count, why_total, the table geometry, and every argument verdict in its order with all later faults present.
-// Prints every failure and exits non-zero if there is one.
+// and lane count, why_total, and the table geometry.  (The argument verdicts: tests/cpp/typed_call_check.cpp.)  Prints every
+// failure and exits non-zero if there is one.
 #include "explain_plan.h"
 
 #include <algorithm>
@@ -123,63 +123,11 @@ static void check_tables()
     if (why_offset(0x7FFFFFFF, 1023, 1024, 8) != ((size_t)0x7FFFFFFF * 1024 + 1023) * 8) fail("offsets: 64-bit");
 }
 
-// ---- the verdicts ----------------------------------------------------------------------------------------------------------------
-
-static void check_verdicts()
-{
-    const int32_t n = 10, top_max = 1024;
-    const int32_t seeds[] = {1, 2}, bad_seeds[] = {1, 10};
-    const int32_t pool[] = {3, 4}, bad_pool[] = {3, 10};
-    const int64_t dptr[] = {0, 1, 2}, bad_dptr[] = {1, 1, 2};
-    const int32_t didx[] = {5, 6};
-    const int32_t lab[10] = {0};
-    int32_t src[1];
-    double term[1];
-    auto v = [&](bool g, const int32_t *s, int32_t K, int32_t top_n, int32_t cand, uint32_t mask, bool outs, int64_t pc, const int32_t *pi,
-                 const int64_t *dp, const int32_t *lb, int32_t cap, int32_t r, const void *ws, const void *wt) {
-        return explain_check(g, n, s, K, top_n, top_max, cand, mask, outs, pc, pi, dp, didx, lb, cap, r, ws, wt);
-    };
-    // everything wrong at once: the order peels off one fault at a time
-    ExplainCheck c = v(false, nullptr, -1, 0, 999, 0xffff, false, 2, nullptr, bad_dptr, lab, 0, -1, nullptr, nullptr);
-    if (c.verdict != EXPLAIN_CAP || c.cap.verdict != CAP_FILTER || c.cap.filter.typed.verdict != TYPED_NULL_GRAPH) fail("verdict: NULL graph first");
-    c = v(true, bad_seeds, 2, 0, 1, 0, true, 2, bad_pool, bad_dptr, lab, 0, -1, nullptr, nullptr);
-    if (c.verdict != EXPLAIN_CAP || c.cap.verdict != CAP_FILTER) fail("verdict: the filtered part before the rest");
-    c = v(true, seeds, 2, 5, 1, 0, true, 2, pool, bad_dptr, lab, 0, -1, nullptr, nullptr);
-    if (c.verdict != EXPLAIN_CAP || c.cap.verdict != CAP_FILTER || c.cap.filter.verdict != FILTER_DENY) fail("verdict: deny lists before the cap");
-    c = v(true, seeds, 2, 2000, 1, 0, true, 2, pool, dptr, lab, 0, -1, nullptr, nullptr);
-    if (c.verdict != EXPLAIN_CAP || c.cap.verdict != CAP_BAD_CAP) fail("verdict: group_cap < 1 before n_why and the limits");
-    c = v(true, seeds, 2, 2000, 1, 0, true, 2, pool, dptr, lab, 99, -1, nullptr, nullptr);
-    if (c.verdict != EXPLAIN_BAD_N_WHY) fail("verdict: n_why < 0 before the limits");
-    c = v(true, seeds, 2, 2000, 1, 0, true, 2, pool, dptr, lab, 99, 99, nullptr, term);
-    if (c.verdict != EXPLAIN_NULL_WHY) fail("verdict: NULL why_src before the limits");
-    c = v(true, seeds, 2, 2000, 1, 0, true, 2, pool, dptr, lab, 99, 99, src, nullptr);
-    if (c.verdict != EXPLAIN_NULL_WHY) fail("verdict: NULL why_term before the limits");
-    c = v(true, seeds, 2, 2000, 1, 0, true, 2, pool, dptr, lab, 99, 99, src, term);
-    if (c.verdict != EXPLAIN_TOP_N_LIMIT) fail("verdict: top_n's limit first of the limits");
-    c = v(true, seeds, 2, 1024, 1, 0, true, 2, pool, dptr, lab, 99, 99, src, term);
-    if (c.verdict != EXPLAIN_CAP_LIMIT) fail("verdict: group_cap's limit before n_why's");
-    c = v(true, seeds, 2, 1024, 1, 0, true, 2, pool, dptr, lab, 8, 9, src, term);
-    if (c.verdict != EXPLAIN_WHY_LIMIT) fail("verdict: n_why's limit");
-    c = v(true, seeds, 2, 1024, 1, 0, true, 2, pool, dptr, nullptr, 99, 9, src, term);
-    if (c.verdict != EXPLAIN_WHY_LIMIT) fail("verdict: group_cap is not looked at without labels");
-    c = v(true, seeds, 2, 1024, 1, 0, true, 2, pool, dptr, lab, 8, 8, src, term);
-    if (c.verdict != EXPLAIN_OK) fail("verdict: the largest legal call");
-    c = v(true, seeds, 2, 1, -1, 0, true, -1, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr);
-    if (c.verdict != EXPLAIN_OK) fail("verdict: n_why 0 needs no tables");
-    c = v(true, nullptr, 0, 1, 1, 0, false, -1, nullptr, nullptr, lab, 0, -5, nullptr, nullptr);
-    if (c.verdict != EXPLAIN_NOOP) fail("verdict: K == 0 is a no-op before the cap and n_why");
-    // the capped entry's own order is the explained entry's up to the cap's lower bound
-    const CapCheck cc = cap_check(true, n, seeds, 2, 5, top_max, 1, 0, true, 2, pool, bad_dptr, didx, lab, 0);
-    c = v(true, seeds, 2, 5, 1, 0, true, 2, pool, bad_dptr, lab, 0, 3, src, term);
-    if (cc.verdict != c.cap.verdict || cc.filter.verdict != c.cap.filter.verdict) fail("verdict: the capped entry's part");
-}
-
 int main()
 {
     check_addend();
     check_select();
     check_tables();
-    check_verdicts();
     std::printf("%d failures\n", failures);
     return failures != 0;
 }

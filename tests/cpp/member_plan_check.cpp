@@ -1,8 +1,8 @@
 // Host-side check of the typed ends' plan (recommendersystems_amd/csrc/member_plan.h), built against the headers alone by
 // tests/test_member_plan.py: the (slot, member) pairs of hand-made and random cases against a direct walk over the sets (how
-// often each row of each slot is named), the pairs' order and group offsets, then the argument verdicts that
-// rwr_recommend_typed_eval_batch and rwr_recommend_restart_typed_batch add, against a plain restatement of their header
-// comments, first finding first.  Prints every failure and exits non-zero if there is one.
+// often each row of each slot is named), and the pairs' order and group offsets.  (The argument verdicts that
+// rwr_recommend_typed_eval_batch and rwr_recommend_restart_typed_batch add: tests/cpp/typed_call_check.cpp.)  Prints every
+// failure and exits non-zero if there is one.
 #include "member_plan.h"
 
 #include <algorithm>
@@ -91,70 +91,6 @@ static size_t check_case(const std::string &name, int32_t n, const Sets &sets, i
     return check_slots(name, n, sets, slot_k, (size_t)TG * G);
 }
 
-// ---- the verdicts, restated ------------------------------------------------------------------------------------------------
-
-struct EvalArgs {
-    bool have_graph;
-    int32_t n, K;
-    const int32_t *seeds;
-    int32_t cand_type;
-    uint32_t mask;
-    const int64_t *test_ptr, *test_ids;
-    const void *n_hits, *sum_precision;
-};
-
-// rwr.h, rwr_recommend_typed_eval_batch: NULL g first, K == 0 a no-op, then K, the seeds' presence, cand_type, the mask, every
-// seed; then test_ptr, the result arrays, test_ptr[0], the first decrease, test_ids, the first set that is too large
-static void check_eval_verdict(const std::string &name, const EvalArgs &a)
-{
-    TypedVerdict tv = TYPED_OK;
-    int32_t bad_k = -1, bad_seed = 0;
-    if (!a.have_graph) tv = TYPED_NULL_GRAPH;
-    else if (a.K < 0) tv = TYPED_NEGATIVE_K;
-    else if (a.K == 0) tv = TYPED_NOOP;
-    else if (!a.seeds) tv = TYPED_NULL_ARG;
-    else if (a.cand_type < 0 || a.cand_type > 255) tv = TYPED_BAD_CAND_TYPE;
-    else if (a.mask & ~0xFFu) tv = TYPED_BAD_MASK;
-    else
-        for (int32_t k = 0; k < a.K; ++k)
-            if (a.seeds[k] < 0 || a.seeds[k] >= a.n) { tv = TYPED_SEED_RANGE, bad_k = k, bad_seed = a.seeds[k]; break; }
-    EvalVerdict ev = EVAL_OK;
-    int32_t ev_k = -1;
-    if (tv == TYPED_OK) {
-        if (!a.test_ptr) ev = EVAL_NULL_PTR;
-        else if (!a.n_hits || !a.sum_precision) ev = EVAL_NULL_OUT;
-        else if (a.test_ptr[0] != 0) ev = EVAL_BAD_PTR0;
-        else {
-            for (int32_t k = 0; k < a.K && ev == EVAL_OK; ++k)
-                if (a.test_ptr[k + 1] < a.test_ptr[k]) ev = EVAL_PTR_DECREASES, ev_k = k;
-            if (ev == EVAL_OK && a.test_ptr[a.K] > 0 && !a.test_ids) ev = EVAL_NULL_IDS;
-            for (int32_t k = 0; k < a.K && ev == EVAL_OK; ++k)
-                if (a.test_ptr[k + 1] - a.test_ptr[k] > 0x7FFFFFFFll) ev = EVAL_SET_TOO_LARGE, ev_k = k;
-        }
-    }
-    const TypedEvalCheck c = typed_eval_check(a.have_graph, a.n, a.seeds, a.K, a.cand_type, a.mask, a.test_ptr, a.test_ids,
-                                              a.n_hits, a.sum_precision);
-    if (c.typed.verdict != tv || (tv == TYPED_SEED_RANGE && (c.typed.bad_k != bad_k || c.typed.bad_seed != bad_seed)))
-        fail(name + ": typed verdict " + std::to_string((int)c.typed.verdict) + ", expected " + std::to_string((int)tv));
-    if (c.eval.verdict != ev || (ev_k >= 0 && c.eval.bad_k != ev_k))
-        fail(name + ": eval verdict " + std::to_string((int)c.eval.verdict) + ", expected " + std::to_string((int)ev));
-    if (c.typed.verdict == TYPED_BAD_TOP_N || c.typed.verdict == TYPED_TOP_N_LIMIT) fail(name + ": a top_n verdict");
-}
-
-// rwr.h, rwr_recommend_restart_typed_batch: top_n < 1, cand_type, the mask, then the limit
-static void check_restart_verdict(int32_t top_n, int32_t top_n_max, int32_t cand_type, uint32_t mask)
-{
-    TypedVerdict want = TYPED_OK;
-    if (top_n < 1) want = TYPED_BAD_TOP_N;
-    else if (cand_type < 0 || cand_type > 255) want = TYPED_BAD_CAND_TYPE;
-    else if (mask & ~0xFFu) want = TYPED_BAD_MASK;
-    else if (top_n > top_n_max) want = TYPED_TOP_N_LIMIT;
-    const TypedVerdict got = restart_typed_check(top_n, top_n_max, cand_type, mask);
-    if (got != want)
-        fail("restart verdict top_n " + std::to_string(top_n) + " cand " + std::to_string(cand_type) + " mask " + std::to_string(mask) +
-             ": " + std::to_string((int)got) + ", expected " + std::to_string((int)want));
-}
-
 int main()
 {
     // one member, a member twice, an empty set, only empty sets
@@ -209,56 +145,6 @@ int main()
         const MemberPlan c = member_plan(5, 3, slot_k, 2, 3, ok, nullptr);
         if (c.check.verdict != EXCLUDE_NULL_IDX || !c.pair_slot.empty()) fail("NULL idx: not refused whole");
     }
-
-    // the verdicts of the evaluating typed entry: every finding alone, then random combinations (the first one wins)
-    {
-        const int32_t seeds[3] = {0, 4, 2}, bad_seeds[3] = {0, 5, -1};
-        const int64_t ok[4] = {0, 2, 2, 4}, ptr0[4] = {1, 2, 2, 4}, dec[4] = {0, 2, 1, 4}, big[4] = {0, 2, 0x80000002ll, 0x80000003ll};
-        const int64_t ids[4] = {7, 7, 9, -1}, zero[4] = {0, 0, 0, 0};
-        int64_t h[3];
-        double sp[3];
-        const EvalArgs good{true, 5, 3, seeds, 1, 0x0cu, ok, ids, h, sp};
-        check_eval_verdict("good", good);
-        EvalArgs a = good;
-        a.have_graph = false; check_eval_verdict("NULL graph", a); a = good;
-        a.K = -1; check_eval_verdict("negative K", a); a = good;
-        a.K = 0; check_eval_verdict("K = 0", a);
-        a.seeds = nullptr, a.test_ptr = nullptr, a.n_hits = nullptr; check_eval_verdict("K = 0 with nothing", a); a = good;
-        a.seeds = nullptr; check_eval_verdict("NULL seeds", a); a = good;
-        a.cand_type = 256; check_eval_verdict("cand_type 256", a); a.cand_type = -1; check_eval_verdict("cand_type -1", a); a = good;
-        a.cand_type = 255, a.mask = 0xffu; check_eval_verdict("the widest legal type and mask", a); a = good;
-        a.mask = 0x100u; check_eval_verdict("mask bit 8", a); a = good;
-        a.seeds = bad_seeds; check_eval_verdict("seed range", a); a = good;
-        a.test_ptr = nullptr; check_eval_verdict("NULL test_ptr", a); a = good;
-        a.n_hits = nullptr; check_eval_verdict("NULL n_hits", a); a = good;
-        a.sum_precision = nullptr; check_eval_verdict("NULL sum_precision", a); a = good;
-        a.test_ptr = ptr0; check_eval_verdict("test_ptr[0]", a); a = good;
-        a.test_ptr = dec; check_eval_verdict("decrease", a); a = good;
-        a.test_ids = nullptr; check_eval_verdict("NULL test_ids", a);
-        a.test_ptr = zero; check_eval_verdict("NULL test_ids, empty sets", a); a = good;
-        a.test_ptr = big; check_eval_verdict("set too large", a); a = good;
-        // the typed arguments come before the test sets
-        a.seeds = bad_seeds, a.test_ptr = nullptr; check_eval_verdict("seed range before NULL test_ptr", a); a = good;
-        a.mask = 0x100u, a.n_hits = nullptr; check_eval_verdict("mask before NULL n_hits", a); a = good;
-        const int64_t *ptrs[5] = {ok, ptr0, dec, big, nullptr};
-        for (int it = 0; it < 4000; ++it) {
-            EvalArgs r = good;
-            r.have_graph = rng() % 8 != 0;
-            r.K = (int32_t)(rng() % 5) - 1;
-            r.seeds = rng() % 6 == 0 ? nullptr : (rng() % 3 == 0 ? bad_seeds : seeds);
-            r.cand_type = (int32_t)(rng() % 260) - 2;
-            r.mask = rng() % 3 == 0 ? (uint32_t)(rng() % 0x400u) : 0x0cu;
-            r.test_ptr = ptrs[rng() % 5];
-            r.test_ids = rng() % 4 == 0 ? nullptr : ids;
-            r.n_hits = rng() % 6 == 0 ? nullptr : h;
-            r.sum_precision = rng() % 6 == 0 ? nullptr : sp;
-            check_eval_verdict("random verdict " + std::to_string(it), r);
-        }
-    }
-    // ... and of the typed restart entry
-    for (int32_t top_n : {-1, 0, 1, 10, 1024, 1025, 0x7FFFFFFF})
-        for (int32_t cand : {-1, 0, 1, 255, 256})
-            for (uint32_t mask : {0u, 0x0cu, 0xffu, 0x100u, 0x80000000u}) check_restart_verdict(top_n, 1024, cand, mask);
 
     std::printf("%d failures\n", failures);
     return failures ? 1 : 0;

@@ -1,8 +1,9 @@
 """CPU-side check of the typed recommendation's host plan (recommendersystems_amd/csrc/cand_plan.h): the block geometry and
-block offsets of the candidate-list compaction, which cached list serves a call (hit, rebuild in place, which entry a new type
-evicts -- over sequences with a growing node count), and the verdicts on the arguments of rwr_recommend_typed_batch.
-tests/cpp/cand_plan_check.cpp, a program of its own built against the header alone with the address and undefined-behaviour
-sanitizers, compares all three with brute-force loops.  No library, no Python extension and no GPU are involved."""
+block offsets of the candidate-list compaction (the one host model, filter_plan.h's, without a pool), and which cached list
+serves a call (hit, rebuild in place, which entry a new type evicts -- over sequences with a growing node count).  The verdicts
+on the arguments of rwr_recommend_typed_batch are tests/test_typed_call.py's.  tests/cpp/cand_plan_check.cpp, a program of its
+own built against the headers alone with the address and undefined-behaviour sanitizers, compares both with brute-force loops.
+No library, no Python extension and no GPU are involved."""
 import os
 import subprocess
 

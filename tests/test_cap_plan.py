@@ -1,9 +1,9 @@
 """CPU-side check of the group cap's host plan (recommendersystems_amd/csrc/cap_plan.h): the order of the sort keys
 (label << 32 | row), the chunk and segment tables for segment lengths 0, 1, m, m + 1, CAP_CHUNK - 1, CAP_CHUNK, CAP_CHUNK + 1 and
 3 x CAP_CHUNK + 1 (and at small chunks), all labels negative / one label for everything / every row its own label, the selection
-model against a brute-force sort for m = 1..8 (all-zero columns: ties by id; equal (score, id) pairs: ties by row), and the
-verdicts on the arguments of rwr_recommend_capped_batch and rwr_recommend_capped_positions_batch in their documented order with
-all later faults present.  tests/cpp/cap_plan_check.cpp, a program of its own built against the header alone with the address
+model against a brute-force sort for m = 1..8 (all-zero columns: ties by id; equal (score, id) pairs: ties by row).  (The
+verdicts on the arguments of rwr_recommend_capped_batch and rwr_recommend_capped_positions_batch are
+tests/test_typed_call.py's.)  tests/cpp/cap_plan_check.cpp, a program of its own built against the header alone with the address
 and undefined-behaviour sanitizers, compares all of them with brute-force loops.  No library, no Python extension and no GPU
 are involved."""
 import os

@@ -1,8 +1,8 @@
 """CPU-side check of the explained entry's host plan (recommendersystems_amd/csrc/explain_plan.h): the addend as two separately
 rounded products, the selection model the reasons kernel compiles -- best n_why by (value bits descending, in-list position
 ascending) and why_total -- against a brute-force sort for n_why = 0..8, in-degrees 0, 1, n_why - 1 .. n_why + 1, 63, 64, 65, 255 ..
-257, 513 and 700, lane counts 1, 2, 64 and 256, with ties everywhere and with mostly zero sources, the table sizes and offsets,
-and the verdicts on the arguments of rwr_recommend_explained_batch in their documented order with all later faults present.
+257, 513 and 700, lane counts 1, 2, 64 and 256, with ties everywhere and with mostly zero sources, and the table sizes and
+offsets.  (The verdicts on the arguments of rwr_recommend_explained_batch are tests/test_typed_call.py's.)
 tests/cpp/explain_plan_check.cpp, a program of its own built against the header alone with the address and undefined-behaviour
 sanitizers, compares all of them with brute-force loops.  No library, no Python extension and no GPU are involved."""
 import os

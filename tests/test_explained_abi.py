@@ -1,5 +1,5 @@
 """The reasons of ranked entries (rwr_recommend_explained_batch) at the C-ABI and in the host mirrors -- checks that need no GPU.
-The argument verdicts beyond the NULL graph are explain_plan.h's, checked in their order by tests/test_explain_plan.py; here the
+The argument verdicts beyond the NULL graph are typed_call.h's, checked in their order by tests/test_typed_call.py; here the
 header's text states that order."""
 import ctypes as C
 import inspect

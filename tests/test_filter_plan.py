@@ -1,7 +1,7 @@
 """CPU-side check of the filtered recommendation's host plan (recommendersystems_amd/csrc/filter_plan.h): the bitmap and block
 geometry of the candidate-list build (n = 0, 1, 31, 32, 33, 255, 256, 257 and beyond one scan chunk), the bitmap, block offsets
-and list of pools in any order and with duplicates, and the verdicts on the arguments of rwr_recommend_filtered_batch and
-rwr_recommend_filtered_positions_batch in their documented order.  tests/cpp/filter_plan_check.cpp, a program of its own built
+and list of pools in any order and with duplicates.  (The verdicts on the arguments of rwr_recommend_filtered_batch and
+rwr_recommend_filtered_positions_batch are tests/test_typed_call.py's.)  tests/cpp/filter_plan_check.cpp, a program of its own built
 against the header alone with the address and undefined-behaviour sanitizers, compares all of them with brute-force loops.  No
 library, no Python extension and no GPU are involved."""
 import os

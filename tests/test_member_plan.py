@@ -1,7 +1,7 @@
 """CPU-side check of the typed ends' host plan (recommendersystems_amd/csrc/member_plan.h): the (slot, member) pairs whose own
 rows rwr_recommend_restart_typed_batch marks -- slot order, group offsets, empty padding slots, repeated members, empty sets,
-group boundaries -- and the argument verdicts that rwr_recommend_typed_eval_batch and rwr_recommend_restart_typed_batch add to
-those of the entries they extend.  tests/cpp/member_plan_check.cpp, a program of its own built against the headers alone with
+group boundaries.  (The argument verdicts that rwr_recommend_typed_eval_batch and rwr_recommend_restart_typed_batch add to
+those of the entries they extend are tests/test_typed_call.py's.)  tests/cpp/member_plan_check.cpp, a program of its own built against the headers alone with
 the address and undefined-behaviour sanitizers, compares them with brute-force loops.  No library, no Python extension and no
 GPU are involved."""
 import os
