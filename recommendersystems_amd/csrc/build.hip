@@ -332,7 +332,8 @@ __global__ __launch_bounds__(256) void k_patch_links(int64_t count, const int64_
 // rebuilds such a graph per fold and methodology (Experiment.cs:69-105); its build was launch-bound: 18 dependent launches
 // of a few microseconds of work each cost ~270 us, the work itself ~60.  Same element-wise bodies, same sorts, same order of
 // operations per element as the general path (k_row_prepare, k_in_ptr, k_gather_in, k_order_keys*, k_item_*): bit-identical
-// arrays (tests/test_gpu_parity.py: test_build_graph_bitwise, the golden fixtures, the hypothesis graphs, incremental rebuilds).
+// arrays (tests/test_gpu_parity.py: test_build_graph_bitwise, the golden fixtures, the hypothesis graphs, incremental rebuilds;
+// tests/test_gpu_build_edges.py: both builds at their tile, long-row and sort-pass edges).
 #ifdef RWR_EXPERIMENTS
 #define BS_STAMP(I) { if (a.stamps && tid == 0) a.stamps[(I)] = __builtin_amdgcn_s_memrealtime(); }
 #else
