@@ -112,6 +112,30 @@ namespace Recommenders.RWRBased {
             return pos;
         }
 
+        // rwr_graph_remove_links on a built graph: the raw links at the given flattened positions (distinct, any order) leave
+        // their lists ON THE DEVICE (what edges[src].RemoveAt(k) does to the list); the surviving link at old position e is
+        // afterwards at e - (removed positions < e).  The dictionaries are not touched: remove the same links from `edges`, and
+        // the next buildGraph() finds nothing more to send.  (Deleting from `edges` WITHOUT this call makes buildGraph() send
+        // the graph whole in this binding: only the Python mirror finds removed links by a list diff.)
+        public void RemoveLinks(long[] linkIndex) {
+            int n = nodes.Count;
+            Native.Check(Native.rwr_graph_remove_links(handle, linkIndex.Length, linkIndex));
+            // the flat copies behind LoadNormalizedGraph() and the next buildGraph()'s diff follow
+            long m = rowptr[n];
+            var gone = new bool[m];
+            foreach (long p in linkIndex) gone[p] = true;
+            var rp = new long[n + 1];
+            var nd = new int[m - linkIndex.Length]; var nt = new byte[m - linkIndex.Length]; var nw = new double[m - linkIndex.Length];
+            long f = 0;
+            for (int i = 0; i < n; i++) {
+                for (long p = rowptr[i]; p < rowptr[i + 1]; p++)
+                    if (!gone[p]) { nd[f] = dst[p]; nt[f] = etype[p]; nw[f] = sentW[p]; f++; }
+                rp[i + 1] = f;
+            }
+            rowptr = rp; dst = nd; etype = nt; sentW = nw;
+            graph = null;
+        }
+
         // rwr_graph_append_nodes on a built graph: node j of `added` gets index nodes.Count + j and an empty list ON THE DEVICE
         // (nodes.Add(n + j, ...); edges.Add(n + j, new List<ForwardLink>()), Graph.cs:39-40), then the links are appended as
         // AppendLinks appends them, src and targets ranging over the grown node set; one device-side rebuild for both.  Returns

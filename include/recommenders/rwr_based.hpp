@@ -144,6 +144,31 @@ public:
         return pos;
     }
 
+    // rwr_graph_remove_links on a built graph: the raw links at the given flattened positions (distinct, any order) leave
+    // their lists on the device (edges[src].RemoveAt(k)); the surviving link at old position e is afterwards at
+    // e - (removed positions < e).  The caller's `edges` are not touched: remove the same links there before the next
+    // buildGraph(), which then finds nothing more to send.  (Deleting from `edges` WITHOUT this call makes buildGraph() send
+    // the graph whole in this binding: only the Python mirror finds removed links by a list diff.)
+    void removeLinks(const std::vector<int64_t> &linkIndex)
+    {
+        check(rwr_graph_remove_links(handle(), (int64_t)linkIndex.size(), linkIndex.data()));
+        // the flat copies behind graph() and the next buildGraph()'s diff follow
+        const int n = (int)nodes.size();
+        std::vector<uint8_t> gone((size_t)rowptr_[n], 0);
+        for (int64_t p : linkIndex) gone[(size_t)p] = 1;
+        std::vector<int64_t> rp((size_t)n + 1, 0);
+        std::vector<int32_t> nd;
+        std::vector<uint8_t> nt;
+        std::vector<double> nw;
+        for (int i = 0; i < n; ++i) {
+            for (int64_t p = rowptr_[i]; p < rowptr_[i + 1]; ++p)
+                if (!gone[(size_t)p]) { nd.push_back(sent_dst_[p]); nt.push_back(sent_etype_[p]); nw.push_back(sent_w_[p]); }
+            rp[(size_t)i + 1] = (int64_t)nd.size();
+        }
+        rowptr_ = rp; dst_ = nd; etype_ = nt;
+        sent_dst_ = nd; sent_etype_ = nt; sent_w_ = nw;
+    }
+
     // the public field Graph.graph (Graph.cs:43): normalised explicit links per node; empty optional == null
     std::map<int, std::unique_ptr<std::vector<ForwardLink>>> graph()
     {

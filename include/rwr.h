@@ -191,7 +191,9 @@ int32_t rwr_graph_destroy(rwr_graph *g);
  * on the same handle.  Argument errors (RWR_E_INVALID / RWR_E_RANGE) are detected before
  * anything is patched and leave the graph as it was; a failure AFTER the patch (out of device
  * memory during the rebuild, a HIP error) invalidates the handle: every later call on it
- * fails with RWR_E_INVALID until it is destroyed. */
+ * fails with RWR_E_INVALID until it is destroyed.  Not in scope of THIS entry: links that join
+ * or leave a list (rwr_graph_append_links, rwr_graph_remove_links, below; both move positions
+ * handed out earlier, each by the formula in its comment). */
 int32_t rwr_graph_update_links(rwr_graph *g, int64_t count, const int64_t *link_index,
                                const uint8_t *etype /* may be NULL */, const double *w /* may be NULL */);
 /* Appends links to the resident graph: link q = (dst[q], etype[q], w[q]) goes to the END of node
@@ -210,8 +212,9 @@ int32_t rwr_graph_update_links(rwr_graph *g, int64_t count, const int64_t *link_
  * position e of row i is now at e + (number of appended links with src < i).
  * count == 0 just rebuilds, as rwr_graph_update_links does.
  * Not in scope of THIS entry: appending NODES (rwr_graph_append_nodes, below, appends nodes and
- * links in one call); not in scope at all: REMOVING links (relabel them to UNDEFINED through
- * rwr_graph_update_links, which leaves the walk bit for bit as if they were gone).
+ * links in one call) and REMOVING links (rwr_graph_remove_links, below, takes them out of their
+ * lists; relabelling them to UNDEFINED through rwr_graph_update_links leaves the walk bit for bit
+ * as if they were gone, but keeps them in the lists and in every count).
  * Errors, all found on the host before any device work; they leave the graph exactly as it was:
  * RWR_E_INVALID (g NULL, count < 0, a NULL src/dst/etype/w with count > 0, a handle invalidated
  * earlier), RWR_E_RANGE (a src[q] or dst[q] outside [0, n); the message names q),
@@ -243,7 +246,7 @@ int32_t rwr_graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, 
  * A handle in row-partitioned use (rwr_part_begin was called) loses that state: the next
  * rwr_part_* call other than rwr_part_begin fails with RWR_E_INVALID.
  * Not in scope: REMOVING or renumbering nodes, and inserting a node anywhere but at the end
- * (create a new graph).
+ * (create a new graph).  Links, of old and new nodes alike, leave through rwr_graph_remove_links.
  * Errors, all found on the host before any device work; they leave the graph exactly as it was:
  * RWR_E_INVALID (g NULL, n_new < 0, count < 0, a NULL node_id/node_type with n_new > 0, a NULL
  * src/dst/etype/w with count > 0, a handle invalidated earlier), RWR_E_RANGE (a src[q] or dst[q]
@@ -256,6 +259,36 @@ int32_t rwr_graph_append_nodes(rwr_graph *g, int32_t n_new, const int64_t *node_
                                const uint8_t *node_type, int64_t count, const int32_t *src,
                                const int32_t *dst, const uint8_t *etype, const double *w,
                                int64_t *new_index_out /* count, may be NULL */);
+/* Removes links from the resident graph: the links at the positions link_index[q] of the current
+ * flattened raw list -- the currency of rwr_graph_update_links and of new_index_out -- leave their
+ * lists, which is what edges[src].RemoveAt(k) does to the reference's List<ForwardLink>.  The
+ * positions may come in any order; all must be distinct and lie in [0, nnz_raw).  Every surviving
+ * link keeps its order within its list.  The library compacts its resident raw lists on the device
+ * (only the positions cross the boundary) and re-runs Graph.buildGraph and the transpose there: the
+ * resulting state -- normalised weights, dangling flags, in-neighbour lists, processing orders,
+ * rwr_graph_size, the n / nnz_raw / nnz / uniform / uniform_path statistics -- is bit for bit what
+ * rwr_graph_create would build from the shortened lists, and every later call behaves accordingly:
+ * a removed LIKE link of a seed makes its target a candidate again (Recommender.cs:20-24), a
+ * removed FOLLOW target reappears in the typed "who to follow" list, and a node that loses its
+ * last explicit link becomes dangling.  Removing every link is legal and equals a create from
+ * empty lists.  The memory of the removed links is given back (13 bytes each, plus 8 of the
+ * normalised weight), and they no longer count against the limit of 2^32-2 links.
+ * Positions handed out earlier move: the surviving link at old position e is now at
+ * e - (number of removed positions < e).
+ * count == 0 just rebuilds, as rwr_graph_update_links does.
+ * A graph built in one launch (at most 8 192 nodes and 65 536 links) that grew past that size
+ * does not return to the one-launch build when it shrinks again; its state is the same bits.
+ * Errors, all found on the host before any device work; they leave the graph exactly as it was,
+ * in this order: RWR_E_INVALID (g NULL; count < 0 or a NULL link_index with count > 0; a handle
+ * invalidated earlier), RWR_E_RANGE (a position outside [0, nnz_raw); the message names the first
+ * such q), RWR_E_INVALID (a position given twice; the message names the second occurrence's q).
+ * Failures come in two phases.  BEFORE THE SWAP: the shortened lists are written into new buffers,
+ * which the handle takes only when all of them exist; running out of device memory up to there
+ * returns RWR_E_NOMEM and leaves the graph untouched and usable.  AFTER THE SWAP: a failure inside
+ * the rebuild (out of device memory, a HIP error) invalidates the handle exactly as a failed
+ * rwr_graph_update_links does: every later call on it fails with RWR_E_INVALID until it is
+ * destroyed.  Not to be called concurrently with other calls on the same handle. */
+int32_t rwr_graph_remove_links(rwr_graph *g, int64_t count, const int64_t *link_index);
 /* Graph.size() (Graph.cs:91-93) plus link counts; any out pointer may be NULL */
 int32_t rwr_graph_size(const rwr_graph *g, int32_t *n, int64_t *nnz_raw, int64_t *nnz_explicit);
 /* Backs the public field Graph.graph (Graph.cs:43): w_out[e] = normalised weight of raw

@@ -30,7 +30,7 @@ template <class F>
 static int32_t bound(const char *who, rwr_graph *g, F &&body)
 {
     if (g->poisoned) {
-        set_error("this graph handle was invalidated by a failed rebuild (rwr_graph_update_links / rwr_graph_append_links / rwr_graph_append_nodes); destroy it");
+        set_error("this graph handle was invalidated by a failed rebuild (rwr_graph_update_links / rwr_graph_append_links / rwr_graph_append_nodes / rwr_graph_remove_links); destroy it");
         return RWR_E_INVALID;
     }
     DeviceGuard dev_guard(g->device);
@@ -268,6 +268,20 @@ int32_t rwr_graph_append_nodes(rwr_graph *g, int32_t n_new, const int64_t *node_
     const int32_t rc = bound("rwr_graph_append_nodes", g, [&] {
         return graph_append(g, "rwr_graph_append_nodes", n_new, node_id, node_type, count, src, dst, etype, w, new_index_out, &swapped);
     });
+    if (rc != RWR_OK && swapped) g->poisoned = 1;   // (the two phases of rwr_graph_append_links)
+    return rc;
+}
+
+int32_t rwr_graph_remove_links(rwr_graph *g, int64_t count, const int64_t *link_index)
+{
+    g_err[0] = 0;
+    if (!g) { set_error("rwr_graph_remove_links: graph is NULL"); return RWR_E_INVALID; }
+    if (count < 0 || (count > 0 && !link_index)) {
+        set_error("rwr_graph_remove_links: count must be >= 0 and link_index non-NULL when count > 0");
+        return RWR_E_INVALID;
+    }
+    bool swapped = false;
+    const int32_t rc = bound("rwr_graph_remove_links", g, [&] { return graph_remove(g, count, link_index, &swapped); });
     if (rc != RWR_OK && swapped) g->poisoned = 1;   // (the two phases of rwr_graph_append_links)
     return rc;
 }

@@ -6,6 +6,7 @@
 #include "engine.h"
 #include "append_plan.h"
 #include "node_append_plan.h"
+#include "seg_copy.h"
 
 #include <chrono>
 #include <cstdio>
@@ -14,19 +15,11 @@
 
 namespace rwr {
 
-template <typename T>
-static void swap_blocks(DevBuf<T> &a, DevBuf<T> &b)
-{
-    T *tp = a.p; a.p = b.p; b.p = tp;
-    size_t tc = a.count; a.count = b.count; b.count = tc;
-    size_t tr = a.reserved; a.reserved = b.reserved; b.reserved = tr;
-}
-
 // ---- rwr_graph_append_links: the resident raw lists merged with a few new links, on the device.
 // The host plan (append_plan.h) leaves one table entry per DISTINCT appended source s_j: brk[j] = rowptr_old[s_j + 1] and
 // cum[j] = links appended to s_0 .. s_j.  The old flat position e moves to e + cum[upper_bound(brk, e) - 1]: between two
 // breakpoints the move is constant, so the copy is a sequence of plain shifted block copies.
-constexpr int AP_THREADS = 256;
+constexpr int AP_THREADS = SEG_THREADS;   // (seg_copy.h: the lanes of a segment's block copies)
 constexpr int AP_CHUNK = 8192;     // old positions per workgroup
 // More breakpoints than this in a chunk: the dense path of k_append_merge (per-element shifts).  The value is reasoned, not
 // tuned: a segment is walked by all 256 lanes, so segments under 256 elements leave lanes idle in every one of the three block
@@ -58,41 +51,6 @@ __global__ __launch_bounds__(256) void k_append_rowptr(int32_t n, int32_t n_old,
         else hi = mid;
     }
     rp_new[i] = rp_old[i < n_old ? i : (int64_t)n_old] + (lo > 0 ? cum[lo - 1] : 0);
-}
-
-// one segment [a, b) of old positions, all moving by sh: three coalesced block copies by the whole workgroup
-template <typename T>
-__device__ __forceinline__ void append_copy_seg(const T *__restrict__ src, T *__restrict__ out, int64_t a, int64_t b, int64_t sh,
-                                                int tid)
-{
-    int64_t e = a + tid;
-    for (; e + 3 * AP_THREADS < b; e += 4 * AP_THREADS) {      // four loads in flight per lane
-        const T v0 = src[e], v1 = src[e + AP_THREADS], v2 = src[e + 2 * AP_THREADS], v3 = src[e + 3 * AP_THREADS];
-        out[e + sh] = v0;
-        out[e + sh + AP_THREADS] = v1;
-        out[e + sh + 2 * AP_THREADS] = v2;
-        out[e + sh + 3 * AP_THREADS] = v3;
-    }
-    for (; e < b; e += AP_THREADS) out[e + sh] = src[e];
-}
-// ... of the byte array: four elements per lane, stored as one aligned dword (the source is as aligned as the shift leaves it:
-// it is read byte by byte, from lines the neighbouring lanes read as well)
-__device__ __forceinline__ void append_copy_seg_bytes(const uint8_t *__restrict__ src, uint8_t *__restrict__ out, int64_t a,
-                                                      int64_t b, int64_t sh, int tid)
-{
-    const int64_t len = b - a;
-    int64_t head = (int64_t)((4 - (reinterpret_cast<uintptr_t>(out + a + sh) & 3)) & 3);
-    if (head > len) head = len;
-    if (tid < head) out[a + sh + tid] = src[a + tid];
-    const int64_t nd = (len - head) >> 2;                      // whole dwords
-    const uint8_t *s4 = src + a + head;
-    uint32_t *o4 = reinterpret_cast<uint32_t *>(out + a + sh + head);
-    for (int64_t d = tid; d < nd; d += AP_THREADS) {
-        const uint8_t *q = s4 + 4 * d;
-        o4[d] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-    }
-    const int64_t t0 = head + 4 * nd;                          // up to three bytes left
-    if (tid < len - t0) out[a + sh + t0 + tid] = src[a + t0 + tid];
 }
 
 // A workgroup takes AP_CHUNK consecutive old positions and finds the breakpoints inside its chunk ONCE, brk[j .. jend) (every
@@ -150,9 +108,9 @@ __global__ __launch_bounds__(AP_THREADS) void k_append_merge(int64_t m_old, int3
     while (a < c1) {
         const int64_t sh = j > 0 ? cum[j - 1] : 0;             // (brk[j] > a here)
         const int64_t b = (j < nb && brk[j] < c1) ? brk[j] : c1;
-        append_copy_seg<double>(w_o, w_n, a, b, sh, tid);
-        append_copy_seg<int32_t>(dst_o, dst_n, a, b, sh, tid);
-        append_copy_seg_bytes(et_o, et_n, a, b, sh, tid);
+        copy_seg<double>(w_o, w_n, a, b, sh, tid);
+        copy_seg<int32_t>(dst_o, dst_n, a, b, sh, tid);
+        copy_seg_bytes(et_o, et_n, a, b, sh, tid);
         a = b;
         while (j < nb && brk[j] <= a) ++j;                      // (coinciding breakpoints: rows without links in between)
     }

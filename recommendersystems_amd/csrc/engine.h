@@ -197,6 +197,16 @@ int32_t idle_on_error(hipStream_t s, F &&body)
     return rc;
 }
 
+// two buffers change places: how an edit of the resident lists hands its NEW buffers to the handle (append.hip, remove.hip);
+// the old ones go back to the block cache when the edit's locals go out of scope
+template <typename T>
+void swap_blocks(DevBuf<T> &a, DevBuf<T> &b)
+{
+    T *tp = a.p; a.p = b.p; b.p = tp;
+    size_t tc = a.count; a.count = b.count; b.count = tc;
+    size_t tr = a.reserved; a.reserved = b.reserved; b.reserved = tr;
+}
+
 // no C++ exception crosses the C boundary
 template <class F>
 int32_t no_throw(const char *who, F &&body)
@@ -225,6 +235,9 @@ int32_t graph_update_links(rwr_graph *g, int64_t count, const int64_t *idx, cons
 int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t *node_id, const uint8_t *node_type,
                      int64_t count, const int32_t *src, const int32_t *dst, const uint8_t *etype, const double *w,
                      int64_t *new_index_out, bool *swapped);
+// rwr_graph_remove_links (remove.hip): compacts the resident raw lists without the links at the given positions
+// (new buffers, swapped in when all of them exist: *swapped) and re-derives; the plan is remove_plan.h's.
+int32_t graph_remove(rwr_graph *g, int64_t count, const int64_t *link_index, bool *swapped);
 // value-free graphs: materialise in_w (= w_src[in_src]) for an entry point that runs the weighted kernels
 int32_t ensure_in_w(rwr_graph *g);
 // sort.hip: m sorted payload words as the int32 row list their readers take (no launch for m <= 0)

@@ -189,6 +189,49 @@ def _merged_flat(flat, src, dst, etype, w, pos):
     return (node_id, node_type, new_rowptr, out[0], out[1], out[2])
 
 
+def _shrunk_lists(old_flat, new_flat):
+    """The positions (in ``old_flat``'s flattened raw list, ascending) of the links by which the lists of ``old_flat`` exceed
+    those of ``new_flat``: the node arrays are equal, no list is longer, every list of unchanged length is bitwise equal, and
+    every shorter list is a subsequence of its old self by (target, type, weight bits).  ``None`` otherwise.  Where several
+    old links could be the ones that left (copies of one link in one list), the earliest match is kept: any choice leaves
+    the same lists.  No change gives an empty array."""
+    o_id, o_type, o_rp, o_dst, o_et, o_w = old_flat
+    n_id, n_type, n_rp, n_dst, n_et, n_w = new_flat
+    if o_id.shape != n_id.shape or not ((o_id == n_id).all() and (o_type == n_type).all()):
+        return None
+    o_len, n_len = np.diff(o_rp), np.diff(n_rp)
+    if (n_len > o_len).any():
+        return None
+    o_wb, n_wb = o_w.view(np.uint64), n_w.view(np.uint64)
+    same = n_len == o_len
+    o_same, n_same = np.repeat(same, o_len), np.repeat(same, n_len)
+    if not ((o_dst[o_same] == n_dst[n_same]).all() and (o_et[o_same] == n_et[n_same]).all()
+            and (o_wb[o_same] == n_wb[n_same]).all()):
+        return None
+    gone = []
+    for i in np.flatnonzero(~same):                      # the shorter lists, link by link
+        k, a1 = int(o_rp[i]), int(o_rp[i + 1])
+        for j in range(int(n_rp[i]), int(n_rp[i + 1])):
+            while k < a1 and not (o_dst[k] == n_dst[j] and o_et[k] == n_et[j] and o_wb[k] == n_wb[j]):
+                gone.append(k)
+                k += 1
+            if k == a1:
+                return None
+            k += 1
+        gone.extend(range(k, a1))
+    return np.array(gone, dtype=np.int64)
+
+
+def _removed_flat(flat, pos):
+    """``flat`` (as ``Graph._flatten`` returns it) without the links at the flattened positions ``pos`` (distinct, any
+    order), as rwr_graph_remove_links leaves the lists: new arrays, the other links in their order."""
+    node_id, node_type, rowptr, o_dst, o_et, o_w = flat
+    keep = np.ones(int(rowptr[-1]), dtype=bool)
+    keep[pos] = False
+    new_rowptr = rowptr - np.searchsorted(np.sort(pos), rowptr, side="left")
+    return (node_id, node_type, new_rowptr.astype(np.int64), o_dst[keep], o_et[keep], o_w[keep])
+
+
 class Graph:
     """class Graph (Graph.cs:37-94).  ``nodes``/``edges`` are the caller's dictionaries
     (kept by reference, Graph.cs:46-47); ``buildGraph()`` hands the RAW links to
@@ -197,6 +240,7 @@ class Graph:
     incremental_rebuilds = 0     # buildGraph() calls (all instances) that went through rwr_graph_update_links
     append_rebuilds = 0          # ... and those that went through rwr_graph_append_links (lists that only grew)
     node_append_rebuilds = 0     # ... and through rwr_graph_append_nodes (nodes added at the end, lists that only grew)
+    remove_rebuilds = 0          # ... and through rwr_graph_remove_links (lists that only shrank)
 
     def __init__(self, nodes: Dict[int, Node], edges: Dict[int, List[ForwardLink]], *, mode: Optional[str] = None,
                  device: int = -1, tile_seeds: int = 0, tile_group: int = 0, profile: bool = False,
@@ -256,8 +300,10 @@ class Graph:
         type or weight differ are sent (rwr_graph_update_links); when the lists only grew at their ends, only the new links
         (rwr_graph_append_links); when, besides, the node dictionary gained keys at its end -- the old nodes unchanged and in
         the same order, the new keys continuing the index sequence -- only the new nodes and links (rwr_graph_append_nodes);
-        lists that grew AND whose old links changed, a changed old node or a reordered dictionary are sent whole.  The device
-        state is the same either way."""
+        when lists only lost links (``del edges[u][k]``: every shorter list a subsequence of its old self, the others
+        unchanged) only the positions of the links that left (rwr_graph_remove_links);
+        lists that grew AND whose old links changed, lists that shrank AND grew or changed, a changed old node or a reordered
+        dictionary are sent whole.  The device state is the same either way."""
         lib = _lib.load()
         flat = self._flat if self._flat is not None else self._flatten()
         node_id, node_type, rowptr, dst, etype, w = flat
@@ -280,6 +326,15 @@ class Graph:
                 self._sent = flat
                 self._graph_cache = None
                 Graph.append_rebuilds += 1
+                return
+            gone = _shrunk_lists(self._sent, flat)
+            if gone is not None:
+                # (the library directly, as above: flat IS _sent without those links)
+                _lib.check(lib.rwr_graph_remove_links(self._handle(), int(gone.shape[0]), _p(gone, C.c_int64)))
+                self._rowptr = rowptr
+                self._sent = flat
+                self._graph_cache = None
+                Graph.remove_rebuilds += 1
                 return
             more = _grown_nodes(self._sent, flat) if self._sent_in_order and self._keys_in_order() else None
             if more is not None:
@@ -354,6 +409,28 @@ class Graph:
             self._rowptr = rowptr
         self._graph_cache = None
         return pos
+
+    def removeLinks(self, link_index) -> None:
+        """rwr_graph_remove_links: the raw links at the given flattened positions (distinct, any order) leave their lists
+        (edges[src].RemoveAt(k)), then the device-side rebuild.  Positions move: the surviving link at old position e is
+        now at e - (removed positions < e).
+
+        The object's record of what the device holds follows, as for appendLinks.  A dictionary graph: the caller deletes
+        the same links from ``edges`` and the next buildGraph() finds nothing more to send.  A flat graph: the object
+        continues with shortened COPIES of the arrays; the caller's arrays are not touched."""
+        idx = np.ascontiguousarray(link_index, dtype=np.int64)
+        if idx.ndim != 1:
+            raise ValueError("link_index must be one-dimensional")
+        _lib.check(_lib.load().rwr_graph_remove_links(self._handle(), int(idx.shape[0]), _p(idx, C.c_int64)))
+        if self._flat is not None:
+            self._flat = _removed_flat(self._flat, idx)
+            self._desc = None
+            self._rowptr = self._flat[2]
+        else:
+            if self._sent is not None:
+                self._sent = _removed_flat(self._sent, idx)
+            self._rowptr = self._rowptr - np.searchsorted(np.sort(idx), self._rowptr, side="left")
+        self._graph_cache = None
 
     def appendNodes(self, nodes, src=(), dst=(), etype=(), w=()) -> Tuple[int, np.ndarray]:
         """rwr_graph_append_nodes: node j of ``nodes`` (``Node`` objects or ``(id, type)`` pairs) gets index n + j and an empty
