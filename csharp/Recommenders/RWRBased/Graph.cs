@@ -168,6 +168,37 @@ namespace Recommenders.RWRBased {
             return pos;
         }
 
+        // rwr_graph_remove_nodes on a built graph: the nodes at the given indices (distinct, any order) leave the graph ON THE
+        // DEVICE with every raw link from or to them (nodes.Remove(i); edges.Remove(i), and the links to i out of the other
+        // lists); the others close up and keep their order.  newNodeIndex[i] is the new index of old node i and
+        // newLinkIndex[e] the new position of the link at old flattened position e, -1 for what left.  The dictionaries are
+        // not touched: take the same nodes and links out of `nodes` / `edges` and re-key both by newNodeIndex BEFORE any other
+        // call on this object (it reads nodes.Count), and the next buildGraph() finds nothing more to send.  (Removing nodes
+        // from the dictionaries WITHOUT this call makes buildGraph() send the graph whole in this binding: only the Python
+        // mirror finds lost nodes by a diff.)
+        public void RemoveNodes(int[] nodeIndex, out int[] newNodeIndex, out long[] newLinkIndex) {
+            int nOld = sentId.Length;
+            long m = rowptr[nOld];
+            newNodeIndex = new int[nOld]; newLinkIndex = new long[m];
+            long removed;
+            Native.Check(Native.rwr_graph_remove_nodes(handle, nodeIndex.Length, nodeIndex, newNodeIndex, newLinkIndex, out removed));
+            // the flat copies behind LoadNormalizedGraph() and the next buildGraph()'s diff follow
+            int n = nOld - nodeIndex.Length;
+            var id2 = new long[n]; var ty2 = new byte[n]; var rp = new long[n + 1];
+            var nd = new int[m - removed]; var nt = new byte[m - removed]; var nw = new double[m - removed];
+            for (int i = 0; i < nOld; i++) {
+                int to = newNodeIndex[i];
+                if (to < 0) continue;
+                id2[to] = sentId[i]; ty2[to] = sentType[i];
+                long f = rp[to];
+                for (long p = rowptr[i]; p < rowptr[i + 1]; p++)
+                    if (newLinkIndex[p] >= 0) { nd[f] = newNodeIndex[dst[p]]; nt[f] = etype[p]; nw[f] = sentW[p]; f++; }
+                rp[to + 1] = f;
+            }
+            rowptr = rp; dst = nd; etype = nt; sentW = nw; sentId = id2; sentType = ty2;
+            graph = null;
+        }
+
         // the flat arrays buildGraph() hands to librwr, without building: Recommender.EvaluateGraphs sends many graphs at once
         internal void Flatten(out long[] id, out byte[] type, out long[] rp, out int[] d, out byte[] et, out double[] w) {
             int n = nodes.Count;

@@ -39,6 +39,7 @@ namespace Recommenders.RWRBased {
         [DllImport(Lib)] public static extern int rwr_graph_append_nodes(GraphHandle g, int n_new, long[] node_id, byte[] node_type,
             long count, int[] src, int[] dst, byte[] etype, double[] w, long[] new_index_out);
         [DllImport(Lib)] public static extern int rwr_graph_remove_links(GraphHandle g, long count, long[] link_index);
+        [DllImport(Lib)] public static extern int rwr_graph_remove_nodes(GraphHandle g, int count, int[] node_index, int[] new_node_index_out, long[] new_link_index_out, out long links_removed_out);
         [DllImport(Lib)] public static extern int rwr_graph_destroy(IntPtr g);
         [DllImport(Lib)] public static extern int rwr_graph_get_normalized(GraphHandle g, double[] w_out, byte[] dangling_out);
         [DllImport(Lib)] public static extern int rwr_get_stats(GraphHandle g, ref RwrStats stats_out);

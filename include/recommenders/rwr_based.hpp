@@ -169,6 +169,41 @@ public:
         sent_dst_ = nd; sent_etype_ = nt; sent_w_ = nw;
     }
 
+    // rwr_graph_remove_nodes on a built graph: the nodes at the given indices (distinct, any order) leave the graph on the
+    // device with every raw link from or to them; the others close up and keep their order.  Returns (newNodeIndex,
+    // newLinkIndex): the new index of every old node and the new flattened position of every old link, -1 for what left.
+    // The caller's `nodes` / `edges` are not touched: take the same nodes and links out and re-key both by newNodeIndex BEFORE
+    // any other call on this object (it reads nodes.size()); the next buildGraph() then finds nothing more to send.
+    // (Removing nodes from the maps WITHOUT this call makes buildGraph() send the graph whole in this binding.)
+    std::pair<std::vector<int32_t>, std::vector<int64_t>> removeNodes(const std::vector<int32_t> &nodeIndex)
+    {
+        const size_t n_old = sent_id_.size();
+        const size_t m = (size_t)rowptr_[n_old];
+        std::vector<int32_t> nn(n_old ? n_old : 1);
+        std::vector<int64_t> nl(m ? m : 1);
+        int64_t removed = 0;
+        check(rwr_graph_remove_nodes(handle(), (int32_t)nodeIndex.size(), nodeIndex.data(), nn.data(), nl.data(), &removed));
+        nn.resize(n_old);
+        nl.resize(m);
+        // the flat copies behind graph() and the next buildGraph()'s diff follow
+        const size_t n = n_old - nodeIndex.size();
+        std::vector<int64_t> id2(n), rp(n + 1, 0);
+        std::vector<uint8_t> ty2(n), nt;
+        std::vector<int32_t> nd;
+        std::vector<double> nw;
+        for (size_t i = 0; i < n_old; ++i) {
+            if (nn[i] < 0) continue;
+            const size_t to = (size_t)nn[i];
+            id2[to] = sent_id_[i]; ty2[to] = sent_type_[i];
+            for (int64_t p = rowptr_[i]; p < rowptr_[i + 1]; ++p)
+                if (nl[(size_t)p] >= 0) { nd.push_back(nn[(size_t)sent_dst_[p]]); nt.push_back(sent_etype_[p]); nw.push_back(sent_w_[p]); }
+            rp[to + 1] = (int64_t)nd.size();
+        }
+        rowptr_ = rp; dst_ = nd; etype_ = nt;
+        sent_id_ = id2; sent_type_ = ty2; sent_dst_ = nd; sent_etype_ = nt; sent_w_ = nw;
+        return {nn, nl};
+    }
+
     // the public field Graph.graph (Graph.cs:43): normalised explicit links per node; empty optional == null
     std::map<int, std::unique_ptr<std::vector<ForwardLink>>> graph()
     {

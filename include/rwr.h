@@ -245,8 +245,9 @@ int32_t rwr_graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, 
  * n_new > 0 with count == 0 is legal.  new_index_out as in rwr_graph_append_links.
  * A handle in row-partitioned use (rwr_part_begin was called) loses that state: the next
  * rwr_part_* call other than rwr_part_begin fails with RWR_E_INVALID.
- * Not in scope: REMOVING or renumbering nodes, and inserting a node anywhere but at the end
- * (create a new graph).  Links, of old and new nodes alike, leave through rwr_graph_remove_links.
+ * Not in scope of THIS entry: REMOVING or renumbering nodes (rwr_graph_remove_nodes, below, takes
+ * nodes out with their links and renumbers the others) and inserting a node anywhere but at the
+ * end (create a new graph).  Links, of old and new nodes alike, leave through rwr_graph_remove_links.
  * Errors, all found on the host before any device work; they leave the graph exactly as it was:
  * RWR_E_INVALID (g NULL, n_new < 0, count < 0, a NULL node_id/node_type with n_new > 0, a NULL
  * src/dst/etype/w with count > 0, a handle invalidated earlier), RWR_E_RANGE (a src[q] or dst[q]
@@ -289,6 +290,50 @@ int32_t rwr_graph_append_nodes(rwr_graph *g, int32_t n_new, const int64_t *node_
  * rwr_graph_update_links does: every later call on it fails with RWR_E_INVALID until it is
  * destroyed.  Not to be called concurrently with other calls on the same handle. */
 int32_t rwr_graph_remove_links(rwr_graph *g, int64_t count, const int64_t *link_index);
+/* Removes nodes from the resident graph: the nodes node_index[q] -- current node indices, in any
+ * order, all distinct and inside [0, n) -- leave it, which is what nodes.Remove(i); edges.Remove(i)
+ * plus a renumbering does to the reference's dictionaries.  Every raw link whose source OR target
+ * is a removed node leaves with them; every other link keeps its order within its list.  The
+ * surviving nodes close up and keep their order: old node i becomes
+ * i - (number of removed nodes < i), and every surviving target is rewritten to the new index.
+ * Only the node list crosses the boundary: the links that point TO a removed node are found on the
+ * device, in the resident lists, which are compacted there together with the node arrays and both
+ * ITEM orders.  Then Graph.buildGraph and the transpose are re-run there: the resulting state --
+ * normalised weights, dangling flags, in-neighbour lists, processing orders, both ITEM orders
+ * (equal ids rank in index order, as rwr_graph_create ranks them), rwr_graph_size,
+ * rwr_graph_get_normalized, the n / nnz_raw / nnz / uniform / uniform_path statistics -- is bit for
+ * bit what rwr_graph_create would build from the shortened and renumbered arrays, and every later
+ * Model, Recommendation, typed, filtered, capped or explained call behaves accordingly: a removed
+ * ITEM is in no list, a personalised Model starts at rank[seed] = n - count (Model.cs:44), and a
+ * node whose every out-link pointed to removed nodes becomes dangling.
+ * Outputs, each may be NULL, written only when the call succeeds (a refused call writes nothing):
+ * new_node_index_out[i], i over the n nodes before the call, is the new index of old node i or -1
+ * if it was removed; new_link_index_out[e], e over the nnz_raw positions before the call, is the
+ * new position of that link in the flattened raw list -- the currency of rwr_graph_update_links
+ * and rwr_graph_remove_links -- or -1; *links_removed_out is the number of links that left.
+ * new_link_index_out is the one thing that makes a per-link array cross the boundary.
+ * count == 0 just rebuilds, as rwr_graph_update_links does: both index outputs are the identity
+ * and *links_removed_out is 0.
+ * A handle in row-partitioned use (rwr_part_begin was called) loses that state, as in
+ * rwr_graph_append_nodes.  The candidate lists of the typed entries are rebuilt by the next call
+ * that needs them.  A graph built in one launch that grew past that size does not return to the
+ * one-launch build when it shrinks again; its state is the same bits.
+ * Errors, all found on the host before any device work; they leave the graph exactly as it was,
+ * in this order: RWR_E_INVALID (g NULL; count < 0 or a NULL node_index with count > 0; a handle
+ * invalidated earlier), RWR_E_RANGE (an index outside [0, n); the message names the first such q),
+ * RWR_E_INVALID (an index given twice; the message names the second occurrence's q),
+ * RWR_E_UNSUPPORTED (count == n: rwr_graph_create refuses n <= 0, so a graph cannot lose its last
+ * node; destroy the graph instead).
+ * Failures come in two phases.  BEFORE THE SWAP: everything is written into new buffers, which the
+ * handle takes only when all of them exist and are filled; running out of device memory up to
+ * there returns RWR_E_NOMEM and leaves the graph untouched and usable.  AFTER THE SWAP: a failure
+ * inside the rebuild (out of device memory, a HIP error) invalidates the handle exactly as a failed
+ * rwr_graph_update_links does: every later call on it fails with RWR_E_INVALID until it is
+ * destroyed.  Not to be called concurrently with other calls on the same handle. */
+int32_t rwr_graph_remove_nodes(rwr_graph *g, int32_t count, const int32_t *node_index,
+                               int32_t *new_node_index_out /* n before the call, may be NULL */,
+                               int64_t *new_link_index_out /* nnz_raw before the call, may be NULL */,
+                               int64_t *links_removed_out /* may be NULL */);
 /* Graph.size() (Graph.cs:91-93) plus link counts; any out pointer may be NULL */
 int32_t rwr_graph_size(const rwr_graph *g, int32_t *n, int64_t *nnz_raw, int64_t *nnz_explicit);
 /* Backs the public field Graph.graph (Graph.cs:43): w_out[e] = normalised weight of raw
@@ -384,7 +429,8 @@ int32_t rwr_recommend_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float
  *     seeds / ids / scores / counts, top_n < 1, cand_type outside [0, 255] or a mask bit >= 8 give RWR_E_INVALID; a seed
  *     outside [0, n) gives RWR_E_RANGE with its batch position in the message.  A refused call writes nothing.
  *   - The candidate list of a node type is built on the device by the first call that names it and kept with the handle
- *     (four types at most; rwr_graph_append_nodes makes the next call rebuild it).
+ *     (four types at most; rwr_graph_append_nodes and rwr_graph_remove_nodes make the next call
+ *     rebuild it).
  *   - opts.tile_seeds, tile_group and workspace_bytes keep their meaning (the seeds run as tiles of the batched SpMM). */
 int32_t rwr_recommend_typed_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
                                   int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,

@@ -20,7 +20,7 @@ RWR_WHY_MAX = 8                # include/rwr.h: reasons per entry of the explain
 # every symbol include/rwr.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "rwr_version", "rwr_device_count", "rwr_last_error",
-    "rwr_graph_create", "rwr_graph_update_links", "rwr_graph_append_links", "rwr_graph_append_nodes", "rwr_graph_remove_links", "rwr_graph_destroy", "rwr_graph_size", "rwr_graph_get_normalized",
+    "rwr_graph_create", "rwr_graph_update_links", "rwr_graph_append_links", "rwr_graph_append_nodes", "rwr_graph_remove_links", "rwr_graph_remove_nodes", "rwr_graph_destroy", "rwr_graph_size", "rwr_graph_get_normalized",
     "rwr_recommend", "rwr_recommend_eval", "rwr_recommend_eval_batch", "rwr_eval_graphs", "rwr_recommend_batch", "rwr_model_run", "rwr_model_deliver",
     "rwr_model_run_restart", "rwr_model_deliver_restart", "rwr_model_run_batch", "rwr_model_run_restart_batch",
     "rwr_recommend_restart_batch", "rwr_recommend_restart_eval_batch", "rwr_recommend_typed_batch",
@@ -96,6 +96,8 @@ def load():
                                            p(C.c_uint8), p(C.c_double), p(C.c_int64)]
     lib.rwr_graph_remove_links.restype = C.c_int32
     lib.rwr_graph_remove_links.argtypes = [C.c_void_p, C.c_int64, p(C.c_int64)]
+    lib.rwr_graph_remove_nodes.restype = C.c_int32
+    lib.rwr_graph_remove_nodes.argtypes = [C.c_void_p, C.c_int32, p(C.c_int32), p(C.c_int32), p(C.c_int64), p(C.c_int64)]
     lib.rwr_graph_destroy.restype = C.c_int32
     lib.rwr_graph_destroy.argtypes = [C.c_void_p]
     lib.rwr_graph_size.restype = C.c_int32

@@ -30,7 +30,7 @@ template <class F>
 static int32_t bound(const char *who, rwr_graph *g, F &&body)
 {
     if (g->poisoned) {
-        set_error("this graph handle was invalidated by a failed rebuild (rwr_graph_update_links / rwr_graph_append_links / rwr_graph_append_nodes / rwr_graph_remove_links); destroy it");
+        set_error("this graph handle was invalidated by a failed rebuild (rwr_graph_update_links / rwr_graph_append_links / rwr_graph_append_nodes / rwr_graph_remove_links / rwr_graph_remove_nodes); destroy it");
         return RWR_E_INVALID;
     }
     DeviceGuard dev_guard(g->device);
@@ -282,6 +282,23 @@ int32_t rwr_graph_remove_links(rwr_graph *g, int64_t count, const int64_t *link_
     }
     bool swapped = false;
     const int32_t rc = bound("rwr_graph_remove_links", g, [&] { return graph_remove(g, count, link_index, &swapped); });
+    if (rc != RWR_OK && swapped) g->poisoned = 1;   // (the two phases of rwr_graph_append_links)
+    return rc;
+}
+
+int32_t rwr_graph_remove_nodes(rwr_graph *g, int32_t count, const int32_t *node_index, int32_t *new_node_index_out,
+                               int64_t *new_link_index_out, int64_t *links_removed_out)
+{
+    g_err[0] = 0;
+    if (!g) { set_error("rwr_graph_remove_nodes: graph is NULL"); return RWR_E_INVALID; }
+    if (count < 0 || (count > 0 && !node_index)) {
+        set_error("rwr_graph_remove_nodes: count must be >= 0 and node_index non-NULL when count > 0");
+        return RWR_E_INVALID;
+    }
+    bool swapped = false;
+    const int32_t rc = bound("rwr_graph_remove_nodes", g, [&] {
+        return graph_remove_nodes(g, count, node_index, new_node_index_out, new_link_index_out, links_removed_out, &swapped);
+    });
     if (rc != RWR_OK && swapped) g->poisoned = 1;   // (the two phases of rwr_graph_append_links)
     return rc;
 }

@@ -10,9 +10,11 @@
 // rows before it only -- no atomic decides a position -- so the list is the same on every run.  The host model of the
 // offset table and of the list is filter_plan.h's (filter_block_offsets, filter_list): a call's pool only narrows the match.
 //
-// Node types of resident nodes never change and nodes are only ever appended behind the last one (rwr_graph_append_nodes),
-// so the list built while the graph had n nodes is valid exactly as long as the graph still has n nodes: that comparison is
-// the cache's whole validity test, and no (re)build has to reset anything.
+// Node types of resident nodes never change, and between two removals nodes are only ever appended behind the last one
+// (rwr_graph_append_nodes), so the list built while the graph had n nodes is valid exactly as long as the graph still has n
+// nodes: that comparison is the cache's whole validity test, and no (re)build has to reset anything.  The one edit that breaks
+// the premise, rwr_graph_remove_nodes (after it a later append can bring n back to a cached value over other rows), empties
+// every entry itself (node_remove.hip); cand_cache_choose never sees a list of another node set.
 #pragma once
 
 #include <cstddef>

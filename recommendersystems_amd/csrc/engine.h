@@ -83,7 +83,8 @@ struct rwr_graph {
     int32_t tail_state = 0;
     // candidate rows by node type (rwr_recommend_typed_batch): cand_rows[e] = the rows with node_type ==
     // cand_entry[e].type by row index ascending, compacted on the device on first use (typed.hip).  An entry is valid while
-    // cand_entry[e].n == n (cand_plan.h: node types never change, nodes are only appended), so no (re)build resets it
+    // cand_entry[e].n == n (cand_plan.h: node types never change, and between two removals nodes are only appended), so no
+    // (re)build resets it; rwr_graph_remove_nodes, after which the same n can stand for other rows, empties every entry
     rwr::DevBuf<int32_t> cand_rows[rwr::CAND_CACHE];
     rwr::CandEntry cand_entry[rwr::CAND_CACHE];
     uint64_t cand_calls = 0;          // typed calls so far: the entries' use stamps
@@ -238,6 +239,11 @@ int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t
 // rwr_graph_remove_links (remove.hip): compacts the resident raw lists without the links at the given positions
 // (new buffers, swapped in when all of them exist: *swapped) and re-derives; the plan is remove_plan.h's.
 int32_t graph_remove(rwr_graph *g, int64_t count, const int64_t *link_index, bool *swapped);
+// rwr_graph_remove_nodes (node_remove.hip): compacts the resident raw lists without the links from or to the given
+// nodes, renumbers the targets, compacts the node arrays and the ITEM orders (new buffers, swapped in when all of them exist:
+// *swapped) and re-derives; the plan is node_remove_plan.h's.  The three outputs (each may be NULL) are written on success only.
+int32_t graph_remove_nodes(rwr_graph *g, int32_t count, const int32_t *node_index, int32_t *new_node_index_out,
+                           int64_t *new_link_index_out, int64_t *links_removed_out, bool *swapped);
 // value-free graphs: materialise in_w (= w_src[in_src]) for an entry point that runs the weighted kernels
 int32_t ensure_in_w(rwr_graph *g);
 // sort.hip: m sorted payload words as the int32 row list their readers take (no launch for m <= 0)

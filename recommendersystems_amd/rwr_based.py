@@ -232,6 +232,56 @@ def _removed_flat(flat, pos):
     return (node_id, node_type, new_rowptr.astype(np.int64), o_dst[keep], o_et[keep], o_w[keep])
 
 
+def _removed_nodes_flat(flat, lost):
+    """``flat`` (as ``Graph._flatten`` returns it) without the nodes ``lost`` (distinct indices, any order), as
+    rwr_graph_remove_nodes leaves the graph: every link from or to a lost node gone, the other nodes closed up in their order
+    and every remaining target renumbered.  Returns ``(new_flat, new_node_index, new_link_index)``, the two index arrays
+    over the old nodes and the old flattened positions with -1 for what left."""
+    node_id, node_type, rowptr, o_dst, o_et, o_w = flat
+    n = int(node_id.shape[0])
+    stay = np.ones(n, dtype=bool)
+    stay[lost] = False
+    new_node = np.where(stay, np.cumsum(stay) - 1, -1).astype(np.int32)
+    src = np.repeat(np.arange(n), np.diff(rowptr))
+    keep = stay[src] & stay[o_dst]
+    new_link = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int64)
+    new_rowptr = np.zeros(int(stay.sum()) + 1, dtype=np.int64)
+    new_rowptr[1:] = np.cumsum(np.bincount(src[keep], minlength=n)[stay])
+    new_flat = (node_id[stay], node_type[stay], new_rowptr, new_node[o_dst[keep]].astype(np.int32), o_et[keep], o_w[keep])
+    return new_flat, new_node, new_link
+
+
+def _lost_nodes(old_flat, new_flat):
+    """The indices (in ``old_flat``, ascending) of the nodes by which ``old_flat`` exceeds ``new_flat``: the remaining nodes
+    are unchanged and in order -- matched by (id, type), the earliest old node for each new one -- and, with the nodes mapped
+    to their new indices, every remaining list is its old self minus the links to lost nodes, bitwise.  ``None`` otherwise
+    (also when no node is missing).  Where nodes of equal (id, type) leave a choice that the earliest match gets wrong, the
+    lists do not compare equal and the graph is sent whole."""
+    o_id, o_type = old_flat[0], old_flat[1]
+    n_id, n_type = new_flat[0], new_flat[1]
+    n_old, n_new = int(o_id.shape[0]), int(n_id.shape[0])
+    if n_new >= n_old or n_new == 0:
+        return None
+    lost, k = [], 0
+    for j in range(n_new):
+        while k < n_old and not (o_id[k] == n_id[j] and o_type[k] == n_type[j]):
+            lost.append(k)
+            k += 1
+        if k == n_old:
+            return None
+        k += 1
+    lost.extend(range(k, n_old))
+    lost = np.array(lost, dtype=np.int32)
+    want = _removed_nodes_flat(old_flat, lost)[0]
+    for a, b in zip(want[2:], new_flat[2:]):
+        if a.shape != b.shape:
+            return None
+    if not ((want[2] == new_flat[2]).all() and (want[3] == new_flat[3]).all() and (want[4] == new_flat[4]).all()
+            and (want[5].view(np.uint64) == new_flat[5].view(np.uint64)).all()):
+        return None
+    return lost
+
+
 class Graph:
     """class Graph (Graph.cs:37-94).  ``nodes``/``edges`` are the caller's dictionaries
     (kept by reference, Graph.cs:46-47); ``buildGraph()`` hands the RAW links to
@@ -241,6 +291,7 @@ class Graph:
     append_rebuilds = 0          # ... and those that went through rwr_graph_append_links (lists that only grew)
     node_append_rebuilds = 0     # ... and through rwr_graph_append_nodes (nodes added at the end, lists that only grew)
     remove_rebuilds = 0          # ... and through rwr_graph_remove_links (lists that only shrank)
+    node_remove_rebuilds = 0     # ... and through rwr_graph_remove_nodes (nodes lost, the others unchanged and in order)
 
     def __init__(self, nodes: Dict[int, Node], edges: Dict[int, List[ForwardLink]], *, mode: Optional[str] = None,
                  device: int = -1, tile_seeds: int = 0, tile_group: int = 0, profile: bool = False,
@@ -302,6 +353,9 @@ class Graph:
         the same order, the new keys continuing the index sequence -- only the new nodes and links (rwr_graph_append_nodes);
         when lists only lost links (``del edges[u][k]``: every shorter list a subsequence of its old self, the others
         unchanged) only the positions of the links that left (rwr_graph_remove_links);
+        when the node dictionary only lost nodes -- the remaining ones unchanged, in order and re-keyed 0 .. n-1, every
+        remaining list its old self minus the links to lost nodes, with the targets re-keyed alike -- only the lost indices
+        (rwr_graph_remove_nodes);
         lists that grew AND whose old links changed, lists that shrank AND grew or changed, a changed old node or a reordered
         dictionary are sent whole.  The device state is the same either way."""
         lib = _lib.load()
@@ -349,6 +403,16 @@ class Graph:
                 self._sent = flat
                 self._graph_cache = None
                 Graph.node_append_rebuilds += 1
+                return
+            lost = _lost_nodes(self._sent, flat)
+            if lost is not None:
+                # (the library directly: flat IS _sent without those nodes)
+                _lib.check(lib.rwr_graph_remove_nodes(self._handle(), int(lost.shape[0]), _p(lost, C.c_int32), None, None, None))
+                self._n = int(node_id.shape[0])
+                self._rowptr = rowptr
+                self._sent = flat
+                self._graph_cache = None
+                Graph.node_remove_rebuilds += 1
                 return
         if self._h:
             lib.rwr_graph_destroy(self._h)
@@ -431,6 +495,36 @@ class Graph:
                 self._sent = _removed_flat(self._sent, idx)
             self._rowptr = self._rowptr - np.searchsorted(np.sort(idx), self._rowptr, side="left")
         self._graph_cache = None
+
+    def removeNodes(self, node_index) -> Tuple[np.ndarray, np.ndarray]:
+        """rwr_graph_remove_nodes: the nodes at the given indices (distinct, any order) leave the graph with every raw link
+        from or to them (nodes.Remove(i); edges.Remove(i), and the links to i out of the other lists), the others close up
+        and keep their order, then the device-side rebuild.  Returns ``(new_node_index, new_link_index)``: the new index
+        of every old node and the new flattened position of every old link, -1 for what left.
+
+        The object's record of what the device holds follows, as for removeLinks.  A dictionary graph: the caller takes
+        the same nodes and links out of ``nodes`` / ``edges`` and re-keys both by ``new_node_index``; the next buildGraph()
+        finds nothing more to send.  A flat graph: the object continues with shortened COPIES of the arrays."""
+        idx = np.ascontiguousarray(node_index, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError("node_index must be one-dimensional")
+        new_node = np.zeros(self._n, dtype=np.int32)
+        new_link = np.zeros(int(self._rowptr[-1]), dtype=np.int64)
+        _lib.check(_lib.load().rwr_graph_remove_nodes(self._handle(), int(idx.shape[0]), _p(idx, C.c_int32),
+                                                      _p(new_node, C.c_int32), _p(new_link, C.c_int64), None))
+        stay = new_node >= 0
+        if self._flat is not None:
+            self._flat = _removed_nodes_flat(self._flat, idx)[0]
+            self._desc = None
+            self._rowptr = self._flat[2]
+        else:
+            if self._sent is not None:
+                self._sent = _removed_nodes_flat(self._sent, idx)[0]
+            kept = np.concatenate([[0], np.cumsum(new_link >= 0)]).astype(np.int64)   # kept links in front of a position
+            self._rowptr = np.concatenate([kept[self._rowptr[:-1][stay]], kept[-1:]])
+        self._n = int(stay.sum())
+        self._graph_cache = None
+        return new_node, new_link
 
     def appendNodes(self, nodes, src=(), dst=(), etype=(), w=()) -> Tuple[int, np.ndarray]:
         """rwr_graph_append_nodes: node j of ``nodes`` (``Node`` objects or ``(id, type)`` pairs) gets index n + j and an empty

@@ -1,0 +1,503 @@
+"""rwr_graph_remove_nodes on the GPU: after the call the handle must be bit for bit what rwr_graph_create builds
+from the shortened and renumbered arrays.  The yardstick of every case is therefore a FRESH handle created from the arrays a
+brute-force NumPy erase produces (the links from or to a lost node dropped, the targets renumbered by a cumulative sum of the
+surviving nodes); on the smallest case the C oracle is asked as well.  "Equal" = the snapshot of
+tests/test_gpu_graph_remove.py: the bits of rwr_graph_get_normalized, rwr_graph_size, the uniform / uniform_path / nnz_raw /
+nnz statistics, rwr_model_run for three seeds and the global model, the full rwr_recommend lists of those seeds (every ITEM,
+so both ITEM orders show), a rwr_recommend_batch at top-10 and a typed "who to follow" call.  Both index outputs are compared
+with NumPy in every case."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import graphgen as gg
+from tests.test_gpu_graph_append import D, T, _api, assert_same, bipartite, build, patched, sizes
+from tests.test_gpu_graph_remove import _dictionary, check_fresh, shortened, snap, sources
+
+pytestmark = pytest.mark.gpu
+
+
+def without(g, lost):
+    """(the arrays of g without the nodes `lost`, new index of every old node, new position of every old link): the brute force."""
+    n = g["node_id"].shape[0]
+    stay = np.ones(n, dtype=bool)
+    stay[np.asarray(lost, dtype=np.int64)] = False
+    new_node = np.where(stay, np.cumsum(stay) - 1, -1).astype(np.int32)
+    src = sources(g)
+    keep = stay[src] & stay[g["dst"]]
+    new_link = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int64)
+    rowptr = np.zeros(int(stay.sum()) + 1, dtype=np.int64)
+    np.cumsum(np.bincount(new_node[src[keep]], minlength=int(stay.sum())), out=rowptr[1:])
+    out = dict(node_id=g["node_id"][stay], node_type=g["node_type"][stay], rowptr=rowptr,
+               dst=new_node[g["dst"][keep]].astype(np.int32), etype=g["etype"][keep], w=g["w"][keep])
+    return out, new_node, new_link
+
+
+def from_links(node_id, node_type, src, dst, etype, w):
+    """Flat arrays from a link list: lists in the order of the links."""
+    n = len(node_id)
+    src = np.asarray(src, dtype=np.int64)
+    order = np.argsort(src, kind="stable")
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(src, minlength=n), out=rowptr[1:])
+    return dict(node_id=np.asarray(node_id, dtype=np.int64), node_type=np.asarray(node_type, dtype=np.uint8), rowptr=rowptr,
+                dst=np.asarray(dst, dtype=np.int32)[order], etype=np.asarray(etype, dtype=np.uint8)[order],
+                w=np.asarray(w, dtype=np.float64)[order])
+
+
+def grown(g, ids, types):
+    """g with nodes (empty lists) behind its last one."""
+    k = len(ids)
+    return dict(g, node_id=np.concatenate([g["node_id"], np.asarray(ids, dtype=np.int64)]),
+                node_type=np.concatenate([g["node_type"], np.asarray(types, dtype=np.uint8)]),
+                rowptr=np.concatenate([g["rowptr"], np.full(k, g["rowptr"][-1], dtype=np.int64)]))
+
+
+def remove(G, g, lost):
+    """G.removeNodes(lost) with both outputs and the sizes checked against the brute force; returns (want, new_node, new_link)."""
+    want, nn, nl = without(g, lost)
+    got_n, got_l = G.removeNodes(np.asarray(lost, dtype=np.int32))
+    assert np.array_equal(got_n, nn) and np.array_equal(got_l, nl)
+    assert sizes(G)[:2] == (want["node_id"].shape[0], int(want["rowptr"][-1]))
+    return want, nn, nl
+
+
+def typed(G, users):
+    _, _, _, Recommender, _ = _api()
+    from recommendersystems_amd.rwr_based import EdgeType, NodeType
+    ids, sc, cnt = Recommender(G).RecommendationTypedBatch(np.asarray(users, dtype=np.int32), D, T, 10, NodeType.USER,
+                                                           (EdgeType.FRIENDSHIP, EdgeType.FOLLOW), True)
+    return ids, sc.view(np.uint64), cnt
+
+
+def _small():
+    """100 users x 200 items with likes, friend / follow / mention links: about 300 nodes and 2 000 links.  Three nodes are
+    added by hand: a USER without any link, a USER whose only link is a LIKE of item 150, and a last ITEM without links."""
+    g = gg.random_graph(31, n_users=100, n_items=200, n_likes=1100, n_friend=60, n_mention=40)
+    et = g["etype"].copy()
+    fr = np.flatnonzero(et == gg.EDGE_FRIENDSHIP)
+    et[fr[::2]] = gg.EDGE_FOLLOW
+    g = grown(dict(g, etype=et), [90001, 90002, 90003], [gg.NODE_USER, gg.NODE_USER, gg.NODE_ITEM])
+    g, _ = patched(g, [301], [150], [gg.EDGE_LIKE], [1.0])
+    return g
+
+
+ISO, LONELY, LIKED = 300, 301, 150
+
+
+# ------------------------------------------------------------------------------------------------------------------ cases
+
+def test_one_launch_path():
+    """A USER, an ITEM, node 0, node n - 1, a node without links and the only target of another node, which becomes dangling."""
+    from oracle.c_oracle import FlatGraph
+    _, _, _, Recommender, _ = _api()
+    g = _small()
+    n, m = g["node_id"].shape[0], int(g["rowptr"][-1])
+    assert n == 303 and 1500 < m < 4000
+    lost = [40, 220, 0, n - 1, ISO, LIKED]
+    G = build(g)
+    assert G.normalized()[1][LONELY] == 0
+    want, nn, nl = remove(G, g, lost)
+    assert G.normalized()[1][nn[LONELY]] == 1 and int((nl < 0).sum()) > 6
+    seeds, batch = (int(nn[7]), int(nn[33]), int(nn[LONELY])), nn[np.arange(1, 40)]
+    check_fresh(G, want, seeds, batch, nn[np.arange(1, 40, 3)])
+    ids, sc = Recommender(G).RecommendationArrays(seeds[0], D, T)
+    oi, osc = FlatGraph(**want).recommend(seeds[0], D, T)
+    assert np.array_equal(ids, oi) and np.array_equal(sc.view(np.uint64), osc.view(np.uint64))
+    G.close()
+
+
+def _general():
+    """n above 8 192 and four chunks of 8 192 links.  Rows 0 .. 8 189 are users whose one link is a LIKE of the hub (the last
+    node, an ITEM): positions 0 .. 8 189.  Row 8 190 is a user with five links: positions 8 190 .. 8 194, across the chunk
+    edge.  Then a weighted bipartite graph, whose first 100 users like the hub as well (8 290 in-links)."""
+    b = bipartite(9, 600, 500, 11000, unit=False)
+    nb, fans, row = b["node_id"].shape[0], 8190, 8190
+    base = row + 1
+    hub = base + nb
+    rng = np.random.default_rng(19)
+    src = np.concatenate([np.arange(fans), np.full(5, row), sources(b) + base, base + np.arange(100)])
+    dst = np.concatenate([np.full(fans, hub), base + 600 + rng.permutation(500)[:5], b["dst"] + base, np.full(100, hub)])
+    et = np.concatenate([np.full(fans + 5, gg.EDGE_LIKE), b["etype"], np.full(100, gg.EDGE_LIKE)])
+    w = np.concatenate([np.ones(fans + 5), b["w"], np.full(100, 2.25)])
+    ids = np.concatenate([np.arange(10 ** 6, 10 ** 6 + base), b["node_id"], [77]])
+    types = np.concatenate([np.full(base, gg.NODE_USER), b["node_type"], [gg.NODE_ITEM]])
+    g = from_links(ids, types, src, dst, et, w)
+    m = int(g["rowptr"][-1])
+    assert g["node_id"].shape[0] > 8192 and 3 * 8192 < m <= 4 * 8192
+    assert int(g["rowptr"][row]) == 8190 and int(g["rowptr"][row + 1]) == 8195 and (g["dst"][:8190] == hub).all()
+    return g, row, base, hub
+
+
+def test_general_path():
+    """The hub and the row across the chunk edge leave: the first chunk keeps nothing, and 8 190 rows that start in it become
+    dangling.  Fifteen more nodes of both types leave with them."""
+    g, row, base, hub = _general()
+    rng = np.random.default_rng(20)
+    lost = np.concatenate([[hub, row, 17, 18, 8189], base + 5 + rng.permutation(1000)[:12]])
+    G = build(g)
+    want, nn, nl = remove(G, g, rng.permutation(lost))
+    assert (nl[:8192] < 0).all() and G.normalized()[1][:8187].all()
+    users = nn[base + np.arange(0, 600, 15)]
+    users = users[users >= 0]
+    check_fresh(G, want, (3, int(users[1]), int(users[-1])), users, users[::4])
+    G.close()
+
+
+def test_general_path_keeps_most():
+    """The same graph, neither the hub nor row 8 190 removed: every chunk keeps nearly all of its links."""
+    g, row, base, hub = _general()
+    lost = [0, 8191, base + 3, base + 700, hub - 1]
+    G = build(g)
+    want, nn, nl = remove(G, g, lost)
+    users = nn[base + np.arange(0, 600, 15)]
+    users = users[users >= 0]
+    check_fresh(G, want, (3, int(users[1]), int(users[-1])), users, users[::4])
+    G.close()
+
+
+def test_crossing_8192_nodes_downwards():
+    """8 200 nodes minus 20: the handle, built by the general derive, stays on it, while the fresh handle of 8 180 nodes builds
+    in one launch.  All of the snapshot is bitwise."""
+    g = bipartite(5, 3000, 5200, 20000)
+    n, m = g["node_id"].shape[0], int(g["rowptr"][-1])
+    assert n == 8200 and m <= 65536
+    lost = np.random.default_rng(21).permutation(n)[:20]
+    lost = lost[(lost != 0) & (lost != 17) & (lost != 5)]
+    lost = np.concatenate([lost, np.setdiff1d(np.arange(6000, 6040), lost)])[:20]
+    G = build(g)
+    want, nn, nl = remove(G, g, lost)
+    assert want["node_id"].shape[0] == 8180
+    batch = nn[np.arange(0, 400, 10)]
+    check_fresh(G, want, (0, int(nn[17]), int(nn[5])), batch[batch >= 0], nn[[0, 5, 17]])
+    G.close()
+
+
+def test_round_trips():
+    g = _small()
+    n = g["node_id"].shape[0]
+    seeds, batch, who = (1, 7, 33), np.arange(1, 40), np.arange(1, 40, 3)
+    lost = np.array([120, 60, 250, 299])
+    # remove, then rwr_graph_append_nodes brings nodes of the same kind back behind the last one, with links
+    G = build(g)
+    want, nn, nl = remove(G, g, lost)
+    n1 = want["node_id"].shape[0]
+    new_id, new_type = [555, 556], [gg.NODE_ITEM, gg.NODE_USER]
+    a = (np.array([1, 7, n1 + 1], dtype=np.int32), np.array([n1, n1, n1], dtype=np.int32),
+         np.full(3, gg.EDGE_LIKE, dtype=np.uint8), np.ones(3))
+    G.appendNodes(list(zip(new_id, new_type)), *a)
+    want2, _ = patched(grown(want, new_id, new_type), *a)
+    check_fresh(G, want2, seeds, batch, who)
+    G.close()
+    # remove, then the three link edits at positions taken from new_link_index_out
+    G = build(g)
+    want, nn, nl = remove(G, g, lost)
+    old = np.flatnonzero(nl >= 0)[::9][:60]
+    at = nl[old]
+    assert np.array_equal(want["w"][at], g["w"][old]) and np.array_equal(want["dst"][at], nn[g["dst"][old]])
+    new_t = np.where(np.arange(at.shape[0]) % 3 == 0, gg.EDGE_UNDEFINED, gg.EDGE_LIKE).astype(np.uint8)
+    new_w = np.linspace(0.5, 3.0, at.shape[0])
+    G.updateLinks(at[:40], new_t[:40], new_w[:40])
+    want = dict(want, etype=want["etype"].copy(), w=want["w"].copy())
+    want["etype"][at[:40]], want["w"][at[:40]] = new_t[:40], new_w[:40]
+    check_fresh(G, want, seeds, batch, who)
+    G.removeLinks(at[40:])
+    want = shortened(want, at[40:])
+    check_fresh(G, want, seeds, batch, who)
+    b = (np.array([1, 7, 33, 200], dtype=np.int32), np.array([210, 211, 212, 7], dtype=np.int32),
+         np.full(4, gg.EDGE_LIKE, dtype=np.uint8), np.array([1.0, 0.75, 1.0, 1.0]))
+    got_pos = G.appendLinks(*b)
+    want, want_pos = patched(want, *b)
+    assert np.array_equal(got_pos, want_pos)
+    check_fresh(G, want, seeds, batch, who)
+    G.removeNodes([])                                     # count == 0 just rebuilds
+    check_fresh(G, want, seeds, batch, who)
+    G.close()
+    # rwr_graph_append_nodes, then exactly those nodes leave: the state before the append
+    G = build(g)
+    before = snap(G, seeds, batch, who)
+    G.appendNodes([(777, gg.NODE_ITEM), (778, gg.NODE_USER)], [1, n + 1, 150], [n, n, n + 1], [gg.EDGE_LIKE] * 3, [1.0] * 3)
+    got_n, got_l = G.removeNodes([n + 1, n])
+    assert np.array_equal(got_n, np.concatenate([np.arange(n), [-1, -1]])) and int((got_l < 0).sum()) == 3
+    assert_same(snap(G, seeds, batch, who), before)
+    G.close()
+
+
+def _items(ids):
+    """Ten users, then one ITEM per entry of ids; every user likes a few items, most items are liked by nobody (equal
+    scores: the ITEM order decides their places in a full list)."""
+    k = len(ids)
+    rng = np.random.default_rng(23)
+    u = np.repeat(np.arange(10), 3)
+    v = 10 + rng.integers(0, k, 30)
+    key = np.unique(u * 1000 + v)
+    u, v = key // 1000, key % 1000
+    return from_links(np.concatenate([np.arange(100, 110), ids]), [gg.NODE_USER] * 10 + [gg.NODE_ITEM] * k,
+                      np.concatenate([u, v]), np.concatenate([v, u]), np.full(2 * u.shape[0], gg.EDGE_LIKE), np.ones(2 * u.shape[0]))
+
+
+def test_item_orders():
+    seeds, batch, who = (0, 4, 8), np.arange(10), np.arange(0, 10, 3)
+    # equal ids on both sides of a removed ITEM (600 items: three blocks of the order's compaction)
+    ids = np.where(np.arange(600) % 4 == 0, 50, 50 + np.arange(600) % 3).astype(np.int64)
+    g = _items(ids)
+    G = build(g)
+    want, nn, nl = remove(G, g, [10 + 4, 10 + 5, 10 + 6, 10 + 255, 10 + 256, 10 + 257, 10 + 300, 3])
+    seeds2 = tuple(int(nn[s]) for s in seeds)
+    check_fresh(G, want, seeds2, nn[batch][nn[batch] >= 0], nn[who][nn[who] >= 0])
+    G.close()
+    # the largest and the smallest ITEM id leave, then an ITEM arrives whose id lies outside the new range (id_key_*)
+    ids = np.array([40, -(1 << 40), 7, 1 << 50, 12, 12, 9, 1000], dtype=np.int64)
+    g = _items(ids)
+    G = build(g)
+    want, nn, nl = remove(G, g, [10 + 3, 10 + 1])
+    check_fresh(G, want, seeds, batch, who)
+    G.appendNodes([(5000, gg.NODE_ITEM), (-3, gg.NODE_ITEM), (12, gg.NODE_ITEM)], [0], [want["node_id"].shape[0]], [gg.EDGE_LIKE], [1.0])
+    want, _ = patched(grown(want, [5000, -3, 12], [gg.NODE_ITEM] * 3), [0], [want["node_id"].shape[0]], [gg.EDGE_LIKE], [1.0])
+    check_fresh(G, want, seeds, batch, who)
+    G.close()
+    # the last ITEM of a graph leaves; then one arrives
+    g = _items(np.array([5], dtype=np.int64))
+    G = build(g)
+    want, nn, nl = remove(G, g, [10])
+    assert int(want["rowptr"][-1]) == 0
+    check_fresh(G, want, seeds, batch, who)
+    G.appendNodes([(9, gg.NODE_ITEM)], [2], [10], [gg.EDGE_LIKE], [1.0])
+    want, _ = patched(grown(want, [9], [gg.NODE_ITEM]), [2], [10], [gg.EDGE_LIKE], [1.0])
+    check_fresh(G, want, seeds, batch, who)
+    G.close()
+
+
+def test_cached_candidate_lists_are_dropped():
+    """A typed USER call caches the USER rows for n nodes.  One USER leaves (the items move down by one) and one USER arrives
+    behind the last node: n is back, the rows are others.  The typed call must answer as on a fresh handle."""
+    g = _small()
+    n = g["node_id"].shape[0]
+    users = np.arange(1, 40, 3)
+    G = build(g)
+    typed(G, users)
+    want, nn, nl = remove(G, g, [50])
+    G.appendNodes([(4242, gg.NODE_USER)], [n - 1, 3], [3, n - 1], [gg.EDGE_FOLLOW] * 2, [1.0] * 2)
+    want, _ = patched(grown(want, [4242], [gg.NODE_USER]), [n - 1, 3], [3, n - 1], [gg.EDGE_FOLLOW] * 2, [1.0] * 2)
+    assert sizes(G)[0] == n
+    F = build(want)
+    a, b = typed(G, users), typed(F, users)
+    assert all(np.array_equal(x, y) for x, y in zip(a, b))
+    check_fresh(G, want, (1, 7, 33), np.arange(1, 40), users)
+    F.close()
+    G.close()
+
+
+def test_semantics_visible_to_a_caller():
+    _, _, _, Recommender, _ = _api()
+    g = _small()
+    rp, src = g["rowptr"], sources(g)
+    # a removed ITEM is in no list
+    G = build(g)
+    before, _ = Recommender(G).RecommendationArrays(7, D, T)
+    item = int(np.flatnonzero(np.isin(g["node_id"], before[:1]))[0])
+    want, nn, nl = remove(G, g, [item])
+    after, _ = Recommender(G).RecommendationArrays(int(nn[7]), D, T)
+    assert int(g["node_id"][item]) not in set(after.tolist()) and after.shape[0] == before.shape[0] - 1
+    bi, _, bc = Recommender(G).RecommendationBatch(np.arange(0, 40, dtype=np.int32), D, T, 300)
+    assert int(g["node_id"][item]) not in set(bi.ravel().tolist())
+    G.close()
+    # a seed that LIKEd only removed items: the fresh handle's list (the node is dangling now)
+    G = build(g)
+    want, nn, nl = remove(G, g, [LIKED])
+    check_fresh(G, want, (int(nn[LONELY]), 7, 33), np.arange(0, 40), np.arange(1, 40, 3))
+    G.close()
+    # one odd weight in a uniform graph: it leaves with its row's node, and the graph is uniform again
+    h = gg.random_graph(33, n_users=50, n_items=80, n_likes=400, uniform=True)
+    r = int(np.flatnonzero(np.diff(h["rowptr"])[:50] >= 3)[0])
+    h = dict(h, w=h["w"].copy())
+    h["w"][int(h["rowptr"][r]) + 1] = 2.0
+    G = build(h)
+    assert G.stats()["uniform"] == 0
+    other = 49 if r != 49 else 48
+    want, nn, nl = remove(G, h, [other])
+    assert G.stats()["uniform"] == 0
+    check_fresh(G, want, (0, int(nn[r]), 20), np.arange(0, 40), np.arange(0, 40, 3))
+    want2, nn2, _ = remove(G, want, [int(nn[r])])
+    st = G.stats()
+    assert st["uniform"] == 1 and st["uniform_path"] == 1
+    check_fresh(G, want2, (0, 5, 20), np.arange(0, 40), np.arange(0, 40, 3))
+    G.close()
+
+
+def test_warm_handle():
+    """Every lazily built structure of the previous matrix exists (tail rows, frontier lists, batch workspaces, the sweep
+    tables of a single-seed call, the model batch's matrices, a cached candidate list) when the nodes leave."""
+    _, _, Model, Recommender, _ = _api()
+    g = bipartite(17, 4000, 9000, 60000)
+    n = g["node_id"].shape[0]
+    G = build(g)
+    rec = Recommender(G)
+    batch = np.arange(0, 4000, 100)
+    rec.RecommendationBatch(batch.astype(np.int32), D, T, 10)
+    rec.RecommendationArrays(5, D, T)
+    Model.RunBatch(G, float(np.float32(D)), batch[:16], T)
+    typed(G, batch[:8])
+    lost = np.random.default_rng(41).permutation(n)[:300]
+    lost = lost[~np.isin(lost, [5, 250, 3999])]
+    want, nn, nl = remove(G, g, lost)
+    F = build(want)
+    nb = nn[batch][nn[batch] >= 0]
+    seeds, who = (int(nn[5]), int(nn[250]), int(nn[3999])), nb[::4]
+    assert_same(snap(G, seeds, nb, who), snap(F, seeds, nb, who))
+    ra, ia = Model.RunBatch(G, float(np.float32(D)), nb[:16], T)
+    rf, if_ = Model.RunBatch(F, float(np.float32(D)), nb[:16], T)
+    assert np.array_equal(ra.view(np.uint64), rf.view(np.uint64)) and np.array_equal(ia, if_)
+    F.close()
+    G.close()
+
+
+def test_row_partitioned_state_is_lost():
+    """After a removal rwr_part_step is refused until rwr_part_begin; after rwr_part_begin over the whole range the ranking is
+    the fresh handle's (tolerance parity as in test_row_partitioned_logical_ranks: identical lists, scores within 1e-9)."""
+    import torch
+    _lib, _, _, _, _ = _api()
+    from recommendersystems_amd import partitioned as pt
+    g = gg.random_graph(51, n_users=300, n_items=900, n_likes=7000, n_friend=200, n_mention=100)
+    n = g["node_id"].shape[0]
+    seeds = np.array([0, 7, 123, 250, 298], dtype=np.int32)
+    d = float(np.float32(D))
+    lost = np.array([299, 400, 401, 1199])
+    want, nn, nl = without(g, lost)
+
+    def walk(be):
+        x, y, _ = be.begin(seeds, d)
+        for _ in range(T):
+            be.step(x, y)
+            x, y = y, x
+        return be.rank(x, 20)
+
+    be = pt.HipSlabBackend(g, 0, n)
+    x, y, _ = be.begin(seeds, d)
+    be.step(x, y)
+    torch.cuda.synchronize()
+    be.graph.removeNodes(lost)
+    be.n = be.hi = n - 4
+    x = torch.zeros((n - 4) * be.G, dtype=torch.float64, device=be.dev)
+    y = torch.zeros_like(x)
+    with pytest.raises(_lib.RwrError) as e:
+        be.step(x, y)
+    assert e.value.status == _lib.RWR_E_INVALID and "rwr_part_begin" in str(e.value)
+    got = walk(be)
+    ref = walk(pt.HipSlabBackend(want, 0, n - 4))
+    assert np.array_equal(got[0], ref[0]) and np.array_equal(got[2], ref[2])
+    assert np.abs(got[1] - ref[1]).max() <= 1e-9
+    be.graph.close()
+
+
+def test_refusals_leave_a_live_graph_alone():
+    _lib, _, _, _, _p = _api()
+    lib = _lib.load()
+    g = _small()
+    n, m = g["node_id"].shape[0], int(g["rowptr"][-1])
+    G = build(g)
+    seeds, batch, who = (1, 9, 20), np.arange(1, 40), np.arange(1, 40, 3)
+    before = snap(G, seeds, batch, who)
+    h = G._handle()
+    out_n, out_l, out_c = np.full(n, -5, dtype=np.int32), np.full(m, -5, dtype=np.int64), C.c_int64(-5)
+
+    def call(count, idx):
+        a = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32)
+        return lib.rwr_graph_remove_nodes(h, count, None if a is None else _p(a, C.c_int32), _p(out_n, C.c_int32),
+                                          _p(out_l, C.c_int64), C.byref(out_c))
+
+    def message():
+        return lib.rwr_last_error().decode()
+
+    for bad, q in ((n, 2), (-1, 0), (2 ** 31 - 1, 3)):
+        idx = np.array([3, 5, 7, 9], dtype=np.int32)
+        idx[q] = bad
+        assert call(4, idx) == _lib.RWR_E_RANGE
+        assert "node_index[%d]" % q in message(), message()
+    assert call(4, [3, 5, 3, 5]) == _lib.RWR_E_INVALID
+    assert "node_index[2]" in message(), message()
+    assert call(5, [3, 5, 7, 7, n]) == _lib.RWR_E_RANGE       # range comes before duplicate
+    assert "node_index[4]" in message(), message()
+    assert call(n, np.random.default_rng(3).permutation(n)) == _lib.RWR_E_UNSUPPORTED
+    assert "destroy" in message(), message()
+    assert call(n + 1, np.concatenate([np.arange(n), [0]])) == _lib.RWR_E_INVALID   # duplicate comes before count == n
+    assert call(-1, [3, 5]) == _lib.RWR_E_INVALID
+    assert call(2, None) == _lib.RWR_E_INVALID
+    assert (out_n == -5).all() and (out_l == -5).all() and out_c.value == -5        # a refused call writes nothing
+    assert_same(snap(G, seeds, batch, who), before)       # same bits, not poisoned
+    assert call(3, [3, 5, 290]) == _lib.RWR_OK             # ... and valid arguments go through
+    want, nn, nl = without(g, [3, 5, 290])
+    assert np.array_equal(out_n, nn) and np.array_equal(out_l, nl) and out_c.value == int((nl < 0).sum())
+    G._flat, G._n, G._rowptr = tuple(want[k] for k in ("node_id", "node_type", "rowptr", "dst", "etype", "w")), n - 3, want["rowptr"]
+    check_fresh(G, want, (0, 7, 20), np.arange(0, 40), np.arange(0, 40, 3))
+    assert call(0, None) == _lib.RWR_OK                    # count == 0: identities, nothing left
+    assert np.array_equal(out_n[:n - 3], np.arange(n - 3)) and np.array_equal(out_l[:int(want["rowptr"][-1])], np.arange(int(want["rowptr"][-1])))
+    assert out_c.value == 0
+    check_fresh(G, want, (0, 7, 20), np.arange(0, 40), np.arange(0, 40, 3))
+    G.close()
+
+
+def _rekeyed(nodes, edges, new_node):
+    """The dictionaries without the lost nodes, re-keyed 0 .. n-1 in order, as a caller keeps them for Graph.cs."""
+    from recommendersystems_amd.rwr_based import ForwardLink
+    nodes2 = {int(new_node[i]): nd for i, nd in nodes.items() if new_node[i] >= 0}
+    edges2 = {int(new_node[i]): [ForwardLink(int(new_node[l.targetNode]), l.type, l.weight) for l in L if new_node[l.targetNode] >= 0]
+              for i, L in edges.items() if new_node[i] >= 0}
+    return nodes2, edges2
+
+
+def test_mirror():
+    """Graph.removeNodes on a flat and on a dictionary graph, the buildGraph() path for a dictionary that only lost nodes,
+    and its counter; a dictionary that lost a node and gained a link is sent whole."""
+    _, Graph, _, _, _ = _api()
+    from recommendersystems_amd.rwr_based import EdgeType, ForwardLink
+    g = _small()
+    lost = [12, 150, 299]
+    want, nn, nl = without(g, lost)
+    seeds, batch, who = (0, 8, 20), np.arange(0, 40), np.arange(0, 40, 3)
+    # flat: the object continues with shortened copies; the caller's arrays are untouched
+    keep = {k: v.copy() for k, v in g.items()}
+    G = build(g)
+    G.removeNodes(lost)
+    assert all(np.array_equal(g[k], keep[k]) for k in g)
+    F = build(want)
+    fields = lambda X: {i: None if L is None else [(l.targetNode, int(l.type), l.weight) for l in L] for i, L in X.graph.items()}
+    assert fields(G) == fields(F)
+    G.buildGraph()                                        # destroy + create from the shortened copies
+    assert sizes(G) == sizes(F)
+    assert_same(snap(G, seeds, batch, who), snap(F, seeds, batch, who))
+    G.close()
+    # dictionary: buildGraph() after the dictionaries lost the nodes goes through rwr_graph_remove_nodes
+    counters = lambda: (Graph.node_remove_rebuilds, Graph.remove_rebuilds, Graph.append_rebuilds, Graph.incremental_rebuilds,
+                        Graph.node_append_rebuilds)
+    nodes, edges = _dictionary(g)
+    G = Graph(nodes, edges)
+    G.buildGraph()
+    G.nodes, G.edges = _rekeyed(nodes, edges, nn)
+    c0 = counters()
+    G.buildGraph()
+    assert counters() == (c0[0] + 1,) + c0[1:]
+    assert sizes(G) == sizes(F)
+    assert_same(snap(G, seeds, batch, who), snap(F, seeds, batch, who))
+    # removeNodes directly, the dictionaries re-keyed alike: the next buildGraph() finds nothing to send
+    want2, nn2, _ = without(want, [5, 200])
+    G.removeNodes([200, 5])
+    G.nodes, G.edges = _rekeyed(G.nodes, G.edges, nn2)
+    c0 = counters()
+    G.buildGraph()
+    assert counters() == c0[:3] + (c0[3] + 1,) + c0[4:]  # an update of no links
+    F2 = build(want2)
+    assert_same(snap(G, seeds, batch, who), snap(F2, seeds, batch, who))
+    # a lost node AND a new link: destroy + create
+    want3, nn3, _ = without(want2, [9])
+    G.nodes, G.edges = _rekeyed(G.nodes, G.edges, nn3)
+    G.edges[0].append(ForwardLink(150, EdgeType.LIKE, 1.0))
+    want3, _ = patched(want3, [0], [150], [gg.EDGE_LIKE], [1.0])
+    c0 = counters()
+    G.buildGraph()
+    assert counters() == c0
+    F3 = build(want3)
+    assert_same(snap(G, seeds, batch, who), snap(F3, seeds, batch, who))
+    for X in (F, F2, F3, G):
+        X.close()
