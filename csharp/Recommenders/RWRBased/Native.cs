@@ -52,6 +52,10 @@ namespace Recommenders.RWRBased {
         // its bit in excl_edge_mask are left out, and the seed itself when exclude_self != 0 (Recommender.RecommendationTypedBatch)
         [DllImport(Lib)] public static extern int rwr_recommend_typed_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,
             int top_n, int cand_type, uint excl_edge_mask, int exclude_self, long[] ids, double[] scores, int[] counts);
+        // the audiences of K targets: list k ranks the nodes s of type cand_type (-1: any) by the score a walk FROM s gives
+        // targets[k]; the sources of the raw links into targets[k] whose type has its bit in etype_mask are left out, and
+        // targets[k] itself when exclude_self != 0; out_node may be null (Recommender.AudienceBatch)
+        [DllImport(Lib)] public static extern int rwr_recommend_audience_batch(GraphHandle g, int K, int[] targets, float d, int n_iter, int cand_type, uint etype_mask, int exclude_self, int top_n, long[] out_id, double[] out_score, int[] out_node, int[] out_count);
         // the same K walks evaluated on the device: Hits and the running-precision sum (Experiment.cs:121-128) of every seed's WHOLE
         // list of type cand_type (its first top_n entries when top_n > 0, any value) against test set k; no list is written
         [DllImport(Lib)] public static extern int rwr_recommend_typed_eval_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,

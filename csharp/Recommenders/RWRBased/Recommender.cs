@@ -72,6 +72,33 @@ namespace Recommenders.RWRBased {
             return all;
         }
 
+        // addition: the audiences of K targets (rwr_recommend_audience_batch) -- list k ranks the nodes s of candType (null: of
+        // any type) by the score a walk of nIteration steps FROM s gives targets[k], by one reverse walk per target.  The nodes
+        // with a raw link of a type in exclEdgeTypes to targets[k] are left out, targets[k] itself too with excludeSelf.  The
+        // scores agree with the forward walks' to the tolerance rwr.h derives, not bitwise
+        public List<KeyValuePair<long, double>>[] AudienceBatch(int[] targets, float dampingFactor, int nIteration, NodeType? candType = null,
+                                                                IEnumerable<EdgeType> exclEdgeTypes = null, bool excludeSelf = false,
+                                                                int topN = 100) {
+            if (topN < 1) throw new System.ArgumentOutOfRangeException("topN", "AudienceBatch needs topN >= 1");
+            int K = targets.Length;
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            var ids = new long[(long)K * topN]; var scores = new double[(long)K * topN]; var counts = new int[K];
+            Native.Check(Native.rwr_recommend_audience_batch(graph.handle, K, targets, dampingFactor, nIteration, candType.HasValue ? (int)candType.Value : -1, mask, excludeSelf ? 1 : 0, topN, ids, scores, null, counts));
+            var all = new List<KeyValuePair<long, double>>[K];
+            for (int k = 0; k < K; k++) {
+                all[k] = new List<KeyValuePair<long, double>>(counts[k]);
+                for (int q = 0; q < counts[k]; q++) all[k].Add(new KeyValuePair<long, double>(ids[(long)k * topN + q], scores[(long)k * topN + q]));
+            }
+            return all;
+        }
+
+        // ... and for one target
+        public List<KeyValuePair<long, double>> Audience(int target, float dampingFactor, int nIteration, NodeType? candType = null,
+                                                         IEnumerable<EdgeType> exclEdgeTypes = null, bool excludeSelf = false, int topN = 100) {
+            return AudienceBatch(new[] { target }, dampingFactor, nIteration, candType, exclEdgeTypes, excludeSelf, topN)[0];
+        }
+
         // addition: the top-N lists of K seeds among the nodes of ONE node type (rwr_recommend_typed_batch).  candType: the
         // candidates' type; exclEdgeTypes: the targets of the seed's raw links of these types are no candidates (null: none);
         // excludeSelf: neither is the seed.  "Who to follow" is (NodeType.USER, {FRIENDSHIP, FOLLOW}, true); (NodeType.ITEM,

@@ -482,6 +482,36 @@ public:
         return out;
     }
 
+    // addition: the audiences of K targets (rwr_recommend_audience_batch) -- list k ranks the nodes s of candType (< 0: of any
+    // type) by the score a walk of nIteration steps FROM s gives targets[k], by one reverse walk per target.  The nodes with a
+    // raw link of a type in exclEdgeTypes to targets[k] are left out, targets[k] itself too with excludeSelf.  The scores
+    // agree with the forward walks' to the tolerance rwr.h derives, not bitwise.  nodes (may be nullptr) receives the
+    // entries' node indices, list by list
+    std::vector<std::vector<std::pair<int64_t, double>>> audienceBatch(const std::vector<int> &targets, float dampingFactor,
+                                                                       int nIteration, int candType,
+                                                                       const std::vector<EdgeType> &exclEdgeTypes = {},
+                                                                       bool excludeSelf = false, int topN = 100,
+                                                                       std::vector<std::vector<int32_t>> *nodes = nullptr)
+    {
+        const int32_t K = (int32_t)targets.size();
+        if (topN < 1) throw std::invalid_argument("audienceBatch: topN must be >= 1");
+        uint32_t mask = 0;
+        for (EdgeType t : exclEdgeTypes) mask |= 1u << (unsigned)t;
+        std::vector<int32_t> tg(targets.begin(), targets.end());
+        std::vector<int64_t> ids((size_t)K * (size_t)topN);
+        std::vector<double> scores((size_t)K * (size_t)topN);
+        std::vector<int32_t> rows((size_t)K * (size_t)topN), counts((size_t)K);
+        check(rwr_recommend_audience_batch(graph_.handle(), K, tg.data(), dampingFactor, nIteration, candType < 0 ? -1 : candType, mask, excludeSelf ? 1 : 0, topN, ids.data(), scores.data(), rows.data(), counts.data()));
+        std::vector<std::vector<std::pair<int64_t, double>>> out((size_t)K);
+        if (nodes) nodes->assign((size_t)K, {});
+        for (int32_t k = 0; k < K; ++k)
+            for (int32_t q = 0; q < counts[k]; ++q) {
+                out[k].emplace_back(ids[(size_t)k * (size_t)topN + q], scores[(size_t)k * (size_t)topN + q]);
+                if (nodes) (*nodes)[k].push_back(rows[(size_t)k * (size_t)topN + q]);
+            }
+        return out;
+    }
+
     // addition: the same lists within a candidate pool, with a deny list per seed and with a diversity cap -- at most groupCap
     // entries per group of nodes in every list (rwr_recommend_capped_batch).  candType < 0: nodes of any type; pool == nullptr:
     // no pool, else node INDICES in any order; deny == nullptr: no deny lists, else one list of node indices per seed; groupOf

@@ -648,6 +648,42 @@ int32_t rwr_recommend_explained_batch(rwr_graph *g, const int32_t *seeds, int32_
                                       double  *why_term   /* K x top_n x n_why */,
                                       int64_t *why_total  /* K x top_n, may be NULL */);
 
+/* The audience of an item -- an addition: the opposite question of every entry above.  Given K targets (nodes of any type;
+ * they may repeat), list k ranks the nodes s of node type cand_type (-1: of any type) by
+ *     S_k[s] ~ x_T^(s)[targets[k]],
+ * the score a personalised walk of n_iter steps FROM s gives targets[k] -- "a tweet was just published, whom do we notify".
+ * No walk from any s is run: the scores of all s at once are a reverse walk of n_iter steps from the target over the
+ * out-link lists, with the restart mass of every s's walk (which depends on the dangling nodes it reaches) from one more
+ * reverse walk of the dangling indicator.
+ *   - Left out of list k: every s that has a raw link to targets[k] whose edge type has its bit in etype_mask (they already
+ *     like or follow it; UNDEFINED links count when their bit is set, as in the typed entries), and with exclude_self
+ *     targets[k] itself.  A bit of the mask beyond the edge types the header names is refused.
+ *   - The order is score descending, then id descending, then node index ascending.  The tables are K x top_n; out_node
+ *     (the entries' node indices, -1 behind a list's end) may be NULL; out_count[k] is the number of entries written.
+ *   - Duality: s is in the whole audience list of v exactly when v is in the whole list of
+ *     rwr_recommend_typed_batch(seed s, cand_type = the node type of v, the same mask, the same exclude_self).  The two
+ *     scores agree to tol_rel (below).
+ *   - Tolerance parity: this is the first ranking entry whose scores are NOT bitwise the forward walk's, because the addends
+ *     of a sum arrive in another order.  All addends are >= 0, so no sum cancels; the one subtraction of the forward walk,
+ *     rank - (1 - d) * rank, costs a factor 1 / d; a forward step sums at most n addends into a row, a reverse step at most
+ *     the longest out-list.  Hence |S - x| <= tol_rel * x with
+ *         tol_rel = 8 * (n_iter + 1) * (n + L + 8) * 2^-53 / d,   L = max(largest in-degree, largest out-degree),
+ *     and where the forward score is +0.0 the reverse score is +0.0.  With d = 0 only S >= 0 and finiteness hold.
+ *   - Determinism: the same call gives the same arrays twice, and list k does not depend on what else is in the batch or on
+ *     K -- no floating-point atomics, a row's addends in list order.
+ *   - Fixed n_iter >= 0 only: the threshold modes of Model.run have no reverse counterpart (a walk's own convergence test
+ *     needs its own rank vector).  n_iter = 0 gives n at the target itself and 0 elsewhere.
+ *   - Refusals, in this order: g NULL or a poisoned handle (RWR_E_INVALID); K < 0, or NULL targets, out_id, out_score or
+ *     out_count with K > 0 (RWR_E_INVALID); a target outside [0, n) (RWR_E_RANGE, the message names k); top_n outside
+ *     [1, 1024] (RWR_E_RANGE); n_iter < 0 (RWR_E_INVALID); cand_type outside [-1, 255] or a mask bit beyond the edge types
+ *     (RWR_E_INVALID); the domain of the Recommendation entries -- a graph with a negative or non-finite normalised weight,
+ *     or d outside [0, 1] (RWR_E_UNSUPPORTED); then K == 0 succeeds and touches nothing.  A refused call writes nothing.
+ *   - Not here: duals of the restart-vector entries; Hits / average precision of audiences; a pool of seeds. */
+int32_t rwr_recommend_audience_batch(rwr_graph *g, int32_t K, const int32_t *targets, float d, int32_t n_iter,
+                                     int32_t cand_type, uint32_t etype_mask, int32_t exclude_self, int32_t top_n,
+                                     int64_t *out_id, double *out_score, int32_t *out_node /* K x top_n, may be NULL */,
+                                     int32_t *out_count);
+
 /* ---- Model ---------------------------------------------------------------------------
  * Backs the public class Model: ctor (Model.cs:33-50 personalised, seed >= 0;
  * Model.cs:14-31 global, seed == -1), run(int) / run(double) / run() (Model.cs:68-73,

@@ -6,6 +6,8 @@
 #include <vector>
 #include <string.h>
 
+#include "audience.h"
+#include "audience_plan.h"
 #include "eval_plan.h"
 #include "exclude_plan.h"
 #include "handle.h"
@@ -471,6 +473,44 @@ int32_t rwr_recommend_explained_batch(rwr_graph *g, const int32_t *seeds, int32_
     c.top_n = top_n, c.ids = ids, c.scores = scores, c.counts = counts;
     c.n_why = n_why, c.nodes = nodes, c.why_src = why_src, c.why_term = why_term, c.why_total = why_total;
     return typed_entry("rwr_recommend_explained_batch", g, c, d, n_iter);
+}
+
+// The audience of K targets (audience.hip).  The refusals in rwr.h's order: the handle, audience_plan.h's ladder,
+// the domain, and only then the no-op
+int32_t rwr_recommend_audience_batch(rwr_graph *g, int32_t K, const int32_t *targets, float d, int32_t n_iter, int32_t cand_type,
+                                     uint32_t etype_mask, int32_t exclude_self, int32_t top_n, int64_t *out_id, double *out_score,
+                                     int32_t *out_node, int32_t *out_count)
+{
+    const char *who = "rwr_recommend_audience_batch";
+    g_err[0] = 0;
+    const int32_t n = g ? g->n : 0;
+    if (g && g->poisoned) return bound(who, g, [] { return (int32_t)RWR_OK; });   // (bound words the refusal of such a handle)
+    const AudCheck c = audience_check(g != nullptr, n, K, targets, n_iter, cand_type, etype_mask, top_n, out_id, out_score, out_count);
+    switch (c.verdict) {
+        case AUD_OK:
+        case AUD_NOOP: break;
+        case AUD_NULL_GRAPH: set_error("%s: NULL graph", who); return RWR_E_INVALID;
+        case AUD_NEGATIVE_K: set_error("%s: negative K", who); return RWR_E_INVALID;
+        case AUD_NULL_ARG: set_error("%s: NULL targets, out_id, out_score or out_count", who); return RWR_E_INVALID;
+        case AUD_TARGET_RANGE:
+            set_error("%s: target %d (batch position %d) is outside [0, %d)", who, c.bad_target, c.bad_k, n);
+            return RWR_E_RANGE;
+        case AUD_TOP_N_RANGE: set_error("%s: top_n %d is outside [1, %d]", who, top_n, (int)AUD_TOP_N_MAX); return RWR_E_RANGE;
+        case AUD_NEGATIVE_ITER:
+            set_error("%s: n_iter %d is negative (a fixed number of steps only: the threshold modes have no reverse counterpart)", who, n_iter);
+            return RWR_E_INVALID;
+        case AUD_BAD_CAND_TYPE: set_error("%s: cand_type %d is outside [-1, 255]", who, cand_type); return RWR_E_INVALID;
+        case AUD_BAD_MASK:
+            set_error("%s: etype_mask 0x%x has a bit beyond the %u edge types", who, etype_mask, TYPED_EDGE_TYPES);
+            return RWR_E_INVALID;
+    }
+    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
+    if (K == 0) return RWR_OK;
+    // Recommender.cs:14,16 -> Model.cs:33: the float is widened to double
+    return bound(who, g, [&] {
+        return audience_body(g, K, targets, (double)d, n_iter, cand_type, etype_mask, exclude_self, top_n, out_id, out_score, out_node,
+                             out_count, who);
+    });
 }
 
 int32_t rwr_recommend(rwr_graph *g, int32_t seed, float d, int32_t n_iter, int32_t top_n, int64_t *out_id,

@@ -1206,6 +1206,42 @@ class Recommender:
         c = int(counts[0])
         return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist())), nodes[0, :c], src[0, :c], term[0, :c], total[0, :c]
 
+    def AudienceBatch(self, targets, d: float, n_iter: int, cand_type=None, etype_mask=(), exclude_self: bool = False,
+                      top_n: int = 100):
+        """The audiences of K targets (rwr_recommend_audience_batch, an addition, see include/rwr.h): (ids[K,top_n],
+        scores[K,top_n], nodes[K,top_n], counts[K]).  List k ranks the nodes s of NodeType cand_type (None: of any type) by the
+        score a walk of n_iter steps FROM s gives targets[k]; the nodes with a raw link to targets[k] whose EdgeType is in
+        etype_mask (an iterable of EdgeType, or the mask as an int) are left out, targets[k] too with exclude_self.  targets:
+        node indices, taken as they are (any type, repeats allowed).  nodes: the entries' node indices, -1 behind a list's end.
+        The scores agree with the forward walks' to the tolerance the header derives, not bitwise."""
+        lib = _lib.load()
+        targets = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+        K = int(targets.shape[0])
+        if isinstance(etype_mask, (int, np.integer)):
+            mask = int(etype_mask)
+        else:
+            mask = 0
+            for t in etype_mask:
+                mask |= 1 << int(EdgeType(t))
+        top_n = int(top_n)
+        width = max(top_n, 0)
+        ids = np.zeros((K, width), dtype=np.int64)
+        sc = np.zeros((K, width), dtype=np.float64)
+        nodes = np.full((K, width), -1, dtype=np.int32)
+        counts = np.zeros(K, dtype=np.int32)
+        _lib.check(lib.rwr_recommend_audience_batch(self.graph._handle(), K, _p(targets, C.c_int32), C.c_float(d), int(n_iter),
+                                                    -1 if cand_type is None else int(cand_type), mask, 1 if exclude_self else 0,
+                                                    top_n, _p(ids, C.c_int64), _p(sc, C.c_double), _p(nodes, C.c_int32),
+                                                    _p(counts, C.c_int32)))
+        return ids, sc, nodes, counts
+
+    def Audience(self, target: int, d: float, n_iter: int, cand_type=None, etype_mask=(), exclude_self: bool = False,
+                 top_n: int = 100) -> List[Tuple[int, float]]:
+        """AudienceBatch for one target, as Recommendation returns its list: [(node id, score), ...]."""
+        ids, sc, _, counts = self.AudienceBatch([int(target)], d, n_iter, cand_type, etype_mask, exclude_self, top_n)
+        c = int(counts[0])
+        return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist()))
+
     def RecommendationCappedPositionsBatch(self, seeds, dampingFactor: float, nIteration: int, testSets, candType=None,
                                            exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None, groupOf=None,
                                            groupCap: int = 1):
