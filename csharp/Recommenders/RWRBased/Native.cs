@@ -56,6 +56,11 @@ namespace Recommenders.RWRBased {
         // targets[k]; the sources of the raw links into targets[k] whose type has its bit in etype_mask are left out, and
         // targets[k] itself when exclude_self != 0; out_node may be null (Recommender.AudienceBatch)
         [DllImport(Lib)] public static extern int rwr_recommend_audience_batch(GraphHandle g, int K, int[] targets, float d, int n_iter, int cand_type, uint etype_mask, int exclude_self, int top_n, long[] out_id, double[] out_score, int[] out_node, int[] out_count);
+        // the audiences of K weighted target sets (CSR: set_ptr, set_idx, set_w or null for 1.0 each), within an optional pool
+        // of node indices (n_pool < 0: none) and with an optional deny list per set (Recommender.AudienceSetBatch)
+        [DllImport(Lib)] public static extern int rwr_recommend_audience_set_batch(GraphHandle g, int K, long[] set_ptr, int[] set_idx, double[] set_w, float d, int n_iter, int cand_type, uint etype_mask, int exclude_members, int n_pool, int[] pool_idx, long[] deny_ptr, int[] deny_idx, int top_n, long[] out_id, double[] out_score, int[] out_node, int[] out_count);
+        // ... and the position and score of every test id in those WHOLE lists (Recommender.AudienceSetPositionsBatch)
+        [DllImport(Lib)] public static extern int rwr_recommend_audience_set_positions_batch(GraphHandle g, int K, long[] set_ptr, int[] set_idx, double[] set_w, float d, int n_iter, int cand_type, uint etype_mask, int exclude_members, int n_pool, int[] pool_idx, long[] deny_ptr, int[] deny_idx, long[] test_ptr, long[] test_ids, long[] out_pos, double[] out_score, long[] out_len);
         // the same K walks evaluated on the device: Hits and the running-precision sum (Experiment.cs:121-128) of every seed's WHOLE
         // list of type cand_type (its first top_n entries when top_n > 0, any value) against test set k; no list is written
         [DllImport(Lib)] public static extern int rwr_recommend_typed_eval_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter,

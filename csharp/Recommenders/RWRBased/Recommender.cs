@@ -99,6 +99,91 @@ namespace Recommenders.RWRBased {
             return AudienceBatch(new[] { target }, dampingFactor, nIteration, candType, exclEdgeTypes, excludeSelf, topN)[0];
         }
 
+        // addition: the audiences of K weighted target sets (rwr_recommend_audience_set_batch) -- list k ranks the nodes s of
+        // candType (null: any type) by the weighted sum of the scores a walk FROM s gives the members of sets[k].  weights:
+        // null for 1.0 each, else one weight per member (a member that repeats has its weights added).  Left out: the nodes
+        // with a raw link of a type in exclEdgeTypes to any member, the members with excludeMembers, the node indices of
+        // deny[k] (deny null: none), and with a pool (node indices, any order) every node outside it
+        public List<KeyValuePair<long, double>>[] AudienceSetBatch(int[][] sets, float dampingFactor, int nIteration, double[][] weights = null,
+                                                                   NodeType? candType = null, IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                   bool excludeMembers = false, int[] pool = null, int[][] deny = null,
+                                                                   int topN = 100) {
+            if (topN < 1) throw new System.ArgumentOutOfRangeException("topN", "AudienceSetBatch needs topN >= 1");
+            int K = sets.Length;
+            long[] setPtr, denyPtr; int[] setIdx, denyIdx; double[] setW; uint mask;
+            PackAudienceSets(sets, weights, exclEdgeTypes, deny, out setPtr, out setIdx, out setW, out denyPtr, out denyIdx, out mask);
+            var ids = new long[(long)K * topN]; var scores = new double[(long)K * topN]; var counts = new int[K];
+            Native.Check(Native.rwr_recommend_audience_set_batch(graph.handle, K, setPtr, setIdx, setW, dampingFactor, nIteration, candType.HasValue ? (int)candType.Value : -1, mask, excludeMembers ? 1 : 0, pool == null ? -1 : pool.Length, pool == null || pool.Length == 0 ? new int[1] : pool, denyPtr, denyIdx, topN, ids, scores, null, counts));
+            var all = new List<KeyValuePair<long, double>>[K];
+            for (int k = 0; k < K; k++) {
+                all[k] = new List<KeyValuePair<long, double>>(counts[k]);
+                for (int q = 0; q < counts[k]; q++) all[k].Add(new KeyValuePair<long, double>(ids[(long)k * topN + q], scores[(long)k * topN + q]));
+            }
+            return all;
+        }
+
+        // ... for one set
+        public List<KeyValuePair<long, double>> AudienceSet(int[] members, float dampingFactor, int nIteration, double[] weights = null,
+                                                            NodeType? candType = null, IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                            bool excludeMembers = false, int[] pool = null, int[] deny = null, int topN = 100) {
+            return AudienceSetBatch(new[] { members }, dampingFactor, nIteration, weights == null ? null : new[] { weights }, candType,
+                                    exclEdgeTypes, excludeMembers, pool, deny == null ? null : new[] { deny }, topN)[0];
+        }
+
+        // ... and the 0-based position and the score of every test id in the sets' WHOLE audience lists
+        // (rwr_recommend_audience_set_positions_batch): positions[k][j] / scores[k][j] answer testSets[k][j] (-1 / +0.0: not in
+        // the list), listLen[k] is list k's length
+        public long[][] AudienceSetPositionsBatch(int[][] sets, float dampingFactor, int nIteration, long[][] testSets, out double[][] scores,
+                                                  out long[] listLen, double[][] weights = null, NodeType? candType = null,
+                                                  IEnumerable<EdgeType> exclEdgeTypes = null, bool excludeMembers = false, int[] pool = null,
+                                                  int[][] deny = null) {
+            int K = sets.Length;
+            if (testSets.Length != K) throw new System.ArgumentException("one test set per target set", "testSets");
+            long[] setPtr, denyPtr; int[] setIdx, denyIdx; double[] setW; uint mask;
+            PackAudienceSets(sets, weights, exclEdgeTypes, deny, out setPtr, out setIdx, out setW, out denyPtr, out denyIdx, out mask);
+            var testPtr = new long[K + 1];
+            var testIds = new List<long>();
+            for (int k = 0; k < K; k++) { testIds.AddRange(testSets[k]); testPtr[k + 1] = testIds.Count; }
+            int total = testIds.Count;
+            testIds.Add(0);
+            var pos = new long[total + 1]; var sc = new double[total + 1];
+            listLen = new long[K];
+            Native.Check(Native.rwr_recommend_audience_set_positions_batch(graph.handle, K, setPtr, setIdx, setW, dampingFactor, nIteration, candType.HasValue ? (int)candType.Value : -1, mask, excludeMembers ? 1 : 0, pool == null ? -1 : pool.Length, pool == null || pool.Length == 0 ? new int[1] : pool, denyPtr, denyIdx, testPtr, testIds.ToArray(), pos, sc, K == 0 ? new long[1] : listLen));
+            var all = new long[K][];
+            scores = new double[K][];
+            for (int k = 0; k < K; k++) {
+                int len = (int)(testPtr[k + 1] - testPtr[k]);
+                all[k] = new long[len]; scores[k] = new double[len];
+                System.Array.Copy(pos, testPtr[k], all[k], 0, len);
+                System.Array.Copy(sc, testPtr[k], scores[k], 0, len);
+            }
+            return all;
+        }
+
+        // the arrays the audience set entries take: the sets and the deny lists as CSR (null where the caller gave none)
+        static void PackAudienceSets(int[][] sets, double[][] weights, IEnumerable<EdgeType> exclEdgeTypes, int[][] deny, out long[] setPtr,
+                                     out int[] setIdx, out double[] setW, out long[] denyPtr, out int[] denyIdx, out uint mask) {
+            int K = sets.Length;
+            if (weights != null && weights.Length != K) throw new System.ArgumentException("one weight list per set", "weights");
+            if (deny != null && deny.Length != K) throw new System.ArgumentException("one deny list per set", "deny");
+            mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            setPtr = new long[K + 1];
+            var idx = new List<int>(); var w = new List<double>(); var dn = new List<int>();
+            denyPtr = deny == null ? null : new long[K + 1];
+            for (int k = 0; k < K; k++) {
+                if (weights != null && weights[k].Length != sets[k].Length) throw new System.ArgumentException("one weight per member", "weights");
+                idx.AddRange(sets[k]);
+                if (weights != null) w.AddRange(weights[k]);
+                setPtr[k + 1] = idx.Count;
+                if (deny != null) { dn.AddRange(deny[k]); denyPtr[k + 1] = dn.Count; }
+            }
+            idx.Add(0); w.Add(0.0); dn.Add(0);
+            setIdx = idx.ToArray();
+            setW = weights == null ? null : w.ToArray();
+            denyIdx = deny == null ? null : dn.ToArray();
+        }
+
         // addition: the top-N lists of K seeds among the nodes of ONE node type (rwr_recommend_typed_batch).  candType: the
         // candidates' type; exclEdgeTypes: the targets of the seed's raw links of these types are no candidates (null: none);
         // excludeSelf: neither is the seed.  "Who to follow" is (NodeType.USER, {FRIENDSHIP, FOLLOW}, true); (NodeType.ITEM,

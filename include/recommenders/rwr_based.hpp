@@ -512,6 +512,86 @@ public:
         return out;
     }
 
+    // addition: the audiences of K weighted target SETS (rwr_recommend_audience_set_batch) -- list k ranks the nodes s of candType
+    // (< 0: of any type) by sum_v weights[k][v] * (the score a walk FROM s gives member v of sets[k]).  weights == nullptr: 1.0
+    // each, else one weight per member; a member that repeats has its weights added.  Left out: the nodes with a raw link of a
+    // type in exclEdgeTypes to any member, the members with excludeMembers, the node indices of (*deny)[k], and with a pool
+    // (node indices, any order) every node outside it.  nodes (may be nullptr) receives the entries' node indices
+    std::vector<std::vector<std::pair<int64_t, double>>> audienceSetBatch(const std::vector<std::vector<int>> &sets, float dampingFactor,
+                                                                          int nIteration,
+                                                                          const std::vector<std::vector<double>> *weights = nullptr,
+                                                                          int candType = -1,
+                                                                          const std::vector<EdgeType> &exclEdgeTypes = {},
+                                                                          bool excludeMembers = false,
+                                                                          const std::vector<int> *pool = nullptr,
+                                                                          const std::vector<std::vector<int>> *deny = nullptr,
+                                                                          int topN = 100,
+                                                                          std::vector<std::vector<int32_t>> *nodes = nullptr)
+    {
+        if (topN < 1) throw std::invalid_argument("audienceSetBatch: topN must be >= 1");
+        AudienceSets a = packAudienceSets_(sets, weights, exclEdgeTypes, pool, deny);
+        const int32_t K = a.K;
+        std::vector<int64_t> ids((size_t)K * (size_t)topN);
+        std::vector<double> scores((size_t)K * (size_t)topN);
+        std::vector<int32_t> rows((size_t)K * (size_t)topN), counts((size_t)K);
+        check(rwr_recommend_audience_set_batch(graph_.handle(), K, a.sp.data(), a.si.data(), weights ? a.sw.data() : nullptr, dampingFactor, nIteration, candType < 0 ? -1 : candType, a.mask, excludeMembers ? 1 : 0, a.nPool, a.pool.data(), deny ? a.dp.data() : nullptr, a.di.data(), topN, ids.data(), scores.data(), rows.data(), counts.data()));
+        std::vector<std::vector<std::pair<int64_t, double>>> out((size_t)K);
+        if (nodes) nodes->assign((size_t)K, {});
+        for (int32_t k = 0; k < K; ++k)
+            for (int32_t q = 0; q < counts[k]; ++q) {
+                out[k].emplace_back(ids[(size_t)k * (size_t)topN + q], scores[(size_t)k * (size_t)topN + q]);
+                if (nodes) (*nodes)[k].push_back(rows[(size_t)k * (size_t)topN + q]);
+            }
+        return out;
+    }
+
+    // ... for one set
+    std::vector<std::pair<int64_t, double>> audienceSet(const std::vector<int> &members, float dampingFactor, int nIteration,
+                                                        const std::vector<double> *weights = nullptr, int candType = -1,
+                                                        const std::vector<EdgeType> &exclEdgeTypes = {}, bool excludeMembers = false,
+                                                        const std::vector<int> *pool = nullptr, const std::vector<int> *deny = nullptr,
+                                                        int topN = 100)
+    {
+        const std::vector<std::vector<double>> w1 = {weights ? *weights : std::vector<double>()};
+        const std::vector<std::vector<int>> d1 = {deny ? *deny : std::vector<int>()};
+        return audienceSetBatch({members}, dampingFactor, nIteration, weights ? &w1 : nullptr, candType, exclEdgeTypes, excludeMembers,
+                                pool, deny ? &d1 : nullptr, topN)[0];
+    }
+
+    // ... and the 0-based position and score of every test id in the sets' WHOLE audience lists
+    // (rwr_recommend_audience_set_positions_batch): positions[k][j] / scores[k][j] answer testSets[k][j] (-1 / +0.0: not in the
+    // list), listLen[k] is list k's length.  scores and listLen may be nullptr
+    std::vector<std::vector<int64_t>> audienceSetPositionsBatch(const std::vector<std::vector<int>> &sets, float dampingFactor,
+                                                                int nIteration, const std::vector<std::vector<int64_t>> &testSets,
+                                                                const std::vector<std::vector<double>> *weights = nullptr,
+                                                                int candType = -1, const std::vector<EdgeType> &exclEdgeTypes = {},
+                                                                bool excludeMembers = false, const std::vector<int> *pool = nullptr,
+                                                                const std::vector<std::vector<int>> *deny = nullptr,
+                                                                std::vector<std::vector<double>> *scores = nullptr,
+                                                                std::vector<int64_t> *listLen = nullptr)
+    {
+        AudienceSets a = packAudienceSets_(sets, weights, exclEdgeTypes, pool, deny);
+        const int32_t K = a.K;
+        if ((int32_t)testSets.size() != K) throw std::invalid_argument("audienceSetPositionsBatch: one test set per target set");
+        std::vector<int64_t> tp((size_t)K + 1, 0), ti;
+        for (int32_t k = 0; k < K; ++k) {
+            ti.insert(ti.end(), testSets[k].begin(), testSets[k].end());
+            tp[(size_t)k + 1] = (int64_t)ti.size();
+        }
+        std::vector<int64_t> pos(ti.size() + 1, -1), len((size_t)K + 1, 0);
+        std::vector<double> sc(ti.size() + 1, 0.0);
+        ti.push_back(0);
+        check(rwr_recommend_audience_set_positions_batch(graph_.handle(), K, a.sp.data(), a.si.data(), weights ? a.sw.data() : nullptr, dampingFactor, nIteration, candType < 0 ? -1 : candType, a.mask, excludeMembers ? 1 : 0, a.nPool, a.pool.data(), deny ? a.dp.data() : nullptr, a.di.data(), tp.data(), ti.data(), pos.data(), sc.data(), len.data()));
+        std::vector<std::vector<int64_t>> out((size_t)K);
+        if (scores) scores->assign((size_t)K, {});
+        for (int32_t k = 0; k < K; ++k) {
+            out[k].assign(pos.begin() + tp[(size_t)k], pos.begin() + tp[(size_t)k + 1]);
+            if (scores) (*scores)[k].assign(sc.begin() + tp[(size_t)k], sc.begin() + tp[(size_t)k + 1]);
+        }
+        if (listLen) listLen->assign(len.begin(), len.begin() + K);
+        return out;
+    }
+
     // addition: the same lists within a candidate pool, with a deny list per seed and with a diversity cap -- at most groupCap
     // entries per group of nodes in every list (rwr_recommend_capped_batch).  candType < 0: nodes of any type; pool == nullptr:
     // no pool, else node INDICES in any order; deny == nullptr: no deny lists, else one list of node indices per seed; groupOf
@@ -737,6 +817,38 @@ public:
     }
 
 private:
+    // the arrays the audience set entries take (every array holds at least one element, so that its pointer is valid)
+    struct AudienceSets {
+        int32_t K = 0, nPool = -1;
+        uint32_t mask = 0;
+        std::vector<int64_t> sp, dp;
+        std::vector<int32_t> si, pool, di;
+        std::vector<double> sw;
+    };
+    static AudienceSets packAudienceSets_(const std::vector<std::vector<int>> &sets, const std::vector<std::vector<double>> *weights,
+                                          const std::vector<EdgeType> &exclEdgeTypes, const std::vector<int> *pool,
+                                          const std::vector<std::vector<int>> *deny)
+    {
+        AudienceSets a;
+        a.K = (int32_t)sets.size();
+        if (weights && weights->size() != sets.size()) throw std::invalid_argument("audience sets: one weight list per set");
+        if (deny && deny->size() != sets.size()) throw std::invalid_argument("audience sets: one deny list per set");
+        for (EdgeType t : exclEdgeTypes) a.mask |= 1u << (unsigned)t;
+        a.sp.assign(1, 0);
+        a.dp.assign(1, 0);
+        for (size_t k = 0; k < sets.size(); ++k) {
+            if (weights && (*weights)[k].size() != sets[k].size()) throw std::invalid_argument("audience sets: one weight per member");
+            a.si.insert(a.si.end(), sets[k].begin(), sets[k].end());
+            if (weights) a.sw.insert(a.sw.end(), (*weights)[k].begin(), (*weights)[k].end());
+            a.sp.push_back((int64_t)a.si.size());
+            if (deny) a.di.insert(a.di.end(), (*deny)[k].begin(), (*deny)[k].end());
+            a.dp.push_back((int64_t)a.di.size());
+        }
+        if (pool) { a.nPool = (int32_t)pool->size(); a.pool.assign(pool->begin(), pool->end()); }
+        a.si.push_back(0); a.sw.push_back(0.0); a.pool.push_back(0); a.di.push_back(0);
+        return a;
+    }
+
     Graph &graph_;
 };
 

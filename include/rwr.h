@@ -678,11 +678,78 @@ int32_t rwr_recommend_explained_batch(rwr_graph *g, const int32_t *seeds, int32_
  *     [1, 1024] (RWR_E_RANGE); n_iter < 0 (RWR_E_INVALID); cand_type outside [-1, 255] or a mask bit beyond the edge types
  *     (RWR_E_INVALID); the domain of the Recommendation entries -- a graph with a negative or non-finite normalised weight,
  *     or d outside [0, 1] (RWR_E_UNSUPPORTED); then K == 0 succeeds and touches nothing.  A refused call writes nothing.
- *   - Not here: duals of the restart-vector entries; Hits / average precision of audiences; a pool of seeds. */
+ *   - Answered by rwr_recommend_audience_set_batch below: the duals of the restart-vector entries (weighted target sets), a
+ *     pool of seeds and deny lists; Hits / average precision of audiences follow on the host from its positions entry.  Not
+ *     here or there: a cap per group of seeds; negative weights. */
 int32_t rwr_recommend_audience_batch(rwr_graph *g, int32_t K, const int32_t *targets, float d, int32_t n_iter,
                                      int32_t cand_type, uint32_t etype_mask, int32_t exclude_self, int32_t top_n,
                                      int64_t *out_id, double *out_score, int32_t *out_node /* K x top_n, may be NULL */,
                                      int32_t *out_count);
+
+/* The audience of a weighted target SET -- an addition: a campaign, an author's items of today, a topic.  Set k is the
+ * members set_idx[set_ptr[k] .. set_ptr[k + 1]) (node indices in [0, n), any order, any node type) with the weights set_w
+ * beside them (> 0; set_w == NULL: every weight 1.0).  List k ranks the nodes s of cand_type (-1: of any type) by
+ *     S_k[s] ~ sum over the distinct members v of set k of a_v * x_T^(s)[v],
+ * x_T^(s) the rank row rwr_model_run(g, s, (double)d, RWR_RUN_ITERATIONS, n_iter, ...) returns: the dual of the
+ * restart-vector walks.  The reverse walk is linear in its start and the restart mass does not depend on the target, so a
+ * set costs the n_iter reverse steps of one target, started from sum_v a_v e_v.
+ *   - A member that repeats in its set has its weights added on the host, in list order, before anything reaches the device
+ *     (a_v above is that sum).  A node may belong to several sets, and a set may repeat in the batch.
+ *   - Left out of list k: every s that has a raw link of a masked edge type to ANY member of set k (the mask test is
+ *     rwr_recommend_audience_batch's); with exclude_members the members of set k themselves; the rows of deny list k
+ *     (deny_idx[deny_ptr[k] .. deny_ptr[k + 1]), node indices; deny_ptr == NULL: none); and with n_pool >= 0 every node outside
+ *     pool_idx[0 .. n_pool) -- node indices in any order, duplicates allowed, ONE pool for the whole call, intersected with
+ *     cand_type as in rwr_recommend_filtered_batch; n_pool == 0 gives empty lists, n_pool < 0 means no pool.
+ *   - The order, the K x top_n tables, out_node (may be NULL) and top_n in [1, 1024] are rwr_recommend_audience_batch's.
+ *   - (a) One-member sets of weight 1.0 without pool and deny lists return bitwise what rwr_recommend_audience_batch returns
+ *     for those targets -- ids, scores, nodes, counts -- with exclude_members in the place of exclude_self.
+ *   - (b) Determinism: list k does not depend on K or on the rest of the batch, and the same call gives the same arrays
+ *     twice -- no floating-point atomics.  A weight that is a power of two scales a one-member list's scores exactly.
+ *   - (c) Scores do not depend on the pool or the deny lists: a narrowed list is bitwise the whole list with those rows
+ *     struck out.
+ *   - (d) Tolerance: |S - F| <= tol_rel * F for F = sum_v a_v x_T^(s)[v] summed in double, with
+ *         tol_rel = 8 * (n_iter + 1) * (n + L + m + 8) * 2^-53 / d,   L as above, m = the largest set's size
+ *     (a reverse step sums what it summed for one target; F adds m roundings of terms >= 0).  Where every forward addend is
+ *     +0.0 the score is +0.0.
+ *   - (e) Fixed n_iter >= 0 only, and the domain of rwr_recommend_audience_batch.  Weights are finite and in [2^-256, 2^256]:
+ *     scores are <= n * (the sum of a set's weights), so none overflows.
+ *   - Refusals, in this order: g NULL or a poisoned handle (RWR_E_INVALID); K < 0, or with K > 0 a NULL set_ptr, out_id,
+ *     out_score or out_count (RWR_E_INVALID); the sets -- set_ptr[0] != 0, set_ptr decreasing, an empty set (the message
+ *     names k), a NULL set_idx (all RWR_E_INVALID), then the first member outside [0, n) or weight that is not finite or
+ *     outside [2^-256, 2^256] (RWR_E_RANGE, the message names k and the position in the set); top_n outside [1, 1024]
+ *     (RWR_E_RANGE); n_iter < 0 (RWR_E_INVALID); cand_type outside [-1, 255] or a mask bit beyond the edge types
+ *     (RWR_E_INVALID); n_pool > 0 with a NULL pool_idx (RWR_E_INVALID), a pool index outside [0, n) (RWR_E_RANGE); the deny
+ *     lists as rwr_recommend_filtered_batch reports them; the domain (RWR_E_UNSUPPORTED); then K == 0 succeeds and touches
+ *     nothing.  A refused call writes nothing.
+ *   - Not here: a cache of the restart mass per handle; Hits / average precision as one device sum (the positions below give
+ *     every metric on the host); a cap per group of seeds; negative weights. */
+int32_t rwr_recommend_audience_set_batch(rwr_graph *g, int32_t K,
+                                         const int64_t *set_ptr /* K + 1 */, const int32_t *set_idx,
+                                         const double *set_w /* may be NULL: all 1.0 */,
+                                         float d, int32_t n_iter, int32_t cand_type, uint32_t etype_mask, int32_t exclude_members,
+                                         int32_t n_pool /* -1: no pool */, const int32_t *pool_idx,
+                                         const int64_t *deny_ptr /* K + 1, may be NULL */, const int32_t *deny_idx,
+                                         int32_t top_n, int64_t *out_id, double *out_score,
+                                         int32_t *out_node /* K x top_n, may be NULL */, int32_t *out_count);
+/* ... and the positions and scores of test ids in the WHOLE audience lists: rwr_recommend_filtered_positions_batch's
+ * semantics over the lists rwr_recommend_audience_set_batch defines, not cut by any top_n.  For test id
+ * test_ids[test_ptr[k] + j], out_pos holds the 0-based index of the first entry of list k with that id and out_score that
+ * entry's score, bitwise the list's; an id the list does not hold (excluded, denied, outside the pool, of another type, carried
+ * by no node) answers -1 / +0.0.  out_len[k] is the list's length.  A test id may repeat; a test set may be empty.
+ *   - Refusals, in this order: those of rwr_recommend_audience_set_batch up to and including the deny lists, without the
+ *     list tables and top_n; the test sets as rwr_recommend_filtered_positions_batch reports them (a NULL test_ptr or out_pos,
+ *     test_ptr[0] != 0, test_ptr decreasing, a NULL test_ids: RWR_E_INVALID; a set of more than INT32_MAX ids:
+ *     RWR_E_UNSUPPORTED); the domain; then K == 0 succeeds.  A refused call writes nothing. */
+int32_t rwr_recommend_audience_set_positions_batch(rwr_graph *g, int32_t K,
+                                                   const int64_t *set_ptr /* K + 1 */, const int32_t *set_idx,
+                                                   const double *set_w /* may be NULL: all 1.0 */,
+                                                   float d, int32_t n_iter, int32_t cand_type, uint32_t etype_mask,
+                                                   int32_t exclude_members,
+                                                   int32_t n_pool /* -1: no pool */, const int32_t *pool_idx,
+                                                   const int64_t *deny_ptr /* K + 1, may be NULL */, const int32_t *deny_idx,
+                                                   const int64_t *test_ptr /* K + 1 */, const int64_t *test_ids,
+                                                   int64_t *out_pos /* test_ptr[K] */, double *out_score /* test_ptr[K], may be NULL */,
+                                                   int64_t *out_len /* K, may be NULL */);
 
 /* ---- Model ---------------------------------------------------------------------------
  * Backs the public class Model: ctor (Model.cs:33-50 personalised, seed >= 0;

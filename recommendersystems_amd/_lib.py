@@ -28,7 +28,7 @@ EXPORTS = [
     "rwr_recommend_typed_positions_batch", "rwr_recommend_restart_typed_positions_batch",
     "rwr_recommend_filtered_batch", "rwr_recommend_filtered_positions_batch",
     "rwr_recommend_capped_batch", "rwr_recommend_capped_positions_batch", "rwr_recommend_explained_batch",
-    "rwr_recommend_audience_batch",
+    "rwr_recommend_audience_batch", "rwr_recommend_audience_set_batch", "rwr_recommend_audience_set_positions_batch",
     "rwr_part_begin", "rwr_part_step", "rwr_part_local_step", "rwr_part_finish_step", "rwr_part_rank",
     "rwr_get_stats", "rwr_reset_stats",
 ]
@@ -157,6 +157,16 @@ def load():
     lib.rwr_recommend_audience_batch.restype = C.c_int32
     lib.rwr_recommend_audience_batch.argtypes = [C.c_void_p, C.c_int32, p(C.c_int32), C.c_float, C.c_int32, C.c_int32, C.c_uint32,
                                                  C.c_int32, C.c_int32, p(C.c_int64), p(C.c_double), p(C.c_int32), p(C.c_int32)]
+    lib.rwr_recommend_audience_set_batch.restype = C.c_int32
+    lib.rwr_recommend_audience_set_batch.argtypes = [C.c_void_p, C.c_int32, p(C.c_int64), p(C.c_int32), p(C.c_double), C.c_float,
+                                                     C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, p(C.c_int32),
+                                                     p(C.c_int64), p(C.c_int32), C.c_int32, p(C.c_int64), p(C.c_double),
+                                                     p(C.c_int32), p(C.c_int32)]
+    lib.rwr_recommend_audience_set_positions_batch.restype = C.c_int32
+    lib.rwr_recommend_audience_set_positions_batch.argtypes = [C.c_void_p, C.c_int32, p(C.c_int64), p(C.c_int32), p(C.c_double),
+                                                               C.c_float, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_int32,
+                                                               p(C.c_int32), p(C.c_int64), p(C.c_int32), p(C.c_int64), p(C.c_int64),
+                                                               p(C.c_int64), p(C.c_double), p(C.c_int64)]
     lib.rwr_recommend_restart_typed_positions_batch.restype = C.c_int32
     lib.rwr_recommend_restart_typed_positions_batch.argtypes = [C.c_void_p, C.c_int32, p(C.c_int64), p(C.c_int32), p(C.c_double),
                                                                 p(C.c_int32), p(C.c_int64), p(C.c_int32), C.c_double, C.c_int32,

@@ -506,11 +506,60 @@ int32_t rwr_recommend_audience_batch(rwr_graph *g, int32_t K, const int32_t *tar
     }
     RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
     if (K == 0) return RWR_OK;
+    // the same body as the set entries: set k = {targets[k]}, weight 1.0, no pool, no deny lists
     // Recommender.cs:14,16 -> Model.cs:33: the float is widened to double
     return bound(who, g, [&] {
-        return audience_body(g, K, targets, (double)d, n_iter, cand_type, etype_mask, exclude_self, top_n, out_id, out_score, out_node,
-                             out_count, who);
+        std::vector<int64_t> set_ptr((size_t)K + 1);
+        for (int32_t k = 0; k <= K; ++k) set_ptr[(size_t)k] = k;
+        AudCall call;
+        call.K = K, call.set_ptr = set_ptr.data(), call.set_idx = targets, call.n_iter = n_iter, call.cand_type = cand_type;
+        call.etype_mask = etype_mask, call.exclude_members = exclude_self;
+        call.top_n = top_n, call.out_id = out_id, call.out_score = out_score, call.out_node = out_node, call.out_count = out_count;
+        return audience_body(g, call, (double)d, who);
     });
+}
+
+// The audiences of K weighted target sets (audience.hip), for both destinations.  The refusals in rwr.h's
+// order: the handle, audience_set_plan.h's ladder -- which also words every refusal --, the domain, and only then the no-op
+static int32_t audience_set_entry(const char *who, rwr_graph *g, const AudCall &call, float d)
+{
+    g_err[0] = 0;
+    const int32_t n = g ? g->n : 0;
+    if (g && g->poisoned) return bound(who, g, [] { return (int32_t)RWR_OK; });   // (bound words the refusal of such a handle)
+    const AudStatus st = audience_set_status(who, audience_set_check(call, g != nullptr, n), call, n);
+    if (st.status != RWR_OK) { set_error("%s", st.text); return st.status; }
+    RWR_TRY(check_ranked_domain(who, g, (double)d, "rwr_model_run_batch"));
+    if (call.K == 0) return RWR_OK;
+    return bound(who, g, [&] { return audience_body(g, call, (double)d, who); });
+}
+
+int32_t rwr_recommend_audience_set_batch(rwr_graph *g, int32_t K, const int64_t *set_ptr, const int32_t *set_idx, const double *set_w,
+                                         float d, int32_t n_iter, int32_t cand_type, uint32_t etype_mask, int32_t exclude_members,
+                                         int32_t n_pool, const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx,
+                                         int32_t top_n, int64_t *out_id, double *out_score, int32_t *out_node, int32_t *out_count)
+{
+    AudCall c;
+    c.K = K, c.set_ptr = set_ptr, c.set_idx = set_idx, c.set_w = set_w, c.n_iter = n_iter, c.cand_type = cand_type;
+    c.etype_mask = etype_mask, c.exclude_members = exclude_members, c.n_pool = n_pool, c.pool_idx = pool_idx;
+    c.deny_ptr = deny_ptr, c.deny_idx = deny_idx;
+    c.top_n = top_n, c.out_id = out_id, c.out_score = out_score, c.out_node = out_node, c.out_count = out_count;
+    return audience_set_entry("rwr_recommend_audience_set_batch", g, c, d);
+}
+
+int32_t rwr_recommend_audience_set_positions_batch(rwr_graph *g, int32_t K, const int64_t *set_ptr, const int32_t *set_idx,
+                                                   const double *set_w, float d, int32_t n_iter, int32_t cand_type,
+                                                   uint32_t etype_mask, int32_t exclude_members, int32_t n_pool,
+                                                   const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx,
+                                                   const int64_t *test_ptr, const int64_t *test_ids, int64_t *out_pos,
+                                                   double *out_score, int64_t *out_len)
+{
+    AudCall c;
+    c.K = K, c.set_ptr = set_ptr, c.set_idx = set_idx, c.set_w = set_w, c.n_iter = n_iter, c.cand_type = cand_type;
+    c.etype_mask = etype_mask, c.exclude_members = exclude_members, c.n_pool = n_pool, c.pool_idx = pool_idx;
+    c.deny_ptr = deny_ptr, c.deny_idx = deny_idx;
+    c.dest = AUD_POSITIONS;
+    c.test_ptr = test_ptr, c.test_ids = test_ids, c.out_pos = out_pos, c.out_score = out_score, c.out_len = out_len;
+    return audience_set_entry("rwr_recommend_audience_set_positions_batch", g, c, d);
 }
 
 int32_t rwr_recommend(rwr_graph *g, int32_t seed, float d, int32_t n_iter, int32_t top_n, int64_t *out_id,

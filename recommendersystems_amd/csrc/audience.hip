@@ -17,9 +17,15 @@
 // Arithmetic: every addend is >= 0; a row's addends are summed in list order, each as one fma; no floating-point atomics.  A
 // column's values depend on its target, d, T and the graph alone -- not on its lane, its tile, G or the batch.  The result
 // is NOT bitwise the forward walk's (the addends arrive in another order): rwr.h states the derived tolerance.
+//
+// Weighted target sets (rwr_recommend_audience_set_batch and its positions entry): the walk is linear in its
+// start and rho does not depend on the target, so set k = {(v, a_v)} is the same T steps from g_0 = sum_v a_v e_v
+// (k_rev_init_sets, from audience_set_plan.h's merged pairs).  The one body runs an AudCall: sets, pool, deny lists and the
+// list or positions destination; rwr_recommend_audience_batch fills it with one-member unit sets.
 #include "audience.h"
 
 #include "audience_plan.h"
+#include "audience_set_plan.h"
 #include "explain.h"
 #include "filter.h"
 #include "iterate.h"
@@ -150,15 +156,18 @@ __global__ __launch_bounds__(256) void k_rev_join(int32_t n, int G, int tg, int3
     gout[at] = c1 * acc;
 }
 
-// g_0 of a group: 1 at (target row, slot's column) of every live slot; the matrix was cleared
-__global__ __launch_bounds__(64) void k_rev_init(int32_t n, int G, int nslots, const int32_t *__restrict__ slot_target,
-                                                 double *__restrict__ g0)
+// g_0 of a group: the merged weight at (member row, slot's column) of every (slot, member) pair of the group
+// (audience_set_plan.h: aud_set_pairs), one thread per pair; the matrix was cleared.  The pairs' cells are distinct after the
+// merge, so a store serves and no order matters.  A one-member unit set stores the 1.0 a single target's column starts from.
+__global__ __launch_bounds__(256) void k_rev_init_sets(int32_t n, int G, int nslots, int32_t npairs, const int32_t *__restrict__ pair_slot,
+                                                       const int32_t *__restrict__ pair_row, const double *__restrict__ pair_w,
+                                                       double *__restrict__ g0)
 {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nslots) return;
-    const int32_t v = slot_target[q];
-    if (v < 0 || v >= n) return;
-    g0[(size_t)(q / G) * (size_t)n * G + (size_t)v * G + (q % G)] = 1.0;
+    const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= npairs) return;
+    const int32_t q = pair_slot[j], v = pair_row[j];
+    if (q < 0 || q >= nslots || v < 0 || v >= n) return;         // (the plan names slots of the group and rows of [0, n) only)
+    g0[(size_t)(q / G) * (size_t)n * G + (size_t)v * G + (q % G)] = pair_w[j];
 }
 
 // after the last step: S += n * g_T
@@ -266,32 +275,40 @@ int32_t rev_step(rwr_graph *g, int G, int tg, const LongRows &L, const double *g
 
 }  // namespace
 
-int32_t audience_body(rwr_graph *g, int32_t K, const int32_t *targets, double d, int32_t n_iter, int32_t cand_type,
-                      uint32_t etype_mask, int32_t exclude_self, int32_t top_n, int64_t *ids, double *scores, int32_t *nodes,
-                      int32_t *counts, const char *who)
+int32_t audience_body(rwr_graph *g, const AudCall &call, double d, const char *who)
 {
     const double t_begin = now_ms();
-    const int32_t n = g->n, T = n_iter;
+    const int32_t n = g->n, T = call.n_iter, K = call.K;
     const double c1 = 1 - d, nn = (double)n;
+    const uint32_t etype_mask = call.etype_mask;
     hipStream_t s = g->stream;
     // (the end and what it points to are declared before idle: ranked_end.h's lifetime rule; so is every scratch buffer)
     WhyEnd why;                                                  // no reasons (T = 0, n_why = 0): only the entries' rows
-    why.nodes = nodes;
+    why.nodes = call.out_node;
+    PosEnd pe;                                                   // (set up as typed.hip sets up the filtered positions entry's)
+    pe.ev.test_ptr = call.test_ptr, pe.ev.test_ids = call.test_ids;
+    pe.pos_out = call.out_pos, pe.score_out = call.out_score, pe.list_len = call.out_len;
     RankedEnd end;
     end.who = who;
-    end.top_n = top_n, end.ids = ids, end.scores = scores, end.counts = counts;
-    if (nodes) end.why = &why;
+    if (call.dest == AUD_LISTS) {
+        end.top_n = call.top_n, end.ids = call.out_id, end.scores = call.out_score, end.counts = call.out_count;
+        if (call.out_node) end.why = &why;
+    } else {
+        end.pos = &pe;
+    }
+    end.deny_ptr = call.deny_ptr, end.deny_idx = call.deny_idx;
     Profile prof(g);
     DevBuf<int32_t> own_rows;
     DevBuf<double> rho, h;
     LongRows L;
     DevBuf<uint32_t> t_bitmap;
-    DevBuf<int32_t> t_node, t_ptr, t_slot;
-    if (cand_type == FILTER_ANY_TYPE) {
-        RWR_TRY(filter_rows_build(g, cand_type, -1, nullptr, own_rows, &end.nrows, prof));
+    DevBuf<int32_t> t_node, t_ptr, t_slot, p_slot, p_row;
+    DevBuf<double> p_w;
+    if (call.n_pool >= 0 || call.cand_type == FILTER_ANY_TYPE) {
+        RWR_TRY(filter_rows_build(g, call.cand_type, call.n_pool, call.pool_idx, own_rows, &end.nrows, prof));
         end.rows = own_rows.p;
     } else {
-        RWR_TRY(cand_rows_get(g, cand_type, &end.rows, &end.nrows));
+        RWR_TRY(cand_rows_get(g, call.cand_type, &end.rows, &end.nrows));
     }
 
     // the long rows of the current raw lists, and the tables of rho and h, before the workspace is sized from what is free
@@ -311,11 +328,17 @@ int32_t audience_body(rwr_graph *g, int32_t K, const int32_t *targets, double d,
     RWR_TRY(ensure_workspace(g, G, K, &TG, g->vf ? 0 : 1));
     double *S = g->X.p, *ga = g->Y.p, *gb = g->vf ? g->Z0.p : g->cs_diff.p;
     const int ntiles = (int)cdiv((size_t)K, (size_t)G);
-    std::vector<int32_t> slot_k, slot_target;
-    RWR_TRY(upload_seed_slots(g, targets, K, G, &slot_k, &slot_target));
-    end.members = exclude_self != 0, end.slot_member = g->d_seeds.p;   // (the target's own row, named by slot; no sets, no deny lists)
+    // the sets are dealt to the slots by their first members (a column's values do not depend on its slot)
+    std::vector<int32_t> slot_k, first_member((size_t)K);
+    for (int32_t k = 0; k < K; ++k) first_member[(size_t)k] = call.set_idx[call.set_ptr[k]];
+    RWR_TRY(upload_seed_slots(g, first_member.data(), K, G, &slot_k));
+    // the members' own rows: the end's (slot, member) pairs over the caller's sets; the in-links are marked here, so its mask is 0
+    end.set_ptr = call.set_ptr, end.set_idx = call.set_idx, end.mask = 0, end.members = call.exclude_members != 0;
     // (a host vector that is uploaded outlives the stream's work, like the device buffers)
-    const AudTargets tt = etype_mask != 0 ? aud_targets(slot_target.size(), slot_target.data(), (size_t)TG * G) : AudTargets{};
+    const AudSets merged = aud_set_merge(K, call.set_ptr, call.set_idx, call.set_w);
+    const AudSetPairs pairs = aud_set_pairs(merged, slot_k.size(), slot_k.data(), (size_t)TG * G);
+    const AudTargets tt = etype_mask != 0 ? aud_set_targets(merged, slot_k.size(), slot_k.data(), (size_t)TG * G) : AudTargets{};
+    if (pairs.slot.size() > 0x7FFFFFFFull) { set_error("%s: too many set members", who); return RWR_E_UNSUPPORTED; }
     StreamsIdle idle{g};
     RWR_TRY(end.prepare(g, K, slot_k, (size_t)TG * G, s));
 
@@ -327,6 +350,9 @@ int32_t audience_body(rwr_graph *g, int32_t K, const int32_t *targets, double d,
         RWR_TRY(upload_vec(L.p1, plan.piece_p1, s));
         RWR_TRY(L.part.alloc((size_t)aud_part_elems((uint64_t)L.npieces, TG, G)));
     }
+    RWR_TRY(upload_vec(p_slot, pairs.slot, s));
+    RWR_TRY(upload_vec(p_row, pairs.row, s));
+    RWR_TRY(upload_vec(p_w, pairs.w, s));
     if (etype_mask != 0) {
         RWR_TRY(upload_vec(t_node, tt.node, s));
         RWR_TRY(upload_vec(t_ptr, tt.ptr, s));
@@ -351,7 +377,10 @@ int32_t audience_body(rwr_graph *g, int32_t K, const int32_t *targets, double d,
         hipEvent_t i0; RWR_TRY(prof.record(i0, s));
         RWR_HIP(hipMemsetAsync(S, 0, elems * sizeof(double), s));
         RWR_HIP(hipMemsetAsync(ga, 0, elems * sizeof(double), s));
-        hipLaunchKernelGGL(k_rev_init, dim3(cdiv((size_t)tg * G, 64)), dim3(64), 0, s, n, G, tg * G, g->d_seeds.p + q0, ga);
+        const int64_t m0 = pairs.group_off[(size_t)grp], npairs = pairs.group_off[(size_t)grp + 1] - m0;
+        if (npairs > 0)
+            hipLaunchKernelGGL(k_rev_init_sets, dim3(cdiv((size_t)npairs, 256)), dim3(256), 0, s, n, G, tg * G, (int32_t)npairs,
+                               p_slot.p + m0, p_row.p + m0, p_w.p + m0, ga);
         double *cur = ga, *nxt = gb;
         for (int32_t j = 0; j < T; ++j) {                        // S += rho_{T-1-j} * g_j, g_{j+1} = B(g_j)
             hipEvent_t a; RWR_TRY(prof.record(a, s));

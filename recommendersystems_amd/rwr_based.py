@@ -1242,6 +1242,89 @@ class Recommender:
         c = int(counts[0])
         return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist()))
 
+    @staticmethod
+    def _pack_target_sets(sets, weights):
+        """K target sets as the audience set entries take them: (K, set_ptr, set_idx, set_w or None).  sets: K iterables of
+        node indices; weights: None (every weight 1.0) or K iterables parallel to the sets."""
+        members = [np.ascontiguousarray(m if isinstance(m, np.ndarray) else list(m), dtype=np.int32).reshape(-1) for m in sets]
+        K = len(members)
+        sp = np.zeros(K + 1, dtype=np.int64)
+        sp[1:] = np.cumsum([len(m) for m in members])
+        si = np.ascontiguousarray(np.concatenate(members + [np.zeros(0, dtype=np.int32)]), dtype=np.int32)
+        if si.shape[0] == 0:
+            si = np.zeros(1, dtype=np.int32)
+        sw = None
+        if weights is not None:
+            ws = [np.ascontiguousarray(w if isinstance(w, np.ndarray) else list(w), dtype=np.float64).reshape(-1) for w in weights]
+            if len(ws) != K or any(len(w) != len(m) for w, m in zip(ws, members)):
+                raise ValueError("weights must hold one weight per member of every set")
+            sw = np.ascontiguousarray(np.concatenate(ws + [np.zeros(0)]), dtype=np.float64)
+            if sw.shape[0] == 0:
+                sw = np.zeros(1, dtype=np.float64)
+        return K, sp, si, sw
+
+    @staticmethod
+    def _edge_mask(etype_mask):
+        if isinstance(etype_mask, (int, np.integer)):
+            return int(etype_mask)
+        mask = 0
+        for t in etype_mask:
+            mask |= 1 << int(EdgeType(t))
+        return mask
+
+    def AudienceSetBatch(self, sets, d: float, n_iter: int, weights=None, cand_type=None, etype_mask=(),
+                         exclude_members: bool = False, pool=None, deny=None, top_n: int = 100):
+        """The audiences of K weighted target sets (rwr_recommend_audience_set_batch, an addition, see include/rwr.h):
+        (ids[K,top_n], scores[K,top_n], nodes[K,top_n], counts[K]).  sets: K iterables of node indices (any type, any order;
+        a member that repeats has its weights added); weights: None for 1.0 each, or K iterables parallel to the sets.  List k
+        ranks the nodes s of cand_type (None: any type) by the weighted sum of the scores a walk of n_iter steps FROM s gives
+        the members; the nodes with a raw link of a masked EdgeType to any member are left out, the members too with
+        exclude_members, the node indices of deny[k], and with a pool (an iterable of node indices, [] for an empty one)
+        every node outside it."""
+        lib = _lib.load()
+        K, sp, si, sw = self._pack_target_sets(sets, weights)
+        pc, pi, dp, di = _pack_filter(pool, deny, K)
+        top_n = int(top_n)
+        width = max(top_n, 0)
+        ids = np.zeros((K, width), dtype=np.int64)
+        sc = np.zeros((K, width), dtype=np.float64)
+        nodes = np.full((K, width), -1, dtype=np.int32)
+        counts = np.zeros(K, dtype=np.int32)
+        _lib.check(lib.rwr_recommend_audience_set_batch(
+            self.graph._handle(), K, _p(sp, C.c_int64), _p(si, C.c_int32), None if sw is None else _p(sw, C.c_double), C.c_float(d),
+            int(n_iter), -1 if cand_type is None else int(cand_type), self._edge_mask(etype_mask), 1 if exclude_members else 0, pc,
+            None if pi is None else _p(pi, C.c_int32), None if dp is None else _p(dp, C.c_int64),
+            None if di is None else _p(di, C.c_int32), top_n, _p(ids, C.c_int64), _p(sc, C.c_double), _p(nodes, C.c_int32),
+            _p(counts, C.c_int32)))
+        return ids, sc, nodes, counts
+
+    def AudienceSet(self, members, d: float, n_iter: int, weights=None, cand_type=None, etype_mask=(),
+                    exclude_members: bool = False, pool=None, deny=None, top_n: int = 100) -> List[Tuple[int, float]]:
+        """AudienceSetBatch for one set, as Recommendation returns its list: [(node id, score), ...]; deny: the set's one deny
+        list (an iterable of node indices) or None."""
+        ids, sc, _, counts = self.AudienceSetBatch([members], d, n_iter, None if weights is None else [weights], cand_type,
+                                                   etype_mask, exclude_members, pool, None if deny is None else [deny], top_n)
+        c = int(counts[0])
+        return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist()))
+
+    def AudienceSetPositionsBatch(self, sets, d: float, n_iter: int, testSets, weights=None, cand_type=None, etype_mask=(),
+                                  exclude_members: bool = False, pool=None, deny=None):
+        """The 0-based position and the score of every test id in K sets' WHOLE audience lists
+        (rwr_recommend_audience_set_positions_batch, an addition, see include/rwr.h): (positions, scores, listLen[K]) as
+        RecommendationFilteredPositionsBatch returns them, over the lists AudienceSetBatch defines.  An id the list does not
+        hold answers -1 / +0.0."""
+        lib = _lib.load()
+        K, sp, si, sw = self._pack_target_sets(sets, weights)
+        pc, pi, dp, di = _pack_filter(pool, deny, K)
+        tp, ti, pos, sc, ln = _pack_tests(testSets, K)
+        _lib.check(lib.rwr_recommend_audience_set_positions_batch(
+            self.graph._handle(), K, _p(sp, C.c_int64), _p(si, C.c_int32), None if sw is None else _p(sw, C.c_double), C.c_float(d),
+            int(n_iter), -1 if cand_type is None else int(cand_type), self._edge_mask(etype_mask), 1 if exclude_members else 0, pc,
+            None if pi is None else _p(pi, C.c_int32), None if dp is None else _p(dp, C.c_int64),
+            None if di is None else _p(di, C.c_int32), _p(tp, C.c_int64), _p(ti, C.c_int64), _p(pos, C.c_int64), _p(sc, C.c_double),
+            _p(ln, C.c_int64)))
+        return _split_tests(tp, pos), _split_tests(tp, sc), ln
+
     def RecommendationCappedPositionsBatch(self, seeds, dampingFactor: float, nIteration: int, testSets, candType=None,
                                            exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None, groupOf=None,
                                            groupCap: int = 1):
