@@ -59,6 +59,8 @@ namespace Recommenders.RWRBased {
         // the audiences of K weighted target sets (CSR: set_ptr, set_idx, set_w or null for 1.0 each), within an optional pool
         // of node indices (n_pool < 0: none) and with an optional deny list per set (Recommender.AudienceSetBatch)
         [DllImport(Lib)] public static extern int rwr_recommend_audience_set_batch(GraphHandle g, int K, long[] set_ptr, int[] set_idx, double[] set_w, float d, int n_iter, int cand_type, uint etype_mask, int exclude_members, int n_pool, int[] pool_idx, long[] deny_ptr, int[] deny_idx, int top_n, long[] out_id, double[] out_score, int[] out_node, int[] out_count);
+        // ... with top_n up to 65 536: up to 1 024 entries the same lists, beyond them their continuation (Recommender.AudienceSetLongBatch)
+        [DllImport(Lib)] public static extern int rwr_recommend_audience_set_long_batch(GraphHandle g, int K, long[] set_ptr, int[] set_idx, double[] set_w, float d, int n_iter, int cand_type, uint etype_mask, int exclude_members, int n_pool, int[] pool_idx, long[] deny_ptr, int[] deny_idx, int top_n, long[] out_id, double[] out_score, int[] out_node, int[] out_count);
         // ... and the position and score of every test id in those WHOLE lists (Recommender.AudienceSetPositionsBatch)
         [DllImport(Lib)] public static extern int rwr_recommend_audience_set_positions_batch(GraphHandle g, int K, long[] set_ptr, int[] set_idx, double[] set_w, float d, int n_iter, int cand_type, uint etype_mask, int exclude_members, int n_pool, int[] pool_idx, long[] deny_ptr, int[] deny_idx, long[] test_ptr, long[] test_ids, long[] out_pos, double[] out_score, long[] out_len);
         // the same K walks evaluated on the device: Hits and the running-precision sum (Experiment.cs:121-128) of every seed's WHOLE
@@ -92,6 +94,9 @@ namespace Recommenders.RWRBased {
             int top_n, int cand_type, uint excl_edge_mask, int exclude_self, long pool_count, int[] pool_idx, long[] deny_ptr,
             int[] deny_idx, int[] group_of, int group_cap, int n_why, long[] ids, double[] scores, int[] counts, int[] nodes,
             int[] why_src, double[] why_term, long[] why_total);
+        // the capped lists with top_n up to 65 536, ordered by score descending, id descending, node index ascending; nodes
+        // (K x top_n, may be null) receives the entries' node indices (Recommender.RecommendationLongBatch)
+        [DllImport(Lib)] public static extern int rwr_recommend_long_batch(GraphHandle g, int[] seeds, int K, float d, int n_iter, int top_n, int cand_type, uint excl_edge_mask, int exclude_self, long pool_count, int[] pool_idx, long[] deny_ptr, int[] deny_idx, int[] group_of, int group_cap, long[] ids, double[] scores, int[] counts, int[] nodes);
         // ... and the positions and scores of the test entries in the WHOLE capped lists
         [DllImport(Lib)] public static extern int rwr_recommend_capped_positions_batch(GraphHandle g, int[] seeds, int K, float d,
             int n_iter, int cand_type, uint excl_edge_mask, int exclude_self, long pool_count, int[] pool_idx, long[] deny_ptr,

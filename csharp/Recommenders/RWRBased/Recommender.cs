@@ -130,6 +130,34 @@ namespace Recommenders.RWRBased {
                                     exclEdgeTypes, excludeMembers, pool, deny == null ? null : new[] { deny }, topN)[0];
         }
 
+        // addition: AudienceSetBatch for lists of up to 65 536 entries (rwr_recommend_audience_set_long_batch): up to 1 024 entries
+        // it returns AudienceSetBatch's lists, a longer list continues them
+        public List<KeyValuePair<long, double>>[] AudienceSetLongBatch(int[][] sets, float dampingFactor, int nIteration, double[][] weights = null,
+                                                                       NodeType? candType = null, IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                       bool excludeMembers = false, int[] pool = null, int[][] deny = null,
+                                                                       int topN = 4096) {
+            if (topN < 1) throw new System.ArgumentOutOfRangeException("topN", "AudienceSetLongBatch needs topN >= 1");
+            int K = sets.Length;
+            long[] setPtr, denyPtr; int[] setIdx, denyIdx; double[] setW; uint mask;
+            PackAudienceSets(sets, weights, exclEdgeTypes, deny, out setPtr, out setIdx, out setW, out denyPtr, out denyIdx, out mask);
+            var ids = new long[(long)K * topN]; var scores = new double[(long)K * topN]; var counts = new int[K];
+            Native.Check(Native.rwr_recommend_audience_set_long_batch(graph.handle, K, setPtr, setIdx, setW, dampingFactor, nIteration, candType.HasValue ? (int)candType.Value : -1, mask, excludeMembers ? 1 : 0, pool == null ? -1 : pool.Length, pool == null || pool.Length == 0 ? new int[1] : pool, denyPtr, denyIdx, topN, ids, scores, null, counts));
+            var all = new List<KeyValuePair<long, double>>[K];
+            for (int k = 0; k < K; k++) {
+                all[k] = new List<KeyValuePair<long, double>>(counts[k]);
+                for (int q = 0; q < counts[k]; q++) all[k].Add(new KeyValuePair<long, double>(ids[(long)k * topN + q], scores[(long)k * topN + q]));
+            }
+            return all;
+        }
+
+        // ... for one set
+        public List<KeyValuePair<long, double>> AudienceSetLong(int[] members, float dampingFactor, int nIteration, double[] weights = null,
+                                                                NodeType? candType = null, IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                bool excludeMembers = false, int[] pool = null, int[] deny = null, int topN = 4096) {
+            return AudienceSetLongBatch(new[] { members }, dampingFactor, nIteration, weights == null ? null : new[] { weights }, candType,
+                                        exclEdgeTypes, excludeMembers, pool, deny == null ? null : new[] { deny }, topN)[0];
+        }
+
         // ... and the 0-based position and the score of every test id in the sets' WHOLE audience lists
         // (rwr_recommend_audience_set_positions_batch): positions[k][j] / scores[k][j] answer testSets[k][j] (-1 / +0.0: not in
         // the list), listLen[k] is list k's length
@@ -394,6 +422,43 @@ namespace Recommenders.RWRBased {
                                                                      int[] groupOf = null, int groupCap = 1) {
             return RecommendationCappedBatch(new[] { idxTargetNode }, dampingFactor, nIteration, topN, candType, exclEdgeTypes, excludeSelf,
                                              pool, deny == null ? null : new[] { deny }, groupOf, groupCap)[0];
+        }
+
+        // addition: RecommendationCappedBatch for lists of up to 65 536 entries (rwr_recommend_long_batch): candidates for a
+        // re-ranker.  The order is score descending, id descending, node index ascending; nodes[k * topN + j]: the node index of
+        // entry j of seed k (-1 behind the list's end).  Up to 1 024 entries the call is the explained call without reasons
+        public List<KeyValuePair<long, double>>[] RecommendationLongBatch(int[] seeds, float dampingFactor, int nIteration, int topN,
+                                                                          out int[] nodes, NodeType? candType = null,
+                                                                          IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                          bool excludeSelf = false, int[] pool = null,
+                                                                          int[][] deny = null, int[] groupOf = null, int groupCap = 1) {
+            if (topN < 1 || topN > 65536) throw new System.ArgumentOutOfRangeException("topN", "RecommendationLongBatch needs topN in [1, 65536]");
+            int K = seeds.Length;
+            uint mask = 0;
+            if (exclEdgeTypes != null) foreach (var t in exclEdgeTypes) mask |= 1u << (int)t;
+            long[] denyPtr; int[] denyIdx;
+            PackDeny(deny, K, out denyPtr, out denyIdx);
+            long poolCount = pool == null ? -1 : pool.Length;
+            int[] poolIdx = (pool != null && pool.Length == 0) ? new int[1] : pool;
+            var ids = new long[(long)K * topN]; var scores = new double[(long)K * topN]; var counts = new int[K];
+            nodes = new int[(long)K * topN];
+            Native.Check(Native.rwr_recommend_long_batch(graph.handle, seeds, K, dampingFactor, nIteration, topN, candType.HasValue ? (int)candType.Value : -1, mask, excludeSelf ? 1 : 0, poolCount, poolIdx, denyPtr, denyIdx, groupOf, groupCap, ids, scores, counts, nodes));
+            var all = new List<KeyValuePair<long, double>>[K];
+            for (int k = 0; k < K; k++) {
+                all[k] = new List<KeyValuePair<long, double>>(counts[k]);
+                for (int q = 0; q < counts[k]; q++) all[k].Add(new KeyValuePair<long, double>(ids[(long)k * topN + q], scores[(long)k * topN + q]));
+            }
+            return all;
+        }
+
+        // ... and for one seed (deny: its one deny list)
+        public List<KeyValuePair<long, double>> RecommendationLong(int idxTargetNode, float dampingFactor, int nIteration, int topN,
+                                                                   NodeType? candType = null, IEnumerable<EdgeType> exclEdgeTypes = null,
+                                                                   bool excludeSelf = false, int[] pool = null, int[] deny = null,
+                                                                   int[] groupOf = null, int groupCap = 1) {
+            int[] nodes;
+            return RecommendationLongBatch(new[] { idxTargetNode }, dampingFactor, nIteration, topN, out nodes, candType, exclEdgeTypes,
+                                           excludeSelf, pool, deny == null ? null : new[] { deny }, groupOf, groupCap)[0];
         }
 
         // addition: RecommendationCappedBatch with the reasons of every list entry (rwr_recommend_explained_batch).  nodes[k * topN + j]:

@@ -558,6 +558,49 @@ public:
                                 pool, deny ? &d1 : nullptr, topN)[0];
     }
 
+    // addition: audienceSetBatch for lists of up to RWR_LONG_TOP_N_MAX = 65 536 entries (rwr_recommend_audience_set_long_batch): up
+    // to 1 024 entries it returns audienceSetBatch's lists, a longer list continues them.  The arguments as there
+    std::vector<std::vector<std::pair<int64_t, double>>> audienceSetLongBatch(const std::vector<std::vector<int>> &sets, float dampingFactor,
+                                                                              int nIteration,
+                                                                              const std::vector<std::vector<double>> *weights = nullptr,
+                                                                              int candType = -1,
+                                                                              const std::vector<EdgeType> &exclEdgeTypes = {},
+                                                                              bool excludeMembers = false,
+                                                                              const std::vector<int> *pool = nullptr,
+                                                                              const std::vector<std::vector<int>> *deny = nullptr,
+                                                                              int topN = 4096,
+                                                                              std::vector<std::vector<int32_t>> *nodes = nullptr)
+    {
+        if (topN < 1) throw std::invalid_argument("audienceSetLongBatch: topN must be >= 1");
+        AudienceSets a = packAudienceSets_(sets, weights, exclEdgeTypes, pool, deny);
+        const int32_t K = a.K;
+        std::vector<int64_t> ids((size_t)K * (size_t)topN);
+        std::vector<double> scores((size_t)K * (size_t)topN);
+        std::vector<int32_t> rows((size_t)K * (size_t)topN), counts((size_t)K);
+        check(rwr_recommend_audience_set_long_batch(graph_.handle(), K, a.sp.data(), a.si.data(), weights ? a.sw.data() : nullptr, dampingFactor, nIteration, candType < 0 ? -1 : candType, a.mask, excludeMembers ? 1 : 0, a.nPool, a.pool.data(), deny ? a.dp.data() : nullptr, a.di.data(), topN, ids.data(), scores.data(), rows.data(), counts.data()));
+        std::vector<std::vector<std::pair<int64_t, double>>> out((size_t)K);
+        if (nodes) nodes->assign((size_t)K, {});
+        for (int32_t k = 0; k < K; ++k)
+            for (int32_t q = 0; q < counts[k]; ++q) {
+                out[k].emplace_back(ids[(size_t)k * (size_t)topN + q], scores[(size_t)k * (size_t)topN + q]);
+                if (nodes) (*nodes)[k].push_back(rows[(size_t)k * (size_t)topN + q]);
+            }
+        return out;
+    }
+
+    // ... for one set
+    std::vector<std::pair<int64_t, double>> audienceSetLong(const std::vector<int> &members, float dampingFactor, int nIteration,
+                                                            const std::vector<double> *weights = nullptr, int candType = -1,
+                                                            const std::vector<EdgeType> &exclEdgeTypes = {}, bool excludeMembers = false,
+                                                            const std::vector<int> *pool = nullptr, const std::vector<int> *deny = nullptr,
+                                                            int topN = 4096)
+    {
+        const std::vector<std::vector<double>> w1 = {weights ? *weights : std::vector<double>()};
+        const std::vector<std::vector<int>> d1 = {deny ? *deny : std::vector<int>()};
+        return audienceSetLongBatch({members}, dampingFactor, nIteration, weights ? &w1 : nullptr, candType, exclEdgeTypes, excludeMembers,
+                                    pool, deny ? &d1 : nullptr, topN)[0];
+    }
+
     // ... and the 0-based position and score of every test id in the sets' WHOLE audience lists
     // (rwr_recommend_audience_set_positions_batch): positions[k][j] / scores[k][j] answer testSets[k][j] (-1 / +0.0: not in the
     // list), listLen[k] is list k's length.  scores and listLen may be nullptr
@@ -628,6 +671,58 @@ public:
             for (int32_t q = 0; q < counts[k]; ++q)
                 out[k].emplace_back(ids[(size_t)k * (size_t)topN + q], scores[(size_t)k * (size_t)topN + q]);
         return out;
+    }
+
+    // addition: recommendCappedBatch for lists of up to RWR_LONG_TOP_N_MAX = 65 536 entries (rwr_recommend_long_batch): candidates
+    // for a re-ranker.  The order is score descending, id descending, node index ascending; nodes (may be nullptr) receives the
+    // entries' node indices.  Up to 1 024 entries the call is recommendExplainedBatch without reasons.  The other arguments as in
+    // recommendCappedBatch
+    std::vector<std::vector<std::pair<int64_t, double>>> recommendLongBatch(const std::vector<int> &seeds, float dampingFactor,
+                                                                            int nIteration, int topN, int candType,
+                                                                            const std::vector<EdgeType> &exclEdgeTypes,
+                                                                            bool excludeSelf, const std::vector<int32_t> *pool,
+                                                                            const std::vector<std::vector<int32_t>> *deny,
+                                                                            const std::vector<int32_t> *groupOf, int groupCap,
+                                                                            std::vector<std::vector<int32_t>> *nodes = nullptr)
+    {
+        const int32_t K = (int32_t)seeds.size();
+        if (topN < 1 || topN > RWR_LONG_TOP_N_MAX) throw std::invalid_argument("recommendLongBatch: topN must lie in [1, 65536]");
+        if (deny && deny->size() != seeds.size()) throw std::invalid_argument("recommendLongBatch: deny must hold one entry per seed");
+        uint32_t mask = 0;
+        for (EdgeType t : exclEdgeTypes) mask |= 1u << (unsigned)t;
+        std::vector<int32_t> sd(seeds.begin(), seeds.end());
+        std::vector<int64_t> dptr((size_t)K + 1, 0);
+        std::vector<int32_t> didx;
+        if (deny)
+            for (int32_t k = 0; k < K; ++k) {
+                didx.insert(didx.end(), (*deny)[(size_t)k].begin(), (*deny)[(size_t)k].end());
+                dptr[(size_t)k + 1] = (int64_t)didx.size();
+            }
+        didx.push_back(0);                                       // (at least one element behind the pointer)
+        const int32_t none = 0;
+        std::vector<int64_t> ids((size_t)K * (size_t)topN);
+        std::vector<double> scores((size_t)K * (size_t)topN);
+        std::vector<int32_t> counts((size_t)K), rows(nodes ? (size_t)K * (size_t)topN : 0);
+        check(rwr_recommend_long_batch(graph_.handle(), sd.data(), K, dampingFactor, nIteration, topN, candType < 0 ? -1 : candType, mask, excludeSelf ? 1 : 0, pool ? (int64_t)pool->size() : -1, pool ? (pool->empty() ? &none : pool->data()) : nullptr, deny ? dptr.data() : nullptr, deny ? didx.data() : nullptr, groupOf ? groupOf->data() : nullptr, groupCap, ids.data(), scores.data(), counts.data(), nodes ? rows.data() : nullptr));
+        std::vector<std::vector<std::pair<int64_t, double>>> out((size_t)K);
+        if (nodes) nodes->assign((size_t)K, {});
+        for (int32_t k = 0; k < K; ++k)
+            for (int32_t q = 0; q < counts[k]; ++q) {
+                out[k].emplace_back(ids[(size_t)k * (size_t)topN + q], scores[(size_t)k * (size_t)topN + q]);
+                if (nodes) (*nodes)[k].push_back(rows[(size_t)k * (size_t)topN + q]);
+            }
+        return out;
+    }
+
+    // ... for one seed (deny: its one deny list)
+    std::vector<std::pair<int64_t, double>> recommendLong(int idxTargetNode, float dampingFactor, int nIteration, int topN, int candType,
+                                                          const std::vector<EdgeType> &exclEdgeTypes = {}, bool excludeSelf = false,
+                                                          const std::vector<int32_t> *pool = nullptr, const std::vector<int32_t> *deny = nullptr,
+                                                          const std::vector<int32_t> *groupOf = nullptr, int groupCap = 1)
+    {
+        const std::vector<std::vector<int32_t>> d1 = {deny ? *deny : std::vector<int32_t>()};
+        return recommendLongBatch({idxTargetNode}, dampingFactor, nIteration, topN, candType, exclEdgeTypes, excludeSelf, pool,
+                                  deny ? &d1 : nullptr, groupOf, groupCap)[0];
     }
 
     // addition: recommendCappedBatch with the reasons of every list entry (rwr_recommend_explained_batch): per entry its node

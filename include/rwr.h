@@ -751,6 +751,49 @@ int32_t rwr_recommend_audience_set_positions_batch(rwr_graph *g, int32_t K,
                                                    int64_t *out_pos /* test_ptr[K] */, double *out_score /* test_ptr[K], may be NULL */,
                                                    int64_t *out_len /* K, may be NULL */);
 
+/* Ranked lists beyond 1 024 entries -- an addition: candidates for a re-ranker, a campaign's audience of 20 000 users.  The
+ * two entries below take the argument lists of rwr_recommend_capped_batch and rwr_recommend_audience_set_batch with top_n in
+ * [1, RWR_LONG_TOP_N_MAX]; no other entry changes its limit.
+ *   - rwr_recommend_long_batch: list k is the rank row rwr_model_run(g, seeds[k], (double)d, RWR_RUN_ITERATIONS, n_iter, ...)
+ *     returns, narrowed as rwr_recommend_capped_batch narrows it (cand_type, the masked links, exclude_self, the pool, deny
+ *     list k, at most group_cap entries per group) and ranked by score descending, then id descending, then node index
+ *     ascending -- a total order: ids and nodes are those of that ranking for any number of equal (score, id) pairs across
+ *     the cut, scores are bitwise the row's, and the same call gives the same arrays twice.  The tables are K x top_n;
+ *     nodes[k * top_n + j] is the node index of entry j (may be NULL); cells at j >= counts[k] hold 0 / +0.0 / -1.
+ *   - top_n <= 1024 runs rwr_recommend_explained_batch with n_why == 0 and why_total == NULL, launch for launch, and returns
+ *     that call's arrays.  Beyond, the lists are collected, sorted in runs of 4 096 entries and merged on the device; no
+ *     floating-point atomic and no integer atomic's arrival order decides an entry.
+ *   - Refusals of rwr_recommend_long_batch, in this order: everything rwr_recommend_capped_batch reports up to and including
+ *     group_cap < 1 (RWR_E_INVALID / RWR_E_RANGE as there); the limits -- top_n > RWR_LONG_TOP_N_MAX, then group_cap >
+ *     RWR_GROUP_CAP_MAX (both RWR_E_UNSUPPORTED with the limit in the message); the domain.  K == 0 succeeds after the graph
+ *     and K are looked at, as there.  A refused call writes nothing.
+ *   - rwr_recommend_audience_set_long_batch: rwr_recommend_audience_set_batch with top_n in [1, RWR_LONG_TOP_N_MAX] -- its
+ *     sets, weights, exclusions, pool, deny lists, order, tolerance (d) and determinism (b), (c).  top_n <= 1024 returns that
+ *     entry's arrays through the same body; a longer list continues it: its first 1 024 entries are bitwise that entry's
+ *     list of top_n = 1024.  Refusals: that entry's, in its order, with top_n outside [1, RWR_LONG_TOP_N_MAX] (RWR_E_RANGE)
+ *     in the place of its top_n step.
+ *   - Memory: beside the K x top_n tables the device holds, per pass over some tiles of a tile group, two buffers of
+ *     (top_n - 1 + 3072) entries of 24 bytes per list; a group whose buffers would pass 1 GiB is ranked tile by tile.  Running
+ *     out of device memory is RWR_E_NOMEM.
+ *   - Not here: long lists of the restart-vector walks; reasons (n_why > 0) for long lists; lists longer than
+ *     RWR_LONG_TOP_N_MAX, which the positions entries answer; any change to rwr_recommend_batch's own sort path. */
+#define RWR_LONG_TOP_N_MAX 65536
+int32_t rwr_recommend_long_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                 int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self,
+                                 int64_t pool_count, const int32_t *pool_idx,
+                                 const int64_t *deny_ptr /* K + 1, may be NULL */, const int32_t *deny_idx,
+                                 const int32_t *group_of /* n, may be NULL */, int32_t group_cap,
+                                 int64_t *ids, double *scores, int32_t *counts,
+                                 int32_t *nodes /* K x top_n, may be NULL */);
+int32_t rwr_recommend_audience_set_long_batch(rwr_graph *g, int32_t K,
+                                              const int64_t *set_ptr /* K + 1 */, const int32_t *set_idx,
+                                              const double *set_w /* may be NULL: all 1.0 */,
+                                              float d, int32_t n_iter, int32_t cand_type, uint32_t etype_mask, int32_t exclude_members,
+                                              int32_t n_pool /* -1: no pool */, const int32_t *pool_idx,
+                                              const int64_t *deny_ptr /* K + 1, may be NULL */, const int32_t *deny_idx,
+                                              int32_t top_n, int64_t *out_id, double *out_score,
+                                              int32_t *out_node /* K x top_n, may be NULL */, int32_t *out_count);
+
 /* ---- Model ---------------------------------------------------------------------------
  * Backs the public class Model: ctor (Model.cs:33-50 personalised, seed >= 0;
  * Model.cs:14-31 global, seed == -1), run(int) / run(double) / run() (Model.cs:68-73,

@@ -16,6 +16,7 @@ RWR_MODE_EXACT = 0
 RWR_RUN_ITERATIONS, RWR_RUN_THRESHOLD, RWR_RUN_DEFAULT_THRESHOLD = 0, 1, 2
 RWR_GROUP_CAP_MAX = 8          # include/rwr.h: entries per group of the capped entries at most
 RWR_WHY_MAX = 8                # include/rwr.h: reasons per entry of the explained entry at most
+RWR_LONG_TOP_N_MAX = 65536     # include/rwr.h: entries per list of the long entries at most
 
 # every symbol include/rwr.h declares (tests check that the library exports all of them)
 EXPORTS = [
@@ -29,6 +30,7 @@ EXPORTS = [
     "rwr_recommend_filtered_batch", "rwr_recommend_filtered_positions_batch",
     "rwr_recommend_capped_batch", "rwr_recommend_capped_positions_batch", "rwr_recommend_explained_batch",
     "rwr_recommend_audience_batch", "rwr_recommend_audience_set_batch", "rwr_recommend_audience_set_positions_batch",
+    "rwr_recommend_long_batch", "rwr_recommend_audience_set_long_batch",
     "rwr_part_begin", "rwr_part_step", "rwr_part_local_step", "rwr_part_finish_step", "rwr_part_rank",
     "rwr_get_stats", "rwr_reset_stats",
 ]
@@ -167,6 +169,12 @@ def load():
                                                                C.c_float, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_int32,
                                                                p(C.c_int32), p(C.c_int64), p(C.c_int32), p(C.c_int64), p(C.c_int64),
                                                                p(C.c_int64), p(C.c_double), p(C.c_int64)]
+    lib.rwr_recommend_long_batch.restype = C.c_int32
+    lib.rwr_recommend_long_batch.argtypes = [C.c_void_p, p(C.c_int32), C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_uint32, C.c_int32, C.c_int64, p(C.c_int32), p(C.c_int64), p(C.c_int32),
+                                             p(C.c_int32), C.c_int32, p(C.c_int64), p(C.c_double), p(C.c_int32), p(C.c_int32)]
+    lib.rwr_recommend_audience_set_long_batch.restype = C.c_int32
+    lib.rwr_recommend_audience_set_long_batch.argtypes = list(lib.rwr_recommend_audience_set_batch.argtypes)
     lib.rwr_recommend_restart_typed_positions_batch.restype = C.c_int32
     lib.rwr_recommend_restart_typed_positions_batch.argtypes = [C.c_void_p, C.c_int32, p(C.c_int64), p(C.c_int32), p(C.c_double),
                                                                 p(C.c_int32), p(C.c_int64), p(C.c_int32), C.c_double, C.c_int32,

@@ -11,6 +11,7 @@
 #include "eval_plan.h"
 #include "exclude_plan.h"
 #include "handle.h"
+#include "long_plan.h"
 #include "rank.h"
 #include "typed_call.h"
 
@@ -560,6 +561,37 @@ int32_t rwr_recommend_audience_set_positions_batch(rwr_graph *g, int32_t K, cons
     c.dest = AUD_POSITIONS;
     c.test_ptr = test_ptr, c.test_ids = test_ids, c.out_pos = out_pos, c.out_score = out_score, c.out_len = out_len;
     return audience_set_entry("rwr_recommend_audience_set_positions_batch", g, c, d);
+}
+
+// Lists of up to RWR_LONG_TOP_N_MAX entries (long_list.hip): the explained entry's call without reasons and the
+// audience set entry's call, each with long_plan.h's top_n limit in its ladder; the drivers name the long destination from
+// top_n alone
+int32_t rwr_recommend_long_batch(rwr_graph *g, const int32_t *seeds, int32_t K, float d, int32_t n_iter, int32_t top_n,
+                                 int32_t cand_type, uint32_t excl_edge_mask, int32_t exclude_self, int64_t pool_count,
+                                 const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx, const int32_t *group_of,
+                                 int32_t group_cap, int64_t *ids, double *scores, int32_t *counts, int32_t *nodes)
+{
+    TypedCall c;
+    c.seeds = seeds, c.K = K, c.cand_type = cand_type, c.excl_edge_mask = excl_edge_mask, c.exclude_self = exclude_self;
+    c.pool_count = pool_count, c.pool_idx = pool_idx, c.deny_ptr = deny_ptr, c.deny_idx = deny_idx;
+    c.group_of = group_of, c.group_cap = group_cap;
+    c.top_n = top_n, c.ids = ids, c.scores = scores, c.counts = counts, c.nodes = nodes;
+    long_call_fill(c);
+    return typed_entry("rwr_recommend_long_batch", g, c, d, n_iter);
+}
+
+int32_t rwr_recommend_audience_set_long_batch(rwr_graph *g, int32_t K, const int64_t *set_ptr, const int32_t *set_idx, const double *set_w,
+                                              float d, int32_t n_iter, int32_t cand_type, uint32_t etype_mask, int32_t exclude_members,
+                                              int32_t n_pool, const int32_t *pool_idx, const int64_t *deny_ptr, const int32_t *deny_idx,
+                                              int32_t top_n, int64_t *out_id, double *out_score, int32_t *out_node, int32_t *out_count)
+{
+    AudCall c;
+    c.K = K, c.set_ptr = set_ptr, c.set_idx = set_idx, c.set_w = set_w, c.n_iter = n_iter, c.cand_type = cand_type;
+    c.etype_mask = etype_mask, c.exclude_members = exclude_members, c.n_pool = n_pool, c.pool_idx = pool_idx;
+    c.deny_ptr = deny_ptr, c.deny_idx = deny_idx;
+    c.top_n = top_n, c.out_id = out_id, c.out_score = out_score, c.out_node = out_node, c.out_count = out_count;
+    long_aud_fill(c);
+    return audience_set_entry("rwr_recommend_audience_set_long_batch", g, c, d);
 }
 
 int32_t rwr_recommend(rwr_graph *g, int32_t seed, float d, int32_t n_iter, int32_t top_n, int64_t *out_id,

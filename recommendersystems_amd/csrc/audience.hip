@@ -29,6 +29,7 @@
 #include "explain.h"
 #include "filter.h"
 #include "iterate.h"
+#include "long_list.h"
 #include "ranked_end.h"
 
 namespace rwr {
@@ -285,6 +286,8 @@ int32_t audience_body(rwr_graph *g, const AudCall &call, double d, const char *w
     // (the end and what it points to are declared before idle: ranked_end.h's lifetime rule; so is every scratch buffer)
     WhyEnd why;                                                  // no reasons (T = 0, n_why = 0): only the entries' rows
     why.nodes = call.out_node;
+    LongEnd lng;                                                 // rwr_recommend_audience_set_long_batch beyond the select's limit
+    lng.nodes = call.out_node;
     PosEnd pe;                                                   // (set up as typed.hip sets up the filtered positions entry's)
     pe.ev.test_ptr = call.test_ptr, pe.ev.test_ids = call.test_ids;
     pe.pos_out = call.out_pos, pe.score_out = call.out_score, pe.list_len = call.out_len;
@@ -292,7 +295,8 @@ int32_t audience_body(rwr_graph *g, const AudCall &call, double d, const char *w
     end.who = who;
     if (call.dest == AUD_LISTS) {
         end.top_n = call.top_n, end.ids = call.out_id, end.scores = call.out_score, end.counts = call.out_count;
-        if (call.out_node) end.why = &why;
+        if (long_applies(call.top_n)) end.lng = &lng;            // (only the long entry's ladder lets such a top_n through)
+        else if (call.out_node) end.why = &why;
     } else {
         end.pos = &pe;
     }

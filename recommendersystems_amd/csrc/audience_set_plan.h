@@ -47,6 +47,7 @@ struct AudCall {
     // the destination
     AudDest dest = AUD_LISTS;
     int32_t top_n = 0;                     // AUD_LISTS
+    int32_t top_n_max = AUD_TOP_N_MAX;     // ... its limit: the select path's, or the long entry's (long_plan.h)
     int64_t *out_id = nullptr;
     double *out_score = nullptr;           // AUD_LISTS: K x top_n; AUD_POSITIONS: test_ptr[K], may be nullptr
     int32_t *out_node = nullptr;           // may be nullptr
@@ -75,7 +76,7 @@ enum AudSetVerdict : int32_t {
     AUDSET_NULL_IDX,          // 3: NULL set_idx                                                     (RWR_E_INVALID)
     AUDSET_MEMBER_RANGE,      // 3: member bad_index at position bad_pos of set bad_k is outside [0, n) (RWR_E_RANGE)
     AUDSET_WEIGHT_RANGE,      // 3: weight bad_w at position bad_pos of set bad_k                    (RWR_E_RANGE)
-    AUDSET_TOP_N_RANGE,       // 4: AUD_LISTS: top_n outside [1, AUD_TOP_N_MAX]                      (RWR_E_RANGE)
+    AUDSET_TOP_N_RANGE,       // 4: AUD_LISTS: top_n outside [1, top_n_max]                          (RWR_E_RANGE)
     AUDSET_NEGATIVE_ITER,     // 5: n_iter < 0                                                       (RWR_E_INVALID)
     AUDSET_BAD_CAND_TYPE,     // 5a: cand_type outside [-1, 255]                                     (RWR_E_INVALID)
     AUDSET_BAD_MASK,          // 5b: a mask bit >= AUD_EDGE_TYPES                                    (RWR_E_INVALID)
@@ -128,7 +129,7 @@ inline AudSetCheck audience_set_check(const AudCall &a, bool have_graph, int32_t
             }
         c.bad_k = -1, c.bad_pos = -1;
     }
-    if (lists && (a.top_n < 1 || a.top_n > AUD_TOP_N_MAX)) return is(AUDSET_TOP_N_RANGE);
+    if (lists && (a.top_n < 1 || a.top_n > a.top_n_max)) return is(AUDSET_TOP_N_RANGE);
     if (a.n_iter < 0) return is(AUDSET_NEGATIVE_ITER);
     if (a.cand_type < -1 || a.cand_type > 255) return is(AUDSET_BAD_CAND_TYPE);
     if (a.etype_mask >> AUD_EDGE_TYPES) return is(AUDSET_BAD_MASK);
@@ -191,7 +192,7 @@ inline AudStatus audience_set_status(const char *who, const AudSetCheck &c, cons
         case AUDSET_WEIGHT_RANGE:
             return aud_refusal(RWR_E_RANGE, "%s: weight %g (set %d, position %lld) is not a finite number in [2^-256, 2^256]", who, c.bad_w,
                                c.bad_k, (long long)c.bad_pos);
-        case AUDSET_TOP_N_RANGE: return aud_refusal(RWR_E_RANGE, "%s: top_n %d is outside [1, %d]", who, a.top_n, (int)AUD_TOP_N_MAX);
+        case AUDSET_TOP_N_RANGE: return aud_refusal(RWR_E_RANGE, "%s: top_n %d is outside [1, %d]", who, a.top_n, (int)a.top_n_max);
         case AUDSET_NEGATIVE_ITER:
             return aud_refusal(RWR_E_INVALID,
                                "%s: n_iter %d is negative (a fixed number of steps only: the threshold modes have no reverse counterpart)", who,

@@ -21,10 +21,11 @@ int32_t rank_tile(rwr_graph *g, int G, const int32_t *d_slot_k_tile, int32_t top
 int32_t rank_group_select(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, int32_t top_n, const double *X,
                           const int32_t *d_seeds, hipStream_t s, const int32_t *rows = nullptr, int32_t nrows = 0);
 // ... the select's levels alone (explain.hip follows them with a row-carrying collect and sort-and-emit): the thresholds of the
-// tg * G segments in *st_out, room for SEL_SLOTS candidates of cand_size bytes per segment in *cand_out; m > 0 rows
+// tg * G segments in *st_out, room for SEL_SLOTS candidates of cand_size bytes per segment in *cand_out; m > 0 rows.  slots > 0
+// (long_list.hip): room for `slots` candidates per segment, for a top_n beyond SEL_MAX_K
 struct SelState;   // rank_keys.h
 int32_t rank_group_levels(rwr_graph *g, int G, int tg, int32_t top_n, const double *X, const int32_t *d_seeds, hipStream_t s,
-                          const int32_t *rows, int32_t m, size_t cand_size, SelState **st_out, void **cand_out);
+                          const int32_t *rows, int32_t m, size_t cand_size, SelState **st_out, void **cand_out, size_t slots = 0);
 // a tile group whose exclusion has been applied: the select when top_n allows it and RWR_RANK_SORT does not force the sort
 int32_t rank_group(rwr_graph *g, int G, int tg, const int32_t *d_slot_k, const int32_t *d_seeds, int32_t top_n, const double *X,
                    hipStream_t s);

@@ -450,14 +450,15 @@ int32_t rank_tile(rwr_graph *g, int G, const int32_t *d_slot_k_tile, int32_t top
 
 // The histogram / decide levels of a tile group's select over the m rows of `rows`: they fix the thresholds in *st_out (nseg states); *cand_out = room for SEL_SLOTS
 // candidates of cand_size bytes per segment, for the collect and the sort-and-emit that follow (here, or explain.hip's
-// row-carrying pair)
+// row-carrying pair).  slots > 0: room for that many candidates per segment instead (long_list.hip, whose top_n and collect
+// capacity lie beyond SEL_MAX_K and SEL_SLOTS; the levels themselves do not depend on either)
 int32_t rank_group_levels(rwr_graph *g, int G, int tg, int32_t top_n, const double *X, const int32_t *d_seeds, hipStream_t s,
-                          const int32_t *rows, int32_t m, size_t cand_size, SelState **st_out, void **cand_out)
+                          const int32_t *rows, int32_t m, size_t cand_size, SelState **st_out, void **cand_out, size_t slots)
 {
     const int nseg = tg * G;
     const size_t st_bytes = (size_t)nseg * sizeof(SelState);
     const size_t hist_bytes = (size_t)nseg * 256 * sizeof(uint32_t);
-    const size_t cand_bytes = (size_t)nseg * SEL_SLOTS * cand_size;
+    const size_t cand_bytes = (size_t)nseg * (slots > 0 ? slots : (size_t)SEL_SLOTS) * cand_size;
     const size_t ticket_bytes = SEL_LEVELS * sizeof(unsigned int);
     RWR_TRY(g->sort_temp.ensure(st_bytes + hist_bytes + ticket_bytes + cand_bytes + 64));
     SelState *st = (SelState *)g->sort_temp.p;

@@ -4,7 +4,7 @@
 // sets by counting, or the test ids' positions in the whole lists are found by the same counting; after the last group the
 // result is copied back once.  Three independent descriptions say which end: the candidates, the exclusion, the destination;
 // the filtered entries add a fourth, the seeds' deny lists, the capped entries a fifth, the group cap, the explained entry a
-// sixth, the reasons of the list's entries.
+// sixth, the reasons of the list's entries; the long entries name a fourth destination, lists beyond the select's limit.
 //
 // Lifetime: the object (and the EvalEnd or PosEnd it points to) is declared before the driver's StreamsIdle, so the device copies of
 // its plans outlive the kernels that read them, on error paths too.
@@ -19,6 +19,7 @@ namespace rwr {
 struct Profile;   // iterate.h
 struct GroupCap;  // group_cap.h
 struct WhyEnd;    // explain.h
+struct LongEnd;   // long_list.h
 
 struct RankedEnd {
     const char *who = "";              // the entry point, for the messages
@@ -57,6 +58,10 @@ struct RankedEnd {
     // select's last two launches are explain.hip's row-carrying pair -- and every entry's best in-link addends over the
     // group's previous ranks are found after the ranking.  nullptr: the stock launches, nothing more
     WhyEnd *why = nullptr;
+    // the long lists (the long entries; the list destination only, without reasons): top_n lies beyond the
+    // select's limit -- long_list.hip's collect, run sort and merge passes write the lists, always with their entries' rows.
+    // nullptr: top_n is within the select's limit
+    LongEnd *lng = nullptr;
 
     // The zeroed output tables (or records) of the call and the plans of this slot assignment: slot_k[slot] = batch position,
     // -1 = padding; slots_per_group slots form a tile group.  The driver has put slot_k into g->d_slot_k -- the ranking's

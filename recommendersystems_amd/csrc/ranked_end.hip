@@ -4,6 +4,7 @@
 #include "explain.h"
 #include "group_cap.h"
 #include "iterate.h"
+#include "long_list.h"
 
 namespace rwr {
 
@@ -71,6 +72,7 @@ int32_t RankedEnd::prepare(rwr_graph *g, int32_t K, const std::vector<int32_t> &
     else if (pos) RWR_TRY(pos_prepare(g, *pos, K, slot_k, slots_per_group, who, s));
     else RWR_TRY(ensure_out_tables(g, K, top_n, s));
     if (why && !ev && !pos) RWR_TRY(why_prepare(g, *why, K, top_n, s));
+    if (lng && !ev && !pos) RWR_TRY(long_prepare(g, *lng, K, top_n, s));
     if (mask != 0) {                                            // (mask 0 looks at no link)
         plan = exclude_plan(g->n, g->h_rowptr.data(), slot_k.size(), slot_k.data(), slots_per_group, K, set_ptr, set_idx);
         if (plan.check.verdict != EXCLUDE_OK) {                 // (api.hip refuses such sets before the call gets here)
@@ -134,6 +136,10 @@ int32_t RankedEnd::finish_group(rwr_graph *g, int G, int tg, int grp, size_t q0,
     if (cap) RWR_TRY(cap_group(g, *cap, G, tg, slot_k, X, s));
     if (ev) RWR_TRY(eval_group(g, *ev, G, tg, q0, X, rows ? rows : g->item_rows.p, rows ? nrows : g->n_items, s));
     else if (pos) RWR_TRY(pos_group(g, *pos, G, tg, q0, X, rows ? rows : g->item_rows.p, rows ? nrows : g->n_items, s));
+    else if (lng) {                                             // (top_n beyond the select's limit: long_list.hip's entry)
+        if (!rows || why) { set_error("%s: long lists need a candidate list and carry no reasons", who); return RWR_E_INVALID; }
+        if (nrows > 0) RWR_TRY(long_rank_group(g, *lng, G, tg, slot_k, top_n, X, s, rows, nrows));
+    }
     else if (why) {                                             // (a candidate list and top_n <= the select's limit: explain.hip's entry)
         if (!rows) { set_error("%s: reasons need a candidate list", who); return RWR_E_INVALID; }
         if (nrows > 0) {
@@ -152,6 +158,7 @@ int32_t RankedEnd::copy_back(rwr_graph *g, int32_t K)
     if (ev) return eval_copy_back(g, *ev, K, who, g->stream);
     if (pos) return pos_copy_back(g, *pos, K, who, g->stream);
     RWR_TRY(copy_lists_back(g, K, top_n, ids, scores, counts, top_n));
+    if (lng) return long_copy_back(g, *lng, K, top_n);
     return why ? why_copy_back(g, *why, K, top_n) : RWR_OK;
 }
 

@@ -22,10 +22,12 @@
 // marked after the link exclusion.  rwr_recommend_capped_batch and rwr_recommend_capped_positions_batch (group_cap.hip,
 // DESIGN.md 3.21) add group labels, from which a GroupCap joins the end: built here once the candidate list exists, applied
 // by the end after the deny marks.  rwr_recommend_explained_batch (explain.hip) adds a WhyEnd: the end then
-// also reads the group's previous ranks.  All eight entries come in through the one typed_body().
+// also reads the group's previous ranks.  rwr_recommend_long_batch (long_list.hip) is the explained entry without
+// reasons up to the select's limit and names a LongEnd beyond it.  All nine entries come in through the one typed_body().
 #include "explain.h"
 #include "filter.h"
 #include "group_cap.h"
+#include "long_list.h"
 
 namespace rwr {
 
@@ -173,6 +175,8 @@ int32_t typed_body(rwr_graph *g, const TypedCall &call, double d, int32_t n_iter
     WhyEnd why;
     why.n_why = call.n_why, why.T = T, why.c1 = 1 - d;           // (GroupIter's c1: Model.cs:84)
     why.nodes = call.nodes, why.why_src = call.why_src, why.why_term = call.why_term, why.why_total = call.why_total;
+    LongEnd lng;
+    lng.nodes = call.nodes;
     EvalEnd ev;
     ev.test_ptr = call.test_ptr, ev.test_ids = call.test_ids, ev.top_n = call.top_n;
     ev.n_hits = call.n_hits, ev.sum_precision = call.sum_precision, ev.list_len = call.list_len;
@@ -183,7 +187,8 @@ int32_t typed_body(rwr_graph *g, const TypedCall &call, double d, int32_t n_iter
     end.who = who;
     if (call.dest == CALL_LISTS) {
         end.top_n = call.top_n, end.ids = call.ids, end.scores = call.scores, end.counts = call.counts;
-        if (call.n_why > 0 || call.nodes || call.why_total) end.why = &why;
+        if (long_applies(call.top_n)) end.lng = &lng;            // (only the long entry's ladder lets such a top_n through)
+        else if (call.n_why > 0 || call.nodes || call.why_total) end.why = &why;
     } else if (call.dest == CALL_EVAL) {
         end.ev = &ev;
     } else {

@@ -63,6 +63,10 @@ struct TypedCall {
     // entries), and what its top_n limit's message appends
     bool any_type = false;
     const char *top_n_hint = "";
+    // the long entry (long_plan.h) replaces the ladder's top_n limit: > 0: this one instead of the select path's, worded
+    // with top_n_what
+    int32_t top_n_max = 0;
+    const char *top_n_what = "the select path's limit";
 };
 
 enum CallVerdict : int32_t {
@@ -90,7 +94,7 @@ enum CallVerdict : int32_t {
     CALL_BAD_CAP,             // group_of != NULL with group_cap < 1                       (RWR_E_INVALID)
     CALL_BAD_N_WHY,           // n_why < 0                                                 (RWR_E_INVALID)
     CALL_NULL_WHY,            // n_why > 0 with a NULL why_src or why_term                 (RWR_E_INVALID)
-    CALL_TOP_N_LIMIT,         // CALL_LISTS: top_n > top_n_max, the select path's limit    (RWR_E_UNSUPPORTED)
+    CALL_TOP_N_LIMIT,         // CALL_LISTS: top_n > top_n_max, the select path's limit -- or the call's own (RWR_E_UNSUPPORTED)
     CALL_CAP_LIMIT,           // group_of != NULL with group_cap > CAP_MAX                 (RWR_E_UNSUPPORTED)
     CALL_WHY_LIMIT,           // n_why > WHY_MAX                                           (RWR_E_UNSUPPORTED)
 };
@@ -153,7 +157,7 @@ inline CallCheck typed_call_check(const TypedCall &a, bool have_graph, int32_t n
     if (a.group_of && a.group_cap < 1) return is(CALL_BAD_CAP);
     if (lists && a.n_why < 0) return is(CALL_BAD_N_WHY);
     if (lists && a.n_why > 0 && (!a.why_src || !a.why_term)) return is(CALL_NULL_WHY);
-    if (lists && a.top_n > top_n_max) return is(CALL_TOP_N_LIMIT);
+    if (lists && a.top_n > (a.top_n_max > 0 ? a.top_n_max : top_n_max)) return is(CALL_TOP_N_LIMIT);
     if (a.group_of && a.group_cap > CAP_MAX) return is(CALL_CAP_LIMIT);
     if (lists && a.n_why > WHY_MAX) return is(CALL_WHY_LIMIT);
     return c;
@@ -244,8 +248,8 @@ inline CallStatus call_status(const char *who, const CallCheck &c, const TypedCa
         case CALL_BAD_N_WHY: return call_refusal(RWR_E_INVALID, "%s: n_why %d is below 0", who, a.n_why);
         case CALL_NULL_WHY: return call_refusal(RWR_E_INVALID, "%s: NULL why_src or why_term with n_why %d", who, a.n_why);
         case CALL_TOP_N_LIMIT:
-            return call_refusal(RWR_E_UNSUPPORTED, "%s: top_n %d is beyond the select path's limit of %d entries%s", who, a.top_n, top_n_max,
-                                a.top_n_hint);
+            return call_refusal(RWR_E_UNSUPPORTED, "%s: top_n %d is beyond %s of %d entries%s", who, a.top_n, a.top_n_what,
+                                a.top_n_max > 0 ? a.top_n_max : top_n_max, a.top_n_hint);
         case CALL_CAP_LIMIT:
             return call_refusal(RWR_E_UNSUPPORTED, "%s: group_cap %d is beyond the limit of RWR_GROUP_CAP_MAX = %d entries per group", who,
                                 a.group_cap, (int)RWR_GROUP_CAP_MAX);

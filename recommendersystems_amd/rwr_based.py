@@ -1325,6 +1325,80 @@ class Recommender:
             _p(ln, C.c_int64)))
         return _split_tests(tp, pos), _split_tests(tp, sc), ln
 
+    def RecommendationLongBatch(self, seeds, dampingFactor: float, nIteration: int, topN: int, candType=None, exclEdgeTypes=(),
+                                excludeSelf: bool = False, pool=None, deny=None, groupOf=None, groupCap: int = 1,
+                                wantNodes: bool = True):
+        """RecommendationCappedBatch for lists of up to 65 536 entries (rwr_recommend_long_batch, an addition, see
+        include/rwr.h): (ids[K,topN], scores[K,topN], counts[K], nodes[K,topN]).  The order is score descending, id descending,
+        node index ascending; nodes: the entries' node indices (-1 behind a list's end), None with wantNodes False.  Up to
+        1 024 entries the call is the explained call without reasons; candidate generation for a re-ranker is what the longer
+        lists are for."""
+        lib = _lib.load()
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        K = int(seeds.shape[0])
+        mask = 0
+        for t in exclEdgeTypes:
+            mask |= 1 << int(EdgeType(t))
+        pc, pi, dp, di = _pack_filter(pool, deny, K)
+        go = _pack_groups(groupOf)
+        if go is not None and go.shape[0] < self.graph.stats()["n"]:
+            raise ValueError("groupOf must hold one label per node of the graph")
+        topN = int(topN)
+        width = max(topN, 0)
+        ids = np.zeros((K, width), dtype=np.int64)
+        sc = np.zeros((K, width), dtype=np.float64)
+        counts = np.zeros(K, dtype=np.int32)
+        nodes = np.full((K, width), -1, dtype=np.int32) if wantNodes else None
+        _lib.check(lib.rwr_recommend_long_batch(
+            self.graph._handle(), _p(seeds, C.c_int32), K, C.c_float(dampingFactor), int(nIteration), topN,
+            -1 if candType is None else int(candType), mask, 1 if excludeSelf else 0, pc, None if pi is None else _p(pi, C.c_int32),
+            None if dp is None else _p(dp, C.c_int64), None if di is None else _p(di, C.c_int32),
+            None if go is None else _p(go, C.c_int32), int(groupCap), _p(ids, C.c_int64), _p(sc, C.c_double),
+            _p(counts, C.c_int32), None if nodes is None else _p(nodes, C.c_int32)))
+        return ids, sc, counts, nodes
+
+    def RecommendationLong(self, idxTargetNode: int, dampingFactor: float, nIteration: int, topN: int, candType=None,
+                           exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None, groupOf=None,
+                           groupCap: int = 1) -> List[Tuple[int, float]]:
+        """RecommendationLongBatch for one seed, as Recommendation returns its list: [(node id, score), ...]; deny: the seed's
+        one deny list (an iterable of node indices) or None."""
+        ids, sc, counts, _ = self.RecommendationLongBatch([int(idxTargetNode)], dampingFactor, nIteration, topN, candType,
+                                                          exclEdgeTypes, excludeSelf, pool, None if deny is None else [deny],
+                                                          groupOf, groupCap, False)
+        c = int(counts[0])
+        return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist()))
+
+    def AudienceSetLongBatch(self, sets, d: float, n_iter: int, weights=None, cand_type=None, etype_mask=(),
+                             exclude_members: bool = False, pool=None, deny=None, top_n: int = 4096):
+        """AudienceSetBatch for lists of up to 65 536 entries (rwr_recommend_audience_set_long_batch, an addition, see
+        include/rwr.h): (ids[K,top_n], scores[K,top_n], nodes[K,top_n], counts[K]).  Up to 1 024 entries it returns
+        AudienceSetBatch's arrays; a longer list continues that list."""
+        lib = _lib.load()
+        K, sp, si, sw = self._pack_target_sets(sets, weights)
+        pc, pi, dp, di = _pack_filter(pool, deny, K)
+        top_n = int(top_n)
+        width = max(top_n, 0)
+        ids = np.zeros((K, width), dtype=np.int64)
+        sc = np.zeros((K, width), dtype=np.float64)
+        nodes = np.full((K, width), -1, dtype=np.int32)
+        counts = np.zeros(K, dtype=np.int32)
+        _lib.check(lib.rwr_recommend_audience_set_long_batch(
+            self.graph._handle(), K, _p(sp, C.c_int64), _p(si, C.c_int32), None if sw is None else _p(sw, C.c_double), C.c_float(d),
+            int(n_iter), -1 if cand_type is None else int(cand_type), self._edge_mask(etype_mask), 1 if exclude_members else 0, pc,
+            None if pi is None else _p(pi, C.c_int32), None if dp is None else _p(dp, C.c_int64),
+            None if di is None else _p(di, C.c_int32), top_n, _p(ids, C.c_int64), _p(sc, C.c_double), _p(nodes, C.c_int32),
+            _p(counts, C.c_int32)))
+        return ids, sc, nodes, counts
+
+    def AudienceSetLong(self, members, d: float, n_iter: int, weights=None, cand_type=None, etype_mask=(),
+                        exclude_members: bool = False, pool=None, deny=None, top_n: int = 4096) -> List[Tuple[int, float]]:
+        """AudienceSetLongBatch for one set, as Recommendation returns its list: [(node id, score), ...]; deny: the set's one
+        deny list (an iterable of node indices) or None."""
+        ids, sc, _, counts = self.AudienceSetLongBatch([members], d, n_iter, None if weights is None else [weights], cand_type,
+                                                       etype_mask, exclude_members, pool, None if deny is None else [deny], top_n)
+        c = int(counts[0])
+        return list(zip(ids[0, :c].tolist(), sc[0, :c].tolist()))
+
     def RecommendationCappedPositionsBatch(self, seeds, dampingFactor: float, nIteration: int, testSets, candType=None,
                                            exclEdgeTypes=(), excludeSelf: bool = False, pool=None, deny=None, groupOf=None,
                                            groupCap: int = 1):
