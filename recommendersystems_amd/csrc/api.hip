@@ -41,6 +41,18 @@ static int32_t bound(const char *who, rwr_graph *g, F &&body)
     return no_throw(who, body);
 }
 
+// ... of an edit that fills NEW buffers and hands them to the handle (append.hip, remove.hip, node_remove.hip): before the swap
+// the handle still holds the old lists and everything derived from them, so a failure there leaves it usable; a failure after
+// it (`body` has set *swapped) leaves derived arrays that no longer match the new lists, and the handle is poisoned.
+template <class F>
+static int32_t bound_edit(const char *who, rwr_graph *g, F &&body)
+{
+    bool swapped = false;
+    const int32_t rc = bound(who, g, [&] { return body(&swapped); });
+    if (rc != RWR_OK && swapped) g->poisoned = 1;
+    return rc;
+}
+
 // The arrays of one graph as rwr_graph_create and rwr_eval_graphs take them.  The messages open with "<who>:" (at < 0) or
 // "<who>: graph <at>:" and call the node count n_name.
 static int32_t check_graph_arrays(const char *who, int32_t at, const char *n_name, int32_t n, const int64_t *node_id,
@@ -244,12 +256,9 @@ int32_t rwr_graph_append_links(rwr_graph *g, int64_t count, const int32_t *src, 
         set_error("rwr_graph_append_links: count must be >= 0 and src/dst/etype/w non-NULL when count > 0");
         return RWR_E_INVALID;
     }
-    bool swapped = false;
-    const int32_t rc = bound("rwr_graph_append_links", g, [&] { return graph_append(g, "rwr_graph_append_links", 0, nullptr, nullptr, count, src, dst, etype, w, new_index_out, &swapped); });
-    // before the swap the handle still holds the old lists and everything derived from them; a failure after it leaves derived
-    // arrays that no longer match the merged lists
-    if (rc != RWR_OK && swapped) g->poisoned = 1;
-    return rc;
+    return bound_edit("rwr_graph_append_links", g, [&](bool *swapped) {
+        return graph_append(g, "rwr_graph_append_links", 0, nullptr, nullptr, count, src, dst, etype, w, new_index_out, swapped);
+    });
 }
 
 int32_t rwr_graph_append_nodes(rwr_graph *g, int32_t n_new, const int64_t *node_id, const uint8_t *node_type, int64_t count,
@@ -267,12 +276,9 @@ int32_t rwr_graph_append_nodes(rwr_graph *g, int32_t n_new, const int64_t *node_
         return RWR_E_INVALID;
     }
     // (node types are taken as rwr_graph_create takes them: unchecked, anything but ITEM is no candidate)
-    bool swapped = false;
-    const int32_t rc = bound("rwr_graph_append_nodes", g, [&] {
-        return graph_append(g, "rwr_graph_append_nodes", n_new, node_id, node_type, count, src, dst, etype, w, new_index_out, &swapped);
+    return bound_edit("rwr_graph_append_nodes", g, [&](bool *swapped) {
+        return graph_append(g, "rwr_graph_append_nodes", n_new, node_id, node_type, count, src, dst, etype, w, new_index_out, swapped);
     });
-    if (rc != RWR_OK && swapped) g->poisoned = 1;   // (the two phases of rwr_graph_append_links)
-    return rc;
 }
 
 int32_t rwr_graph_remove_links(rwr_graph *g, int64_t count, const int64_t *link_index)
@@ -283,10 +289,7 @@ int32_t rwr_graph_remove_links(rwr_graph *g, int64_t count, const int64_t *link_
         set_error("rwr_graph_remove_links: count must be >= 0 and link_index non-NULL when count > 0");
         return RWR_E_INVALID;
     }
-    bool swapped = false;
-    const int32_t rc = bound("rwr_graph_remove_links", g, [&] { return graph_remove(g, count, link_index, &swapped); });
-    if (rc != RWR_OK && swapped) g->poisoned = 1;   // (the two phases of rwr_graph_append_links)
-    return rc;
+    return bound_edit("rwr_graph_remove_links", g, [&](bool *swapped) { return graph_remove(g, count, link_index, swapped); });
 }
 
 int32_t rwr_graph_remove_nodes(rwr_graph *g, int32_t count, const int32_t *node_index, int32_t *new_node_index_out,
@@ -298,12 +301,9 @@ int32_t rwr_graph_remove_nodes(rwr_graph *g, int32_t count, const int32_t *node_
         set_error("rwr_graph_remove_nodes: count must be >= 0 and node_index non-NULL when count > 0");
         return RWR_E_INVALID;
     }
-    bool swapped = false;
-    const int32_t rc = bound("rwr_graph_remove_nodes", g, [&] {
-        return graph_remove_nodes(g, count, node_index, new_node_index_out, new_link_index_out, links_removed_out, &swapped);
+    return bound_edit("rwr_graph_remove_nodes", g, [&](bool *swapped) {
+        return graph_remove_nodes(g, count, node_index, new_node_index_out, new_link_index_out, links_removed_out, swapped);
     });
-    if (rc != RWR_OK && swapped) g->poisoned = 1;   // (the two phases of rwr_graph_append_links)
-    return rc;
 }
 
 int32_t rwr_graph_destroy(rwr_graph *g)

@@ -3,13 +3,11 @@
 // here merge the resident raw lists with the new links, and the resident ITEM order with the new ITEM rows, into NEW buffers, the
 // handle takes them, and build.hip's re-derive (the incremental rebuild with nothing to patch) rebuilds the walk's data from
 // them -- the same kernels in the same order as rwr_graph_create, hence the same bits.
-#include "engine.h"
+#include "edit.h"
 #include "append_plan.h"
 #include "node_append_plan.h"
 #include "seg_copy.h"
 
-#include <chrono>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -20,44 +18,27 @@ namespace rwr {
 // cum[j] = links appended to s_0 .. s_j.  The old flat position e moves to e + cum[upper_bound(brk, e) - 1]: between two
 // breakpoints the move is constant, so the copy is a sequence of plain shifted block copies.
 constexpr int AP_THREADS = SEG_THREADS;   // (seg_copy.h: the lanes of a segment's block copies)
-constexpr int AP_CHUNK = 8192;     // old positions per workgroup
-// More breakpoints than this in a chunk: the dense path of k_append_merge (per-element shifts).  The value is reasoned, not
-// tuned: a segment is walked by all 256 lanes, so segments under 256 elements leave lanes idle in every one of the three block
-// copies, and 8 192 / 32 = 256 is the average segment length at which that starts.  A bisection over at most 8 192 breakpoints
-// of the chunk costs each element up to 13 uniform-ish loads from a table the whole workgroup keeps in cache.
-constexpr int AP_DENSE_BREAKS = 32;
 
-// the experiments build's wall-clock stamps (RWR_APPEND_TIMING=1), as RWR_BUILD_TIMING in build.h: tools/append_latency.py
-static double at_now()
-{
-    using namespace std::chrono;
-    return duration<double, std::micro>(steady_clock::now().time_since_epoch()).count();
-}
-static const bool at_on = [] { const char *e = RWR_TUNE_ENV("RWR_APPEND_TIMING"); return e && atoi(e) != 0; }();
-#define AT(label) do { if (at_on) { const double t__ = at_now(); fprintf(stderr, "[append] %-28s %8.1f us\n", label, t__ - at_t); at_t = t__; } } while (0)
+static const Stamps append_stamps("append", "RWR_APPEND_TIMING");   // (engine.h; tools/append_latency.py)
 
-// rowptr_new[i] = rowptr_old[min(i, n_old)] + (appended links with src < i), i in [0, n]: the rows past n_old are the call's
-// new nodes, whose lists were empty before it
+// the new row pointers, i in [0, n]: one bisection over the distinct sources per row pointer (append_plan.h)
 __global__ __launch_bounds__(256) void k_append_rowptr(int32_t n, int32_t n_old, int32_t nb, const int32_t *__restrict__ srcs,
                                                        const int64_t *__restrict__ cum, const int64_t *__restrict__ rp_old,
                                                        int64_t *__restrict__ rp_new)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i > n) return;
-    int lo = 0, hi = nb;               // lower_bound(srcs, i)
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if ((int64_t)srcs[mid] < i) lo = mid + 1;
-        else hi = mid;
-    }
-    rp_new[i] = rp_old[i < n_old ? i : (int64_t)n_old] + (lo > 0 ? cum[lo - 1] : 0);
+    rp_new[i] = ap_rowptr_new(srcs, cum, nb, rp_old, n_old, i);
 }
 
 // A workgroup takes AP_CHUNK consecutive old positions and finds the breakpoints inside its chunk ONCE, brk[j .. jend) (every
 // lane runs the same two bisections: uniform loads).  Then one of two paths, chosen per chunk:
 // * sparse, at most AP_DENSE_BREAKS breakpoints in the chunk: it walks them, and each segment in between is three shifted
 //   block copies without any search per element;
-// * dense, more than that: every lane takes elements in lane order and finds each one's shift by bisecting brk[j .. jend).
+// * dense, more than that (a bulk append that touches most rows: segments of a few dozen elements, which would leave most
+//   lanes idle in the block copies): every lane takes elements in lane order and finds each one's shift by bisecting the
+//   chunk's OWN breakpoints -- at most 13 steps over entries the whole workgroup reads.  Loads stay lane-consecutive; the
+//   stores of a wave fall into a few pieces of consecutive addresses.
 // Both write every old position of the chunk exactly once, at e + shift(e): the choice changes the speed, never the result.
 __global__ __launch_bounds__(AP_THREADS) void k_append_merge(int64_t m_old, int32_t nb, const int64_t *__restrict__ brk,
                                                              const int64_t *__restrict__ cum, const int32_t *__restrict__ dst_o,
@@ -68,51 +49,24 @@ __global__ __launch_bounds__(AP_THREADS) void k_append_merge(int64_t m_old, int3
     const int tid = threadIdx.x;
     const int64_t c0 = (int64_t)blockIdx.x * AP_CHUNK;
     const int64_t c1 = c0 + AP_CHUNK < m_old ? c0 + AP_CHUNK : m_old;
-    int lo = 0, hi = nb;               // upper_bound(brk, c0)
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (brk[mid] <= c0) lo = mid + 1;
-        else hi = mid;
-    }
-    int j = lo;
-    // Many breakpoints inside the chunk (a bulk append that touches most rows: segments of a few dozen elements, which would
-    // leave most lanes idle in the block copies below): every lane takes elements of the chunk in lane order and finds each
-    // one's shift by bisecting the chunk's OWN breakpoints, brk[j .. jend) -- at most 13 steps over entries the whole workgroup
-    // reads.  brk[0 .. j) <= c0 <= e, so the bisection of [j, jend) is the global upper_bound(brk, e).  Loads stay
-    // lane-consecutive; the stores of a wave fall into a few pieces of consecutive addresses.
-    int jend = j;
-    {
-        int h2 = nb;                   // upper_bound(brk, c1 - 1) within [j, nb)
-        while (jend < h2) {
-            const int mid = (jend + h2) >> 1;
-            if (brk[mid] <= c1 - 1) jend = mid + 1;
-            else h2 = mid;
-        }
-    }
-    if (jend - j > AP_DENSE_BREAKS) {
+    const ApSlice s = ap_chunk_slice(brk, nb, c0, c1);
+    if (ap_chunk_dense(s)) {
         for (int64_t e = c0 + tid; e < c1; e += AP_THREADS) {
-            int l2 = j, h2 = jend;     // upper_bound(brk, e) within [j, jend)
-            while (l2 < h2) {
-                const int mid = (l2 + h2) >> 1;
-                if (brk[mid] <= e) l2 = mid + 1;
-                else h2 = mid;
-            }
-            const int64_t sh = l2 > 0 ? cum[l2 - 1] : 0;
-            w_n[e + sh] = w_o[e];
-            dst_n[e + sh] = dst_o[e];
-            et_n[e + sh] = et_o[e];
+            const int64_t to = ap_dense_dest(brk, cum, s, e);
+            w_n[to] = w_o[e];
+            dst_n[to] = dst_o[e];
+            et_n[to] = et_o[e];
         }
         return;
     }
-    int64_t a = c0;
-    while (a < c1) {
-        const int64_t sh = j > 0 ? cum[j - 1] : 0;             // (brk[j] > a here)
-        const int64_t b = (j < nb && brk[j] < c1) ? brk[j] : c1;
-        copy_seg<double>(w_o, w_n, a, b, sh, tid);
-        copy_seg<int32_t>(dst_o, dst_n, a, b, sh, tid);
-        copy_seg_bytes(et_o, et_n, a, b, sh, tid);
-        a = b;
-        while (j < nb && brk[j] <= a) ++j;                      // (coinciding breakpoints: rows without links in between)
+    int j = s.j;
+    for (int64_t a = c0; a < c1;) {
+        const ApSeg g = ap_segment(brk, cum, nb, c1, a, j);
+        copy_seg<double>(w_o, w_n, g.a, g.b, g.sh, tid);
+        copy_seg<int32_t>(dst_o, dst_n, g.a, g.b, g.sh, tid);
+        copy_seg_bytes(et_o, et_n, g.a, g.b, g.sh, tid);
+        a = g.b;
+        j = g.next;
     }
 }
 
@@ -169,7 +123,7 @@ int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t
     const int32_t n_old = g->n;
     hipStream_t s = g->stream;
     *swapped = false;
-    double at_t = at_on ? at_now() : 0.0;
+    Stamps stamp = append_stamps.begin();
     const NodeAppendPlan np = node_append_plan(n_old, n_new, node_id, node_type, (uint8_t)RWR_NODE_ITEM);
     if (np.verdict == NODE_APPEND_TOO_MANY) {
         set_error("%s: %d + %d nodes exceed this build's limit of 2^31-1", who, n_old, n_new);
@@ -204,7 +158,7 @@ int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t
     const int64_t m_old = plan.m_old, m_new = plan.m_new;
     const size_t nb = plan.srcs.size();
     const int32_t ni_old = g->n_items, ni_new = np.n_new_items, ni = ni_old + ni_new;
-    AT("plan (host)");
+    stamp("plan (host)");
     // the new links in list order
     std::vector<int32_t> h_dst((size_t)(links ? count : 0));
     std::vector<uint8_t> h_et((size_t)(links ? count : 0));
@@ -215,47 +169,32 @@ int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t
         h_et[(size_t)k] = etype[q];
         h_w[(size_t)k] = w[q];
     }
-    AT("new links in order (host)");
+    stamp("new links in order (host)");
     // ---- phase 1: every buffer exists before anything is launched
     DevBuf<int64_t> rp_n, d_brk, d_cum, d_pos;
-    DevBuf<int32_t> dst_n, d_srcs, d_dst;
-    DevBuf<uint8_t> et_n, d_et;
-    DevBuf<double> w_n, wn_n, d_w;
+    DevBuf<int32_t> d_srcs, d_dst;
+    DevBuf<uint8_t> d_et;
+    DevBuf<double> d_w;
+    StagedLinks ln;
     RWR_TRY(rp_n.alloc((size_t)n + 1));
     RWR_TRY(d_srcs.alloc(nb));
     RWR_TRY(d_cum.alloc(nb));
     if (links) {
-        RWR_TRY(dst_n.alloc((size_t)m_new));
-        RWR_TRY(et_n.alloc((size_t)m_new));
-        RWR_TRY(w_n.alloc((size_t)m_new));
-        RWR_TRY(wn_n.alloc((size_t)m_new));
+        RWR_TRY(ln.alloc((size_t)m_new));
         RWR_TRY(d_brk.alloc(nb));
         RWR_TRY(d_pos.alloc((size_t)count));
         RWR_TRY(d_dst.alloc((size_t)count));
         RWR_TRY(d_et.alloc((size_t)count));
         RWR_TRY(d_w.alloc((size_t)count));
     }
-    // ... and of a call that adds nodes: the node SoA, the two ITEM orders, and every n-sized array the re-derive writes
-    // (it fills them whole, as the first build does with its own fresh allocations)
-    DevBuf<int64_t> nid_n, inp_n;
-    DevBuf<uint8_t> nty_n, dang_n;
-    DevBuf<double> wsrc_n;
-    DevBuf<int32_t> ro_n, rox_n, irows_n, iord_n, d_bsorted;
+    // ... and of a call that adds nodes: the node-sized arrays, with the two ITEM orders if an ITEM is among the new nodes
+    StagedNodes nd;
+    DevBuf<int32_t> d_bsorted;
     if (grow) {
-        RWR_TRY(nid_n.alloc((size_t)n));
-        RWR_TRY(nty_n.alloc((size_t)n));
-        RWR_TRY(dang_n.alloc((size_t)n));
-        RWR_TRY(wsrc_n.alloc((size_t)n));
-        RWR_TRY(inp_n.alloc((size_t)n + 1));
-        RWR_TRY(ro_n.alloc((size_t)n));
-        RWR_TRY(rox_n.alloc((size_t)n));
-        if (ni_new > 0) {
-            RWR_TRY(irows_n.alloc((size_t)ni));
-            RWR_TRY(iord_n.alloc((size_t)ni));
-            RWR_TRY(d_bsorted.alloc((size_t)ni_new));
-        }
+        RWR_TRY(nd.alloc((size_t)n, (size_t)ni, ni_new > 0));
+        if (ni_new > 0) RWR_TRY(d_bsorted.alloc((size_t)ni_new));
     }
-    AT("allocate new buffers");
+    stamp("allocate new buffers");
     // the id range of the grown ITEM set (rwr_graph_create's sort-key parameters): the handle knows the largest resident id;
     // the smallest one is the last entry of the resident order, read back once per handle
     uint64_t key_lo = g->id_key_lo, key_hi = g->id_key_top;
@@ -268,7 +207,7 @@ int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t
         RWR_HIP(hipMemcpy(&last_id, g->node_id.p + last_row, sizeof(int64_t), hipMemcpyDeviceToHost));
         key_lo = nap_orderable(last_id);
         lo_known = true;
-        AT("read back the smallest id");
+        stamp("read back the smallest id");
     }
     if (ni_new > 0) {
         if (ni_old > 0) {
@@ -299,25 +238,25 @@ int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t
         if (links) {
             if (m_old > 0)
                 hipLaunchKernelGGL(k_append_merge, dim3(cdiv((size_t)m_old, (size_t)AP_CHUNK)), dim3(AP_THREADS), 0, s, m_old,
-                                   (int32_t)nb, d_brk.p, d_cum.p, g->dst.p, g->etype.p, g->w_raw.p, dst_n.p, et_n.p, w_n.p);
+                                   (int32_t)nb, d_brk.p, d_cum.p, g->dst.p, g->etype.p, g->w_raw.p, ln.dst.p, ln.etype.p, ln.w_raw.p);
             hipLaunchKernelGGL(k_append_scatter, dim3(cdiv((size_t)count, 256)), dim3(256), 0, s, count, d_pos.p, d_dst.p,
-                               d_et.p, d_w.p, dst_n.p, et_n.p, w_n.p);
+                               d_et.p, d_w.p, ln.dst.p, ln.etype.p, ln.w_raw.p);
         }
         if (grow) {
             // node SoA: the resident part device to device, the new tail from the caller's arrays
-            RWR_HIP(hipMemcpyAsync(nid_n.p, g->node_id.p, sizeof(int64_t) * (size_t)n_old, hipMemcpyDeviceToDevice, s));
-            RWR_HIP(hipMemcpyAsync(nid_n.p + n_old, node_id, sizeof(int64_t) * (size_t)n_new, hipMemcpyHostToDevice, s));
-            RWR_HIP(hipMemcpyAsync(nty_n.p, g->node_type.p, (size_t)n_old, hipMemcpyDeviceToDevice, s));
-            RWR_HIP(hipMemcpyAsync(nty_n.p + n_old, node_type, (size_t)n_new, hipMemcpyHostToDevice, s));
+            RWR_HIP(hipMemcpyAsync(nd.node_id.p, g->node_id.p, sizeof(int64_t) * (size_t)n_old, hipMemcpyDeviceToDevice, s));
+            RWR_HIP(hipMemcpyAsync(nd.node_id.p + n_old, node_id, sizeof(int64_t) * (size_t)n_new, hipMemcpyHostToDevice, s));
+            RWR_HIP(hipMemcpyAsync(nd.node_type.p, g->node_type.p, (size_t)n_old, hipMemcpyDeviceToDevice, s));
+            RWR_HIP(hipMemcpyAsync(nd.node_type.p + n_old, node_type, (size_t)n_new, hipMemcpyHostToDevice, s));
             if (ni_new > 0) {
                 if (ni_old > 0)
-                    RWR_HIP(hipMemcpyAsync(irows_n.p, g->item_rows.p, sizeof(int32_t) * (size_t)ni_old, hipMemcpyDeviceToDevice, s));
-                RWR_HIP(hipMemcpyAsync(irows_n.p + ni_old, np.new_item_rows.data(), sizeof(int32_t) * (size_t)ni_new,
+                    RWR_HIP(hipMemcpyAsync(nd.item_rows.p, g->item_rows.p, sizeof(int32_t) * (size_t)ni_old, hipMemcpyDeviceToDevice, s));
+                RWR_HIP(hipMemcpyAsync(nd.item_rows.p + ni_old, np.new_item_rows.data(), sizeof(int32_t) * (size_t)ni_new,
                                        hipMemcpyHostToDevice, s));
                 RWR_HIP(hipMemcpyAsync(d_bsorted.p, np.new_item_sorted.data(), sizeof(int32_t) * (size_t)ni_new,
                                        hipMemcpyHostToDevice, s));
                 hipLaunchKernelGGL(k_item_order_merge, dim3(cdiv((size_t)ni, 256)), dim3(256), 0, s, ni_old, ni_new,
-                                   g->item_order.p, d_bsorted.p, nid_n.p, iord_n.p);
+                                   g->item_order.p, d_bsorted.p, nd.node_id.p, nd.item_order.p);
             }
         }
         RWR_HIP(hipGetLastError());
@@ -325,32 +264,19 @@ int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t
         return RWR_OK;
     };
     RWR_TRY(idle_on_error(s, merge));
-    AT("upload + merge kernels");
+    stamp("upload + merge kernels");
     // ---- phase 2: the handle takes the merged lists and the grown node arrays
     *swapped = true;
     growth.keep = true;
     swap_blocks(g->rowptr, rp_n);
-    if (links) {
-        swap_blocks(g->dst, dst_n);
-        swap_blocks(g->etype, et_n);
-        swap_blocks(g->w_raw, w_n);
-        swap_blocks(g->w_norm_raw, wn_n);
-    }
+    if (links) ln.take(g);
     node_append_shift_rowptr(g->h_rowptr, n, plan.srcs, plan.cum);
     g->nnz_raw = m_new;
     g->stats.nnz_raw = m_new;
     if (m_new > ONE_LAUNCH_MAX_M) g->staged = 0;                // past the one-launch build: the general derive from now on
     if (grow) {
-        swap_blocks(g->node_id, nid_n);
-        swap_blocks(g->node_type, nty_n);
-        swap_blocks(g->dangling, dang_n);
-        swap_blocks(g->w_src, wsrc_n);
-        swap_blocks(g->in_ptr, inp_n);
-        swap_blocks(g->row_order, ro_n);
-        swap_blocks(g->row_order_x, rox_n);
+        nd.take(g);
         if (ni_new > 0) {
-            swap_blocks(g->item_rows, irows_n);
-            swap_blocks(g->item_order, iord_n);
             node_append_id_keys(true, key_lo, key_hi, &g->id_key_top, &g->id_key_bits);
             g->id_key_lo = key_lo;
             g->id_key_lo_known = lo_known ? 1 : 0;
@@ -362,16 +288,12 @@ int32_t graph_append(rwr_graph *g, const char *who, int32_t n_new, const int64_t
         g->stats.n = n;
         // a staged graph's pinned read-back area is sized for ONE_LAUNCH_MAX_N nodes (stage_layout.h: STAGE_BYTES)
         if (n > ONE_LAUNCH_MAX_N) g->staged = 0;
-        // nothing cached for the old node count survives: the list a single-seed call left in pinned memory, and a
-        // row-partitioned run (the re-derive ends it; its slab and seeds go too, so that only rwr_part_begin restarts it)
-        g->sm_pin_count = -1;
-        g->part_lo = g->part_hi = g->part_K = g->part_steps = 0;
-        g->part_seeds.clear();
+        forget_node_set(g, /*cand_lists=*/false);               // (the candidate lists stay: nodes were only appended)
     }
     if (new_index_out && links) memcpy(new_index_out, plan.new_index.data(), sizeof(int64_t) * (size_t)count);
-    AT("swap + host row pointers");
+    stamp("swap + host row pointers");
     const int32_t rc = graph_update_links(g, 0, nullptr, nullptr, nullptr);   // (count 0: the re-derive alone, build.hip)
-    AT("re-derive");
+    stamp("re-derive");
     return rc;
 }
 

@@ -10,6 +10,9 @@
 // c_j the shift is cum[upper_bound(brk, e) - 1] (0 before the first breakpoint), the new row pointer of row i is
 // rowptr_old[i] + cum[lower_bound(srcs, i) - 1] (the appended links with src < i), and the r-th link appended to s_j lands at
 // brk[j] + (cum[j] - c_j) + r.  The tables have one entry per DISTINCT source: O(count), never O(n) or O(m).
+//
+// The index arithmetic of the device kernels (ap_* below) is __host__ __device__ and runs in that program as well, chunk by
+// chunk through both of the merge kernel's paths.
 #pragma once
 
 #include <algorithm>
@@ -17,7 +20,89 @@
 #include <numeric>
 #include <vector>
 
+#if defined(__HIPCC__)
+#define APP_HD __host__ __device__
+#else
+#define APP_HD
+#endif
+
 namespace rwr {
+
+// ---- what the device kernels compute per row pointer and per chunk of old positions (append.hip)
+constexpr int AP_CHUNK = 8192;     // old positions per workgroup
+// More breakpoints than this in a chunk: the dense path of k_append_merge (per-element shifts).  The value is reasoned, not
+// tuned: a segment is walked by all 256 lanes, so segments under 256 elements leave lanes idle in every one of the three block
+// copies, and 8 192 / 32 = 256 is the average segment length at which that starts.  A bisection over at most 8 192 breakpoints
+// of the chunk costs each element up to 13 uniform-ish loads from a table the whole workgroup keeps in cache.
+constexpr int AP_DENSE_BREAKS = 32;
+
+// first k in [0, nb) with srcs[k] >= i (nb if there is none): the distinct sources below row i
+APP_HD inline int ap_sources_below(const int32_t *srcs, int nb, int64_t i)
+{
+    int lo = 0, hi = nb;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if ((int64_t)srcs[mid] < i) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+// first k in [lo, hi) with brk[k] > v (hi if there is none)
+APP_HD inline int ap_upper_bound(const int64_t *brk, int lo, int hi, int64_t v)
+{
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (brk[mid] <= v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// rowptr_new[i] = rowptr_old[min(i, n_old)] + (appended links with src < i), i in [0, n]: the rows past n_old are the call's
+// new nodes, whose lists were empty before it (rowptr_old has n_old + 1 entries)
+APP_HD inline int64_t ap_rowptr_new(const int32_t *srcs, const int64_t *cum, int nb, const int64_t *rowptr_old, int32_t n_old,
+                                    int64_t i)
+{
+    const int k = ap_sources_below(srcs, nb, i);
+    return rowptr_old[i < n_old ? i : (int64_t)n_old] + (k > 0 ? cum[k - 1] : 0);
+}
+
+// the breakpoints inside the chunk [c0, c1) of old positions, c0 < c1: brk[j .. jend) lie in (c0, c1 - 1]; brk[0 .. j) <= c0
+// have moved the whole chunk already, brk[jend ..) >= c1 move nothing of it
+struct ApSlice { int j, jend; };
+APP_HD inline ApSlice ap_chunk_slice(const int64_t *brk, int nb, int64_t c0, int64_t c1)
+{
+    ApSlice s;
+    s.j = ap_upper_bound(brk, 0, nb, c0);
+    s.jend = ap_upper_bound(brk, s.j, nb, c1 - 1);
+    return s;
+}
+APP_HD inline bool ap_chunk_dense(ApSlice s) { return s.jend - s.j > AP_DENSE_BREAKS; }
+
+// Sparse path: the segment of the chunk that starts at old position a, where j is the first breakpoint behind a (brk[j] > a;
+// for a = c0 that is the slice's j).  Old positions [a, b) move up by sh; the walk goes on at a = b with j = next, which has
+// skipped every breakpoint equal to b (coinciding ones: sources that are neighbouring rows without links), until b == c1.
+struct ApSeg { int64_t a, b, sh; int next; };
+APP_HD inline ApSeg ap_segment(const int64_t *brk, const int64_t *cum, int nb, int64_t c1, int64_t a, int j)
+{
+    ApSeg g;
+    g.a = a;
+    g.sh = j > 0 ? cum[j - 1] : 0;
+    g.b = (j < nb && brk[j] < c1) ? brk[j] : c1;
+    while (j < nb && brk[j] <= g.b) ++j;
+    g.next = j;
+    return g;
+}
+
+// Dense path: the new position of the old position e of the chunk.  brk[0 .. j) <= c0 <= e and brk[jend ..) > e, so the
+// bisection of the chunk's own slice is the global upper_bound(brk, e).
+APP_HD inline int64_t ap_dense_dest(const int64_t *brk, const int64_t *cum, ApSlice s, int64_t e)
+{
+    const int k = ap_upper_bound(brk, s.j, s.jend, e);
+    return e + (k > 0 ? cum[k - 1] : 0);
+}
+
+// ---- the host plan
 
 constexpr int64_t APPEND_MAX_LINKS = 0xFFFFFFFEll;   // the build's per-device limit of 2^32-2 links (build.hip: graph_build_upload)
 

@@ -3,18 +3,10 @@
 #pragma once
 #include "engine.h"
 
-#include <chrono>
-
 namespace rwr {
 
-// the experiments build's wall-clock stamps (RWR_BUILD_TIMING=1); a function that uses BT keeps the last stamp in `bt_t`
-static inline double bt_now()
-{
-    using namespace std::chrono;
-    return duration<double, std::micro>(steady_clock::now().time_since_epoch()).count();
-}
-static const bool bt_on = [] { const char *e = RWR_TUNE_ENV("RWR_BUILD_TIMING"); return e && atoi(e) != 0; }();
-#define BT(label) do { if (bt_on) { const double t__ = bt_now(); fprintf(stderr, "[build] %-28s %8.1f us\n", label, t__ - bt_t); bt_t = t__; } } while (0)
+// the experiments build's wall-clock stamps of the build's stages (RWR_BUILD_TIMING=1; engine.h: Stamps)
+static const Stamps build_stamps("build", "RWR_BUILD_TIMING");
 
 // build.hip
 int32_t graph_build_upload(rwr_graph *g, const int64_t *node_id, const uint8_t *node_type, const int64_t *rowptr,

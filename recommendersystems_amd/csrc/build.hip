@@ -484,7 +484,7 @@ int32_t graph_build_upload(rwr_graph *g, const int64_t *node_id, const uint8_t *
     const int32_t n = g->n;
     const int64_t m = g->nnz_raw;
     hipStream_t s = g->stream;
-    double bt_t = bt_now();
+    Stamps stamp = build_stamps.begin();
     if (m >= 0xFFFFFFFFll) {
         set_error("rwr_graph_create: %lld links exceed this build's per-device limit of 2^32-2", (long long)m);
         return RWR_E_UNSUPPORTED;
@@ -522,7 +522,7 @@ int32_t graph_build_upload(rwr_graph *g, const int64_t *node_id, const uint8_t *
     RWR_TRY(g->item_order.alloc(n_items));
     RWR_TRY(g->item_rows.alloc(n_items));
 
-    BT("host prep + allocs");
+    stamp("host prep + allocs");
     g->staged = graph_fits_small_build(n, m);   // (a staged upload is unpacked by the one-launch build alone)
     if (g->staged) {
         if (!g->sm_stage) RWR_HIP(hipHostMalloc(&g->sm_stage, STAGE_BYTES, hipHostMallocMapped | hipHostMallocPortable));
@@ -551,7 +551,7 @@ int32_t graph_build_upload(rwr_graph *g, const int64_t *node_id, const uint8_t *
             RWR_HIP(hipMemcpyAsync(g->w_raw.p, w, sizeof(double) * m, hipMemcpyHostToDevice, s));
         }
     }
-    BT("H2D enqueue");
+    stamp("H2D enqueue");
     return RWR_OK;
 }
 
@@ -623,7 +623,7 @@ int32_t graph_apply_flags(rwr_graph *g, int64_t nnz, const int *h_flags)
 int32_t derive_finish(rwr_graph *g, const int *h_flags, hipEvent_t e0, hipEvent_t e1)
 {
     const int32_t n = g->n;
-    double bt_t = bt_now();
+    Stamps stamp = build_stamps.begin();
     g->max_in_deg = h_flags[2];
     g->bin_end[0] = g->bin_end[1] = g->bin_end[2] = g->bin_huge = g->bin_hub = 0;
     static const int hub_t_env = [] { const char *e = getenv("RWR_HUB_T"); return e ? atoi(e) : 2048; }();   // (measured best on the MovieLens-shaped graph: 2048 / prefix 256)
@@ -643,7 +643,7 @@ int32_t derive_finish(rwr_graph *g, const int *h_flags, hipEvent_t e0, hipEvent_
         g->x_bins[ph][1] += deg >= 32;
         g->x_bins[ph][2] += deg >= 4;
     }
-    BT("D2H in_ptr/dangling + bins");
+    stamp("D2H in_ptr/dangling + bins");
     float ms = 0.f;
     if (e0 && e1) RWR_HIP(hipEventElapsedTime(&ms, e0, e1));      // (a batch build is not timed per graph)
     g->stats.build_ms = ms;
@@ -670,7 +670,7 @@ static int32_t graph_derive(rwr_graph *g, bool first)
     const int64_t m = g->nnz_raw;
     const int32_t n_items = g->n_items;
     hipStream_t s = g->stream;
-    double bt_t = bt_now();
+    Stamps stamp = build_stamps.begin();
     hipEvent_t e0 = g->ev_a, e1 = g->ev_b;
     DevBuf<int32_t> esrc;
     DevBuf<uint32_t> skey, skey2, sval, sval2;
@@ -691,7 +691,7 @@ static int32_t graph_derive(rwr_graph *g, bool first)
     int h_flags[4] = {0, 0, 0, 0};   // [0] some row non-uniform, [1] bad target, [2] max in-degree, [3] a weight or row sum not in (0, inf)
     RWR_HIP(hipMemsetAsync(flags.p, 0, sizeof(h_flags), s));
 
-    BT("derive allocs");
+    stamp("derive allocs");
     RWR_HIP(hipEventRecord(e0, s));
 
     hipLaunchKernelGGL(k_row_prepare, dim3(cdiv(n, RP_WPB * WAVE)), dim3(RP_WPB * WAVE), 0, s, n, g->rowptr.p, g->dst.p, g->etype.p,
@@ -709,9 +709,9 @@ static int32_t graph_derive(rwr_graph *g, bool first)
     int64_t nnz = 0;
     RWR_HIP(hipMemcpyAsync(&nnz, g->in_ptr.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     RWR_HIP(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, s));
-    BT("enqueue row pass + link sort");
+    stamp("enqueue row pass + link sort");
     RWR_HIP(hipStreamSynchronize(s));
-    BT("sync 1 (H2D + row pass + sort)");
+    stamp("sync 1 (H2D + row pass + sort)");
     RWR_TRY(graph_apply_flags(g, nnz, h_flags));
     RWR_TRY(g->in_src.ensure((size_t)nnz + 64));   // (padded: wide index loads may run past a row's end)
     if (g->vf) g->in_w.release();
@@ -762,9 +762,9 @@ static int32_t graph_derive(rwr_graph *g, bool first)
     g->h_dangling.resize((size_t)n);
     RWR_HIP(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, s));
     RWR_HIP(hipEventRecord(e1, s));
-    BT("enqueue gather + orders");
+    stamp("enqueue gather + orders");
     RWR_HIP(hipStreamSynchronize(s));
-    BT("sync 2 (orders)");
+    stamp("sync 2 (orders)");
     RWR_HIP(hipMemcpy(g->h_in_ptr.data(), g->in_ptr.p, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost));
     RWR_HIP(hipMemcpy(g->h_dangling.data(), g->dangling.p, (size_t)n, hipMemcpyDeviceToHost));
     return derive_finish(g, h_flags, e0, e1);

@@ -84,23 +84,23 @@ static int32_t small_build_end(rwr_graph *g, SmallBuild &b, hipEvent_t e0, hipEv
 int32_t graph_derive_small(rwr_graph *g, bool first)
 {
     hipStream_t s = g->stream;
-    double bt_t = bt_now();
+    Stamps stamp = build_stamps.begin();
     hipEvent_t e0 = g->ev_a, e1 = g->ev_b;
     SmallBuild b;
     RWR_TRY(small_build_begin(g, first, b));
-    BT("derive allocs");
+    stamp("derive allocs");
 #ifdef RWR_EXPERIMENTS
     DevBuf<unsigned long long> stamps_d;
-    if (bt_on) { RWR_TRY(stamps_d.alloc(8)); b.a.stamps = stamps_d.p; }
+    if (build_stamps.on()) { RWR_TRY(stamps_d.alloc(8)); b.a.stamps = stamps_d.p; }
 #endif
     RWR_HIP(hipEventRecord(e0, s));
     RWR_TRY(launch_build_small(b.a, s));
     RWR_HIP(hipEventRecord(e1, s));
-    BT("enqueue one-launch build");
+    stamp("enqueue one-launch build");
     RWR_HIP(hipStreamSynchronize(s));                      // the ONE synchronisation of an ego-network-sized build
-    BT("sync (whole build)");
+    stamp("sync (whole build)");
 #ifdef RWR_EXPERIMENTS
-    if (bt_on) {
+    if (build_stamps.on()) {
         unsigned long long hs[8];
         RWR_HIP(hipMemcpy(hs, stamps_d.p, sizeof(hs), hipMemcpyDeviceToHost));
         unsigned long long rp[16];
@@ -148,7 +148,7 @@ int32_t graphs_build_multi(rwr_graph **gs, int32_t count, const rwr_graph_desc *
     std::vector<SmallBuild> builds((size_t)count);
 #ifdef RWR_EXPERIMENTS
     static const bool mt_on = [] { const char *e = getenv("RWR_X_MULTI_TIMING"); return e && atoi(e) != 0; }();
-    double mt0 = bt_now(), mt1 = 0, mt2 = 0, mt3 = 0, mt4 = 0, mt_up = 0, mt_begin = 0;
+    double mt0 = Stamps::now(), mt1 = 0, mt2 = 0, mt3 = 0, mt4 = 0, mt_up = 0, mt_begin = 0;
 #endif
     for (int32_t i = 0; i < count; ++i) {
         rwr_graph *g = gs[i];
@@ -157,32 +157,32 @@ int32_t graphs_build_multi(rwr_graph **gs, int32_t count, const rwr_graph_desc *
         g->stage_dev_ext = d_in.p + in_off[i];
         const rwr_graph_desc &D = descs[i];
 #ifdef RWR_EXPERIMENTS
-        const double u0 = bt_now();
+        const double u0 = Stamps::now();
 #endif
         RWR_TRY(graph_build_upload(g, D.node_id, D.node_type, D.rowptr, D.dst, D.etype, D.w));
         if (!small_build_ok(g)) { set_error("graphs_build_multi: graph %d does not qualify for the one-launch build", caller_index[i]); return RWR_E_INVALID; }
 #ifdef RWR_EXPERIMENTS
-        const double u1 = bt_now();
+        const double u1 = Stamps::now();
         mt_up += u1 - u0;
 #endif
         RWR_TRY(small_build_begin(g, true, builds[i]));
 #ifdef RWR_EXPERIMENTS
-        mt_begin += bt_now() - u1;
+        mt_begin += Stamps::now() - u1;
 #endif
         h_args[i] = builds[i].a;
     }
 #ifdef RWR_EXPERIMENTS
-    mt1 = bt_now();
+    mt1 = Stamps::now();
 #endif
     RWR_HIP(hipMemcpyAsync(d_in.p, pin, in_bytes, hipMemcpyHostToDevice, s));
     RWR_HIP(hipMemcpyAsync(d_args.p, h_args, sizeof(BuildSmallArgs) * (size_t)count, hipMemcpyHostToDevice, s));
     RWR_TRY(launch_build_small_multi(d_args.p, count, s));
 #ifdef RWR_EXPERIMENTS
-    mt2 = bt_now();
+    mt2 = Stamps::now();
 #endif
     RWR_HIP(hipStreamSynchronize(s));
 #ifdef RWR_EXPERIMENTS
-    mt3 = bt_now();
+    mt3 = Stamps::now();
 #endif
     for (int32_t i = 0; i < count; ++i) {
         rwr_graph *g = gs[i];
@@ -199,7 +199,7 @@ int32_t graphs_build_multi(rwr_graph **gs, int32_t count, const rwr_graph_desc *
         }
     }
 #ifdef RWR_EXPERIMENTS
-    mt4 = bt_now();
+    mt4 = Stamps::now();
     if (mt_on)
         fprintf(stderr, "[multi build] %d graphs: prep %.0f us (upload %.0f, begin %.0f), enqueue %.0f, wait %.0f, finish %.0f\n", count, mt1 - mt0,
                 mt_up, mt_begin, mt2 - mt1, mt3 - mt2, mt4 - mt3);

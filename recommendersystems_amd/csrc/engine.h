@@ -1,5 +1,6 @@
 // Device-resident graph and batch workspace (internal).
 #pragma once
+#include <chrono>
 #include <cstdlib>
 #include <new>
 
@@ -181,6 +182,47 @@ namespace rwr {
 
 double now_ms();   // recommend.hip: a steady clock, for the wall times of rwr_stats
 
+// The experiments build's wall-clock stamps of a host function's stages, for tools/*_latency.py: one object per switch at
+// file scope -- Stamps("append", "RWR_APPEND_TIMING"), which reads the variable once, through RWR_TUNE_ENV -- and one copy per
+// call, begin(), which keeps the time of the call's last stamp.  stamp("label") prints the microseconds since then to stderr
+// as "[tag] label  us".  In the shipped library on() is a constant false and every stamp compiles to nothing.
+class Stamps {
+public:
+    Stamps(const char *tag, const char *env_name) : tag_(tag)
+    {
+        const char *e = RWR_TUNE_ENV(env_name);
+        on_ = e && atoi(e) != 0;
+    }
+#ifdef RWR_EXPERIMENTS
+    bool on() const { return on_; }
+#else
+    bool on() const { return false; }
+#endif
+    static double now()                // microseconds of a steady clock
+    {
+        using namespace std::chrono;
+        return duration<double, std::micro>(steady_clock::now().time_since_epoch()).count();
+    }
+    Stamps begin() const
+    {
+        Stamps s = *this;
+        s.t_ = on() ? now() : 0.0;
+        return s;
+    }
+    void operator()(const char *label)
+    {
+        if (!on()) return;
+        const double t = now();
+        fprintf(stderr, "[%s] %-28s %8.1f us\n", tag_, label, t - t_);
+        t_ = t;
+    }
+
+private:
+    const char *tag_;
+    bool on_ = false;
+    double t_ = 0.0;
+};
+
 // scratch buffers of one call are released only after both streams are idle (also on error paths): declared after them
 struct StreamsIdle {
     rwr_graph *g;
@@ -198,8 +240,9 @@ int32_t idle_on_error(hipStream_t s, F &&body)
     return rc;
 }
 
-// two buffers change places: how an edit of the resident lists hands its NEW buffers to the handle (append.hip, remove.hip);
-// the old ones go back to the block cache when the edit's locals go out of scope
+// two buffers change places: how an edit of the resident graph hands a NEW buffer to the handle (edit.h: StagedLinks and
+// StagedNodes group the exchanges of the three edit drivers); the old one goes back to the block cache when the edit's locals
+// go out of scope
 template <typename T>
 void swap_blocks(DevBuf<T> &a, DevBuf<T> &b)
 {

@@ -13,11 +13,13 @@ namespace rwr {
 // workspace is sized; the stream is idle on return.  Booked as prof.rank.
 int32_t filter_rows_build(rwr_graph *g, int32_t cand_type, int64_t pool_count, const int32_t *pool_idx, DevBuf<int32_t> &list,
                           int32_t *nrows, Profile &prof);
-// typed.hip: cand_plan.h's one-workgroup scan of nb block counts in off[0 .. nb], and the whole compaction of the rows that
+// typed.hip: cand_plan.h's one-workgroup scan of nb block counts in off[0 .. nb] (in 32 bits for lists of rows, in 64 for
+// node_remove.hip's chunks of links: the one scan kernel of the library), and the whole compaction of the rows that
 // filter_match(type, bitmap) accepts (bitmap: device, may be nullptr) on g->stream -- count per block into off (device,
 // cand_blocks(n) + 1 cells, the caller's), scan, read-back of the total (one synchronisation), allocation of `list`, ordered
 // scatter.  The scatter is launched, not waited for: off, the bitmap and list must outlive it.
 void launch_cand_scan(int32_t nb, int32_t *off, hipStream_t s);
+void launch_cand_scan(int64_t nb, int64_t *off, hipStream_t s);
 int32_t cand_compact(rwr_graph *g, int32_t type, const uint32_t *bitmap, int32_t *off, DevBuf<int32_t> &list, int32_t *nrows);
 
 }  // namespace rwr

@@ -4,27 +4,17 @@
 // buffers, renumber every surviving target, compact the node arrays and the two ITEM orders, and hand the new row pointers
 // back.  The handle takes the buffers when all of it is done, and build.hip's re-derive (the incremental rebuild with nothing
 // to patch) rebuilds the walk's data from them -- the same kernels in the same order as rwr_graph_create, hence the same bits.
-#include "engine.h"
+#include "edit.h"
 #include "filter.h"
 #include "node_append_plan.h"
 #include "node_remove_plan.h"
 
-#include <chrono>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
 namespace rwr {
 
-// the experiments build's wall-clock stamps (RWR_NODE_REMOVE_TIMING=1), as RWR_REMOVE_TIMING in remove.hip:
-// tools/remove_nodes_latency.py
-static double nt_now()
-{
-    using namespace std::chrono;
-    return duration<double, std::micro>(steady_clock::now().time_since_epoch()).count();
-}
-static const bool nt_on = [] { const char *e = RWR_TUNE_ENV("RWR_NODE_REMOVE_TIMING"); return e && atoi(e) != 0; }();
-#define NT(label) do { if (nt_on) { const double t__ = nt_now(); fprintf(stderr, "[remove_nodes] %-28s %8.1f us\n", label, t__ - nt_t); nt_t = t__; } } while (0)
+static const Stamps node_remove_stamps("remove_nodes", "RWR_NODE_REMOVE_TIMING");   // (engine.h; tools/remove_nodes_latency.py)
 
 // what every kernel over the links reads besides the links
 struct NrmTables {
@@ -65,34 +55,7 @@ __global__ __launch_bounds__(NRM_THREADS) void k_nrm_count(NrmTables T, const in
     }
 }
 
-// 2. scan: one workgroup, off[0 .. nb) from counts to exclusive offsets in place, off[nb] = their sum.  k_cand_scan (typed.hip)
-// in 64 bits: a graph has up to 2^32-2 links.
-__global__ __launch_bounds__(NRM_THREADS) void k_nrm_scan(int64_t nb, int64_t *__restrict__ off)
-{
-    __shared__ int64_t wsum[NRM_WAVES];
-    __shared__ int64_t carry_s;
-    const int tid = threadIdx.x, lane = tid & (NRM_WAVE - 1), wv = tid / NRM_WAVE;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t b0 = 0; b0 < nb; b0 += NRM_THREADS) {
-        const int64_t b = b0 + tid;
-        const int64_t c = b < nb ? off[b] : 0;
-        int64_t inc = c;                                             // inclusive scan inside the wave
-        for (int o = 1; o < NRM_WAVE; o <<= 1) {
-            const int64_t v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
-        }
-        if (lane == NRM_WAVE - 1) wsum[wv] = inc;
-        __syncthreads();
-        int64_t base = carry_s;
-        for (int q = 0; q < wv; ++q) base += wsum[q];
-        if (b < nb) off[b] = base + inc - c;
-        __syncthreads();                                             // (every thread has read carry_s)
-        if (tid == NRM_THREADS - 1) carry_s = base + inc;
-        __syncthreads();
-    }
-    if (tid == 0) off[nb] = carry_s;
-}
+// 2. scan: the chunks' counts to exclusive offsets in place, off[nchunks] = their sum -- launch_cand_scan (typed.hip) in 64 bits.
 
 // 3. scatter.  The workgroup recomputes the predicate trip by trip and ranks its kept links stably: the element of trip t, wave
 // wv, lane l stands behind the kept elements of the earlier trips (base), of the lower waves of its trip (wc) and of the lower
@@ -222,7 +185,7 @@ int32_t graph_remove_nodes(rwr_graph *g, int32_t count, const int32_t *node_inde
     const int32_t n = g->n;
     hipStream_t s = g->stream;
     *swapped = false;
-    double nt_t = nt_on ? nt_now() : 0.0;
+    Stamps stamp = node_remove_stamps.begin();
     NodeRemovePlan plan = node_remove_plan(n, g->h_rowptr.data(), g->h_is_item.data(), count, node_index);
     if (plan.verdict == NODE_REMOVE_BAD_RANGE) {
         set_error("rwr_graph_remove_nodes: node_index[%d] = %d is outside [0, %d)", plan.bad_q, node_index[plan.bad_q], n);
@@ -253,36 +216,26 @@ int32_t graph_remove_nodes(rwr_graph *g, int32_t count, const int32_t *node_inde
     const int64_t nchunks = nrm_chunks(m_old), ni = (int64_t)plan.iv_lo.size();
     const int32_t lb = nrm_list_blocks(ni_old);
     std::vector<int64_t> h_rp_new((size_t)n_new + 1);
-    NT("plan (host)");
+    stamp("plan (host)");
     // ---- phase 1: every buffer exists before anything is launched (a length of 0 is a block of one element, as in the build)
-    DevBuf<int64_t> rp_n, d_ivlo, d_ivhi, d_off, nid_n, inp_n, d_ends, d_link;
-    DevBuf<int32_t> dst_n, d_newidx, ro_n, rox_n, irows_n, iord_n, d_loff;
-    DevBuf<uint8_t> et_n, d_bits, nty_n, dang_n;
-    DevBuf<double> w_n, wn_n, wsrc_n;
+    DevBuf<int64_t> rp_n, d_ivlo, d_ivhi, d_off, d_ends, d_link;
+    DevBuf<int32_t> d_newidx, d_loff;
+    DevBuf<uint8_t> d_bits;
+    StagedLinks ln;
+    StagedNodes nd;
     RWR_TRY(rp_n.alloc((size_t)n_new + 1));
     RWR_TRY(d_ivlo.alloc((size_t)ni));
     RWR_TRY(d_ivhi.alloc((size_t)ni));
     RWR_TRY(d_off.alloc((size_t)nchunks + 1));
     RWR_TRY(d_bits.alloc(plan.bits.size()));
     RWR_TRY(d_newidx.alloc((size_t)n + 1));
-    RWR_TRY(dst_n.alloc((size_t)m_cap));
-    RWR_TRY(et_n.alloc((size_t)m_cap));
-    RWR_TRY(w_n.alloc((size_t)m_cap));
-    RWR_TRY(wn_n.alloc((size_t)m_cap));                         // (not copied: the re-derive writes all of it)
+    RWR_TRY(ln.alloc((size_t)m_cap));
     if (new_link_index_out) RWR_TRY(d_link.alloc((size_t)m_old));
-    // ... the node SoA, the two ITEM orders, and every n-sized array the re-derive fills whole (§3.13's table)
-    RWR_TRY(nid_n.alloc((size_t)n_new));
-    RWR_TRY(nty_n.alloc((size_t)n_new));
-    RWR_TRY(dang_n.alloc((size_t)n_new));
-    RWR_TRY(wsrc_n.alloc((size_t)n_new));
-    RWR_TRY(inp_n.alloc((size_t)n_new + 1));
-    RWR_TRY(ro_n.alloc((size_t)n_new));
-    RWR_TRY(rox_n.alloc((size_t)n_new));
-    RWR_TRY(irows_n.alloc((size_t)ni_new));
-    RWR_TRY(iord_n.alloc((size_t)ni_new));
+    // ... the node-sized arrays and the two ITEM orders (§3.13's table)
+    RWR_TRY(nd.alloc((size_t)n_new, (size_t)ni_new, /*with_item_lists=*/true));
     RWR_TRY(d_loff.alloc((size_t)lb + 1));
     RWR_TRY(d_ends.alloc(2));
-    NT("allocate new buffers");
+    stamp("allocate new buffers");
     int64_t h_ends[2] = {0, 0};
     // (a failure from here to the swap waits for the stream before it returns: the copies read the plan's vectors and the kernels
     //  write this function's buffers, all of which go away on return -- and the handle, untouched, stays usable)
@@ -295,15 +248,15 @@ int32_t graph_remove_nodes(rwr_graph *g, int32_t count, const int32_t *node_inde
         }
         const NrmTables T{n, m_old, ni, d_ivlo.p, d_ivhi.p, d_bits.p};
         hipLaunchKernelGGL(k_nrm_count, dim3((unsigned)nchunks), dim3(NRM_THREADS), 0, s, T, g->dst.p, d_off.p);
-        hipLaunchKernelGGL(k_nrm_scan, dim3(1), dim3(NRM_THREADS), 0, s, nchunks, d_off.p);
+        launch_cand_scan(nchunks, d_off.p, s);
         hipLaunchKernelGGL(k_nrm_scatter, dim3((unsigned)nchunks), dim3(NRM_THREADS), 0, s, T, d_newidx.p, g->rowptr.p, g->dst.p,
-                           g->etype.p, g->w_raw.p, d_off.p, m_cap, dst_n.p, et_n.p, w_n.p, rp_n.p,
+                           g->etype.p, g->w_raw.p, d_off.p, m_cap, ln.dst.p, ln.etype.p, ln.w_raw.p, rp_n.p,
                            new_link_index_out ? d_link.p : (int64_t *)nullptr);
         hipLaunchKernelGGL(k_nrm_nodes, dim3(cdiv((size_t)n, 256)), dim3(256), 0, s, n, d_newidx.p, g->node_id.p, g->node_type.p,
-                           nid_n.p, nty_n.p);
+                           nd.node_id.p, nd.node_type.p);
         if (lb > 0) {
             const int32_t *lists[2] = {g->item_rows.p, g->item_order.p};
-            int32_t *outs[2] = {irows_n.p, iord_n.p};
+            int32_t *outs[2] = {nd.item_rows.p, nd.item_order.p};
             for (int a = 0; a < 2; ++a) {                            // (one offset table: the stream runs them in turn)
                 hipLaunchKernelGGL(k_nrm_list_count, dim3((unsigned)lb), dim3(NRM_THREADS), 0, s, n, ni_old, lists[a], d_bits.p, d_loff.p);
                 launch_cand_scan(lb, d_loff.p, s);
@@ -312,7 +265,7 @@ int32_t graph_remove_nodes(rwr_graph *g, int32_t count, const int32_t *node_inde
             }
         }
         if (ni_new > 0) {
-            hipLaunchKernelGGL(k_nrm_id_ends, dim3(1), dim3(NRM_WAVE), 0, s, n_new, ni_new, iord_n.p, nid_n.p, d_ends.p);
+            hipLaunchKernelGGL(k_nrm_id_ends, dim3(1), dim3(NRM_WAVE), 0, s, n_new, ni_new, nd.item_order.p, nd.node_id.p, d_ends.p);
             RWR_HIP(hipMemcpyAsync(h_ends, d_ends.p, sizeof(h_ends), hipMemcpyDeviceToHost, s));
         }
         RWR_HIP(hipGetLastError());
@@ -327,23 +280,12 @@ int32_t graph_remove_nodes(rwr_graph *g, int32_t count, const int32_t *node_inde
         set_error("rwr_graph_remove_nodes: the compaction left %lld links of at most %lld", (long long)m_new, (long long)m_cap);
         return RWR_E_HIP;
     }
-    NT("upload + compaction kernels");
+    stamp("upload + compaction kernels");
     // ---- phase 2: the handle takes the shortened lists and the smaller node arrays
     *swapped = true;
     swap_blocks(g->rowptr, rp_n);
-    swap_blocks(g->dst, dst_n);
-    swap_blocks(g->etype, et_n);
-    swap_blocks(g->w_raw, w_n);
-    swap_blocks(g->w_norm_raw, wn_n);
-    swap_blocks(g->node_id, nid_n);
-    swap_blocks(g->node_type, nty_n);
-    swap_blocks(g->dangling, dang_n);
-    swap_blocks(g->w_src, wsrc_n);
-    swap_blocks(g->in_ptr, inp_n);
-    swap_blocks(g->row_order, ro_n);
-    swap_blocks(g->row_order_x, rox_n);
-    swap_blocks(g->item_rows, irows_n);
-    swap_blocks(g->item_order, iord_n);
+    ln.take(g);
+    nd.take(g);
     g->h_rowptr.swap(h_rp_new);                                 // (exchanges: nothing on the host can fail here)
     g->h_is_item.swap(plan.is_item_new);
     g->n = n_new;
@@ -358,26 +300,16 @@ int32_t graph_remove_nodes(rwr_graph *g, int32_t count, const int32_t *node_inde
     g->id_key_lo_known = 1;
     // (g->staged stays as it is: a staged handle stays staged, and one that left the one-launch build does not go back when n or
     //  the link count drop below its limits again; the general derive gives the same bits)
-    // Nothing cached for the old node set survives.  The candidate lists: their validity test is the node count alone
-    // (cand_plan.h), and a later rwr_graph_append_nodes can bring n back to a cached value over other rows.  The list a
-    // single-seed call left in pinned memory, and a row-partitioned run (the re-derive ends it; its slab and seeds go too, so
-    // that only rwr_part_begin restarts it), as in graph_append.
-    for (int e = 0; e < CAND_CACHE; ++e) {
-        g->cand_entry[e] = CandEntry{};
-        g->cand_rows[e].release();
-    }
-    g->sm_pin_count = -1;
-    g->part_lo = g->part_hi = g->part_K = g->part_steps = 0;
-    g->part_seeds.clear();
-    NT("swap + host state");
+    forget_node_set(g, /*cand_lists=*/true);                    // (the one edit after which the same n can stand for other rows)
+    stamp("swap + host state");
     const int32_t rc = graph_update_links(g, 0, nullptr, nullptr, nullptr);   // (count 0: the re-derive alone, build.hip)
-    NT("re-derive");
+    stamp("re-derive");
     if (rc != RWR_OK) return rc;
     if (new_link_index_out && m_old > 0)
         RWR_HIP(hipMemcpy(new_link_index_out, d_link.p, sizeof(int64_t) * (size_t)m_old, hipMemcpyDeviceToHost));
     if (new_node_index_out) memcpy(new_node_index_out, plan.new_index.data(), sizeof(int32_t) * (size_t)n);
     if (links_removed_out) *links_removed_out = m_old - m_new;
-    NT("outputs");
+    stamp("outputs");
     return RWR_OK;
 }
 

@@ -2,26 +2,17 @@
 // removed positions; the kernels here compact the resident raw lists around them into NEW buffers, the handle takes them, and
 // build.hip's re-derive (the incremental rebuild with nothing to patch) rebuilds the walk's data from them -- the same kernels
 // in the same order as rwr_graph_create, hence the same bits.  The mirror image of append.hip's merge.
-#include "engine.h"
+#include "edit.h"
 #include "remove_plan.h"
 #include "seg_copy.h"
 
-#include <chrono>
-#include <cstdio>
 #include <vector>
 
 namespace rwr {
 
 constexpr int RM_THREADS = SEG_THREADS;
 
-// the experiments build's wall-clock stamps (RWR_REMOVE_TIMING=1), as RWR_APPEND_TIMING in append.hip: tools/remove_latency.py
-static double rt_now()
-{
-    using namespace std::chrono;
-    return duration<double, std::micro>(steady_clock::now().time_since_epoch()).count();
-}
-static const bool rt_on = [] { const char *e = RWR_TUNE_ENV("RWR_REMOVE_TIMING"); return e && atoi(e) != 0; }();
-#define RT(label) do { if (rt_on) { const double t__ = rt_now(); fprintf(stderr, "[remove] %-28s %8.1f us\n", label, t__ - rt_t); rt_t = t__; } } while (0)
+static const Stamps remove_stamps("remove", "RWR_REMOVE_TIMING");   // (engine.h; tools/remove_latency.py)
 
 // rowptr_new[i] = rowptr_old[i] - (removed positions in front of it), i in [0, n]: one bisection over r per row pointer
 __global__ __launch_bounds__(256) void k_remove_rowptr(int32_t n, int64_t nr, const int64_t *__restrict__ r,
@@ -80,7 +71,7 @@ int32_t graph_remove(rwr_graph *g, int64_t count, const int64_t *link_index, boo
     const int32_t n = g->n;
     hipStream_t s = g->stream;
     *swapped = false;
-    double rt_t = rt_on ? rt_now() : 0.0;
+    Stamps stamp = remove_stamps.begin();
     RemovePlan plan = remove_plan(n, g->h_rowptr.data(), count, link_index);
     if (plan.verdict == REMOVE_BAD_RANGE) {
         set_error("rwr_graph_remove_links: link_index[%lld] = %lld is outside [0, %lld)", (long long)plan.bad_q,
@@ -97,47 +88,39 @@ int32_t graph_remove(rwr_graph *g, int64_t count, const int64_t *link_index, boo
         return graph_update_links(g, 0, nullptr, nullptr, nullptr);
     }
     const int64_t m_old = plan.m_old, m_new = plan.m_new;       // (count > 0 passed the range check: m_old > 0)
-    RT("plan (host)");
+    stamp("plan (host)");
     // ---- phase 1: every buffer exists before anything is launched (a length of 0 is a block of one element, as in the build)
     DevBuf<int64_t> rp_n, d_r;
-    DevBuf<int32_t> dst_n;
-    DevBuf<uint8_t> et_n;
-    DevBuf<double> w_n, wn_n;
+    StagedLinks ln;
     RWR_TRY(rp_n.alloc((size_t)n + 1));
     RWR_TRY(d_r.alloc((size_t)count));
-    RWR_TRY(dst_n.alloc((size_t)m_new));
-    RWR_TRY(et_n.alloc((size_t)m_new));
-    RWR_TRY(w_n.alloc((size_t)m_new));
-    RWR_TRY(wn_n.alloc((size_t)m_new));                         // (not copied: the re-derive writes all of it)
-    RT("allocate new buffers");
+    RWR_TRY(ln.alloc((size_t)m_new));
+    stamp("allocate new buffers");
     // (a failure from here to the swap waits for the stream before it returns: the copy reads the plan's vector and the kernels
     //  write this function's buffers, all of which go away on return -- and the handle, untouched, stays usable)
     auto compact = [&]() -> int32_t {
         RWR_HIP(hipMemcpyAsync(d_r.p, plan.r.data(), sizeof(int64_t) * (size_t)count, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_remove_rowptr, dim3(cdiv((size_t)n + 1, 256)), dim3(256), 0, s, n, count, d_r.p, g->rowptr.p, rp_n.p);
         hipLaunchKernelGGL(k_remove_compact, dim3(cdiv((size_t)m_old, (size_t)RM_CHUNK)), dim3(RM_THREADS), 0, s, m_old, count,
-                           d_r.p, g->dst.p, g->etype.p, g->w_raw.p, dst_n.p, et_n.p, w_n.p);
+                           d_r.p, g->dst.p, g->etype.p, g->w_raw.p, ln.dst.p, ln.etype.p, ln.w_raw.p);
         RWR_HIP(hipGetLastError());
         RWR_HIP(hipStreamSynchronize(s));
         return RWR_OK;
     };
     RWR_TRY(idle_on_error(s, compact));
-    RT("upload + compaction kernels");
+    stamp("upload + compaction kernels");
     // ---- phase 2: the handle takes the shortened lists
     *swapped = true;
     swap_blocks(g->rowptr, rp_n);
-    swap_blocks(g->dst, dst_n);
-    swap_blocks(g->etype, et_n);
-    swap_blocks(g->w_raw, w_n);
-    swap_blocks(g->w_norm_raw, wn_n);
+    ln.take(g);
     g->h_rowptr.swap(plan.rowptr_new);
     g->nnz_raw = m_new;
     g->stats.nnz_raw = m_new;
     // (g->staged stays as it is: a handle that left the one-launch build does not go back when the link count drops below
     //  ONE_LAUNCH_MAX_M again; the general derive gives the same bits)
-    RT("swap + host row pointers");
+    stamp("swap + host row pointers");
     const int32_t rc = graph_update_links(g, 0, nullptr, nullptr, nullptr);   // (count 0: the re-derive alone, build.hip)
-    RT("re-derive");
+    stamp("re-derive");
     return rc;
 }
 

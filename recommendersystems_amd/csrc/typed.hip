@@ -28,6 +28,7 @@
 #include "filter.h"
 #include "group_cap.h"
 #include "long_list.h"
+#include "node_remove_plan.h"   // (nrm_wave_count, nrm_rank_in_chunk: a match's position inside its workgroup)
 
 namespace rwr {
 
@@ -42,7 +43,7 @@ __device__ __forceinline__ bool cand_match(int32_t n, const uint8_t *__restrict_
     const int32_t i = cand_block_lo(b) + (int32_t)threadIdx.x;
     const bool m = i < cand_block_hi(b, n) && filter_match(node_type, t, bitmap, i);
     *bal = __ballot(m);
-    if ((threadIdx.x & (WAVE - 1)) == 0) wc[threadIdx.x / WAVE] = __popcll(*bal);
+    if ((threadIdx.x & (WAVE - 1)) == 0) wc[threadIdx.x / WAVE] = nrm_wave_count(*bal);
     __syncthreads();
     return m;
 }
@@ -60,25 +61,28 @@ __global__ __launch_bounds__(CAND_BLOCK) void k_cand_count(int32_t n, const uint
     }
 }
 
-// one workgroup: off[0 .. nb) from counts to exclusive offsets in place, off[nb] = their sum
-__global__ __launch_bounds__(CAND_SCAN_CHUNK) void k_cand_scan(int32_t nb, int32_t *__restrict__ off)
+// THE workgroup scan of the library's compactions: one workgroup, off[0 .. nb) from counts to exclusive offsets in place,
+// off[nb] = their sum.  T = int32_t for lists of rows (here, group_cap.hip, node_remove.hip's ITEM orders), int64_t for the
+// link chunks of node_remove.hip: a graph has up to 2^32-2 links.
+template <typename T>
+__global__ __launch_bounds__(CAND_SCAN_CHUNK) void k_cand_scan(T nb, T *__restrict__ off)
 {
-    __shared__ int32_t wsum[CAND_SCAN_CHUNK / WAVE];
-    __shared__ int32_t carry_s;
+    __shared__ T wsum[CAND_SCAN_CHUNK / WAVE];
+    __shared__ T carry_s;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
     if (tid == 0) carry_s = 0;
     __syncthreads();
-    for (int32_t c0 = 0; c0 < nb; c0 += CAND_SCAN_CHUNK) {
-        const int32_t b = c0 + tid;
-        const int32_t cnt = b < nb ? off[b] : 0;
-        int32_t inc = cnt;                                       // inclusive scan inside the wave
+    for (T c0 = 0; c0 < nb; c0 += CAND_SCAN_CHUNK) {
+        const T b = c0 + tid;
+        const T cnt = b < nb ? off[b] : 0;
+        T inc = cnt;                                             // inclusive scan inside the wave
         for (int o = 1; o < WAVE; o <<= 1) {
-            const int32_t v = __shfl_up(inc, o);
+            const T v = __shfl_up(inc, o);
             if (lane >= o) inc += v;
         }
         if (lane == WAVE - 1) wsum[wv] = inc;
         __syncthreads();
-        int32_t base = carry_s;
+        T base = carry_s;
         for (int q = 0; q < wv; ++q) base += wsum[q];
         if (b < nb) off[b] = base + inc - cnt;
         __syncthreads();                                         // (every thread has read carry_s)
@@ -95,17 +99,18 @@ __global__ __launch_bounds__(CAND_BLOCK) void k_cand_scatter(int32_t n, const ui
     __shared__ int32_t wc[CAND_BLOCK / WAVE];
     unsigned long long bal;
     if (!cand_match(n, node_type, t, bitmap, wc, &bal)) return;
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    int32_t pos = off[blockIdx.x];
-    for (int q = 0; q < wv; ++q) pos += wc[q];
-    pos += __popcll(bal & ((1ull << lane) - 1ull));
+    const int32_t pos = off[blockIdx.x] + nrm_rank_in_chunk(0, wc, threadIdx.x / WAVE, bal, threadIdx.x & (WAVE - 1));
     if (pos >= 0 && pos < total) rows[pos] = cand_block_lo(blockIdx.x) + (int32_t)threadIdx.x;
 }
 
-// ... for group_cap.hip's key and segment-head lists, which are compacted the same way
+// ... for every other compaction as well (filter.h)
 void launch_cand_scan(int32_t nb, int32_t *off, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_cand_scan, dim3(1), dim3(CAND_SCAN_CHUNK), 0, s, nb, off);
+    hipLaunchKernelGGL(k_cand_scan<int32_t>, dim3(1), dim3(CAND_SCAN_CHUNK), 0, s, nb, off);
+}
+void launch_cand_scan(int64_t nb, int64_t *off, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_cand_scan<int64_t>, dim3(1), dim3(CAND_SCAN_CHUNK), 0, s, nb, off);
 }
 
 int32_t cand_compact(rwr_graph *g, int32_t type, const uint32_t *bitmap, int32_t *off, DevBuf<int32_t> &list, int32_t *nrows)

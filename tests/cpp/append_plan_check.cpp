@@ -1,6 +1,8 @@
 // Host-side check of the append plan (recommendersystems_amd/csrc/append_plan.h), built against the header alone by
 // tests/test_append_plan.py: the plan of a few hundred small cases against a brute-force list-of-lists append
-// (edges[src].Add(link), Graph.cs:40), then every validation verdict with the entry it reports.
+// (edges[src].Add(link), Graph.cs:40), then every validation verdict with the entry it reports.  Every case also goes through
+// the kernels' own arithmetic (the ap_* functions of the header, which append.hip's k_append_rowptr and k_append_merge call):
+// the new row pointers, and every chunk of old positions through BOTH paths of the merge, whichever the kernel would pick.
 // Prints every failure and exits non-zero if there is one.
 #include "append_plan.h"
 
@@ -23,9 +25,68 @@ static void fail(const std::string &what)
 struct Tag { int64_t a, b; };
 static bool same(const Tag &x, const Tag &y) { return x.a == y.a && x.b == y.b; }
 
-// deg[i] links per row, the links (src[q], dst[q]) appended: checks every output of the plan against the lists
+// What the device does with the plan's tables.  rowptr_old has n_old + 1 entries (exactly: a read past them is the
+// sanitizer's); the rows [n_old, n) are the call's new nodes.  want_rowptr: the brute-force append's row pointers.
+static void check_kernel_arithmetic(const std::string &name, const AppendPlan &p, const std::vector<int64_t> &rowptr_old,
+                                    int32_t n, const std::vector<int64_t> &want_rowptr)
+{
+    const int32_t n_old = (int32_t)rowptr_old.size() - 1;
+    const int nb = (int)p.srcs.size();
+    const int64_t m = p.m_old;
+    // k_append_rowptr: one call per row pointer
+    for (int64_t i = 0; i <= n; ++i)
+        if (ap_rowptr_new(p.srcs.data(), p.cum.data(), nb, rowptr_old.data(), n_old, i) != want_rowptr[(size_t)i]) {
+            fail(name + ": ap_rowptr_new(" + std::to_string(i) + ")");
+            break;
+        }
+    // k_append_merge: every chunk through the dense and the sparse path
+    std::vector<int64_t> dense((size_t)m, -1), sparse((size_t)m, -1);
+    std::vector<int> written((size_t)p.m_new, 0);
+    for (int64_t c0 = 0; c0 < m; c0 += AP_CHUNK) {
+        const int64_t c1 = c0 + AP_CHUNK < m ? c0 + AP_CHUNK : m;
+        const ApSlice s = ap_chunk_slice(p.brk.data(), nb, c0, c1);
+        if (s.j < 0 || s.jend < s.j || s.jend > nb) { fail(name + ": chunk slice at " + std::to_string(c0)); return; }
+        for (int k = 0; k < nb; ++k)
+            if ((p.brk[(size_t)k] > c0 && p.brk[(size_t)k] <= c1 - 1) != (k >= s.j && k < s.jend)) {
+                fail(name + ": breakpoint " + std::to_string(k) + " and the slice of chunk " + std::to_string(c0));
+                break;
+            }
+        if (ap_chunk_dense(s) != (s.jend - s.j > 32)) fail(name + ": sparse / dense choice at " + std::to_string(c0));
+        for (int64_t e = c0; e < c1; ++e) dense[(size_t)e] = ap_dense_dest(p.brk.data(), p.cum.data(), s, e);
+        int j = s.j, segments = 0;
+        for (int64_t a = c0; a < c1;) {
+            const ApSeg g = ap_segment(p.brk.data(), p.cum.data(), nb, c1, a, j);
+            if (g.a != a || g.b <= g.a || g.b > c1 || g.next < j || g.next > nb) {   // (never an empty segment: the walk ends)
+                fail(name + ": segment at " + std::to_string(a) + " of chunk " + std::to_string(c0));
+                return;
+            }
+            for (int64_t e = g.a; e < g.b; ++e) {
+                if (sparse[(size_t)e] != -1) fail(name + ": the sparse path takes old position " + std::to_string(e) + " twice");
+                sparse[(size_t)e] = e + g.sh;
+            }
+            a = g.b;
+            j = g.next;
+            ++segments;
+        }
+        if (segments > s.jend - s.j + 1) fail(name + ": more segments than breakpoints + 1 in chunk " + std::to_string(c0));
+    }
+    for (int64_t e = 0; e < m; ++e) {
+        const int64_t want = e + p.shift(e);
+        if (dense[(size_t)e] != want) { fail(name + ": dense path, old position " + std::to_string(e)); break; }
+        if (sparse[(size_t)e] != want) { fail(name + ": sparse path, old position " + std::to_string(e)); break; }
+        if (want < 0 || want >= p.m_new || written[(size_t)want]++) { fail(name + ": destination of " + std::to_string(e) + " taken"); break; }
+    }
+    for (size_t k = 0; k < p.pos.size(); ++k)
+        if (p.pos[k] < 0 || p.pos[k] >= p.m_new || written[(size_t)p.pos[k]]++) {
+            fail(name + ": an old link is merged onto the place of appended link " + std::to_string(k));
+            break;
+        }
+}
+
+// deg[i] links per row, the links (src[q], dst[q]) appended: checks every output of the plan against the lists.  The last
+// n_new_rows rows (without links) are new nodes of the call: the device's old row pointers end before them.
 static void check_case(const std::string &name, const std::vector<int64_t> &deg, const std::vector<int32_t> &src,
-                       const std::vector<int32_t> &dst)
+                       const std::vector<int32_t> &dst, int32_t n_new_rows = 0)
 {
     const int32_t n = (int32_t)deg.size();
     const int64_t count = (int64_t)src.size();
@@ -52,6 +113,7 @@ static void check_case(const std::string &name, const std::vector<int64_t> &deg,
         fail(name + ": table lengths");
         return;
     }
+    check_kernel_arithmetic(name, p, std::vector<int64_t>(rowptr.begin(), rowptr.end() - n_new_rows), n, rowptr_new);
     const size_t D = p.srcs.size();
     if (p.cnt.size() != D || p.brk.size() != D || p.cum.size() != D) { fail(name + ": distinct-source table lengths"); return; }
     if ((int64_t)D > count) fail(name + ": more table entries than links");
@@ -136,6 +198,77 @@ static void named_cases()
     check_case("row 0 and row n-1", {0, 2, 0}, {2, 0, 2, 0}, {1, 1, 1, 1});
     check_case("one node", {3}, {0, 0}, {0, 0});
     cases_checked += 11;
+}
+
+// rows whose ends are the given old flat positions (non-decreasing; the last one is m_old)
+static std::vector<int64_t> rows_ending_at(const std::vector<int64_t> &ends)
+{
+    std::vector<int64_t> deg(ends.size());
+    for (size_t i = 0; i < ends.size(); ++i) deg[i] = ends[i] - (i ? ends[i - 1] : 0);
+    return deg;
+}
+static std::vector<int32_t> zeros(size_t k) { return std::vector<int32_t>(k, 0); }
+
+// The edges of the merge kernel's chunks (AP_CHUNK = 8 192 old positions) and of its sparse / dense choice (AP_DENSE_BREAKS =
+// 32).  Appending to row s puts a breakpoint at the row's end, so the cases are written as row ends.
+static void chunk_edge_cases()
+{
+    const int64_t C = AP_CHUNK;
+    // list lengths around one and two chunks; breakpoints at 0 (an empty row 0), in the middle, at m - 1 and at m_old (the last
+    // rows: no old link moves), every row appended to, then each one alone
+    for (const int64_t m : {(int64_t)0, (int64_t)1, C - 1, C, C + 1, 2 * C + 1}) {
+        const std::vector<int64_t> ends = {0, m / 3, m / 3, m > 0 ? m - 1 : 0, m, m};
+        const std::vector<int64_t> deg = rows_ending_at(ends);
+        const std::string name = "m_old " + std::to_string(m);
+        check_case(name + ", every row", deg, {5, 0, 1, 2, 3, 4, 0, 4}, zeros(8));
+        for (int32_t s = 0; s < 6; ++s) check_case(name + ", row " + std::to_string(s), deg, {s, s}, zeros(2));
+        cases_checked += 7;
+    }
+    // a breakpoint exactly at a chunk's c0, at c1 - 1, at c1 (the next chunk's c0) and at m_old
+    {
+        const std::vector<int64_t> deg = rows_ending_at({C - 1, C, 2 * C - 1, 2 * C, 2 * C + 1});
+        check_case("chunk edges, all", deg, {0, 1, 2, 3, 4}, zeros(5));
+        for (int32_t s = 0; s < 5; ++s) check_case("chunk edges, row " + std::to_string(s), deg, {s}, zeros(1));
+        check_case("chunk edges, c1 - 1 and c1", deg, {1, 0, 1}, zeros(3));
+        cases_checked += 7;
+    }
+    // exactly 32 and exactly 33 distinct breakpoints inside one chunk: 33 in chunk 0 (dense) and 32 in chunk 1 (sparse), the
+    // other way round, and 33 of which one sits on c0 and so counts for neither chunk
+    for (int variant = 0; variant < 3; ++variant) {
+        std::vector<int64_t> ends;
+        std::vector<int32_t> src;
+        const int n0 = variant == 1 ? 32 : 33, n1 = variant == 1 ? 33 : 32;
+        for (int k = 0; k < n0; ++k) ends.push_back(100 + 200 * (int64_t)k);
+        for (int k = 0; k < n1; ++k) ends.push_back(C + (variant == 2 ? 0 : 7) + 200 * (int64_t)k);
+        ends.push_back(2 * C + 1);
+        for (size_t i = 0; i + 1 < ends.size(); ++i) src.push_back((int32_t)i);
+        src.push_back(3);
+        check_case("32 / 33 breakpoints, variant " + std::to_string(variant), rows_ending_at(ends), src, zeros(src.size()));
+        ++cases_checked;
+    }
+    // runs of coinciding breakpoints (sources that are neighbouring rows without links): a chunk in which ALL breakpoints
+    // coincide, few enough for the sparse path and too many for it; runs among distinct ones; a run on c0 and one on m_old
+    for (const int run : {3, 32, 33, 40}) {
+        std::vector<int64_t> ends = {500};
+        std::vector<int32_t> src;
+        for (int k = 0; k < run; ++k) { ends.push_back(500); src.push_back((int32_t)k + 1); }
+        ends.push_back(C + 5);
+        check_case("all breakpoints coincide, run " + std::to_string(run), rows_ending_at(ends), src, zeros(src.size()));
+        ends = {10, 10, 10, 700, 700, C, C, C, C + 9, 2 * C + 1, 2 * C + 1, 2 * C + 1};
+        for (int k = 0; k < run; ++k) ends.insert(ends.begin() + 5, 700);
+        src.clear();
+        for (size_t i = 0; i < ends.size(); ++i) src.push_back((int32_t)(ends.size() - 1 - i));
+        check_case("runs among distinct breakpoints, run " + std::to_string(run), rows_ending_at(ends), src, zeros(src.size()));
+        cases_checked += 2;
+    }
+    // new nodes behind the last resident one: links from them, from the last resident row and from row 0
+    for (const int64_t m : {(int64_t)0, C, C + 1}) {
+        const std::vector<int64_t> deg = rows_ending_at({0, m / 2, m, m, m, m});
+        check_case("new nodes, m_old " + std::to_string(m), deg, {5, 3, 2, 0, 4, 5, 1}, {4, 5, 3, 0, 0, 1, 5}, 3);
+        check_case("new nodes without links from them, m_old " + std::to_string(m), deg, {1, 2}, {5, 4}, 3);
+        check_case("new nodes alone, m_old " + std::to_string(m), deg, {}, {}, 3);
+        cases_checked += 3;
+    }
 }
 
 static void random_cases()
@@ -241,6 +374,7 @@ static void verdicts()
 int main()
 {
     named_cases();
+    chunk_edge_cases();
     random_cases();
     wide_cases();
     verdicts();

@@ -102,7 +102,7 @@ static void replay_list(const NodeRemovePlan &p, const std::vector<int32_t> &lis
     }
 }
 
-// k_nrm_count, k_nrm_scan, k_nrm_scatter on the host
+// k_nrm_count, the scan (launch_cand_scan in 64 bits), k_nrm_scatter on the host
 static Out replay(const NodeRemovePlan &p, const std::vector<int64_t> &rowptr, const std::vector<int32_t> &dst,
                   const std::vector<int32_t> &item_rows, const std::vector<int32_t> &item_order, bool backwards)
 {

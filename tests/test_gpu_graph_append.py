@@ -204,6 +204,116 @@ def test_general_path_two_calls():
     G.close()
 
 
+AP_CHUNK = 8192            # append_plan.h: old positions per workgroup of the merge kernel
+AP_DENSE_BREAKS = 32       # ... and the breakpoints in a chunk up to which it takes the sparse path
+
+
+def graph_with_row_ends(seed, ends):
+    """A graph whose row i ends at the old flat position ends[i] (non-decreasing; equal neighbours are rows without links):
+    appending to row i puts a breakpoint of the merge exactly there.  The first half of the rows are users that like items,
+    the second half items with links back; mixed weights, so that a misplaced weight shows in w_norm."""
+    rng = np.random.default_rng(seed)
+    rowptr = np.concatenate([[0], np.asarray(ends, dtype=np.int64)])
+    n, m = rowptr.shape[0] - 1, int(rowptr[-1])
+    n_users = n // 2
+    src = np.repeat(np.arange(n), np.diff(rowptr))
+    dst = np.where(src < n_users, rng.integers(n_users, n, m), rng.integers(0, n_users, m)).astype(np.int32)
+    etype = np.where(rng.random(m) < 0.03, gg.EDGE_UNDEFINED, gg.EDGE_LIKE).astype(np.uint8)
+    w = rng.choice(np.array([1.0, 1.0, 0.5, 2.25, 3.0]), m)
+    node_type = np.array([gg.NODE_USER] * n_users + [gg.NODE_ITEM] * (n - n_users), dtype=np.uint8)
+    node_id = rng.permutation(np.arange(500, 500 + 3 * n, 3, dtype=np.int64))
+    return dict(node_id=node_id, node_type=node_type, rowptr=rowptr, dst=dst, etype=etype, w=w)
+
+
+def links_from(seed, g, sources):
+    """one appended link per entry of sources (rows may repeat), to a node of the other kind, with weights of its own"""
+    rng = np.random.default_rng(seed)
+    n = g["node_id"].shape[0]
+    n_users = n // 2
+    src = np.asarray(sources, dtype=np.int32)
+    dst = np.where(src < n_users, rng.integers(n_users, n, src.shape[0]), rng.integers(0, n_users, src.shape[0])).astype(np.int32)
+    return src, dst, np.full(src.shape[0], gg.EDGE_LIKE, dtype=np.uint8), rng.choice(np.array([1.0, 0.5, 2.25]), src.shape[0])
+
+
+def rows_ending_at(g, end):
+    """the rows of g that end at old position `end`, ascending: the first one holds links, the others are empty"""
+    return (np.flatnonzero(g["rowptr"][1:] == end)).tolist()
+
+
+def breakpoints_inside(g, sources, chunk):
+    """table entries of the merge (one per distinct source) that k_append_merge counts for chunk `chunk`"""
+    m = int(g["rowptr"][-1])
+    c0, c1 = chunk * AP_CHUNK, min((chunk + 1) * AP_CHUNK, m)
+    brk = g["rowptr"][np.unique(sources) + 1]
+    return int(((brk > c0) & (brk <= c1 - 1)).sum())
+
+
+def edge_case_b():
+    """m_old = 8 193: a row that ends exactly at 8 192 -- the second chunk's c0 -- and one that ends at 8 191 = c1 - 1"""
+    g = graph_with_row_ends(72, list(range(24, AP_CHUNK - 1, 24)) + [AP_CHUNK - 1, AP_CHUNK, AP_CHUNK + 1])
+    assert int(g["rowptr"][-1]) == AP_CHUNK + 1
+    return g, rows_ending_at(g, AP_CHUNK) + rows_ending_at(g, AP_CHUNK - 1)
+
+
+def test_chunk_edges():
+    """The merge kernel at the edges of its chunks of 8 192 old positions and of its sparse / dense choice, on graphs whose
+    row ends are placed by construction."""
+    seeds, batch = (0, 5, 100), np.arange(40)
+
+    def run(g, sources, seed):
+        a = links_from(seed, g, sources)
+        G = build(g)
+        pos = G.appendLinks(*a)
+        want, want_pos = patched(g, *a)
+        assert np.array_equal(pos, want_pos)
+        check_against_fresh(G, want, seeds, batch)
+        G.close()
+
+    # (a) m_old = 8 192, one full chunk: an empty row 0 (breakpoint 0: every old link moves) and the last row (breakpoint
+    # m_old: none does)
+    g = graph_with_row_ends(71, [0] + list(range(24, AP_CHUNK, 24)) + [AP_CHUNK])
+    n = g["node_id"].shape[0]
+    assert int(g["rowptr"][-1]) == AP_CHUNK and g["rowptr"][1] == 0
+    run(g, [0, n - 1, 0], 171)
+    # (b)
+    g, sources = edge_case_b()
+    run(g, sources, 172)
+    # (c) m_old = 16 385, three chunks: 33 table entries inside chunk 0 (dense) and 32 inside chunk 1 (sparse), runs of three
+    # neighbouring empty rows among each (coinciding breakpoints), the row that ends at the last chunk's c0 and the last row,
+    # which is the one-element last chunk
+    ends = sorted(list(range(48, 2 * AP_CHUNK, 48)) + [2400] * 3 + [12000] * 3 + [2 * AP_CHUNK, 2 * AP_CHUNK + 1])
+    g = graph_with_row_ends(73, ends)
+    assert int(g["rowptr"][-1]) == 2 * AP_CHUNK + 1
+    sources = []
+    for end in list(range(240, 7201, 240)) + list(range(8400, 15121, 240)) + [2 * AP_CHUNK, 2 * AP_CHUNK + 1]:
+        sources += rows_ending_at(g, end)
+    assert len(rows_ending_at(g, 2400)) == 4 and len(rows_ending_at(g, 12000)) == 4
+    assert breakpoints_inside(g, sources, 0) == AP_DENSE_BREAKS + 1 and breakpoints_inside(g, sources, 1) == AP_DENSE_BREAKS
+    run(g, sources + sources[::7], 173)                   # (some sources twice: their links stay in the order of q)
+
+
+def test_chunk_edges_with_new_nodes():
+    """Sub-case (b) of test_chunk_edges through rwr_graph_append_nodes: three nodes behind the last one, an ITEM among them,
+    with links from and to them beside the links appended at the chunk edge."""
+    g, sources = edge_case_b()
+    n = g["node_id"].shape[0]
+    new_id = np.array([900001, 900002, 900003], dtype=np.int64)
+    new_type = np.array([gg.NODE_USER, gg.NODE_ITEM, gg.NODE_ETC], dtype=np.uint8)
+    a = links_from(174, g, sources + [3])
+    src = np.concatenate([a[0], [n, n + 1, 7, n + 2, n]]).astype(np.int32)
+    dst = np.concatenate([a[1], [n + 1, 2, n + 1, n, n - 1]]).astype(np.int32)
+    et = np.full(src.shape[0], gg.EDGE_LIKE, dtype=np.uint8)
+    w = np.concatenate([a[3], [1.0, 0.5, 2.25, 1.0, 3.0]])
+    G = build(g)
+    first, pos = G.appendNodes(list(zip(new_id.tolist(), new_type.tolist())), src, dst, et, w)
+    ext = dict(g, node_id=np.concatenate([g["node_id"], new_id]), node_type=np.concatenate([g["node_type"], new_type]),
+               rowptr=np.concatenate([g["rowptr"], np.full(3, g["rowptr"][-1], dtype=np.int64)]))
+    want, want_pos = patched(ext, src, dst, et, w)
+    assert first == n and np.array_equal(pos, want_pos)
+    check_against_fresh(G, want, (0, 5, n), np.arange(40))
+    G.close()
+
+
 def _small(uniform=False):
     return gg.random_graph(13, n_users=50, n_items=70, n_likes=260, uniform=uniform, p_undefined=0.0 if uniform else 0.05)
 

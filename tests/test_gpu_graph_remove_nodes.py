@@ -157,6 +157,29 @@ def test_general_path_keeps_most():
     G.close()
 
 
+def test_scan_second_trip():
+    """8 192 x 256 + 1 links are 257 chunks: the scan of the chunks' kept counts takes 256 per trip, so its carry crosses into
+    a second trip, and the last chunk holds one link -- whose target leaves, so that chunk keeps nothing.  4 000 nodes with
+    rows of about 524 links (mixed weights) keep the build short."""
+    n, n_users, m = 4000, 2000, 8192 * 256 + 1
+    rng = np.random.default_rng(23)
+    src = np.repeat(np.arange(n), m // n + (np.arange(n) < m % n))
+    dst = np.where(src < n_users, rng.integers(n_users, n, m), rng.integers(0, n_users, m)).astype(np.int32)
+    g = from_links(np.arange(700, 700 + n), [gg.NODE_USER] * n_users + [gg.NODE_ITEM] * (n - n_users), src, dst,
+                   np.full(m, gg.EDGE_LIKE), rng.choice(np.array([1.0, 1.0, 0.5, 2.25, 3.0]), m))
+    assert int(g["rowptr"][-1]) == m and (m + 8191) // 8192 == 257
+    last_target = int(g["dst"][m - 1])
+    lost = [last_target, n_users + 3]
+    assert last_target not in (0, 17, 1999) and last_target < n_users
+    G = build(g)
+    want, nn, nl = remove(G, g, lost)
+    assert nl[m - 1] == -1 and nl[m - 2] == int(want["rowptr"][-1]) - 1      # (the last chunk keeps nothing)
+    users = nn[np.arange(0, 2000, 50)]
+    users = users[users >= 0]
+    check_fresh(G, want, (0, int(nn[17]), int(nn[1999])), users, users[::4])
+    G.close()
+
+
 def test_crossing_8192_nodes_downwards():
     """8 200 nodes minus 20: the handle, built by the general derive, stays on it, while the fresh handle of 8 180 nodes builds
     in one launch.  All of the snapshot is bitwise."""
